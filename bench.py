@@ -10,7 +10,13 @@ rank decodes its own 256-image slice with no collective on the data path
 (weak scaling).  A barrier + MAX all-reduce of the elapsed time is the only
 cross-rank traffic.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the result line
+  (the headline rate and `ms_per_step`).  --full adds what takes runs of its
+  own: the per-stage HIP-event breakdown and `roofline`, the one-lane figures,
+  the oracle check of the last timed batch, the CPU baseline and the child run
+  at the other hardware-queue setting.  --dump-outputs DIR writes the last
+  timed step's output batch to DIR/output.npy (float32).
   N > 1: either launched by torch.distributed.run (one rank per GPU), or
   started plainly, in which case bench.py spawns the N rank processes itself
   before any GPU call.  The barrier and the MAX-over-ranks reduction of the
@@ -205,6 +211,15 @@ def _args():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline rate does not need: per-stage and roofline "
+                        "figures (profiled steps), the one-lane steps, the oracle check, the CPU "
+                        "baseline, the child run at the other hardware-queue setting, "
+                        "--with-copies")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the output batch of the last timed step to DIR/output.npy "
+                        "(float32; a fixed seeded sample of its elements when it exceeds "
+                        f"{DUMP_MAX_ELEMS} of them)")
     p.add_argument("--batch", type=int, default=BATCH)
     p.add_argument("--distinct", type=int, default=32)
     p.add_argument("--cpu-threads", type=int, default=0,
@@ -260,12 +275,16 @@ def _args():
     p.add_argument("--warmup-mode", choices=["sync", "pipelined"], default="pipelined",
                    help="warmup steps one synchronous batch at a time, or submitted as the timed "
                         "steps are (the device is busy up to the timed region)")
-    p.add_argument("--timed-events", choices=["dominant", "stages", "off"], default="dominant",
+    p.add_argument("--timed-events", choices=["dominant", "stages", "off"], default=None,
                    help="HIP events in the timed steps: around the dominant kernel's stage only "
-                        "(found by an untimed profiled pass first), around every stage, or none "
-                        "(A/B); the per-stage breakdown then comes from as many profiled steps "
-                        "after the timed region")
-    return p.parse_args()
+                        "(found by an untimed profiled pass first; the default with --full), "
+                        "around every stage, or none (the default of a plain run); with --full "
+                        "the per-stage breakdown then comes from as many profiled steps after "
+                        "the timed region")
+    a = p.parse_args()
+    if a.timed_events is None:
+        a.timed_events = "dominant" if a.full else "off"
+    return a
 
 
 def _param_or_none(dec, name: str):
@@ -395,6 +414,33 @@ def _oracle_check(datas, out: torch.Tensor, spec: Output, n_check: int) -> str:
         if not np.array_equal(hyp, ref):
             raise AssertionError(f"timed batch image {i} differs from the oracle")
     return f"{n_check} images of the last timed batch bit-exact vs oracle"
+
+
+# --dump-outputs: at most this many float32 elements (48 MB of the 64 MB allowed)
+DUMP_MAX_ELEMS = 12 * 1024 * 1024
+DUMP_SEED = 20240
+
+
+def _dump_outputs(dirname: str, out: torch.Tensor) -> dict:
+    """Write the batch a caller of the timed path receives (`out`, the output
+    buffer of the last timed step) to `dirname`/output.npy as float32.  A
+    batch of more than DUMP_MAX_ELEMS elements is sampled: the elements at
+    the sorted distinct flat indices drawn by default_rng(DUMP_SEED) (the same
+    indices for the same output shape, so two builds compare element for
+    element)."""
+    os.makedirs(dirname, exist_ok=True)
+    flat = out.detach().cpu().reshape(-1)
+    n = flat.numel()
+    sampled = n > DUMP_MAX_ELEMS
+    if sampled:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_MAX_ELEMS))
+        flat = flat[torch.from_numpy(idx)]
+    arr = flat.to(torch.float32).numpy()
+    if not sampled:
+        arr = arr.reshape(tuple(out.shape))
+    np.save(os.path.join(dirname, "output.npy"), arr)
+    return {"file": "output.npy", "dtype": "float32", "shape": list(arr.shape),
+            "of_elements": n, "sampled": sampled, "seed": DUMP_SEED if sampled else None}
 
 
 def _dry_run(a, rank: int, world: int) -> None:
@@ -579,7 +625,9 @@ def main():
     torch.cuda.synchronize(device)
     elapsed = reduce_max(time.perf_counter() - t0)
     timed_stages = dict(stages)  # the HIP-event times of the timed steps
-    if a.timed_events != "stages":
+    last = outs[(nsub[0] - 1) % len(outs)]  # the last timed step's output batch
+    dumped = _dump_outputs(a.dump_outputs, last) if a.dump_outputs and rank == 0 else None
+    if a.full and a.timed_events != "stages":
         # the per-stage breakdown: as many profiled steps after the timed region
         stages.clear()
         dec.set_profiling(True)
@@ -588,18 +636,20 @@ def main():
 
     # correctness outside the timed region: the last timed batch against
     # the oracle (every distinct image of the slice)
-    last = outs[(nsub[0] - 1) % len(outs)]
-    checked = ("skipped (--debug-mask ablation)" if a.debug_mask else
+    checked = ("not run (plain run; --full compares with the oracle)" if not a.full else
+               "skipped (--debug-mask ablation)" if a.debug_mask else
                _oracle_check(datas, last, spec, min(a.batch, a.distinct, a.oracle_check)))
 
     stages_ms = {k: v / a.steps / 1000.0 for k, v in stages.items()}
     kernels = {k: v for k, v in stages_ms.items() if k not in ("h2d", "d2h_status")}
-    dominant = dom_stage or max(kernels, key=kernels.get)
-    # the dominant kernel's launch time inside the timed region (its own HIP
-    # events on its lane streams); with --timed-events off, from the
-    # profiled steps after it
-    timed_ms = {k: v / a.steps / 1000.0 for k, v in timed_stages.items()}
-    kernel_ms = timed_ms.get(dominant, kernels[dominant])
+    dominant = kernel_ms = None
+    if a.full:
+        dominant = dom_stage or max(kernels, key=kernels.get)
+        # the dominant kernel's launch time inside the timed region (its own HIP
+        # events on its lane streams); with --timed-events off, from the
+        # profiled steps after it
+        timed_ms = {k: v / a.steps / 1000.0 for k, v in timed_stages.items()}
+        kernel_ms = timed_ms.get(dominant, kernels[dominant])
     comp_bytes = float(np.mean(sizes))
     # §8(d): compressed in + RGB224 out (u8: 150,528 B; fp16/bf16: 301,056 B)
     per_image_bytes = comp_bytes + nbytes_out / a.batch
@@ -609,7 +659,7 @@ def main():
     # with the other lanes' kernels, so the per-launch time above is a shared
     # wall time.  One lane, synchronous batches, the same HIP-event stages.
     lanes1 = None
-    if a.lanes1_steps > 0 and not a.debug_mask:
+    if a.full and a.lanes1_steps > 0 and not a.debug_mask:
         dec1 = _lib.Decoder(device.index)
         dec1.set_param("lanes", 1)
         if a.piece_bytes >= 0:
@@ -648,7 +698,7 @@ def main():
         ranks = [mine]
 
     copies = None
-    if a.with_copies and rank == 0:
+    if a.full and a.with_copies and rank == 0:
         host_out = torch.empty_like(out, device="cpu").pin_memory()
         t1 = time.perf_counter()
         nrep = max(5, a.steps // 4)
@@ -659,7 +709,8 @@ def main():
         copies = a.batch * nrep / (time.perf_counter() - t1)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.workload == "pad224":
+    if (a.full and rank == 0 and world == 1 and not a.no_cpu_baseline
+            and a.workload == "pad224"):
         threads = a.cpu_threads or _cpu_cores()["usable"]
         cpu = _cpu_baseline(datas, threads, a.cpu_images, a.cpu_images // 2, a.cpu_runs)
 
@@ -667,10 +718,10 @@ def main():
     # hardware-queue count (4 <-> 16): the record carries both rates
     queues = None
     hwq = dec.get_param("hw_queues")
-    if (rank == 0 and world == 1 and not a.no_queue_compare and not a.debug_mask
+    if (a.full and rank == 0 and world == 1 and not a.no_queue_compare and not a.debug_mask
             and a.workload == "pad224"):
         other = 16 if hwq != 16 else 4
-        cmd = [sys.executable, os.path.abspath(__file__), "--hw-queues", str(other),
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--hw-queues", str(other),
                "--steps", str(a.steps), "--warmup", str(a.warmup), "--batch", str(a.batch),
                "--lanes", str(a.lanes), "--no-cpu-baseline", "--lanes1-steps", "0",
                "--no-queue-compare", "--oracle-check", "8"]
@@ -685,23 +736,23 @@ def main():
                             "oracle_check": c["oracle_check"]}}
 
     traffic = issue = rocprof_ms = None
-    if a.workload == "pad224" and a.lanes in KSTATS and a.batch == BATCH:
+    if a.full and a.workload == "pad224" and a.lanes in KSTATS and a.batch == BATCH:
         rocprof_ms = _rocprof_ms(a.lanes, dominant)
-    if a.workload == "pad224" and a.lanes == 4:  # the configuration the PMC passes ran
+    if a.full and a.workload == "pad224" and a.lanes == 4:  # the configuration the PMC passes ran
         traffic = _pmc(PMC_TRAFFIC, dominant, a.batch)
         issue = _pmc(PMC_ISSUE, dominant, a.batch)
     # `achieved` and `frac` from this run's own HIP-event duration of the
     # dominant kernel (events recorded on the lane streams the kernel runs
-    # on), so a kernel change shows in the headline fields at once.  The
+    # on), so a kernel change shows in the roofline fields at once.  The
     # committed rocprofv3 summary of this configuration rides along under
     # `profile`, with whether it was taken on this very library build.
-    achieved = launch_bytes / (kernel_ms / 1e3) / 1e9
-    prof_match = _profile_build_match()
+    achieved = launch_bytes / (kernel_ms / 1e3) / 1e9 if a.full else None
+    prof_match = _profile_build_match() if a.full else None
     # (the PMC traffic per launch over this run's launch duration: the same
     # time base as `achieved` / `frac`)
     hbm_frac = (traffic["traffic_bytes"] / (kernel_ms / 1e3) / 1e9 / HBM_PEAK_GBS
                 if traffic else None)
-    busy = _kernel_busy_ms(a.lanes, dominant) if a.workload == "pad224" else None
+    busy = _kernel_busy_ms(a.lanes, dominant) if a.full and a.workload == "pad224" else None
     if rank == 0:
         value = world * a.batch * a.steps / elapsed
         rec = {
@@ -779,9 +830,10 @@ def main():
                 "limiter_time_base": "kernel_ms",
                 "pipeline_GBps": round(launch_bytes / (elapsed / a.steps) / 1e9, 3),
                 "lanes1": lanes1,
-            },
+            } if a.full else None,
             "stages_ms": {k: round(v, 4) for k, v in stages_ms.items()},
-            "stages_source": ("HIP events of every stage in the timed steps"
+            "stages_source": None if not stages_ms else
+                             ("HIP events of every stage in the timed steps"
                               if a.timed_events == "stages" else
                               "HIP events of every stage in as many profiled steps after the "
                               "timed region (" + ("the timed steps bracket the dominant kernel "
@@ -794,6 +846,13 @@ def main():
             "ranks": ranks,
             "cpu_baseline": cpu,
         }
+        if not a.full:
+            # a plain run carries the headline and its configuration only
+            del rec["roofline"], rec["cpu_baseline"]
+            if not stages_ms:  # (present with an explicit --timed-events)
+                del rec["stages_ms"], rec["stages_source"]
+        if dumped is not None:
+            rec["dumped_outputs"] = dumped
         if queues is not None:
             queues["this_run"]["value"] = rec["value"]
             queues["other_over_this"] = round(queues["other"]["value"] / rec["value"], 4)

@@ -48,7 +48,7 @@ def test_configs0_dataloading_1k_files_pixels(oracle, tmp_path):
 
 
 def test_configs2_eight_rank_launch_rehearsed(tmp_path):
-    rec = _run(["bench.py", "--gpus", "8", "--batch", "256", "--rehearse-one-gpu", "--steps", "3",
+    rec = _run(["bench.py", "--full", "--gpus", "8", "--batch", "256", "--rehearse-one-gpu", "--steps", "3",
                 "--warmup", "1", "--lanes1-steps", "0", "--no-cpu-baseline", "--bind", "split"], 600)
     assert rec["n_gpus"] == 8 and rec["config"]["global_batch"] == 2048
     ranks = sorted(rec["ranks"], key=lambda r: r["rank"])

@@ -27,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_four_queue_lanes_structure_and_rate():
     env = dict(os.environ)
     env["GPU_MAX_HW_QUEUES"] = "4"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--hw-queues", "4", "--steps", "40",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--hw-queues", "4", "--steps", "40",
            "--warmup", "5", "--no-cpu-baseline", "--lanes1-steps", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -12,15 +12,15 @@ for l in open('$out/$name.json'):
     if l.startswith('{'):
         d=json.loads(l); print('$name', d.get('value'), d.get('unit'), d.get('config',{}).get('lanes'), d.get('config',{}).get('hw_queues'))"
 }
-run bench_default 400 python -u bench.py
-run bench_driver 200 python -u bench.py --gpus 1 --steps 20 --warmup 5
-run bench_lanes1 200 python -u bench.py --lanes 1 --no-cpu-baseline --no-queue-compare
-run bench_fullres 200 python -u bench.py --workload fullres --no-cpu-baseline --no-queue-compare
-run bench_imagenet_f16 200 python -u bench.py --workload imagenet --no-cpu-baseline --no-queue-compare
-run bench_imagenet_bf16 200 python -u bench.py --workload imagenet --norm-dtype bfloat16 --no-cpu-baseline --no-queue-compare
-run bench_mixed 200 python -u bench.py --workload mixed --no-cpu-baseline --no-queue-compare
-run bench_big1 200 python -u bench.py --workload big1 --no-cpu-baseline --no-queue-compare
-run bench_with_copies 300 python -u bench.py --with-copies --no-cpu-baseline --no-queue-compare
+run bench_default 400 python -u bench.py --full
+run bench_driver 200 python -u bench.py --full --gpus 1 --steps 20 --warmup 5
+run bench_lanes1 200 python -u bench.py --full --lanes 1 --no-cpu-baseline --no-queue-compare
+run bench_fullres 200 python -u bench.py --full --workload fullres --no-cpu-baseline --no-queue-compare
+run bench_imagenet_f16 200 python -u bench.py --full --workload imagenet --no-cpu-baseline --no-queue-compare
+run bench_imagenet_bf16 200 python -u bench.py --full --workload imagenet --norm-dtype bfloat16 --no-cpu-baseline --no-queue-compare
+run bench_mixed 200 python -u bench.py --full --workload mixed --no-cpu-baseline --no-queue-compare
+run bench_big1 200 python -u bench.py --full --workload big1 --no-cpu-baseline --no-queue-compare
+run bench_with_copies 300 python -u bench.py --full --with-copies --no-cpu-baseline --no-queue-compare
 run stream_bytes 300 python -u bench_stream.py --source bytes
 run stream_file 300 python -u bench_stream.py
 run stream_d2h 300 python -u bench_stream.py --source bytes --d2h

@@ -6,7 +6,7 @@ out=gpurun_out/ktq2
 mkdir -p $out
 for q in 4 16; do
   timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d $out/q$q -o run -- \
-    python3 -u bench.py --steps 100 --warmup 10 --no-cpu-baseline --lanes1-steps 0 --hw-queues $q \
+    python3 -u bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --lanes1-steps 0 --hw-queues $q \
     > $out/q$q.log 2>&1 || { tail -5 $out/q$q.log; exit 1; }
   f=$(ls $out/q$q/*/run_kernel_trace.csv $out/q$q/run_kernel_trace.csv 2>/dev/null | head -1)
   python3 tools/queue_map.py $f > $out/q$q.map.txt

@@ -11,7 +11,7 @@ for lanes in 4 1; do
 for m in 0 0x4000 0x80000 0x8000 0x1000 0x84000; do
   d=gpurun_out/ws/l${lanes}_$m
   SPDL_AMD_LIB=$LIB timeout -s KILL 90 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $d -o run --output-format csv \
-    -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-queue-compare --lanes1-steps 0 --lanes $lanes --debug-mask $((m)) > $d.log 2>&1 || { echo "mask $m rc=$?"; tail -3 $d.log; exit 1; }
+    -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-queue-compare --lanes1-steps 0 --lanes $lanes --debug-mask $((m)) > $d.log 2>&1 || { echo "mask $m rc=$?"; tail -3 $d.log; exit 1; }
   python3 - $d $m $lanes <<'PY'
 import csv, glob, sys, re
 d, m, lanes = sys.argv[1:]
