@@ -1218,7 +1218,11 @@ static int planes_to_rgb(const jo_info* info, const uint8_t* planes, int fmt, ui
   for (int y = 0; y < H; y++)
     for (int x = 0; x < W; x++) {
       uint8_t rgb[3];
-      int yv = pc[0][(size_t)y * st[0] + x];
+      /* every component by box replication from its own grid, the first
+       * included (libjpeg's upsampler without do_fancy_upsampling: luma
+       * sampled below chroma is legal there) */
+      int lx = x * info->comp_h[0] / info->hmax, ly = y * info->comp_v[0] / info->vmax;
+      int yv = pc[0][(size_t)ly * st[0] + lx];
       if (info->ncomp == 1) {
         rgb[0] = rgb[1] = rgb[2] = (uint8_t)yv;
       } else if (info->color == JO_COLOR_RGB) { /* all components 1x1 */

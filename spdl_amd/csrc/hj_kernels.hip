@@ -4794,7 +4794,10 @@ __global__ void __launch_bounds__(256) csc_kernel(const uint8_t* __restrict__ pl
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npx;
        i += (int64_t)gridDim.x * blockDim.x) {
     const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
-    const int yv = planes[dd.plane_off[0] + (int64_t)y * dd.plane_stride[0] + x];
+    // (the first component from its own grid too: luma sampled below chroma
+    // is legal for libjpeg, whose plain upsampler replicates)
+    const int lx = x * in.comp_h[0] / in.hmax, ly = y * in.comp_v[0] / in.vmax;
+    const int yv = planes[dd.plane_off[0] + (int64_t)ly * dd.plane_stride[0] + lx];
     int rgb[3];
     if (in.ncomp == 1) {
       rgb[0] = rgb[1] = rgb[2] = yv;

@@ -145,6 +145,26 @@ def test_simple_idct_matches_independent_restatement(oracle):
             blk[1:8] = 0
             blk[0] = int(rng.integers(1500, 4000))
         np.testing.assert_array_equal(oracle.idct_block(blk, 0), _py_simple_idct(blk))
+    # full-range int16 blocks: the 32-bit row and column sums pass 2^31 and
+    # must wrap the same way in both -- random, every coefficient at an
+    # extreme in random sign patterns, and sparse
+    for it in range(600):
+        kind = it % 3
+        if kind == 0:
+            blk = rng.integers(-32768, 32768, size=64).astype(np.int16)
+        elif kind == 1:
+            blk = rng.choice(np.array([32767, -32767, -32768], np.int16), size=64)
+        else:
+            blk = np.zeros(64, np.int16)
+            n = int(rng.integers(1, 9))
+            blk[rng.integers(0, 64, size=n)] = rng.integers(-32768, 32768, size=n).astype(np.int16)
+            if it % 2:
+                blk[0] = int(rng.integers(-32768, 32768))
+        np.testing.assert_array_equal(oracle.idct_block(blk, 0), _py_simple_idct(blk))
+    for sign in (1, -1):  # one sign everywhere: the largest sums of all
+        for v in (32767, -32768):
+            blk = np.full(64, v if sign > 0 else -v - (v < 0), np.int16)
+            np.testing.assert_array_equal(oracle.idct_block(blk, 0), _py_simple_idct(blk))
 
 
 @pytest.mark.parametrize(
