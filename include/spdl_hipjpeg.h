@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SPDL_HJ_ABI_VERSION 6
+#define SPDL_HJ_ABI_VERSION 7
 
 enum spdl_hj_status {
   SPDL_HJ_OK = 0,
@@ -54,12 +54,29 @@ enum spdl_hj_status {
 };
 
 /* output pixel formats (reference nvjpeg/detail/utils.cpp:94-110):
- * RGB/BGR planar [3,H,W]; RGB24/BGR24 interleaved [H,W,3]; YUV = raw planes. */
+ * RGB/BGR planar [3,H,W]; RGB24/BGR24 interleaved [H,W,3].
+ *
+ * YUV (since ABI 7): the frame's own planar format -- what the reference's
+ * filter graph returns when the chain has no format node (load_image_batch
+ * with pix_fmt=None, src/spdl/io/_composite.py:438-462): gray8 stays gray8,
+ * yuvj444p / yuvj422p / yuvj420p keep their subsampling.  With hs, vs the
+ * frame's chroma ratios (1,1 / 2,1 / 2,2) and ow x oh the output size,
+ *   cw = ceil(ow / hs), ch = ceil(oh / vs)
+ *   per image: Y plane oh x ow, then U ch x cw, then V ch x cw, every plane
+ *   tightly packed (av_image_copy_to_buffer order); gray: the Y plane alone
+ *   bytes per image = ow * oh + 2 * cw * ch        (gray: ow * oh)
+ * and image i starts at i * bytes per image; size out_dev from these.
+ * Accepted: gray, and YCbCr with chroma ratios (1,1), (2,1), (2,2).  4:4:0,
+ * 4:1:1, 4:1:0, 1x4, RGB-coded and 4-component frames, and an image whose
+ * format differs from image 0's, get SPDL_HJ_ERR_UNSUPPORTED (that image
+ * alone when it is not image 0; the others decode).  dtype must be U8 and csc
+ * SWSCALE (otherwise the spec is invalid); both IDCTs are allowed. */
 enum spdl_hj_pix_fmt {
   SPDL_HJ_FMT_RGB = 0,
   SPDL_HJ_FMT_BGR = 1,
   SPDL_HJ_FMT_RGB24 = 2,
   SPDL_HJ_FMT_BGR24 = 3,
+  SPDL_HJ_FMT_YUV = 4,
 };
 
 enum spdl_hj_aspect { SPDL_HJ_ASPECT_NONE = 0, SPDL_HJ_ASPECT_DECREASE = 1, SPDL_HJ_ASPECT_INCREASE = 2 };
@@ -90,7 +107,36 @@ enum spdl_hj_csc { SPDL_HJ_CSC_SWSCALE = 0, SPDL_HJ_CSC_JFIF = 1 };
  * builds (src/spdl/io/_preprocessing.py:214-234) is applied per image:
  *   scale=w=fit_w:h=fit_h[:force_original_aspect_ratio=decrease|increase]
  *   [,pad=w=pad_w:h=pad_h:x=-1:y=-1:color=black][,crop=w=crop_w:h=crop_h]
- * fit_w/fit_h <= 0 mean "input size"; pad/crop <= 0 mean "absent". */
+ * fit_w/fit_h == 0 mean "input size"; pad/crop == 0 mean "absent"; a
+ * negative pad or crop size is SPDL_HJ_ERR_BAD_GEOMETRY, as in FFmpeg.
+ * Negative fit_w/fit_h (since ABI 7) have vf_scale's meaning
+ * (ff_scale_adjust_dimensions): -1 keeps the aspect ratio, -n also makes the
+ * result divisible by n.  With fw = max(1, -fit_w), fh = max(1, -fit_h) and
+ * rescale(a, b) = a / b rounded to nearest, ties away from zero (av_rescale):
+ *   both negative        the input size
+ *   fit_w < 0            w = rescale(h * inW, inH * fw) * fw
+ *   fit_h < 0            h = rescale(w * inH, inW * fh) * fh
+ * before force_original_aspect_ratio is applied (which may undo the
+ * divisibility, as in FFmpeg).
+ *
+ * SPDL_HJ_FMT_YUV with resize == 0 returns the full-resolution planes cropped
+ * to each component's true size (the bytes of spdl_hj_decode_planes).  With
+ * resize == 1 the chain runs on the frame's own format: one swscale context
+ * yuvj4xxp -> yuvj4xxp (gray8 -> gray8), luma and chroma planes each through
+ * their own filters (chroma ceil(w / hs) x ceil(h / vs) on both sides, centred
+ * siting) and swscale's 8-bit planar writers; pad and crop then move whole
+ * planes on the chroma grid:
+ *   crop  x = ((w - crop_w) / 2) rounded down to a multiple of hs, y likewise
+ *         with vs; a crop_w / crop_h that is no multiple of its ratio gives
+ *         that image SPDL_HJ_ERR_BAD_GEOMETRY (vf_crop would shrink it
+ *         silently)
+ *   pad   x = ((pad_w - w) / 2) rounded down to a multiple of hs, y likewise;
+ *         a scaled size or a pad size that is no multiple of its ratio gives
+ *         that image SPDL_HJ_ERR_BAD_GEOMETRY: vf_pad rounds the input there
+ *         in a way nothing here can pin, and a refusal is better than a guess
+ *   pad bytes (color=black): yuvj Y = 0, U = V = 128; gray8 16 (drawutils
+ *         uses the limited-range luma of black for gray8)
+ * Gray and 4:4:4 have ratio 1: none of the rounding applies to them. */
 typedef struct spdl_hj_output {
   int32_t pix_fmt;      /* spdl_hj_pix_fmt */
   int32_t dtype;        /* spdl_hj_dtype; F16/BF16 apply (x/255 - mean)/std */
@@ -159,7 +205,9 @@ void spdl_hj_destroy(spdl_hj_ctx* ctx);
  * default stream, (void*)2 = per-thread default, the reference's 0x2 sentinel
  * in src/libspdl/cuda/types.h:22-39).  The batch is packed into pinned
  * staging and copied with one hipMemcpyAsync.  Output layout per image is
- * [3,H,W] (planar) or [H,W,3] (interleaved) at offset i * per-image-size.
+ * [3,H,W] (planar) or [H,W,3] (interleaved) at offset i * per-image-size
+ * (SPDL_HJ_FMT_YUV: the Y, U, V planes and the bytes per image stated at
+ * spdl_hj_pix_fmt; an image the call refuses leaves its bytes untouched).
  * status[i] (optional, host) receives the per-image code.  With sync != 0 the
  * call returns after the stream has drained (reference default sync=true,
  * decoding.cpp:247-251) and fails if any image failed. */

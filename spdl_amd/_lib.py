@@ -15,10 +15,11 @@ from dataclasses import dataclass
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPDL_AMD_LIB") or os.path.join(_HERE, "lib", "libspdl_hipjpeg.so")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # enums (mirror include/spdl_hipjpeg.h)
-PIX_FMTS = {"rgb": 0, "bgr": 1, "rgb24": 2, "bgr24": 3}
+# "yuv": the frame's own planar format (SPDL_HJ_FMT_YUV, see planar_layout)
+PIX_FMTS = {"rgb": 0, "bgr": 1, "rgb24": 2, "bgr24": 3, "yuv": 4}
 ASPECT = {None: 0, "none": 0, "decrease": 1, "increase": 2}
 FILTERS = {"bicubic": 0, "bilinear": 1, "lanczos": 2}
 IDCT = {"simple": 0, "islow": 1}
@@ -95,6 +96,11 @@ class Output:
 
         scale=w=fit_w:h=fit_h[:force_original_aspect_ratio=aspect]
         [,pad=w=pad_w:h=pad_h:x=-1:y=-1:color=black][,crop=w=crop_w:h=crop_h]
+
+    Negative ``fit_w`` / ``fit_h`` have vf_scale's meaning (``-1`` keeps the
+    aspect ratio, ``-n`` also makes the size divisible by n).
+    ``pix_fmt="yuv"`` keeps the frame's own planar format: the chain with no
+    format node (u8, ``csc="swscale"`` only; layout: :func:`planar_layout`).
     """
 
     pix_fmt: str = "rgb"
@@ -148,6 +154,27 @@ class Output:
         if not self.normalize:
             return torch.uint8
         return torch.bfloat16 if self.norm_dtype == "bfloat16" else torch.float16
+
+
+def planar_layout(ow: int, oh: int, hs: int, vs: int, gray: bool) -> tuple[tuple, int]:
+    """(shape, bytes) of one ``pix_fmt="yuv"`` image of ``ow`` x ``oh`` whose
+    frame has chroma ratios ``hs``, ``vs`` (include/spdl_hipjpeg.h: Y, then U,
+    then V of ceil(ow / hs) x ceil(oh / vs), tightly packed), in the layout
+    the reference's convert_frames gives such a frame
+    (src/libspdl/core/detail/ffmpeg/conversion.cpp:196-281): ``[oh, ow, 1]``
+    gray8, ``[3, oh, ow]`` yuvj444p, ``[1, 2 oh, ow]`` yuvj422p, ``[1, oh +
+    oh / 2, ow]`` yuvj420p.  A 4:2:2 / 4:2:0 size that is odd on a subsampled
+    axis does not fill such rows: the reference fails the copy there."""
+    if gray:
+        return (oh, ow, 1), ow * oh
+    if (hs, vs) not in ((1, 1), (2, 1), (2, 2)):
+        raise RuntimeError(f"Unsupported pixel format: chroma ratios {hs}x{vs}")
+    nbytes = ow * oh + 2 * (-(-ow // hs)) * (-(-oh // vs))
+    if (hs, vs) == (1, 1):
+        return (3, oh, ow), nbytes
+    if ow % hs or oh % vs:
+        raise RuntimeError("Failed to copy image data.")
+    return (1, 2 * oh if vs == 1 else oh + oh // 2, ow), nbytes
 
 
 _LIB = None

@@ -169,6 +169,11 @@ struct SwsDesc {
   // hscale_kernel (pre_rl luma / pre_rc chroma rows, row-major int16 in the
   // workspace's hbuf) and sws_kernel stages its bands from there
   int32_t pre, pre_rl, pre_rc;
+  // planar destination (SPDL_HJ_FMT_YUV, yuv_planes_kernel): the frame's own
+  // planes, the chroma ones chr_w x chr_h (the source's subsampling shifts
+  // hsub / vsub kept), hc / vc filtering chroma plane to chroma plane; rb and
+  // col_chunk tile every plane, luma and chroma alike
+  int32_t yuv, hsub, vsub, chr_h;
 };
 
 struct ImageDesc {      // host-filled per image
@@ -200,6 +205,11 @@ struct ImageDesc {      // host-filled per image
   int32_t hs_wg0, hs_wgs;  // hscale_kernel workgroups (SwsDesc::pre images)
   int32_t sws_wg0, sws_bands, sws_chunks;  // sws_kernel tiles: bands x column chunks
   int64_t hbuf_off;        // their horizontal-pass rows (int16 units)
+  // a status the host decided for this image alone (planar output: a frame
+  // format or a geometry it refuses); parse_kernel reports it and every later
+  // kernel skips the image, the rest of the batch decodes
+  int32_t refuse;
+  int32_t pad_;
 };
 
 // sws_kernel LDS budget per workgroup (bytes): the horizontal-pass columns of

@@ -50,6 +50,9 @@ hipError_t launch_nv12(const uint8_t*, uint8_t*, int, int, int, int, int, hipStr
 hipError_t launch_sws(const uint8_t*, const ImageDesc*, const ImageInfo*, const int32_t*, void*,
                       const BatchParams&, const uint32_t*, int, int, int, int, int, int32_t*,
                       const uint32_t*, int, int16_t*, hipStream_t);
+hipError_t launch_yuv_planes(const uint8_t*, const ImageDesc*, const ImageInfo*, const int32_t*,
+                             void*, const uint32_t*, int, int, int32_t*, const uint32_t*, int,
+                             int16_t*, hipStream_t);
 hipError_t launch_rgb_unscaled(const uint8_t*, const ImageDesc*, const ImageInfo*, void*,
                                const BatchParams&, int64_t, int, int32_t*, hipStream_t);
 hipError_t launch_idct_rgb(const uint32_t*, const uint2*, const ImageDesc*, const ImageInfo*, void*,
@@ -353,13 +356,27 @@ struct Geom {
   int sw, sh, dx, dy, ow, oh;
 };
 
-int geometry(int w, int h, const spdl_hj_output* o, Geom* g) {
+// hs / vs: the chroma ratios of a planar destination (SPDL_HJ_FMT_YUV), which
+// pad and crop offsets and sizes must respect; 1 for every packed output
+int geometry(int w, int h, const spdl_hj_output* o, Geom* g, int hs = 1, int vs = 1) {
   if (w <= 0 || h <= 0) return SPDL_HJ_ERR_BAD_GEOMETRY;
   if (!o->resize) {
     *g = {w, h, 0, 0, w, h};
     return SPDL_HJ_OK;
   }
-  int64_t fw = o->fit_w > 0 ? o->fit_w : w, fh = o->fit_h > 0 ? o->fit_h : h;
+  if (o->pad_w < 0 || o->pad_h < 0 || o->crop_w < 0 || o->crop_h < 0)
+    return SPDL_HJ_ERR_BAD_GEOMETRY;
+  // vf_scale's ff_scale_adjust_dimensions: 0 is the input size; -n keeps the
+  // aspect ratio from the other side and makes the result divisible by n
+  // (av_rescale: nearest, ties away from zero); both negative: the input size
+  int64_t fw = o->fit_w ? o->fit_w : w, fh = o->fit_h ? o->fit_h : h;
+  const int64_t dw = fw < -1 ? -fw : 1, dh = fh < -1 ? -fh : 1;
+  if (fw < 0 && fh < 0) {
+    fw = w;
+    fh = h;
+  }
+  if (fw < 0) fw = rescale_rnd(fh, w, (int64_t)h * dw) * dw;
+  if (fh < 0) fh = rescale_rnd(fw, h, (int64_t)w * dh) * dh;
   int64_t sw = fw, sh = fh;
   if (o->aspect != SPDL_HJ_ASPECT_NONE) {
     int64_t tw = rescale_rnd(fh, w, h), th = rescale_rnd(fw, h, w);
@@ -378,16 +395,21 @@ int geometry(int w, int h, const spdl_hj_output* o, Geom* g) {
     cw = o->pad_w;
     ch = o->pad_h;
     if (cw < sw || ch < sh) return SPDL_HJ_ERR_BAD_GEOMETRY;
-    px = (cw - sw) / 2;
-    py = (ch - sh) / 2;
+    // a subsampled frame: vf_pad rounds an input or box size that is no
+    // multiple of the chroma ratio in ways not pinned here -- refused
+    if (sw % hs || cw % hs || sh % vs || ch % vs) return SPDL_HJ_ERR_BAD_GEOMETRY;
+    px = (cw - sw) / 2 / hs * hs;
+    py = (ch - sh) / 2 / vs * vs;
   }
   int64_t ow = cw, oh = ch, cx = 0, cy = 0;
   if (o->crop_w > 0 && o->crop_h > 0) {
     ow = o->crop_w;
     oh = o->crop_h;
     if (ow > cw || oh > ch) return SPDL_HJ_ERR_BAD_GEOMETRY;
-    cx = (cw - ow) / 2;
-    cy = (ch - oh) / 2;
+    // (vf_crop would shrink such a size to a multiple without saying so)
+    if (ow % hs || oh % vs) return SPDL_HJ_ERR_BAD_GEOMETRY;
+    cx = (cw - ow) / 2 / hs * hs;
+    cy = (ch - oh) / 2 / vs * vs;
   }
   if (sw > 65535 || sh > 65535 || ow > 65535 || oh > 65535) return SPDL_HJ_ERR_BAD_GEOMETRY;
   *g = {(int)sw, (int)sh, (int)(px - cx), (int)(py - cy), (int)ow, (int)oh};
@@ -398,6 +420,7 @@ int geometry(int w, int h, const spdl_hj_output* o, Geom* g) {
 // One per distinct (source size, sampling, output placement, filter); cached
 // per context so a stream of same-size images plans once.
 enum { kPlanYuv = 0, kPlanGray = 1, kPlanGbr = 2 };  // source planes of a plan
+constexpr int kPlanPlanar = 4;  // | kPlanYuv / kPlanGray: the planar destination (SPDL_HJ_FMT_YUV)
 struct PlanKey {
   int w, h, hsub, vsub, mode, filter, sw, sh, dx, dy, ow, oh;
   bool operator<(const PlanKey& o) const {
@@ -412,6 +435,13 @@ struct PackedPlan {
   int bands = 0, chunks = 0, lds = 0;
   bool special = false;         // swscale's unscaled yuv2rgb_c_24_rgb converter
 };
+
+// yuv_planes_kernel's LDS of one tile (hj_kernels.hip): the horizontal-pass
+// columns, then the u8 tile with room to sit at its destination's alignment
+inline int64_t planar_tile_lds(int ncols, int rows, int rb, int chunk) {
+  const int64_t h = (2 * (int64_t)ncols * sws_col_stride(rows) + 15) & ~(int64_t)15;
+  return h + (int64_t)rb * ((chunk + 30) & ~15) + 16;
+}
 
 class PlanCache {
  public:
@@ -452,6 +482,7 @@ class PlanCache {
 
   static std::shared_ptr<const PackedPlan> build(const PlanKey& k, int* rc, int pre_mode,
                                                  int max_cols) {
+    if (k.mode & kPlanPlanar) return build_planar(k, rc, pre_mode, max_cols);
     SwsPlan pl;
     // gbr: the luma plan (gray) applied to each of the three RGB planes
     *rc = sws_plan(k.w, k.h, k.hsub, k.vsub, k.mode != kPlanYuv, k.sw, k.sh, k.filter, &pl);
@@ -543,6 +574,94 @@ class PlanCache {
     return pp;
   }
 
+  // The planar destination (hj_sws.h sws_plan_planar): the same tables
+  // (no row writers), one band height and column chunk for the luma and the
+  // chroma tiles; `bands` counts the image's tiles, luma then U then V
+  static std::shared_ptr<const PackedPlan> build_planar(const PlanKey& k, int* rc, int pre_mode,
+                                                        int max_cols) {
+    SwsPlan pl;
+    const bool gray = (k.mode & ~kPlanPlanar) == kPlanGray;
+    *rc = sws_plan_planar(k.w, k.h, k.hsub, k.vsub, gray, k.sw, k.sh, k.filter, &pl);
+    if (*rc) return nullptr;
+    auto pp = std::make_shared<PackedPlan>();
+    SwsDesc& d = pp->d;
+    d.sw = k.sw;
+    d.sh = k.sh;
+    d.chr_w = pl.chrDstW;
+    d.chr_h = pl.chrDstH;
+    d.gray = pl.gray;
+    d.yuv = 1;
+    d.hsub = pl.hsub;
+    d.vsub = pl.vsub;
+    const SwsAxis* ax[4] = {&pl.hl, &pl.hc, &pl.vl, &pl.vc};
+    int32_t* taps[4] = {&d.hl_taps, &d.hc_taps, &d.vl_taps, &d.vc_taps};
+    int32_t* sizes[4] = {&d.hl_size, &d.hc_size, &d.vl_size, &d.vc_size};
+    for (int i = 0; i < 4; i++) {  // rows cut and padded as build() does (hpass buckets)
+      const SwsAxis& a = *ax[i];
+      int q = (a.eff + 3) / 4;
+      if (i < 2) q = q <= 4 ? q : q <= 6 ? 6 : q <= 8 ? 8 : q <= 12 ? 12 : q <= 16 ? 16 : q;
+      const int stride = 4 * q;
+      *taps[i] = a.eff;
+      *sizes[i] = stride;
+      std::vector<int16_t> rows((size_t)a.n * stride, 0);
+      for (int r = 0; r < a.n; r++)
+        for (int t = 0; t < a.eff; t++) rows[(size_t)r * stride + t] = a.coef[(size_t)r * a.size + t];
+      put(pp->blob, &d.off[2 * i], a.pos.data(), a.pos.size() * 4);
+      put(pp->blob, &d.off[2 * i + 1], rows.data(), rows.size() * 2);
+    }
+    put(pp->blob, &d.off[kVmode], nullptr, 0);
+    auto reach = [](const SwsAxis& a) {
+      int r = 0;
+      for (int y = 0; y < a.n; y++) r = std::max(r, a.pos[y] + a.eff);
+      return r;
+    };
+    d.pre = pre_mode > 0 || (pre_mode < 0 && (k.h >= kPreRatio * k.sh || pl.hl.eff > 64));
+    d.pre_rl = d.pre ? reach(pl.vl) : 0;
+    d.pre_rc = d.pre && !pl.gray ? reach(pl.vc) : 0;
+    // the planes' placement: luma as the key says, chroma at the shifted
+    // offsets (multiples of the ratios: geometry()) in a ceil-shifted box
+    struct Pl {
+      const SwsAxis* v;
+      int sw, sh, dx, dy, ow, oh;
+    };
+    const Pl pls[2] = {
+        {&pl.vl, k.sw, k.sh, k.dx, k.dy, k.ow, k.oh},
+        {&pl.vc, pl.chrDstW, pl.chrDstH, k.dx >> pl.hsub, k.dy >> pl.vsub,
+         -((-k.ow) >> pl.hsub), -((-k.oh) >> pl.vsub)}};
+    const int npl = pl.gray ? 1 : 2;
+    for (int cols = std::min(max_cols, kSwsMaxCols); cols >= 16 && !pp->bands; cols /= 2) {
+      const int chunk = k.ow < cols ? k.ow : cols;
+      static const int kRb[] = {32, 24, 16, 12, 8, 6, 4, 3, 2, 1};
+      for (int rb : kRb) {
+        int64_t lds = planar_tile_lds(0, 0, rb, chunk);
+        for (int c = 0; c < npl; c++) {
+          const Pl& P = pls[c];
+          for (int yo0 = 0; yo0 < P.oh; yo0 += rb) {
+            const int ys0 = std::max(yo0 - P.dy, 0), ys1 = std::min(yo0 + rb - P.dy, P.sh);
+            if (ys0 >= ys1) continue;
+            const int rows = P.v->pos[ys1 - 1] + P.v->eff - P.v->pos[ys0];
+            const int ncols = std::min(chunk, P.sw);
+            lds = std::max(lds, planar_tile_lds(ncols, rows, rb, chunk));
+          }
+        }
+        if (lds <= kSwsLdsBudget || (!d.pre && rb == 1 && lds <= 64 * 1024)) {
+          d.rb = rb;
+          d.col_chunk = chunk;
+          pp->lds = (int)lds;
+          pp->chunks = 1;
+          for (int c = 0; c < npl; c++)
+            pp->bands += (c ? 2 : 1) * ((pls[c].oh + rb - 1) / rb) * ((pls[c].ow + chunk - 1) / chunk);
+          break;
+        }
+      }
+    }
+    if (!pp->bands) {
+      *rc = SPDL_HJ_ERR_BAD_GEOMETRY;
+      return nullptr;
+    }
+    return pp;
+  }
+
   std::map<PlanKey, std::shared_ptr<const PackedPlan>> map_;
   int pre_mode_ = -1;
   int max_cols_ = kSwsMaxCols;
@@ -579,6 +698,8 @@ struct Layout {
   int sws_bands = 0, sws_chunks = 0, sws_lds = 0;
   bool all_special = true;  // every image takes swscale's unscaled converter
   bool fuse_ok = true;      // ... with standard 4:2:0 / 4:2:2 MCUs (idct_rgb_kernel)
+  int yuv_hs = 0, yuv_vs = 0;  // SPDL_HJ_FMT_YUV: image 0's chroma shifts, and whether it is
+  bool yuv_gray = false;      // gray -- the batch's plane layout
   int64_t cmyk_px = 0;      // 4-component images needing cmyk_kernel's K transform: max pixels
   int fused_tiles = 0;      // idct_rgb_kernel workgroups per image (max)
   // entropy work items (image | piece << 24), the images with the most
@@ -607,6 +728,7 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
                  int n, const spdl_hj_output* out, int sub_bits, int64_t piece_bytes, Layout& L,
                  int32_t* status, char* err, size_t errlen, PlanCache* plans) {
   L.desc.assign(n, ImageDesc{});
+  const bool yuv = out->pix_fmt == SPDL_HJ_FMT_YUV;
   // plan -> offset in L.tables.  `alive` holds every placed plan until the
   // layout is built: the cache may evict (and free) a plan mid-batch, and a
   // new plan at a recycled address must not match a stale `placed` entry
@@ -716,13 +838,42 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
     int64_t px = (int64_t)g.ow * g.oh;
     if (px > L.max_px) L.max_px = px;
     if (!plans || out->csc == SPDL_HJ_CSC_JFIF) continue;
-    int hs, vs;
-    if ((rc = chroma_shifts(p, &hs, &vs))) return fail(i, rc, nullptr);
-    // RGB planes (gbrp; CMYK after the K transform, gbrap) through the luma
-    // filters; YCCK after the transform and YCbCr + K are YCbCr 4:4:4
-    const int mode = p.ncomp == 1                                        ? kPlanGray
-                     : p.color == kColorRgb || p.color == kColorCmyk ? kPlanGbr
-                                                                      : kPlanYuv;
+    int hs, vs, mode;
+    if (yuv) {
+      // The frame's own planes: gray8 or yuvj444p / 422p / 420p, every image
+      // in image 0's format.  An image that is not, or whose pad / crop does
+      // not fall on its chroma grid, is refused alone (ImageDesc::refuse): one
+      // workgroup of the output kernel reports it, the others decode.
+      int why = chroma_shifts(p, &hs, &vs);
+      const bool gray = p.ncomp == 1;
+      if (!why && (p.ncomp == 4 || p.color == kColorRgb || hs > 1 || vs > hs))
+        why = SPDL_HJ_ERR_UNSUPPORTED;
+      if (i == 0) {
+        if (why) return fail(0, why, "no planar output for this frame format");
+        L.yuv_hs = hs;
+        L.yuv_vs = vs;
+        L.yuv_gray = gray;
+      } else if (!why && (hs != L.yuv_hs || vs != L.yuv_vs || gray != L.yuv_gray)) {
+        why = SPDL_HJ_ERR_UNSUPPORTED;
+      }
+      if (!why) why = geometry(p.width, p.height, out, &g, 1 << hs, 1 << vs);
+      if (why) {
+        d.refuse = why;
+        d.sws_wg0 = (int32_t)L.sws_wgs++;
+        d.sws_bands = d.sws_chunks = 1;
+        continue;
+      }
+      d.dx = g.dx;
+      d.dy = g.dy;
+      mode = (gray ? kPlanGray : kPlanYuv) | kPlanPlanar;
+    } else {
+      if ((rc = chroma_shifts(p, &hs, &vs))) return fail(i, rc, nullptr);
+      // RGB planes (gbrp; CMYK after the K transform, gbrap) through the luma
+      // filters; YCCK after the transform and YCbCr + K are YCbCr 4:4:4
+      mode = p.ncomp == 1                                        ? kPlanGray
+             : p.color == kColorRgb || p.color == kColorCmyk ? kPlanGbr
+                                                              : kPlanYuv;
+    }
     const PlanKey key{p.width, p.height, hs, vs, mode, out->resize ? out->filter : 0,
                       g.sw, g.sh, g.dx, g.dy, g.ow, g.oh};
     auto plan = plans->get(key, &rc);
@@ -766,6 +917,11 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
     L.sws_lds = std::max(L.sws_lds, plan->lds);
   }
   L.out_elems_per_image = (int64_t)L.ow * L.oh * 3;
+  if (yuv)  // Y, then U and V of ceil(ow / hs) x ceil(oh / vs) (gray: Y alone)
+    L.out_elems_per_image =
+        (int64_t)L.ow * L.oh + (L.yuv_gray ? 0
+                                           : 2 * (int64_t)(-((-L.ow) >> L.yuv_hs)) *
+                                                 (-((-L.oh) >> L.yuv_vs)));
   for (int i = 0; i < n; i++) L.desc[i].out_off = (int64_t)i * L.out_elems_per_image;
   // entropy work list: the images with the most pieces first (their pieces
   // start early and in ticket order), each image's pieces in order
@@ -1210,7 +1366,9 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
   // conversion in one kernel (output_path 1: the generic sws_kernel, 2:
   // separate IDCT + rgb_unscaled_kernel)
   const int idct_kind = (ctx->debug_mask & 0x800) ? 2 : out->idct;
-  const bool fast_rgb = swscale && L.all_special && out->dtype == SPDL_HJ_DTYPE_U8 &&
+  // (the planar output, SPDL_HJ_FMT_YUV, has one kernel of its own)
+  const bool yuv = swscale && out->pix_fmt == SPDL_HJ_FMT_YUV;
+  const bool fast_rgb = swscale && !yuv && L.all_special && out->dtype == SPDL_HJ_DTYPE_U8 &&
                         ctx->output_path != 1;
   const bool fused = fast_rgb && L.fuse_ok && L.fused_tiles > 0 && ctx->output_path != 2;
   if (!(ctx->debug_mask & 0x20000) && !fused)
@@ -1254,7 +1412,12 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
   int32_t* hstat = hs && !planes_only ? static_cast<int32_t*>(slot.pin_status.dev) : nullptr;
   mark(ctx, slot, 6, st);
   if (!planes_only && !(ctx->debug_mask & 0x40000)) {
-    if (fused) {
+    if (yuv) {
+      HJ_HIP(launch_yuv_planes(static_cast<const uint8_t*>(W.planes.p), desc, infos,
+                               static_cast<const int32_t*>(W.wts.p), out_dev, sws_map,
+                               (int)L.sws_wgs, L.sws_lds, hstat, hs_map, (int)L.hs_wgs,
+                               static_cast<int16_t*>(W.hbuf.p), st));
+    } else if (fused) {
       HJ_HIP(launch_idct_rgb(static_cast<const uint32_t*>(W.ents.p),
                              static_cast<const uint2*>(W.bdesc.p), desc, infos, out_dev, bp,
                              idct_kind, L.fused_tiles, n, hstat, st));
@@ -1377,7 +1540,11 @@ int stage_h2d(spdl_hj_ctx* ctx, Slot& s, size_t total, hipStream_t st, char* err
 
 bool valid_output(const spdl_hj_output* o) {
   // the JFIF conversion has no scaler: full resolution only
-  return o && o->pix_fmt >= 0 && o->pix_fmt <= 3 && (o->dtype >= 0 && o->dtype <= 2) &&
+  // ... and the planar output is u8 planes of swscale's scaler alone
+  if (o && o->pix_fmt == SPDL_HJ_FMT_YUV &&
+      (o->dtype != SPDL_HJ_DTYPE_U8 || o->csc != SPDL_HJ_CSC_SWSCALE))
+    return false;
+  return o && o->pix_fmt >= 0 && o->pix_fmt <= SPDL_HJ_FMT_YUV && (o->dtype >= 0 && o->dtype <= 2) &&
          (o->idct == 0 || o->idct == 1) && (o->filter >= 0 && o->filter <= 2) &&
          o->aspect >= 0 && o->aspect <= 2 &&
          (o->csc == SPDL_HJ_CSC_SWSCALE || (o->csc == SPDL_HJ_CSC_JFIF && !o->resize));

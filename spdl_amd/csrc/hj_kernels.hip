@@ -347,6 +347,7 @@ __global__ void __launch_bounds__(256, 8) parse_kernel(const uint8_t* __restrict
           (s.info.mcux * s.info.mcuy + s.info.ri - 1) / s.info.ri > dd.seg_cap)
         rc = kErrBadRestart;
     }
+    if (rc == kOk && dd.refuse) rc = dd.refuse;  // the host refused this image alone
     s.info.status = rc;
     st = rc;
   }
@@ -5392,6 +5393,171 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
   }
 }
 
+// yuv_planes_kernel: the planar destination (SPDL_HJ_FMT_YUV) -- the scale
+// chain on the frame's own format, yuvj4xxp -> yuvj4xxp or gray8 -> gray8
+// (hj_sws.h sws_plan_planar).  A sibling of sws_kernel without the colour
+// arithmetic: every plane goes through its own filters (luma hl / vl, chroma
+// hc / vc, chroma plane to chroma plane) and swscale's 8-bit planar writer
+//   clip8((2^18 + sum tap x) >> 19)          (yuv2planeX_8_c; a size-1 filter
+//   holds the tap 4096, which makes it yuv2plane1_8_c's clip8((x + 64) >> 7))
+// as the gbr branch of sws_kernel does per RGB plane.  One workgroup per
+// (plane, row band, column chunk) tile of one image, flat grid through
+// sws_map; an image's tiles are its luma tiles, then U's, then V's, bands of
+// SwsDesc::rb rows and chunks of SwsDesc::col_chunk columns of the plane.
+// Horizontal pass (hpass, or hscale_kernel's rows for a large downscale) into
+// column-major LDS, vertical pass one column per thread into a u8 tile in
+// LDS, pad region filled with the plane's pad byte (Y 0, U = V 128; gray8
+// 16), then the tile out.  Plane rows are ow or cw bytes, not 4-aligned in
+// general: a run of the tile (the whole tile when it spans the plane's
+// width, else one row) sits in LDS at its destination's offset within 16
+// bytes, so after a head of single bytes both sides are 16-byte aligned for
+// dwordx4 stores, and a tail of single bytes ends it.
+__device__ __forceinline__ void yuv_stage(const int16_t* __restrict__ src, int w, int rows, int c0,
+                                          int ncols, int r0, int r1, int16_t* dst, int cst,
+                                          int tid, int nt) {
+  // hscale_kernel's row-major rows [r0, r1) x [c0, c0 + ncols) into the
+  // column-major LDS (rows past the last one read it: zero taps only)
+  const int nr = r1 - r0, ne = ncols * nr;
+  for (int i0 = tid; i0 < ne; i0 += 4 * nt) {
+    int16_t v[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = min(i0 + u * nt, ne - 1);
+      const int r = i / ncols, c = i - r * ncols;
+      v[u] = src[(int64_t)min(r0 + r, rows - 1) * w + c0 + c];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = i0 + u * nt;
+      if (i < ne) {
+        const int r = i / ncols, c = i - r * ncols;
+        dst[c * cst + r] = v[u];
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restrict__ planes,
+                                                         const ImageDesc* __restrict__ desc,
+                                                         const ImageInfo* __restrict__ infos,
+                                                         const int32_t* __restrict__ pool,
+                                                         uint8_t* __restrict__ out,
+                                                         int32_t* __restrict__ host_status,
+                                                         const int16_t* __restrict__ hbuf,
+                                                         const uint32_t* __restrict__ sws_map) {
+  extern __shared__ __attribute__((aligned(16))) int16_t yuv_lds[];
+  const int img = (int)sws_map[blockIdx.x], tid = threadIdx.x, nt = blockDim.x;
+  const ImageDesc& dd = desc[img];
+  int t = (int)blockIdx.x - dd.sws_wg0;
+  const ImageInfo& in = infos[img];
+  // the image's final status, straight into the slot's pinned status array
+  // (an image the host refused has this one workgroup)
+  if (host_status && t == 0 && tid == 0) host_status[img] = in.status;
+  if (in.status != kOk) return;
+  const SwsDesc& s = dd.sws;
+  // the tile's plane: its box (W x H), the scaled content (psw x psh) and
+  // where that sits in the box (the chroma offsets are exact shifts: the host
+  // keeps pad and crop on the chroma grid)
+  const int cw = (dd.ow + (1 << s.hsub) - 1) >> s.hsub, ch = (dd.oh + (1 << s.vsub) - 1) >> s.vsub;
+  const int ltiles = ((dd.oh + s.rb - 1) / s.rb) * ((dd.ow + s.col_chunk - 1) / s.col_chunk);
+  int c = 0;
+  if (t >= ltiles) {
+    const int ctiles = ((ch + s.rb - 1) / s.rb) * ((cw + s.col_chunk - 1) / s.col_chunk);
+    t -= ltiles;
+    c = 1 + t / ctiles;
+    t -= (c - 1) * ctiles;
+    if (s.gray || c > 2) return;
+  }
+  const bool luma = c == 0;
+  const int W = luma ? dd.ow : cw, H = luma ? dd.oh : ch;
+  const int psw = luma ? s.sw : s.chr_w, psh = luma ? s.sh : s.chr_h;
+  const int pdx = luma ? dd.dx : dd.dx >> s.hsub, pdy = luma ? dd.dy : dd.dy >> s.vsub;
+  const int padv = luma ? (s.gray ? 16 : 0) : 128;
+  const int chunks = (W + s.col_chunk - 1) / s.col_chunk;
+  const int band = t / chunks, chunk = t - band * chunks;
+  const int yo0 = band * s.rb, xo0 = chunk * s.col_chunk;
+  if (yo0 >= H || xo0 >= W) return;
+  const int yo1 = min(yo0 + s.rb, H), xo1 = min(xo0 + s.col_chunk, W);
+  const int th = yo1 - yo0, tw = xo1 - xo0;
+  const int ys0 = max(yo0 - pdy, 0), ys1 = min(yo1 - pdy, psh);
+  const int xs0 = max(xo0 - pdx, 0), xs1 = min(xo1 - pdx, psw);
+  const bool content = ys0 < ys1 && xs0 < xs1;
+  const int ncl = content ? xs1 - xs0 : 0;
+  const int32_t* T = pool + dd.wt_off;
+  const int32_t* vpos = T + s.off[luma ? kVlPos : kVcPos];
+  const uint32_t* vco = reinterpret_cast<const uint32_t*>(T + s.off[luma ? kVlCoef : kVcCoef]);
+  const int vnp = (luma ? s.vl_size : s.vc_size) / 2, vtaps = luma ? s.vl_taps : s.vc_taps;
+  int r0 = 0, r1 = 0;
+  if (content) {
+    r0 = vpos[ys0];
+    r1 = vpos[ys1 - 1] + vtaps;
+  }
+  // LDS: the horizontal-pass columns, then the u8 tile
+  const int cst = sws_col_stride(r1 - r0);
+  int16_t* hcol = yuv_lds;
+  uint8_t* tile = reinterpret_cast<uint8_t*>(yuv_lds) + ((2 * ncl * cst + 15) & ~15);
+  // the tile's destination: one run when the tile spans the plane's width
+  const int64_t pbase = dd.out_off + (luma ? 0 : (int64_t)dd.ow * dd.oh + (int64_t)(c - 1) * cw * ch);
+  uint8_t* dst = out + pbase + (int64_t)yo0 * W + xo0;
+  const bool whole = tw == W;
+  const int nrun = whole ? 1 : th, runlen = whole ? th * W : tw;
+  const int pitch = (tw + 30) & ~15;  // LDS bytes between the runs of a chunked tile
+  const uint32_t g0 = (uint32_t)(uintptr_t)dst;
+  auto tpos = [&](int r, int k) {  // tile byte of row r, column k
+    return whole ? (int)(g0 & 15u) + r * W + k : r * pitch + (int)((g0 + (uint32_t)(r * W)) & 15u) + k;
+  };
+  // pad: tile pixels outside the scaled content
+  for (int i = tid; i < th * tw; i += nt) {
+    const int r = i / tw, k = i - r * tw;
+    const int ys = yo0 + r - pdy, xs = xo0 + k - pdx;
+    if (ys < 0 || ys >= psh || xs < 0 || xs >= psw) tile[tpos(r, k)] = (uint8_t)padv;
+  }
+  if (content && s.pre) {
+    const int64_t poff = luma ? 0 : (int64_t)s.pre_rl * s.sw + (int64_t)(c - 1) * s.pre_rc * s.chr_w;
+    yuv_stage(hbuf + dd.hbuf_off + poff, psw, luma ? s.pre_rl : s.pre_rc, xs0, ncl, r0, r1, hcol,
+              cst, tid, nt);
+  } else if (content) {
+    hpass(planes + dd.plane_off[c], dd.plane_stride[c], in.comp_hpx[c],
+          T + s.off[luma ? kHlPos : kHcPos],
+          reinterpret_cast<const int16_t*>(T + s.off[luma ? kHlCoef : kHcCoef]),
+          luma ? s.hl_size : s.hc_size, luma ? s.hl_taps : s.hc_taps, xs0, ncl, r0, r1, hcol, cst,
+          tid, nt);
+  }
+  __syncthreads();
+  if (content) {
+    // vertical taps + the planar writer, one scaled column per thread (the
+    // row's first source row and taps are uniform: scalar loads)
+    for (int cl = tid; cl < ncl; cl += nt) {
+      const uint32_t* col = reinterpret_cast<const uint32_t*>(hcol + cl * cst);
+      const int k = xs0 + cl + pdx - xo0;
+      for (int ys = ys0; ys < ys1; ys++) {
+        const int v = ((1 << 18) + vdot_pairs(col, vpos[ys] - r0, vco + (int64_t)ys * vnp, vnp)) >> 19;
+        tile[tpos(ys + pdy - yo0, k)] = (uint8_t)clip_i8(v);
+      }
+    }
+  }
+  __syncthreads();
+  // the tile out: per run up to 15 head bytes, 16-byte vectors, up to 15 tail
+  // bytes; a thread takes one of these items at a time
+  const int items = 30 + runlen / 16 + 1;
+  for (int i = tid; i < nrun * items; i += nt) {
+    const int r = i / items, j = i - r * items;
+    uint8_t* g = dst + (int64_t)r * W;
+    const uint8_t* l = tile + tpos(r, 0);
+    const int head = min(runlen, (int)((16u - ((uint32_t)(uintptr_t)g & 15u)) & 15u));
+    const int nvec = (runlen - head) >> 4, tail = runlen - head - 16 * nvec;
+    if (j < 15) {
+      if (j < head) g[j] = l[j];
+    } else if (j < 30) {
+      const int o = head + 16 * nvec + (j - 15);
+      if (j - 15 < tail) g[o] = l[o];
+    } else if (j - 30 < nvec) {
+      const int o = head + 16 * (j - 30);
+      *reinterpret_cast<uint4*>(g + o) = *reinterpret_cast<const uint4*>(l + o);
+    }
+  }
+}
+
 // swscale's unscaled special converter (ff_get_unscaled_swscale ->
 // yuv2rgb_c_24_rgb: yuvj420p with even height / yuvj422p, even width ->
 // rgb24) for full-resolution output: nearest chroma and the same table
@@ -5837,6 +6003,18 @@ hipError_t launch_sws(const uint8_t* planes, const ImageDesc* desc, const ImageI
   const dim3 grid = sws_map ? dim3(sws_wgs) : dim3(bands, chunks, n);
   hipLaunchKernelGGL(sws_kernel, grid, dim3(256), lds_bytes, st, planes, desc, infos, pool, out, p,
                      host_status, hbuf, sws_map);
+  return hipGetLastError();
+}
+hipError_t launch_yuv_planes(const uint8_t* planes, const ImageDesc* desc, const ImageInfo* infos,
+                             const int32_t* pool, void* out, const uint32_t* sws_map, int sws_wgs,
+                             int lds_bytes, int32_t* host_status, const uint32_t* hs_map,
+                             int hs_wgs, int16_t* hbuf, hipStream_t st) {
+  if (hs_wgs > 0)
+    hipLaunchKernelGGL(hscale_kernel, dim3(hs_wgs), dim3(256), 0, st, planes, desc, infos, pool,
+                       hs_map, hbuf);
+  // (always the flat grid: every image's own tiles, three planes each)
+  hipLaunchKernelGGL(yuv_planes_kernel, dim3(sws_wgs), dim3(256), lds_bytes, st, planes, desc,
+                     infos, pool, static_cast<uint8_t*>(out), host_status, hbuf, sws_map);
   return hipGetLastError();
 }
 hipError_t launch_cmyk(const ImageDesc* desc, const ImageInfo* infos, uint8_t* planes,

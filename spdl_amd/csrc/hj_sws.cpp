@@ -310,4 +310,38 @@ int sws_plan(int srcW, int srcH, int hsub, int vsub, bool gray, int dstW, int ds
   return SPDL_HJ_OK;
 }
 
+int sws_plan_planar(int srcW, int srcH, int hsub, int vsub, bool gray, int dstW, int dstH, int kind,
+                    SwsPlan* p) {
+  *p = SwsPlan{};
+  p->srcW = srcW;
+  p->srcH = srcH;
+  p->dstW = dstW;
+  p->dstH = dstH;
+  p->gray = gray;
+  p->hsub = gray ? 0 : hsub;
+  p->vsub = gray ? 0 : vsub;
+  p->chrSrcW = ceil_rshift(srcW, p->hsub);
+  p->chrSrcH = ceil_rshift(srcH, p->vsub);
+  p->chrDstW = ceil_rshift(dstW, p->hsub);
+  p->chrDstH = ceil_rshift(dstH, p->vsub);
+  const int lp = local_pos(0, 0);
+  if (!FilterBuilder((int)xinc(srcW, dstW), srcW, dstW, 4, 1 << 14, kind, lp, lp).build(&p->hl) ||
+      !FilterBuilder((int)xinc(srcH, dstH), srcH, dstH, 2, 1 << 12, kind, lp, lp).build(&p->vl))
+    return SPDL_HJ_ERR_BAD_GEOMETRY;
+  if (!gray) {
+    const int hp = local_pos(p->hsub, -513), vp = local_pos(p->vsub, -513);
+    if (!FilterBuilder((int)xinc(p->chrSrcW, p->chrDstW), p->chrSrcW, p->chrDstW, 4, 1 << 14, kind,
+                       hp, hp)
+             .build(&p->hc) ||
+        !FilterBuilder((int)xinc(p->chrSrcH, p->chrDstH), p->chrSrcH, p->chrDstH, 2, 1 << 12, kind,
+                       vp, vp)
+             .build(&p->vc))
+      return SPDL_HJ_ERR_BAD_GEOMETRY;
+  }
+  // yuv2plane1 ignores its tap (see hj_sws.h)
+  for (SwsAxis* a : {&p->vl, &p->vc})
+    if (a->size == 1) std::fill(a->coef.begin(), a->coef.end(), (int16_t)(1 << 12));
+  return SPDL_HJ_OK;
+}
+
 }  // namespace hj

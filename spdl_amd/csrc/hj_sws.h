@@ -50,4 +50,17 @@ SwsCsc sws_csc();
 int sws_plan(int srcW, int srcH, int hsub, int vsub, bool gray, int dstW, int dstH, int kind,
              SwsPlan* out);
 
+// The plan of a planar destination that keeps the source's format
+// (SPDL_HJ_FMT_YUV: yuvj4xxp -> yuvj4xxp, gray8 -> gray8; a scale filter with
+// no format node after it): chrDstW x chrDstH = ceil(dstW >> hsub) x
+// ceil(dstH >> vsub), luma filters as sws_plan, chroma filters from chroma
+// plane to chroma plane with centred siting on both sides.  No colour tables,
+// no `full`, no `special`: swscale's 8-bit planar writers (vscale.c
+// lum_planar_vscale / chr_planar_vscale -> yuv2plane1_8_c, yuv2planeX_8_c)
+// take every row, and `vmode` stays empty.  A vertical filter of size 1 holds
+// the tap 4096, with which yuv2planeX's (2^18 + tap x) >> 19 is yuv2plane1's
+// (x + 64) >> 7, the writer swscale picks for that size whatever the tap.
+int sws_plan_planar(int srcW, int srcH, int hsub, int vsub, bool gray, int dstW, int dstH, int kind,
+                    SwsPlan* out);
+
 }  // namespace hj

@@ -102,6 +102,34 @@ def _shape(out: Output, w: int, h: int) -> tuple:
     return (3, h, w) if out.planar else (h, w, 3)
 
 
+def _frame_format(info) -> tuple[int, int, bool]:
+    """(hs, vs, gray): the chroma ratios of the planar frame FFmpeg's decoder
+    makes of this file, for the ``pix_fmt="yuv"`` output; the frames
+    convert_frames has no layout for raise as :func:`_native_planes` does."""
+    fmt = _UNSUPPORTED_FRAMES.get(info.color)
+    if fmt is not None:
+        raise RuntimeError(f"Unsupported pixel format: {fmt}")
+    if info.ncomp == 1:
+        return 1, 1, True
+    h, v = list(info.h_samp[:3]), list(info.v_samp[:3])
+    hs, vs = h[0] // max(h[1], 1), v[0] // max(v[1], 1)
+    if (h[1], v[1]) != (h[2], v[2]) or h[0] != hs * h[1] or v[0] != vs * v[1] or \
+            (hs, vs) not in ((1, 1), (2, 1), (2, 2)):
+        raise RuntimeError(
+            f"Unsupported pixel format: sampling {h[0]}x{v[0]},{h[1]}x{v[1]},{h[2]}x{v[2]}")
+    return hs, vs, False
+
+
+def _yuv_shape(infos: list, out: Output) -> tuple:
+    """Per-image shape of the ``pix_fmt="yuv"`` result of these images (one
+    frame format, one output size), or the reference's error."""
+    fmts = [_frame_format(i) for i in infos]
+    ow, oh = _lib.output_size(infos[0].width, infos[0].height, out)
+    if any(f != fmts[0] for f in fmts):
+        raise RuntimeError("The input images must have the same size and pixel format.")
+    return _lib.planar_layout(ow, oh, *fmts[0])[0]
+
+
 def decode_image_nvjpeg(
     src,
     *,
@@ -217,6 +245,10 @@ def load_image_batch(
 ):
     """Batch load images into one ``[B,H,W,3]`` buffer with the FFmpeg filter
     semantics of the reference CPU path (scale + centred pad by default).
+    ``pix_fmt=None`` leaves the format node out: the chain then runs on the
+    decoder's own planar format and the batch holds the scaled planes as the
+    reference's convert_frames stacks them (``[B,1,H+H/2,W]`` yuvj420p,
+    ``[B,1,2H,W]`` yuvj422p, ``[B,3,H,W]`` yuvj444p, ``[B,H,W,1]`` gray).
 
     Decoding runs on ``device_config``'s GPU (when absent: the current HIP
     device, or ``$LOCAL_RANK``); without a ``device_config`` the result is
@@ -261,8 +293,12 @@ def load_image_batch(
 
             return convert_array(arr, storage=storage)
         return CPUBuffer(arr)
-    out = parse_image_filter(filter_desc, default_pix_fmt=pix_fmt or "rgb24")
+    # (no format node and pix_fmt=None: the decoder's own planes, scaled)
+    out = parse_image_filter(filter_desc, default_pix_fmt=pix_fmt)
     if normalize:
+        if out.pix_fmt == "yuv":
+            raise ValueError("normalize=True needs an RGB pix_fmt; pix_fmt=None keeps the "
+                             "decoder's planar format")
         out = Output(**{**out.__dict__, "normalize": True, "mean": tuple(mean),
                         "std": tuple(std), "norm_dtype": norm_dtype})
     datas, keep = [], []
@@ -282,7 +318,10 @@ def load_image_batch(
     info = _lib.get_image_info(datas[0])
     ow, oh = _lib.output_size(info.width, info.height, out)
     dtype = out.torch_dtype
-    shape = _shape(out, ow, oh)
+    if out.pix_fmt == "yuv":
+        shape = _yuv_shape([_lib.get_image_info(d) for d in datas], out)
+    else:
+        shape = _shape(out, ow, oh)
     try:
         buf = _decode(datas, out, cfg, shape, True, dtype=dtype)
     except RuntimeError:
@@ -351,13 +390,15 @@ def load_image(
     *,
     filter_desc: str | None = _FILTER_DESC_DEFAULT,
     device_config: CUDAConfig | None = None,
-    pix_fmt: str = "rgb24",
+    pix_fmt: str | None = "rgb24",
     **kwargs,
 ):
     """Single image.  ``filter_desc=None`` returns the decoded planes in the
     layout of the reference's convert_frames of an unfiltered frame (Y, U, V
     back to back: ``[1, 1.5H, W]`` yuvj420p, ``[1, 2H, W]`` yuvj422p,
     ``[3, H, W]`` yuvj444p, ``[H, W, 1]`` gray; see :func:`_native_planes`);
+    ``pix_fmt=None`` with a scale / pad / crop chain returns the same layout
+    of the scaled planes (the chain runs on the frame's own format);
     otherwise RGB per the filter."""
     kwargs.pop("name", None)  # only names the source in FFmpeg demux errors
     _ignore_ffmpeg_configs(kwargs)
@@ -375,8 +416,11 @@ def load_image(
         filter_desc = get_video_filter_desc(pix_fmt=pix_fmt)
     out = parse_image_filter(filter_desc, default_pix_fmt=pix_fmt)
     info = _lib.get_image_info(data)
-    ow, oh = _lib.output_size(info.width, info.height, out)
-    buf = _decode([data], out, cfg, _shape(out, ow, oh), False)
+    if out.pix_fmt == "yuv":  # pix_fmt=None, no format node: the frame's planes
+        shape = _yuv_shape([info], out)
+    else:
+        shape = _shape(out, *_lib.output_size(info.width, info.height, out))
+    buf = _decode([data], out, cfg, shape, False)
     if device_config is None:
         return _to_host(buf)
     return buf

@@ -85,9 +85,19 @@ def _kv(args: str) -> dict:
     return out
 
 
-def parse_image_filter(filter_desc: str | None, default_pix_fmt: str = "rgb24") -> Output:
-    """Translate an image filter chain into an :class:`Output` spec."""
-    spec = dict(pix_fmt=default_pix_fmt, resize=False)
+def _size(kv: dict, key: str, part: str, required: bool = False) -> int:
+    v = int(kv[key] if required else kv.get(key, 0))
+    if v < 0:
+        raise ValueError(f"negative {key} is not valid here: {part}")
+    return v
+
+
+def parse_image_filter(filter_desc: str | None, default_pix_fmt: str | None = "rgb24") -> Output:
+    """Translate an image filter chain into an :class:`Output` spec.
+
+    ``default_pix_fmt=None``: a chain without a ``format`` node keeps the
+    decoder's own planar format (``pix_fmt="yuv"``), as libavfilter does."""
+    spec = dict(pix_fmt=default_pix_fmt or "yuv", resize=False)
     if not filter_desc:
         return Output(**spec)
     have_scale = False
@@ -98,9 +108,8 @@ def parse_image_filter(filter_desc: str | None, default_pix_fmt: str = "rgb24") 
         name, _, args = part.partition("=")
         kv = _kv(args)
         if name == "scale":
+            # (negative sizes: vf_scale's -1 / -n, resolved by the library)
             w, h = int(kv.get("w", 0)), int(kv.get("h", 0))
-            if w < 0 or h < 0:
-                raise ValueError(f"negative scale sizes are not supported: {part}")
             spec.update(resize=True, fit_w=w, fit_h=h)
             flags = kv.get("flags", "bicubic")
             if flags in _NOT_IMPLEMENTED:
@@ -125,11 +134,11 @@ def parse_image_filter(filter_desc: str | None, default_pix_fmt: str = "rgb24") 
                 raise ValueError("only centred pad (x=-1:y=-1) is supported")
             if kv.get("color", "black") != "black":
                 raise ValueError("only color=black is supported")
-            spec.update(resize=True, pad_w=int(kv["w"]), pad_h=int(kv["h"]))
+            spec.update(resize=True, pad_w=_size(kv, "w", part, True), pad_h=_size(kv, "h", part, True))
         elif name == "crop":
             if "x" in kv or "y" in kv:
                 raise ValueError("only centred crop is supported")
-            spec.update(resize=True, crop_w=int(kv.get("w", 0)), crop_h=int(kv.get("h", 0)))
+            spec.update(resize=True, crop_w=_size(kv, "w", part), crop_h=_size(kv, "h", part))
         elif name == "format":
             pf = kv.get("pix_fmts", kv.get("w"))
             if pf not in ("rgb24", "bgr24", "rgb", "bgr"):
