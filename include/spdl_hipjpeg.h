@@ -311,6 +311,36 @@ int spdl_hj_debug_entropy(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
                           size_t coef_cap, uint8_t* clean, size_t clean_cap, int32_t* diag,
                           char* err, size_t errlen);
 
+/* Debug/parity surface (additive in ABI 7; needs no device and no context):
+ * the scale / colour-conversion plan the library makes of one image, as its
+ * decode calls do -- the chain's geometry, then the swscale tables and the
+ * tiling of sws_kernel / yuv_planes_kernel.  The algorithm is libswscale's
+ * (third-party FFmpeg: sws_init_context and initFilter, libswscale/utils.c;
+ * packed_vscale, vscale.c), which runs behind the reference's filter graph
+ * (FilterGraphImpl::filter, src/libspdl/core/detail/ffmpeg/filter_graph.cpp:
+ * 280-313).
+ *   width, height, hsub, vsub  the frame and its chroma shifts (0-2)
+ *   mode     0 YCbCr planes, 1 gray, 2 three RGB planes through the luma filters
+ *   planar   1: the SPDL_HJ_FMT_YUV destination (mode 0 or 1)
+ *   prepass, max_cols  the "sws_prepass" (-1, 0, 1) and "sws_cols" knobs
+ * Returns what a decode call's plan returns (SPDL_HJ_ERR_BAD_GEOMETRY: scale
+ * filter too long, or a refused chain).  info must hold 40 ints:
+ *   [0..4]   special (the unscaled converter), full, gray, gbr, pre
+ *   [5..10]  sw, sh, dx, dy, ow, oh (filled even when the plan is refused)
+ *   [11..14] taps of the hl, hc, vl, vc filters (trailing zeros cut)
+ *   [15..18] their row strides in the tables (taps, multiples of 4)
+ *   [19..22] their row counts
+ *   [23..31] rb, col_chunk, bands, chunks, LDS bytes, pre_rl, pre_rc, chr_w,
+ *            chr_h (planar only)
+ * vmode (optional, sh ints; packed outputs only): the row writers, mode |
+ * yalpha << 4 | uvalpha << 17 with mode 0 X, 1 One, 2 Two.  pos[i] / coef[i]
+ * (optional, i = hl, hc, vl, vc): count[i] positions and count[i] * stride[i]
+ * taps, as shipped to the device; call once without them for the sizes. */
+int spdl_hj_debug_sws_plan(int32_t width, int32_t height, int32_t hsub, int32_t vsub, int32_t mode,
+                           int32_t planar, const spdl_hj_output* out, int32_t prepass,
+                           int32_t max_cols, int32_t* info, int32_t* vmode, int32_t* const* pos,
+                           int16_t* const* coef);
+
 /* Batched NV12 -> planar RGB (bgr == 0) or BGR: src_dev is
  * [num_frames, h2 = 1.5 H, width] u8 in device memory (pitch = width), dst_dev
  * [num_frames, 3, H, width] u8.  matrix_coeff selects the matrix (1 BT.709

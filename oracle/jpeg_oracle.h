@@ -184,6 +184,10 @@ int jo_sws_init(jo_sws* s, int srcW, int srcH, int hsub, int vsub, int gray, int
 void jo_sws_free(jo_sws* s);
 int jo_sws_scale(const jo_sws* s, const uint8_t* const* planes, const int* stride, uint8_t* rgb);
 
+/* Test helper: the whole plan of jo_sws_init (info: 16 ints; see sws_oracle.c). */
+int jo_sws_plan(int srcW, int srcH, int hsub, int vsub, int gray, int dstW, int dstH, int kind,
+                int* info, int32_t* const* pos, int16_t* const* coef);
+
 /* Full-resolution RGB with a chosen colour conversion (JO_CSC_*). */
 int jo_decode_rgb_csc(const uint8_t* data, size_t size, int idct, int csc, int fmt, uint8_t* out);
 

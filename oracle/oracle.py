@@ -274,6 +274,33 @@ def sws_axis(src: int, dst: int, filt: str = "bicubic", align: int = 4, one: int
     return pos, coef[: dst * n].reshape(dst, n)
 
 
+def sws_plan(src_w: int, src_h: int, hsub: int, vsub: int, gray: bool, dst_w: int, dst_h: int,
+             filt: str = "bicubic"):
+    """The whole plan jo_sws_init makes of one geometry, or None when swscale
+    would refuse it (a filter too long): the flags, the chroma sizes and the
+    four filters ``hl``, ``hc``, ``vl``, ``vc`` as ``{"size", "n", "pos",
+    "coef" [n, size]}`` (gray: ``hc`` and ``vc`` are empty)."""
+    L = lib()
+    vp, ip = ctypes.c_void_p, ctypes.c_int
+    L.jo_sws_plan.argtypes = [ip] * 8 + [vp, vp, vp]
+    args = (src_w, src_h, hsub, vsub, int(bool(gray)), dst_w, dst_h, FILTER[filt])
+    info = np.zeros(16, np.int32)
+    if L.jo_sws_plan(*args, info.ctypes.data, None, None):
+        return None
+    size, n = [int(v) for v in info[8:12]], [int(v) for v in info[12:16]]
+    pos = [np.zeros(n[k], np.int32) for k in range(4)]
+    coef = [np.zeros((n[k], size[k]), np.int16) for k in range(4)]
+    pp = (vp * 4)(*[a.ctypes.data for a in pos])
+    cp = (vp * 4)(*[a.ctypes.data for a in coef])
+    if L.jo_sws_plan(*args, info.ctypes.data, pp, cp):
+        raise OracleError(7)
+    plan = dict(zip(("full", "gray", "special", "chrSrcW", "chrSrcH", "chrDstW", "chrDstH"),
+                    (int(v) for v in info[:7])))
+    for k, a in enumerate(("hl", "hc", "vl", "vc")):
+        plan[a] = {"size": size[k], "n": n[k], "pos": pos[k], "coef": coef[k]}
+    return plan
+
+
 def decode_resize(
     data: bytes,
     rs: Resize,

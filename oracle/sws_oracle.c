@@ -353,7 +353,10 @@ int jo_sws_init(jo_sws* s, int srcW, int srcH, int hsub, int vsub, int gray, int
       f[k]->n = n[k];
       f[k]->pos = (int32_t*)malloc(sizeof(int32_t) * (n[k] + 3));
       f[k]->coef = (int16_t*)malloc(sizeof(int16_t) * (n[k] + 3));
-      if (!f[k]->pos || !f[k]->coef) return -1;
+      if (!f[k]->pos || !f[k]->coef) {
+        jo_sws_free(s);
+        return -1;
+      }
       for (int i = 0; i < n[k]; i++) {
         f[k]->pos[i] = k == 3 ? (i >> vsub) : i;
         f[k]->coef[i] = (int16_t)(k < 2 ? 1 << 14 : 1 << 12);
@@ -373,14 +376,18 @@ int jo_sws_init(jo_sws* s, int srcW, int srcH, int hsub, int vsub, int gray, int
   if (jo_sws_init_filter((int)lumXInc, srcW, dstW, 4, 1 << 14, kind, local_pos(0, 0),
                     local_pos(0, 0), &s->hl) ||
       jo_sws_init_filter((int)lumYInc, srcH, dstH, 2, 1 << 12, kind, local_pos(0, 0),
-                    local_pos(0, 0), &s->vl))
+                    local_pos(0, 0), &s->vl)) {
+    jo_sws_free(s);  /* a refused later axis must not leak the earlier ones */
     return -1;
+  }
   if (!gray) {
     if (jo_sws_init_filter((int)chrXInc, s->chrSrcW, s->chrDstW, 4, 1 << 14, kind,
                       local_pos(s->chr_src_hsub, -513), local_pos(chrDstHSub, -513), &s->hc) ||
         jo_sws_init_filter((int)chrYInc, s->chrSrcH, s->chrDstH, 2, 1 << 12, kind,
-                      local_pos(s->chr_src_vsub, -513), local_pos(0, -513), &s->vc))
+                      local_pos(s->chr_src_vsub, -513), local_pos(0, -513), &s->vc)) {
+      jo_sws_free(s);
       return -1;
+    }
   }
   return 0;
 }
@@ -390,6 +397,30 @@ void jo_sws_free(jo_sws* s) {
   jo_sws_filter_free(&s->hc);
   jo_sws_filter_free(&s->vl);
   jo_sws_filter_free(&s->vc);
+}
+
+/* Test helper: the whole plan jo_sws_init makes.  info (16 ints): full, gray,
+ * unscaled_special, chrSrcW, chrSrcH, chrDstW, chrDstH, 0, then the sizes
+ * and the row counts of hl, hc, vl, vc.  pos[i] / coef[i] (optional) receive
+ * n positions and n * size taps.  Returns 0, or -1 when the plan is refused. */
+int jo_sws_plan(int srcW, int srcH, int hsub, int vsub, int gray, int dstW, int dstH, int kind,
+                int* info, int32_t* const* pos, int16_t* const* coef) {
+  jo_sws s;
+  if (srcW <= 0 || srcH <= 0 || dstW <= 0 || dstH <= 0) return -1;
+  if (jo_sws_init(&s, srcW, srcH, hsub, vsub, gray, dstW, dstH, kind)) return -1;
+  const jo_sws_filter* f[4] = {&s.hl, &s.hc, &s.vl, &s.vc};
+  const int head[8] = {s.full, s.gray, s.unscaled_special, s.chrSrcW, s.chrSrcH, s.chrDstW,
+                       s.chrDstH, 0};
+  memcpy(info, head, sizeof(head));
+  for (int k = 0; k < 4; k++) {
+    info[8 + k] = f[k]->size;
+    info[12 + k] = f[k]->n;
+    if (pos && pos[k] && f[k]->n) memcpy(pos[k], f[k]->pos, sizeof(int32_t) * (size_t)f[k]->n);
+    if (coef && coef[k] && f[k]->n)
+      memcpy(coef[k], f[k]->coef, sizeof(int16_t) * (size_t)f[k]->n * f[k]->size);
+  }
+  jo_sws_free(&s);
+  return 0;
 }
 
 /* hScale8To15_c */

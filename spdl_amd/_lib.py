@@ -42,6 +42,7 @@ EXPORTED = (
     "spdl_hj_set_param",
     "spdl_hj_get_param",
     "spdl_hj_debug_entropy",
+    "spdl_hj_debug_sws_plan",
     "spdl_hj_last_ticket",
     "spdl_hj_wait",
     "spdl_hj_staging_acquire",
@@ -268,6 +269,56 @@ def output_size(width: int, height: int, out: Output) -> tuple[int, int]:
     if rc:
         raise RuntimeError(f"invalid output geometry for {width}x{height} ({rc})")
     return ow.value, oh.value
+
+
+PLAN_MODES = {"yuv": 0, "gray": 1, "gbr": 2}
+_PLAN_AXES = ("hl", "hc", "vl", "vc")
+
+
+def debug_sws_plan(width: int, height: int, hsub: int, vsub: int, mode: str, out: Output,
+                   prepass: int = -1, max_cols: int = 256) -> dict:
+    """The scale / colour plan the library makes of a ``width`` x ``height``
+    frame with chroma shifts ``hsub``, ``vsub`` under ``out`` (tests; needs no
+    GPU): ``{"rc": code}`` plus, when the plan is accepted, the flags, the
+    tiling and the four filter tables as the device gets them
+    (spdl_hj_debug_sws_plan, include/spdl_hipjpeg.h).  ``mode``: "yuv", "gray"
+    or "gbr"; ``out.pix_fmt == "yuv"`` selects the planar destination."""
+    import numpy as np
+
+    L = lib()
+    fn = L.spdl_hj_debug_sws_plan  # bound on first use: an older A/B build has no such symbol
+    if fn.argtypes is None:
+        i32, vp = ctypes.c_int32, ctypes.c_void_p
+        fn.argtypes = [i32] * 6 + [ctypes.POINTER(OutputSpec), i32, i32, vp, vp, vp, vp]
+    spec = out.to_c()
+    planar = int(out.pix_fmt == "yuv")
+    info = np.zeros(40, np.int32)
+    args = (int(width), int(height), int(hsub), int(vsub), PLAN_MODES[mode], planar,
+            ctypes.byref(spec), int(prepass), int(max_cols), info.ctypes.data)
+    rc = fn(*args, None, None, None)
+    geo = dict(zip(("sw", "sh", "dx", "dy", "ow", "oh"), (int(v) for v in info[5:11])))
+    if rc:
+        return {"rc": int(rc), **geo}
+    n = [int(v) for v in info[19:23]]
+    stride = [int(v) for v in info[15:19]]
+    pos = [np.zeros(n[i], np.int32) for i in range(4)]
+    coef = [np.zeros((n[i], stride[i]), np.int16) for i in range(4)]
+    vmode = np.zeros(0 if planar else geo["sh"], np.int32)
+    pp = (ctypes.c_void_p * 4)(*[a.ctypes.data for a in pos])
+    cp = (ctypes.c_void_p * 4)(*[a.ctypes.data for a in coef])
+    rc = fn(*args, vmode.ctypes.data, pp, cp)
+    if rc:
+        raise RuntimeError(f"spdl_hj_debug_sws_plan: {rc} on the second call")
+    plan = {"rc": 0, **geo}
+    plan.update(zip(("special", "full", "gray", "gbr", "pre"), (int(v) for v in info[0:5])))
+    plan.update(zip(("rb", "col_chunk", "bands", "chunks", "lds", "pre_rl", "pre_rc", "chr_w",
+                     "chr_h"), (int(v) for v in info[23:32])))
+    plan["planar"] = planar
+    plan["vmode"] = vmode
+    for i, a in enumerate(_PLAN_AXES):
+        plan[a] = {"taps": int(info[11 + i]), "stride": stride[i], "n": n[i], "pos": pos[i],
+                   "coef": coef[i]}
+    return plan
 
 
 def buffer_address(src) -> tuple[int, int, object]:

@@ -434,6 +434,7 @@ struct PackedPlan {
   std::vector<int32_t> blob;    // tables, 16-byte aligned sections
   int bands = 0, chunks = 0, lds = 0;
   bool special = false;         // swscale's unscaled yuv2rgb_c_24_rgb converter
+  int axis_n[4] = {};           // rows of the hl, hc, vl, vc tables (spdl_hj_debug_sws_plan)
 };
 
 // yuv_planes_kernel's LDS of one tile (hj_kernels.hip): the horizontal-pass
@@ -471,6 +472,11 @@ class PlanCache {
     map_.emplace(k, p);
     return p;
   }
+  // one plan outside any cache (spdl_hj_debug_sws_plan)
+  static std::shared_ptr<const PackedPlan> plan(const PlanKey& k, int* rc, int pre_mode,
+                                                int max_cols) {
+    return build(k, rc, pre_mode, max_cols);
+  }
 
  private:
   static void put(std::vector<int32_t>& blob, int32_t* off, const void* data, size_t bytes) {
@@ -504,6 +510,7 @@ class PlanCache {
       // of 4 (the kernel reads taps 4 at a time)
       const SwsAxis& a = *ax[i];
       const int eff = a.eff;
+      pp->axis_n[i] = a.n;
       // horizontal rows: padded to the kernel's register bucket of taps
       // (hpass: 4, 8, 12, 16, 24, 32, 48, 64; longer rows use a plain loop)
       int q = (eff + 3) / 4;
@@ -598,6 +605,7 @@ class PlanCache {
     int32_t* sizes[4] = {&d.hl_size, &d.hc_size, &d.vl_size, &d.vc_size};
     for (int i = 0; i < 4; i++) {  // rows cut and padded as build() does (hpass buckets)
       const SwsAxis& a = *ax[i];
+      pp->axis_n[i] = a.n;
       int q = (a.eff + 3) / 4;
       if (i < 2) q = q <= 4 ? q : q <= 6 ? 6 : q <= 8 ? 8 : q <= 12 ? 12 : q <= 16 ? 16 : q;
       const int stride = 4 * q;
@@ -2118,6 +2126,48 @@ int spdl_hj_debug_entropy(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
     size_t n = (size_t)hi.clean_len < clean_cap ? (size_t)hi.clean_len : clean_cap;
     HJ_HIP(hipMemcpy(clean, W.clean.p, n, hipMemcpyDeviceToHost));
   }
+  return SPDL_HJ_OK;
+}
+
+int spdl_hj_debug_sws_plan(int32_t width, int32_t height, int32_t hsub, int32_t vsub, int32_t mode,
+                           int32_t planar, const spdl_hj_output* out, int32_t prepass,
+                           int32_t max_cols, int32_t* info, int32_t* vmode, int32_t* const* pos,
+                           int16_t* const* coef) {
+  if (!out || !info || mode < kPlanYuv || mode > kPlanGbr || (planar && mode == kPlanGbr) ||
+      hsub < 0 || hsub > 2 || vsub < 0 || vsub > 2 || prepass < -1 || prepass > 1 ||
+      max_cols < 16 || max_cols > kSwsMaxCols)
+    return SPDL_HJ_ERR_INVALID_ARG;
+  memset(info, 0, sizeof(int32_t) * 40);
+  // the key build_layout makes of an image of this size and sampling
+  Geom g;
+  int rc = planar ? geometry(width, height, out, &g, 1 << hsub, 1 << vsub)
+                  : geometry(width, height, out, &g);
+  if (rc) return rc;
+  const PlanKey key{width, height, hsub, vsub, mode | (planar ? kPlanPlanar : 0),
+                    out->resize ? out->filter : 0, g.sw, g.sh, g.dx, g.dy, g.ow, g.oh};
+  const int32_t geo[6] = {g.sw, g.sh, g.dx, g.dy, g.ow, g.oh};
+  memcpy(info + 5, geo, sizeof(geo));
+  auto pp = PlanCache::plan(key, &rc, prepass, max_cols);
+  if (!pp) return rc;
+  const SwsDesc& d = pp->d;
+  const int32_t head[5] = {pp->special, d.full, d.gray, d.gbr, d.pre};
+  memcpy(info, head, sizeof(head));
+  const int32_t taps[4] = {d.hl_taps, d.hc_taps, d.vl_taps, d.vc_taps};
+  const int32_t sizes[4] = {d.hl_size, d.hc_size, d.vl_size, d.vc_size};
+  memcpy(info + 11, taps, sizeof(taps));
+  memcpy(info + 15, sizes, sizeof(sizes));
+  memcpy(info + 19, pp->axis_n, sizeof(pp->axis_n));
+  const int32_t tile[9] = {d.rb, d.col_chunk, pp->bands, pp->chunks, pp->lds,
+                           d.pre_rl, d.pre_rc, d.chr_w, d.chr_h};
+  memcpy(info + 23, tile, sizeof(tile));
+  // the tables as the device gets them: the blob's sections
+  const int32_t* blob = pp->blob.data();
+  for (int i = 0; i < 4; i++) {
+    if (pos && pos[i]) memcpy(pos[i], blob + d.off[2 * i], sizeof(int32_t) * pp->axis_n[i]);
+    if (coef && coef[i])
+      memcpy(coef[i], blob + d.off[2 * i + 1], sizeof(int16_t) * (size_t)pp->axis_n[i] * sizes[i]);
+  }
+  if (vmode && !planar) memcpy(vmode, blob + d.off[kVmode], sizeof(int32_t) * g.sh);
   return SPDL_HJ_OK;
 }
 
