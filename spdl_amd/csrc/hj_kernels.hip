@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include "hj_common.h"
+#include "hj_destuff.h"
 #include "hj_idct.h"
 
 namespace hj {
@@ -603,22 +604,6 @@ __global__ void __launch_bounds__(256) lut_kernel(const uint8_t* __restrict__ by
 // destuff_kernel
 // ---------------------------------------------------------------------------
 
-// Copy `n` bytes LDS -> global with 4-byte stores where the destination is
-// aligned (head / tail bytes singly); all threads of the workgroup take part.
-__device__ __forceinline__ void lds_to_global(uint8_t* __restrict__ dst, const uint8_t* src,
-                                              int n, int tid) {
-  const int head = min(n, (int)((4 - ((uintptr_t)dst & 3)) & 3));
-  if (tid < head) dst[tid] = src[tid];
-  const int nw = (n - head) >> 2;
-  uint32_t* d32 = reinterpret_cast<uint32_t*>(dst + head);
-  for (int i = tid; i < nw; i += 256) {
-    const uint8_t* q = src + head + 4 * i;
-    d32[i] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-  }
-  const int t0 = head + 4 * nw;
-  if (t0 + tid < n) dst[t0 + tid] = src[t0 + tid];
-}
-
 constexpr int kDsThreads = 256;
 constexpr int kDsPer = kDsChunk / kDsThreads;
 
@@ -657,48 +642,75 @@ __device__ __forceinline__ void wg_scan2(int a, int b, int& ea, int& eb, int& ta
   }
 }
 
-// Classify the 16 bytes [j0, j0 + 16) of an entropy-coded segment run
-// (T.81 B.1.1.5, F.1.2.3): keep = data byte (a 0xFF followed by the stuffed
-// 0x00, or any byte not preceded by 0xFF); rst = 0xFF starting an RSTn marker
-// (fill 0xFF allowed before it); *term = first 0xFF starting any other marker
-// (bytes past the file read as 0xD9, EOI).  Bytes before `start` are ignored.
-__device__ __forceinline__ void ds_classify(const uint8_t* __restrict__ d, int size, int start,
-                                            int j0, uint32_t& keep, uint32_t& rst, int& term,
-                                            uint8_t (&b)[18]) {
-  b[0] = j0 > 0 && j0 - 1 < size ? d[j0 - 1] : 0;
+// Wave inclusive scan in six DPP adds: Hillis-Steele inside each row of 16
+// lanes (a shift past the row's start reads 0), then the rows' totals handed
+// on by row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3.
+// Every lane of the wave must be active.
+__device__ __forceinline__ int wave_incl_scan_dpp(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);  // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);  // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);  // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);  // row_shr:8
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31
+  return v;
+}
+
+// Workgroup exclusive scan of one word (the destuff kernels pack two counters
+// in it: rst << 16 | keep, a chunk holds at most 2048 / 4096); also the total.
+__device__ __forceinline__ void wg_scan1(int v, int& ex, int& tot, int* sh /* 4 ints */) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int iv = wave_incl_scan_dpp(v);
+  if (lane == 63) sh[wid] = iv;
+  __syncthreads();
+  ex = iv - v;
+  tot = 0;
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+    if (w < wid) ex += sh[w];
+    tot += sh[w];
+  }
+}
+
+// A thread's group for hj_destuff.h: the 16 bytes [j0, j0 + 16) of file `d` as
+// words, the byte before (0 where there is none) and the byte after; bytes
+// past the file read as 0xD9 (EOI).
+__device__ __forceinline__ void ds_load(const uint8_t* __restrict__ d, int size, int j0,
+                                        uint32_t (&w)[4], uint32_t& prev, uint32_t& next) {
+  prev = ds_prev_byte(d, size, j0);
   if (j0 + 16 <= size) {
     const uint4 q = *reinterpret_cast<const uint4*>(d + j0);
-    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int i = 0; i < 16; i++) b[1 + i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+    w[0] = q.x;
+    w[1] = q.y;
+    w[2] = q.z;
+    w[3] = q.w;
   } else {
-#pragma unroll
-    for (int i = 0; i < 16; i++) b[1 + i] = j0 + i < size ? d[j0 + i] : 0xD9;
+    ds_load_bytes(d, size, j0, w);
   }
-  b[17] = j0 + 16 < size ? d[j0 + 16] : 0xD9;
-  keep = rst = 0;
-  term = 0x7FFFFFFF;
-#pragma unroll
-  for (int i = 0; i < 16; i++) {
-    const int j = j0 + i;
-    if (j < start || j >= size) continue;
-    const bool prev_ff = j > start && b[i] == 0xFF;
-    if (b[1 + i] != 0xFF) {
-      keep |= (uint32_t)!prev_ff << i;
-    } else if (!prev_ff) {
-      if (b[2 + i] == 0x00) {
-        keep |= 1u << i;
-      } else {
-        int k = j + 1;
-        while (k < size && d[k] == 0xFF) k++;
-        if (k < size && d[k] >= 0xD0 && d[k] <= 0xD7) {
-          rst |= 1u << i;
-        } else {
-          term = min(term, j);
-        }
-      }
-    }
-  }
+  next = ds_next_byte(d, size, j0);
+}
+
+// destuff_write_kernel's LDS stage: a chunk's kept bytes at the destination's
+// offset within 16 bytes, so that the copy-out moves 16 bytes at a time
+// (yuv_planes_kernel stages its tiles the same way).  16 bytes of slack in
+// front (a group is stored below its first kept byte by up to 15 zero bytes),
+// 15 of offset and 32 behind.
+constexpr int kDsStageWords = (16 + 16 + kDsChunk + 32) / 4;
+
+// Copy the `n` staged bytes to `dst` (staged from byte 16 + (dst & 15) on):
+// head bytes singly, 16-byte LDS loads and global stores, tail bytes singly.
+__device__ __forceinline__ void stage_to_global(uint8_t* __restrict__ dst, const uint32_t* stage,
+                                                int n, int tid) {
+  const int a = (int)((uintptr_t)dst & 15);
+  const uint8_t* src = reinterpret_cast<const uint8_t*>(stage) + 16 + a;
+  const int head = min(n, (16 - a) & 15);
+  if (tid < head) dst[tid] = src[tid];
+  const int nv = (n - head) >> 4;
+  const uint4* s4 = reinterpret_cast<const uint4*>(src + head);
+  uint4* d4 = reinterpret_cast<uint4*>(dst + head);
+  for (int i = tid; i < nv; i += kDsThreads) d4[i] = s4[i];
+  const int t0 = head + 16 * nv;
+  if (t0 + tid < n) dst[t0 + tid] = src[t0 + tid];
 }
 
 // Destuffing runs as count -> per-image prefix -> write over 4 KB chunks of
@@ -707,8 +719,7 @@ __global__ void __launch_bounds__(kDsThreads) destuff_count_kernel(
     const uint8_t* __restrict__ bytes, const ImageDesc* __restrict__ desc,
     const ImageInfo* __restrict__ infos, DsChunk* __restrict__ chunks,
     const uint32_t* __restrict__ ds_map) {
-  __shared__ int sh[8];
-  __shared__ int shterm;
+  __shared__ int shsum, shterm;
   // (chunk, image) grid, or a flat grid over every image's chunks (ds_map:
   // workgroup -> image) when the batch's sizes differ widely
   const bool flat = ds_map != nullptr;
@@ -719,19 +730,32 @@ __global__ void __launch_bounds__(kDsThreads) destuff_count_kernel(
   const int size = (int)dd.in_size, start = infos[img].scan_start;
   const int cbase = (start & ~15) + k * kDsChunk;
   if (cbase >= size || k >= dd.ds_cap) return;
-  if (tid == 0) shterm = 0x7FFFFFFF;
-  uint32_t keep, rst;
-  int term;
-  uint8_t b[18];
-  ds_classify(bytes + dd.in_off, size, start, cbase + tid * kDsPer, keep, rst, term, b);
-  int ek, er, tk, tr;
-  wg_scan2(__popc(keep), __popc(rst), ek, er, tk, tr, sh);
-  if (term != 0x7FFFFFFF) atomicMin(&shterm, term);
+  if (tid == 0) {
+    shsum = 0;
+    shterm = 0x7FFFFFFF;
+  }
+  __syncthreads();
+  const uint8_t* d = bytes + dd.in_off;
+  const int j0 = cbase + tid * kDsPer;
+  uint32_t w[4], prev, next;
+  ds_load(d, size, j0, w, prev, next);
+  uint32_t slow;
+  int cnt = ds_count_words(w, prev, next, j0, start, size, slow);
+  if (slow) {  // a marker: rare, at most one per image besides RSTn
+    uint32_t rst;
+    int term;
+    ds_resolve(d, size, j0, slow, rst, term);
+    cnt += __popc(rst) << 16;
+    if (term != 0x7FFFFFFF) atomicMin(&shterm, term);
+  }
+  // rst << 16 | keep: at most 2048 and 4096 per chunk
+  const int wsum = wave_incl_scan_dpp(cnt);
+  if ((tid & 63) == 63) atomicAdd(&shsum, wsum);
   __syncthreads();
   if (tid == 0) {
     DsChunk& c = chunks[dd.ds_off + k];
-    c.keep = tk;
-    c.rst = tr;
+    c.keep = shsum & 0xFFFF;
+    c.rst = shsum >> 16;
     c.term = shterm;
   }
 }
@@ -776,8 +800,8 @@ __global__ void __launch_bounds__(kDsThreads) destuff_write_kernel(
     const uint8_t* __restrict__ bytes, const ImageDesc* __restrict__ desc,
     ImageInfo* __restrict__ infos, const DsChunk* __restrict__ chunks, uint8_t* __restrict__ clean,
     uint32_t* __restrict__ segs, const uint32_t* __restrict__ ds_map) {
-  __shared__ int sh[8];
-  __shared__ __attribute__((aligned(16))) uint8_t ob[kDsChunk];
+  __shared__ int sh[4];
+  __shared__ __attribute__((aligned(16))) uint32_t stage[kDsStageWords];
   const bool flat = ds_map != nullptr;
   const int img = flat ? (int)ds_map[blockIdx.x] : (int)blockIdx.y;
   const int k = flat ? (int)blockIdx.x - desc[img].ds_wg0 : (int)blockIdx.x, tid = threadIdx.x;
@@ -789,41 +813,57 @@ __global__ void __launch_bounds__(kDsThreads) destuff_write_kernel(
   // the chunk holding the last scan byte also finishes the image
   const int last = (max(end - 1, start) - base) / kDsChunk;
   if (k > last || k >= dd.ds_cap) return;
+  for (int i = tid; i < kDsStageWords / 4; i += kDsThreads)
+    reinterpret_cast<uint4*>(stage)[i] = make_uint4(0, 0, 0, 0);
+  const uint8_t* d = bytes + dd.in_off;
   const int j0 = cbase + tid * kDsPer;
-  uint32_t keep, rst;
-  int term;
-  uint8_t b[18];  // b[1 + i] = byte j0 + i (classified and compacted from registers)
-  ds_classify(bytes + dd.in_off, size, start, j0, keep, rst, term, b);
-  const int lim = end - j0;  // bytes at or past the scan end are not part of it
-  const uint32_t m = lim >= 16 ? 0xFFFFu : (lim <= 0 ? 0u : ((1u << lim) - 1u));
-  keep &= m;
-  rst &= m;
-  int ek, er, tk, tr;
-  wg_scan2(__popc(keep), __popc(rst), ek, er, tk, tr, sh);
+  uint32_t w[4], prev, next;
+  ds_load(d, size, j0, w, prev, next);
+  // bytes at or past the scan end are not part of it
+  const DsMasks m = ds_classify_words(w, prev, next, j0, start, end);
+  const uint32_t keep = m.keep;
+  uint32_t rst = 0;
+  if (m.slow) {
+    int term;
+    ds_resolve(d, size, j0, m.slow, rst, term);
+  }
+  int ex, tot;
+  wg_scan1((int)(__popc(rst) << 16 | __popc(keep)), ex, tot, sh);  // syncs: the stage is zero
+  const int ek = ex & 0xFFFF, er = ex >> 16, tk = tot & 0xFFFF, tr = tot >> 16;
   const DsChunk& c = chunks[dd.ds_off + k];
   uint32_t* sg = segs + dd.seg_off;
-  // compact this thread's kept bytes; RSTn markers record segment starts
-  {
-    int o = ek, r = c.rst_pre + er;
+  if (rst) {  // RSTn markers record segment starts
+    int r = c.rst_pre + er;
     bool overflow = false;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      if (keep >> i & 1u) {
-        ob[o++] = b[1 + i];
-      } else if (rst >> i & 1u) {
-        r++;
-        if (r < dd.seg_cap) sg[r] = (uint32_t)(c.keep_pre + o);
-        else overflow = true;
-      }
+    for (uint32_t q = rst; q; q &= q - 1) {
+      const int i = ds_ctz(q);
+      r++;
+      if (r < dd.seg_cap) sg[r] = (uint32_t)(c.keep_pre + ek + __popc(keep & ((1u << i) - 1u)));
+      else overflow = true;
     }
     if (overflow) infos[img].status = kErrBadRestart;
   }
+  uint8_t* out = clean + dd.in_off + c.keep_pre;
+  // compact the kept bytes in registers: one step per dropped byte, as many
+  // steps as the wave's worst group needs (one or two on ordinary scans)
+  uint32_t drop;
+  ds_compact_begin(w, keep, drop);
+  while (__any(drop != 0u)) ds_compact_step(w, drop);
+  if (keep) {
+    // the kept bytes start at register byte ctz(keep), zeros below and above:
+    // shift the group to its byte offset in the stage and OR the five words in
+    const int p = 16 + (int)((uintptr_t)out & 15) + ek - ds_ctz(keep);
+    uint32_t x[5];
+    ds_shift_words(w, (uint32_t)(p & 3), x);
+    uint32_t* q = stage + (p >> 2);
+#pragma unroll
+    for (int i = 0; i < 5; i++) atomicOr(q + i, x[i]);
+  }
   __syncthreads();
-  uint8_t* out = clean + dd.in_off;
-  lds_to_global(out + c.keep_pre, ob, tk, tid);
+  stage_to_global(out, stage, tk, tid);
   if (k == last) {
     const int clen = c.keep_pre + tk;
-    if (tid < 64) out[clen + tid] = 0;  // zero padding past the data
+    if (tid < 64) out[tk + tid] = 0;  // zero padding past the data
     if (tid == 0) {
       infos[img].clean_len = clen;
       infos[img].nseg = min(c.rst_pre + tr + 1, dd.seg_cap);
