@@ -4866,12 +4866,26 @@ __global__ void __launch_bounds__(256) csc_kernel(const uint8_t* __restrict__ pl
 // then pad (black) / crop, optional (x/255 - mean)/std, stores in the
 // caller's layout.  Workgroup = (band of output rows, chunk of output
 // columns, image).  The band's source rows are scaled horizontally into LDS
-// (hScale8To15: one thread per column, taps in registers, v_dot2 on int16
-// pairs), then each output pixel runs the vertical taps and the RGB24 writer
-// swscale picks for its row (yuv2rgb_{X,2,1}_c table path or the _full_
-// path, libswscale/output.c).  Tables come from the host plan (hj_sws.cpp);
+// (hScale8To15: one thread per column, taps in registers as lo / hi bytes,
+// v_dot4 on the source bytes), then each output pixel runs the vertical taps
+// and the RGB24 writer swscale picks for its row (yuv2rgb_{X,2,1}_c table
+// path, a pixel pair per work item, or the _full_ path, libswscale/output.c).  Tables come from the host plan (hj_sws.cpp);
 // arithmetic: oracle/sws_oracle.c.
 // ---------------------------------------------------------------------------
+
+// A/B switches of the output stage's arithmetic (make variant DEFS=-DHJ_SWS_...=0
+// builds the earlier form): the pad as rectangles instead of a scan of the
+// tile, one pixel pair per work item on the table path, v_dot4 in the
+// horizontal pass
+#ifndef HJ_SWS_PADRECT
+#define HJ_SWS_PADRECT 1
+#endif
+#ifndef HJ_SWS_PAIRS
+#define HJ_SWS_PAIRS 1
+#endif
+#ifndef HJ_SWS_DOT4
+#define HJ_SWS_DOT4 1
+#endif
 
 typedef short hj_short2 __attribute__((ext_vector_type(2)));
 // 16-byte vector load from a 4-byte aligned address (gfx950 global loads
@@ -4910,6 +4924,35 @@ __device__ __forceinline__ int32_t hdot(const uint32_t (&w)[NW], uint32_t sh, co
   return h;
 }
 
+// The same sum with v_dot4 on the bytes themselves, no widening: a tap splits
+// as 256 * hi + lo (lo 0..255, hi -128..127: any int16 tap), and with
+// p' = p ^ 0x80 = p - 128 as a signed byte
+//   sum p * tap = udot4(p, lo) + 256 * (sdot4(p', hi) + 128 * sum hi)
+// modulo 2^32, which is what the v_dot2 sum is too.  wp[2i] holds the lo
+// bytes of taps 4i .. 4i + 3, wp[2i + 1] the hi bytes; k0 = 128 * sum hi.
+// 4 taps: 1 align + 1 xor + 2 dot4 against 1 align + 2 perm + 2 dot2.
+template <int NQ, int NW>
+__device__ __forceinline__ int32_t hdot4(const uint32_t (&w)[NW], uint32_t sh, const uint32_t* wp,
+                                         int32_t k0) {
+  uint32_t a = 0;
+  int32_t b = k0;
+#pragma unroll
+  for (int i = 0; i < NQ; i++) {
+    const uint32_t u = __builtin_amdgcn_alignbyte(w[i + 1], w[i], sh);
+    a = __builtin_amdgcn_udot4(u, wp[2 * i], a, false);
+    b = __builtin_amdgcn_sdot4((int32_t)(u ^ 0x80808080u), (int32_t)wp[2 * i + 1], b, false);
+  }
+  return (int32_t)(a + ((uint32_t)b << 8));
+}
+
+// the taps 4k .. 4k + 3 of a table row (int16 x4) as hdot4's lo and hi words;
+// returns the sum of the four hi bytes
+__device__ __forceinline__ int32_t split_taps(uint2 t, uint32_t& lo, uint32_t& hi, int32_t sum) {
+  lo = __builtin_amdgcn_perm(t.y, t.x, 0x06040200u);
+  hi = __builtin_amdgcn_perm(t.y, t.x, 0x07050301u);
+  return __builtin_amdgcn_sdot4((int32_t)hi, 0x01010101, sum, false);
+}
+
 __device__ __forceinline__ int16_t h15(int32_t h) {  // hScale8To15: (sum >> 7), capped
   return (int16_t)min(h >> 7, (1 << 15) - 1);
 }
@@ -4933,12 +4976,19 @@ __device__ __forceinline__ void hpass_cols(const uint8_t* plane, int stride, int
     const uint32_t sh = (uint32_t)(p & 3);
     uint32_t wp[2 * NQ];
     const uint2* cp = reinterpret_cast<const uint2*>(coef + (int64_t)x * cstride);
+#if HJ_SWS_DOT4
+    int32_t k0 = 0;  // 128 * the sum of the taps' hi bytes (hdot4)
+#pragma unroll
+    for (int k = 0; k < NQ; k++) k0 = split_taps(cp[k], wp[2 * k], wp[2 * k + 1], k0);
+    k0 <<= 7;
+#else
 #pragma unroll
     for (int k = 0; k < NQ; k++) {
       const uint2 t = cp[k];
       wp[2 * k] = t.x;
       wp[2 * k + 1] = t.y;
     }
+#endif
     const uint8_t* base = plane + (p & ~3);
     int16_t* out = lds + c * cst;
     // rows in groups of G: the G loads are issued back to back, so one
@@ -4951,7 +5001,11 @@ __device__ __forceinline__ void hpass_cols(const uint8_t* plane, int stride, int
         if (r + g < r1) load_words<NW>(base + (int64_t)min(r + g, ph - 1) * stride, w[g]);
 #pragma unroll
       for (int g = 0; g < G; g++)
+#if HJ_SWS_DOT4
+        if (r + g < r1) out[(r + g - r0) * rst] = h15(hdot4<NQ>(w[g], sh, wp, k0));
+#else
         if (r + g < r1) out[(r + g - r0) * rst] = h15(hdot<NQ>(w[g], sh, wp));
+#endif
     }
   }
 }
@@ -5017,6 +5071,34 @@ __device__ __forceinline__ int32_t vdot_pairs(const uint32_t* col, int p, const 
     w0 = w2;
   }
   return acc;
+}
+
+// two columns against the same taps (the two pixels of a pair, or U and V):
+// each tap pair is read once
+__device__ __forceinline__ void vdot_pairs2(const uint32_t* col0, const uint32_t* col1, int p,
+                                            const uint32_t* f, int np, int32_t& acc0,
+                                            int32_t& acc1) {
+  const uint32_t* c0 = col0 + (p >> 1);
+  const uint32_t* c1 = col1 + (p >> 1);
+  const uint32_t sh = (uint32_t)(p & 1) * 16u;
+  int32_t a0 = 0, a1 = 0;
+  uint32_t x0 = c0[0], y0 = c1[0];
+  for (int i = 0; i < np; i += 2) {
+    const uint32_t x1 = c0[i + 1], x2 = c0[i + 2], y1 = c1[i + 1], y2 = c1[i + 2];
+    const uint2 ff = *reinterpret_cast<const uint2*>(f + i);
+    a0 = __builtin_amdgcn_sdot2(__builtin_bit_cast(hj_short2, __builtin_amdgcn_alignbit(x1, x0, sh)),
+                                __builtin_bit_cast(hj_short2, ff.x), a0, false);
+    a1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(hj_short2, __builtin_amdgcn_alignbit(y1, y0, sh)),
+                                __builtin_bit_cast(hj_short2, ff.x), a1, false);
+    a0 = __builtin_amdgcn_sdot2(__builtin_bit_cast(hj_short2, __builtin_amdgcn_alignbit(x2, x1, sh)),
+                                __builtin_bit_cast(hj_short2, ff.y), a0, false);
+    a1 = __builtin_amdgcn_sdot2(__builtin_bit_cast(hj_short2, __builtin_amdgcn_alignbit(y2, y1, sh)),
+                                __builtin_bit_cast(hj_short2, ff.y), a1, false);
+    x0 = x2;
+    y0 = y2;
+  }
+  acc0 = a0;
+  acc1 = a1;
 }
 
 // rows p and p + 1 of a column as (lo, hi) int16
@@ -5221,10 +5303,9 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
       vt[i] = v;
     }
   }
-  auto put = [&](int xo, int yo, const int* rgb) {
-    // (selects, not a dynamically indexed array: that would live in scratch)
-    const int c0v = swap ? rgb[2] : rgb[0], c2v = swap ? rgb[0] : rgb[2];
-    const int cv[3] = {c0v, rgb[1], c2v};
+  // one pixel, its three values in the output's channel order
+  auto putc = [&](int xo, int yo, int c0v, int c1v, int c2v) {
+    const int cv[3] = {c0v, c1v, c2v};
     if (u8) {
 #pragma unroll
       for (int ch = 0; ch < 3; ch++) {
@@ -5246,7 +5327,58 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
       static_cast<uint16_t*>(out)[oi] = to_f16_bits(f, p.dtype);
     }
   };
+  auto put = [&](int xo, int yo, const int* rgb) {
+    // (selects, not a dynamically indexed array: that would live in scratch)
+    putc(xo, yo, swap ? rgb[2] : rgb[0], rgb[1], swap ? rgb[0] : rgb[2]);
+  };
   // pad: tile pixels outside the scaled image are black
+#if HJ_SWS_PADRECT
+  {
+    // the content's rows and columns in output coordinates (no content: every
+    // row of the tile counts as above it).  A tile of content alone has
+    // nothing to fill; otherwise the pad is at most four rectangles: the rows
+    // above and below, the columns left and right of the content rows.
+    const int cy0 = content ? ys0 + dd.dy : yo1, cy1 = content ? ys1 + dd.dy : yo1;
+    const int cxa = xs0 + dd.dx, cxb = xs1 + dd.dx;
+    if (cy0 > yo0 || cy1 < yo1 || cxa > xo0 || cxb < xo1) {
+      const int lane = tid & 63, nw = nt >> 6;
+      const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+      // bytes [off, off + n) of the u8 tile, thread t of nth: words where
+      // the run is aligned, single bytes at its ends
+      auto zrun = [&](int off, int n, int t, int nth) {
+        const int head = min(n, -off & 3), words = (n - head) >> 2;
+        const int tail = n - head - 4 * words;
+        uint8_t* q = tile + off + head;
+        if (t < head) tile[off + t] = 0;
+        for (int i = t; i < words; i += nth) reinterpret_cast<uint32_t*>(q)[i] = 0u;
+        if (t < tail) q[4 * words + t] = 0;
+      };
+      // rows [ya, yb) x columns [xa, xb)
+      auto fill = [&](int ya, int yb, int xa, int xb) {
+        if (ya >= yb || xa >= xb) return;
+        if (!u8) {  // straight to the output: a row per wave at a time
+          for (int yo = ya + wave; yo < yb; yo += nw)
+            for (int xo = xa + lane; xo < xb; xo += 64) putc(xo, yo, 0, 0, 0);
+          return;
+        }
+        const int bpp = planar ? 1 : 3, np_ = planar ? 3 : 1;
+        const int ps = th * tw;  // bytes of a planar tile's plane
+        if (xb - xa == tw) {     // whole rows: one run per plane
+          for (int pc = 0; pc < np_; pc++)
+            zrun((pc * ps + (ya - yo0) * tw) * bpp, (yb - ya) * tw * bpp, tid, nt);
+          return;
+        }
+        for (int yo = ya + wave; yo < yb; yo += nw)
+          for (int pc = 0; pc < np_; pc++)
+            zrun((pc * ps + (yo - yo0) * tw + (xa - xo0)) * bpp, (xb - xa) * bpp, lane, 64);
+      };
+      fill(yo0, cy0, xo0, xo1);
+      fill(cy1, yo1, xo0, xo1);
+      fill(cy0, cy1, xo0, cxa);
+      fill(cy0, cy1, cxb, xo1);
+    }
+  }
+#else
   {
     const int npx = th * tw;
     const int zero[3] = {0, 0, 0};
@@ -5256,6 +5388,7 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
       if (ys < 0 || ys >= s.sh || xs < 0 || xs >= s.sw) put(xo, yo, zero);
     }
   }
+#endif
   if (content && s.pre) {
     // the horizontal pass was run once per source row by hscale_kernel
     // (large downscales): copy the band's rows into the column-major LDS
@@ -5314,7 +5447,90 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
     }
   }
   __syncthreads();
-  if (content && !(p.debug_mask & 0x200)) {
+#if HJ_SWS_PAIRS
+  const bool pairs = !s.full && !s.gbr && !s.gray;
+#else
+  const bool pairs = false;
+#endif
+  if (content && pairs && !(p.debug_mask & 0x200)) {
+    // The table writers (yuv2rgb_{X,2,1}_c) share one U, V between the two
+    // pixels of a chroma column: a work item owns chroma column cx0 + cc and
+    // those of luma columns 2 (cx0 + cc), + 1 that lie in [xs0, xs1) -- a
+    // tile may begin or end in the middle of a pair.  U, V and their four
+    // table offsets once, Y and the clips per pixel.  A wave works on one
+    // output row at a time (its header is wave-uniform: scalar mode tests
+    // and row offsets); the (row, 64 pairs) units go round the waves.
+    const int npl = s.vl_size / 2, npc = s.vc_size / 2;  // tap pairs per row
+    const int lane = tid & 63, nw = nt >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nch = (ncc + 63) >> 6, nrows = ys1 - ys0;
+    int r = 0, chk = wave;
+    while (chk >= nch) {
+      chk -= nch;
+      r++;
+    }
+    while (r < nrows) {
+      const uint32_t* row = vt + r * vrw;
+      const uint4 hdr = *reinterpret_cast<const uint4*>(row);
+      const int m = (int)hdr.x;
+      const int lp = (int)hdr.y, cp = (int)hdr.z;
+      const int mode = m & 15, ya = (m >> 4) & 8191, ua = (m >> 17) & 8191;
+      const uint32_t* lf = row + 4;  // luma tap pairs, then chroma
+      const uint32_t* cf = lf + npl;
+      const int cc = chk * 64 + lane;
+      if (cc < ncc) {
+        const int xe = 2 * (cx0 + cc) - xs0;  // the even pixel's column in the tile, -1: not ours
+        const bool h0 = xe >= 0, h1 = xe + 1 < ncl;
+        const uint32_t* l0 = reinterpret_cast<const uint32_t*>(hl + max(xe, 0) * lst);
+        const uint32_t* l1 = reinterpret_cast<const uint32_t*>(hl + min(xe + 1, ncl - 1) * lst);
+        const uint32_t* ucol = reinterpret_cast<const uint32_t*>(hu + cc * cst);
+        const uint32_t* vcol = reinterpret_cast<const uint32_t*>(hv + cc * cst);
+        int Y0, Y1, U, V;
+        if (mode == kSwsX) {
+          int32_t a0, a1;
+          vdot_pairs2(l0, l1, lp, lf, npl, a0, a1);
+          Y0 = ((1 << 18) + a0) >> 19;
+          Y1 = ((1 << 18) + a1) >> 19;
+          vdot_pairs2(ucol, vcol, cp, cf, npc, a0, a1);
+          U = ((1 << 18) + a0) >> 19;
+          V = ((1 << 18) + a1) >> 19;
+        } else {
+          int y00, y01, y10, y11, u0, u1, v0, v1;
+          vpair(l0, lp, y00, y01);
+          vpair(l1, lp, y10, y11);
+          vpair(ucol, cp, u0, u1);
+          vpair(vcol, cp, v0, v1);
+          if (mode == kSwsTwo) {
+            Y0 = (y00 * (4096 - ya) + y01 * ya) >> 19;
+            Y1 = (y10 * (4096 - ya) + y11 * ya) >> 19;
+            U = (u0 * (4096 - ua) + u1 * ua) >> 19;
+            V = (v0 * (4096 - ua) + v1 * ua) >> 19;
+          } else {
+            if (!ua) {
+              u1 = u0;
+              v1 = v0;
+            }
+            Y0 = (y00 + 64) >> 7;
+            Y1 = (y10 + 64) >> 7;
+            U = (u0 * (4096 - ua) + u1 * ua + (128 << 11)) >> 19;
+            V = (v0 * (4096 - ua) + v1 * ua + (128 << 11)) >> 19;
+          }
+        }
+        // the chroma terms of the first and last channel swap with the channels
+        const int tr = tab_off(p.crv, V), tb = tab_off(p.cbu, U);
+        const int t0 = swap ? tb : tr, t2 = swap ? tr : tb;
+        const int t1 = tab_off(p.cgu, U) + tab_off(p.cgv, V);
+        const int yo = ys0 + r + dd.dy, xo = xs0 + xe + dd.dx;
+        if (h0) putc(xo, yo, clip_i8(Y0 + t0), clip_i8(Y0 + t1), clip_i8(Y0 + t2));
+        if (h1) putc(xo + 1, yo, clip_i8(Y1 + t0), clip_i8(Y1 + t1), clip_i8(Y1 + t2));
+      }
+      chk += nw;
+      while (chk >= nch) {
+        chk -= nch;
+        r++;
+      }
+    }
+  } else if (content && !(p.debug_mask & 0x200)) {
     // vertical taps + RGB24 writer, one scaled column per thread
     const int npl = s.vl_size / 2, npc = s.vc_size / 2;  // tap pairs per row
     for (int cl = tid; cl < ncl; cl += nt) {
