@@ -212,11 +212,11 @@ struct ImageDesc {      // host-filled per image
   int32_t pad_;
 };
 
-// sws_kernel LDS budget per workgroup (bytes): the horizontal-pass columns of
-// a band (int16 luma + two chroma planes), the u8 output tile and the band's
-// vertical tables; the host picks the tallest band that fits.  32 KiB: the
-// 2-lane schedule runs 3.6 % faster than at 48 KiB (smaller bands leave room
-// for the other lane's workgroups; r02 A/B, 24 and 64 KiB slower)
+// sws_kernel LDS budget per workgroup (bytes) for what hj_sws_tile.h
+// sws_lds_layout lays out: a band's horizontal-pass columns, the u8 output
+// tile and the vertical tables; the host picks the tallest band that fits.
+// 32 KiB: the 2-lane schedule runs 3.6 % faster than at 48 KiB (smaller bands
+// leave room for the other lane's workgroups; r02 A/B, 24 and 64 KiB slower)
 #ifndef HJ_SWS_LDS_KB
 #define HJ_SWS_LDS_KB 32
 #endif

@@ -21,7 +21,6 @@
 #include <functional>
 #include <map>
 #include <memory>
-#include <tuple>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -30,6 +29,7 @@
 #include "../../include/spdl_hipjpeg.h"
 #include "hj_common.h"
 #include "hj_sws.h"
+#include "hj_sws_tile.h"
 
 namespace hj {
 hipError_t launch_parse(const uint8_t*, const ImageDesc*, ImageDesc*, ImageInfo*, HuffTable*,
@@ -416,265 +416,6 @@ int geometry(int w, int h, const spdl_hj_output* o, Geom* g, int hs = 1, int vs 
   return SPDL_HJ_OK;
 }
 
-// ---- swscale plans (hj_sws.h), packed for the device ----------------------
-// One per distinct (source size, sampling, output placement, filter); cached
-// per context so a stream of same-size images plans once.
-enum { kPlanYuv = 0, kPlanGray = 1, kPlanGbr = 2 };  // source planes of a plan
-constexpr int kPlanPlanar = 4;  // | kPlanYuv / kPlanGray: the planar destination (SPDL_HJ_FMT_YUV)
-struct PlanKey {
-  int w, h, hsub, vsub, mode, filter, sw, sh, dx, dy, ow, oh;
-  bool operator<(const PlanKey& o) const {
-    return std::tie(w, h, hsub, vsub, mode, filter, sw, sh, dx, dy, ow, oh) <
-           std::tie(o.w, o.h, o.hsub, o.vsub, o.mode, o.filter, o.sw, o.sh, o.dx, o.dy, o.ow, o.oh);
-  }
-};
-
-struct PackedPlan {
-  SwsDesc d{};                  // offsets relative to the blob
-  std::vector<int32_t> blob;    // tables, 16-byte aligned sections
-  int bands = 0, chunks = 0, lds = 0;
-  bool special = false;         // swscale's unscaled yuv2rgb_c_24_rgb converter
-  int axis_n[4] = {};           // rows of the hl, hc, vl, vc tables (spdl_hj_debug_sws_plan)
-};
-
-// yuv_planes_kernel's LDS of one tile (hj_kernels.hip): the horizontal-pass
-// columns, then the u8 tile with room to sit at its destination's alignment
-inline int64_t planar_tile_lds(int ncols, int rows, int rb, int chunk) {
-  const int64_t h = (2 * (int64_t)ncols * sws_col_stride(rows) + 15) & ~(int64_t)15;
-  return h + (int64_t)rb * ((chunk + 30) & ~15) + 16;
-}
-
-class PlanCache {
- public:
-  // the horizontal pass of large downscales in hscale_kernel (SwsDesc::pre):
-  // -1 when the vertical ratio is >= kPreRatio or the luma filter is longer
-  // than the kernel's register buckets (64 taps), 0 never, 1 always
-  // (spdl_hj_set_param "sws_prepass"; outputs are identical)
-  static constexpr int kPreRatio = 4;
-  void set_pre_mode(int m) {
-    if (m != pre_mode_) map_.clear();
-    pre_mode_ = m;
-  }
-  int pre_mode() const { return pre_mode_; }
-  // widest column chunk a tile may take (16-256; the tiler then picks the
-  // tallest band that fits the LDS budget)
-  void set_max_cols(int c) {
-    if (c != max_cols_) map_.clear();
-    max_cols_ = c;
-  }
-  int max_cols() const { return max_cols_; }
-  std::shared_ptr<const PackedPlan> get(const PlanKey& k, int* rc) {
-    auto it = map_.find(k);
-    if (it != map_.end()) return it->second;
-    auto p = build(k, rc, pre_mode_, max_cols_);
-    if (!p) return nullptr;
-    if (map_.size() >= 512) map_.clear();  // bounded: a stream of odd sizes replans
-    map_.emplace(k, p);
-    return p;
-  }
-  // one plan outside any cache (spdl_hj_debug_sws_plan)
-  static std::shared_ptr<const PackedPlan> plan(const PlanKey& k, int* rc, int pre_mode,
-                                                int max_cols) {
-    return build(k, rc, pre_mode, max_cols);
-  }
-
- private:
-  static void put(std::vector<int32_t>& blob, int32_t* off, const void* data, size_t bytes) {
-    *off = (int32_t)blob.size();
-    const size_t words = (bytes + 3) / 4;
-    blob.resize(blob.size() + ((words + 3) & ~(size_t)3), 0);
-    if (bytes) memcpy(blob.data() + *off, data, bytes);
-  }
-
-  static std::shared_ptr<const PackedPlan> build(const PlanKey& k, int* rc, int pre_mode,
-                                                 int max_cols) {
-    if (k.mode & kPlanPlanar) return build_planar(k, rc, pre_mode, max_cols);
-    SwsPlan pl;
-    // gbr: the luma plan (gray) applied to each of the three RGB planes
-    *rc = sws_plan(k.w, k.h, k.hsub, k.vsub, k.mode != kPlanYuv, k.sw, k.sh, k.filter, &pl);
-    if (*rc) return nullptr;
-    auto pp = std::make_shared<PackedPlan>();
-    pp->special = pl.special && k.dx == 0 && k.dy == 0 && k.ow == k.sw && k.oh == k.sh;
-    SwsDesc& d = pp->d;
-    d.sw = k.sw;
-    d.sh = k.sh;
-    d.chr_w = pl.chrDstW;
-    d.full = pl.full;
-    d.gray = pl.gray;
-    d.gbr = k.mode == kPlanGbr;
-    const SwsAxis* ax[4] = {&pl.hl, &pl.hc, &pl.vl, &pl.vc};
-    int32_t* taps[4] = {&d.hl_taps, &d.hc_taps, &d.vl_taps, &d.vc_taps};
-    int32_t* sizes[4] = {&d.hl_size, &d.hc_size, &d.vl_size, &d.vc_size};
-    for (int i = 0; i < 4; i++) {
-      // rows cut to the taps that are ever non-zero, padded to a multiple
-      // of 4 (the kernel reads taps 4 at a time)
-      const SwsAxis& a = *ax[i];
-      const int eff = a.eff;
-      pp->axis_n[i] = a.n;
-      // horizontal rows: padded to the kernel's register bucket of taps
-      // (hpass: 4, 8, 12, 16, 24, 32, 48, 64; longer rows use a plain loop)
-      int q = (eff + 3) / 4;
-      if (i < 2) q = q <= 4 ? q : q <= 6 ? 6 : q <= 8 ? 8 : q <= 12 ? 12 : q <= 16 ? 16 : q;
-      const int stride = 4 * q;
-      *taps[i] = eff;
-      *sizes[i] = stride;
-      std::vector<int16_t> rows((size_t)a.n * stride, 0);
-      for (int r = 0; r < a.n; r++)
-        for (int t = 0; t < eff; t++) rows[(size_t)r * stride + t] = a.coef[(size_t)r * a.size + t];
-      put(pp->blob, &d.off[2 * i], a.pos.data(), a.pos.size() * 4);
-      put(pp->blob, &d.off[2 * i + 1], rows.data(), rows.size() * 2);
-    }
-    put(pp->blob, &d.off[kVmode], pl.vmode.data(), pl.vmode.size() * 4);
-    // source rows the vertical filters reach (first tap + taps, max over rows)
-    auto reach = [](const SwsAxis& a) {
-      int r = 0;
-      for (int y = 0; y < a.n; y++) r = std::max(r, a.pos[y] + a.eff);
-      return r;
-    };
-    d.pre = pre_mode > 0 ||
-            (pre_mode < 0 && !pp->special && (k.h >= kPreRatio * k.sh || pl.hl.eff > 64));
-    d.pre_rl = d.pre ? reach(pl.vl) : 0;
-    d.pre_rc = d.pre && !pl.gray ? reach(pl.vc) : 0;
-    // tiling: the tallest band (and widest column chunk) whose horizontal
-    // pass rows (+ 4 slack rows) and u8 output tile fit the LDS budget;
-    // bands are in output rows
-    for (int cols = std::min(max_cols, kSwsMaxCols); cols >= 16 && !pp->bands; cols /= 2) {
-      const int chunk = k.ow < cols ? k.ow : cols;
-      static const int kRb[] = {32, 24, 16, 12, 8, 6, 4, 3, 2, 1};
-      for (int rb : kRb) {
-        int64_t lds = 0;
-        for (int yo0 = 0; yo0 < k.oh; yo0 += rb) {
-          const int ys0 = std::max(yo0 - k.dy, 0), ys1 = std::min(yo0 + rb - k.dy, k.sh);
-          if (ys0 >= ys1) continue;
-          const int64_t lrows = pl.vl.pos[ys1 - 1] + pl.vl.eff - pl.vl.pos[ys0];
-          const int64_t crows = pl.gray ? 0 : pl.vc.pos[ys1 - 1] + pl.vc.eff - pl.vc.pos[ys0];
-          for (int xo0 = 0; xo0 < k.ow; xo0 += chunk) {
-            const int xs0 = std::max(xo0 - k.dx, 0), xs1 = std::min(xo0 + chunk - k.dx, k.sw);
-            if (xs0 >= xs1) continue;
-            const int64_t ncl = xs1 - xs0;
-            const int64_t ncc = pl.gray ? 0 : pl.full ? ncl : ((xs1 - 1) >> 1) - (xs0 >> 1) + 1;
-            const int64_t h = 2 * ((d.gbr ? 3 : 1) * ncl * sws_col_stride((int)lrows) +
-                                   (pl.gray ? 0 : 2 * ncc * sws_col_stride((int)crows)));
-            lds = std::max(lds, (h + 15) & ~(int64_t)15);
-          }
-        }
-        // + the u8 output tile and the band's staged vertical tables
-        const int64_t tile = (((int64_t)rb * chunk * 3 + 15) & ~(int64_t)15) +
-                             (int64_t)rb * (16 + 2 * (d.vl_size + d.vc_size));
-        // (the launch's LDS is the batch's largest plan's: a plan over the
-        // budget slows every image's tiles; only a one-row band of a plan
-        // without the hscale pre-pass may exceed it)
-        if (lds + tile <= kSwsLdsBudget || (!d.pre && rb == 1 && lds + tile <= 64 * 1024)) {
-          d.rb = rb;
-          d.col_chunk = chunk;
-          pp->lds = (int)(lds + tile);
-          pp->bands = (k.oh + rb - 1) / rb;
-          pp->chunks = (k.ow + chunk - 1) / chunk;
-          break;
-        }
-      }
-    }
-    if (!pp->bands) {
-      *rc = SPDL_HJ_ERR_BAD_GEOMETRY;
-      return nullptr;
-    }
-    return pp;
-  }
-
-  // The planar destination (hj_sws.h sws_plan_planar): the same tables
-  // (no row writers), one band height and column chunk for the luma and the
-  // chroma tiles; `bands` counts the image's tiles, luma then U then V
-  static std::shared_ptr<const PackedPlan> build_planar(const PlanKey& k, int* rc, int pre_mode,
-                                                        int max_cols) {
-    SwsPlan pl;
-    const bool gray = (k.mode & ~kPlanPlanar) == kPlanGray;
-    *rc = sws_plan_planar(k.w, k.h, k.hsub, k.vsub, gray, k.sw, k.sh, k.filter, &pl);
-    if (*rc) return nullptr;
-    auto pp = std::make_shared<PackedPlan>();
-    SwsDesc& d = pp->d;
-    d.sw = k.sw;
-    d.sh = k.sh;
-    d.chr_w = pl.chrDstW;
-    d.chr_h = pl.chrDstH;
-    d.gray = pl.gray;
-    d.yuv = 1;
-    d.hsub = pl.hsub;
-    d.vsub = pl.vsub;
-    const SwsAxis* ax[4] = {&pl.hl, &pl.hc, &pl.vl, &pl.vc};
-    int32_t* taps[4] = {&d.hl_taps, &d.hc_taps, &d.vl_taps, &d.vc_taps};
-    int32_t* sizes[4] = {&d.hl_size, &d.hc_size, &d.vl_size, &d.vc_size};
-    for (int i = 0; i < 4; i++) {  // rows cut and padded as build() does (hpass buckets)
-      const SwsAxis& a = *ax[i];
-      pp->axis_n[i] = a.n;
-      int q = (a.eff + 3) / 4;
-      if (i < 2) q = q <= 4 ? q : q <= 6 ? 6 : q <= 8 ? 8 : q <= 12 ? 12 : q <= 16 ? 16 : q;
-      const int stride = 4 * q;
-      *taps[i] = a.eff;
-      *sizes[i] = stride;
-      std::vector<int16_t> rows((size_t)a.n * stride, 0);
-      for (int r = 0; r < a.n; r++)
-        for (int t = 0; t < a.eff; t++) rows[(size_t)r * stride + t] = a.coef[(size_t)r * a.size + t];
-      put(pp->blob, &d.off[2 * i], a.pos.data(), a.pos.size() * 4);
-      put(pp->blob, &d.off[2 * i + 1], rows.data(), rows.size() * 2);
-    }
-    put(pp->blob, &d.off[kVmode], nullptr, 0);
-    auto reach = [](const SwsAxis& a) {
-      int r = 0;
-      for (int y = 0; y < a.n; y++) r = std::max(r, a.pos[y] + a.eff);
-      return r;
-    };
-    d.pre = pre_mode > 0 || (pre_mode < 0 && (k.h >= kPreRatio * k.sh || pl.hl.eff > 64));
-    d.pre_rl = d.pre ? reach(pl.vl) : 0;
-    d.pre_rc = d.pre && !pl.gray ? reach(pl.vc) : 0;
-    // the planes' placement: luma as the key says, chroma at the shifted
-    // offsets (multiples of the ratios: geometry()) in a ceil-shifted box
-    struct Pl {
-      const SwsAxis* v;
-      int sw, sh, dx, dy, ow, oh;
-    };
-    const Pl pls[2] = {
-        {&pl.vl, k.sw, k.sh, k.dx, k.dy, k.ow, k.oh},
-        {&pl.vc, pl.chrDstW, pl.chrDstH, k.dx >> pl.hsub, k.dy >> pl.vsub,
-         -((-k.ow) >> pl.hsub), -((-k.oh) >> pl.vsub)}};
-    const int npl = pl.gray ? 1 : 2;
-    for (int cols = std::min(max_cols, kSwsMaxCols); cols >= 16 && !pp->bands; cols /= 2) {
-      const int chunk = k.ow < cols ? k.ow : cols;
-      static const int kRb[] = {32, 24, 16, 12, 8, 6, 4, 3, 2, 1};
-      for (int rb : kRb) {
-        int64_t lds = planar_tile_lds(0, 0, rb, chunk);
-        for (int c = 0; c < npl; c++) {
-          const Pl& P = pls[c];
-          for (int yo0 = 0; yo0 < P.oh; yo0 += rb) {
-            const int ys0 = std::max(yo0 - P.dy, 0), ys1 = std::min(yo0 + rb - P.dy, P.sh);
-            if (ys0 >= ys1) continue;
-            const int rows = P.v->pos[ys1 - 1] + P.v->eff - P.v->pos[ys0];
-            const int ncols = std::min(chunk, P.sw);
-            lds = std::max(lds, planar_tile_lds(ncols, rows, rb, chunk));
-          }
-        }
-        if (lds <= kSwsLdsBudget || (!d.pre && rb == 1 && lds <= 64 * 1024)) {
-          d.rb = rb;
-          d.col_chunk = chunk;
-          pp->lds = (int)lds;
-          pp->chunks = 1;
-          for (int c = 0; c < npl; c++)
-            pp->bands += (c ? 2 : 1) * ((pls[c].oh + rb - 1) / rb) * ((pls[c].ow + chunk - 1) / chunk);
-          break;
-        }
-      }
-    }
-    if (!pp->bands) {
-      *rc = SPDL_HJ_ERR_BAD_GEOMETRY;
-      return nullptr;
-    }
-    return pp;
-  }
-
-  std::map<PlanKey, std::shared_ptr<const PackedPlan>> map_;
-  int pre_mode_ = -1;
-  int max_cols_ = kSwsMaxCols;
-};
-
 // chroma subsampling shifts of the yuvj4xxp frame FFmpeg's mjpeg decoder
 // makes of this sampling (444 / 422 / 420 / 440 / 411 ...); others are not
 // a swscale input format here
@@ -894,17 +635,12 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
     }
     d.wt_off = it->second;
     d.sws = plan->d;
-    if (plan->d.pre) {  // hscale_kernel rows: luma, then the two chroma planes
-      const SwsDesc& sd = plan->d;
-      const int wc = sd.gbr ? sd.sw : sd.chr_w, rc = sd.gbr ? sd.pre_rl : sd.pre_rc;
-      const int tl = (sd.pre_rl + kHsRows - 1) / kHsRows;
-      const bool chroma = sd.gbr || !sd.gray;  // (gbr plans are gray plans on three planes)
-      const int tc = chroma ? (rc + kHsRows - 1) / kHsRows : 0;
+    if (plan->d.pre) {  // hscale_kernel's tiles and rows (hj_sws_tile.h)
       d.hs_wg0 = (int32_t)L.hs_wgs;
-      d.hs_wgs = tl + 2 * tc;
+      d.hs_wgs = hs_tiles(plan->d).wgs;
       L.hs_wgs += d.hs_wgs;
       d.hbuf_off = L.total_hbuf;
-      L.total_hbuf += (int64_t)sd.pre_rl * sd.sw + (chroma ? 2 * (int64_t)rc * wc : 0);
+      L.total_hbuf += hs_hbuf_size(plan->d);
     }
     L.all_special = L.all_special && plan->special;
     // idct_rgb_kernel's MCU shapes: Y 2x2 or 2x1, U and V 1x1
@@ -2147,7 +1883,7 @@ int spdl_hj_debug_sws_plan(int32_t width, int32_t height, int32_t hsub, int32_t 
                     out->resize ? out->filter : 0, g.sw, g.sh, g.dx, g.dy, g.ow, g.oh};
   const int32_t geo[6] = {g.sw, g.sh, g.dx, g.dy, g.ow, g.oh};
   memcpy(info + 5, geo, sizeof(geo));
-  auto pp = PlanCache::plan(key, &rc, prepass, max_cols);
+  auto pp = PlanCache::build(key, &rc, prepass, max_cols);
   if (!pp) return rc;
   const SwsDesc& d = pp->d;
   const int32_t head[5] = {pp->special, d.full, d.gray, d.gbr, d.pre};

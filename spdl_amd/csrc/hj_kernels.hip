@@ -30,6 +30,7 @@
 #include "hj_common.h"
 #include "hj_destuff.h"
 #include "hj_idct.h"
+#include "hj_sws_tile.h"
 
 namespace hj {
 
@@ -4873,20 +4874,6 @@ __global__ void __launch_bounds__(256) csc_kernel(const uint8_t* __restrict__ pl
 // arithmetic: oracle/sws_oracle.c.
 // ---------------------------------------------------------------------------
 
-// A/B switches of the output stage's arithmetic (make variant DEFS=-DHJ_SWS_...=0
-// builds the earlier form): the pad as rectangles instead of a scan of the
-// tile, one pixel pair per work item on the table path, v_dot4 in the
-// horizontal pass
-#ifndef HJ_SWS_PADRECT
-#define HJ_SWS_PADRECT 1
-#endif
-#ifndef HJ_SWS_PAIRS
-#define HJ_SWS_PAIRS 1
-#endif
-#ifndef HJ_SWS_DOT4
-#define HJ_SWS_DOT4 1
-#endif
-
 typedef short hj_short2 __attribute__((ext_vector_type(2)));
 // 16-byte vector load from a 4-byte aligned address (gfx950 global loads
 // allow it): one global_load_dwordx4 instead of four dword loads
@@ -4976,19 +4963,10 @@ __device__ __forceinline__ void hpass_cols(const uint8_t* plane, int stride, int
     const uint32_t sh = (uint32_t)(p & 3);
     uint32_t wp[2 * NQ];
     const uint2* cp = reinterpret_cast<const uint2*>(coef + (int64_t)x * cstride);
-#if HJ_SWS_DOT4
     int32_t k0 = 0;  // 128 * the sum of the taps' hi bytes (hdot4)
 #pragma unroll
     for (int k = 0; k < NQ; k++) k0 = split_taps(cp[k], wp[2 * k], wp[2 * k + 1], k0);
     k0 <<= 7;
-#else
-#pragma unroll
-    for (int k = 0; k < NQ; k++) {
-      const uint2 t = cp[k];
-      wp[2 * k] = t.x;
-      wp[2 * k + 1] = t.y;
-    }
-#endif
     const uint8_t* base = plane + (p & ~3);
     int16_t* out = lds + c * cst;
     // rows in groups of G: the G loads are issued back to back, so one
@@ -5001,11 +4979,7 @@ __device__ __forceinline__ void hpass_cols(const uint8_t* plane, int stride, int
         if (r + g < r1) load_words<NW>(base + (int64_t)min(r + g, ph - 1) * stride, w[g]);
 #pragma unroll
       for (int g = 0; g < G; g++)
-#if HJ_SWS_DOT4
         if (r + g < r1) out[(r + g - r0) * rst] = h15(hdot4<NQ>(w[g], sh, wp, k0));
-#else
-        if (r + g < r1) out[(r + g - r0) * rst] = h15(hdot<NQ>(w[g], sh, wp));
-#endif
     }
   }
 }
@@ -5139,8 +5113,9 @@ __device__ __forceinline__ void full_rgb(const BatchParams& p, int Y, int U, int
 // hscale_kernel: swscale's horizontal pass (hScale8To15) of every source row
 // a large downscale reads, once, into a row-major int16 buffer (per image:
 // luma pre_rl x sw, then the two chroma planes pre_rc x chr_w -- gbr: three
-// planes through the luma filters).  sws_kernel then stages its bands from
-// there instead of re-filtering the rows its bands share: with a 17.9x
+// planes through the luma filters; hj_sws_tile.h hs_tiles / hs_plane).  The
+// output kernels then stage their bands from there (hbuf_stage) instead of
+// re-filtering the rows their bands share: with a 17.9x
 // bicubic downscale (12 MP -> 224) each band's 72-tap window overlaps its
 // neighbours' 4x.  Flat grid (hs_map: workgroup -> image), kHsRows rows of
 // one plane per workgroup.  Arithmetic: hpass (oracle sws_oracle.c hscale).
@@ -5156,27 +5131,25 @@ __global__ void __launch_bounds__(256) hscale_kernel(const uint8_t* __restrict__
   const ImageDesc& dd = desc[img];
   const SwsDesc& s = dd.sws;
   const int32_t* T = pool + dd.wt_off;
-  const int tl = (s.pre_rl + kHsRows - 1) / kHsRows;  // luma tiles
-  // (a gbr plan is a gray one -- luma filters only -- applied to three planes)
-  const int tc = s.gbr ? tl : (s.gray ? 0 : (s.pre_rc + kHsRows - 1) / kHsRows);
+  const HsTiles ht = hs_tiles(s);
   int t = (int)blockIdx.x - dd.hs_wg0;
   int c = 0;
-  if (t >= tl) {
-    t -= tl;
-    c = 1 + t / tc;
-    t %= tc;
+  if (t >= ht.tl) {
+    t -= ht.tl;
+    c = 1 + t / ht.tc;
+    t %= ht.tc;
   }
-  const bool lumaf = c == 0 || s.gbr;  // luma filters
-  const int rows = lumaf ? s.pre_rl : s.pre_rc;
-  const int w = lumaf ? s.sw : s.chr_w;
+  // (a gbr plan is a gray one -- luma filters only -- applied to three planes)
+  const bool lumaf = c == 0 || s.gbr;
+  const HsPlane hp = hs_plane(s, c);
+  const int rows = hp.rows, w = hp.w;
   const int r0 = t * kHsRows, r1 = min(r0 + kHsRows, rows);
-  const int64_t pbase = c == 0 ? 0 : (int64_t)s.pre_rl * s.sw + (c == 1 ? 0 : (int64_t)rows * w);
   const uint8_t* plane = planes + dd.plane_off[c];
   const int stride = dd.plane_stride[c], ph = in.comp_hpx[c];
   const int32_t* pos = T + s.off[lumaf ? kHlPos : kHcPos];
   const int16_t* coef = reinterpret_cast<const int16_t*>(T + s.off[lumaf ? kHlCoef : kHcCoef]);
   const int cstride = lumaf ? s.hl_size : s.hc_size, taps = lumaf ? s.hl_taps : s.hc_taps;
-  int16_t* dst = hbuf + dd.hbuf_off + pbase + (int64_t)r0 * w;
+  int16_t* dst = hbuf + dd.hbuf_off + hp.off + (int64_t)r0 * w;
   if (taps <= 64) {  // the register-bucket kernels of sws_kernel's own pass
     hpass(plane, stride, ph, pos, coef, cstride, taps, 0, w, r0, r1, dst, 1, threadIdx.x,
           blockDim.x, w);
@@ -5219,6 +5192,32 @@ __global__ void __launch_bounds__(256) hscale_kernel(const uint8_t* __restrict__
   }
 }
 
+// hscale_kernel's row-major rows [r0, r1) x [c0, c0 + ncols) of a `rows` x `w`
+// plane into an output kernel's column-major LDS (rows past the last one read
+// it: zero taps only); 4 elements per thread and step, the loads issued together
+__device__ __forceinline__ void hbuf_stage(const int16_t* __restrict__ src, int w, int rows, int c0,
+                                           int ncols, int r0, int r1, int16_t* dst, int cst,
+                                           int tid, int nt) {
+  const int nr = r1 - r0, ne = ncols * nr;
+  for (int i0 = tid; i0 < ne; i0 += 4 * nt) {
+    int16_t v[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = min(i0 + u * nt, ne - 1);
+      const int r = i / ncols, c = i - r * ncols;
+      v[u] = src[(int64_t)min(r0 + r, rows - 1) * w + c0 + c];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = i0 + u * nt;
+      if (i < ne) {
+        const int r = i / ncols, c = i - r * ncols;
+        dst[c * cst + r] = v[u];
+      }
+    }
+  }
+}
+
 __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ planes,
                                                   const ImageDesc* __restrict__ desc,
                                                   const ImageInfo* __restrict__ infos,
@@ -5247,22 +5246,21 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
   const SwsDesc& s = dd.sws;
   const int yo0 = band * s.rb, xo0 = chunk * s.col_chunk;
   if (yo0 >= dd.oh || xo0 >= dd.ow) return;
-  const int yo1 = min(yo0 + s.rb, dd.oh), xo1 = min(xo0 + s.col_chunk, dd.ow);
-  const int th = yo1 - yo0, tw = xo1 - xo0;
-  // content of this tile in scaled coordinates
-  const int ys0 = max(yo0 - dd.dy, 0), ys1 = min(yo1 - dd.dy, s.sh);
-  const int xs0 = max(xo0 - dd.dx, 0), xs1 = min(xo1 - dd.dx, s.sw);
-  const bool content = ys0 < ys1 && xs0 < xs1;
+  // the tile's end and its content in scaled coordinates
+  const SwsWindow win =
+      sws_window(yo0, xo0, s.rb, s.col_chunk, dd.dx, dd.dy, dd.ow, dd.oh, s.sw, s.sh);
+  const int yo1 = win.yo1, xo1 = win.xo1, th = yo1 - yo0, tw = xo1 - xo0;
+  const int ys0 = win.ys0, ys1 = win.ys1, xs0 = win.xs0, xs1 = win.xs1;
+  const bool content = win.content;
   const bool planar = p.pix_fmt == 0 || p.pix_fmt == 1;
   const bool swap = p.pix_fmt == 1 || p.pix_fmt == 3;
   const bool u8 = p.dtype == 0;
   const int64_t pl = (int64_t)dd.ow * dd.oh;
-  // LDS: horizontal-pass rows (luma, then the two chroma planes), 4 slack
-  // rows, then (u8 output) the tile in output layout for wide stores
   const int32_t* T = pool + dd.wt_off;
   const int32_t* vl_pos = T + s.off[kVlPos];
   const int32_t* vc_pos = T + s.off[kVcPos];
-  int lr0 = 0, lr1 = 0, cr0 = 0, cr1 = 0, cx0 = 0, ncc = 0;
+  int lr0 = 0, lr1 = 0, cr0 = 0, cr1 = 0;
+  SwsChromaCols ccols = {0, 0};
   const int ncl = content ? xs1 - xs0 : 0;
   if (content) {
     lr0 = vl_pos[ys0];
@@ -5270,23 +5268,21 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
     if (!s.gray) {
       cr0 = vc_pos[ys0];
       cr1 = vc_pos[ys1 - 1] + s.vc_taps;
-      cx0 = s.full ? xs0 : xs0 >> 1;
-      ncc = (s.full ? xs1 - 1 : (xs1 - 1) >> 1) + 1 - cx0;
+      ccols = sws_chroma_cols(xs0, xs1, s.full);
     }
   }
-  // horizontal-pass output, column-major (sws_col_stride); gbr: the R, G, B
-  // planes all through the luma filters (hl, hu, hv)
-  const int lst = sws_col_stride(lr1 - lr0), cst = sws_col_stride(cr1 - cr0);
-  int16_t* hl = sws_lds;
-  int16_t* hu = hl + ncl * lst;
-  int16_t* hv = hu + (s.gbr ? ncl * lst : s.gray ? 0 : ncc * cst);
-  const int hrow_end = (int)((hv + (s.gbr ? ncl * lst : s.gray ? 0 : ncc * cst)) - sws_lds);
-  uint8_t* tile = reinterpret_cast<uint8_t*>(sws_lds) + ((2 * hrow_end + 15) & ~15);
-  // the band's vertical tables, staged once (the per-row loads of the V pass
-  // are then LDS broadcasts): per output row {mode, first luma row, first
-  // chroma row (both band-relative), 0, luma taps, chroma taps}
-  const int vrw = 4 + (s.vl_size + s.vc_size) / 2;
-  uint32_t* vt = reinterpret_cast<uint32_t*>(tile + ((s.rb * s.col_chunk * 3 + 15) & ~15));
+  const int cx0 = ccols.cx0, ncc = ccols.ncc;
+  // LDS (sws_lds_layout): the horizontal-pass output, column-major (gbr: the
+  // R, G, B planes all through the luma filters: hl, hu, hv), then the u8 tile
+  // in output layout for wide stores, then the band's vertical tables
+  const SwsLds lay = sws_lds_layout(ncl, ncc, lr1 - lr0, cr1 - cr0, s.gbr, s.gray, s.rb,
+                                    s.col_chunk, s.vl_size, s.vc_size);
+  const int lst = lay.lst, cst = lay.cst, vrw = lay.vrw;
+  int16_t *hl = sws_lds, *hu = hl + lay.hu, *hv = hl + lay.hv;
+  uint8_t* tile = reinterpret_cast<uint8_t*>(sws_lds) + lay.tile;
+  // the vertical tables are staged once (the per-row loads of the V pass are
+  // then LDS broadcasts); their first rows are band-relative
+  uint32_t* vt = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(sws_lds) + lay.vt);
   if (content) {
     const int32_t* vmode = T + s.off[kVmode];
     const uint32_t* vlw = reinterpret_cast<const uint32_t*>(T + s.off[kVlCoef]);
@@ -5332,7 +5328,6 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
     putc(xo, yo, swap ? rgb[2] : rgb[0], rgb[1], swap ? rgb[0] : rgb[2]);
   };
   // pad: tile pixels outside the scaled image are black
-#if HJ_SWS_PADRECT
   {
     // the content's rows and columns in output coordinates (no content: every
     // row of the tile counts as above it).  A tile of content alone has
@@ -5378,53 +5373,17 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
       fill(cy0, cy1, cxb, xo1);
     }
   }
-#else
-  {
-    const int npx = th * tw;
-    const int zero[3] = {0, 0, 0};
-    for (int i = tid; i < npx; i += nt) {
-      const int yo = yo0 + i / tw, xo = xo0 + i % tw;
-      const int ys = yo - dd.dy, xs = xo - dd.dx;
-      if (ys < 0 || ys >= s.sh || xs < 0 || xs >= s.sw) put(xo, yo, zero);
-    }
-  }
-#endif
   if (content && s.pre) {
     // the horizontal pass was run once per source row by hscale_kernel
     // (large downscales): copy the band's rows into the column-major LDS
     const int16_t* hb = hbuf + dd.hbuf_off;
-    const int wl = s.sw, wc = s.gbr ? s.sw : s.chr_w;
-    const int64_t cbase = (int64_t)s.pre_rl * wl;
-    auto stage = [&](const int16_t* src, int w, int rows, int c0, int ncols, int r0, int r1,
-                     int16_t* dst, int cst_) {
-      // (4 elements per thread and step, the loads issued together)
-      const int nr = r1 - r0, ne = ncols * nr;
-      for (int i0 = tid; i0 < ne; i0 += 4 * nt) {
-        int16_t v[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const int i = min(i0 + u * nt, ne - 1);
-          const int r = i / ncols, c = i - r * ncols;
-          v[u] = src[(int64_t)min(r0 + r, rows - 1) * w + c0 + c];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const int i = i0 + u * nt;
-          if (i < ne) {
-            const int r = i / ncols, c = i - r * ncols;
-            dst[c * cst_ + r] = v[u];
-          }
-        }
-      }
-    };
-    stage(hb, wl, s.pre_rl, xs0, ncl, lr0, lr1, hl, lst);
-    if (s.gbr) {
-      stage(hb + cbase, wl, s.pre_rl, xs0, ncl, lr0, lr1, hu, lst);
-      stage(hb + 2 * cbase, wl, s.pre_rl, xs0, ncl, lr0, lr1, hv, lst);
-    } else if (!s.gray) {
-      const int64_t cpl = (int64_t)s.pre_rc * wc;
-      stage(hb + cbase, wc, s.pre_rc, cx0, ncc, cr0, cr1, hu, cst);
-      stage(hb + cbase + cpl, wc, s.pre_rc, cx0, ncc, cr0, cr1, hv, cst);
+    hbuf_stage(hb, s.sw, s.pre_rl, xs0, ncl, lr0, lr1, hl, lst, tid, nt);
+    if (s.gbr || !s.gray) {  // G and B through the luma window, or U and V
+      const HsPlane p1 = hs_plane(s, 1), p2 = hs_plane(s, 2);
+      const int c0 = s.gbr ? xs0 : cx0, nc = s.gbr ? ncl : ncc;
+      const int q0 = s.gbr ? lr0 : cr0, q1 = s.gbr ? lr1 : cr1, st = s.gbr ? lst : cst;
+      hbuf_stage(hb + p1.off, p1.w, p1.rows, c0, nc, q0, q1, hu, st, tid, nt);
+      hbuf_stage(hb + p2.off, p2.w, p2.rows, c0, nc, q0, q1, hv, st, tid, nt);
     }
   } else if (content && s.gbr) {
     // three planes, a third of the threads each
@@ -5447,11 +5406,7 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
     }
   }
   __syncthreads();
-#if HJ_SWS_PAIRS
   const bool pairs = !s.full && !s.gbr && !s.gray;
-#else
-  const bool pairs = false;
-#endif
   if (content && pairs && !(p.debug_mask & 0x200)) {
     // The table writers (yuv2rgb_{X,2,1}_c) share one U, V between the two
     // pixels of a chroma column: a work item owns chroma column cx0 + cc and
@@ -5668,31 +5623,6 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
 // width, else one row) sits in LDS at its destination's offset within 16
 // bytes, so after a head of single bytes both sides are 16-byte aligned for
 // dwordx4 stores, and a tail of single bytes ends it.
-__device__ __forceinline__ void yuv_stage(const int16_t* __restrict__ src, int w, int rows, int c0,
-                                          int ncols, int r0, int r1, int16_t* dst, int cst,
-                                          int tid, int nt) {
-  // hscale_kernel's row-major rows [r0, r1) x [c0, c0 + ncols) into the
-  // column-major LDS (rows past the last one read it: zero taps only)
-  const int nr = r1 - r0, ne = ncols * nr;
-  for (int i0 = tid; i0 < ne; i0 += 4 * nt) {
-    int16_t v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int i = min(i0 + u * nt, ne - 1);
-      const int r = i / ncols, c = i - r * ncols;
-      v[u] = src[(int64_t)min(r0 + r, rows - 1) * w + c0 + c];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int i = i0 + u * nt;
-      if (i < ne) {
-        const int r = i / ncols, c = i - r * ncols;
-        dst[c * cst + r] = v[u];
-      }
-    }
-  }
-}
-
 __global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restrict__ planes,
                                                          const ImageDesc* __restrict__ desc,
                                                          const ImageInfo* __restrict__ infos,
@@ -5714,14 +5644,13 @@ __global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restri
   // the tile's plane: its box (W x H), the scaled content (psw x psh) and
   // where that sits in the box (the chroma offsets are exact shifts: the host
   // keeps pad and crop on the chroma grid)
-  const int cw = (dd.ow + (1 << s.hsub) - 1) >> s.hsub, ch = (dd.oh + (1 << s.vsub) - 1) >> s.vsub;
-  const int ltiles = ((dd.oh + s.rb - 1) / s.rb) * ((dd.ow + s.col_chunk - 1) / s.col_chunk);
+  const PlanarTiles pt = planar_tiles(dd.ow, dd.oh, s.hsub, s.vsub, s.rb, s.col_chunk, s.gray);
+  const int cw = pt.cw, ch = pt.ch;
   int c = 0;
-  if (t >= ltiles) {
-    const int ctiles = ((ch + s.rb - 1) / s.rb) * ((cw + s.col_chunk - 1) / s.col_chunk);
-    t -= ltiles;
-    c = 1 + t / ctiles;
-    t -= (c - 1) * ctiles;
+  if (t >= pt.ltiles) {
+    t -= pt.ltiles;
+    c = 1 + t / pt.ctiles;
+    t -= (c - 1) * pt.ctiles;
     if (s.gray || c > 2) return;
   }
   const bool luma = c == 0;
@@ -5729,15 +5658,14 @@ __global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restri
   const int psw = luma ? s.sw : s.chr_w, psh = luma ? s.sh : s.chr_h;
   const int pdx = luma ? dd.dx : dd.dx >> s.hsub, pdy = luma ? dd.dy : dd.dy >> s.vsub;
   const int padv = luma ? (s.gray ? 16 : 0) : 128;
-  const int chunks = (W + s.col_chunk - 1) / s.col_chunk;
+  const int chunks = luma ? pt.lchunks : pt.cchunks;
   const int band = t / chunks, chunk = t - band * chunks;
   const int yo0 = band * s.rb, xo0 = chunk * s.col_chunk;
   if (yo0 >= H || xo0 >= W) return;
-  const int yo1 = min(yo0 + s.rb, H), xo1 = min(xo0 + s.col_chunk, W);
-  const int th = yo1 - yo0, tw = xo1 - xo0;
-  const int ys0 = max(yo0 - pdy, 0), ys1 = min(yo1 - pdy, psh);
-  const int xs0 = max(xo0 - pdx, 0), xs1 = min(xo1 - pdx, psw);
-  const bool content = ys0 < ys1 && xs0 < xs1;
+  const SwsWindow win = sws_window(yo0, xo0, s.rb, s.col_chunk, pdx, pdy, W, H, psw, psh);
+  const int yo1 = win.yo1, xo1 = win.xo1, th = yo1 - yo0, tw = xo1 - xo0;
+  const int ys0 = win.ys0, ys1 = win.ys1, xs0 = win.xs0, xs1 = win.xs1;
+  const bool content = win.content;
   const int ncl = content ? xs1 - xs0 : 0;
   const int32_t* T = pool + dd.wt_off;
   const int32_t* vpos = T + s.off[luma ? kVlPos : kVcPos];
@@ -5748,16 +5676,17 @@ __global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restri
     r0 = vpos[ys0];
     r1 = vpos[ys1 - 1] + vtaps;
   }
-  // LDS: the horizontal-pass columns, then the u8 tile
-  const int cst = sws_col_stride(r1 - r0);
+  // LDS (planar_lds_layout): the horizontal-pass columns, then the u8 tile
+  const PlanarLds lay = planar_lds_layout(ncl, r1 - r0, th, tw);
+  const int cst = lay.cst;
   int16_t* hcol = yuv_lds;
-  uint8_t* tile = reinterpret_cast<uint8_t*>(yuv_lds) + ((2 * ncl * cst + 15) & ~15);
+  uint8_t* tile = reinterpret_cast<uint8_t*>(yuv_lds) + lay.tile;
   // the tile's destination: one run when the tile spans the plane's width
   const int64_t pbase = dd.out_off + (luma ? 0 : (int64_t)dd.ow * dd.oh + (int64_t)(c - 1) * cw * ch);
   uint8_t* dst = out + pbase + (int64_t)yo0 * W + xo0;
   const bool whole = tw == W;
   const int nrun = whole ? 1 : th, runlen = whole ? th * W : tw;
-  const int pitch = (tw + 30) & ~15;  // LDS bytes between the runs of a chunked tile
+  const int pitch = lay.pitch;  // LDS bytes between the runs of a chunked tile
   const uint32_t g0 = (uint32_t)(uintptr_t)dst;
   auto tpos = [&](int r, int k) {  // tile byte of row r, column k
     return whole ? (int)(g0 & 15u) + r * W + k : r * pitch + (int)((g0 + (uint32_t)(r * W)) & 15u) + k;
@@ -5769,9 +5698,8 @@ __global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restri
     if (ys < 0 || ys >= psh || xs < 0 || xs >= psw) tile[tpos(r, k)] = (uint8_t)padv;
   }
   if (content && s.pre) {
-    const int64_t poff = luma ? 0 : (int64_t)s.pre_rl * s.sw + (int64_t)(c - 1) * s.pre_rc * s.chr_w;
-    yuv_stage(hbuf + dd.hbuf_off + poff, psw, luma ? s.pre_rl : s.pre_rc, xs0, ncl, r0, r1, hcol,
-              cst, tid, nt);
+    const HsPlane hp = hs_plane(s, c);
+    hbuf_stage(hbuf + dd.hbuf_off + hp.off, hp.w, hp.rows, xs0, ncl, r0, r1, hcol, cst, tid, nt);
   } else if (content) {
     hpass(planes + dd.plane_off[c], dd.plane_stride[c], in.comp_hpx[c],
           T + s.off[luma ? kHlPos : kHcPos],

@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "../../include/spdl_hipjpeg.h"
+#include "hj_sws_tile.h"
 
 namespace hj {
 namespace {
@@ -342,6 +343,169 @@ int sws_plan_planar(int srcW, int srcH, int hsub, int vsub, bool gray, int dstW,
   for (SwsAxis* a : {&p->vl, &p->vc})
     if (a->size == 1) std::fill(a->coef.begin(), a->coef.end(), (int16_t)(1 << 12));
   return SPDL_HJ_OK;
+}
+
+// ---- the packer and the tiler ----------------------------------------------
+namespace {
+
+void put(std::vector<int32_t>& blob, int32_t* off, const void* data, size_t bytes) {
+  *off = (int32_t)blob.size();
+  const size_t words = (bytes + 3) / 4;
+  blob.resize(blob.size() + ((words + 3) & ~(size_t)3), 0);
+  if (bytes) memcpy(blob.data() + *off, data, bytes);
+}
+
+// source rows a vertical filter reaches (first tap + taps, max over rows)
+int reach(const SwsAxis& a) {
+  int r = 0;
+  for (int y = 0; y < a.n; y++) r = std::max(r, a.pos[y] + a.eff);
+  return r;
+}
+
+// What both destinations share: the sizes, the tables of the plan into the
+// blob, and the pre-pass switch and its rows.
+void pack_tables(const PlanKey& k, const SwsPlan& pl, int pre_mode, PackedPlan* pp) {
+  SwsDesc& d = pp->d;
+  d.sw = k.sw;
+  d.sh = k.sh;
+  d.chr_w = pl.chrDstW;
+  d.gray = pl.gray;
+  const SwsAxis* ax[4] = {&pl.hl, &pl.hc, &pl.vl, &pl.vc};
+  int32_t* taps[4] = {&d.hl_taps, &d.hc_taps, &d.vl_taps, &d.vc_taps};
+  int32_t* sizes[4] = {&d.hl_size, &d.hc_size, &d.vl_size, &d.vc_size};
+  for (int i = 0; i < 4; i++) {
+    // rows cut to the taps that are ever non-zero, padded to a multiple
+    // of 4 (the kernel reads taps 4 at a time); horizontal rows to the
+    // kernel's register bucket of taps (hpass: 4, 8, 12, 16, 24, 32, 48, 64;
+    // longer rows use a plain loop)
+    const SwsAxis& a = *ax[i];
+    pp->axis_n[i] = a.n;
+    const int eff = a.eff;
+    int q = (eff + 3) / 4;
+    if (i < 2) q = q <= 4 ? q : q <= 6 ? 6 : q <= 8 ? 8 : q <= 12 ? 12 : q <= 16 ? 16 : q;
+    const int stride = 4 * q;
+    *taps[i] = eff;
+    *sizes[i] = stride;
+    std::vector<int16_t> rows((size_t)a.n * stride, 0);
+    for (int r = 0; r < a.n; r++)
+      for (int t = 0; t < eff; t++) rows[(size_t)r * stride + t] = a.coef[(size_t)r * a.size + t];
+    put(pp->blob, &d.off[2 * i], a.pos.data(), a.pos.size() * 4);
+    put(pp->blob, &d.off[2 * i + 1], rows.data(), rows.size() * 2);
+  }
+  put(pp->blob, &d.off[kVmode], pl.vmode.data(), pl.vmode.size() * 4);  // (planar: none)
+  d.pre = pre_mode > 0 || (pre_mode < 0 && !pp->special &&
+                           (k.h >= PlanCache::kPreRatio * k.sh || pl.hl.eff > 64));
+  d.pre_rl = d.pre ? reach(pl.vl) : 0;
+  d.pre_rc = d.pre && !pl.gray ? reach(pl.vc) : 0;
+}
+
+// Tiling: the widest column chunk, then the tallest band, whose largest tile's
+// LDS (lds_of(rb, chunk), bytes) fits the budget.  The launch's LDS is the
+// batch's largest plan's, so a plan over the budget slows every image's tiles:
+// only a one-row band of a plan without the hscale pre-pass may exceed it.
+template <class LdsOf>
+bool pick_tile(int ow, int max_cols, PackedPlan* pp, LdsOf lds_of) {
+  SwsDesc& d = pp->d;
+  for (int cols = std::min(max_cols, kSwsMaxCols); cols >= 16; cols /= 2) {
+    const int chunk = ow < cols ? ow : cols;
+    for (int rb : {32, 24, 16, 12, 8, 6, 4, 3, 2, 1}) {
+      const int lds = lds_of(rb, chunk);
+      if (lds <= kSwsLdsBudget || (!d.pre && rb == 1 && lds <= 64 * 1024)) {
+        d.rb = rb;
+        d.col_chunk = chunk;
+        pp->lds = lds;
+        return true;
+      }
+    }
+  }
+  return false;
+}
+
+int build_rgb(const PlanKey& k, int pre_mode, int max_cols, PackedPlan* pp) {
+  SwsPlan pl;
+  // gbr: the luma plan (gray) applied to each of the three RGB planes
+  if (int rc = sws_plan(k.w, k.h, k.hsub, k.vsub, k.mode != kPlanYuv, k.sw, k.sh, k.filter, &pl))
+    return rc;
+  pp->special = pl.special && k.dx == 0 && k.dy == 0 && k.ow == k.sw && k.oh == k.sh;
+  SwsDesc& d = pp->d;
+  d.full = pl.full;
+  d.gbr = k.mode == kPlanGbr;
+  pack_tables(k, pl, pre_mode, pp);
+  const auto lds_of = [&](int rb, int chunk) {
+    int lds = sws_lds_layout(0, 0, 0, 0, d.gbr, pl.gray, rb, chunk, d.vl_size, d.vc_size).end;
+    for (int yo0 = 0; yo0 < k.oh; yo0 += rb)
+      for (int xo0 = 0; xo0 < k.ow; xo0 += chunk) {
+        // (whole bands and chunks: a short last one is sized as a whole one)
+        const SwsWindow w =
+            sws_window(yo0, xo0, rb, chunk, k.dx, k.dy, xo0 + chunk, yo0 + rb, k.sw, k.sh);
+        if (!w.content) continue;
+        const int lrows = pl.vl.pos[w.ys1 - 1] + pl.vl.eff - pl.vl.pos[w.ys0];
+        const int crows = pl.gray ? 0 : pl.vc.pos[w.ys1 - 1] + pl.vc.eff - pl.vc.pos[w.ys0];
+        const int ncc = pl.gray ? 0 : sws_chroma_cols(w.xs0, w.xs1, pl.full).ncc;
+        lds = std::max(lds, sws_lds_layout(w.xs1 - w.xs0, ncc, lrows, crows, d.gbr, pl.gray, rb, chunk,
+                                           d.vl_size, d.vc_size).end);
+      }
+    return lds;
+  };
+  if (!pick_tile(k.ow, max_cols, pp, lds_of)) return SPDL_HJ_ERR_BAD_GEOMETRY;
+  pp->bands = tile_div_up(k.oh, d.rb);
+  pp->chunks = tile_div_up(k.ow, d.col_chunk);
+  return SPDL_HJ_OK;
+}
+
+// The planar destination (hj_sws.h sws_plan_planar): the same tables (no row
+// writers), one band height and column chunk for the luma and the chroma tiles
+int build_planar(const PlanKey& k, int pre_mode, int max_cols, PackedPlan* pp) {
+  SwsPlan pl;
+  const bool gray = (k.mode & ~kPlanPlanar) == kPlanGray;
+  if (int rc = sws_plan_planar(k.w, k.h, k.hsub, k.vsub, gray, k.sw, k.sh, k.filter, &pl)) return rc;
+  SwsDesc& d = pp->d;
+  d.chr_h = pl.chrDstH;
+  d.yuv = 1;
+  d.hsub = pl.hsub;
+  d.vsub = pl.vsub;
+  pack_tables(k, pl, pre_mode, pp);
+  // the planes' placement: luma as the key says, chroma at the shifted
+  // offset (a multiple of the ratio: geometry()) in a ceil-shifted box
+  const SwsAxis* pv[2] = {&pl.vl, &pl.vc};
+  const int psw[2] = {k.sw, pl.chrDstW}, psh[2] = {k.sh, pl.chrDstH};
+  const int pdy[2] = {k.dy, k.dy >> pl.vsub};
+  const int poh[2] = {k.oh, planar_tiles(k.ow, k.oh, pl.hsub, pl.vsub, 1, 1, pl.gray).ch};
+  const auto lds_of = [&](int rb, int chunk) {
+    int lds = planar_lds_layout(0, 0, rb, chunk).bound;
+    for (int c = 0; c < (pl.gray ? 1 : 2); c++)
+      for (int yo0 = 0; yo0 < poh[c]; yo0 += rb) {
+        // (a whole band: a short last one is sized as a whole one)
+        const SwsWindow w = sws_window(yo0, 0, rb, chunk, 0, pdy[c], chunk, yo0 + rb, psw[c], psh[c]);
+        if (w.ys0 >= w.ys1) continue;
+        const int rows = pv[c]->pos[w.ys1 - 1] + pv[c]->eff - pv[c]->pos[w.ys0];
+        lds = std::max(lds, planar_lds_layout(std::min(chunk, psw[c]), rows, rb, chunk).bound);
+      }
+    return lds;
+  };
+  if (!pick_tile(k.ow, max_cols, pp, lds_of)) return SPDL_HJ_ERR_BAD_GEOMETRY;
+  pp->bands = planar_tiles(k.ow, k.oh, pl.hsub, pl.vsub, d.rb, d.col_chunk, pl.gray).total;
+  pp->chunks = 1;
+  return SPDL_HJ_OK;
+}
+
+}  // namespace
+
+std::shared_ptr<const PackedPlan> PlanCache::build(const PlanKey& k, int* rc, int pre_mode,
+                                                   int max_cols) {
+  auto pp = std::make_shared<PackedPlan>();
+  *rc = (k.mode & kPlanPlanar ? build_planar : build_rgb)(k, pre_mode, max_cols, pp.get());
+  return *rc ? nullptr : pp;
+}
+
+std::shared_ptr<const PackedPlan> PlanCache::get(const PlanKey& k, int* rc) {
+  auto it = map_.find(k);
+  if (it != map_.end()) return it->second;
+  auto p = build(k, rc, pre_mode_, max_cols_);
+  if (!p) return nullptr;
+  if (map_.size() >= 512) map_.clear();  // bounded: a stream of odd sizes replans
+  map_.emplace(k, p);
+  return p;
 }
 
 }  // namespace hj

@@ -12,6 +12,9 @@
 #pragma once
 #include <stdint.h>
 
+#include <map>
+#include <memory>
+#include <tuple>
 #include <vector>
 
 #include "hj_common.h"
@@ -62,5 +65,57 @@ int sws_plan(int srcW, int srcH, int hsub, int vsub, bool gray, int dstW, int ds
 // (x + 64) >> 7, the writer swscale picks for that size whatever the tap.
 int sws_plan_planar(int srcW, int srcH, int hsub, int vsub, bool gray, int dstW, int dstH, int kind,
                     SwsPlan* out);
+
+// ---- plans packed for the device -------------------------------------------
+// One per distinct (source size, sampling, output placement, filter): the
+// tables as one blob, and the tiling the kernels run it with (hj_sws_tile.h).
+enum { kPlanYuv = 0, kPlanGray = 1, kPlanGbr = 2 };  // source planes of a plan
+constexpr int kPlanPlanar = 4;  // | kPlanYuv / kPlanGray: the planar destination (SPDL_HJ_FMT_YUV)
+struct PlanKey {
+  int w, h, hsub, vsub, mode, filter, sw, sh, dx, dy, ow, oh;
+  bool operator<(const PlanKey& o) const {
+    return std::tie(w, h, hsub, vsub, mode, filter, sw, sh, dx, dy, ow, oh) <
+           std::tie(o.w, o.h, o.hsub, o.vsub, o.mode, o.filter, o.sw, o.sh, o.dx, o.dy, o.ow, o.oh);
+  }
+};
+
+struct PackedPlan {
+  SwsDesc d{};                  // offsets relative to the blob
+  std::vector<int32_t> blob;    // tables, 16-byte aligned sections
+  int bands = 0, chunks = 0, lds = 0;  // tiles (planar: `bands` counts them all), LDS bytes
+  bool special = false;         // swscale's unscaled yuv2rgb_c_24_rgb converter
+  int axis_n[4] = {};           // rows of the hl, hc, vl, vc tables (spdl_hj_debug_sws_plan)
+};
+
+// Cached per context, so a stream of same-size images plans once.
+class PlanCache {
+ public:
+  // the horizontal pass of large downscales in hscale_kernel (SwsDesc::pre):
+  // -1 when the vertical ratio is >= kPreRatio or the luma filter is longer
+  // than the kernel's register buckets (64 taps), 0 never, 1 always
+  // (spdl_hj_set_param "sws_prepass"; outputs are identical)
+  static constexpr int kPreRatio = 4;
+  void set_pre_mode(int m) {
+    if (m != pre_mode_) map_.clear();
+    pre_mode_ = m;
+  }
+  int pre_mode() const { return pre_mode_; }
+  // widest column chunk a tile may take (16-256; the tiler then picks the
+  // tallest band that fits the LDS budget)
+  void set_max_cols(int c) {
+    if (c != max_cols_) map_.clear();
+    max_cols_ = c;
+  }
+  int max_cols() const { return max_cols_; }
+  std::shared_ptr<const PackedPlan> get(const PlanKey& k, int* rc);  // nullptr: *rc says why
+  // one plan outside any cache (spdl_hj_debug_sws_plan, tests/native)
+  static std::shared_ptr<const PackedPlan> build(const PlanKey& k, int* rc, int pre_mode,
+                                                 int max_cols);
+
+ private:
+  std::map<PlanKey, std::shared_ptr<const PackedPlan>> map_;
+  int pre_mode_ = -1;
+  int max_cols_ = kSwsMaxCols;
+};
 
 }  // namespace hj

@@ -269,7 +269,9 @@ def test_edges_family_reaches_both_clamps(oracle, name, filt):
 def test_planner_sweep_under_sanitizers(tmp_path):
     """tests/native/sws_plan_sweep.cpp + hj_sws.cpp built with ASan and UBSan
     and run as a program of its own: about 45 000 plans of sws_plan and
-    sws_plan_planar, no report and every built-in check green."""
+    sws_plan_planar, each accepted one packed and tiled (PlanCache::build)
+    under four placements and both knobs and every tile walked with
+    hj_sws_tile.h; no report and every built-in check green."""
     import os
     import shutil
     import subprocess
