@@ -14,7 +14,10 @@
 //   planes  : u8 component planes padded to whole blocks
 //   wts     : swscale tables (positions, Q14/Q12 taps, row writers) per
 //             distinct geometry of the batch (host-built, hj_sws.cpp)
+// and what crosses the launch seam by value: BatchParams, EntropyParams and the
+// Ablate bits.  The launchers and the BatchBuffers they take: hj_launch.h.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #ifndef HJ_HD
@@ -275,6 +278,37 @@ struct DsChunk {
   int32_t pad_[3];
 };
 
+// ff_yuv2rgb_c_init_tables coefficients, full-range BT.601 source (hj_sws.cpp sws_csc)
+struct SwsCsc {
+  int32_t crv, cbu, cgu, cgv;                     // table increments (cy-scaled)
+  int32_t y_coeff, y_offset, v2r, v2g, u2g, u2b;  // yuv2rgb_write_full
+};
+
+// Timing ablations: the bits of the context's debug_mask, as bench.py and tools/
+// pass them.  Each skips one phase (its cost shows as a time difference; outputs
+// are wrong).  Only -DHJ_ABLATIONS=1 builds take the knob and keep entropy_image's tests.
+#ifndef HJ_ABLATIONS
+#define HJ_ABLATIONS 0
+#endif
+enum Ablate : int32_t {
+  kAblSwsHpass = 0x100,  // sws_kernel: the horizontal pass of yuv / gray tiles
+  kAblSwsVpass = 0x200,  // sws_kernel: the vertical pass and the RGB writers
+  kAblSwsStore = 0x400,  // sws_kernel: the u8 tile's stores
+  kAblIdctNone = 0x800,  // idct_kernel / idct_rgb_kernel: no transform (instance <2>)
+  // entropy_image.  Round 0 always runs: the sync rounds and the block scan
+  // read the slot records it writes (a mask that skipped it left them unwritten,
+  // and the write pass then stored descriptors at garbage block indices).
+  kAblEntWrite = 0x1000,  // the write and DC passes
+  kAblEntSync = 0x2000,   // the sync rounds
+  kAblEntList = 0x4000,   // the write pass's list stores
+  kAblEntDc = 0x8000,     // the DC pass
+  kAblEntDesc = 0x80000,  // the write pass's descriptor stores
+  kAblEntropy = kAblEntWrite | kAblEntSync | kAblEntList | kAblEntDc | kAblEntDesc,
+  kAblNoMultiscan = 0x10000,  // run_pipeline: no multiscan launch
+  kAblNoIdct = 0x20000,       // ... no IDCT launch
+  kAblNoOutput = 0x40000,     // ... no output launch
+};
+
 struct BatchParams {
   int32_t n;
   int32_t pix_fmt, dtype, idct;
@@ -284,9 +318,25 @@ struct BatchParams {
   int32_t debug_mask;    // diagnostics: skip kernel phases (timing ablations only)
   int32_t xcd_order;     // XCD-aware tile order ("xcd_order"): bit 0 sws_kernel, bit 1 idct_kernel
   float mean[3], std[3];
-  // ff_yuv2rgb_c_init_tables coefficients (hj_sws.h SwsCsc)
-  int32_t crv, cbu, cgu, cgv;
-  int32_t y_coeff, y_offset, v2r, v2g, u2g, u2b;
+  SwsCsc csc;
+};
+static_assert(sizeof(BatchParams) == 108 && offsetof(BatchParams, csc) == 68, "BatchParams layout");
+
+// entropy_kernel's parameters, by value: run_pipeline -> launch_entropy -> entropy_image
+struct EntropyParams {
+  int32_t sub_bits;    // Huffman subsequence size (bits, multiple of 32)
+  int32_t warm_slots;  // round 0: slots decoded before a run's first slot (its start-state guess)
+  // the fewest slots a run holds (0: runs = threads).  A small image spread over
+  // every thread gives each run less than its warm-up's worth of bits, so round 0
+  // decodes mostly warm-up; with a floor of K slots per run only ceil(slots / K)
+  // runs work (the rest idle at the barriers): issue cycles scale with the bits.
+  int32_t min_run_slots;
+  // sync rounds after which still-unresolved chains of runs are re-decoded
+  // wave-cooperatively (entropy_image chain_round; 0: never)
+  int32_t chain_after;
+  int32_t prio;    // s_setprio of the entropy waves, 0-3 (A/B knob: flat at four lanes, r05)
+  int32_t ablate;  // the batch's Ablate bits that concern this kernel (kAblEntropy)
+  int64_t handoff_ticks;  // piece hand-off wait bound (wall_clock64 ticks with nothing arriving)
 };
 
 enum Status {

@@ -28,37 +28,9 @@
 
 #include "../../include/spdl_hipjpeg.h"
 #include "hj_common.h"
+#include "hj_launch.h"
 #include "hj_sws.h"
 #include "hj_sws_tile.h"
-
-namespace hj {
-hipError_t launch_parse(const uint8_t*, const ImageDesc*, ImageDesc*, ImageInfo*, HuffTable*,
-                        const void*, void*, int64_t, const uint32_t*, uint32_t*, int, uint64_t*,
-                        uint32_t*, uint32_t*, uint32_t*, uint32_t*, int, int, hipStream_t);
-hipError_t launch_destuff(const uint8_t*, const ImageDesc*, ImageInfo*, DsChunk*, uint8_t*,
-                          uint32_t*, const uint32_t*, int, int, int, hipStream_t);
-hipError_t launch_entropy(const uint8_t*, const uint32_t*, const ImageDesc*, ImageInfo*,
-                          const HuffTable*, uint32_t*, uint2*, uint32_t*, const uint32_t*, uint64_t*,
-                          int, int, int, int, int, int64_t, hipStream_t);
-hipError_t launch_idct(const uint32_t*, const uint2*, const ImageDesc*, const ImageInfo*, uint8_t*,
-                       int, const uint32_t*, int, int, int, int, hipStream_t);
-hipError_t launch_multiscan(const uint8_t*, uint8_t*, const ImageDesc*, ImageInfo*, uint32_t*, uint2*, int,
-                            hipStream_t);
-hipError_t launch_csc(const uint8_t*, const ImageDesc*, const ImageInfo*, void*,
-                      const BatchParams&, int64_t, int, int32_t*, hipStream_t);
-hipError_t launch_nv12(const uint8_t*, uint8_t*, int, int, int, int, int, hipStream_t);
-hipError_t launch_sws(const uint8_t*, const ImageDesc*, const ImageInfo*, const int32_t*, void*,
-                      const BatchParams&, const uint32_t*, int, int, int, int, int, int32_t*,
-                      const uint32_t*, int, int16_t*, hipStream_t);
-hipError_t launch_yuv_planes(const uint8_t*, const ImageDesc*, const ImageInfo*, const int32_t*,
-                             void*, const uint32_t*, int, int, int32_t*, const uint32_t*, int,
-                             int16_t*, hipStream_t);
-hipError_t launch_rgb_unscaled(const uint8_t*, const ImageDesc*, const ImageInfo*, void*,
-                               const BatchParams&, int64_t, int, int32_t*, hipStream_t);
-hipError_t launch_idct_rgb(const uint32_t*, const uint2*, const ImageDesc*, const ImageInfo*, void*,
-                           const BatchParams&, int, int, int, int32_t*, hipStream_t);
-hipError_t launch_cmyk(const ImageDesc*, const ImageInfo*, uint8_t*, int64_t, int, hipStream_t);
-}  // namespace hj
 
 using namespace hj;
 
@@ -953,6 +925,56 @@ int collect_status(spdl_hj_ctx* ctx, Slot& s, int32_t* status, char* err, size_t
   return SPDL_HJ_OK;
 }
 
+// The entropy launch as the knobs have it, "by schedule" defaults resolved:
+// what run_pipeline launches with and spdl_hj_get_param reports as in effect.
+EntropyParams entropy_schedule(const spdl_hj_ctx* c, int* threads) {
+  const int t = *threads = c->entropy_threads ? c->entropy_threads : (c->lanes > 1 ? 256 : 512);
+  EntropyParams ep{};
+  ep.sub_bits = c->sub_bits;
+  ep.warm_slots = c->warm_slots >= 0 ? c->warm_slots : (t <= 256 ? 6 : 12);
+  ep.min_run_slots = c->min_run_slots;
+  ep.chain_after = c->chain_after >= 0 ? c->chain_after : (t >= 512 ? 1 : 2);
+  ep.prio = c->entropy_prio;
+  ep.ablate = c->debug_mask & kAblEntropy;  // the kernel tests the same names
+  ep.handoff_ticks = c->handoff_wait_us * 100;
+  return ep;
+}
+
+// Size the lane's workspace (stream-ordered growth) for the batch of layout L,
+// whose files end at max_end of d_bytes; its buffers, typed, for the launchers.
+template <class T>
+hipError_t grow(DevBuf& d, size_t bytes, hipStream_t st, T** p) {
+  const hipError_t e = d.ensure(bytes, st, true);
+  *p = static_cast<T*>(d.p);
+  return e;
+}
+int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_bytes,
+                      int64_t max_end, hipStream_t st, BatchBuffers* b, char* err, size_t errlen) {
+  b->bytes = d_bytes;
+  b->n = n;
+  b->nwork = (int)L.work.size();
+  HJ_HIP(grow(W.clean, (size_t)max_end + 512, st, &b->clean));
+  HJ_HIP(grow(W.segs, (size_t)L.total_segs * 4 + 64, st, &b->segs));
+  HJ_HIP(grow(W.dschunks, (size_t)L.total_ds * sizeof(DsChunk) + 64, st, &b->dschunks));
+  HJ_HIP(grow(W.desc, sizeof(ImageDesc) * n + sizeof(uint32_t) * b->nwork, st, &b->desc));
+  b->work = reinterpret_cast<uint32_t*>(b->desc + n);  // the work list follows the descriptors
+  HJ_HIP(grow(W.chain, (size_t)(kChainHead + L.chain_granules) * 8 + 64, st, &b->chain));
+  HJ_HIP(grow(W.maps, (size_t)(L.ds_wgs + L.idct_wgs + L.hs_wgs + L.sws_wgs) * 4 + 64, st,
+              &b->ds_map));
+  b->idct_map = b->ds_map + L.ds_wgs;
+  b->hs_map = b->idct_map + L.idct_wgs;
+  b->sws_map = b->hs_map + L.hs_wgs;
+  HJ_HIP(grow(W.hbuf, (size_t)L.total_hbuf * 2 + 64, st, &b->hbuf));
+  HJ_HIP(grow(W.info, sizeof(ImageInfo) * n, st, &b->infos));
+  HJ_HIP(grow(W.luts, sizeof(HuffTable) * 8 * n, st, &b->luts));
+  HJ_HIP(grow(W.ents, (size_t)L.total_blocks * 256 + 256, st, &b->ents));
+  HJ_HIP(grow(W.bdesc, (size_t)L.total_blocks * 8 + 64, st, &b->bdesc));
+  HJ_HIP(grow(W.planes, (size_t)L.total_planes + 256, st, &b->planes));
+  HJ_HIP(grow(W.recs, (size_t)L.total_recs * 4 + 256, st, &b->recs));
+  HJ_HIP(grow(W.wts, L.tables.size() * 4 + 256, st, &b->wts));
+  return SPDL_HJ_OK;
+}
+
 // device pipeline over bytes already in HBM; `slot` provides the descriptor
 // and status staging and is marked done on `st` at the end.  `st` is the
 // execution stream (exec_stream()), the workspace is the slot's lane.
@@ -986,19 +1008,8 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
   if (!(ctx->lean_waits && W.used && W.last_st == st)) HJ_HIP(hipStreamWaitEvent(st, W.done, 0));
   W.last_st = st;
   W.used = true;
-  HJ_HIP(W.clean.ensure((size_t)max_end + 512, st, true));
-  HJ_HIP(W.segs.ensure((size_t)L.total_segs * 4 + 64, st, true));
-  HJ_HIP(W.dschunks.ensure((size_t)L.total_ds * sizeof(DsChunk) + 64, st, true));
-  const int nwork = (int)L.work.size();
-  const size_t desc_bytes = sizeof(ImageDesc) * n + sizeof(uint32_t) * nwork;  // + work list
-  HJ_HIP(W.desc.ensure(desc_bytes, st, true));
-  HJ_HIP(W.chain.ensure((size_t)(kChainHead + L.chain_granules) * 8 + 64, st, true));
-  HJ_HIP(W.maps.ensure((size_t)(L.ds_wgs + L.idct_wgs + L.hs_wgs + L.sws_wgs) * 4 + 64, st, true));
-  HJ_HIP(W.hbuf.ensure((size_t)L.total_hbuf * 2 + 64, st, true));
-  auto* ds_map = static_cast<uint32_t*>(W.maps.p);
-  auto* idct_map = ds_map + L.ds_wgs;
-  auto* hs_map = idct_map + L.idct_wgs;
-  auto* sws_map = hs_map + L.hs_wgs;
+  BatchBuffers B;
+  if (int rc = workspace_buffers(W, L, n, d_bytes, max_end, st, &B, err, errlen)) return rc;
   // A grid is flat (one workgroup per image tile, through the map) when the
   // (max tiles) x images grid would be mostly empty; a batch of similar
   // images keeps the 2-D grid, whose workgroups need no map lookup
@@ -1008,53 +1019,36 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
   const bool ds_flat = use_flat(L.ds_wgs, L.max_chunks);
   const bool idct_flat = use_flat(L.idct_wgs, (L.max_blocks + kIdctThreads - 1) / kIdctThreads);
   const bool sws_flat = use_flat(L.sws_wgs, (int64_t)L.sws_bands * L.sws_chunks);
-  HJ_HIP(W.info.ensure(sizeof(ImageInfo) * n, st, true));
-  HJ_HIP(W.luts.ensure(sizeof(HuffTable) * 8 * n, st, true));
-  HJ_HIP(W.ents.ensure((size_t)L.total_blocks * 256 + 256, st, true));
-  HJ_HIP(W.bdesc.ensure((size_t)L.total_blocks * 8 + 64, st, true));
-  HJ_HIP(W.planes.ensure((size_t)L.total_planes + 256, st, true));
-  HJ_HIP(W.recs.ensure((size_t)L.total_recs * 4 + 256, st, true));
-  HJ_HIP(W.wts.ensure(L.tables.size() * 4 + 256, st, true));
+  const size_t desc_bytes = sizeof(ImageDesc) * n + sizeof(uint32_t) * B.nwork;  // + work list
   HJ_HIP(slot.pin_desc.ensure(desc_bytes));
   HJ_HIP(slot.pin_status.ensure(sizeof(int32_t) * n));
   slot.n = n;
   memcpy(slot.pin_desc.p, L.desc.data(), sizeof(ImageDesc) * n);
-  memcpy(static_cast<ImageDesc*>(slot.pin_desc.p) + n, L.work.data(), sizeof(uint32_t) * nwork);
+  memcpy(static_cast<ImageDesc*>(slot.pin_desc.p) + n, L.work.data(), sizeof(uint32_t) * B.nwork);
   // the batch's swscale tables travel with the descriptors
   const bool swscale = !planes_only && out->csc == SPDL_HJ_CSC_SWSCALE;
   const size_t tb = swscale ? L.tables.size() * 4 : 0;
   HJ_HIP(slot.pin_tables.ensure(tb + 16));
   if (tb) memcpy(slot.pin_tables.p, L.tables.data(), tb);
-  const bool hs = ctx->host_staging != 0;
+  const bool hs = ctx->host_staging != 0;  // parse_kernel pulls them from the pinned pages
   if (!hs) {
-    HJ_HIP(hipMemcpyAsync(W.desc.p, slot.pin_desc.p, desc_bytes, hipMemcpyHostToDevice, st));
-    if (tb) HJ_HIP(hipMemcpyAsync(W.wts.p, slot.pin_tables.p, tb, hipMemcpyHostToDevice, st));
+    HJ_HIP(hipMemcpyAsync(B.desc, slot.pin_desc.p, desc_bytes, hipMemcpyHostToDevice, st));
+    if (tb) HJ_HIP(hipMemcpyAsync(B.wts, slot.pin_tables.p, tb, hipMemcpyHostToDevice, st));
   }
   mark(ctx, slot, 1, st);
-  auto* desc = static_cast<const ImageDesc*>(W.desc.p);
-  auto* infos = static_cast<ImageInfo*>(W.info.p);
-  auto* work = reinterpret_cast<uint32_t*>(static_cast<ImageDesc*>(W.desc.p) + n);
-  auto* chain = static_cast<uint64_t*>(W.chain.p);
-  HJ_HIP(launch_parse(d_bytes, hs ? static_cast<const ImageDesc*>(slot.pin_desc.dev) : nullptr,
-                      static_cast<ImageDesc*>(W.desc.p), infos,
-                      static_cast<HuffTable*>(W.luts.p), hs ? slot.pin_tables.dev : nullptr,
-                      W.wts.p, hs ? (int64_t)tb : 0,
-                      hs ? reinterpret_cast<const uint32_t*>(
-                               static_cast<const ImageDesc*>(slot.pin_desc.dev) + n)
-                         : nullptr,
-                      work, nwork, chain, ds_map, idct_map, hs_map, sws_map, ctx->parse_threads, n,
-                      st));
+  HJ_HIP(launch_parse(B, hs ? static_cast<const ImageDesc*>(slot.pin_desc.dev) : nullptr,
+                      hs ? slot.pin_tables.dev : nullptr, hs ? (int64_t)tb : 0,
+                      ctx->parse_threads, st));
   mark(ctx, slot, 2, st);
-  const bool ms_side = L.ms_side && !(ctx->debug_mask & 0x10000) && side_streams_fit(ctx);
+  const int abl = ctx->debug_mask;  // timing ablations (hj_common.h Ablate)
+  const bool ms_side = L.ms_side && !(abl & kAblNoMultiscan) && side_streams_fit(ctx);
   if (ms_side) {
     if (!W.side) HJ_HIP(create_stream(&W.side, -1));
     if (!W.ev_parsed) HJ_HIP(hipEventCreateWithFlags(&W.ev_parsed, hipEventDisableTiming));
     if (!W.ev_ms) HJ_HIP(hipEventCreateWithFlags(&W.ev_ms, hipEventDisableTiming));
     HJ_HIP(hipEventRecord(W.ev_parsed, st));
     HJ_HIP(hipStreamWaitEvent(W.side, W.ev_parsed, 0));
-    HJ_HIP(launch_multiscan(d_bytes, static_cast<uint8_t*>(W.clean.p), desc, infos,
-                            static_cast<uint32_t*>(W.ents.p), static_cast<uint2*>(W.bdesc.p), n,
-                            W.side));
+    HJ_HIP(launch_multiscan(B, W.side));
     HJ_HIP(hipEventRecord(W.ev_ms, W.side));
   }
   // If a launch below fails and returns early, the lane's stream still joins
@@ -1068,62 +1062,36 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
       (void)hipStreamWaitEvent(st, w->ev_ms, 0);
       (void)hipEventRecord(w->done, st);
     }
-  } side_join;
-  if (ms_side) {
-    side_join.st = st;
-    side_join.w = &W;
-  }
-  HJ_HIP(launch_destuff(d_bytes, desc, infos, static_cast<DsChunk*>(W.dschunks.p),
-                        static_cast<uint8_t*>(W.clean.p), static_cast<uint32_t*>(W.segs.p),
-                        ds_flat ? ds_map : nullptr, (int)L.ds_wgs, L.max_chunks, n, st));
+  } side_join{st, ms_side ? &W : nullptr};
+  HJ_HIP(launch_destuff(B, ds_flat, (int)L.ds_wgs, L.max_chunks, st));
   mark(ctx, slot, 3, st);
-  const int ent_threads =
-      ctx->entropy_threads ? ctx->entropy_threads : (ctx->lanes > 1 ? 256 : 512);
-  const int warm = ctx->warm_slots >= 0 ? ctx->warm_slots : (ent_threads <= 256 ? 6 : 12);
-  HJ_HIP(launch_entropy(static_cast<const uint8_t*>(W.clean.p),
-                        static_cast<const uint32_t*>(W.segs.p), desc, infos,
-                        static_cast<const HuffTable*>(W.luts.p),
-                        static_cast<uint32_t*>(W.ents.p), static_cast<uint2*>(W.bdesc.p),
-                        static_cast<uint32_t*>(W.recs.p), work, chain,
-                        ctx->sub_bits,
-                        warm | (ctx->min_run_slots << 8) |
-                            ((ctx->chain_after >= 0 ? ctx->chain_after : (ent_threads >= 512 ? 1 : 2))
-                             << 26) |
-                            ((((ctx->debug_mask >> 12) & 0xF) | (((ctx->debug_mask >> 19) & 1) << 4))
-                             << 16) |
-                            (ctx->entropy_prio << 24),
-                        ent_threads, ctx->entropy_lds_pad, nwork, ctx->handoff_wait_us * 100, st));
+  int ent_threads;
+  const EntropyParams ep = entropy_schedule(ctx, &ent_threads);
+  HJ_HIP(launch_entropy(B, ep, ent_threads, ctx->entropy_lds_pad, st));
   // (the entropy stage ends here: the multiscan launch or the wait for the
   // side stream counts to the IDCT stage)
   mark(ctx, slot, 4, st);
   // progressive / non-interleaved images (the kernels above skipped them)
-  // (debug_mask 0x10000 / 0x20000 / 0x40000: timing ablations that skip the
-  // multiscan / IDCT / output launch; the output is wrong)
   if (ms_side) {
     side_join.w = nullptr;
     HJ_HIP(hipStreamWaitEvent(st, W.ev_ms, 0));
-  } else if (!(ctx->debug_mask & 0x10000) && !(ctx->ms_skip_empty && L.ms_known && !L.ms_side))
-    HJ_HIP(launch_multiscan(d_bytes, static_cast<uint8_t*>(W.clean.p), desc, infos,
-                            static_cast<uint32_t*>(W.ents.p),
-                            static_cast<uint2*>(W.bdesc.p), n, st));
+  } else if (!(abl & kAblNoMultiscan) && !(ctx->ms_skip_empty && L.ms_known && !L.ms_side))
+    HJ_HIP(launch_multiscan(B, st));
   // full resolution u8 through swscale's unscaled converter: IDCT and
   // conversion in one kernel (output_path 1: the generic sws_kernel, 2:
   // separate IDCT + rgb_unscaled_kernel)
-  const int idct_kind = (ctx->debug_mask & 0x800) ? 2 : out->idct;
+  const int idct_kind = (abl & kAblIdctNone) ? 2 : out->idct;
   // (the planar output, SPDL_HJ_FMT_YUV, has one kernel of its own)
   const bool yuv = swscale && out->pix_fmt == SPDL_HJ_FMT_YUV;
   const bool fast_rgb = swscale && !yuv && L.all_special && out->dtype == SPDL_HJ_DTYPE_U8 &&
                         ctx->output_path != 1;
   const bool fused = fast_rgb && L.fuse_ok && L.fused_tiles > 0 && ctx->output_path != 2;
-  if (!(ctx->debug_mask & 0x20000) && !fused)
-    HJ_HIP(launch_idct(static_cast<const uint32_t*>(W.ents.p),
-                     static_cast<const uint2*>(W.bdesc.p), desc, infos,
-                     static_cast<uint8_t*>(W.planes.p), idct_kind, idct_flat ? idct_map : nullptr,
-                     (int)L.idct_wgs, L.max_blocks, n, (ctx->xcd_order >> 1) & 1, st));
+  if (!(abl & kAblNoIdct) && !fused)
+    HJ_HIP(launch_idct(B, idct_kind, idct_flat, (int)L.idct_wgs, L.max_blocks,
+                       (ctx->xcd_order >> 1) & 1, st));
   // 4-component frames: FFmpeg's K transform on the planes (not on the raw
   // planes surface, which returns the IDCT output as the oracle does)
-  if (!planes_only && L.cmyk_px > 0)
-    HJ_HIP(launch_cmyk(desc, infos, static_cast<uint8_t*>(W.planes.p), L.cmyk_px, n, st));
+  if (!planes_only && L.cmyk_px > 0) HJ_HIP(launch_cmyk(B, L.cmyk_px, st));
   mark(ctx, slot, 5, st);
   BatchParams bp{};
   bp.n = n;
@@ -1135,55 +1103,32 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
   bp.out_w = L.ow;
   bp.out_h = L.oh;
   bp.sub_bits = ctx->sub_bits;
-  bp.debug_mask = ctx->debug_mask;
+  bp.debug_mask = abl;
   bp.xcd_order = ctx->xcd_order;
-  for (int c = 0; c < 3; c++) {
-    bp.mean[c] = out->mean[c];
-    bp.std[c] = out->std[c];
-  }
-  const SwsCsc csc = sws_csc();
-  bp.crv = csc.crv;
-  bp.cbu = csc.cbu;
-  bp.cgu = csc.cgu;
-  bp.cgv = csc.cgv;
-  bp.y_coeff = csc.y_coeff;
-  bp.y_offset = csc.y_offset;
-  bp.v2r = csc.v2r;
-  bp.v2g = csc.v2g;
-  bp.u2g = csc.u2g;
-  bp.u2b = csc.u2b;
+  memcpy(bp.mean, out->mean, sizeof(bp.mean));
+  memcpy(bp.std, out->std, sizeof(bp.std));
+  bp.csc = sws_csc();
   // the output kernel writes each image's status into the pinned array itself
   int32_t* hstat = hs && !planes_only ? static_cast<int32_t*>(slot.pin_status.dev) : nullptr;
   mark(ctx, slot, 6, st);
-  if (!planes_only && !(ctx->debug_mask & 0x40000)) {
-    if (yuv) {
-      HJ_HIP(launch_yuv_planes(static_cast<const uint8_t*>(W.planes.p), desc, infos,
-                               static_cast<const int32_t*>(W.wts.p), out_dev, sws_map,
-                               (int)L.sws_wgs, L.sws_lds, hstat, hs_map, (int)L.hs_wgs,
-                               static_cast<int16_t*>(W.hbuf.p), st));
-    } else if (fused) {
-      HJ_HIP(launch_idct_rgb(static_cast<const uint32_t*>(W.ents.p),
-                             static_cast<const uint2*>(W.bdesc.p), desc, infos, out_dev, bp,
-                             idct_kind, L.fused_tiles, n, hstat, st));
-    } else if (fast_rgb) {
-      // full resolution, u8: swscale's unscaled converter needs no scaling passes
-      HJ_HIP(launch_rgb_unscaled(static_cast<const uint8_t*>(W.planes.p), desc, infos, out_dev,
-                                 bp, L.max_px, n, hstat, st));
-    } else if (swscale) {
-      HJ_HIP(launch_sws(static_cast<const uint8_t*>(W.planes.p), desc, infos,
-                        static_cast<const int32_t*>(W.wts.p), out_dev, bp,
-                        sws_flat ? sws_map : nullptr, (int)L.sws_wgs, L.sws_bands, L.sws_chunks, n,
-                        L.sws_lds, hstat, hs_map, (int)L.hs_wgs,
-                        static_cast<int16_t*>(W.hbuf.p), st));
-    } else {
-      HJ_HIP(launch_csc(static_cast<const uint8_t*>(W.planes.p), desc, infos, out_dev, bp,
-                        L.max_px, n, hstat, st));
-    }
+  if (!planes_only && !(abl & kAblNoOutput)) {
+    const int sws_wgs = (int)L.sws_wgs, hs_wgs = (int)L.hs_wgs;
+    if (yuv)
+      HJ_HIP(launch_yuv_planes(B, out_dev, sws_wgs, L.sws_lds, hs_wgs, hstat, st));
+    else if (fused)
+      HJ_HIP(launch_idct_rgb(B, out_dev, bp, idct_kind, L.fused_tiles, hstat, st));
+    else if (fast_rgb)  // swscale's unscaled converter needs no scaling passes
+      HJ_HIP(launch_rgb_unscaled(B, out_dev, bp, L.max_px, hstat, st));
+    else if (swscale)
+      HJ_HIP(launch_sws(B, out_dev, bp, sws_flat, sws_wgs, L.sws_bands, L.sws_chunks, L.sws_lds,
+                        hs_wgs, hstat, st));
+    else
+      HJ_HIP(launch_csc(B, out_dev, bp, L.max_px, hstat, st));
   }
   mark(ctx, slot, 7, st);
   // per-image status: strided D2H of ImageInfo::status
   if (!hstat)
-    HJ_HIP(hipMemcpy2DAsync(slot.pin_status.p, sizeof(int32_t), W.info.p, sizeof(ImageInfo),
+    HJ_HIP(hipMemcpy2DAsync(slot.pin_status.p, sizeof(int32_t), B.infos, sizeof(ImageInfo),
                             sizeof(int32_t), n, hipMemcpyDeviceToHost, st));
   mark(ctx, slot, 8, st);
   HJ_HIP(hipEventRecord(W.done, st));
@@ -2111,20 +2056,21 @@ int spdl_hj_set_param(spdl_hj_ctx* ctx, const char* name, int64_t value) {
 
 int spdl_hj_get_param(spdl_hj_ctx* ctx, const char* name, int64_t* value) {
   if (!ctx || !name || !value) return SPDL_HJ_ERR_INVALID_ARG;
-  const int ent = ctx->entropy_threads ? ctx->entropy_threads : (ctx->lanes > 1 ? 256 : 512);
+  int ent_threads;
+  const EntropyParams ep = entropy_schedule(ctx, &ent_threads);
   const struct {
     const char* n;
     int64_t v;
   } tab[] = {
       {"sub_bits", ctx->sub_bits},
-      {"entropy_threads", ent},
-      {"warmup_slots", ctx->warm_slots >= 0 ? ctx->warm_slots : (ent <= 256 ? 6 : 12)},
+      {"entropy_threads", ent_threads},
+      {"warmup_slots", ep.warm_slots},
       {"lanes", ctx->lanes},
       {"entropy_piece_bytes", ctx->piece_bytes},
       {"sws_prepass", ctx->plans.pre_mode()},
       {"entropy_prio", ctx->entropy_prio},
       {"min_run_slots", ctx->min_run_slots},
-      {"chain_after", ctx->chain_after >= 0 ? ctx->chain_after : (ent >= 512 ? 1 : 2)},
+      {"chain_after", ep.chain_after},
       {"parse_threads", ctx->parse_threads},
       {"sws_cols", ctx->plans.max_cols()},
       {"hw_queues", ctx->hw_queues},

@@ -17,10 +17,8 @@
 //                   predictors, and a final pass writes dequantised
 //                   coefficients.
 //   idct_kernel     8x8 IDCT (FFmpeg simple_idct or IJG islow), block -> plane.
-//   weights_kernel  per-image resampling tables (Q14), resize mode only.
-//   csc_kernel / resize_kernel   planes -> RGB (nearest chroma, JFIF integer
-//                   colour conversion), resize/pad/crop, optional
-//                   (x/255-mean)/std -> fp16, planar or interleaved.
+//   output kernels  planes -> RGB / planar YUV (DESIGN.md section 3 lists them).
+// The launchers (hj_launch.h) are at the end of the file.
 //
 // Semantics follow oracle/jpeg_oracle.c line for line (the CPU restatement of
 // SPDL's FFmpeg path); the two are compared bit-exactly by tests/.
@@ -30,6 +28,7 @@
 #include "hj_common.h"
 #include "hj_destuff.h"
 #include "hj_idct.h"
+#include "hj_launch.h"
 #include "hj_sws_tile.h"
 
 namespace hj {
@@ -1882,27 +1881,9 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
                               const HuffTable* __restrict__ luts, uint32_t* __restrict__ ents,
                               uint2* __restrict__ bdesc, uint32_t* __restrict__ recs,
                               uint64_t* __restrict__ chain, const int piece,
-                              const int sub_bits_param,
-                              const int warm_param, const int64_t handoff_ticks) {
+                              const EntropyParams ep) {
   const int tid = threadIdx.x;
-  // warm_param: warm-up slots; bits 16-19 = timing ablations (BatchParams
-  // debug_mask >> 12: 1 skips the write and DC passes, 2 the sync rounds,
-  // 8 the DC pass, 4 the list stores, 16 (debug_mask 0x80000) the write
-  // pass's descriptor stores; outputs are wrong.  Round 0 always runs: the sync rounds
-  // and the block scan read the slot records it writes -- a round-4 mask
-  // that skipped it left them unwritten, and the write pass then stored
-  // descriptors at garbage block indices)
-  const int warm_slots = warm_param & 0xFF;
-  // bits 8-15: the fewest slots a run holds (0: runs = threads).  A small
-  // image spread over every thread gives each run less than its warm-up's
-  // worth of bits, so round 0 decodes mostly warm-up; with a floor of K slots
-  // per run only ceil(slots / K) runs work (the rest idle at the barriers),
-  // and the workgroup's issue cycles scale with the image's bits.
-  const int min_run_slots = (warm_param >> 8) & 0xFF;
-  // bits 26-29: sync rounds after which still-unresolved chains of runs are
-  // re-decoded wave-cooperatively (chain_round below; 0: never)
-  const int chain_after = (warm_param >> 26) & 0xF;
-  const int dbg = (warm_param >> 16) & 0xFF;
+  const int ablate = HJ_ABLATIONS ? ep.ablate : 0;  // (release builds: no tests, no live SGPR)
   uint32_t* win = &S.win[0][tid];
   const ImageDesc dd = desc[img];
   const ImageInfo& in = infos[img];
@@ -2030,7 +2011,7 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
   }
   maxbits = (uint32_t)S.sc.red[0];
   __syncthreads();
-  const uint32_t N = slot_bits(maxbits, sub_bits_param, budget);
+  const uint32_t N = slot_bits(maxbits, ep.sub_bits, budget);
   if ((int64_t)kMaxSlots * 8 * P > dd.rec_cap) {  // host-sized slot state
     if (tid == 0) infos[img].status = kErrBadGeometry;
     if (P > 1) chain_fail(myrec, tid);
@@ -2053,7 +2034,7 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
   for (int seg_lo = seg_a; seg_lo < seg_b; seg_lo += seg_per_chunk) {
     const int nsc = min(seg_per_chunk, seg_b - seg_lo);
     const int nslots = nsc * cmax;
-    const int K = max((nslots + nruns - 1) / nruns, min_run_slots);
+    const int K = max((nslots + nruns - 1) / nruns, ep.min_run_slots);
     const int r0 = min((pc * NT + tid) * K, nslots), r1 = min(r0 + K, nslots);
     auto slot_seg = [&](int k) { return seg_lo + k / cmax; };
     auto slot_j = [&](int k) { return k % cmax; };
@@ -2098,7 +2079,7 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
           // segment start, which is exact) and decode up to the slot, so the
           // run's first state is usually already synchronised and the sync
           // rounds below have short chains to settle
-          const uint32_t wb = (uint32_t)warm_slots * N;
+          const uint32_t wb = (uint32_t)ep.warm_slots * N;
           dec_init<NT>(d, win, words, ss - s0 > wb ? ss - wb : s0, 0, 0);
           decode_state<NT, kSlow>(S, d, win, words, tm, ss);
         }
@@ -2199,8 +2180,8 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
     };
     auto sync_rounds = [&]() -> int {
       int rounds = 0;
-      for (; !(dbg & 2);) {
-        if (chain_after > 0 && rounds >= chain_after) chain_round();
+      for (; !(ablate & kAblEntSync);) {
+        if (ep.chain_after > 0 && rounds >= ep.chain_after) chain_round();
         if (tid == 0) S.flag = 0;
         __syncthreads();
         bool redo = false;
@@ -2314,7 +2295,7 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       if (pc == 0) break;
       // the previous piece's end state and block count as the sequential
       // decoder sees them
-      if (tid < 64) chain_lookback(S, crec, pc, tid, handoff_ticks);
+      if (tid < 64) chain_lookback(S, crec, pc, tid, ep.handoff_ticks);
       __syncthreads();
       const int ok = S.lb_ok;
       if (ok < 0) {
@@ -2368,8 +2349,9 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       }
     }
     // (timing ablations: a later piece still needs this one's DC record)
-    if ((dbg & 9) && chained && tid < kMaxComp) gran_put(myrec, kChDc + tid, kTagDc, 0u);
-    if (dbg & 1) continue;
+    if ((ablate & (kAblEntWrite | kAblEntDc)) && chained && tid < kMaxComp)
+      gran_put(myrec, kChDc + tid, kTagDc, 0u);
+    if (ablate & kAblEntWrite) continue;
     // ---- write pass: decode each run once more from its synchronised
     // start, appending its blocks' coefficient lists; the sequential decoder's
     // stop and error rules per segment ----
@@ -2384,8 +2366,8 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       o.last = (uint32_t)nblocks * 64u - 1u;
       o.nblk = (uint32_t)nblocks;
 #if HJ_ABLATIONS
-      o.no_list = (dbg & 4) != 0;
-      o.no_desc = (dbg & 16) != 0;
+      o.no_list = (ablate & kAblEntList) != 0;
+      o.no_desc = (ablate & kAblEntDesc) != 0;
 #endif
       o.bstart = o.cur;
       o.dcv = 0;
@@ -2449,7 +2431,7 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       tph[3] += t - tstamp;
       tstamp = t;
     }
-    if (dbg & 8) continue;
+    if (ablate & kAblEntDc) continue;
     // ---- DC predictors: the write pass stored raw DC differences.  Sum them
     // per component over this run's blocks, segmented-scan the sums over the
     // runs (predictors restart at each restart segment), then replace each
@@ -2498,7 +2480,7 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       __syncthreads();
       if (chained && pc > 0) {
         // the predictors entering this piece: the sums of all earlier pieces
-        if (tid < 64) chain_dc(S, crec, pc, tid, handoff_ticks);
+        if (tid < 64) chain_dc(S, crec, pc, tid, ep.handoff_ticks);
         __syncthreads();
         const int ok = S.lb_ok;
         if (ok < 0) {
@@ -2542,7 +2524,7 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       tstamp = t;
     }
   }
-  if (tid == 0 && S.err != kOk && !dbg) infos[img].status = S.err;
+  if (tid == 0 && S.err != kOk && !ablate) infos[img].status = S.err;
   if (tid == 0 && piece == 0) {
     infos[img].sync_rounds = rounds_total;
     for (int i = 0; i < 4; i++) infos[img].tphase[i] = tph[i];
@@ -2565,26 +2547,18 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
 // pool) runs the LDS-only decode loops; a wide one (parse_kernel's ent_wide)
 // the loops that may read HBM table copies and the canonical fallback.
 template <int NT, int NTAB>
-__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT >= 256 ? 4 : 1))) entropy_kernel(const uint8_t* __restrict__ clean,
-                                                     const uint32_t* __restrict__ segs,
-                                                     const ImageDesc* __restrict__ desc,
-                                                     ImageInfo* __restrict__ infos,
-                                                     const HuffTable* __restrict__ luts,
-                                                     uint32_t* __restrict__ ents,
-                                                     uint2* __restrict__ bdesc,
-                                                     uint32_t* __restrict__ recs,
-                                                     const uint32_t* __restrict__ work,
-                                                     uint64_t* __restrict__ chain,
-                                                     const int sub_bits_param, const int warm_slots,
-                                                     const int nwork, const int64_t handoff_ticks) {
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT >= 256 ? 4 : 1)))
+entropy_kernel(const uint8_t* __restrict__ clean, const uint32_t* __restrict__ segs,
+               const ImageDesc* __restrict__ desc, ImageInfo* __restrict__ infos,
+               const HuffTable* __restrict__ luts, uint32_t* __restrict__ ents,
+               uint2* __restrict__ bdesc, uint32_t* __restrict__ recs,
+               const uint32_t* __restrict__ work, uint64_t* __restrict__ chain,
+               const EntropyParams ep, const int nwork) {
   __shared__ EntShared<NT, NTAB> S;
   __shared__ uint32_t item;
-  // warm_slots bits 24+: wave priority (s_setprio) of the entropy waves
-  // (an A/B knob: flat at four lanes, r05 profiles/r05/ab_entropy_prio.txt)
-  const int prio = (warm_slots >> 24) & 3;
-  if (prio == 3) __builtin_amdgcn_s_setprio(3);
-  else if (prio == 2) __builtin_amdgcn_s_setprio(2);
-  else if (prio == 1) __builtin_amdgcn_s_setprio(1);
+  if (ep.prio == 3) __builtin_amdgcn_s_setprio(3);  // (the instruction takes an immediate)
+  else if (ep.prio == 2) __builtin_amdgcn_s_setprio(2);
+  else if (ep.prio == 1) __builtin_amdgcn_s_setprio(1);
   if (threadIdx.x == 0) {
     const uint32_t t = __hip_atomic_fetch_add((__attribute__((address_space(1))) uint32_t*)chain,
                                               1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2596,10 +2570,10 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT >= 2
   const int img = (int)(w & 0xFFFFFFu), piece = (int)(w >> 24);
   if (infos[img].ent_wide)
     entropy_image<NT, NTAB, true>(S, img, clean, segs, desc, infos, luts, ents, bdesc, recs, chain,
-                                  piece, sub_bits_param, warm_slots, handoff_ticks);
+                                  piece, ep);
   else
     entropy_image<NT, NTAB, false>(S, img, clean, segs, desc, infos, luts, ents, bdesc, recs,
-                                   chain, piece, sub_bits_param, warm_slots, handoff_ticks);
+                                   chain, piece, ep);
 }
 
 // ---------------------------------------------------------------------------
@@ -4518,13 +4492,6 @@ __global__ void __launch_bounds__(256) multiscan_kernel(const uint8_t* __restric
   }
 }
 
-hipError_t launch_multiscan(const uint8_t* bytes, uint8_t* clean, const ImageDesc* desc,
-                            ImageInfo* infos, uint32_t* ents, uint2* bdesc, int n, hipStream_t st) {
-  hipLaunchKernelGGL(multiscan_kernel, dim3(n), dim3(256), 0, st, bytes, clean, desc, infos, ents,
-                     bdesc);
-  return hipGetLastError();
-}
-
 // ---------------------------------------------------------------------------
 // idct_kernel
 // ---------------------------------------------------------------------------
@@ -5093,12 +5060,12 @@ __device__ __forceinline__ int tab_off(int32_t inc, int c) {
 
 // output.c yuv2rgb_write_full (RGB24): 2^22-scaled sums, 30-bit clip
 __device__ __forceinline__ void full_rgb(const BatchParams& p, int Y, int U, int V, int* rgb) {
-  Y -= p.y_offset;
-  Y *= p.y_coeff;
+  Y -= p.csc.y_offset;
+  Y *= p.csc.y_coeff;
   Y += 1 << 21;
-  int R = (int)((uint32_t)Y + (uint32_t)V * (uint32_t)p.v2r);
-  int G = (int)((uint32_t)Y + (uint32_t)V * (uint32_t)p.v2g + (uint32_t)U * (uint32_t)p.u2g);
-  int B = (int)((uint32_t)Y + (uint32_t)U * (uint32_t)p.u2b);
+  int R = (int)((uint32_t)Y + (uint32_t)V * (uint32_t)p.csc.v2r);
+  int G = (int)((uint32_t)Y + (uint32_t)V * (uint32_t)p.csc.v2g + (uint32_t)U * (uint32_t)p.csc.u2g);
+  int B = (int)((uint32_t)Y + (uint32_t)U * (uint32_t)p.csc.u2b);
   if ((R | G | B) & 0xC0000000) {
     auto c30 = [](int a) { return (a & ~((1 << 30) - 1)) ? ((~a) >> 31) & ((1 << 30) - 1) : a; };
     R = c30(R);
@@ -5392,7 +5359,7 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
       hpass(planes + dd.plane_off[c], dd.plane_stride[c], in.comp_hpx[c], T + s.off[kHlPos],
             reinterpret_cast<const int16_t*>(T + s.off[kHlCoef]), s.hl_size, s.hl_taps, xs0, ncl,
             lr0, lr1, c == 0 ? hl : c == 1 ? hu : hv, lst, t3, third);
-  } else if (content && !(p.debug_mask & 0x100)) {  // (debug_mask: timing ablations only)
+  } else if (content && !(p.debug_mask & kAblSwsHpass)) {
     hpass(planes + dd.plane_off[0], dd.plane_stride[0], in.comp_hpx[0], T + s.off[kHlPos],
           reinterpret_cast<const int16_t*>(T + s.off[kHlCoef]), s.hl_size, s.hl_taps, xs0, ncl,
           lr0, lr1, hl, lst, tid, nt);
@@ -5407,7 +5374,7 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
   }
   __syncthreads();
   const bool pairs = !s.full && !s.gbr && !s.gray;
-  if (content && pairs && !(p.debug_mask & 0x200)) {
+  if (content && pairs && !(p.debug_mask & kAblSwsVpass)) {
     // The table writers (yuv2rgb_{X,2,1}_c) share one U, V between the two
     // pixels of a chroma column: a work item owns chroma column cx0 + cc and
     // those of luma columns 2 (cx0 + cc), + 1 that lie in [xs0, xs1) -- a
@@ -5472,9 +5439,9 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
           }
         }
         // the chroma terms of the first and last channel swap with the channels
-        const int tr = tab_off(p.crv, V), tb = tab_off(p.cbu, U);
+        const int tr = tab_off(p.csc.crv, V), tb = tab_off(p.csc.cbu, U);
         const int t0 = swap ? tb : tr, t2 = swap ? tr : tb;
-        const int t1 = tab_off(p.cgu, U) + tab_off(p.cgv, V);
+        const int t1 = tab_off(p.csc.cgu, U) + tab_off(p.csc.cgv, V);
         const int yo = ys0 + r + dd.dy, xo = xs0 + xe + dd.dx;
         if (h0) putc(xo, yo, clip_i8(Y0 + t0), clip_i8(Y0 + t1), clip_i8(Y0 + t2));
         if (h1) putc(xo + 1, yo, clip_i8(Y1 + t0), clip_i8(Y1 + t1), clip_i8(Y1 + t2));
@@ -5485,7 +5452,7 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
         r++;
       }
     }
-  } else if (content && !(p.debug_mask & 0x200)) {
+  } else if (content && !(p.debug_mask & kAblSwsVpass)) {
     // vertical taps + RGB24 writer, one scaled column per thread
     const int npl = s.vl_size / 2, npc = s.vc_size / 2;  // tap pairs per row
     for (int cl = tid; cl < ncl; cl += nt) {
@@ -5572,15 +5539,15 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
               V = (v0 * (4096 - ua) + v1 * ua + (128 << 11)) >> 19;
             }
           }
-          rgb[0] = clip_i8(Y + tab_off(p.crv, V));
-          rgb[1] = clip_i8(Y + tab_off(p.cgu, U) + tab_off(p.cgv, V));
-          rgb[2] = clip_i8(Y + tab_off(p.cbu, U));
+          rgb[0] = clip_i8(Y + tab_off(p.csc.crv, V));
+          rgb[1] = clip_i8(Y + tab_off(p.csc.cgu, U) + tab_off(p.csc.cgv, V));
+          rgb[2] = clip_i8(Y + tab_off(p.csc.cbu, U));
         }
         put(xs + dd.dx, ys + dd.dy, rgb);
       }
     }
   }
-  if (!u8 || (p.debug_mask & 0x400)) return;
+  if (!u8 || (p.debug_mask & kAblSwsStore)) return;
   __syncthreads();
   // the u8 tile out with wide stores: whole rows of an interleaved image are
   // one contiguous run, planar ones three
@@ -5791,9 +5758,9 @@ __device__ __forceinline__ void rgbu_group(const uint32_t (&yw)[PX / 4], const u
     const int Y = (int)((yw[i >> 2] >> (8 * (i & 3))) & 0xFFu);
     const int U = (int)((uw[i >> 3] >> (8 * ((i >> 1) & 3))) & 0xFFu);
     const int V = (int)((vw[i >> 3] >> (8 * ((i >> 1) & 3))) & 0xFFu);
-    const int r = clip_i8(Y + tab_off(p.crv, V));
-    const int gg = clip_i8(Y + tab_off(p.cgu, U) + tab_off(p.cgv, V));
-    const int b = clip_i8(Y + tab_off(p.cbu, U));
+    const int r = clip_i8(Y + tab_off(p.csc.crv, V));
+    const int gg = clip_i8(Y + tab_off(p.csc.cgu, U) + tab_off(p.csc.cgv, V));
+    const int b = clip_i8(Y + tab_off(p.csc.cbu, U));
     c0[i] = (uint32_t)(swap ? b : r);
     c1[i] = (uint32_t)gg;
     c2[i] = (uint32_t)(swap ? r : b);
@@ -5955,33 +5922,6 @@ __global__ void __launch_bounds__(kFusedThreads) idct_rgb_kernel(const uint32_t*
   }
 }
 
-hipError_t launch_idct_rgb(const uint32_t* ents, const uint2* bdesc, const ImageDesc* desc,
-                           const ImageInfo* infos, void* out, const BatchParams& p, int idct,
-                           int tiles, int n, int32_t* host_status, hipStream_t st) {
-  const dim3 grid(tiles, n);
-  uint8_t* o = static_cast<uint8_t*>(out);
-  if (idct == 2)  // timing ablation (debug_mask 0x800)
-    hipLaunchKernelGGL(idct_rgb_kernel<2>, grid, dim3(kFusedThreads), 0, st, ents, bdesc, desc, infos, o, p,
-                       host_status);
-  else if (idct == 1)
-    hipLaunchKernelGGL(idct_rgb_kernel<1>, grid, dim3(kFusedThreads), 0, st, ents, bdesc, desc, infos, o, p,
-                       host_status);
-  else
-    hipLaunchKernelGGL(idct_rgb_kernel<0>, grid, dim3(kFusedThreads), 0, st, ents, bdesc, desc, infos, o, p,
-                       host_status);
-  return hipGetLastError();
-}
-
-hipError_t launch_rgb_unscaled(const uint8_t* planes, const ImageDesc* desc,
-                               const ImageInfo* infos, void* out, const BatchParams& p,
-                               int64_t max_px, int n, int32_t* host_status, hipStream_t st) {
-  const int64_t groups = (max_px + kRgbPx - 1) / kRgbPx + 64;
-  const int gx = (int)std::min<int64_t>((groups + 255) / 256, 1024);
-  hipLaunchKernelGGL(rgb_unscaled_kernel, dim3(gx, n), dim3(256), 0, st, planes, desc, infos,
-                     static_cast<uint8_t*>(out), p, host_status);
-  return hipGetLastError();
-}
-
 // FFmpeg mjpeg's in-decoder conversion of a 4-component frame (oracle
 // jo_cmyk_transform; parity unpinned), in place on the IDCT planes:
 //   Adobe 0 (GBRAP): inverted CMYK -> RGB, R = c k 257 >> 16 ...
@@ -6038,84 +5978,6 @@ __global__ void __launch_bounds__(256) cmyk_kernel(const ImageDesc* __restrict__
   }
 }
 
-// ---------------------------------------------------------------------------
-// launchers (host side, same TU)
-// ---------------------------------------------------------------------------
-
-hipError_t launch_parse(const uint8_t* bytes, const ImageDesc* host_desc, ImageDesc* desc,
-                        ImageInfo* infos, HuffTable* luts, const void* host_tables, void* tables,
-                        int64_t table_bytes, const uint32_t* host_work, uint32_t* work, int nwork,
-                        uint64_t* chain, uint32_t* ds_map, uint32_t* idct_map, uint32_t* hs_map,
-                        uint32_t* sws_map, int threads, int n, hipStream_t st) {
-  hipLaunchKernelGGL(parse_kernel, dim3(n), dim3(threads), 0, st, bytes, host_desc, desc, infos, luts,
-                     static_cast<const uint4*>(host_tables), static_cast<uint4*>(tables),
-                     (table_bytes + 15) / 16, host_work, work, nwork, chain, ds_map, idct_map,
-                     hs_map, sws_map);
-  hipLaunchKernelGGL(lut_kernel, dim3(8, n), dim3(256), 0, st, bytes, desc, infos, luts);
-  return hipGetLastError();
-}
-hipError_t launch_destuff(const uint8_t* bytes, const ImageDesc* desc, ImageInfo* infos,
-                          DsChunk* chunks, uint8_t* clean, uint32_t* segs, const uint32_t* ds_map,
-                          int ds_wgs, int max_chunks, int n, hipStream_t st) {
-  // ds_map null: the (max chunks, image) grid of a batch of similar sizes
-  const dim3 grid = ds_map ? dim3(ds_wgs) : dim3(max_chunks, n);
-  hipLaunchKernelGGL(destuff_count_kernel, grid, dim3(kDsThreads), 0, st, bytes, desc, infos,
-                     chunks, ds_map);
-  hipLaunchKernelGGL(destuff_prefix_kernel, dim3(n), dim3(kDsThreads), 0, st, desc, infos, chunks);
-  hipLaunchKernelGGL(destuff_write_kernel, grid, dim3(kDsThreads), 0, st, bytes, desc, infos,
-                     chunks, clean, segs, ds_map);
-  return hipGetLastError();
-}
-hipError_t launch_entropy(const uint8_t* clean, const uint32_t* segs, const ImageDesc* desc,
-                          ImageInfo* infos, const HuffTable* luts, uint32_t* ents, uint2* bdesc,
-                          uint32_t* recs, const uint32_t* work, uint64_t* chain, int sub_bits,
-                          int warm_slots, int threads, int lds_pad, int nwork,
-                          int64_t handoff_ticks, hipStream_t st) {
-  // one workgroup per work item (image or piece); wide scans take the
-  // HBM-table loops inside
-#define HJ_ENT(T, NTAB)                                                                       \
-  hipLaunchKernelGGL((entropy_kernel<T, NTAB>), dim3(nwork), dim3(T), lds_pad, st, clean, segs, \
-                     desc, infos, luts, ents, bdesc, recs, work, chain, sub_bits, warm_slots,    \
-                     nwork, handoff_ticks)
-  if (threads == 1024) {
-    HJ_ENT(1024, 4);
-  } else if (threads == 512) {
-    HJ_ENT(512, 4);
-  } else if (threads == 128) {
-    HJ_ENT(128, 4);
-  } else {
-    HJ_ENT(256, 4);
-  }
-#undef HJ_ENT
-  return hipGetLastError();
-}
-hipError_t launch_idct(const uint32_t* ents, const uint2* bdesc, const ImageDesc* desc,
-                       const ImageInfo* infos, uint8_t* planes, int idct, const uint32_t* idct_map,
-                       int idct_wgs, int max_blocks, int n, int xcd, hipStream_t st) {
-  // flat: every image's tiles, no empty workgroups; idct_map null: (max
-  // tiles, image)
-  const dim3 grid = idct_map ? dim3(idct_wgs)
-                             : dim3((max_blocks + kIdctThreads - 1) / kIdctThreads, n);
-  if (idct == 2)  // timing ablation (debug_mask 0x800): no transform, wrong output
-    hipLaunchKernelGGL(idct_kernel<2>, grid, dim3(kIdctThreads), 0, st, ents, bdesc, desc, infos,
-                       planes, idct_map, xcd);
-  else if (idct == 1)
-    hipLaunchKernelGGL(idct_kernel<1>, grid, dim3(kIdctThreads), 0, st, ents, bdesc, desc, infos,
-                       planes, idct_map, xcd);
-  else
-    hipLaunchKernelGGL(idct_kernel<0>, grid, dim3(kIdctThreads), 0, st, ents, bdesc, desc, infos,
-                       planes, idct_map, xcd);
-  return hipGetLastError();
-}
-hipError_t launch_csc(const uint8_t* planes, const ImageDesc* desc, const ImageInfo* infos,
-                      void* out, const BatchParams& p, int64_t max_px, int n, int32_t* host_status,
-                      hipStream_t st) {
-  int64_t gx64 = (max_px + 255) / 256;
-  int gx = (int)(gx64 < 4096 ? gx64 : 4096);
-  hipLaunchKernelGGL(csc_kernel, dim3(gx, n), dim3(256), 0, st, planes, desc, infos, out, p,
-                     host_status);
-  return hipGetLastError();
-}
 // ---------------------------------------------------------------------------
 // NV12 -> planar RGB/BGR (the video path's colour conversion; reference
 // src/libspdl/cuda/detail/color_conversion.cu:90-138).  One thread per 2x2
@@ -6176,36 +6038,118 @@ hipError_t launch_nv12(const uint8_t* src, uint8_t* dst, int frames, int height,
   return hipGetLastError();
 }
 
-hipError_t launch_sws(const uint8_t* planes, const ImageDesc* desc, const ImageInfo* infos,
-                      const int32_t* pool, void* out, const BatchParams& p,
-                      const uint32_t* sws_map, int sws_wgs, int bands, int chunks, int n,
-                      int lds_bytes, int32_t* host_status, const uint32_t* hs_map, int hs_wgs,
-                      int16_t* hbuf, hipStream_t st) {
-  if (hs_wgs > 0)
-    hipLaunchKernelGGL(hscale_kernel, dim3(hs_wgs), dim3(256), 0, st, planes, desc, infos, pool,
-                       hs_map, hbuf);
-  const dim3 grid = sws_map ? dim3(sws_wgs) : dim3(bands, chunks, n);
-  hipLaunchKernelGGL(sws_kernel, grid, dim3(256), lds_bytes, st, planes, desc, infos, pool, out, p,
-                     host_status, hbuf, sws_map);
+// ---------------------------------------------------------------------------
+// launchers (host side, same TU; declared in hj_launch.h)
+// ---------------------------------------------------------------------------
+
+hipError_t launch_parse(const BatchBuffers& b, const ImageDesc* host_desc, const void* host_tables,
+                        int64_t table_bytes, int threads, hipStream_t st) {
+  const auto* host_work = host_desc ? reinterpret_cast<const uint32_t*>(host_desc + b.n) : nullptr;
+  hipLaunchKernelGGL(parse_kernel, dim3(b.n), dim3(threads), 0, st, b.bytes, host_desc, b.desc,
+                     b.infos, b.luts, static_cast<const uint4*>(host_tables),
+                     reinterpret_cast<uint4*>(b.wts), (table_bytes + 15) / 16, host_work, b.work,
+                     b.nwork, b.chain, b.ds_map, b.idct_map, b.hs_map, b.sws_map);
+  hipLaunchKernelGGL(lut_kernel, dim3(8, b.n), dim3(256), 0, st, b.bytes, b.desc, b.infos, b.luts);
   return hipGetLastError();
 }
-hipError_t launch_yuv_planes(const uint8_t* planes, const ImageDesc* desc, const ImageInfo* infos,
-                             const int32_t* pool, void* out, const uint32_t* sws_map, int sws_wgs,
-                             int lds_bytes, int32_t* host_status, const uint32_t* hs_map,
-                             int hs_wgs, int16_t* hbuf, hipStream_t st) {
-  if (hs_wgs > 0)
-    hipLaunchKernelGGL(hscale_kernel, dim3(hs_wgs), dim3(256), 0, st, planes, desc, infos, pool,
-                       hs_map, hbuf);
-  // (always the flat grid: every image's own tiles, three planes each)
-  hipLaunchKernelGGL(yuv_planes_kernel, dim3(sws_wgs), dim3(256), lds_bytes, st, planes, desc,
-                     infos, pool, static_cast<uint8_t*>(out), host_status, hbuf, sws_map);
+hipError_t launch_destuff(const BatchBuffers& b, bool flat, int ds_wgs, int max_chunks,
+                          hipStream_t st) {
+  // not flat: the (max chunks, image) grid of a batch of similar sizes
+  const dim3 grid = flat ? dim3(ds_wgs) : dim3(max_chunks, b.n);
+  const uint32_t* map = flat ? b.ds_map : nullptr;
+  hipLaunchKernelGGL(destuff_count_kernel, grid, dim3(kDsThreads), 0, st, b.bytes, b.desc, b.infos,
+                     b.dschunks, map);
+  hipLaunchKernelGGL(destuff_prefix_kernel, dim3(b.n), dim3(kDsThreads), 0, st, b.desc, b.infos,
+                     b.dschunks);
+  hipLaunchKernelGGL(destuff_write_kernel, grid, dim3(kDsThreads), 0, st, b.bytes, b.desc, b.infos,
+                     b.dschunks, b.clean, b.segs, map);
   return hipGetLastError();
 }
-hipError_t launch_cmyk(const ImageDesc* desc, const ImageInfo* infos, uint8_t* planes,
-                       int64_t max_px, int n, hipStream_t st) {
+hipError_t launch_entropy(const BatchBuffers& b, const EntropyParams& ep, int threads, int lds_pad,
+                          hipStream_t st) {
+  // one workgroup per work item (image or piece)
+#define HJ_ENT(T, NTAB)                                                                        \
+  hipLaunchKernelGGL((entropy_kernel<T, NTAB>), dim3(b.nwork), dim3(T), lds_pad, st, b.clean,  \
+                     b.segs, b.desc, b.infos, b.luts, b.ents, b.bdesc, b.recs, b.work, b.chain, \
+                     ep, b.nwork)
+  switch (threads) {
+    case 1024: HJ_ENT(1024, 4); break;
+    case 512: HJ_ENT(512, 4); break;
+    case 128: HJ_ENT(128, 4); break;
+    default: HJ_ENT(256, 4);
+  }
+#undef HJ_ENT
+  return hipGetLastError();
+}
+hipError_t launch_multiscan(const BatchBuffers& b, hipStream_t st) {
+  hipLaunchKernelGGL(multiscan_kernel, dim3(b.n), dim3(256), 0, st, b.bytes, b.clean, b.desc,
+                     b.infos, b.ents, b.bdesc);
+  return hipGetLastError();
+}
+// kernel K's instance for an IDCT kind: 0 simple, 1 islow, 2 none (kAblIdctNone)
+#define HJ_IDCT_KIND(K, kind, ...)                               \
+  do {                                                           \
+    if ((kind) == 2) hipLaunchKernelGGL(K<2>, __VA_ARGS__);      \
+    else if ((kind) == 1) hipLaunchKernelGGL(K<1>, __VA_ARGS__); \
+    else hipLaunchKernelGGL(K<0>, __VA_ARGS__);                  \
+  } while (0)
+hipError_t launch_idct(const BatchBuffers& b, int idct, bool flat, int idct_wgs, int max_blocks,
+                       int xcd, hipStream_t st) {
+  // flat: every image's tiles, no empty workgroups; else (max tiles, image)
+  const int max_tiles = (max_blocks + kIdctThreads - 1) / kIdctThreads;
+  const dim3 grid = flat ? dim3(idct_wgs) : dim3(max_tiles, b.n);
+  HJ_IDCT_KIND(idct_kernel, idct, grid, dim3(kIdctThreads), 0, st, b.ents, b.bdesc, b.desc, b.infos,
+               b.planes, flat ? b.idct_map : nullptr, xcd);
+  return hipGetLastError();
+}
+hipError_t launch_idct_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int idct,
+                           int tiles, int32_t* host_status, hipStream_t st) {
+  HJ_IDCT_KIND(idct_rgb_kernel, idct, dim3(tiles, b.n), dim3(kFusedThreads), 0, st, b.ents, b.bdesc,
+               b.desc, b.infos, static_cast<uint8_t*>(out), p, host_status);
+  return hipGetLastError();
+}
+#undef HJ_IDCT_KIND
+hipError_t launch_cmyk(const BatchBuffers& b, int64_t max_px, hipStream_t st) {
   // max_px: the largest 4-component image of the batch (grid-stride beyond)
   const int gx = (int)std::min<int64_t>((max_px / 4 + 255) / 256 + 1, 1024);
-  hipLaunchKernelGGL(cmyk_kernel, dim3(gx, n), dim3(256), 0, st, desc, infos, planes);
+  hipLaunchKernelGGL(cmyk_kernel, dim3(gx, b.n), dim3(256), 0, st, b.desc, b.infos, b.planes);
+  return hipGetLastError();
+}
+hipError_t launch_csc(const BatchBuffers& b, void* out, const BatchParams& p, int64_t max_px,
+                      int32_t* host_status, hipStream_t st) {
+  const int gx = (int)std::min<int64_t>((max_px + 255) / 256, 4096);
+  hipLaunchKernelGGL(csc_kernel, dim3(gx, b.n), dim3(256), 0, st, b.planes, b.desc, b.infos, out, p,
+                     host_status);
+  return hipGetLastError();
+}
+hipError_t launch_rgb_unscaled(const BatchBuffers& b, void* out, const BatchParams& p,
+                               int64_t max_px, int32_t* host_status, hipStream_t st) {
+  const int64_t groups = (max_px + kRgbPx - 1) / kRgbPx + 64;
+  const int gx = (int)std::min<int64_t>((groups + 255) / 256, 1024);
+  hipLaunchKernelGGL(rgb_unscaled_kernel, dim3(gx, b.n), dim3(256), 0, st, b.planes, b.desc,
+                     b.infos, static_cast<uint8_t*>(out), p, host_status);
+  return hipGetLastError();
+}
+static void launch_hscale(const BatchBuffers& b, int hs_wgs, hipStream_t st) {
+  if (hs_wgs > 0)
+    hipLaunchKernelGGL(hscale_kernel, dim3(hs_wgs), dim3(256), 0, st, b.planes, b.desc, b.infos,
+                       b.wts, b.hs_map, b.hbuf);
+}
+hipError_t launch_sws(const BatchBuffers& b, void* out, const BatchParams& p, bool flat,
+                      int sws_wgs, int bands, int chunks, int lds_bytes, int hs_wgs,
+                      int32_t* host_status, hipStream_t st) {
+  launch_hscale(b, hs_wgs, st);
+  const dim3 grid = flat ? dim3(sws_wgs) : dim3(bands, chunks, b.n);
+  hipLaunchKernelGGL(sws_kernel, grid, dim3(256), lds_bytes, st, b.planes, b.desc, b.infos, b.wts,
+                     out, p, host_status, b.hbuf, flat ? b.sws_map : nullptr);
+  return hipGetLastError();
+}
+hipError_t launch_yuv_planes(const BatchBuffers& b, void* out, int sws_wgs, int lds_bytes,
+                             int hs_wgs, int32_t* host_status, hipStream_t st) {
+  launch_hscale(b, hs_wgs, st);
+  // (always the flat grid: every image's own tiles, three planes each)
+  hipLaunchKernelGGL(yuv_planes_kernel, dim3(sws_wgs), dim3(256), lds_bytes, st, b.planes, b.desc,
+                     b.infos, b.wts, static_cast<uint8_t*>(out), host_status, b.hbuf, b.sws_map);
   return hipGetLastError();
 }
 

@@ -41,12 +41,7 @@ struct SwsPlan {
   std::vector<int32_t> vmode;  // per output row
 };
 
-// Coefficients of ff_yuv2rgb_c_init_tables for a full-range BT.601 source.
-struct SwsCsc {
-  int32_t crv, cbu, cgu, cgv;                    // table increments (cy-scaled)
-  int32_t y_coeff, y_offset, v2r, v2g, u2g, u2b;  // yuv2rgb_write_full
-};
-SwsCsc sws_csc();
+SwsCsc sws_csc();  // (hj_common.h)
 
 // kind: SPDL_HJ_FILTER_*.  Returns 0, or an SPDL_HJ_ERR_* code (a filter
 // longer than swscale handles without cascading: BAD_GEOMETRY).
