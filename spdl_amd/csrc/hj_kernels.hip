@@ -2597,7 +2597,7 @@ entropy_kernel(const uint8_t* __restrict__ clean, const uint32_t* __restrict__ s
 //   - Huffman tables as VGPRs read with v_readlane at a uniform lane
 //     (RTab: a 6-bit first level, the canonical limits for the rest);
 //   - a block's coefficients gathered in the lanes of one VGPR (v_writelane)
-//     and stored as one coalesced band store;
+//     and stored in one instruction (an AC first scan: the coded lanes);
 //   - AC refinement: 64-block chunks, the blocks' non-zero masks in VGPR
 //     lanes (prefetched a chunk ahead), the correction / new-coefficient
 //     records written to the lanes of the decoding block, and applied by
@@ -3688,7 +3688,6 @@ __device__ __forceinline__ int ms_decode_scan(MsShared& S, int si, uint64_t soft
   int32_t pred[kMaxComp] = {0, 0, 0, 0};
   int eobrun = 0;
   const int al = sc.al, ss = sc.ss, se = sc.se;
-  const bool inband = lane >= ss && lane <= se;
   const uint64_t band = ms_range(ss, se);
   uint32_t vblk = 0;  // the block being decoded, lane k = coefficient k
   RTab atr;  // AC refinement: the table with packed first-level entries
@@ -3851,7 +3850,10 @@ __device__ __forceinline__ int ms_decode_scan(MsShared& S, int si, uint64_t soft
             }
             if (rc != kOk) break;
             if (nz) {
-              if (inband) blev[lane] = (int32_t)vblk;
+              // only the coefficients the scan codes (oracle ms_block_decode,
+              // libjpeg decode_mcu_AC_first): a first scan whose band overlaps
+              // an earlier one's leaves that scan's other values alone
+              if ((nz >> lane) & 1ull) blev[lane] = (int32_t)vblk;
               vblk = 0;
               if (ms_lane0()) atomicOr(reinterpret_cast<unsigned long long*>(masks + b), nz);
             }
@@ -4298,7 +4300,10 @@ __global__ void __launch_bounds__(256) multiscan_kernel(const uint8_t* __restric
       for (int k = 0; k < y.ns; k++) cy |= 1 << y.comp[k];
       const int ly = prog ? y.ss : 0, hy = prog ? y.se : 63;
       if ((cx & cy) && !(hy < lx || hx < ly)) {
-        if (xac && y.ss > 0) sm |= 1ull << j;  // (AC scans have one component)
+        // (AC scans have one component; only a refinement scan trails: a
+        // first scan does not wait on its way, so one whose band overlaps an
+        // earlier AC scan's -- no legal progression -- starts after it)
+        if (xac && x.ah != 0 && y.ss > 0) sm |= 1ull << j;
         else m |= 1ull << j;
       }
     }

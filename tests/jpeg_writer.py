@@ -1,4 +1,6 @@
-"""Coefficient-level baseline JPEG writer (ITU-T T.81), for tests.
+"""Coefficient-level JPEG writer (ITU-T T.81), for tests: baseline, and
+progressive by a scan script (spectral selection, successive approximation,
+EOB runs).
 
 Every other JPEG the suite decodes was made by an encoder from pixels, so it
 only holds what an encoder emits.  `write_jpeg` takes the quantised levels,
@@ -90,6 +92,36 @@ def flat_table(symbols, length: int | None = None):
     bits = [0] * 16
     bits[length - 1] = len(symbols)
     return bits, symbols
+
+
+def ranked_table(symbols, share: int = 4):
+    """Code lengths that grow along `symbols` the way an optimiser's do along
+    falling frequencies: each symbol takes the shortest length (from 2 bits)
+    that costs at most 1 / `share` of the code space still free and leaves
+    every later symbol a 16-bit code; the all-ones code stays free."""
+    symbols = list(symbols)
+    bits = [0] * 16
+    free = (1 << 16) - 1  # in units of 2^-16
+    length = 2
+    for i in range(len(symbols)):
+        later = len(symbols) - i - 1
+        while length < 16 and (1 << (16 - length)) * share > free - later:
+            length += 1
+        bits[length - 1] += 1
+        free -= 1 << (16 - length)
+        assert free >= later
+    _check_kraft(bits)
+    return bits, symbols
+
+
+def progressive_ac_symbols():
+    """The alphabet of a progressive AC scan -- EOB0..EOB14, ZRL, the 240
+    (run, size) pairs; Annex K's tables hold no EOBn above 0 -- short runs
+    and small sizes first."""
+    def rank(sym):
+        r, s = sym >> 4, sym & 15
+        return (r + 2 if r < 15 else 6) if s == 0 else r + 2 * s
+    return sorted([n << 4 for n in range(1, 15)] + AC_SYMBOLS, key=lambda sym: (rank(sym), sym))
 
 
 def short_table(inverted: bool = False) -> dict:
@@ -189,12 +221,15 @@ class _Coder:
         self.bw = bw
         self.codes = {k: canonical_codes(*t) for k, t in dht.items()}
         self.stats = stats
+        self.sst = None  # the statistics of one scripted scan
 
     def sym(self, cls: str, tid: int, symbol: int) -> None:
         code, length = self.codes[(cls, tid)][symbol]
         self.bw.put(code, length)
         if self.stats is not None:
             self.stats[(cls, tid)][symbol] += 1
+        if self.sst is not None:
+            self.sst[cls][symbol] += 1
 
     def block(self, lv, pred: int, td: int, ta: int, extra) -> int:
         """One block (64 levels, zig-zag order, lv[0] absolute). Returns the new predictor."""
@@ -260,6 +295,128 @@ class _Coder:
         if last < se:
             self.sym("ac", ta, EOB)
 
+    # -- scripted progressive scans (T.81 G.1.2): successive approximation and
+    # -- EOB runs.  One coder per scan; `run` is the pending EOBRUN, `run_bits`
+    # -- the correction bits of its blocks, written after the EOBn symbol.
+
+    def begin(self, policy, sst) -> None:
+        """policy: 0 closes every block on its own (EOB0), n > 0 lets a run
+        grow to the largest length of category n (2^(n+1) - 1 blocks), "max"
+        to 32767; sst: this scan's statistics (or None)."""
+        self.limit = 32767 if policy == "max" else 1 if policy == 0 else min((2 << policy) - 1, 32767)
+        self.run, self.run_bits, self.sst = 0, [], sst
+
+    def _field(self, bits) -> None:
+        """One correction-bit field: the bits a decoder takes in one step."""
+        for b in bits:
+            self.bw.put(b, 1)
+        if self.sst is not None and bits:
+            self.sst["corr_fields"][len(bits)] += 1
+
+    def flush_run(self, ta: int) -> None:
+        if self.run:
+            n = self.run.bit_length() - 1
+            self.sym("ac", ta, n << 4)
+            self.bw.put(self.run - (1 << n), n)
+            if self.sst is not None:
+                self.sst["eob"][n] += 1
+            self.run = 0
+        for bits in self.run_bits:
+            self._field(bits)
+        self.run_bits = []
+
+    def _close(self, ta: int, bits) -> None:
+        """The block ends inside an EOB run, which carries its correction bits."""
+        if self.sst is not None and self.run and bits:
+            self.sst["corr_bits_inside_runs"] += len(bits)
+        self.run += 1
+        self.run_bits.append(list(bits))
+        if self.run >= self.limit:
+            self.flush_run(ta)
+
+    def _raw(self, td: int, ta: int, extra) -> None:
+        for cls, symbol, value, nbits in extra:
+            self.sym(cls, td if cls == "dc" else ta, symbol)
+            self.bw.put(value, nbits)
+
+    def dc_first_al(self, lv0: int, pred: int, td: int, al: int) -> int:
+        """DC first scan: the difference of level >> Al (arithmetic shift)."""
+        return self.dc_first(int(lv0) >> al, pred, td)
+
+    def dc_refine(self, lv0: int, al: int) -> None:
+        self.bw.put((int(lv0) >> al) & 1, 1)
+
+    def ac_first_al(self, lv, ss: int, se: int, al: int, td: int, ta: int, extra) -> None:
+        """AC first scan of [ss, se]: sign * (|level| >> Al), with EOB runs."""
+        if extra is None and not np.any(lv[ss:se + 1]):
+            return self._close(ta, [])
+        run = 0
+        for k in range(ss, se + 1):
+            v = int(lv[k])
+            a = abs(v) >> al
+            if a == 0:
+                run += 1
+                continue
+            self.flush_run(ta)
+            while run > 15:
+                self.sym("ac", ta, ZRL)
+                run -= 16
+            s = a.bit_length()
+            assert s <= 15
+            self.sym("ac", ta, (run << 4) | s)
+            self.bw.put(_amp(a if v > 0 else -a, s), s)
+            run = 0
+        if extra is not None:
+            self.flush_run(ta)
+            self._raw(td, ta, extra)
+        elif run:
+            self._close(ta, [])
+
+    def ac_refine(self, lv, ss: int, se: int, ah: int, al: int, td: int, ta: int, extra,
+                  repeat: bool) -> None:
+        """AC refinement of [ss, se] at bit Al.  History: |level| >> Ah != 0.
+        A coefficient that turns non-zero is coded (run of zero-history
+        coefficients, 1) plus its sign; every history coefficient passed adds
+        one correction bit, written after the symbol that passes it (or after
+        the EOBn of the run the block ends in); 16 zero-history coefficients
+        in front of a new one are a ZRL.  `repeat`: the scan comes a second
+        time -- the history is |level| >> Al, nothing is new and every
+        correction bit is 1.  `extra`: raw symbols in place of the block's
+        EOB; the block's remaining correction bits follow them."""
+        if extra is None and not np.any(lv[ss:se + 1]):
+            return self._close(ta, [])
+        hs = al if repeat else ah
+        mag = [abs(int(lv[k])) for k in range(se + 1)]
+        hist = [m >> hs != 0 for m in mag]
+        new = [not h and m >> al != 0 for h, m in zip(hist, mag)]
+        last_new = max((k for k in range(ss, se + 1) if new[k]), default=ss - 1)
+        run, bits = 0, []
+        for k in range(ss, se + 1):
+            if not hist[k] and not new[k]:
+                run += 1
+                continue
+            while run > 15 and k <= last_new:
+                self.flush_run(ta)
+                self.sym("ac", ta, ZRL)
+                run -= 16
+                self._field(bits)
+                bits = []
+            if hist[k]:
+                bits.append(1 if repeat else (mag[k] >> al) & 1)
+                continue
+            assert mag[k] >> al == 1, "a coefficient enters a refinement scan as +-1"
+            self.flush_run(ta)
+            self.sym("ac", ta, (run << 4) | 1)
+            self.bw.put(1 if lv[k] > 0 else 0, 1)
+            self._field(bits)
+            run, bits = 0, []
+        if extra is not None:
+            self.flush_run(ta)
+            self._raw(td, ta, extra)
+            self._field(bits)
+        elif run or bits:
+            self._close(ta, bits)
+
 
 # ---- the writer -------------------------------------------------------------
 
@@ -270,9 +427,10 @@ def _seg(marker: int, payload: bytes) -> bytes:
 def write_jpeg(width, height, samp, levels, qtables, tq, dht, td, ta, *, restart_interval=0,
                pq=0, comp_ids=(1, 2, 3, 4), scans="interleaved", rst_fill=0, adobe=None,
                extra_symbols=None, emit_dri=False, table_segments="merged", stats=None,
-               bands=((1, 5), (6, 63))) -> bytes:
+               bands=((1, 5), (6, 63)), script=None) -> bytes:
     """A baseline (SOF0) JPEG of the given quantised levels (or, with
-    scans="spectral", a progressive one by spectral selection alone).
+    scans="spectral", a progressive one by spectral selection alone; with
+    scans="script", a progressive one scan by scan as `script` lists them).
 
     samp      [(h, v)] per component
     levels    per component [bh, bw, 64] (block_grids' first shape), zig-zag
@@ -297,7 +455,35 @@ def write_jpeg(width, height, samp, levels, qtables, tq, dht, td, ta, *, restart
               non-zero coefficient, in place of the EOB
     table_segments  "merged": one DQT and one DHT segment hold all tables;
               "single": one segment per table
-    stats     a dict, filled with {(cls, id): Counter(symbol -> count)}
+    stats     a dict, filled with {(cls, id): Counter(symbol -> count)}; a
+              scripted stream adds stats["scans"], one dict per scan:
+              "entry" (components, ss, se, ah, al), "dc" / "ac"
+              Counter(symbol), "eob" Counter(EOBn category), "corr_fields"
+              Counter(length of a correction-bit field: the bits that follow
+              one symbol, or one block's bits inside an EOB run) and
+              "corr_bits_inside_runs" (correction bits of blocks a run skips)
+    script    scans="script": SOF2 with one SOS per entry
+              (components, ss, se, ah, al[, options]), coded by T.81 G.1.2:
+              DC first (the difference of level >> al), DC refinement (bit al
+              of the level), AC first (sign * (|level| >> al)) and AC
+              refinement, each with the entry's Ss / Se / Ah / Al bytes.
+              Several components make an interleaved scan (DC only), one
+              component a scan over its own grid.  Nothing checks that the
+              entries form a legal progression: the same refinement may come
+              twice and first scans may overlap.  options:
+                "eobrun"  0 (default): every block closed by its own EOB0; n:
+                          runs up to the longest of category n; "max": a run
+                          ends at 32767 blocks, at a restart and at the
+                          scan's end
+                "td", "ta"  table ids per component for this scan
+                "dht"     {(cls, id): table} written in a DHT segment in front
+                          of this SOS; replaces that id from here on
+                "levels"  levels this scan codes in place of `levels`
+                "repeat"  AC refinement written again at the same Al: the
+                          history is |level| >> al, every correction bit 1
+              extra_symbols is keyed (scan index, c, by, bx) here; in a
+              refinement scan the block's pending correction bits follow the
+              raw symbols
     """
     nc = len(samp)
     assert nc in (1, 3, 4) and len(levels) == nc
@@ -331,7 +517,7 @@ def write_jpeg(width, height, samp, levels, qtables, tq, dht, td, ta, *, restart
     sof = bytes([8]) + height.to_bytes(2, "big") + width.to_bytes(2, "big") + bytes([nc])
     for c in range(nc):
         sof += bytes([comp_ids[c], (samp[c][0] << 4) | samp[c][1], tq[c]])
-    out += _seg(0xC2 if scans == "spectral" else 0xC0, sof)
+    out += _seg(0xC2 if scans in ("spectral", "script") else 0xC0, sof)
     if table_segments == "merged":
         out += _seg(0xC4, b"".join(dhts))
     else:
@@ -340,11 +526,55 @@ def write_jpeg(width, height, samp, levels, qtables, tq, dht, td, ta, *, restart
     if restart_interval or emit_dri:
         out += _seg(0xDD, restart_interval.to_bytes(2, "big"))
 
-    def sos(comps, ss=0, se=63):
+    def sos(comps, ss=0, se=63, ahal=0, td=td, ta=ta):
         p = bytes([len(comps)])
         for c in comps:
             p += bytes([comp_ids[c], (td[c] << 4) | ta[c]])
-        return _seg(0xDA, p + bytes([ss, se, 0]))
+        return _seg(0xDA, p + bytes([ss, se, ahal]))
+
+    def script_scan(i, entry, tables):
+        comps, ss, se, ah, al = entry[:5]
+        opt = entry[5] if len(entry) > 5 else {}
+        comps = list(comps)
+        std, sta = opt.get("td", td), opt.get("ta", ta)
+        lvs = opt.get("levels", levels)
+        assert (ss == 0) == (se == 0) and (ss == 0 or len(comps) == 1)
+        if len(comps) > 1:
+            units = [[u for u in mcu if u[0] in comps] for mcu in mcus]
+        else:
+            bh, bw_ = grids[comps[0]][1]
+            units = [[(comps[0], y, x)] for y in range(bh) for x in range(bw_)]
+        sst = None
+        if stats is not None:
+            sst = {"entry": (tuple(comps), ss, se, ah, al), "dc": Counter(), "ac": Counter(),
+                   "eob": Counter(), "corr_fields": Counter(), "corr_bits_inside_runs": 0}
+            stats["scans"].append(sst)
+        bw = _Bits()
+        coder = _Coder(bw, tables, stats)
+        coder.begin(opt.get("eobrun", 0), sst)
+        pred = [0] * nc
+        for j, unit in enumerate(units):
+            if restart_interval and j and j % restart_interval == 0:
+                if ss:
+                    coder.flush_run(sta[comps[0]])
+                bw.marker(0xD0 + (j // restart_interval - 1) % 8, rst_fill)
+                pred = [0] * nc
+            for c, by, bx in unit:
+                lv = lvs[c][by][bx]
+                ex = extra_symbols.get((i, c, by, bx))
+                if ss == 0 and ah == 0:
+                    pred[c] = coder.dc_first_al(lv[0], pred[c], std[c], al)
+                elif ss == 0:
+                    coder.dc_refine(lv[0], al)
+                elif ah == 0 and not opt.get("repeat"):
+                    coder.ac_first_al(lv, ss, se, al, std[c], sta[c], ex)
+                else:
+                    coder.ac_refine(lv, ss, se, ah, al, std[c], sta[c], ex,
+                                    bool(opt.get("repeat")))
+        if ss:
+            coder.flush_run(sta[comps[0]])
+        bw.pad()
+        return sos(comps, ss, se, (ah << 4) | al, std, sta) + bytes(bw.out)
 
     def scan(comps, units, band=None):
         """units: per MCU, the list of (c, by, bx) blocks.  band: None for a
@@ -390,6 +620,22 @@ def write_jpeg(width, height, samp, levels, qtables, tq, dht, td, ta, *, restart
             for ss, se in bands:
                 out += sos([c], ss, se) + scan(
                     [c], [[(c, y, x)] for y in range(bh) for x in range(bw_)], (ss, se))
+    elif scans == "script":
+        tables = dict(dht)
+        if stats is not None:
+            stats["scans"] = []
+        for i, entry in enumerate(script):
+            more = entry[5].get("dht") if len(entry) > 5 else None
+            if more:
+                tables.update(more)
+                seg = b""
+                for (cls, tid), (bits, vals) in more.items():
+                    assert len(bits) == 16 and sum(bits) == len(vals)
+                    seg += bytes([((cls == "ac") << 4) | tid]) + bytes(bits) + bytes(vals)
+                    if stats is not None:
+                        stats.setdefault((cls, tid), Counter())
+                out += _seg(0xC4, seg)
+            out += script_scan(i, entry, tables)
     elif scans == "per_component":
         for c in range(nc):
             bh, bw_ = grids[c][1]

@@ -9,10 +9,12 @@ zig-zag order, tables, sampling) and the writer's symbol histogram.  Families:
   3  coefficient extremes (deep tables)   EXTREME_CASES (+ per_component twins)
   4  block structure  STRUCTURE_CASES
   5  spectral selection (SOF2 without refinement)   PROGRESSIVE_CASES
+  6  scan scripts (SOF2 with successive approximation, EOB runs, odd scan
+     orders, streams libjpeg only warns about)   SCRIPT_CASES, SCRIPT_BAD
 
-Families 1, 2, 4 and 5 keep amplitudes small (CAPPED: at most 25 % of the
-oracle's RGB samples at 0 or 255, asserted by the tests); family 3 saturates
-by nature.
+Families 1, 2, 4, 5 and most of 6 keep amplitudes small (CAPPED: at most 25 %
+of the oracle's RGB samples at 0 or 255, asserted by the tests); family 3 and
+SCRIPT_UNCAPPED saturate by nature or decode to other levels than were coded.
 """
 
 from __future__ import annotations
@@ -60,11 +62,14 @@ class Stream:
     scans: str = "interleaved"
     stats: dict = field(default_factory=dict)
     restart_interval: int = 0
+    script: list | None = None  # scans="script": the scan script
+    expect: list | None = None  # the levels a decoder returns, where they differ from `levels`
 
     def natural_levels(self):
-        """Per component [bh, bw, 64] in natural order (the oracle's layout)."""
+        """Per component [bh, bw, 64] in natural order (the oracle's layout):
+        the levels a decoder returns."""
         out = []
-        for lv in self.levels:
+        for lv in self.levels if self.expect is None else self.expect:
             nat = np.zeros_like(lv)
             nat[..., jw.NATURAL] = lv
             out.append(nat)
@@ -501,8 +506,332 @@ def _progressive_case(key) -> Stream:
 
 PROGRESSIVE_CASES = ["prog_" + k for k in PROGRESSIVE]
 
-CAPPED_CASES = SAMPLING_CASES + TABLE_CASES + STRUCTURE_CASES + PROGRESSIVE_CASES
-ACCEPTED_CASES = CAPPED_CASES + EXTREME_CASES
+
+# ---- family 6: scan scripts (SOF2 with successive approximation) -------------
+#
+# What each stream holds, counted by the writer (stats["scans"]): scans / AC
+# refinement scans / deepest Al / EOBn categories in AC first and in AC
+# refinement scans / longest correction-bit field / fields over 15 bits (the
+# kernel's ms_take_corr_long) / correction bits of blocks inside EOB runs /
+# the reader multiscan_kernel gives the scans by its rule (a restart interval:
+# the stuffed reader; else the word reader over the destuffed copy).
+#
+#   deep_al               21 12  5  0        0         17    1     0  word
+#   al13                  18  3 13  0        0..1      20    9    77  word
+#   dense_history          7  3  1  0        1         63   60  1302  word
+#   dense_history_17       7  3  1  -        0         17  141     0  word
+#   eob_runs               3  1  1  0..8     0..8       2    0    16  word
+#   eob_runs_cap1          3  1  1  0..1     0..1       2    0     8  word
+#   eob_run_14             5  2  1  3,4,9..14 3,4,9..14 1    0     0  word
+#   eob_restart_ri5        3  1  1  0..2     0..2       2    0    14  stuffed
+#   eob_restart_ri64       3  1  1  0..6     0..6       2    0    16  stuffed
+#   eob_restart_fill2      3  1  1  0..2     0..2       2    0    14  stuffed
+#   band_split            13  9  1  0        0..3       7    0   107  word
+#   band_merge            13  3  1  0..2     0..1       8    0     5  word
+#   band_merge_ri3        13  3  1  0..1     0          7    0     0  stuffed
+#   dc_per_component      12  0  1  0        -          0    0     0  word
+#   order                 10  4  1  0        0,1,3      6    0    47  word
+#   refine_tables          8  4  2  0        0..1       8    0    15  word
+#   all_ones               3  1  1  -        0..1      63   32    63  word
+#   all_ones_ri4           3  1  1  0        0         63   29     0  stuffed
+#   scans_64 / scans_65   64 / 65 one-coefficient bands, no refinement of AC
+#   repeat_refine          8  4  1  0        0,1,4     12    0   176  word
+#   overlap_first          5  0  0  0        -          0    0     0  word
+#   overlap_first_long     3  0  0  0,2      -          0    0     0  word
+#   zrl_overshoot_refine   7  3  1  0        0          7    0     0  word
+#
+# deep_al keeps Annex K's tables, which hold no EOBn above EOB0, so its blocks
+# close one by one; the streams with EOB runs use jw.ranked_table.
+
+# the alphabet of an AC refinement scan: EOB0..EOB14, ZRL, (r, 1) for r = 0..15
+REFINE_SYMBOLS = [n << 4 for n in range(15)] + [jw.ZRL] + [(r << 4) | 1 for r in range(16)]
+
+S420 = [(2, 2), (1, 1), (1, 1)]
+RUNS = {"eobrun": "max"}
+
+
+def _dc_chain(comps, al, **opt):
+    """A DC first scan at `al`, then one refinement per bit down to 0."""
+    return [(comps, 0, 0, 0, al, opt)] + [(comps, 0, 0, a + 1, a, opt) for a in range(al - 1, -1, -1)]
+
+
+def _ac_chain(c, ss, se, al, **opt):
+    return [([c], ss, se, 0, al, opt)] + [([c], ss, se, a + 1, a, opt) for a in range(al - 1, -1, -1)]
+
+
+def sa_levels(rng, grids, dc_al, ac_al, ac=3, dc=20, nnz=8, late=0.1, dc_own=False):
+    """moderate_levels scaled for successive approximation: every value moves
+    up by the deepest Al of its chain (so the first scans still code it) and
+    takes random low bits, which the refinement scans correct; a share `late`
+    of the zero AC coefficients holds low bits alone and turns non-zero in a
+    refinement scan.  AC levels cover the component's own grid (the AC scans'),
+    DC levels the padded one unless `dc_own`."""
+    out = []
+    base = moderate_levels(rng, [g[0] for g in grids], ac=ac, dc=dc, nnz=nnz)
+    for lv, (_, own) in zip(base, grids):
+        a = lv[..., 1:]
+        mag = np.abs(a)
+        sign = np.where(a < 0, -1, np.where(a > 0, 1, rng.choice([-1, 1], size=a.shape)))
+        low = rng.integers(0, 1 << ac_al, size=a.shape)
+        mag = np.where(mag > 0, (mag << ac_al) | low, np.where(rng.random(a.shape) < late, low, 0))
+        lv[..., 1:] = sign * mag
+        lv[..., 0] = (lv[..., 0] << dc_al) | rng.integers(0, 1 << dc_al, size=lv.shape[:2])
+        lv[own[0]:, :, 1:] = 0
+        lv[:, own[1]:, 1:] = 0
+        if dc_own:
+            lv[own[0]:, :, 0] = 0
+            lv[:, own[1]:, 0] = 0
+        out.append(lv)
+    return out
+
+
+def _starts(lengths):
+    return [int(x) for x in np.cumsum([0] + list(lengths[:-1]))]
+
+
+# run lengths (the block that holds the EOBn included) of eob_runs' 576 blocks:
+# every category 0..8, blocks coded at 63, 64 and 65 (either side of the first
+# 64-block chunk boundary), the long runs across several boundaries
+_EOB_FIRST = [63, 1, 1, 256, 128, 2, 4, 8, 16, 64, 33]
+_EOB_REFINE = [1, 2, 4, 8, 16, 33, 1, 64, 128, 256, 63]
+# eob_run_14's 16 512 blocks, band 1-5: category 14 between two coded blocks;
+# band 6-63: categories 13 down to 9
+_EOB14_A = [10, 16384 + 100, 18]
+_EOB14_B = [8192, 4096, 2048, 1024, 512, 640]
+
+
+def _eob_levels(rng, nblk, bands):
+    """[nblk, 64]: per (ss, first-scan run lengths, refinement run lengths) the
+    blocks that start a run hold, in the first scan, values of magnitude 2 or
+    3 (coded at Al = 1; a correction bit in the refinement), in the
+    refinement scan new +-1; every other block is empty in the band.  The
+    first scan's blocks lie inside the refinement's runs."""
+    lv = np.zeros((nblk, 64), np.int32)
+    for ss, first, refine in bands:
+        assert sum(first) == nblk and sum(refine) == nblk
+        for b in _starts(first):
+            lv[b, [ss, ss + 2]] = rng.choice([-3, -2, 2, 3], size=2)
+        for b in _starts(refine):
+            lv[b, [ss + 1, ss + 4]] = rng.choice([-1, 1], size=2)
+    return lv
+
+
+def _script_case(key) -> Stream:
+    rng = np.random.default_rng(71 + SCRIPT_KEYS.index(key))
+    w, h, samp = 37, 29, S420
+    dht = jw.std_tables()
+    if key not in ("deep_al", "dc_per_component", "scans_64", "scans_65", "refine_tables"):
+        # scans with EOB runs: Annex K's AC tables hold no EOBn above EOB0
+        syms = jw.progressive_ac_symbols()
+        dht.update({("ac", 0): jw.ranked_table(syms), ("ac", 1): jw.ranked_table(syms, share=8)})
+    kw: dict = {}
+    expect = None
+    q = None
+
+    def grids_of():
+        return jw.block_grids(w, h, samp)
+
+    if key == "deep_al":
+        levels = sa_levels(rng, grids_of(), 5, 4)
+        script = _dc_chain([0, 1, 2], 5) + [e for c in range(3) for e in _ac_chain(c, 1, 63, 4)]
+        q = {0: np.ones(64, int), 1: np.ones(64, int)}
+    elif key == "al13":
+        w, h, samp = 24, 16, [(1, 1)]
+        lv = np.zeros((2, 3, 64), np.int32)
+        lv[..., 0] = rng.integers(-32767, 32768, size=(2, 3))
+        lv[..., 1:21] = 1024 * rng.integers(-31, 32, size=(2, 3, 20))
+        lv[0, 0, 1:4] = [31744, -31744, 8192]
+        levels = [lv]
+        script = _dc_chain([0], 13) + [([0], 1, 20, 0, 13, RUNS)] + [
+            ([0], 1, 20, a + 1, a, RUNS) for a in (12, 11, 10)]
+        q = {0: np.ones(64, int)}
+    elif key in ("dense_history", "dense_history_17"):
+        samp = [(1, 1)] * 3
+        levels = sa_levels(rng, grids_of(), 0, 0)
+        for lv in levels:
+            flat = lv.reshape(-1, 64)
+            n = len(flat)
+            flat[:, 1:] = rng.choice([-3, -2, 2, 3], size=(n, 63))
+            for j in range(n):
+                if key == "dense_history":  # 63 bits after EOB / 62 after EOB / 62 after (0, 1)
+                    if j % 3:
+                        flat[j, 63] = 0 if j % 3 == 1 else (-1) ** j
+                else:  # fields of 15, 16 and 17 bits between new coefficients
+                    flat[j, [(17, 34, 51), (16, 34, 52), (18, 34, 51)][j % 3]] = rng.choice([-1, 1], size=3)
+        for lv, (_, own) in zip(levels, grids_of()):
+            lv[own[0]:, :, 1:] = 0
+            lv[:, own[1]:, 1:] = 0
+        script = [([0, 1, 2], 0, 0, 0, 0)] + [e for c in range(3) for e in _ac_chain(c, 1, 63, 1, **RUNS)]
+        q = {0: np.ones(64, int), 1: np.ones(64, int)}
+    elif key.startswith("eob_runs") or key.startswith("eob_restart"):
+        w, h, samp = 192, 192, [(1, 1)]
+        lv = _eob_levels(rng, 576, [(1, _EOB_FIRST, _EOB_REFINE)])
+        lv[:, 0] = moderate_levels(rng, [(24, 24)])[0][..., 0].reshape(-1)
+        levels = [lv.reshape(24, 24, 64)]
+        opt = {"eobrun": 1} if key == "eob_runs_cap1" else RUNS
+        script = [([0], 0, 0, 0, 0), ([0], 1, 63, 0, 1, opt), ([0], 1, 63, 1, 0, opt)]
+        q = {0: np.full(64, 3)}
+        if key.startswith("eob_restart"):
+            kw.update({"ri5": dict(restart_interval=5), "ri64": dict(restart_interval=64),
+                       "fill2": dict(restart_interval=5, rst_fill=2)}[key.rsplit("_", 1)[1]])
+    elif key == "eob_run_14":
+        w, h, samp = 1032, 1024, [(1, 1)]
+        lv = _eob_levels(rng, 129 * 128, [(1, _EOB14_A, _EOB14_A), (6, _EOB14_B, _EOB14_B)])
+        lv[::97, 0] = rng.integers(-60, 61, size=len(lv[::97]))
+        levels = [lv.reshape(128, 129, 64)]
+        script = [([0], 0, 0, 0, 0), ([0], 1, 5, 0, 1, RUNS), ([0], 6, 63, 0, 1, RUNS),
+                  ([0], 1, 5, 1, 0, RUNS), ([0], 6, 63, 1, 0, RUNS)]
+        q = {0: np.full(64, 3)}
+    elif key in ("band_split", "band_merge", "band_merge_ri3"):
+        levels = sa_levels(rng, grids_of(), 0, 1, ac=5)
+        bands = ((1, 5), (6, 20), (21, 63))
+        script = [([0, 1, 2], 0, 0, 0, 0)]
+        for c in range(3):
+            if key == "band_split":
+                script += [([c], 1, 63, 0, 1, RUNS)] + [([c], a, b, 1, 0, RUNS) for a, b in bands]
+            else:
+                script += [([c], a, b, 0, 1, RUNS) for a, b in bands] + [([c], 1, 63, 1, 0, RUNS)]
+        if key == "band_merge_ri3":
+            kw.update(restart_interval=3)
+    elif key == "dc_per_component":
+        w, h, samp = 70, 29, SAMPLINGS["411"]
+        levels = sa_levels(rng, grids_of(), 1, 0, ac=10, dc_own=True)
+        script = [([c], 0, 0, 0, 1) for c in (1, 2, 0)] + [([c], 0, 0, 1, 0) for c in (1, 2, 0)]
+        script += [([c], a, b, 0, 0) for c in range(3) for a, b in ((1, 5), (6, 63))]
+    elif key == "order":
+        levels = sa_levels(rng, grids_of(), 1, 1, ac=5)
+        script = _ac_chain(2, 1, 63, 1, **RUNS) + _ac_chain(1, 1, 63, 1, **RUNS)
+        script += [([0], 1, 5, 0, 1, RUNS), ([0], 6, 63, 0, 1, RUNS),
+                   ([0], 1, 5, 1, 0, RUNS), ([0], 6, 63, 1, 0, RUNS),
+                   ([0, 1, 2], 0, 0, 1, 0), ([0, 1, 2], 0, 0, 0, 1)]
+        # the DC first scan stores pred << 1 over what the refinement scan set
+        expect = [lv.copy() for lv in levels]
+        for lv in expect:
+            lv[..., 0] &= ~1
+    elif key == "refine_tables":
+        w, h, samp = 29, 51, SAMPLINGS["440"]
+        levels = sa_levels(rng, grids_of(), 0, 1, ac=5)
+        y = levels[0]
+        y[..., 1:] = 0
+        (_, (bh, bw)) = grids_of()[0]
+        for j in range(bh * bw):  # (r, 1) for every r, ZRL, a history coefficient behind them
+            blk, r = y[j // bw, j % bw], j % 16
+            blk[1 + r] = 2 * (-1) ** j  # new at Al = 1 behind r zeros
+            if 1 + r + 17 <= 63:
+                blk[1 + r + 17] = -2 * (-1) ** j  # 16 zeros: ZRL, then (0, 1)
+            if 1 + r + 19 <= 63:
+                blk[1 + r + 19] = rng.choice([-7, -5, 4, 6])  # first scan (Al = 2)
+            blk[63 - r] = rng.choice([-1, 1])  # new at Al = 0
+        dht.update({("ac", 2): jw.deep_table(REFINE_SYMBOLS),
+                    ("ac", 3): jw.deep_table(REFINE_SYMBOLS[::-1])})
+        t2, t3 = {"ta": [2, 2, 2]}, {"ta": [3, 3, 3]}
+        script = [([0, 1, 2], 0, 0, 0, 0), ([0], 1, 63, 0, 2), ([1], 1, 63, 0, 1), ([2], 1, 63, 0, 1),
+                  ([0], 1, 63, 2, 1, dict(RUNS, **t2)), ([1], 1, 63, 1, 0, dict(RUNS, **t3)),
+                  # ids redefined between a component's scans: 2 deep -> flat, 1 Annex K -> flat
+                  ([0], 1, 63, 1, 0, dict(t2, dht={("ac", 2): jw.flat_table(REFINE_SYMBOLS, 7)})),
+                  ([2], 1, 63, 1, 0, dict(RUNS, dht={("ac", 1): jw.flat_table(REFINE_SYMBOLS, 16)}))]
+    elif key in ("all_ones", "all_ones_ri4"):
+        samp = [(1, 1)]
+        lv = np.zeros((4, 5, 64), np.int32)
+        lv[..., 1:] = np.where(rng.random((4, 5, 63)) < 0.97, 3, 1)  # history + bit 1 / new, positive
+        lv[..., 0] = rng.integers(0, 40, size=(4, 5))
+        levels = [lv]
+        script = [([0], 0, 0, 0, 0)] + _ac_chain(0, 1, 63, 1, **RUNS)
+        q = {0: np.ones(64, int)}
+        if key == "all_ones_ri4":
+            kw.update(restart_interval=4)
+    elif key in ("scans_64", "scans_65"):
+        w, h, samp = 64, 8, [(1, 1)]
+        levels = sa_levels(rng, grids_of(), 1, 0, ac=6, nnz=24)
+        levels[0][..., 1:] = np.where(rng.random((1, 8, 63)) < 0.4, rng.integers(-6, 7, size=(1, 8, 63)), 0)
+        al = 1 if key == "scans_65" else 0
+        script = [([0], 0, 0, 0, al)] + [([0], k, k, 0, 0) for k in range(1, 64)]
+        script += [([0], 0, 0, 1, 0)] * al
+    elif key == "repeat_refine":
+        levels = sa_levels(rng, grids_of(), 0, 1, ac=5)
+        script = [([0, 1, 2], 0, 0, 0, 0)] + [e for c in (1, 2, 0) for e in _ac_chain(c, 1, 63, 1, **RUNS)]
+        script.append(([0], 1, 63, 1, 0, dict(RUNS, repeat=True)))
+        # every luma coefficient that is non-zero takes a correction bit 1:
+        # a clear bit 0 is set (the magnitude grows by 1), a set one stays
+        expect = [lv.copy() for lv in levels]
+        a = expect[0][..., 1:]
+        a[...] = np.where((a != 0) & (a % 2 == 0), a + np.sign(a), a)
+    elif key == "overlap_first":
+        levels = sa_levels(rng, grids_of(), 0, 0, ac=10)
+        y2 = levels[0].copy()
+        y2[..., 1:5] = 0  # (not coded by the second scan)
+        flat = y2.reshape(-1, 64)
+        for j in range(len(flat)):
+            if flat[j, 1:].any():
+                flat[j, 11 + j % 40] = 5 if j % 2 else -5  # the scan codes something in every block
+            if j % 2 == 0:
+                flat[j, 5:11] = 0  # zeros where the first scan set values
+            else:
+                flat[j, 5:11] = np.where(flat[j, 5:11] != 0, -flat[j, 5:11], flat[j, 5:11])
+        levels[0][..., 11:] = y2[..., 11:]
+        script = [([0, 1, 2], 0, 0, 0, 0), ([0], 1, 10, 0, 0, RUNS),
+                  ([0], 5, 63, 0, 0, dict(RUNS, levels=[y2, levels[1], levels[2]])),
+                  ([1], 1, 63, 0, 0), ([2], 1, 63, 0, 0)]
+        # a first scan writes the coefficients it codes and leaves the others
+        expect = [lv.copy() for lv in levels]
+        expect[0][..., 5:] = np.where(y2[..., 5:] != 0, y2[..., 5:], levels[0][..., 5:])
+    elif key == "overlap_first_long":
+        # a long first scan of 1-63, then a short one of 5-10 that changes every
+        # 7th block: the short one must start after the long one, not beside it
+        w, h, samp = 192, 192, [(1, 1)]
+        levels = sa_levels(rng, grids_of(), 0, 0, ac=10, nnz=30)
+        levels[0][..., 5:11] = rng.choice([-4, -3, 3, 4], size=(24, 24, 6))
+        y2 = np.zeros_like(levels[0])
+        flat = y2.reshape(-1, 64)
+        flat[::7, 5:11] = rng.choice([-9, 0, 9], size=(len(flat[::7]), 6))
+        script = [([0], 0, 0, 0, 0), ([0], 1, 63, 0, 0, RUNS), ([0], 5, 10, 0, 0, dict(RUNS, levels=[y2]))]
+        expect = [np.where(y2 != 0, y2, levels[0])]
+    elif key in ("zrl_overshoot_refine", "bad_size2", "bad_past_se"):
+        levels = sa_levels(rng, grids_of(), 0, 1, ac=5)
+        (_, (bh, bw)) = grids_of()[0]
+        ex = {}
+        for j in range(bh * bw):
+            if j % 2 == 0 if key == "zrl_overshoot_refine" else j == 3:
+                blk = levels[0][j // bw, j % bw]
+                blk[50:] = 0
+                blk[50] = (-1) ** (j // 2)  # the last new coefficient
+                blk[55], blk[60] = 2, -3  # history behind it: 11 zero-history coefficients are left
+                ex[(2, 0, j // bw, j % bw)] = {
+                    "zrl_overshoot_refine": [("ac", jw.ZRL, 0, 0)],
+                    "bad_size2": [("ac", 0x02, 2, 2)],
+                    "bad_past_se": [("ac", 0xF1, 1, 1)]}[key]
+        script = [([0, 1, 2], 0, 0, 0, 0)] + [e for c in range(3) for e in _ac_chain(c, 1, 63, 1, **RUNS)]
+        kw.update(extra_symbols=ex)
+    else:
+        raise KeyError(key)
+    ids = _std_ids(len(samp))
+    if q is None:
+        q = _small_q(rng, (0, 1), 3)
+    s = _write("scr_" + key, w, h, samp, levels, q, ids, dht, ids, ids, scans="script", script=script, **kw)
+    s.expect = expect
+    s.script = script
+    return s
+
+
+SCRIPT_KEYS = ["deep_al", "al13", "dense_history", "dense_history_17", "eob_runs", "eob_runs_cap1",
+               "eob_run_14", "eob_restart_ri5", "eob_restart_ri64", "eob_restart_fill2", "band_split",
+               "band_merge", "band_merge_ri3", "dc_per_component", "order", "refine_tables", "all_ones",
+               "all_ones_ri4", "scans_64", "scans_65", "repeat_refine", "overlap_first",
+               "zrl_overshoot_refine", "bad_size2", "bad_past_se", "overlap_first_long"]
+# streams a decoder must refuse (a refinement symbol of size 2; a new coefficient past Se)
+SCRIPT_BAD = ["scr_bad_size2", "scr_bad_past_se"]
+# saturate by nature, or decode to other levels than an encoder's: no clamp cap
+SCRIPT_UNCAPPED = ["scr_al13", "scr_repeat_refine", "scr_overlap_first", "scr_overlap_first_long"]
+# the oracle decodes all of these; the device refuses scr_scans_65 (64 scans at most)
+SCRIPT_LEGAL = ["scr_" + k for k in SCRIPT_KEYS if "scr_" + k not in SCRIPT_BAD]
+SCRIPT_CASES = [n for n in SCRIPT_LEGAL if n != "scr_scans_65"]
+SCRIPT_CAPPED = [n for n in SCRIPT_LEGAL if n not in SCRIPT_UNCAPPED]
+# decoded by libjpeg without a warning
+SCRIPT_PILLOW = ["scr_deep_al", "scr_band_split", "scr_band_merge", "scr_dc_per_component",
+                 "scr_eob_runs"]
+
+CAPPED_CASES = SAMPLING_CASES + TABLE_CASES + STRUCTURE_CASES + PROGRESSIVE_CASES + SCRIPT_CAPPED
+ACCEPTED_CASES = SAMPLING_CASES + TABLE_CASES + STRUCTURE_CASES + PROGRESSIVE_CASES + EXTREME_CASES
 
 
 @functools.lru_cache(maxsize=None)
@@ -524,6 +853,8 @@ def case(name: str) -> Stream:
         return _structure_case(rest)
     if kind == "prog":
         return _progressive_case(rest)
+    if kind == "scr":
+        return _script_case(rest)
     raise KeyError(name)
 
 

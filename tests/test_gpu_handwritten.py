@@ -13,7 +13,10 @@ Families 2-5 (entropy-sensitive) also run on a second Decoder with
 sub_bits = 32 and entropy_threads = 128, so these small scans still split
 into many subsequences and chain hand-offs.
 
-Families 1, 2, 4 and 5 assert that at most 25 % of the oracle's RGB samples are
+Family 6 (scan scripts: SOF2 with successive approximation) runs on the one
+Decoder: multiscan_kernel takes no sub_bits / entropy_threads.
+
+Families 1, 2, 4, 5 and the capped cases of 6 assert that at most 25 % of the oracle's RGB samples are
 0 or 255.  Family 3 saturates by nature (share of saturated RGB samples in
 the oracle's output, interleaved / one scan per component: ac1023_q255 0.51 /
 0.51, ac_sizes_11_15 0.52 / 0.53, pq1 0.52 / 0.52, dense 0.00 / 0.00, dc_ramp
@@ -208,3 +211,102 @@ def test_spectral_selection(decoder, fine_decoder, oracle, name):
     check_all(decoder, oracle, d, capped=True)
     check_coefs(fine_decoder, oracle, d)
     check_rgb(fine_decoder, oracle, d, paths=(0,))
+
+
+# ---- family 6: scan scripts -------------------------------------------------
+
+BAD_HUFFMAN = 4  # SPDL_HJ_ERR_BAD_HUFFMAN == JO_ERR_BAD_HUFFMAN
+
+
+def _status(dec, d, out, shape):
+    t = torch.empty(shape, dtype=torch.uint8, device="cuda:0")
+    return dec.decode_batch([d], out, t.data_ptr(), t.numel(), stream=torch.cuda.current_stream(),
+                            check=False)
+
+
+def _good_image_decodes(dec, oracle):
+    good = cases.case("q90_444")
+    hyp = _decode(dec, [good], Output(pix_fmt="rgb24"), (240, 320, 3))[0]
+    np.testing.assert_array_equal(hyp, oracle.decode_rgb(good, 0, "rgb24"), strict=True)
+
+
+@pytest.mark.parametrize("name", hw.SCRIPT_CASES)
+def test_scan_scripts(decoder, oracle, name):
+    """Hand-written progressive streams: Al up to 13 and up to fourteen passes
+    over a coefficient, correction fields of 15..63 bits, EOB runs of every
+    category (across chunk boundaries, cut by restarts, with correction bits
+    inside), refinement bands unlike the first scans', DC scans per
+    component, odd scan orders, deep / flat / redefined refinement tables,
+    refinement through the stuffed reader, and three kinds of stream libjpeg
+    warns about but decodes (a refinement repeated, first scans that overlap,
+    a ZRL past Se in a refinement scan).  The oracle's levels are pinned to
+    libjpeg 9's by test_jpeg_writer.  No fine_decoder here: multiscan_kernel
+    takes no EntropyParams (neither sub_bits nor entropy_threads reaches it;
+    it always runs 256 threads)."""
+    d = hw.case(name).data
+    if name == "scr_eob_run_14":  # 1032 x 1024: coefficients and the simple-IDCT planes only
+        check_coefs(decoder, oracle, d)
+        for h, r in zip(decoder.decode_planes(d, idct="simple"),
+                        oracle.decode_planes(d, idct=oracle.IDCT_SIMPLE)):
+            np.testing.assert_array_equal(h, r, strict=True)
+        return
+    check_all(decoder, oracle, d, capped=name in hw.SCRIPT_CAPPED)
+
+
+def test_scan_scripts_in_a_batch(decoder, oracle):
+    """Scripted streams between encoder-made ones in one batch, decoded twice
+    on the same Decoder: levels, masks or destuffed copies left over from a
+    neighbour or from the first pass would show."""
+    datas = [cases.case("q90_420"), hw.case("scr_deep_al").data, cases.case("gray"),
+             hw.case("scr_band_merge").data, hw.case("prog_420").data, hw.case("scr_order").data,
+             hw.case("scr_eob_restart_ri5").data, hw.case("scr_dense_history").data]
+    out = Output(pix_fmt="rgb24", resize=True, **RESIZE32)
+    refs = [oracle.decode_resize(d, oracle.Resize(**RESIZE32), pix_fmt="rgb24") for d in datas]
+    for again in (0, 1):
+        hyp = _decode(decoder, datas, out, (32, 32, 3))
+        for i, ref in enumerate(refs):
+            np.testing.assert_array_equal(hyp[i], ref, strict=True, err_msg=f"pass {again} image {i}")
+
+
+def test_scan_limit(decoder, oracle):
+    """64 scans decode; the 65th SOS is refused as unsupported (kMsMaxScans:
+    the documented limit -- the oracle decodes that stream); the decoder
+    then decodes q90_444."""
+    s = hw.case("scr_scans_64")  # (every surface: test_scan_scripts)
+    assert len(s.script) == 64
+    check_coefs(decoder, oracle, s.data)
+    check_rgb(decoder, oracle, s.data, paths=(0,))
+    s = hw.case("scr_scans_65")
+    assert len(s.script) == 65
+    assert oracle.decode_rgb(s.data).shape == (s.height, s.width, 3)
+    for out, shape in ((Output(pix_fmt="rgb24"), (s.height, s.width, 3)),
+                       (Output(pix_fmt="rgb24", resize=True, **RESIZE32), (32, 32, 3))):
+        assert _status(decoder, s.data, out, shape) == [UNSUPPORTED]
+        t = torch.empty(shape, dtype=torch.uint8, device="cuda:0")
+        with pytest.raises(RuntimeError, match="Failed to decode an image"):
+            decoder.decode_batch([s.data], out, t.data_ptr(), t.numel(),
+                                 stream=torch.cuda.current_stream())
+    _good_image_decodes(decoder, oracle)
+
+
+@pytest.mark.parametrize("name", hw.SCRIPT_BAD)
+def test_refused_refinement_symbols(decoder, oracle, name):
+    """A refinement symbol of size 2, and a (r, 1) whose run passes Se: the
+    oracle's status from the device, alone and between two good images (which
+    decode); a good image decodes afterwards."""
+    s = hw.case(name)
+    with pytest.raises(oracle.OracleError) as e:
+        oracle.decode_rgb(s.data)
+    assert e.value.code == BAD_HUFFMAN
+    out = Output(pix_fmt="rgb24")
+    assert _status(decoder, s.data, out, (s.height, s.width, 3)) == [e.value.code]
+    twin = hw.case("scr_zrl_overshoot_refine")  # the same layout and size, accepted
+    assert (twin.width, twin.height) == (s.width, s.height)
+    t = torch.empty((3, s.height, s.width, 3), dtype=torch.uint8, device="cuda:0")
+    st = decoder.decode_batch([twin.data, s.data, twin.data], out, t.data_ptr(), t.numel(),
+                              stream=torch.cuda.current_stream(), check=False)
+    assert st == [0, e.value.code, 0]
+    ref = oracle.decode_rgb(twin.data, oracle.IDCT_SIMPLE, "rgb24")
+    for i in (0, 2):
+        np.testing.assert_array_equal(t[i].cpu().numpy(), ref, strict=True)
+    _good_image_decodes(decoder, oracle)

@@ -5,6 +5,7 @@ clip / wrap rules of FFmpeg's mjpeg dequantisation, refuses what it should,
 and Pillow / libjpeg agree on the streams they accept."""
 
 import io
+from collections import Counter
 
 import numpy as np
 import pytest
@@ -52,15 +53,16 @@ def expected_coefs(oracle, s: hw.Stream):
     return out
 
 
-@pytest.mark.parametrize("name", hw.ACCEPTED_CASES)
+@pytest.mark.parametrize("name", hw.ACCEPTED_CASES + hw.SCRIPT_LEGAL)
 def test_level_round_trip(oracle, name):
-    """The oracle returns the levels that were written, and its dequantised
-    coefficients follow the clip and wrap rules."""
+    """The oracle returns the levels that were written (for the scripted
+    streams libjpeg warns about: the levels the case expects by libjpeg's
+    rule), and its dequantised coefficients follow the clip and wrap rules."""
     s = hw.case(name)
     info = oracle.parse(s.data)
     assert (info.width, info.height, info.ncomp) == (s.width, s.height, len(s.samp))
-    assert bool(info.progressive) == (s.scans == "spectral")
-    assert bool(info.multiscan) == (s.scans == "spectral" or
+    assert bool(info.progressive) == (s.scans in ("spectral", "script"))
+    assert bool(info.multiscan) == (s.scans in ("spectral", "script") or
                                     (s.scans == "per_component" and len(s.samp) > 1))
     coefs, levels = oracle.decode_coefs(s.data)
     for got, want in zip(levels, s.natural_levels()):
@@ -171,22 +173,85 @@ def test_writer_structure():
     assert hw.case("blk_rst_fill_1").data.count(b"\xff\xc4") == 1
 
 
+def _scans(name, refine):
+    """The statistics of a case's AC first (refine False) / refinement scans."""
+    return [t for t in hw.case(name).stats["scans"]
+            if t["entry"][1] > 0 and (t["entry"][3] > 0) == refine]
+
+
+def test_script_symbol_coverage():
+    """What the scripted streams are for, counted by the writer: every EOBn
+    category in both AC scan kinds, the 32 refinement symbols, correction
+    fields past the 15 bits of the kernel's short path and up to 63 bits,
+    correction bits inside EOB runs, runs cut by restarts."""
+    for refine in (False, True):
+        cats = set()
+        for name in ("scr_eob_runs", "scr_eob_run_14"):
+            for t in _scans(name, refine):
+                cats |= set(t["eob"])
+                assert set(t["eob"]) == {sym >> 4 for sym in t["ac"] if sym & 15 == 0 and sym != jw.ZRL}
+        assert cats == set(range(15)), (refine, cats)
+        assert {c for t in _scans("scr_eob_runs", refine) for c in t["eob"]} == set(range(9))
+        assert {c for t in _scans("scr_eob_runs_cap1", refine) for c in t["eob"]} == {0, 1}
+    assert sum(t["corr_bits_inside_runs"] for t in _scans("scr_eob_runs", True)) >= 10
+    assert sum(t["corr_bits_inside_runs"] for t in _scans("scr_eob_restart_ri5", True)) >= 10
+    # a restart ends a run: no run of the 5-block intervals is longer than 5
+    for refine in (False, True):
+        assert {c for t in _scans("scr_eob_restart_ri5", refine) for c in t["eob"]} == {0, 1, 2}
+    used = set()
+    for name in hw.SCRIPT_LEGAL:
+        for t in _scans(name, True):
+            used |= set(t["ac"])
+    assert used == set(hw.REFINE_SYMBOLS) and len(used) == 32
+    # every (r, 1) and ZRL under the deep and the flat tables of scr_refine_tables
+    st = hw.case("scr_refine_tables").stats
+    assert {(r << 4) | 1 for r in range(16)} | {jw.ZRL} <= set(st[("ac", 2)])
+    assert len(st[("ac", 3)]) > 4 and len(st[("ac", 1)]) > 4
+    fields = Counter()
+    for t in _scans("scr_dense_history", True):
+        fields += t["corr_fields"]
+    assert fields[63] > 10 and fields[62] > 20  # after EOB: 63 or 62; after (0, 1): 62
+    fields = Counter()
+    for t in _scans("scr_dense_history_17", True):
+        fields += t["corr_fields"]
+    assert all(fields[n] > 10 for n in (15, 16, 17))
+    # scr_all_ones: the refinement data is ones -- stuffed 0xFF bytes
+    for name in ("scr_all_ones", "scr_all_ones_ri4"):
+        d = hw.case(name).data
+        scan = d[d.rindex(b"\xff\xda"):]
+        assert scan.count(b"\xff\x00") * 2 > 0.5 * len(scan), name  # (bytes in 0xFF 0x00 pairs)
+
+
+def test_script_streams_keep_the_spectral_bytes():
+    """scans="script" with Ah = Al = 0 and EOBRUN 0 writes the bytes of
+    scans="spectral" (whose streams the existing cases depend on)."""
+    s = hw.case("prog_420")
+    script = [([0, 1, 2], 0, 0, 0, 0)] + [([c], a, b, 0, 0) for c in range(3) for a, b in ((1, 5), (6, 63))]
+    ids = [0, 1, 1]
+    again = jw.write_jpeg(s.width, s.height, s.samp, s.levels, s.qtables, s.tq, jw.std_tables(), ids, ids,
+                          scans="script", script=script)
+    assert again == s.data
+
+
 @pytest.mark.parametrize("name", hw.CAPPED_CASES)
 def test_clamp_cap(oracle, name):
-    """Families 1, 2 and 4: at most 25 % of the oracle's RGB samples sit at 0
+    """Families 1, 2, 4, 5 and the capped cases of 6: at most 25 % of the oracle's RGB samples sit at 0
     or 255, so the output clamp cannot carry a parity test."""
     assert hw.saturated_share(oracle.decode_rgb(hw.case(name).data)) <= 0.25
 
 
-@pytest.mark.parametrize("name", hw.REFUSED_CASES)
+@pytest.mark.parametrize("name", hw.REFUSED_CASES + hw.SCRIPT_BAD)
 def test_oracle_refuses(oracle, name):
+    # JO_ERR_UNSUPPORTED for the layouts; JO_ERR_BAD_HUFFMAN for a refinement
+    # symbol of size 2 and for a new coefficient whose run passes Se
+    code = 4 if name in hw.SCRIPT_BAD else 2
     with pytest.raises(oracle.OracleError) as e:
         oracle.decode_rgb(hw.case(name).data)
-    assert e.value.code == 2  # JO_ERR_UNSUPPORTED
+    assert e.value.code == code
     rs = oracle.Resize(fit_w=32, fit_h=32, aspect="decrease", pad_w=32, pad_h=32)
     with pytest.raises(oracle.OracleError) as e:
         oracle.decode_resize(hw.case(name).data, rs, "rgb24")
-    assert e.value.code == 2
+    assert e.value.code == code
 
 
 def test_zrl_overshoot_ends_the_block(oracle):
@@ -214,17 +279,22 @@ def _pillow_stream(key):
                                [0, 1, 1]), levels
 
 
-@pytest.mark.parametrize("key", PILLOW_SAMPLINGS)
+@pytest.mark.parametrize("key", PILLOW_SAMPLINGS + hw.SCRIPT_PILLOW)
 def test_pillow_decodes_the_legal_streams(oracle, key):
     """Moderate levels (|AC| <= 30, |DC| <= 300, q = 1), 8-bit tables, Annex K
     codes: Pillow (libjpeg) opens the stream at the right size and mode, and
     its luma is within 1 of the oracle's islow plane (the 1 is Pillow's
-    YCbCr -> RGB -> YCbCr round trip; luma is never subsampled)."""
+    YCbCr -> RGB -> YCbCr round trip; luma is never subsampled).  The same
+    for the scripted progressive streams that are legal T.81."""
     from PIL import Image
 
-    w, h, data, _ = _pillow_stream(key)
+    if key.startswith("scr_"):
+        s = hw.case(key)
+        w, h, data = s.width, s.height, s.data
+    else:
+        w, h, data, _ = _pillow_stream(key)
     im = Image.open(io.BytesIO(data))
-    assert im.size == (w, h) and im.mode == "RGB"
+    assert im.size == (w, h) and im.mode == ("L" if key == "scr_eob_runs" else "RGB")
     im.draft("YCbCr", (w, h))
     luma = np.asarray(im.convert("YCbCr"))[..., 0].astype(int)
     ref = oracle.decode_planes(data, oracle.IDCT_ISLOW)[0].astype(int)
@@ -232,12 +302,18 @@ def test_pillow_decodes_the_legal_streams(oracle, key):
     assert np.abs(luma - ref).max() <= 1
 
 
-@pytest.mark.parametrize("key", PILLOW_SAMPLINGS + ["1x4", "22_21", "gray22"])
+@pytest.mark.parametrize("key", PILLOW_SAMPLINGS + ["1x4", "22_21", "gray22"] + hw.SCRIPT_LEGAL)
 def test_coefficients_match_libjpeg(oracle, key):
-    """libjpeg 9's jpeg_read_coefficients returns the written levels."""
+    """libjpeg 9's jpeg_read_coefficients returns the written levels.  The
+    scripted streams too: for scr_order (DC first scan after its refinement),
+    scr_repeat_refine, scr_overlap_first and scr_zrl_overshoot_refine libjpeg
+    warns of a bogus progression or decodes silently, and returns the levels
+    the case expects (its warnings are not fatal here: ljpin.c's emit_message
+    drops them)."""
     if oracle.ljpin() is None:
         pytest.skip("libjpeg 9 not available on this host")
-    name = next(n for n in hw.SAMPLING_CASES if n.startswith(f"samp_{key}_") and n.endswith("ri1"))
+    name = key if key.startswith("scr_") else next(
+        n for n in hw.SAMPLING_CASES if n.startswith(f"samp_{key}_") and n.endswith("ri1"))
     s = hw.case(name)
     for got, want in zip(oracle.lj_read_coefs(s.data), s.natural_levels()):
         np.testing.assert_array_equal(got, want.astype(np.int16))
