@@ -261,7 +261,47 @@ struct ImageInfo {      // device-filled by the parse kernel
   int64_t dbg[4];       // diagnostics: symbols (round 0), wave iterations, shader clocks, rt ticks
   int32_t sdiag[48];    // diagnostics, multiscan: per scan (16) start / end (wall_clock64
                         // ticks from the decode start) and Huffman symbols decoded
+  uint32_t bpm_magic, mcux_magic;  // parse: idct_div_magic of bpm and mcux (idct_block_pos)
 };
+
+// idct_kernel's block index -> the block's component and its position in the
+// component's plane, in blocks: block j is block b = j % bpm of MCU j / bpm,
+// the MCUs in raster order, mcux to a row.  The two divisions are by numbers
+// fixed per image, so parse leaves m = floor((2^32 - 1) / d) for each:
+// m d = 2^32 - e with 1 <= e <= d, so n m / 2^32 = n / d - (n / 2^32)(e / d)
+// falls short of n / d by less than 1 for every n < 2^32: the high word of
+// n m is the quotient or one below it, which the remainder tells.
+// HJ_IDCT_INDEX=0: the plain divisions.
+#ifndef HJ_IDCT_INDEX
+#define HJ_IDCT_INDEX 1
+#endif
+inline HJ_HD uint32_t idct_div_magic(uint32_t d) { return 0xFFFFFFFFu / d; }  // d >= 1
+struct IdctDivMod {
+  uint32_t q, r;
+};
+inline HJ_HD IdctDivMod idct_divmod(uint32_t n, uint32_t d, uint32_t magic) {
+#if HJ_IDCT_INDEX
+  uint32_t q = (uint32_t)(((uint64_t)n * magic) >> 32);
+  uint32_t r = n - q * d;
+  if (r >= d) {
+    q += 1;
+    r -= d;
+  }
+  return {q, r};
+#else
+  return {n / d, n % d};
+#endif
+}
+struct IdctBlockPos {
+  int c, bx, by;
+};
+inline HJ_HD IdctBlockPos idct_block_pos(const ImageInfo& in, uint32_t j) {
+  const IdctDivMod m = idct_divmod(j, (uint32_t)in.bpm, in.bpm_magic);      // MCU, block of it
+  const IdctDivMod p = idct_divmod(m.q, (uint32_t)in.mcux, in.mcux_magic);  // MCU row, column
+  const int b = (int)m.r, c = in.mcu_comp[b];
+  if (in.ncomp == 1) return {c, (int)p.r, (int)p.q};
+  return {c, (int)p.r * in.comp_h[c] + in.mcu_dx[b], (int)p.q * in.comp_v[c] + in.mcu_dy[b]};
+}
 
 // destuff: chunk-parallel over kDsChunk-byte chunks; per-chunk counts and prefixes
 constexpr int kDsChunk = 4096;

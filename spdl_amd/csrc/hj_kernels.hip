@@ -253,6 +253,8 @@ __device__ static int parse_headers(const Bytes& d, int size, ParseScratch& s) {
         in.bpm = b;
       }
       in.nblocks = in.mcux * in.mcuy * in.bpm;
+      in.bpm_magic = idct_div_magic((uint32_t)in.bpm);
+      in.mcux_magic = idct_div_magic((uint32_t)in.mcux);
       return kOk;
     }
   }
@@ -4513,6 +4515,32 @@ constexpr int kBlkWords = 32;
 // (a coefficient's int16 store into the block words: may_alias, or the
 // compiler may forward the zeroing word stores to the transform's word loads)
 typedef int16_t __attribute__((may_alias)) hj_i16_alias;
+typedef __attribute__((address_space(3))) hj_i16_alias hj_lds_i16;
+typedef __attribute__((address_space(3))) uint32_t hj_lds_u32;
+
+// idct_kernel<simple>'s instruction cuts, one switch each (default on; a
+// variant build without one measures it: make variant DEFS=-DHJ_IDCT_SEED=0):
+//   SEED     the first dot2 of a chain takes its bias as the third operand
+//   DCBIAS   the DC-only row shortcut as a bias of the full sums
+//   PACK     column sums shifted, clipped and packed two at a time
+//   SCATTER  half-word operand selects in the list scatter
+//   GATHER   a group's 16 dequantisation-table reads ahead of its 16 stores
+//   INDEX    block -> (MCU, block of MCU, MCU column, row) by multiplication
+#ifndef HJ_IDCT_SEED
+#define HJ_IDCT_SEED 1
+#endif
+#ifndef HJ_IDCT_DCBIAS
+#define HJ_IDCT_DCBIAS 1
+#endif
+#ifndef HJ_IDCT_PACK
+#define HJ_IDCT_PACK 1
+#endif
+#ifndef HJ_IDCT_SCATTER
+#define HJ_IDCT_SCATTER 1
+#endif
+#ifndef HJ_IDCT_GATHER
+#define HJ_IDCT_GATHER 1
+#endif
 
 // byte offset of IDCT slot s (kSlotOrder) in the word-major block of NT threads
 template <int NT>
@@ -4542,8 +4570,14 @@ __device__ __forceinline__ void list_block(const uint32_t* __restrict__ ents, co
                                            const uint32_t* sqc, uint32_t* b32) {
 #pragma unroll
   for (int w = 0; w < kBlkWords; w++) b32[w * NT] = w == 0 ? (bd.y >> 16) : 0u;
+#if HJ_IDCT_SCATTER
+  // (b32 points into the kernel's LDS: 32-bit LDS addresses)
+  const uint32_t blk_a = (uint32_t)(uintptr_t)(hj_lds_u32*)b32;
+  const uint32_t dummy_a = blk_a + (uint32_t)(kBlkWords * NT * 4);
+#else
   uint8_t* blk = reinterpret_cast<uint8_t*>(b32);
   uint8_t* dummy = reinterpret_cast<uint8_t*>(b32 + kBlkWords * NT);
+#endif
   const uint32_t cap = (uint32_t)nblocks * 64u;
   const uint32_t lo = bd.x & 3u, start = bd.x & ~3u;
   uint32_t count = min(bd.y & 0xFFFFu, 63u);
@@ -4556,16 +4590,52 @@ __device__ __forceinline__ void list_block(const uint32_t* __restrict__ ents, co
     uint4 q[4];
 #pragma unroll
     for (int u = 0; u < 4; u++) q[u] = e4[min(i + u, n4 - 1u)];
+#if HJ_IDCT_GATHER
+    // the 16 table words ahead of the 16 stores: a store may alias the table
+    // for all the compiler knows, so read entry by entry each table read
+    // waits for the store before it and each store for its read -- 16 LDS
+    // round trips in a row
+    uint32_t qsv[16];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      qsv[4 * u] = sqc[q[u].x & 63u];
+      qsv[4 * u + 1] = sqc[q[u].y & 63u];
+      qsv[4 * u + 2] = sqc[q[u].z & 63u];
+      qsv[4 * u + 3] = sqc[q[u].w & 63u];
+    }
+#endif
 #pragma unroll
     for (int u = 0; u < 4; u++) {
       const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
 #pragma unroll
       for (int h = 0; h < 4; h++) {  // (outside the list: into the dummy word)
         const uint32_t k = 4u * (i + u) + h;
+#if HJ_IDCT_GATHER
+        const uint32_t qs = qsv[4 * u + h];
+#else
         const uint32_t qs = sqc[w[h] & 63u];
+#endif
+#if HJ_IDCT_SCATTER
+        // the entry's and the table word's halves picked by the instructions
+        // themselves (SDWA): level x quantiser from the high halves, block
+        // address + slot offset from the low half; k in [lo, lo + count) as
+        // one unsigned compare
+        uint32_t in_a, prod;
+        asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD "
+            "src1_sel:WORD_0"
+            : "=v"(in_a)
+            : "v"(blk_a), "v"(qs));
+        asm("v_mul_lo_u16_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 "
+            "src1_sel:WORD_1"
+            : "=v"(prod)
+            : "v"(w[h]), "v"(qs));
+        const uint32_t a32 = k - lo < count ? in_a : dummy_a;
+        *reinterpret_cast<hj_lds_i16*>(a32) = (int16_t)prod;
+#else
         uint8_t* dst = k >= lo && k < hi_e ? blk + (qs & 0xFFFFu) : dummy;
         // (16-bit multiply: the low half is the sequential decoder's int16 product)
         *reinterpret_cast<hj_i16_alias*>(dst) = (int16_t)pk_mul_lo16(w[h] >> 16, qs >> 16);
+#endif
       }
     }
   }
@@ -4588,17 +4658,39 @@ constexpr uint32_t pk16(int lo, int hi) {
 __device__ __forceinline__ uint32_t pack_lo16(uint32_t lo, uint32_t hi) {
   return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
 }
+// The first dot2 of a chain.  The builtin becomes the two-operand
+// v_dot2c_i32_i16, which accumulates in place and so costs a v_mov of the bias
+// (or of 0) per chain; the three-operand form reads the bias where it is.  Its
+// weight is an SGPR (VOP3: one constant-bus operand, no literal).
+__device__ __forceinline__ int32_t dot2_seed(uint32_t a, uint32_t w, int32_t c) {
+#if HJ_IDCT_SEED
+  int32_t d;
+  asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(w), "v"(c));
+  return d;
+#else
+  return dot2(a, w, c);
+#endif
+}
+__device__ __forceinline__ int32_t dot2_seed0(uint32_t a, uint32_t w) {
+#if HJ_IDCT_SEED
+  int32_t d;
+  asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(d) : "v"(a), "s"(w));
+  return d;
+#else
+  return dot2(a, w, 0);
+#endif
+}
 // an 8-point pass: a[k] even sums (+ bias), b[k] odd sums
 __device__ __forceinline__ void sidct8(uint32_t e0, uint32_t e1, uint32_t o0, uint32_t o1,
                                        int32_t bias, int32_t (&a)[4], int32_t (&b)[4]) {
-  a[0] = dot2(e1, pk16(kW4, kW6), dot2(e0, pk16(kW4, kW2), bias));
-  a[1] = dot2(e1, pk16(-kW4, -kW2), dot2(e0, pk16(kW4, kW6), bias));
-  a[2] = dot2(e1, pk16(-kW4, kW2), dot2(e0, pk16(kW4, -kW6), bias));
-  a[3] = dot2(e1, pk16(kW4, -kW6), dot2(e0, pk16(kW4, -kW2), bias));
-  b[0] = dot2(o1, pk16(kW5, kW7), dot2(o0, pk16(kW1, kW3), 0));
-  b[1] = dot2(o1, pk16(-kW1, -kW5), dot2(o0, pk16(kW3, -kW7), 0));
-  b[2] = dot2(o1, pk16(kW7, kW3), dot2(o0, pk16(kW5, -kW1), 0));
-  b[3] = dot2(o1, pk16(kW3, -kW1), dot2(o0, pk16(kW7, -kW5), 0));
+  a[0] = dot2(e1, pk16(kW4, kW6), dot2_seed(e0, pk16(kW4, kW2), bias));
+  a[1] = dot2(e1, pk16(-kW4, -kW2), dot2_seed(e0, pk16(kW4, kW6), bias));
+  a[2] = dot2(e1, pk16(-kW4, kW2), dot2_seed(e0, pk16(kW4, -kW6), bias));
+  a[3] = dot2(e1, pk16(kW4, -kW6), dot2_seed(e0, pk16(kW4, -kW2), bias));
+  b[0] = dot2(o1, pk16(kW5, kW7), dot2_seed0(o0, pk16(kW1, kW3)));
+  b[1] = dot2(o1, pk16(-kW1, -kW5), dot2_seed0(o0, pk16(kW3, -kW7)));
+  b[2] = dot2(o1, pk16(kW7, kW3), dot2_seed0(o0, pk16(kW5, -kW1)));
+  b[3] = dot2(o1, pk16(kW3, -kW1), dot2_seed0(o0, pk16(kW7, -kW5)));
 }
 // row i of the word-major block: words 4i..4i+3
 template <int NT>
@@ -4606,42 +4698,94 @@ __device__ __forceinline__ uint4 blk_row(const uint32_t* b32, int i) {
   return make_uint4(b32[(4 * i) * NT], b32[(4 * i + 1) * NT], b32[(4 * i + 2) * NT],
                     b32[(4 * i + 3) * NT]);
 }
-// b32: the thread's word 0 of the word-major block; px: 64 pixels, row-major
+// The row pass.  b32: the thread's word 0 of the word-major block; r[i][k]:
+// row i's output k, truncated to int16 by the column pass's packing (FFmpeg
+// keeps the rows in the int16 block; only the low halves are used).
+// DC-only rows (x1..x7 zero) are x0 << 3 in all eight places
+// (idctRowCondDC).  As a bias: with 1024 + x0 every even sum is
+// kW4 x0 + x0 + 1024 = 16384 x0 + 1024 and every odd sum 0, so >> 11 leaves
+// 8 x0 exactly, the int16 truncation being the shortcut's.  (The plain full
+// path differs from the shortcut wherever |x0| > 1024.)
 template <int NT>
-__device__ __forceinline__ void simple_idct_slots(const uint32_t* b32, int32_t (&px)[64]) {
-  // rows: results truncated to int16 (FFmpeg keeps them in the int16 block);
-  // only their low halves are used, packed below.  DC-only rows: x0 << 3.
-  uint32_t r[8][8];
+__device__ __forceinline__ void simple_idct_rows(const uint32_t* b32, uint32_t (&r)[8][8]) {
 #pragma unroll
   for (int i = 0; i < 8; i++) {
     const uint4 q = blk_row<NT>(b32, i);
     int32_t a[4], b[4];
-    sidct8(q.x, q.y, q.z, q.w, 1 << 10, a, b);
     const bool dc_only = ((q.x >> 16) | q.y | q.z | q.w) == 0u;
+#if HJ_IDCT_DCBIAS
+    sidct8(q.x, q.y, q.z, q.w, (1 << 10) + (dc_only ? sext16(q.x) : 0), a, b);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      r[i][k] = (uint32_t)((int32_t)((uint32_t)a[k] + (uint32_t)b[k]) >> 11);
+      r[i][7 - k] = (uint32_t)((int32_t)((uint32_t)a[k] - (uint32_t)b[k]) >> 11);
+    }
+#else
+    sidct8(q.x, q.y, q.z, q.w, 1 << 10, a, b);
     const uint32_t dc = q.x << 3;
-    r[i][0] = dc_only ? dc : (uint32_t)((int32_t)((uint32_t)a[0] + (uint32_t)b[0]) >> 11);
-    r[i][7] = dc_only ? dc : (uint32_t)((int32_t)((uint32_t)a[0] - (uint32_t)b[0]) >> 11);
-    r[i][1] = dc_only ? dc : (uint32_t)((int32_t)((uint32_t)a[1] + (uint32_t)b[1]) >> 11);
-    r[i][6] = dc_only ? dc : (uint32_t)((int32_t)((uint32_t)a[1] - (uint32_t)b[1]) >> 11);
-    r[i][2] = dc_only ? dc : (uint32_t)((int32_t)((uint32_t)a[2] + (uint32_t)b[2]) >> 11);
-    r[i][5] = dc_only ? dc : (uint32_t)((int32_t)((uint32_t)a[2] - (uint32_t)b[2]) >> 11);
-    r[i][3] = dc_only ? dc : (uint32_t)((int32_t)((uint32_t)a[3] + (uint32_t)b[3]) >> 11);
-    r[i][4] = dc_only ? dc : (uint32_t)((int32_t)((uint32_t)a[3] - (uint32_t)b[3]) >> 11);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      r[i][k] = dc_only ? dc : (uint32_t)((int32_t)((uint32_t)a[k] + (uint32_t)b[k]) >> 11);
+      r[i][7 - k] = dc_only ? dc : (uint32_t)((int32_t)((uint32_t)a[k] - (uint32_t)b[k]) >> 11);
+    }
+#endif
   }
-  // columns: (c0 + 32) W4 = c0 W4 + 32 W4
+}
+// column k of the row pass's output: s[j] = the sum of row j before >> 20.
+// (c0 + 32) W4 = c0 W4 + 32 W4
+__device__ __forceinline__ void simple_idct_col(const uint32_t (&r)[8][8], int k,
+                                                int32_t (&s)[8]) {
+  int32_t a[4], b[4];
+  sidct8(pack_lo16(r[0][k], r[2][k]), pack_lo16(r[4][k], r[6][k]), pack_lo16(r[1][k], r[3][k]),
+         pack_lo16(r[5][k], r[7][k]), kW4 * ((1 << 19) / kW4), a, b);
+#pragma unroll
+  for (int u = 0; u < 4; u++) {
+    s[u] = (int32_t)((uint32_t)a[u] + (uint32_t)b[u]);
+    s[7 - u] = (int32_t)((uint32_t)a[u] - (uint32_t)b[u]);
+  }
+}
+// px: 64 pixels, row-major
+template <int NT>
+__device__ __forceinline__ void simple_idct_slots(const uint32_t* b32, int32_t (&px)[64]) {
+  uint32_t r[8][8];
+  simple_idct_rows<NT>(b32, r);
 #pragma unroll
   for (int k = 0; k < 8; k++) {
-    int32_t a[4], b[4];
-    sidct8(pack_lo16(r[0][k], r[2][k]), pack_lo16(r[4][k], r[6][k]), pack_lo16(r[1][k], r[3][k]),
-           pack_lo16(r[5][k], r[7][k]), kW4 * ((1 << 19) / kW4), a, b);
-    px[k] = clip_u8_opaque((int32_t)((uint32_t)a[0] + (uint32_t)b[0]) >> 20);
-    px[8 + k] = clip_u8_opaque((int32_t)((uint32_t)a[1] + (uint32_t)b[1]) >> 20);
-    px[16 + k] = clip_u8_opaque((int32_t)((uint32_t)a[2] + (uint32_t)b[2]) >> 20);
-    px[24 + k] = clip_u8_opaque((int32_t)((uint32_t)a[3] + (uint32_t)b[3]) >> 20);
-    px[32 + k] = clip_u8_opaque((int32_t)((uint32_t)a[3] - (uint32_t)b[3]) >> 20);
-    px[40 + k] = clip_u8_opaque((int32_t)((uint32_t)a[2] - (uint32_t)b[2]) >> 20);
-    px[48 + k] = clip_u8_opaque((int32_t)((uint32_t)a[1] - (uint32_t)b[1]) >> 20);
-    px[56 + k] = clip_u8_opaque((int32_t)((uint32_t)a[0] - (uint32_t)b[0]) >> 20);
+    int32_t s[8];
+    simple_idct_col(r, k, s);
+#pragma unroll
+    for (int j = 0; j < 8; j++) px[8 * j + k] = clip_u8_opaque(s[j] >> 20);
+  }
+}
+
+// four column sums -> clip_u8(s >> 20) as the bytes of a word, a first.
+// v_ashr_pk_u8_i32 shifts two sums and saturates them to bytes 0 and 1 of
+// its result; what it leaves in bytes 2..3 is not relied on (see
+// clip_u8_opaque, hj_idct.h: the compiler's own use of it assumes zero there,
+// which the hardware does not give), the v_perm takes the low halves only.
+// 3 instructions per 4 pixels (11 as shifts, v_med3 and ors; 7 through the
+// high halves, a packed 16-bit shift and v_sat_pk_u8_i16:
+// profiles/r09/idct/not_kept.txt).
+__device__ __forceinline__ uint32_t clip_pair(int32_t a, int32_t b) {
+  uint32_t u;
+  asm("v_ashr_pk_u8_i32 %0, %1, %2, 20" : "=v"(u) : "v"(a), "v"(b));
+  return u;
+}
+__device__ __forceinline__ uint32_t clip_pack4(int32_t a, int32_t b, int32_t c, int32_t d) {
+  return __builtin_amdgcn_perm(clip_pair(c, d), clip_pair(a, b), 0x05040100u);
+}
+// rows: the block's 8 pixel rows as the words the kernels store
+template <int NT>
+__device__ __forceinline__ void simple_idct_packed(const uint32_t* b32, uint2 (&rows)[8]) {
+  uint32_t r[8][8];
+  simple_idct_rows<NT>(b32, r);
+  int32_t s[8][8];  // [column][row]
+#pragma unroll
+  for (int k = 0; k < 8; k++) simple_idct_col(r, k, s[k]);
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    rows[j].x = clip_pack4(s[0][j], s[1][j], s[2][j], s[3][j]);
+    rows[j].y = clip_pack4(s[4][j], s[5][j], s[6][j], s[7][j]);
   }
 }
 
@@ -4672,6 +4816,26 @@ __device__ __forceinline__ void idct_block(const uint32_t* b32, int32_t (&px)[64
     for (int i = 0; i < 64; i++) px[i] = blk[i] & 255;
   } else {
     islow_block(blk, px);
+  }
+}
+
+// The same as the 8 pixel rows a kernel stores (bytes in x order).
+template <int NT, int IDCT>
+__device__ __forceinline__ void idct_block_rows(const uint32_t* b32, uint2 (&rows)[8]) {
+#if HJ_IDCT_PACK
+  if (IDCT == 0) {
+    simple_idct_packed<NT>(b32, rows);
+    return;
+  }
+#endif
+  int32_t px[64];
+  idct_block<NT, IDCT>(b32, px);
+#pragma unroll
+  for (int r = 0; r < 8; r++) {
+    rows[r].x = (uint32_t)px[8 * r] | ((uint32_t)px[8 * r + 1] << 8) |
+                ((uint32_t)px[8 * r + 2] << 16) | ((uint32_t)px[8 * r + 3] << 24);
+    rows[r].y = (uint32_t)px[8 * r + 4] | ((uint32_t)px[8 * r + 5] << 8) |
+                ((uint32_t)px[8 * r + 6] << 16) | ((uint32_t)px[8 * r + 7] << 24);
   }
 }
 
@@ -4715,34 +4879,17 @@ __global__ void __launch_bounds__(kIdctThreads) idct_kernel(const uint32_t* __re
   __syncthreads();
   if (j >= in.nblocks) return;
   const ImageDesc& dd = desc[img];
-  const int bpm = in.bpm;
-  const int mcu = j / bpm, b = j - mcu * bpm;
-  const int c = in.mcu_comp[b];
-  const int mx = mcu % in.mcux, my = mcu / in.mcux;
-  int bx, by;
-  if (in.ncomp == 1) {
-    bx = mx;
-    by = my;
-  } else {
-    bx = mx * in.comp_h[c] + in.mcu_dx[b];
-    by = my * in.comp_v[c] + in.mcu_dy[b];
-  }
+  const IdctBlockPos bp = idct_block_pos(in, (uint32_t)j);
+  const int c = bp.c;
   uint32_t* b32 = &sblk[0][threadIdx.x];
   list_block<kIdctThreads>(ents, bdesc[(size_t)dd.coef_off + j], dd.coef_off, in.nblocks, sq[c],
                            b32);
-  int32_t px[64];
-  idct_block<kIdctThreads, IDCT>(b32, px);
+  uint2 rows[8];
+  idct_block_rows<kIdctThreads, IDCT>(b32, rows);
   const int stride = dd.plane_stride[c];
-  uint8_t* dst = planes + dd.plane_off[c] + (size_t)by * 8 * stride + bx * 8;
+  uint8_t* dst = planes + dd.plane_off[c] + (size_t)bp.by * 8 * stride + bp.bx * 8;
 #pragma unroll
-  for (int r = 0; r < 8; r++) {
-    uint2 v;
-    v.x = (uint32_t)px[8 * r] | ((uint32_t)px[8 * r + 1] << 8) | ((uint32_t)px[8 * r + 2] << 16) |
-          ((uint32_t)px[8 * r + 3] << 24);
-    v.y = (uint32_t)px[8 * r + 4] | ((uint32_t)px[8 * r + 5] << 8) |
-          ((uint32_t)px[8 * r + 6] << 16) | ((uint32_t)px[8 * r + 7] << 24);
-    *reinterpret_cast<uint2*>(dst + (size_t)r * stride) = v;
-  }
+  for (int r = 0; r < 8; r++) *reinterpret_cast<uint2*>(dst + (size_t)r * stride) = rows[r];
 }
 
 // ---------------------------------------------------------------------------
@@ -5880,12 +6027,12 @@ __global__ void __launch_bounds__(kFusedThreads) idct_rgb_kernel(const uint32_t*
   const int m = tid / bpm, b = tid - m * bpm;
   load_dequant<kFusedThreads>(sq, in, tid);
   __syncthreads();
-  int32_t px[64];
+  uint2 px[8];
   if (act) {
     const int j = (my * in.mcux + mx0 + m) * bpm + b;
     list_block<kFusedThreads>(ents, bdesc[(size_t)dd.coef_off + j], dd.coef_off, in.nblocks,
                               sq[in.mcu_comp[b]], &sblk[0][tid]);
-    idct_block<kFusedThreads, IDCT>(&sblk[0][tid], px);
+    idct_block_rows<kFusedThreads, IDCT>(&sblk[0][tid], px);
   }
   __syncthreads();  // every slot read: the tile takes their place
   uint8_t* tl = reinterpret_cast<uint8_t*>(&sblk[0][0]);  // hy x ys luma, then 8 x cs U, V
@@ -5897,14 +6044,7 @@ __global__ void __launch_bounds__(kFusedThreads) idct_rgb_kernel(const uint32_t*
                           : (c == 1 ? tu : tv) + m * 8;
     const int st = c == 0 ? ys : cs;
 #pragma unroll
-    for (int r = 0; r < 8; r++) {
-      uint2 v;
-      v.x = (uint32_t)px[8 * r] | ((uint32_t)px[8 * r + 1] << 8) | ((uint32_t)px[8 * r + 2] << 16) |
-            ((uint32_t)px[8 * r + 3] << 24);
-      v.y = (uint32_t)px[8 * r + 4] | ((uint32_t)px[8 * r + 5] << 8) |
-            ((uint32_t)px[8 * r + 6] << 16) | ((uint32_t)px[8 * r + 7] << 24);
-      *reinterpret_cast<uint2*>(dst + r * st) = v;
-    }
+    for (int r = 0; r < 8; r++) *reinterpret_cast<uint2*>(dst + r * st) = px[r];
   }
   __syncthreads();
   const int w = dd.ow, h = dd.oh;
