@@ -183,6 +183,61 @@ typedef struct spdl_hj_image_info {
 
 typedef struct spdl_hj_ctx spdl_hj_ctx;
 
+/* ---- source crop (additive in ABI 7: two functions, one type, one read-only
+ * parameter; a binding finds them by symbol) --------------------------------
+ * A rectangle of the decoder's own frame, taken before anything else: what
+ * the reference's filter graph does for "crop=w:h:x:y,scale=..."
+ * (src/spdl/io/_preprocessing.py:248-249) -- libavfilter's crop filter with
+ * exact=0, applied while the frame is still yuvj4xxp / gray8 / gbrp (the
+ * format constraint reaches back only as far as scale).  The crop moves the
+ * plane pointers and shrinks the frame; the chain of spdl_hj_output then
+ * builds ONE swscale context for the cropped size.  swscale never reads
+ * outside the crop: border taps fold at the crop's edges and chroma comes from
+ * the cropped chroma planes.  The result is therefore NOT a slice of the
+ * uncropped result (a whole 4:2:0 frame of odd height takes the general
+ * scaler, an even-sized crop of it the unscaled converter).
+ *
+ * With hs, vs the frame's chroma ratios as FFmpeg's pixel format states them
+ * (gray, RGB-coded, 4-component and 4:4:4 frames 1, 1; 4:2:2 2, 1; 4:2:0 2, 2;
+ * 4:4:0 1, 2; 4:1:1 4, 1; 4:1:0 4, 4; in general hmax / h_samp[1],
+ * vmax / v_samp[1]) and W x H the frame:
+ *   w is rounded down to a multiple of hs, h to a multiple of vs; a rounded
+ *     w or h of 0, or one larger than the frame, is SPDL_HJ_ERR_BAD_GEOMETRY
+ *     for that image alone -- the rest of the batch decodes
+ *   x < 0 becomes 0, x + w > W becomes W - w, then x is rounded down to a
+ *     multiple of hs; y likewise with vs
+ *   component c's window is (x >> log2 hs_c, y >> log2 vs_c), of size
+ *     ceil(w / hs_c) x ceil(h / vs_c)
+ *   x or y may be SPDL_HJ_CROP_CENTER: (W - w) / 2; with a w (h) that is no
+ *     multiple of hs (vs) the image is refused with SPDL_HJ_ERR_BAD_GEOMETRY
+ *     (vf_crop's order of rounding and centring is not pinned here, and a
+ *     refusal beats a guess)
+ *   (0, 0, 0, 0) means no crop for that image
+ * These rules restate vf_crop's documented behaviour ("rounded to nearest
+ * smaller value"); they are not pinned against FFmpeg itself.
+ *
+ * Every output format and dtype takes crops (SPDL_HJ_FMT_YUV with its pad /
+ * crop grid rules); csc = JFIF with crops is SPDL_HJ_ERR_INVALID_ARG.  With
+ * resize == 0 the output is the region itself and all regions of the batch
+ * must resolve to one size.  spdl_hj_output_size is unchanged: pass it the
+ * resolved w, h.  Only the MCUs a region touches are inverse-transformed
+ * ("idct_workgroups"); entropy decode still covers the whole scan. */
+#define SPDL_HJ_CROP_CENTER INT32_MIN
+typedef struct {
+  int32_t x, y, w, h;
+} spdl_hj_rect;
+
+/* Resolve one rectangle by the rules above (host only: no device, no
+ * context).  (0, 0, 0, 0) resolves to the whole frame. */
+int spdl_hj_crop_rect(const spdl_hj_image_info* info, const spdl_hj_rect* in, spdl_hj_rect* out);
+
+/* Set the rectangles of the next batch submission on `ctx`: the next
+ * spdl_hj_decode_batch, _device or _staged call consumes them, whether it
+ * succeeds or not; n must equal that call's n (else that call returns
+ * SPDL_HJ_ERR_INVALID_ARG).  rects == NULL or n == 0 clears them.
+ * spdl_hj_decode_planes and spdl_hj_debug_entropy neither use nor clear them. */
+int spdl_hj_set_crops(spdl_hj_ctx* ctx, const spdl_hj_rect* rects, int32_t n);
+
 /* ABI version of the loaded library (== SPDL_HJ_ABI_VERSION). */
 int spdl_hj_abi_version(void);
 
@@ -425,7 +480,9 @@ const char* spdl_hj_stage_name(int32_t i);
  * hand-off gave up, since the context was created; "streams", the HIP
  * streams a batch holding a progressive image may use (one per lane, a
  * multi-scan side stream per lane when the hardware queues allow, the copy
- * stream).
+ * stream); "idct_workgroups" (with the source crop), the IDCT workgroups the last submission
+ * launched (0 when the fused full-resolution kernel ran instead): a source
+ * crop's region-only IDCT shows here.
  * Builds with -DHJ_ABLATIONS=1 also take "debug_mask" (timing ablations that
  * skip kernel phases; outputs wrong); release builds reject it. */
 int spdl_hj_set_param(spdl_hj_ctx* ctx, const char* name, int64_t value);

@@ -53,6 +53,8 @@ EXPORTED = (
     "spdl_hj_tar_index",
     "spdl_hj_nv12_to_planar_rgb",
     "spdl_hj_copy",
+    "spdl_hj_crop_rect",
+    "spdl_hj_set_crops",
 )
 
 
@@ -66,6 +68,24 @@ class ImageInfo(ctypes.Structure):
         ("color", ctypes.c_int32),  # spdl_hj_color: GRAY YCBCR RGB CMYK YCCK YCBCRK
         ("multiscan", ctypes.c_int32),  # progressive or non-interleaved (ABI 5)
     ]
+
+
+CROP_CENTER = -(1 << 31)  # SPDL_HJ_CROP_CENTER: x or y of a source crop, "centred"
+
+
+class Rect(ctypes.Structure):  # spdl_hj_rect
+    _fields_ = [("x", ctypes.c_int32), ("y", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("h", ctypes.c_int32)]
+
+
+def _rect(r) -> Rect:
+    """``(x, y, w, h)`` -> spdl_hj_rect; ``None`` is no crop, an ``x`` or ``y``
+    of ``None`` is centred."""
+    if r is None:
+        return Rect(0, 0, 0, 0)
+    x, y, w, h = r
+    return Rect(CROP_CENTER if x is None else int(x), CROP_CENTER if y is None else int(y),
+                int(w), int(h))
 
 
 class OutputSpec(ctypes.Structure):
@@ -102,6 +122,12 @@ class Output:
     aspect ratio, ``-n`` also makes the size divisible by n).
     ``pix_fmt="yuv"`` keeps the frame's own planar format: the chain with no
     format node (u8, ``csc="swscale"`` only; layout: :func:`planar_layout`).
+
+    ``src_crop=(x, y, w, h)`` crops the decoder's own frame before the chain,
+    for every image (libavfilter's ``crop=w:h:x:y`` ahead of ``scale``; ``x``
+    or ``y`` of ``None`` is centred; include/spdl_hipjpeg.h "source crop").
+    It is no field of the C output spec: the decoder passes it on through
+    ``spdl_hj_set_crops``.
     """
 
     pix_fmt: str = "rgb"
@@ -122,6 +148,7 @@ class Output:
     # "swscale": the reference CPU path's libswscale arithmetic (scale +
     # yuvj -> rgb24); "jfif": IJG libjpeg tables, nearest chroma (full-res)
     csc: str = "swscale"
+    src_crop: tuple | None = None
 
     def to_c(self) -> OutputSpec:
         if self.pix_fmt not in PIX_FMTS:
@@ -242,6 +269,11 @@ def lib() -> ctypes.CDLL:
             vp, i32, i32, i32, i32, i32, vp, sz, ctypes.c_int, vp, i32, cp, sz
         ]
         L.spdl_hj_copy.argtypes = [vp, vp, sz, i32, ctypes.c_int, vp, i32, cp, sz]
+        if hasattr(L, "spdl_hj_set_crops"):  # (additive in ABI 7; an older A/B build has neither)
+            L.spdl_hj_crop_rect.argtypes = [
+                ctypes.POINTER(ImageInfo), ctypes.POINTER(Rect), ctypes.POINTER(Rect)
+            ]
+            L.spdl_hj_set_crops.argtypes = [vp, vp, i32]
         ver = L.spdl_hj_abi_version()
         # (an explicitly chosen older build, ABI >= 5, loads for A/B runs)
         if ver != ABI_VERSION and not (os.environ.get("SPDL_AMD_LIB") and 5 <= ver < ABI_VERSION):
@@ -259,6 +291,15 @@ def get_image_info(data) -> ImageInfo:
     if rc:
         raise RuntimeError(f"Failed to decode an image. (header probe: status {rc})")
     return info
+
+
+def crop_rect(info: ImageInfo, rect) -> tuple[int, tuple | None]:
+    """``(status, (x, y, w, h))`` of the source crop ``rect`` on a frame with
+    the probe ``info``, resolved as the decode calls resolve it
+    (spdl_hj_crop_rect; host only).  The tuple is ``None`` when refused."""
+    r, o = _rect(rect), Rect()
+    rc = lib().spdl_hj_crop_rect(ctypes.byref(info), ctypes.byref(r), ctypes.byref(o))
+    return int(rc), (None if rc else (o.x, o.y, o.w, o.h))
 
 
 def output_size(width: int, height: int, out: Output) -> tuple[int, int]:
@@ -440,13 +481,41 @@ class Decoder:
         return {lib().spdl_hj_stage_name(i).decode(): buf[i] for i in range(n.value)
                 if buf[i] >= 0.0}
 
+    def set_crops(self, crops, n: int | None = None) -> None:
+        """The source crops of the next batch submission (spdl_hj_set_crops):
+        a sequence of ``(x, y, w, h)`` or ``None`` per image; ``None`` or an
+        empty one clears them.  A prebuilt ``(Rect * n)`` array is passed as it
+        is (no marshalling per call)."""
+        if isinstance(crops, ctypes.Array):
+            if lib().spdl_hj_set_crops(self._h, crops, len(crops) if n is None else n):
+                raise ValueError("invalid source crops")
+            return
+        crops = list(crops) if crops is not None else []
+        arr = (Rect * max(len(crops), 1))(*[_rect(r) for r in crops])
+        if lib().spdl_hj_set_crops(self._h, arr if crops else None, len(crops) if n is None else n):
+            raise ValueError("invalid source crops")
+
+    def _crops(self, out: Output, crops, n: int) -> None:
+        """Hand the submission's rectangles to the context: ``crops`` per
+        image, or ``out.src_crop`` for every image."""
+        if crops is not None and out.src_crop is not None:
+            raise ValueError("crops= and Output.src_crop are exclusive")
+        if crops is None and out.src_crop is not None:
+            crops = [out.src_crop] * n
+        if crops is not None:
+            if len(crops) != n:
+                raise ValueError(f"{len(crops)} crops for a batch of {n} images")
+            self.set_crops(crops)
+
     def decode_batch(self, datas, out: Output, out_ptr: int, out_bytes: int, stream=None,
-                     sync: bool = True, check: bool = True) -> list[int]:
+                     sync: bool = True, check: bool = True, crops=None) -> list[int]:
         """Per-image statuses.  A failed image raises RuntimeError unless
-        ``check`` is False (synchronous calls), which returns the statuses."""
+        ``check`` is False (synchronous calls), which returns the statuses.
+        ``crops``: a source crop ``(x, y, w, h)`` or ``None`` per image."""
         n = len(datas)
         if n == 0:
             raise RuntimeError("Failed to decode an image. (the batch is empty)")
+        self._crops(out, crops, n)
         # borrowed for the duration of the call, no copy (the reference binds
         # memoryviews as string_views, src/spdl/io/lib/cuda/memoryview_utils.h:17-20)
         keep = []
@@ -470,13 +539,15 @@ class Decoder:
 
     def decode_batch_device(self, dev_ptr: int, dev_bytes: int, offsets, sizes, infos,
                             out: Output, out_ptr: int, out_bytes: int, stream=None,
-                            sync: bool = True) -> list[int]:
+                            sync: bool = True, crops=None, check: bool = True) -> list[int]:
         """``offsets``/``sizes``: sequences or int64 numpy arrays; ``infos``: a
         sequence of ImageInfo or a prebuilt ``(ImageInfo * n)`` array (pass the
         same objects again to skip re-marshalling on every call)."""
         import numpy as np
 
         n = len(offsets)
+        if crops is not None or out.src_crop is not None:
+            self._crops(out, crops, n)
         offs = np.ascontiguousarray(offsets, dtype=np.int64)
         szs = np.ascontiguousarray(sizes, dtype=np.int64)
         inf = infos if isinstance(infos, ctypes.Array) else (ImageInfo * n)(*infos)
@@ -488,7 +559,7 @@ class Decoder:
             ctypes.byref(spec), out_ptr, out_bytes, _stream_handle(stream), int(bool(sync)),
             status.ctypes.data, err, 1024,
         )
-        if rc:
+        if rc and not (not check and sync and status.any()):
             raise RuntimeError(err.value.decode() or f"Failed to decode an image. ({rc})")
         return status.tolist()
 
@@ -548,8 +619,10 @@ class Decoder:
             raise RuntimeError(err.value.decode())
 
     def decode_staged(self, ticket: int, nbytes: int, offsets, sizes, out: Output, out_ptr: int,
-                      out_bytes: int, stream=None, sync: bool = True) -> list[int]:
+                      out_bytes: int, stream=None, sync: bool = True, crops=None,
+                      check: bool = True) -> list[int]:
         n = len(offsets)
+        self._crops(out, crops, n)
         offs = (ctypes.c_int64 * n)(*offsets)
         szs = (ctypes.c_int64 * n)(*sizes)
         status = (ctypes.c_int32 * max(n, 1))()
@@ -558,7 +631,7 @@ class Decoder:
         rc = lib().spdl_hj_decode_staged(
             self._h, int(ticket), int(nbytes), offs, szs, n, ctypes.byref(spec), out_ptr,
             out_bytes, _stream_handle(stream), int(bool(sync)), status, err, 1024)
-        if rc:
+        if rc and not (not check and sync and any(status)):
             raise RuntimeError(err.value.decode() or f"Failed to decode an image. ({rc})")
         return list(status)[:n]
 

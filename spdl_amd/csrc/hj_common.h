@@ -212,6 +212,17 @@ struct ImageDesc {      // host-filled per image
   // format or a geometry it refuses); parse_kernel reports it and every later
   // kernel skips the image, the rest of the batch decodes
   int32_t refuse;
+  // idct_kernel's blocks of this image: nblocks, or those of the MCU rectangle
+  // covering a source crop (reg_mw x reg_mh MCUs from (reg_mx0, reg_my0);
+  // reg_mw == 0: no crop -- the image's own order and grid)
+  int32_t idct_blocks;
+  int32_t reg_mx0, reg_my0, reg_mw, reg_mh;
+  uint32_t reg_mw_magic;  // idct_div_magic(reg_mw)
+  // The source window (spdl_hj_set_crops; the whole component without a crop):
+  // component c's origin in its plane and its size.  The output kernels read
+  // rows [win_y, win_y + win_h) from column win_x on and nothing else -- plane
+  // bytes outside the crop's MCU rectangle are stale.
+  int32_t win_x[kMaxComp], win_y[kMaxComp], win_w[kMaxComp], win_h[kMaxComp];
   int32_t pad_;
 };
 
@@ -301,6 +312,20 @@ inline HJ_HD IdctBlockPos idct_block_pos(const ImageInfo& in, uint32_t j) {
   const int b = (int)m.r, c = in.mcu_comp[b];
   if (in.ncomp == 1) return {c, (int)p.r, (int)p.q};
   return {c, (int)p.r * in.comp_h[c] + in.mcu_dx[b], (int)p.q * in.comp_v[c] + in.mcu_dy[b]};
+}
+
+// idct_kernel over a source crop: its threads enumerate the blocks of the MCU
+// rectangle covering the crop (mw MCUs to a row, from MCU (mx0, my0); gray
+// and non-interleaved frames: the same with their blocks as the MCUs).  Local
+// index l -> (MCU of the rectangle, block of the MCU) -> the block's index in
+// the image's MCU order, which bdesc and idct_block_pos take.  mw_magic =
+// idct_div_magic(mw), host-made (ImageDesc::reg_mw_magic).
+inline HJ_HD uint32_t idct_region_block(const ImageInfo& in, int mx0, int my0, int mw,
+                                        uint32_t mw_magic, uint32_t l) {
+  const IdctDivMod m = idct_divmod(l, (uint32_t)in.bpm, in.bpm_magic);  // rectangle's MCU, block
+  const IdctDivMod p = idct_divmod(m.q, (uint32_t)mw, mw_magic);        // its row, column there
+  return ((uint32_t)(my0 + (int)p.q) * (uint32_t)in.mcux + (uint32_t)(mx0 + (int)p.r)) *
+             (uint32_t)in.bpm + m.r;
 }
 
 // destuff: chunk-parallel over kDsChunk-byte chunks; per-chunk counts and prefixes

@@ -406,12 +406,46 @@ int chroma_shifts(const spdl_hj_image_info& p, int* hs, int* vs) {
   return SPDL_HJ_OK;
 }
 
+// ---- source crop (spdl_hipjpeg.h: libavfilter's crop, exact=0, on the
+// decoder's frame) -----------------------------------------------------------
+// One axis: the size rounded down to the chroma ratio, the origin clamped into
+// the frame and then rounded down likewise.  A centred origin with an
+// off-grid size is refused (vf_crop's order of rounding and centring there is
+// not pinned).
+int crop_axis(int64_t pos, int64_t size, int64_t full, int ratio, int32_t* opos, int32_t* osize) {
+  const int64_t s = size / ratio * ratio;
+  if (size <= 0 || s <= 0 || s > full) return SPDL_HJ_ERR_BAD_GEOMETRY;
+  if (pos == SPDL_HJ_CROP_CENTER) {
+    if (size % ratio) return SPDL_HJ_ERR_BAD_GEOMETRY;
+    pos = (full - s) / 2;
+  }
+  if (pos < 0) pos = 0;
+  if (pos + s > full) pos = full - s;
+  *opos = (int32_t)(pos / ratio * ratio);
+  *osize = (int32_t)s;
+  return SPDL_HJ_OK;
+}
+
+bool rect_is_none(const spdl_hj_rect& r) { return !(r.x | r.y | r.w | r.h); }
+
+int crop_resolve(const spdl_hj_image_info& p, const spdl_hj_rect& in, spdl_hj_rect* out) {
+  if (p.width <= 0 || p.height <= 0) return SPDL_HJ_ERR_INVALID_ARG;
+  if (rect_is_none(in)) {
+    *out = {0, 0, p.width, p.height};
+    return SPDL_HJ_OK;
+  }
+  int hsub, vsub;
+  if (int rc = chroma_shifts(p, &hsub, &vsub)) return rc;
+  if (int rc = crop_axis(in.x, in.w, p.width, 1 << hsub, &out->x, &out->w)) return rc;
+  return crop_axis(in.y, in.h, p.height, 1 << vsub, &out->y, &out->h);
+}
+
 struct Layout {
   std::vector<ImageDesc> desc;
   std::vector<int32_t> tables;  // the batch's swscale table pool
   int64_t total_blocks = 0, total_planes = 0, total_segs = 0, total_recs = 0;
   int64_t out_elems_per_image = 0;
-  int max_blocks = 0;
+  int max_blocks = 0;  // most blocks idct_kernel transforms of one image (ImageDesc::idct_blocks)
   int64_t max_px = 0;
   int64_t total_ds = 0;
   int max_chunks = 0;
@@ -447,9 +481,21 @@ struct Layout {
 
 int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_image_info* infos,
                  int n, const spdl_hj_output* out, int sub_bits, int64_t piece_bytes, Layout& L,
-                 int32_t* status, char* err, size_t errlen, PlanCache* plans) {
+                 int32_t* status, char* err, size_t errlen, PlanCache* plans,
+                 const spdl_hj_rect* crops = nullptr) {
   L.desc.assign(n, ImageDesc{});
   const bool yuv = out->pix_fmt == SPDL_HJ_FMT_YUV;
+  bool have_size = false;  // L.ow x L.oh is set (by the first image that is not refused)
+  bool have_fmt = false;   // ... and the planar output's frame format
+  // an image the host refuses alone (ImageDesc::refuse): its one output
+  // workgroup reports the status, every other kernel skips it
+  auto refuse = [&](ImageDesc& d, int why) {
+    d.refuse = why;
+    d.sws_wg0 = (int32_t)L.sws_wgs++;
+    d.sws_bands = d.sws_chunks = 1;
+    L.sws_bands = std::max(L.sws_bands, 1);
+    L.sws_chunks = std::max(L.sws_chunks, 1);
+  };
   // plan -> offset in L.tables.  `alive` holds every placed plan until the
   // layout is built: the cache may evict (and free) a plan mid-batch, and a
   // new plan at a recycled address must not match a stale `placed` entry
@@ -484,13 +530,14 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
     }
     int bw[kMaxComp] = {}, bh[kMaxComp] = {};
     int64_t nblocks;
+    int bpm = 0;
     if (p.ncomp == 1) {
       bw[0] = (p.width + 7) / 8;
       bh[0] = (p.height + 7) / 8;
       nblocks = (int64_t)bw[0] * bh[0];
+      bpm = hmax = vmax = 1;  // (a gray frame's factors mean nothing)
     } else {
       int mcux = (p.width + 8 * hmax - 1) / (8 * hmax), mcuy = (p.height + 8 * vmax - 1) / (8 * vmax);
-      int bpm = 0;
       for (int c = 0; c < p.ncomp; c++) {
         if (hmax % p.h_samp[c] || vmax % p.v_samp[c]) return fail(i, SPDL_HJ_ERR_UNSUPPORTED, nullptr);
         bw[c] = mcux * p.h_samp[c];
@@ -506,11 +553,37 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
     d.nblocks = (int)nblocks;
     d.coef_off = L.total_blocks;
     L.total_blocks += nblocks;
-    if (d.nblocks > L.max_blocks) L.max_blocks = d.nblocks;
+    // The source crop: the frame every later step sees (src; the whole frame
+    // without one).  A rectangle that does not resolve refuses its image alone.
+    spdl_hj_rect src{0, 0, p.width, p.height};
+    const bool has_rect = crops && !rect_is_none(crops[i]);
+    int crop_rc = has_rect ? crop_resolve(p, crops[i], &src) : SPDL_HJ_OK;
+    if (crop_rc && crop_rc != SPDL_HJ_ERR_BAD_GEOMETRY) return fail(i, crop_rc, nullptr);
+    if (crop_rc) src = {0, 0, p.width, p.height};
+    d.idct_blocks = d.nblocks;
+    if (has_rect && !crop_rc) {
+      // idct_kernel visits the MCUs the crop touches (gray: its blocks)
+      const int mw8 = 8 * hmax, mh8 = 8 * vmax;
+      d.reg_mx0 = src.x / mw8;
+      d.reg_my0 = src.y / mh8;
+      d.reg_mw = (src.x + src.w - 1) / mw8 - d.reg_mx0 + 1;
+      d.reg_mh = (src.y + src.h - 1) / mh8 - d.reg_my0 + 1;
+      d.reg_mw_magic = idct_div_magic((uint32_t)d.reg_mw);
+      d.idct_blocks = d.reg_mw * d.reg_mh * bpm;
+    }
+    if (d.idct_blocks > L.max_blocks) L.max_blocks = d.idct_blocks;
     for (int c = 0; c < p.ncomp; c++) {
       d.plane_stride[c] = bw[c] * 8;
       d.plane_off[c] = L.total_planes;
       L.total_planes += round_up((int64_t)bw[c] * 8 * bh[c] * 8, 256);
+      // component c's window: origin (x >> log2 hs_c, y >> log2 vs_c), size
+      // ceil(w / hs_c) x ceil(h / vs_c) -- the whole component without a crop
+      const int hsc = p.ncomp == 1 ? 1 : hmax / p.h_samp[c];
+      const int vsc = p.ncomp == 1 ? 1 : vmax / p.v_samp[c];
+      d.win_x[c] = src.x / hsc;
+      d.win_y[c] = src.y / vsc;
+      d.win_w[c] = (src.w + hsc - 1) / hsc;
+      d.win_h[c] = (src.h + vsc - 1) / vsc;
     }
     d.seg_cap = (int32_t)(sizes[i] / 2 + 2);
     d.seg_off = L.total_segs;
@@ -521,7 +594,7 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
     d.ds_wg0 = (int32_t)L.ds_wgs;
     L.ds_wgs += d.ds_cap;
     d.idct_wg0 = (int32_t)L.idct_wgs;
-    L.idct_wgs += (nblocks + kIdctThreads - 1) / kIdctThreads;
+    L.idct_wgs += (d.idct_blocks + kIdctThreads - 1) / kIdctThreads;
     if (d.ds_cap > L.max_chunks) L.max_chunks = d.ds_cap;
     // size-adaptive entropy decode: a file larger than piece_bytes is
     // decoded by ceil(size / piece_bytes) workgroups (progressive and
@@ -539,14 +612,20 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
     d.rec_cap = (int64_t)kMaxSlots * 8 * pieces;
     d.rec_off = L.total_recs;
     L.total_recs += d.rec_cap;
+    if (has_rect) L.all_special = false;  // the full-resolution converters read whole planes
+    if (crop_rc) {
+      refuse(d, crop_rc);
+      continue;
+    }
     Geom g;
-    int rc = geometry(p.width, p.height, out, &g);
+    int rc = geometry(src.w, src.h, out, &g);
     if (rc) return fail(i, rc, nullptr);
     d.dx = g.dx;
     d.dy = g.dy;
     d.ow = g.ow;
     d.oh = g.oh;
-    if (i == 0) {
+    if (!have_size) {
+      have_size = true;
       L.ow = g.ow;
       L.oh = g.oh;
     } else if (g.ow != L.ow || g.oh != L.oh) {
@@ -569,19 +648,19 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
       const bool gray = p.ncomp == 1;
       if (!why && (p.ncomp == 4 || p.color == kColorRgb || hs > 1 || vs > hs))
         why = SPDL_HJ_ERR_UNSUPPORTED;
-      if (i == 0) {
-        if (why) return fail(0, why, "no planar output for this frame format");
+      // (image 0, or the first one after images whose source crop was refused)
+      if (!have_fmt) {
+        have_fmt = true;
+        if (why) return fail(i, why, "no planar output for this frame format");
         L.yuv_hs = hs;
         L.yuv_vs = vs;
         L.yuv_gray = gray;
       } else if (!why && (hs != L.yuv_hs || vs != L.yuv_vs || gray != L.yuv_gray)) {
         why = SPDL_HJ_ERR_UNSUPPORTED;
       }
-      if (!why) why = geometry(p.width, p.height, out, &g, 1 << hs, 1 << vs);
+      if (!why) why = geometry(src.w, src.h, out, &g, 1 << hs, 1 << vs);
       if (why) {
-        d.refuse = why;
-        d.sws_wg0 = (int32_t)L.sws_wgs++;
-        d.sws_bands = d.sws_chunks = 1;
+        refuse(d, why);
         continue;
       }
       d.dx = g.dx;
@@ -595,7 +674,7 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
              : p.color == kColorRgb || p.color == kColorCmyk ? kPlanGbr
                                                               : kPlanYuv;
     }
-    const PlanKey key{p.width, p.height, hs, vs, mode, out->resize ? out->filter : 0,
+    const PlanKey key{src.w, src.h, hs, vs, mode, out->resize ? out->filter : 0,
                       g.sw, g.sh, g.dx, g.dy, g.ow, g.oh};
     auto plan = plans->get(key, &rc);
     if (!plan) return fail(i, rc, rc == SPDL_HJ_ERR_BAD_GEOMETRY ? "scale filter too long" : nullptr);
@@ -684,6 +763,7 @@ struct Slot {
     std::vector<int> idx;
     std::vector<int64_t> off, size;
     std::vector<spdl_hj_image_info> info;
+    std::vector<spdl_hj_rect> rect;  // their source crops (empty: the batch had none)
   } retry;
 };
 
@@ -791,6 +871,9 @@ struct spdl_hj_ctx {
   // images re-decoded in one workgroup after a wait gave up
   int64_t handoff_wait_us = 2000000;
   int64_t handoff_retries = 0;
+  // spdl_hj_set_crops: the source crops of the next batch submission
+  std::vector<spdl_hj_rect> crops;
+  int64_t idct_workgroups = 0;  // IDCT workgroups the last submission launched
 };
 
 namespace {
@@ -981,7 +1064,7 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
 int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t bytes_len,
                  const Layout& L, int n, const spdl_hj_output* out, void* out_dev,
                  size_t out_bytes, hipStream_t st, int sync, int32_t* status, char* err,
-                 size_t errlen, bool planes_only) {
+                 size_t errlen, bool planes_only, const spdl_hj_rect* crops = nullptr) {
   const size_t esz = out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
   if (!planes_only && (size_t)L.out_elems_per_image * n * esz > out_bytes) {
     set_err(err, errlen, "output buffer too small: need %lld bytes, have %zu",
@@ -1086,9 +1169,13 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
   const bool fast_rgb = swscale && !yuv && L.all_special && out->dtype == SPDL_HJ_DTYPE_U8 &&
                         ctx->output_path != 1;
   const bool fused = fast_rgb && L.fuse_ok && L.fused_tiles > 0 && ctx->output_path != 2;
-  if (!(abl & kAblNoIdct) && !fused)
+  ctx->idct_workgroups = 0;
+  if (!(abl & kAblNoIdct) && !fused) {
     HJ_HIP(launch_idct(B, idct_kind, idct_flat, (int)L.idct_wgs, L.max_blocks,
                        (ctx->xcd_order >> 1) & 1, st));
+    ctx->idct_workgroups =
+        idct_flat ? L.idct_wgs : (int64_t)((L.max_blocks + kIdctThreads - 1) / kIdctThreads) * n;
+  }
   // 4-component frames: FFmpeg's K transform on the planes (not on the raw
   // planes surface, which returns the IDCT output as the oracle does)
   if (!planes_only && L.cmyk_px > 0) HJ_HIP(launch_cmyk(B, L.cmyk_px, st));
@@ -1138,8 +1225,10 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
   R.off.clear();
   R.size.clear();
   R.info.clear();
+  R.rect.clear();
   if (!planes_only) {
     for (const auto& m : L.multi) {
+      if (crops) R.rect.push_back(crops[m.first]);
       R.idx.push_back(m.first);
       R.off.push_back(L.desc[m.first].in_off);
       R.size.push_back(L.desc[m.first].in_size);
@@ -1195,7 +1284,7 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, int k) {
   Layout L;
   int32_t st1 = SPDL_HJ_OK;
   int rc = build_layout(&r.off[k], &r.size[k], &r.info[k], 1, &r.out, ctx->sub_bits, 0, L, &st1,
-                        err, errlen, &ctx->plans);
+                        err, errlen, &ctx->plans, r.rect.empty() ? nullptr : &r.rect[k]);
   if (rc) return rc;
   // the spare slot, on the failed batch's lane (its workspace is free: the
   // batch has finished); the caller's last ticket is left as it was
@@ -1208,8 +1297,10 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, int k) {
   rc = exec_stream(ctx, *s, nullptr, &xs, err, errlen);
   if (rc) return rc;
   ctx->handoff_retries++;
+  const int64_t idct_wgs = ctx->idct_workgroups;  // (the batch's, not this re-decode's)
   rc = run_pipeline(ctx, *s, r.bytes, r.len, L, 1, &r.out, r.out_dev + (size_t)r.idx[k] * r.img_bytes,
                     r.img_bytes, xs, 1, &st1, err, errlen, false);
+  ctx->idct_workgroups = idct_wgs;
   ctx->last_ticket = last;
   return rc ? rc : st1;
 }
@@ -1278,6 +1369,27 @@ std::string tar_pax_path(const uint8_t* d, size_t n) {
   return std::string();
 }
 
+// The rectangles spdl_hj_set_crops left for this submission of n images:
+// taken whatever becomes of the call.  nullptr in *rects: none.
+int take_crops(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, std::vector<spdl_hj_rect>* held,
+               const spdl_hj_rect** rects, char* err, size_t errlen) {
+  held->clear();
+  held->swap(ctx->crops);
+  *rects = nullptr;
+  if (held->empty()) return SPDL_HJ_OK;
+  if ((int64_t)held->size() != n) {
+    set_err(err, errlen, "spdl_hj_set_crops gave %zu rectangles for a batch of %d images",
+            held->size(), n);
+    return SPDL_HJ_ERR_INVALID_ARG;
+  }
+  if (out && out->csc == SPDL_HJ_CSC_JFIF) {
+    set_err(err, errlen, "a source crop needs csc = swscale");
+    return SPDL_HJ_ERR_INVALID_ARG;
+  }
+  *rects = held->data();
+  return SPDL_HJ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1297,6 +1409,22 @@ int spdl_hj_output_size(int32_t w, int32_t h, const spdl_hj_output* out, int32_t
   if (rc) return rc;
   *out_w = g.ow;
   *out_h = g.oh;
+  return SPDL_HJ_OK;
+}
+
+int spdl_hj_crop_rect(const spdl_hj_image_info* info, const spdl_hj_rect* in, spdl_hj_rect* out) {
+  if (!info || !in || !out || (info->ncomp != 1 && info->ncomp != 3 && info->ncomp != 4))
+    return SPDL_HJ_ERR_INVALID_ARG;
+  for (int c = 0; c < info->ncomp; c++)
+    if (info->h_samp[c] < 1 || info->h_samp[c] > 4 || info->v_samp[c] < 1 || info->v_samp[c] > 4)
+      return SPDL_HJ_ERR_INVALID_ARG;
+  return crop_resolve(*info, *in, out);
+}
+
+int spdl_hj_set_crops(spdl_hj_ctx* ctx, const spdl_hj_rect* rects, int32_t n) {
+  if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
+  ctx->crops.clear();
+  if (rects && n > 0) ctx->crops.assign(rects, rects + n);
   return SPDL_HJ_OK;
 }
 
@@ -1370,10 +1498,14 @@ void spdl_hj_destroy(spdl_hj_ctx* c) {
 int spdl_hj_decode_batch(spdl_hj_ctx* ctx, const uint8_t* const* data, const size_t* sizes,
                          int32_t n, const spdl_hj_output* out, void* out_dev, size_t out_bytes,
                          void* stream, int32_t sync, int32_t* status, char* err, size_t errlen) {
+  std::vector<spdl_hj_rect> held;
+  const spdl_hj_rect* crops = nullptr;
+  const int crc = ctx ? take_crops(ctx, n, out, &held, &crops, err, errlen) : 0;
   if (!ctx || !data || !sizes || n <= 0 || !valid_output(out) || !out_dev) {
     set_err(err, errlen, n <= 0 ? "the batch is empty" : "invalid argument");
     return SPDL_HJ_ERR_INVALID_ARG;
   }
+  if (crc) return crc;
   DeviceGuard g(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   std::vector<spdl_hj_image_info> infos(n);
@@ -1397,7 +1529,7 @@ int spdl_hj_decode_batch(spdl_hj_ctx* ctx, const uint8_t* const* data, const siz
   }
   Layout L;
   int rc = build_layout(offs.data(), szs.data(), infos.data(), n, out, ctx->sub_bits, ctx->piece_bytes, L, status, err,
-                        errlen, &ctx->plans);
+                        errlen, &ctx->plans, crops);
   if (rc) return rc;
   L.ms_side = prog;
   L.ms_known = true;
@@ -1411,7 +1543,7 @@ int spdl_hj_decode_batch(spdl_hj_ctx* ctx, const uint8_t* const* data, const siz
   if (!rc) rc = stage_h2d(ctx, *s, (size_t)total, xs, err, errlen);
   if (rc) return rc;
   return run_pipeline(ctx, *s, static_cast<const uint8_t*>(s->bytes.p), (size_t)total, L, n, out,
-                      out_dev, out_bytes, xs, sync, status, err, errlen, false);
+                      out_dev, out_bytes, xs, sync, status, err, errlen, false, crops);
 }
 
 int spdl_hj_decode_batch_device(spdl_hj_ctx* ctx, const uint8_t* dev_data, size_t dev_bytes,
@@ -1420,16 +1552,20 @@ int spdl_hj_decode_batch_device(spdl_hj_ctx* ctx, const uint8_t* dev_data, size_
                                 const spdl_hj_output* out, void* out_dev, size_t out_bytes,
                                 void* stream, int32_t sync, int32_t* status, char* err,
                                 size_t errlen) {
+  std::vector<spdl_hj_rect> held;
+  const spdl_hj_rect* crops = nullptr;
+  const int crc = ctx ? take_crops(ctx, n, out, &held, &crops, err, errlen) : 0;
   if (!ctx || !dev_data || !offsets || !sizes || !infos || n <= 0 || !valid_output(out) ||
       !out_dev) {
     set_err(err, errlen, n <= 0 ? "the batch is empty" : "invalid argument");
     return SPDL_HJ_ERR_INVALID_ARG;
   }
+  if (crc) return crc;
   DeviceGuard g(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout L;
   int rc = build_layout(offsets, sizes, infos, n, out, ctx->sub_bits, ctx->piece_bytes, L, status, err, errlen,
-                        &ctx->plans);
+                        &ctx->plans, crops);
   if (rc) return rc;
   // the caller's probe says which files take the multi-scan path (ABI 5)
   for (int i = 0; i < n; i++) L.ms_side = L.ms_side || infos[i].multiscan != 0;
@@ -1442,7 +1578,7 @@ int spdl_hj_decode_batch_device(spdl_hj_ctx* ctx, const uint8_t* dev_data, size_
   if (rc) return rc;
   mark(ctx, *s, 0, xs);
   return run_pipeline(ctx, *s, dev_data, dev_bytes, L, n, out, out_dev, out_bytes, xs, sync,
-                      status, err, errlen, false);
+                      status, err, errlen, false, crops);
 }
 
 int64_t spdl_hj_last_ticket(spdl_hj_ctx* ctx) { return ctx ? ctx->last_ticket : 0; }
@@ -1542,6 +1678,9 @@ int spdl_hj_decode_staged(spdl_hj_ctx* ctx, int64_t ticket, size_t len, const in
                           const int64_t* sizes, int32_t n, const spdl_hj_output* out,
                           void* out_dev, size_t out_bytes, void* stream, int32_t sync,
                           int32_t* status, char* err, size_t errlen) {
+  std::vector<spdl_hj_rect> held;
+  const spdl_hj_rect* crops = nullptr;
+  const int crc = ctx ? take_crops(ctx, n, out, &held, &crops, err, errlen) : 0;
   Slot* s = ctx ? find_slot(ctx, ticket) : nullptr;
   if (!s || !s->staged) {
     set_err(err, errlen, "ticket %lld does not name an acquired staging slot", (long long)ticket);
@@ -1552,6 +1691,10 @@ int spdl_hj_decode_staged(spdl_hj_ctx* ctx, int64_t ticket, size_t len, const in
     set_err(err, errlen, n <= 0 ? "the batch is empty" : "invalid argument");
     s->ticket = 0;
     return SPDL_HJ_ERR_INVALID_ARG;
+  }
+  if (crc) {
+    s->ticket = 0;
+    return crc;
   }
   DeviceGuard g(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1572,7 +1715,7 @@ int spdl_hj_decode_staged(spdl_hj_ctx* ctx, int64_t ticket, size_t len, const in
   }
   Layout L;
   int rc = build_layout(offsets, sizes, infos.data(), n, out, ctx->sub_bits, ctx->piece_bytes, L, status, err, errlen,
-                        &ctx->plans);
+                        &ctx->plans, crops);
   if (rc) {
     s->ticket = 0;
     return rc;
@@ -1585,7 +1728,7 @@ int spdl_hj_decode_staged(spdl_hj_ctx* ctx, int64_t ticket, size_t len, const in
   if (!rc) rc = stage_h2d(ctx, *s, len + 512, xs, err, errlen);
   if (rc) return rc;
   return run_pipeline(ctx, *s, static_cast<const uint8_t*>(s->bytes.p), len + 512, L, n, out,
-                      out_dev, out_bytes, xs, sync, status, err, errlen, false);
+                      out_dev, out_bytes, xs, sync, status, err, errlen, false, crops);
 }
 
 int spdl_hj_tar_index(const uint8_t* data, size_t size, size_t start, int32_t max_entries,
@@ -2088,6 +2231,7 @@ int spdl_hj_get_param(spdl_hj_ctx* ctx, const char* name, int64_t* value) {
       {"ms_skip_empty", ctx->ms_skip_empty},
       {"xcd_order", ctx->xcd_order},
       {"handoff_retries", ctx->handoff_retries},
+      {"idct_workgroups", ctx->idct_workgroups},
   };
   for (const auto& t : tab)
     if (!strcmp(name, t.n)) {

@@ -316,7 +316,7 @@ __global__ void __launch_bounds__(256, 8) parse_kernel(const uint8_t* __restrict
   // the flat grids' dispatch maps: this image's destuff-chunk and IDCT
   // workgroups (written whatever the status: those kernels look it up)
   for (int i = tid; i < dd.ds_cap; i += blockDim.x) ds_map[dd.ds_wg0 + i] = (uint32_t)img;
-  for (int i = tid; i < (dd.nblocks + kIdctThreads - 1) / kIdctThreads; i += blockDim.x)
+  for (int i = tid; i < (dd.idct_blocks + kIdctThreads - 1) / kIdctThreads; i += blockDim.x)
     idct_map[dd.idct_wg0 + i] = (uint32_t)img;
   for (int i = tid; i < dd.hs_wgs; i += blockDim.x) hs_map[dd.hs_wg0 + i] = (uint32_t)img;
   for (int i = tid; i < dd.sws_bands * dd.sws_chunks; i += blockDim.x)
@@ -4872,13 +4872,17 @@ __global__ void __launch_bounds__(kIdctThreads) idct_kernel(const uint32_t* __re
   const bool flat = idct_map != nullptr;
   const int img = flat ? (int)idct_map[gx] : (int)gy;
   const int tile = flat ? (int)gx - desc[img].idct_wg0 : (int)gx;
-  const int j = tile * kIdctThreads + threadIdx.x;
+  int j = tile * kIdctThreads + threadIdx.x;
   const ImageInfo& in = infos[img];
-  if (in.status != kOk || tile * kIdctThreads >= in.nblocks) return;
+  const ImageDesc& dd = desc[img];
+  // (nblocks, or the blocks of the MCU rectangle a source crop touches)
+  const int nb = dd.idct_blocks;
+  if (in.status != kOk || tile * kIdctThreads >= nb) return;
   load_dequant<kIdctThreads>(sq, in, threadIdx.x);
   __syncthreads();
-  if (j >= in.nblocks) return;
-  const ImageDesc& dd = desc[img];
+  if (j >= nb) return;
+  if (dd.reg_mw)
+    j = (int)idct_region_block(in, dd.reg_mx0, dd.reg_my0, dd.reg_mw, dd.reg_mw_magic, (uint32_t)j);
   const IdctBlockPos bp = idct_block_pos(in, (uint32_t)j);
   const int c = bp.c;
   uint32_t* b32 = &sblk[0][threadIdx.x];
@@ -5070,15 +5074,19 @@ __device__ __forceinline__ int16_t h15(int32_t h) {  // hScale8To15: (sum >> 7),
 // column, its taps in registers (rows of the tap table are padded to a
 // multiple of 4 taps, `cstride` int16 apart), one or two 16-byte loads per
 // source row, the next row's load issued before the current row's taps.
-// Rows past the plane (reached by zero taps only) read its last row.
+// Rows past the plane (reached by zero taps only) read its last row.  `plane`
+// is the source window's first row at the plane's column 0 (4-byte aligned),
+// `x0` the window's first column there and `ph` its rows: a source crop's
+// origin has any alignment, the word loads keep the plane's.
 template <int NQ>
-__device__ __forceinline__ void hpass_cols(const uint8_t* plane, int stride, int ph, const int32_t* pos,
-                           const int16_t* coef, int cstride, int c0, int ncols, int r0, int r1,
+__device__ __forceinline__ void hpass_cols(const uint8_t* plane, int stride, int ph, int x0,
+                           const int32_t* pos, const int16_t* coef, int cstride, int c0,
+                           int ncols, int r0, int r1,
                            int16_t* lds, int cst, int tid, int nthreads, int rst = 1) {
   constexpr int NW = (NQ + 1 + 3) / 4 * 4;
   for (int c = tid; c < ncols; c += nthreads) {
     const int x = c0 + c;
-    const int p = pos[x];
+    const int p = x0 + pos[x];  // (the origin first: the split below is of the plane's column)
     const uint32_t sh = (uint32_t)(p & 3);
     uint32_t wp[2 * NQ];
     const uint2* cp = reinterpret_cast<const uint2*>(coef + (int64_t)x * cstride);
@@ -5104,13 +5112,14 @@ __device__ __forceinline__ void hpass_cols(const uint8_t* plane, int stride, int
 }
 
 // taps beyond 64: a plain loop over the table
-__device__ __forceinline__ void hpass_cols_long(const uint8_t* plane, int stride, int ph, const int32_t* pos,
-                                const int16_t* coef, int cstride, int taps, int c0, int ncols,
+__device__ __forceinline__ void hpass_cols_long(const uint8_t* plane, int stride, int ph, int x0,
+                                const int32_t* pos, const int16_t* coef, int cstride, int taps,
+                                int c0, int ncols,
                                 int r0, int r1, int16_t* lds, int cst, int tid, int nthreads,
                                 int rst = 1) {
   for (int c = tid; c < ncols; c += nthreads) {
     const int x = c0 + c;
-    const int p = pos[x];
+    const int p = x0 + pos[x];
     const int16_t* cf = coef + (int64_t)x * cstride;
     for (int r = r0; r < r1; r++) {
       const uint8_t* row = plane + (int64_t)min(r, ph - 1) * stride + p;
@@ -5123,13 +5132,14 @@ __device__ __forceinline__ void hpass_cols_long(const uint8_t* plane, int stride
 
 // (dst column c, row r at dst[c * cst + (r - r0) * rst]: column-major LDS by
 // default, row-major HBM for hscale_kernel)
-__device__ __forceinline__ void hpass(const uint8_t* plane, int stride, int ph, const int32_t* pos,
-                      const int16_t* coef, int cstride, int taps, int c0, int ncols, int r0, int r1,
+__device__ __forceinline__ void hpass(const uint8_t* plane, int stride, int ph, int x0,
+                      const int32_t* pos, const int16_t* coef, int cstride, int taps, int c0,
+                      int ncols, int r0, int r1,
                       int16_t* lds, int cst, int tid, int nthreads, int rst = 1) {
   const int nq = (taps + 3) >> 2;
 #define HJ_HP(N) \
-  hpass_cols<N>(plane, stride, ph, pos, coef, cstride, c0, ncols, r0, r1, lds, cst, tid, nthreads, \
-                rst)
+  hpass_cols<N>(plane, stride, ph, x0, pos, coef, cstride, c0, ncols, r0, r1, lds, cst, tid, \
+                nthreads, rst)
   if (nq <= 1) HJ_HP(1);
   else if (nq <= 2) HJ_HP(2);
   else if (nq <= 3) HJ_HP(3);
@@ -5138,8 +5148,8 @@ __device__ __forceinline__ void hpass(const uint8_t* plane, int stride, int ph, 
   else if (nq <= 8) HJ_HP(8);
   else if (nq <= 12) HJ_HP(12);
   else if (nq <= 16) HJ_HP(16);
-  else hpass_cols_long(plane, stride, ph, pos, coef, cstride, taps, c0, ncols, r0, r1, lds, cst, tid,
-                       nthreads, rst);
+  else hpass_cols_long(plane, stride, ph, x0, pos, coef, cstride, taps, c0, ncols, r0, r1, lds, cst,
+                       tid, nthreads, rst);
 #undef HJ_HP
 }
 
@@ -5229,6 +5239,13 @@ __device__ __forceinline__ void full_rgb(const BatchParams& p, int Y, int U, int
   rgb[2] = B >> 22;
 }
 
+// component c's source window (ImageDesc::win_*): its first row, at the
+// plane's column 0
+__device__ __forceinline__ const uint8_t* win_rows(const uint8_t* planes, const ImageDesc& dd,
+                                                   int c) {
+  return planes + dd.plane_off[c] + (int64_t)dd.win_y[c] * dd.plane_stride[c];
+}
+
 // hscale_kernel: swscale's horizontal pass (hScale8To15) of every source row
 // a large downscale reads, once, into a row-major int16 buffer (per image:
 // luma pre_rl x sw, then the two chroma planes pre_rc x chr_w -- gbr: three
@@ -5263,14 +5280,14 @@ __global__ void __launch_bounds__(256) hscale_kernel(const uint8_t* __restrict__
   const HsPlane hp = hs_plane(s, c);
   const int rows = hp.rows, w = hp.w;
   const int r0 = t * kHsRows, r1 = min(r0 + kHsRows, rows);
-  const uint8_t* plane = planes + dd.plane_off[c];
-  const int stride = dd.plane_stride[c], ph = in.comp_hpx[c];
+  const int stride = dd.plane_stride[c], ph = dd.win_h[c], wx = dd.win_x[c];
+  const uint8_t* plane = win_rows(planes, dd, c);
   const int32_t* pos = T + s.off[lumaf ? kHlPos : kHcPos];
   const int16_t* coef = reinterpret_cast<const int16_t*>(T + s.off[lumaf ? kHlCoef : kHcCoef]);
   const int cstride = lumaf ? s.hl_size : s.hc_size, taps = lumaf ? s.hl_taps : s.hc_taps;
   int16_t* dst = hbuf + dd.hbuf_off + hp.off + (int64_t)r0 * w;
   if (taps <= 64) {  // the register-bucket kernels of sws_kernel's own pass
-    hpass(plane, stride, ph, pos, coef, cstride, taps, 0, w, r0, r1, dst, 1, threadIdx.x,
+    hpass(plane, stride, ph, wx, pos, coef, cstride, taps, 0, w, r0, r1, dst, 1, threadIdx.x,
           blockDim.x, w);
     return;
   }
@@ -5278,7 +5295,7 @@ __global__ void __launch_bounds__(256) hscale_kernel(const uint8_t* __restrict__
   // registers, every row of the tile accumulated in registers across chunks
   const int nch = (taps + 63) / 64;
   for (int x = threadIdx.x; x < w; x += blockDim.x) {
-    const int p0 = pos[x];
+    const int p0 = wx + pos[x];
     const uint32_t sh = (uint32_t)(p0 & 3);
     const uint8_t* base = plane + (p0 & ~3);
     int32_t acc[kHsRows];
@@ -5508,18 +5525,21 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
     // three planes, a third of the threads each
     const int third = nt / 3, c = min(tid / third, 2), t3 = tid - c * third;
     if (tid < 3 * third)
-      hpass(planes + dd.plane_off[c], dd.plane_stride[c], in.comp_hpx[c], T + s.off[kHlPos],
+      hpass(win_rows(planes, dd, c), dd.plane_stride[c], dd.win_h[c], dd.win_x[c],
+            T + s.off[kHlPos],
             reinterpret_cast<const int16_t*>(T + s.off[kHlCoef]), s.hl_size, s.hl_taps, xs0, ncl,
             lr0, lr1, c == 0 ? hl : c == 1 ? hu : hv, lst, t3, third);
   } else if (content && !(p.debug_mask & kAblSwsHpass)) {
-    hpass(planes + dd.plane_off[0], dd.plane_stride[0], in.comp_hpx[0], T + s.off[kHlPos],
+    hpass(win_rows(planes, dd, 0), dd.plane_stride[0], dd.win_h[0], dd.win_x[0],
+          T + s.off[kHlPos],
           reinterpret_cast<const int16_t*>(T + s.off[kHlCoef]), s.hl_size, s.hl_taps, xs0, ncl,
           lr0, lr1, hl, lst, tid, nt);
     if (!s.gray) {
       // the two chroma planes share the tables: half the threads each
       const int half = nt >> 1, t2 = tid < half ? tid : tid - half;
       const int c = tid < half ? 1 : 2;
-      hpass(planes + dd.plane_off[c], dd.plane_stride[c], in.comp_hpx[c], T + s.off[kHcPos],
+      hpass(win_rows(planes, dd, c), dd.plane_stride[c], dd.win_h[c], dd.win_x[c],
+            T + s.off[kHcPos],
             reinterpret_cast<const int16_t*>(T + s.off[kHcCoef]), s.hc_size, s.hc_taps, cx0, ncc,
             cr0, cr1, c == 1 ? hu : hv, cst, t2, half);
     }
@@ -5820,7 +5840,7 @@ __global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restri
     const HsPlane hp = hs_plane(s, c);
     hbuf_stage(hbuf + dd.hbuf_off + hp.off, hp.w, hp.rows, xs0, ncl, r0, r1, hcol, cst, tid, nt);
   } else if (content) {
-    hpass(planes + dd.plane_off[c], dd.plane_stride[c], in.comp_hpx[c],
+    hpass(win_rows(planes, dd, c), dd.plane_stride[c], dd.win_h[c], dd.win_x[c],
           T + s.off[luma ? kHlPos : kHcPos],
           reinterpret_cast<const int16_t*>(T + s.off[luma ? kHlCoef : kHcCoef]),
           luma ? s.hl_size : s.hc_size, luma ? s.hl_taps : s.hc_taps, xs0, ncl, r0, r1, hcol, cst,

@@ -197,6 +197,32 @@ class FilterBuilder {
   std::vector<int64_t> taps_;
 };
 
+// One axis, memoised per thread (a context is one thread's): initFilter's
+// result depends on these seven numbers alone, and a stream of source crops --
+// one new geometry per image -- repeats its axes long before it repeats a
+// geometry (RandomResizedCrop of 480x640 frames to 224x224: 300,000 sizes,
+// about 1,100 axes).  Bounded: cleared at kAxisMemo entries (~5 KB each at 224
+// outputs).  A filter too long for swscale (false) is not kept.
+int64_t xinc(int src, int dst) { return (((int64_t)src << 16) + (dst >> 1)) / dst; }
+
+constexpr size_t kAxisMemo = 2048;
+bool build_axis(int src, int dst, int align, int one, int kind, int src_pos, int dst_pos,
+                SwsAxis* out) {
+  using Key = std::tuple<int, int, int, int, int, int, int>;
+  thread_local std::map<Key, std::shared_ptr<const SwsAxis>> memo;
+  const Key key{src, dst, align, one, kind, src_pos, dst_pos};
+  auto it = memo.find(key);
+  if (it == memo.end()) {
+    auto a = std::make_shared<SwsAxis>();
+    FilterBuilder fb((int)xinc(src, dst), src, dst, align, one, kind, src_pos, dst_pos);
+    if (!fb.build(a.get())) return false;
+    if (memo.size() >= kAxisMemo) memo.clear();
+    it = memo.emplace(key, std::move(a)).first;
+  }
+  *out = *it->second;
+  return true;
+}
+
 // utils.c get_local_pos: -513 (unset) means centred
 int local_pos(int sub, int pos) {
   if (pos == -1 || pos <= -513) pos = (128 << sub) - 128;
@@ -204,8 +230,6 @@ int local_pos(int sub, int pos) {
 }
 
 int ceil_rshift(int a, int b) { return -((-a) >> b); }
-
-int64_t xinc(int src, int dst) { return (((int64_t)src << 16) + (dst >> 1)) / dst; }
 
 void identity(SwsAxis* a, int n, int one, int shift) {
   a->size = a->eff = 1;
@@ -277,16 +301,14 @@ int sws_plan(int srcW, int srcH, int hsub, int vsub, bool gray, int dstW, int ds
   p->chrDstW = ceil_rshift(dstW, dst_hsub);
   p->chrDstH = dstH;
   const int lp = local_pos(0, 0);
-  if (!FilterBuilder((int)xinc(srcW, dstW), srcW, dstW, 4, 1 << 14, kind, lp, lp).build(&p->hl) ||
-      !FilterBuilder((int)xinc(srcH, dstH), srcH, dstH, 2, 1 << 12, kind, lp, lp).build(&p->vl))
+  if (!build_axis(srcW, dstW, 4, 1 << 14, kind, lp, lp, &p->hl) ||
+      !build_axis(srcH, dstH, 2, 1 << 12, kind, lp, lp, &p->vl))
     return SPDL_HJ_ERR_BAD_GEOMETRY;
   if (!gray) {
-    if (!FilterBuilder((int)xinc(p->chrSrcW, p->chrDstW), p->chrSrcW, p->chrDstW, 4, 1 << 14, kind,
-                       local_pos(p->hsub, -513), local_pos(dst_hsub, -513))
-             .build(&p->hc) ||
-        !FilterBuilder((int)xinc(p->chrSrcH, p->chrDstH), p->chrSrcH, p->chrDstH, 2, 1 << 12, kind,
-                       local_pos(p->vsub, -513), local_pos(0, -513))
-             .build(&p->vc))
+    if (!build_axis(p->chrSrcW, p->chrDstW, 4, 1 << 14, kind, local_pos(p->hsub, -513),
+                    local_pos(dst_hsub, -513), &p->hc) ||
+        !build_axis(p->chrSrcH, p->chrDstH, 2, 1 << 12, kind, local_pos(p->vsub, -513),
+                    local_pos(0, -513), &p->vc))
       return SPDL_HJ_ERR_BAD_GEOMETRY;
   }
   // packed_vscale's choice per output row
@@ -326,17 +348,13 @@ int sws_plan_planar(int srcW, int srcH, int hsub, int vsub, bool gray, int dstW,
   p->chrDstW = ceil_rshift(dstW, p->hsub);
   p->chrDstH = ceil_rshift(dstH, p->vsub);
   const int lp = local_pos(0, 0);
-  if (!FilterBuilder((int)xinc(srcW, dstW), srcW, dstW, 4, 1 << 14, kind, lp, lp).build(&p->hl) ||
-      !FilterBuilder((int)xinc(srcH, dstH), srcH, dstH, 2, 1 << 12, kind, lp, lp).build(&p->vl))
+  if (!build_axis(srcW, dstW, 4, 1 << 14, kind, lp, lp, &p->hl) ||
+      !build_axis(srcH, dstH, 2, 1 << 12, kind, lp, lp, &p->vl))
     return SPDL_HJ_ERR_BAD_GEOMETRY;
   if (!gray) {
     const int hp = local_pos(p->hsub, -513), vp = local_pos(p->vsub, -513);
-    if (!FilterBuilder((int)xinc(p->chrSrcW, p->chrDstW), p->chrSrcW, p->chrDstW, 4, 1 << 14, kind,
-                       hp, hp)
-             .build(&p->hc) ||
-        !FilterBuilder((int)xinc(p->chrSrcH, p->chrDstH), p->chrSrcH, p->chrDstH, 2, 1 << 12, kind,
-                       vp, vp)
-             .build(&p->vc))
+    if (!build_axis(p->chrSrcW, p->chrDstW, 4, 1 << 14, kind, hp, hp, &p->hc) ||
+        !build_axis(p->chrSrcH, p->chrDstH, 2, 1 << 12, kind, vp, vp, &p->vc))
       return SPDL_HJ_ERR_BAD_GEOMETRY;
   }
   // yuv2plane1 ignores its tap (see hj_sws.h)

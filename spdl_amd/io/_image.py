@@ -88,14 +88,27 @@ def _alloc_out(cfg: CUDAConfig, shape, dtype) -> CUDABuffer:
 
 
 def _decode(datas: list, out: Output, cfg: CUDAConfig, shape_per_image, batched: bool,
-            dtype=torch.uint8) -> CUDABuffer:
+            dtype=torch.uint8, crops=None) -> CUDABuffer:
     n = len(datas)
     shape = (n, *shape_per_image) if batched else tuple(shape_per_image)
     buf = _alloc_out(cfg, shape, dtype)
     dec = _lib.thread_decoder(cfg.device_index)
     nbytes = int(np.prod(shape)) * (1 if dtype == torch.uint8 else 2)
-    dec.decode_batch(datas, out, buf.data_ptr(), nbytes, stream=_stream(cfg), sync=True)
+    dec.decode_batch(datas, out, buf.data_ptr(), nbytes, stream=_stream(cfg), sync=True,
+                     crops=crops)
     return buf
+
+
+def _src_size(info, rect) -> tuple[int, int]:
+    """The frame the chain sees: the image, or its source crop ``rect``
+    resolved as the decoder resolves it (``None``: no crop)."""
+    if rect is None:
+        return info.width, info.height
+    rc, r = _lib.crop_rect(info, rect)
+    if rc:
+        raise RuntimeError(f"Failed to decode an image. (invalid source crop {tuple(rect)} of a "
+                           f"{info.width}x{info.height} image)")
+    return r[2], r[3]
 
 
 def _shape(out: Output, w: int, h: int) -> tuple:
@@ -120,11 +133,12 @@ def _frame_format(info) -> tuple[int, int, bool]:
     return hs, vs, False
 
 
-def _yuv_shape(infos: list, out: Output) -> tuple:
+def _yuv_shape(infos: list, out: Output, size=None) -> tuple:
     """Per-image shape of the ``pix_fmt="yuv"`` result of these images (one
-    frame format, one output size), or the reference's error."""
+    frame format, one output size), or the reference's error.  ``size``: the
+    first image's source crop size when it has one."""
     fmts = [_frame_format(i) for i in infos]
-    ow, oh = _lib.output_size(infos[0].width, infos[0].height, out)
+    ow, oh = _lib.output_size(*(size or (infos[0].width, infos[0].height)), out)
     if any(f != fmts[0] for f in fmts):
         raise RuntimeError("The input images must have the same size and pixel format.")
     return _lib.planar_layout(ow, oh, *fmts[0])[0]
@@ -241,6 +255,7 @@ def load_image_batch(
     mean=(0.485, 0.456, 0.406),
     std=(0.229, 0.224, 0.225),
     norm_dtype: str = "float16",
+    crops=None,
     **kwargs,
 ):
     """Batch load images into one ``[B,H,W,3]`` buffer with the FFmpeg filter
@@ -255,7 +270,14 @@ def load_image_batch(
     copied back to a host ``CPUBuffer`` -- into ``storage`` when one is given
     (a :func:`cpu_storage`), like the reference's return type.  ``normalize=True`` fuses the ImageNet
     epilogue ((x/255 - mean)/std in fp32 -> ``norm_dtype`` float16 or
-    bfloat16), an extension for config 4."""
+    bfloat16), an extension for config 4.
+
+    ``crops`` (an extension, like ``normalize``): one source crop ``(x, y, w,
+    h)`` or ``None`` per image, taken from the decoder's frame before the
+    chain -- RandomResizedCrop's per-image rectangles with ``width=224,
+    height=224``; ``x`` or ``y`` of ``None`` is centred.  Exclusive with a
+    positioned ``crop`` node ahead of ``scale`` in ``filter_desc``, which
+    crops every image alike."""
     if not srcs:
         raise ValueError("`srcs` must not be empty.")
     storage = kwargs.pop("storage", None)
@@ -267,6 +289,12 @@ def load_image_batch(
             scale_width=width, scale_height=height, pix_fmt=pix_fmt
         )
     cfg = device_config or _default_config()
+    if crops is not None:
+        crops = list(crops)
+        if len(crops) != len(srcs):
+            raise ValueError(f"{len(crops)} crops for {len(srcs)} images")
+        if filter_desc is None:
+            raise ValueError("crops= needs a filter chain (width / height, filter_desc or pix_fmt)")
     if filter_desc is None:
         # no scale and no output format: the decoder's own planes, batched as
         # the reference's convert_frames stacks them ([B, 3, H, W] yuvj444p,
@@ -295,6 +323,8 @@ def load_image_batch(
         return CPUBuffer(arr)
     # (no format node and pix_fmt=None: the decoder's own planes, scaled)
     out = parse_image_filter(filter_desc, default_pix_fmt=pix_fmt)
+    if crops is not None and out.src_crop is not None:
+        raise ValueError("crops= and a source crop in filter_desc are exclusive")
     if normalize:
         if out.pix_fmt == "yuv":
             raise ValueError("normalize=True needs an RGB pix_fmt; pix_fmt=None keeps the "
@@ -316,22 +346,26 @@ def load_image_batch(
     if not datas:
         raise RuntimeError("Failed to load all the images.")
     info = _lib.get_image_info(datas[0])
-    ow, oh = _lib.output_size(info.width, info.height, out)
+    if crops is not None:
+        crops = [crops[i] for i in keep]
+    src = _src_size(info, crops[0] if crops is not None else out.src_crop)
+    ow, oh = _lib.output_size(*src, out)
     dtype = out.torch_dtype
     if out.pix_fmt == "yuv":
-        shape = _yuv_shape([_lib.get_image_info(d) for d in datas], out)
+        shape = _yuv_shape([_lib.get_image_info(d) for d in datas], out, src)
     else:
         shape = _shape(out, ow, oh)
     try:
-        buf = _decode(datas, out, cfg, shape, True, dtype=dtype)
+        buf = _decode(datas, out, cfg, shape, True, dtype=dtype, crops=crops)
     except RuntimeError:
         if strict:
             raise
         # decode one by one to find the survivors (rare path)
         good = []
-        for d in datas:
+        for k, d in enumerate(datas):
             try:
-                good.append(_decode([d], out, cfg, shape, True, dtype=dtype))
+                good.append(_decode([d], out, cfg, shape, True, dtype=dtype,
+                                    crops=None if crops is None else [crops[k]]))
             except RuntimeError as err:
                 _LG.error("Failed to decode an image: %s", err)
         if not good:
@@ -416,10 +450,11 @@ def load_image(
         filter_desc = get_video_filter_desc(pix_fmt=pix_fmt)
     out = parse_image_filter(filter_desc, default_pix_fmt=pix_fmt)
     info = _lib.get_image_info(data)
+    src = _src_size(info, out.src_crop)
     if out.pix_fmt == "yuv":  # pix_fmt=None, no format node: the frame's planes
-        shape = _yuv_shape([info], out)
+        shape = _yuv_shape([info], out, src)
     else:
-        shape = _shape(out, *_lib.output_size(info.width, info.height, out))
+        shape = _shape(out, *_lib.output_size(*src, out))
     buf = _decode([data], out, cfg, shape, False)
     if device_config is None:
         return _to_host(buf)

@@ -6,7 +6,9 @@
 spec, so callers that pass ``filter_desc=`` strings keep working.  Only the
 filters the image path needs are understood: ``scale`` (w, h, flags,
 force_original_aspect_ratio), ``pad`` (w, h, x=-1, y=-1, color=black),
-``crop`` (w, h, centred) and ``format=pix_fmts=``.  Anything else raises.
+``crop`` (w, h, centred; with x and / or y ahead of ``scale``: a source crop
+of the decoder's frame, integers only) and ``format=pix_fmts=``.  Anything
+else raises.
 """
 
 from __future__ import annotations
@@ -80,7 +82,7 @@ def _kv(args: str) -> dict:
         if "=" in item:
             k, v = item.split("=", 1)
         else:  # positional w:h
-            k, v = ("w", "h", "x", "y")[i], item
+            k, v = ("w", "h", "x", "y", "keep_aspect", "exact")[min(i, 5)], item
         out[k.strip()] = v.strip()
     return out
 
@@ -100,7 +102,7 @@ def parse_image_filter(filter_desc: str | None, default_pix_fmt: str | None = "r
     spec = dict(pix_fmt=default_pix_fmt or "yuv", resize=False)
     if not filter_desc:
         return Output(**spec)
-    have_scale = False
+    have_scale = have_pad = False
     for part in filter_desc.split(","):
         part = part.strip()
         if not part:
@@ -135,6 +137,23 @@ def parse_image_filter(filter_desc: str | None, default_pix_fmt: str | None = "r
             if kv.get("color", "black") != "black":
                 raise ValueError("only color=black is supported")
             spec.update(resize=True, pad_w=_size(kv, "w", part, True), pad_h=_size(kv, "h", part, True))
+            have_pad = True
+        elif name == "crop" and ("x" in kv or "y" in kv) and not have_scale and not have_pad:
+            # a crop with a position ahead of scale / pad: a source crop, taken
+            # from the decoder's frame (include/spdl_hipjpeg.h); a missing x or
+            # y is centred, as in vf_crop
+            if "src_crop" in spec:
+                raise ValueError(f"more than one source crop: {part}")
+            extra = sorted(set(kv) - {"w", "h", "x", "y"})
+            if extra:  # exact=1, keep_aspect, out_w ...
+                raise ValueError(f"crop options not supported in a source crop: {extra}")
+            try:
+                w, h = int(kv["w"]), int(kv["h"])
+                x, y = (int(kv[k]) if k in kv else None for k in ("x", "y"))
+            except (KeyError, ValueError):
+                raise ValueError("a source crop takes integer w, h and x / y (no expressions): "
+                                 f"{part}") from None
+            spec["src_crop"] = (x, y, w, h)
         elif name == "crop":
             if "x" in kv or "y" in kv:
                 raise ValueError("only centred crop is supported")
