@@ -190,6 +190,7 @@ int jo_parse(const uint8_t* d, size_t size, jo_info* info) {
       info->restart_interval = be16(s);
     } else if (m == 0xDA) { /* SOS */
       if (!have_sof) return JO_ERR_BAD_HEADER;
+      if (n < 1) return JO_ERR_BAD_HEADER; /* (Ns itself would lie past the segment) */
       int ns = s[0];
       if (ns < 1 || ns > info->ncomp) return JO_ERR_BAD_HEADER;
       /* progressive, or sequential with non-interleaved scans: the first scan
@@ -222,8 +223,10 @@ int jo_parse(const uint8_t* d, size_t size, jo_info* info) {
       info->vmax = vmax;
       for (int c = 0; c < info->ncomp; c++) {
         if (hmax % info->comp_h[c] || vmax % info->comp_v[c]) return JO_ERR_UNSUPPORTED;
-        if (!info->multiscan && (!qt_have[info->comp_tq[c]] || !dc_have[info->comp_td[c]] ||
-                                 !ac_have[info->comp_ta[c]]))
+        /* the quantiser tables are latched at the first SOS, multi-scan frames
+         * included (their Huffman tables may still come before a later scan) */
+        if (!qt_have[info->comp_tq[c]] ||
+            (!info->multiscan && (!dc_have[info->comp_td[c]] || !ac_have[info->comp_ta[c]])))
           return JO_ERR_BAD_HEADER;
         info->comp_w[c] = (info->width * info->comp_h[c] + hmax - 1) / hmax;
         info->comp_h_px[c] = (info->height * info->comp_v[c] + vmax - 1) / vmax;
@@ -607,6 +610,7 @@ static int ms_decode(const uint8_t* d, size_t size, const jo_info* info, int16_t
   memset(dct, 0, sizeof(dct));
   memset(act, 0, sizeof(act));
   int comp_id[JO_MAX_COMP] = {0};
+  int dc_have[4] = {0}, ac_have[4] = {0};
   int ri = 0, rc = JO_OK, nscan = 0;
   size_t pos = 2;
   for (;;) {
@@ -635,6 +639,7 @@ static int ms_decode(const uint8_t* d, size_t size, const jo_info* info, int16_t
         memset(vals, 0, sizeof(vals));
         memcpy(vals, s + 17, (size_t)total);
         build_huff(bits, vals, tc ? &act[th] : &dct[th]);
+        (tc ? ac_have : dc_have)[th] = 1;
         s += 17 + total;
         n -= 17 + total;
       }
@@ -645,7 +650,7 @@ static int ms_decode(const uint8_t* d, size_t size, const jo_info* info, int16_t
       if (n >= 2) ri = be16(s);
     } else if (m == 0xDA) {
       scan_t sc;
-      sc.ns = s[0];
+      sc.ns = n < 1 ? 0 : s[0]; /* (an empty SOS: Ns would lie past the segment) */
       if (sc.ns < 1 || sc.ns > info->ncomp || n < 1 + 2 * sc.ns + 3) { rc = JO_ERR_BAD_HEADER; break; }
       for (int i = 0; i < sc.ns; i++) {
         int cs = s[1 + 2 * i], c = -1;
@@ -670,6 +675,13 @@ static int ms_decode(const uint8_t* d, size_t size, const jo_info* info, int16_t
         rc = JO_ERR_BAD_HEADER;
         break;
       }
+      /* the tables this kind of scan reads (sequential: both; DC first: DC; AC
+       * scans: AC; DC refinement: none) must have been defined by now */
+      const int need_dc = !info->progressive || (sc.ss == 0 && sc.ah == 0);
+      const int need_ac = !info->progressive || sc.ss > 0;
+      for (int i = 0; i < sc.ns; i++)
+        if ((need_dc && !dc_have[sc.td[i]]) || (need_ac && !ac_have[sc.ta[i]])) rc = JO_ERR_BAD_HEADER;
+      if (rc) break;
       size_t end = pos;
       rc = ms_scan(d, size, pos, info, &sc, ri, dct, act, lev, &end);
       if (rc) break;
@@ -968,6 +980,9 @@ void jo_idct_islow(const int16_t* in_biased, uint8_t* out, int stride) {
   int16_t in[64];
   memcpy(in, in_biased, sizeof(in));
   in[0] = (int16_t)(in[0] - JO_DC_BIAS);
+  /* 32-bit two's complement arithmetic, as the device's: full-range
+   * coefficients overflow it, so the sums and products are unsigned (they
+   * wrap by definition) and become signed only where they are shifted */
   int32_t ws[64];
   for (int c = 0; c < 8; c++) {
     const int16_t* p = in + c;
@@ -976,16 +991,16 @@ void jo_idct_islow(const int16_t* in_biased, uint8_t* out, int stride) {
       for (int r = 0; r < 8; r++) ws[r * 8 + c] = dc;
       continue;
     }
-    int32_t z1, z2, z3, t0, t1, t2, t3, t10, t11, t12, t13;
-    z2 = p[0];
-    z3 = p[32];
+    uint32_t z1, z2, z3, t0, t1, t2, t3, t10, t11, t12, t13;
+    z2 = (uint32_t)p[0];
+    z3 = (uint32_t)p[32];
     z2 *= (1 << CB);
     z3 *= (1 << CB);
     z2 += 1 << (CB - P1 - 1);
     t0 = z2 + z3;
     t1 = z2 - z3;
-    z2 = p[16];
-    z3 = p[48];
+    z2 = (uint32_t)p[16];
+    z3 = (uint32_t)p[48];
     z1 = (z2 + z3) * F0541;
     t2 = z1 + z2 * F0765;
     t3 = z1 - z3 * F1847;
@@ -993,51 +1008,51 @@ void jo_idct_islow(const int16_t* in_biased, uint8_t* out, int stride) {
     t13 = t0 - t2;
     t11 = t1 + t3;
     t12 = t1 - t3;
-    t0 = p[56];
-    t1 = p[40];
-    t2 = p[24];
-    t3 = p[8];
+    t0 = (uint32_t)p[56];
+    t1 = (uint32_t)p[40];
+    t2 = (uint32_t)p[24];
+    t3 = (uint32_t)p[8];
     z2 = t0 + t2;
     z3 = t1 + t3;
     z1 = (z2 + z3) * F1175;
-    z2 = z2 * -F1961;
-    z3 = z3 * -F0390;
+    z2 = z2 * (uint32_t)-F1961;
+    z3 = z3 * (uint32_t)-F0390;
     z2 += z1;
     z3 += z1;
-    z1 = (t0 + t3) * -F0899;
+    z1 = (t0 + t3) * (uint32_t)-F0899;
     t0 = t0 * F0298;
     t3 = t3 * F1501;
     t0 += z1 + z2;
     t3 += z1 + z3;
-    z1 = (t1 + t2) * -F2562;
+    z1 = (t1 + t2) * (uint32_t)-F2562;
     t1 = t1 * F2053;
     t2 = t2 * F3072;
     t1 += z1 + z3;
     t2 += z1 + z2;
-    ws[0 * 8 + c] = (t10 + t3) >> (CB - P1);
-    ws[7 * 8 + c] = (t10 - t3) >> (CB - P1);
-    ws[1 * 8 + c] = (t11 + t2) >> (CB - P1);
-    ws[6 * 8 + c] = (t11 - t2) >> (CB - P1);
-    ws[2 * 8 + c] = (t12 + t1) >> (CB - P1);
-    ws[5 * 8 + c] = (t12 - t1) >> (CB - P1);
-    ws[3 * 8 + c] = (t13 + t0) >> (CB - P1);
-    ws[4 * 8 + c] = (t13 - t0) >> (CB - P1);
+    ws[0 * 8 + c] = (int32_t)(t10 + t3) >> (CB - P1);
+    ws[7 * 8 + c] = (int32_t)(t10 - t3) >> (CB - P1);
+    ws[1 * 8 + c] = (int32_t)(t11 + t2) >> (CB - P1);
+    ws[6 * 8 + c] = (int32_t)(t11 - t2) >> (CB - P1);
+    ws[2 * 8 + c] = (int32_t)(t12 + t1) >> (CB - P1);
+    ws[5 * 8 + c] = (int32_t)(t12 - t1) >> (CB - P1);
+    ws[3 * 8 + c] = (int32_t)(t13 + t0) >> (CB - P1);
+    ws[4 * 8 + c] = (int32_t)(t13 - t0) >> (CB - P1);
   }
   for (int r = 0; r < 8; r++) {
     const int32_t* w = ws + r * 8;
     uint8_t* o = out + r * stride;
-    int32_t z1, z2, z3, t0, t1, t2, t3, t10, t11, t12, t13;
-    z2 = w[0] + ((512 << (P1 + 3)) + (1 << (P1 + 2)));
+    uint32_t z1, z2, z3, t0, t1, t2, t3, t10, t11, t12, t13;
+    z2 = (uint32_t)w[0] + ((512 << (P1 + 3)) + (1 << (P1 + 2)));
     if (!(w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7])) {
-      uint8_t v = islow_limit(z2 >> (P1 + 3));
+      uint8_t v = islow_limit((int32_t)z2 >> (P1 + 3));
       for (int i = 0; i < 8; i++) o[i] = v;
       continue;
     }
-    z3 = w[4];
+    z3 = (uint32_t)w[4];
     t0 = (z2 + z3) * (1 << CB);
     t1 = (z2 - z3) * (1 << CB);
-    z2 = w[2];
-    z3 = w[6];
+    z2 = (uint32_t)w[2];
+    z3 = (uint32_t)w[6];
     z1 = (z2 + z3) * F0541;
     t2 = z1 + z2 * F0765;
     t3 = z1 - z3 * F1847;
@@ -1045,36 +1060,36 @@ void jo_idct_islow(const int16_t* in_biased, uint8_t* out, int stride) {
     t13 = t0 - t2;
     t11 = t1 + t3;
     t12 = t1 - t3;
-    t0 = w[7];
-    t1 = w[5];
-    t2 = w[3];
-    t3 = w[1];
+    t0 = (uint32_t)w[7];
+    t1 = (uint32_t)w[5];
+    t2 = (uint32_t)w[3];
+    t3 = (uint32_t)w[1];
     z2 = t0 + t2;
     z3 = t1 + t3;
     z1 = (z2 + z3) * F1175;
-    z2 = z2 * -F1961;
-    z3 = z3 * -F0390;
+    z2 = z2 * (uint32_t)-F1961;
+    z3 = z3 * (uint32_t)-F0390;
     z2 += z1;
     z3 += z1;
-    z1 = (t0 + t3) * -F0899;
+    z1 = (t0 + t3) * (uint32_t)-F0899;
     t0 = t0 * F0298;
     t3 = t3 * F1501;
     t0 += z1 + z2;
     t3 += z1 + z3;
-    z1 = (t1 + t2) * -F2562;
+    z1 = (t1 + t2) * (uint32_t)-F2562;
     t1 = t1 * F2053;
     t2 = t2 * F3072;
     t1 += z1 + z3;
     t2 += z1 + z2;
     const int sh = CB + P1 + 3;
-    o[0] = islow_limit((t10 + t3) >> sh);
-    o[7] = islow_limit((t10 - t3) >> sh);
-    o[1] = islow_limit((t11 + t2) >> sh);
-    o[6] = islow_limit((t11 - t2) >> sh);
-    o[2] = islow_limit((t12 + t1) >> sh);
-    o[5] = islow_limit((t12 - t1) >> sh);
-    o[3] = islow_limit((t13 + t0) >> sh);
-    o[4] = islow_limit((t13 - t0) >> sh);
+    o[0] = islow_limit((int32_t)(t10 + t3) >> sh);
+    o[7] = islow_limit((int32_t)(t10 - t3) >> sh);
+    o[1] = islow_limit((int32_t)(t11 + t2) >> sh);
+    o[6] = islow_limit((int32_t)(t11 - t2) >> sh);
+    o[2] = islow_limit((int32_t)(t12 + t1) >> sh);
+    o[5] = islow_limit((int32_t)(t12 - t1) >> sh);
+    o[3] = islow_limit((int32_t)(t13 + t0) >> sh);
+    o[4] = islow_limit((int32_t)(t13 - t0) >> sh);
   }
 }
 

@@ -29,6 +29,7 @@
 #include "../../include/spdl_hipjpeg.h"
 #include "hj_common.h"
 #include "hj_launch.h"
+#include "hj_probe.h"
 #include "hj_sws.h"
 #include "hj_sws_tile.h"
 
@@ -248,77 +249,6 @@ void parallel_pack(CopyPool* pool, uint8_t* base, const std::vector<CopyItem>& i
   };
   if (!pool || pool->workers() < 2 || total < (4 << 20)) body(0, 1);
   else pool->run(body);
-}
-
-// Components of the first scan (SOS Ns) after `pos`; 255 when no SOS header
-// follows (the device parse then reports the file).
-int first_scan_components(const uint8_t* d, size_t size, size_t pos) {
-  for (;;) {
-    while (pos < size && d[pos] != 0xFF) pos++;
-    while (pos < size && d[pos] == 0xFF) pos++;
-    if (pos >= size) return 255;
-    const int m = d[pos++];
-    if (m == 0x01 || (m >= 0xD0 && m <= 0xD8)) continue;
-    if (m == 0xD9 || pos + 3 > size) return 255;
-    if (m == 0xDA) return d[pos + 2];
-    pos += (size_t)((d[pos] << 8) | d[pos + 1]);
-  }
-}
-
-// ---- host SOF probe (replaces nvjpegGetImageInfo) --------------------------
-// The SOF fields and the frame's colour model (frame_color: the APP14 Adobe
-// flag seen before the SOF, the component ids).
-int probe(const uint8_t* d, size_t size, spdl_hj_image_info* info) {
-  memset(info, 0, sizeof(*info));
-  if (!d || size < 4 || d[0] != 0xFF || d[1] != 0xD8) return SPDL_HJ_ERR_NOT_JPEG;
-  size_t pos = 2;
-  int adobe = -1;
-  for (;;) {
-    while (pos < size && d[pos] != 0xFF) pos++;
-    while (pos < size && d[pos] == 0xFF) pos++;
-    if (pos >= size) return SPDL_HJ_ERR_BAD_HEADER;
-    int m = d[pos++];
-    if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
-    if (m == 0xD9 || m == 0xDA) return SPDL_HJ_ERR_BAD_HEADER;  // no SOF before the scan
-    if (pos + 2 > size) return SPDL_HJ_ERR_BAD_HEADER;
-    int len = (d[pos] << 8) | d[pos + 1];
-    if (len < 2 || pos + (size_t)len > size) return SPDL_HJ_ERR_BAD_HEADER;
-    const uint8_t* s = d + pos + 2;
-    pos += (size_t)len;
-    if (m == 0xEE) {
-      if (len >= 14 && memcmp(s, "Adobe", 5) == 0) adobe = s[11];
-      continue;
-    }
-    if (m == 0xC0 || m == 0xC1 || m == 0xC2) {  // sequential or progressive Huffman
-      if (len < 8) return SPDL_HJ_ERR_BAD_HEADER;
-      if (s[0] != 8) return SPDL_HJ_ERR_UNSUPPORTED;
-      info->height = (s[1] << 8) | s[2];
-      info->width = (s[3] << 8) | s[4];
-      info->ncomp = s[5];
-      if (info->height == 0) return SPDL_HJ_ERR_UNSUPPORTED;
-      if (info->width == 0) return SPDL_HJ_ERR_BAD_HEADER;
-      if (info->ncomp != 1 && info->ncomp != 3 && info->ncomp != 4) return SPDL_HJ_ERR_UNSUPPORTED;
-      if (len < 8 + 3 * info->ncomp) return SPDL_HJ_ERR_BAD_HEADER;
-      int ids[kMaxComp] = {};
-      for (int c = 0; c < info->ncomp; c++) {
-        ids[c] = s[6 + 3 * c];
-        info->h_samp[c] = s[7 + 3 * c] >> 4;
-        info->v_samp[c] = s[7 + 3 * c] & 15;
-        if (info->h_samp[c] < 1 || info->h_samp[c] > 4 || info->v_samp[c] < 1 ||
-            info->v_samp[c] > 4)
-          return SPDL_HJ_ERR_BAD_HEADER;
-      }
-      if (!frame_color(info->ncomp, info->h_samp, info->v_samp, ids, adobe, &info->color))
-        return SPDL_HJ_ERR_UNSUPPORTED;
-      // the scan structure: progressive, or a first scan with fewer
-      // components than the frame (the multi-scan path decodes both)
-      info->multiscan = m == 0xC2 || first_scan_components(d, size, pos) < info->ncomp;
-      return SPDL_HJ_OK;
-    }
-    if (m == 0xC3 || (m >= 0xC5 && m <= 0xC7) || (m >= 0xC9 && m <= 0xCB) ||
-        (m >= 0xCD && m <= 0xCF))
-      return SPDL_HJ_ERR_UNSUPPORTED;  // lossless, hierarchical, arithmetic
-  }
 }
 
 // ---- geometry (FFmpeg scale/pad/crop semantics; see oracle jo_geometry) ----

@@ -185,6 +185,7 @@ __device__ static int parse_headers(const Bytes& d, int size, ParseScratch& s) {
       in.ri = be16(p);
     } else if (m == 0xDA) {
       if (!have_sof) return kErrBadHeader;
+      if (n < 1) return kErrBadHeader;  // (Ns itself would lie past the segment)
       int ns = p[0];
       if (ns < 1 || ns > in.ncomp) return kErrBadHeader;
       // progressive, or sequential with non-interleaved scans: multiscan_kernel
@@ -4141,7 +4142,7 @@ __global__ void __launch_bounds__(256) multiscan_kernel(const uint8_t* __restric
           break;
         }
         MsScan& sc = S.scan[ns];
-        sc.ns = d[p];
+        sc.ns = p < seg_end ? d[p] : 0;  // (an empty SOS: Ns would lie past the segment)
         if (sc.ns < 1 || sc.ns > in.ncomp || p + 1 + 2 * sc.ns + 3 > seg_end) {
           err = kErrBadHeader;
           break;
