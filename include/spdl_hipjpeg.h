@@ -238,6 +238,81 @@ int spdl_hj_crop_rect(const spdl_hj_image_info* info, const spdl_hj_rect* in, sp
  * spdl_hj_decode_planes and spdl_hj_debug_entropy neither use nor clear them. */
 int spdl_hj_set_crops(spdl_hj_ctx* ctx, const spdl_hj_rect* rects, int32_t n);
 
+/* ---- views (additive in ABI 7: one function, two types, one read-only
+ * parameter; a binding finds them by symbol) ---------------------------------
+ * Several outputs of one image from one decode: multi-crop augmentation (two
+ * crops at 224 and six at 96 of every file), a thumbnail beside a training
+ * crop.  A view is a rectangle of one image of the batch; a group is a list of
+ * views that share one output chain and one output buffer.  A views submission
+ * parses, destuffs and Huffman-decodes every image once, inverse-transforms
+ * the bounding MCU rectangle of all of the image's views once
+ * ("idct_workgroups"), and runs the output stage once per group.
+ *
+ * Consumption.  The next spdl_hj_decode_batch, _device or _staged call on
+ * `ctx` consumes the views, whether or not it succeeds (the rule of
+ * spdl_hj_set_crops).  groups == NULL or ngroups == 0 clears them.  The
+ * library copies the groups and their view arrays at spdl_hj_set_views; a
+ * group's out_dev and status must stay valid until the batch has been waited
+ * for.  spdl_hj_decode_planes and spdl_hj_debug_entropy neither use nor clear
+ * them.
+ *
+ * Limits.  ngroups is 1..4 and nviews at least 1 in every group; every `image`
+ * lies in [0, n) of the consuming call.  If a limit is broken -- here or
+ * below -- the consuming call returns SPDL_HJ_ERR_INVALID_ARG and writes
+ * nothing (spdl_hj_set_views itself fails only for a NULL ctx or a negative
+ * ngroups).
+ *
+ * Rectangles.  A view's `rect` follows the source-crop rules exactly:
+ * (0, 0, 0, 0) is the whole frame, SPDL_HJ_CROP_CENTER is accepted, sizes and
+ * origins round to the chroma grid, and spdl_hj_crop_rect resolves it.  From
+ * there on the view is a frame of its own: its own geometry, its own plan, one
+ * swscale context per view.
+ *
+ * Output layout.  Group g's output is [nviews, ...] in view order in its
+ * out_dev (out_bytes long); the layout and the per-view size come from its
+ * `out` as they do for a batch.  All views of a group must produce one size
+ * (with resize == 0: resolve to one size), else SPDL_HJ_ERR_INVALID_ARG, as for
+ * crops.  An image may have any number of views in any group, none included
+ * (it is then entropy-decoded and no more); views may name images in any
+ * order and one image more than once.
+ *
+ * The consuming call's own arguments.  `out` must be a valid spec with csc =
+ * SWSCALE; only its idct field is used, and every group's out.idct must equal
+ * it.  out_dev must be NULL and out_bytes 0.  Views and spdl_hj_set_crops on
+ * one submission give SPDL_HJ_ERR_INVALID_ARG.
+ *
+ * Per group.  out.pix_fmt is one of the four RGB / BGR formats, dtype any of
+ * the three, csc SWSCALE.  SPDL_HJ_FMT_YUV or csc = JFIF in a group gives
+ * SPDL_HJ_ERR_INVALID_ARG (planar-YUV views: not yet).
+ *
+ * Statuses.  A view the host refuses alone -- a rectangle that does not
+ * resolve, a chain its size cannot take (SPDL_HJ_ERR_BAD_GEOMETRY) -- has
+ * that status in its group's status[k] (optional, host, nviews ints; 0 for
+ * the others) before the consuming call returns.  Its bytes stay untouched;
+ * the other views and images decode.  An image's decode status arrives as for
+ * any batch: the call's status[n], or spdl_hj_wait.  A view is valid when its
+ * own status and its image's are both 0; the views of a failed image are left
+ * untouched.  With sync != 0 the call fails if any image failed or any view
+ * was refused, as the crop path fails for a refused image.
+ *
+ * Large files.  A views submission decodes every image in ONE entropy
+ * workgroup, as "entropy_piece_bytes" 0 does: no piece hand-off exists that
+ * could give up, and no image is re-decoded (multi-piece decode under views:
+ * not yet). */
+typedef struct {
+  int32_t image;     /* index into the consuming call's batch */
+  spdl_hj_rect rect; /* source-crop rules; (0, 0, 0, 0): the whole frame */
+} spdl_hj_view;
+typedef struct {
+  spdl_hj_output out; /* the chain of every view of this group */
+  void* out_dev;      /* device memory, [nviews, ...] in view order */
+  size_t out_bytes;
+  const spdl_hj_view* views;
+  int32_t nviews;
+  int32_t* status;    /* optional, host, nviews */
+} spdl_hj_view_group;
+int spdl_hj_set_views(spdl_hj_ctx* ctx, const spdl_hj_view_group* groups, int32_t ngroups);
+
 /* ABI version of the loaded library (== SPDL_HJ_ABI_VERSION). */
 int spdl_hj_abi_version(void);
 
@@ -482,7 +557,10 @@ const char* spdl_hj_stage_name(int32_t i);
  * multi-scan side stream per lane when the hardware queues allow, the copy
  * stream); "idct_workgroups" (with the source crop), the IDCT workgroups the last submission
  * launched (0 when the fused full-resolution kernel ran instead): a source
- * crop's region-only IDCT shows here.
+ * crop's region-only IDCT shows here; "entropy_workgroups" (with views), the
+ * entropy work items of the last submission (one per image, or per piece of
+ * a multi-piece image): with "idct_workgroups" it shows that a views
+ * submission ran the front end once per image.
  * Builds with -DHJ_ABLATIONS=1 also take "debug_mask" (timing ablations that
  * skip kernel phases; outputs wrong); release builds reject it. */
 int spdl_hj_set_param(spdl_hj_ctx* ctx, const char* name, int64_t value);

@@ -55,6 +55,7 @@ EXPORTED = (
     "spdl_hj_copy",
     "spdl_hj_crop_rect",
     "spdl_hj_set_crops",
+    "spdl_hj_set_views",
 )
 
 
@@ -86,6 +87,19 @@ def _rect(r) -> Rect:
     x, y, w, h = r
     return Rect(CROP_CENTER if x is None else int(x), CROP_CENTER if y is None else int(y),
                 int(w), int(h))
+
+
+def _view_rect(r) -> Rect:
+    """A view's rectangle: as :func:`_rect`, and checked -- four numbers."""
+    if r is None:
+        return Rect(0, 0, 0, 0)
+    try:
+        ok = len(r) == 4
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"a view's rect is (x, y, w, h) or None, not {r!r}")
+    return _rect(r)
 
 
 class OutputSpec(ctypes.Structure):
@@ -205,6 +219,65 @@ def planar_layout(ow: int, oh: int, hs: int, vs: int, gray: bool) -> tuple[tuple
     return (1, 2 * oh if vs == 1 else oh + oh // 2, ow), nbytes
 
 
+class View(ctypes.Structure):  # spdl_hj_view
+    _fields_ = [("image", ctypes.c_int32), ("rect", Rect)]
+
+
+class ViewGroupSpec(ctypes.Structure):  # spdl_hj_view_group
+    _fields_ = [("out", OutputSpec), ("out_dev", ctypes.c_void_p), ("out_bytes", ctypes.c_size_t),
+                ("views", ctypes.POINTER(View)), ("nviews", ctypes.c_int32),
+                ("status", ctypes.POINTER(ctypes.c_int32))]
+
+
+class ViewGroup:
+    """One group of a views submission (include/spdl_hipjpeg.h "views"): the
+    output chain ``out``, the views ``[(image, rect_or_None), ...]`` and the
+    device buffer ``[len(views), ...]`` they are written to in view order.
+    After the consuming call, ``statuses`` holds the per-view codes (0, or the
+    status of a view the host refused alone); a view is valid when its own
+    status and its image's are both 0."""
+
+    def __init__(self, out: Output, views, out_ptr: int, out_bytes: int):
+        if not isinstance(out, Output):
+            raise ValueError("ViewGroup(out=...) takes an Output")
+        if out.src_crop is not None:
+            raise ValueError("views= and Output.src_crop are exclusive")
+        self.out, self.out_ptr, self.out_bytes = out, int(out_ptr), int(out_bytes)
+        self.views = []
+        for v in views:
+            try:
+                image, rect = v
+            except (TypeError, ValueError):
+                raise ValueError(f"a view is (image, rect_or_None), not {v!r}") from None
+            if isinstance(image, bool) or not isinstance(image, int):
+                raise ValueError(f"a view is (image, rect_or_None), not {v!r}")
+            self.views.append((image, _view_rect(rect)))
+        n = len(self.views)
+        self._views = (View * max(n, 1))(*[View(i, r) for i, r in self.views])
+        self._status = (ctypes.c_int32 * max(n, 1))()
+
+    @property
+    def statuses(self) -> list[int]:
+        return list(self._status)[: len(self.views)]
+
+    def to_c(self) -> ViewGroupSpec:
+        return ViewGroupSpec(self.out.to_c(), self.out_ptr, self.out_bytes, self._views,
+                             len(self.views), self._status)
+
+
+def _check_views(views, out: Output, crops, out_ptr, out_bytes) -> None:
+    """What a views submission refuses before any library call."""
+    if crops is not None:
+        raise ValueError("views= and crops= are exclusive")
+    if out.src_crop is not None:
+        raise ValueError("views= and Output.src_crop are exclusive")
+    if isinstance(views, ViewGroup) or not all(isinstance(g, ViewGroup) for g in views):
+        raise ValueError("views= takes a sequence of ViewGroup")
+    if out_ptr or out_bytes:
+        raise ValueError("with views= the call's out_ptr and out_bytes must be 0: "
+                         "every group has its own buffer")
+
+
 _LIB = None
 _LIB_LOCK = threading.Lock()
 
@@ -274,6 +347,8 @@ def lib() -> ctypes.CDLL:
                 ctypes.POINTER(ImageInfo), ctypes.POINTER(Rect), ctypes.POINTER(Rect)
             ]
             L.spdl_hj_set_crops.argtypes = [vp, vp, i32]
+        if hasattr(L, "spdl_hj_set_views"):  # (additive in ABI 7 as well)
+            L.spdl_hj_set_views.argtypes = [vp, ctypes.POINTER(ViewGroupSpec), i32]
         ver = L.spdl_hj_abi_version()
         # (an explicitly chosen older build, ABI >= 5, loads for A/B runs)
         if ver != ABI_VERSION and not (os.environ.get("SPDL_AMD_LIB") and 5 <= ver < ABI_VERSION):
@@ -417,6 +492,11 @@ def tar_index(src, start: int = 0, max_entries: int = 1 << 20, with_names: bool 
     return out, pos
 
 
+def _refused(views, rc: int) -> bool:
+    """The call failed (``rc``) because the host refused a view alone."""
+    return views is not None and any(rc == st for g in views for st in g.statuses if st)
+
+
 def _stream_handle(stream) -> int | None:
     if stream is None:
         return None
@@ -495,6 +575,19 @@ class Decoder:
         if lib().spdl_hj_set_crops(self._h, arr if crops else None, len(crops) if n is None else n):
             raise ValueError("invalid source crops")
 
+    def set_views(self, groups) -> None:
+        """The views of the next batch submission (spdl_hj_set_views): a
+        sequence of :class:`ViewGroup`; ``None`` or an empty one clears them.
+        The groups must stay alive until the batch has been waited for (their
+        status arrays are written by the consuming call)."""
+        groups = list(groups) if groups is not None else []
+        if not all(isinstance(g, ViewGroup) for g in groups):
+            raise ValueError("set_views takes a sequence of ViewGroup")
+        arr = (ViewGroupSpec * max(len(groups), 1))(*[g.to_c() for g in groups])
+        self._held_views = groups  # (the library copied the view arrays; the statuses are ours)
+        if lib().spdl_hj_set_views(self._h, arr if groups else None, len(groups)):
+            raise ValueError("invalid views")
+
     def _crops(self, out: Output, crops, n: int) -> None:
         """Hand the submission's rectangles to the context: ``crops`` per
         image, or ``out.src_crop`` for every image."""
@@ -508,14 +601,23 @@ class Decoder:
             self.set_crops(crops)
 
     def decode_batch(self, datas, out: Output, out_ptr: int, out_bytes: int, stream=None,
-                     sync: bool = True, check: bool = True, crops=None) -> list[int]:
+                     sync: bool = True, check: bool = True, crops=None, views=None) -> list[int]:
         """Per-image statuses.  A failed image raises RuntimeError unless
         ``check`` is False (synchronous calls), which returns the statuses.
-        ``crops``: a source crop ``(x, y, w, h)`` or ``None`` per image."""
+        ``crops``: a source crop ``(x, y, w, h)`` or ``None`` per image.
+        ``views``: a sequence of :class:`ViewGroup` -- several outputs per
+        image from one decode; ``out_ptr`` and ``out_bytes`` must then be 0 and
+        of ``out`` only ``idct`` is used.  The per-view statuses are each
+        group's ``statuses``; with ``check=False`` a refused view does not
+        raise either."""
         n = len(datas)
         if n == 0:
             raise RuntimeError("Failed to decode an image. (the batch is empty)")
-        self._crops(out, crops, n)
+        if views is not None:
+            _check_views(views, out, crops, out_ptr, out_bytes)
+            self.set_views(views)
+        else:
+            self._crops(out, crops, n)
         # borrowed for the duration of the call, no copy (the reference binds
         # memoryviews as string_views, src/spdl/io/lib/cuda/memoryview_utils.h:17-20)
         keep = []
@@ -533,20 +635,24 @@ class Decoder:
             self._h, ptrs, sizes, n, ctypes.byref(spec), out_ptr, out_bytes,
             _stream_handle(stream), int(bool(sync)), status, err, 1024,
         )
-        if rc and not (not check and sync and any(status)):
+        if rc and not (not check and sync and (any(status) or _refused(views, rc))):
             raise RuntimeError(err.value.decode() or f"Failed to decode an image. ({rc})")
         return list(status)
 
     def decode_batch_device(self, dev_ptr: int, dev_bytes: int, offsets, sizes, infos,
                             out: Output, out_ptr: int, out_bytes: int, stream=None,
-                            sync: bool = True, crops=None, check: bool = True) -> list[int]:
+                            sync: bool = True, crops=None, check: bool = True,
+                            views=None) -> list[int]:
         """``offsets``/``sizes``: sequences or int64 numpy arrays; ``infos``: a
         sequence of ImageInfo or a prebuilt ``(ImageInfo * n)`` array (pass the
         same objects again to skip re-marshalling on every call)."""
         import numpy as np
 
         n = len(offsets)
-        if crops is not None or out.src_crop is not None:
+        if views is not None:
+            _check_views(views, out, crops, out_ptr, out_bytes)
+            self.set_views(views)
+        elif crops is not None or out.src_crop is not None:
             self._crops(out, crops, n)
         offs = np.ascontiguousarray(offsets, dtype=np.int64)
         szs = np.ascontiguousarray(sizes, dtype=np.int64)
@@ -559,7 +665,7 @@ class Decoder:
             ctypes.byref(spec), out_ptr, out_bytes, _stream_handle(stream), int(bool(sync)),
             status.ctypes.data, err, 1024,
         )
-        if rc and not (not check and sync and status.any()):
+        if rc and not (not check and sync and (status.any() or _refused(views, rc))):
             raise RuntimeError(err.value.decode() or f"Failed to decode an image. ({rc})")
         return status.tolist()
 
@@ -620,9 +726,13 @@ class Decoder:
 
     def decode_staged(self, ticket: int, nbytes: int, offsets, sizes, out: Output, out_ptr: int,
                       out_bytes: int, stream=None, sync: bool = True, crops=None,
-                      check: bool = True) -> list[int]:
+                      check: bool = True, views=None) -> list[int]:
         n = len(offsets)
-        self._crops(out, crops, n)
+        if views is not None:
+            _check_views(views, out, crops, out_ptr, out_bytes)
+            self.set_views(views)
+        else:
+            self._crops(out, crops, n)
         offs = (ctypes.c_int64 * n)(*offsets)
         szs = (ctypes.c_int64 * n)(*sizes)
         status = (ctypes.c_int32 * max(n, 1))()
@@ -631,7 +741,7 @@ class Decoder:
         rc = lib().spdl_hj_decode_staged(
             self._h, int(ticket), int(nbytes), offs, szs, n, ctypes.byref(spec), out_ptr,
             out_bytes, _stream_handle(stream), int(bool(sync)), status, err, 1024)
-        if rc and not (not check and sync and any(status)):
+        if rc and not (not check and sync and (any(status) or _refused(views, rc))):
             raise RuntimeError(err.value.decode() or f"Failed to decode an image. ({rc})")
         return list(status)[:n]
 

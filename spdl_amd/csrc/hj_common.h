@@ -223,7 +223,15 @@ struct ImageDesc {      // host-filled per image
   // rows [win_y, win_y + win_h) from column win_x on and nothing else -- plane
   // bytes outside the crop's MCU rectangle are stale.
   int32_t win_x[kMaxComp], win_y[kMaxComp], win_w[kMaxComp], win_h[kMaxComp];
-  int32_t pad_;
+  // The image this descriptor's output is made of: its own index, except in a
+  // views submission (spdl_hj_set_views, hj_views.h).  There the n image
+  // descriptors serve the front end and the IDCT (their region: the bounding
+  // MCU rectangle of the image's views), and behind them every view has a
+  // descriptor for the output kernels alone -- its own window, placement, plan
+  // and tiles, plane_off / plane_stride copied from image `src`, whose
+  // ImageInfo::status those kernels read.  A refused view (`refuse`) has one
+  // output workgroup that does nothing; its image's status stays clean.
+  int32_t src;
 };
 
 // sws_kernel LDS budget per workgroup (bytes) for what hj_sws_tile.h

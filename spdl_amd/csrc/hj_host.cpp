@@ -32,6 +32,7 @@
 #include "hj_probe.h"
 #include "hj_sws.h"
 #include "hj_sws_tile.h"
+#include "hj_views.h"
 
 using namespace hj;
 
@@ -318,56 +319,30 @@ int geometry(int w, int h, const spdl_hj_output* o, Geom* g, int hs = 1, int vs 
   return SPDL_HJ_OK;
 }
 
-// chroma subsampling shifts of the yuvj4xxp frame FFmpeg's mjpeg decoder
-// makes of this sampling (444 / 422 / 420 / 440 / 411 ...); others are not
-// a swscale input format here
-int chroma_shifts(const spdl_hj_image_info& p, int* hs, int* vs) {
-  *hs = *vs = 0;
-  if (p.ncomp != 3) return SPDL_HJ_OK;  // gray, or 4 components all 1x1 (probe)
-  const int hmax = std::max(p.h_samp[0], std::max(p.h_samp[1], p.h_samp[2]));
-  const int vmax = std::max(p.v_samp[0], std::max(p.v_samp[1], p.v_samp[2]));
-  if (p.h_samp[0] != hmax || p.v_samp[0] != vmax || p.h_samp[1] != p.h_samp[2] ||
-      p.v_samp[1] != p.v_samp[2] || hmax % p.h_samp[1] || vmax % p.v_samp[1])
-    return SPDL_HJ_ERR_UNSUPPORTED;
-  const int rh = hmax / p.h_samp[1], rv = vmax / p.v_samp[1];
-  if ((rh & (rh - 1)) || (rv & (rv - 1))) return SPDL_HJ_ERR_UNSUPPORTED;
-  while ((1 << *hs) < rh) (*hs)++;
-  while ((1 << *vs) < rv) (*vs)++;
-  return SPDL_HJ_OK;
+// The rectangle rules (chroma shifts, the source crop's rounding) are pure
+// arithmetic shared with views: hj_views.h.
+views::Frame frame_of(const spdl_hj_image_info& p) {
+  views::Frame f{p.width, p.height, p.ncomp, {}, {}};
+  for (int c = 0; c < kMaxComp; c++) {
+    f.h_samp[c] = p.h_samp[c];
+    f.v_samp[c] = p.v_samp[c];
+  }
+  return f;
 }
 
-// ---- source crop (spdl_hipjpeg.h: libavfilter's crop, exact=0, on the
-// decoder's frame) -----------------------------------------------------------
-// One axis: the size rounded down to the chroma ratio, the origin clamped into
-// the frame and then rounded down likewise.  A centred origin with an
-// off-grid size is refused (vf_crop's order of rounding and centring there is
-// not pinned).
-int crop_axis(int64_t pos, int64_t size, int64_t full, int ratio, int32_t* opos, int32_t* osize) {
-  const int64_t s = size / ratio * ratio;
-  if (size <= 0 || s <= 0 || s > full) return SPDL_HJ_ERR_BAD_GEOMETRY;
-  if (pos == SPDL_HJ_CROP_CENTER) {
-    if (size % ratio) return SPDL_HJ_ERR_BAD_GEOMETRY;
-    pos = (full - s) / 2;
-  }
-  if (pos < 0) pos = 0;
-  if (pos + s > full) pos = full - s;
-  *opos = (int32_t)(pos / ratio * ratio);
-  *osize = (int32_t)s;
-  return SPDL_HJ_OK;
+int chroma_shifts(const spdl_hj_image_info& p, int* hs, int* vs) {
+  return views::chroma_shifts(frame_of(p), hs, vs);
 }
 
 bool rect_is_none(const spdl_hj_rect& r) { return !(r.x | r.y | r.w | r.h); }
 
+// ---- source crop (spdl_hipjpeg.h: libavfilter's crop, exact=0, on the
+// decoder's frame) -----------------------------------------------------------
 int crop_resolve(const spdl_hj_image_info& p, const spdl_hj_rect& in, spdl_hj_rect* out) {
-  if (p.width <= 0 || p.height <= 0) return SPDL_HJ_ERR_INVALID_ARG;
-  if (rect_is_none(in)) {
-    *out = {0, 0, p.width, p.height};
-    return SPDL_HJ_OK;
-  }
-  int hsub, vsub;
-  if (int rc = chroma_shifts(p, &hsub, &vsub)) return rc;
-  if (int rc = crop_axis(in.x, in.w, p.width, 1 << hsub, &out->x, &out->w)) return rc;
-  return crop_axis(in.y, in.h, p.height, 1 << vsub, &out->y, &out->h);
+  views::Rect r;
+  const int rc = views::resolve(frame_of(p), views::Rect{in.x, in.y, in.w, in.h}, &r);
+  if (!rc) *out = {r.x, r.y, r.w, r.h};
+  return rc;
 }
 
 struct Layout {
@@ -407,13 +382,66 @@ struct Layout {
   // images decoded by several entropy workgroups (hand-offs): their probes,
   // for a one-workgroup re-decode should a hand-off give up
   std::vector<std::pair<int, spdl_hj_image_info>> multi;
+  // A views submission (spdl_hj_set_views): desc holds the n image
+  // descriptors, then every group's view descriptors (views::group_slices);
+  // the output stage runs once per group over its slice.  Empty otherwise.
+  struct Group {
+    spdl_hj_output out;
+    void* out_dev = nullptr;
+    int first = 0, count = 0;        // its view descriptors in desc
+    int sws_wg0 = 0, sws_wgs = 0;    // its tiles in the flat sws grid (sws_map)
+    int sws_lds = 0;
+    int ow = 0, oh = 0;              // every view's output size
+  };
+  std::vector<Group> groups;
+  int view_refused = 0;  // the first status the host gave a view alone (0: none)
+  int view_refused_group = 0, view_refused_index = 0;
+};
+
+// What spdl_hj_set_views left for the next submission: the groups, their view
+// arrays copied.  `bad`: the call's own arguments broke a limit (more groups
+// than views::kMaxGroups, a group without views) -- the consuming call says so.
+struct HeldViews {
+  struct Group {
+    spdl_hj_output out;
+    void* out_dev;
+    size_t out_bytes;
+    std::vector<spdl_hj_view> views;
+    int32_t* status;
+  };
+  std::vector<Group> groups;
+  bool bad = false;
+  bool any() const { return bad || !groups.empty(); }
 };
 
 int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_image_info* infos,
                  int n, const spdl_hj_output* out, int sub_bits, int64_t piece_bytes, Layout& L,
                  int32_t* status, char* err, size_t errlen, PlanCache* plans,
-                 const spdl_hj_rect* crops = nullptr) {
+                 const spdl_hj_rect* crops = nullptr, const HeldViews* hv = nullptr) {
   L.desc.assign(n, ImageDesc{});
+  // Views (validated by take_views): each one's rectangle, resolved with its
+  // image below; `vorder` lists them by image (image i's: [vstart[i], vstart[i + 1]))
+  struct ViewRes {
+    views::Rect in, r;
+    int rc;
+  };
+  std::vector<ViewRes> vres;
+  std::vector<int> vstart, vorder;
+  if (hv) {
+    vstart.assign(n + 1, 0);
+    for (const auto& g : hv->groups)
+      for (const spdl_hj_view& v : g.views) {
+        vstart[v.image + 1]++;
+        vres.push_back({{v.rect.x, v.rect.y, v.rect.w, v.rect.h}, {}, 0});
+      }
+    for (int i = 0; i < n; i++) vstart[i + 1] += vstart[i];
+    vorder.resize(vres.size());
+    std::vector<int> fill(vstart.begin(), vstart.end() - 1);
+    int q = 0;
+    for (const auto& g : hv->groups)
+      for (const spdl_hj_view& v : g.views) vorder[fill[v.image]++] = q++;
+    L.desc.reserve(n + vres.size());
+  }
   const bool yuv = out->pix_fmt == SPDL_HJ_FMT_YUV;
   bool have_size = false;  // L.ow x L.oh is set (by the first image that is not refused)
   bool have_fmt = false;   // ... and the planar output's frame format
@@ -491,7 +519,32 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
     if (crop_rc && crop_rc != SPDL_HJ_ERR_BAD_GEOMETRY) return fail(i, crop_rc, nullptr);
     if (crop_rc) src = {0, 0, p.width, p.height};
     d.idct_blocks = d.nblocks;
-    if (has_rect && !crop_rc) {
+    d.src = i;
+    if (hv) {
+      // idct_kernel visits the bounding MCU rectangle of the image's views over
+      // all groups (the whole grid if one of them is the whole frame; no view:
+      // no block).  A rectangle that does not resolve refuses its view alone.
+      const views::Frame f = frame_of(p);
+      const views::Grid grid{hmax, vmax, 0, 0, bpm};
+      views::McuRect bound{0, 0, 0, 0};
+      bool whole = false;
+      for (int q = vstart[i]; q < vstart[i + 1]; q++) {
+        ViewRes& vr = vres[vorder[q]];
+        vr.rc = views::resolve(f, vr.in, &vr.r);
+        if (vr.rc && vr.rc != SPDL_HJ_ERR_BAD_GEOMETRY) return fail(i, vr.rc, nullptr);
+        if (vr.rc) continue;
+        whole = whole || views::rect_is_none(vr.in);
+        views::mcu_union(&bound, views::mcu_rect(grid, vr.r));
+      }
+      if (!whole) {
+        d.idct_blocks = views::idct_blocks(grid, bound);
+        d.reg_mx0 = bound.mx0;
+        d.reg_my0 = bound.my0;
+        d.reg_mw = bound.mw;
+        d.reg_mh = bound.mh;
+        d.reg_mw_magic = idct_div_magic((uint32_t)std::max(bound.mw, 1));
+      }
+    } else if (has_rect && !crop_rc) {
       // idct_kernel visits the MCUs the crop touches (gray: its blocks)
       const int mw8 = 8 * hmax, mh8 = 8 * vmax;
       d.reg_mx0 = src.x / mw8;
@@ -542,6 +595,7 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
     d.rec_cap = (int64_t)kMaxSlots * 8 * pieces;
     d.rec_off = L.total_recs;
     L.total_recs += d.rec_cap;
+    if (hv) continue;  // (the outputs are the views': their descriptors follow below)
     if (has_rect) L.all_special = false;  // the full-resolution converters read whole planes
     if (crop_rc) {
       refuse(d, crop_rc);
@@ -640,6 +694,132 @@ int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_ima
     d.sws_chunks = plan->chunks;
     L.sws_wgs += (int64_t)plan->bands * plan->chunks;
     L.sws_lds = std::max(L.sws_lds, plan->lds);
+  }
+  if (hv) {
+    // The view descriptors, group by group behind the images': each view a
+    // frame of its own (its window of image `src`'s planes, its geometry, its
+    // plan), tiled in its group's part of the flat sws grid.
+    L.all_special = L.fuse_ok = false;  // (the full-resolution converters read whole planes)
+    std::vector<int32_t> vstatus(vres.size(), SPDL_HJ_OK);
+    int32_t nviews[views::kMaxGroups];
+    views::Slice slice[views::kMaxGroups];
+    for (size_t gi = 0; gi < hv->groups.size(); gi++) nviews[gi] = (int32_t)hv->groups[gi].views.size();
+    views::group_slices(n, nviews, (int)hv->groups.size(), slice);
+    size_t q = 0;
+    for (size_t gi = 0; gi < hv->groups.size(); gi++) {
+      const HeldViews::Group& hg = hv->groups[gi];
+      Layout::Group G;
+      G.out = hg.out;
+      G.out_dev = hg.out_dev;
+      G.first = slice[gi].first;  // (== L.desc.size(): the descriptors are appended in this order)
+      G.count = slice[gi].count;
+      G.sws_wg0 = (int)L.sws_wgs;
+      bool sized = false;
+      for (size_t k = 0; k < hg.views.size(); k++, q++) {
+        const ViewRes& vr = vres[q];
+        const int img = hg.views[k].image;
+        const spdl_hj_image_info& p = infos[img];
+        ImageDesc v = L.desc[img];
+        v.src = img;
+        v.idct_blocks = 0;  // (the front-end and IDCT fields mean nothing here)
+        auto refuse_view = [&](int why) {
+          vstatus[q] = why;
+          if (!L.view_refused) {
+            L.view_refused = why;
+            L.view_refused_group = (int)gi;
+            L.view_refused_index = (int)k;
+          }
+          refuse(v, why);
+          L.desc.push_back(v);
+        };
+        if (vr.rc) {
+          refuse_view(vr.rc);
+          continue;
+        }
+        const views::Frame f = frame_of(p);
+        const views::Grid grid = views::grid_of(f);
+        for (int c = 0; c < p.ncomp; c++) {
+          const views::Window w = views::window(f, grid, vr.r, c);
+          v.win_x[c] = w.x;
+          v.win_y[c] = w.y;
+          v.win_w[c] = w.w;
+          v.win_h[c] = w.h;
+        }
+        Geom g;
+        int rc = geometry(vr.r.w, vr.r.h, &hg.out, &g);
+        if (rc == SPDL_HJ_ERR_BAD_GEOMETRY) {
+          refuse_view(rc);
+          continue;
+        }
+        if (rc) return fail(img, rc, nullptr);
+        if (!sized) {
+          sized = true;
+          G.ow = g.ow;
+          G.oh = g.oh;
+        } else if (g.ow != G.ow || g.oh != G.oh) {
+          set_err(err, errlen,
+                  "all views of a group must produce the same output size "
+                  "(group %zu: %dx%d, view %zu: %dx%d); pass a resize target",
+                  gi, G.ow, G.oh, k, g.ow, g.oh);
+          return SPDL_HJ_ERR_INVALID_ARG;
+        }
+        int hs, vs;
+        if ((rc = chroma_shifts(p, &hs, &vs))) return fail(img, rc, nullptr);
+        const int mode = p.ncomp == 1                                      ? kPlanGray
+                         : p.color == kColorRgb || p.color == kColorCmyk ? kPlanGbr
+                                                                          : kPlanYuv;
+        const PlanKey key{vr.r.w, vr.r.h, hs, vs, mode, hg.out.resize ? hg.out.filter : 0,
+                          g.sw, g.sh, g.dx, g.dy, g.ow, g.oh};
+        auto plan = plans->get(key, &rc);
+        if (!plan && rc == SPDL_HJ_ERR_BAD_GEOMETRY) {  // scale filter too long
+          refuse_view(rc);
+          continue;
+        }
+        if (!plan) return fail(img, rc, nullptr);
+        auto it = placed.find(plan.get());
+        if (it == placed.end()) {
+          it = placed.emplace(plan.get(), (int64_t)L.tables.size()).first;
+          alive.push_back(plan);
+          L.tables.insert(L.tables.end(), plan->blob.begin(), plan->blob.end());
+        }
+        v.dx = g.dx;
+        v.dy = g.dy;
+        v.ow = g.ow;
+        v.oh = g.oh;
+        v.wt_off = it->second;
+        v.sws = plan->d;
+        v.hs_wg0 = v.hs_wgs = 0;
+        v.hbuf_off = 0;
+        if (plan->d.pre) {  // hscale_kernel's tiles and rows, per view
+          v.hs_wg0 = (int32_t)L.hs_wgs;
+          v.hs_wgs = hs_tiles(plan->d).wgs;
+          L.hs_wgs += v.hs_wgs;
+          v.hbuf_off = L.total_hbuf;
+          L.total_hbuf += hs_hbuf_size(plan->d);
+        }
+        v.sws_wg0 = (int32_t)L.sws_wgs;
+        v.sws_bands = plan->bands;
+        v.sws_chunks = plan->chunks;
+        L.sws_wgs += (int64_t)plan->bands * plan->chunks;
+        G.sws_lds = std::max(G.sws_lds, plan->lds);
+        L.desc.push_back(v);
+      }
+      const int64_t per = (int64_t)G.ow * G.oh * 3;
+      const size_t esz = hg.out.dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
+      if ((size_t)(per * G.count) * esz > hg.out_bytes) {
+        set_err(err, errlen, "group %zu: output buffer too small: need %lld bytes, have %zu", gi,
+                (long long)(per * G.count * (int64_t)esz), hg.out_bytes);
+        return SPDL_HJ_ERR_INVALID_ARG;
+      }
+      for (int k = 0; k < G.count; k++) L.desc[G.first + k].out_off = (int64_t)k * per;
+      G.sws_wgs = (int)L.sws_wgs - G.sws_wg0;
+      L.groups.push_back(G);
+    }
+    // (nothing is written before every limit has held)
+    q = 0;
+    for (const HeldViews::Group& hg : hv->groups)
+      for (size_t k = 0; k < hg.views.size(); k++, q++)
+        if (hg.status) hg.status[k] = vstatus[q];
   }
   L.out_elems_per_image = (int64_t)L.ow * L.oh * 3;
   if (yuv)  // Y, then U and V of ceil(ow / hs) x ceil(oh / vs) (gray: Y alone)
@@ -804,6 +984,9 @@ struct spdl_hj_ctx {
   // spdl_hj_set_crops: the source crops of the next batch submission
   std::vector<spdl_hj_rect> crops;
   int64_t idct_workgroups = 0;  // IDCT workgroups the last submission launched
+  int64_t entropy_workgroups = 0;  // ... and its entropy work items (images, or their pieces)
+  // spdl_hj_set_views: the views of the next batch submission
+  HeldViews views;
 };
 
 namespace {
@@ -965,12 +1148,13 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
                       int64_t max_end, hipStream_t st, BatchBuffers* b, char* err, size_t errlen) {
   b->bytes = d_bytes;
   b->n = n;
+  b->ndesc = (int)L.desc.size();  // (+ the view descriptors of a views submission)
   b->nwork = (int)L.work.size();
   HJ_HIP(grow(W.clean, (size_t)max_end + 512, st, &b->clean));
   HJ_HIP(grow(W.segs, (size_t)L.total_segs * 4 + 64, st, &b->segs));
   HJ_HIP(grow(W.dschunks, (size_t)L.total_ds * sizeof(DsChunk) + 64, st, &b->dschunks));
-  HJ_HIP(grow(W.desc, sizeof(ImageDesc) * n + sizeof(uint32_t) * b->nwork, st, &b->desc));
-  b->work = reinterpret_cast<uint32_t*>(b->desc + n);  // the work list follows the descriptors
+  HJ_HIP(grow(W.desc, sizeof(ImageDesc) * b->ndesc + sizeof(uint32_t) * b->nwork, st, &b->desc));
+  b->work = reinterpret_cast<uint32_t*>(b->desc + b->ndesc);  // the work list follows the descriptors
   HJ_HIP(grow(W.chain, (size_t)(kChainHead + L.chain_granules) * 8 + 64, st, &b->chain));
   HJ_HIP(grow(W.maps, (size_t)(L.ds_wgs + L.idct_wgs + L.hs_wgs + L.sws_wgs) * 4 + 64, st,
               &b->ds_map));
@@ -996,7 +1180,8 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
                  size_t out_bytes, hipStream_t st, int sync, int32_t* status, char* err,
                  size_t errlen, bool planes_only, const spdl_hj_rect* crops = nullptr) {
   const size_t esz = out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
-  if (!planes_only && (size_t)L.out_elems_per_image * n * esz > out_bytes) {
+  const bool by_views = !L.groups.empty();  // (build_layout checked every group's buffer)
+  if (!planes_only && !by_views && (size_t)L.out_elems_per_image * n * esz > out_bytes) {
     set_err(err, errlen, "output buffer too small: need %lld bytes, have %zu",
             (long long)(L.out_elems_per_image * n * esz), out_bytes);
     return SPDL_HJ_ERR_INVALID_ARG;
@@ -1032,12 +1217,13 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
   const bool ds_flat = use_flat(L.ds_wgs, L.max_chunks);
   const bool idct_flat = use_flat(L.idct_wgs, (L.max_blocks + kIdctThreads - 1) / kIdctThreads);
   const bool sws_flat = use_flat(L.sws_wgs, (int64_t)L.sws_bands * L.sws_chunks);
-  const size_t desc_bytes = sizeof(ImageDesc) * n + sizeof(uint32_t) * B.nwork;  // + work list
+  const size_t desc_bytes = sizeof(ImageDesc) * B.ndesc + sizeof(uint32_t) * B.nwork;  // + work list
   HJ_HIP(slot.pin_desc.ensure(desc_bytes));
   HJ_HIP(slot.pin_status.ensure(sizeof(int32_t) * n));
   slot.n = n;
-  memcpy(slot.pin_desc.p, L.desc.data(), sizeof(ImageDesc) * n);
-  memcpy(static_cast<ImageDesc*>(slot.pin_desc.p) + n, L.work.data(), sizeof(uint32_t) * B.nwork);
+  memcpy(slot.pin_desc.p, L.desc.data(), sizeof(ImageDesc) * B.ndesc);
+  memcpy(static_cast<ImageDesc*>(slot.pin_desc.p) + B.ndesc, L.work.data(),
+         sizeof(uint32_t) * B.nwork);
   // the batch's swscale tables travel with the descriptors
   const bool swscale = !planes_only && out->csc == SPDL_HJ_CSC_SWSCALE;
   const size_t tb = swscale ? L.tables.size() * 4 : 0;
@@ -1100,7 +1286,9 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
                         ctx->output_path != 1;
   const bool fused = fast_rgb && L.fuse_ok && L.fused_tiles > 0 && ctx->output_path != 2;
   ctx->idct_workgroups = 0;
-  if (!(abl & kAblNoIdct) && !fused) {
+  ctx->entropy_workgroups = B.nwork;
+  // (a views submission whose views were all refused has no block to transform)
+  if (!(abl & kAblNoIdct) && !fused && L.max_blocks > 0) {
     HJ_HIP(launch_idct(B, idct_kind, idct_flat, (int)L.idct_wgs, L.max_blocks,
                        (ctx->xcd_order >> 1) & 1, st));
     ctx->idct_workgroups =
@@ -1126,11 +1314,32 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
   memcpy(bp.std, out->std, sizeof(bp.std));
   bp.csc = sws_csc();
   // the output kernel writes each image's status into the pinned array itself
-  int32_t* hstat = hs && !planes_only ? static_cast<int32_t*>(slot.pin_status.dev) : nullptr;
+  // (not with views: their descriptors are no images; the statuses are copied below)
+  int32_t* hstat =
+      hs && !planes_only && !by_views ? static_cast<int32_t*>(slot.pin_status.dev) : nullptr;
   mark(ctx, slot, 6, st);
   if (!planes_only && !(abl & kAblNoOutput)) {
     const int sws_wgs = (int)L.sws_wgs, hs_wgs = (int)L.hs_wgs;
-    if (yuv)
+    if (by_views) {
+      // once per group: its chain's parameters, its buffer, its slice of the
+      // flat sws grid (hscale_kernel, which takes no parameters of the chain,
+      // runs once over every group's pre-pass rows)
+      bool first = true;
+      for (const Layout::Group& G : L.groups) {
+        BatchParams gp = bp;
+        gp.pix_fmt = G.out.pix_fmt;
+        gp.dtype = G.out.dtype;
+        gp.resize = G.out.resize;
+        gp.filter = G.out.filter;
+        gp.out_w = G.ow;
+        gp.out_h = G.oh;
+        memcpy(gp.mean, G.out.mean, sizeof(gp.mean));
+        memcpy(gp.std, G.out.std, sizeof(gp.std));
+        HJ_HIP(launch_sws(B, G.out_dev, gp, true, G.sws_wgs, 1, 1, G.sws_lds,
+                          first ? hs_wgs : 0, nullptr, st, G.sws_wg0));
+        first = false;
+      }
+    } else if (yuv)
       HJ_HIP(launch_yuv_planes(B, out_dev, sws_wgs, L.sws_lds, hs_wgs, hstat, st));
     else if (fused)
       HJ_HIP(launch_idct_rgb(B, out_dev, bp, idct_kind, L.fused_tiles, hstat, st));
@@ -1177,7 +1386,13 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
   ctx->last_ticket = slot.ticket;
   if (!sync) return SPDL_HJ_OK;
   HJ_HIP(hipEventSynchronize(slot.done));
-  return collect_status(ctx, slot, status, err, errlen);
+  const int rc = collect_status(ctx, slot, status, err, errlen);
+  if (!rc && L.view_refused) {  // as a refused image fails a synchronous crop submission
+    set_err(err, errlen, "Failed to decode an image. (group %d, view %d: %s)",
+            L.view_refused_group, L.view_refused_index, status_str(L.view_refused));
+    return L.view_refused;
+  }
+  return rc;
 }
 
 // Stream the batch of `slot` executes on: the caller's stream with one lane;
@@ -1228,9 +1443,11 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, int k) {
   if (rc) return rc;
   ctx->handoff_retries++;
   const int64_t idct_wgs = ctx->idct_workgroups;  // (the batch's, not this re-decode's)
+  const int64_t ent_wgs = ctx->entropy_workgroups;
   rc = run_pipeline(ctx, *s, r.bytes, r.len, L, 1, &r.out, r.out_dev + (size_t)r.idx[k] * r.img_bytes,
                     r.img_bytes, xs, 1, &st1, err, errlen, false);
   ctx->idct_workgroups = idct_wgs;
+  ctx->entropy_workgroups = ent_wgs;
   ctx->last_ticket = last;
   return rc ? rc : st1;
 }
@@ -1320,6 +1537,39 @@ int take_crops(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, std::vector<s
   return SPDL_HJ_OK;
 }
 
+// The views spdl_hj_set_views left for this submission of n images: taken
+// whatever becomes of the call, and held against the contract's limits
+// (spdl_hipjpeg.h "views").  *hv stays null when there are none.
+int take_views(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, const void* out_dev,
+               size_t out_bytes, bool with_crops, HeldViews* held, const HeldViews** hv, char* err,
+               size_t errlen) {
+  *held = HeldViews{};
+  std::swap(*held, ctx->views);
+  *hv = nullptr;
+  if (!held->any()) return SPDL_HJ_OK;
+  auto bad = [&](const char* what) {
+    set_err(err, errlen, "spdl_hj_set_views: %s", what);
+    return SPDL_HJ_ERR_INVALID_ARG;
+  };
+  if (held->bad || held->groups.empty() || (int)held->groups.size() > views::kMaxGroups)
+    return bad("1 to 4 groups, each with at least one view");
+  if (with_crops) return bad("views and spdl_hj_set_crops on one submission");
+  if (!valid_output(out) || out->csc != SPDL_HJ_CSC_SWSCALE)
+    return bad("the call's output spec must be valid, with csc = swscale");
+  if (out_dev || out_bytes) return bad("the call's out_dev must be NULL and out_bytes 0");
+  for (const HeldViews::Group& g : held->groups) {
+    if (!valid_output(&g.out) || g.out.pix_fmt == SPDL_HJ_FMT_YUV ||
+        g.out.csc != SPDL_HJ_CSC_SWSCALE)
+      return bad("a group's output must be RGB / BGR with csc = swscale");
+    if (g.out.idct != out->idct) return bad("every group's idct must equal the call's");
+    if (!g.out_dev) return bad("a group without an output buffer");
+    for (const spdl_hj_view& v : g.views)
+      if (v.image < 0 || v.image >= n) return bad("a view's image index lies outside the batch");
+  }
+  *hv = held;
+  return SPDL_HJ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1349,6 +1599,25 @@ int spdl_hj_crop_rect(const spdl_hj_image_info* info, const spdl_hj_rect* in, sp
     if (info->h_samp[c] < 1 || info->h_samp[c] > 4 || info->v_samp[c] < 1 || info->v_samp[c] > 4)
       return SPDL_HJ_ERR_INVALID_ARG;
   return crop_resolve(*info, *in, out);
+}
+
+int spdl_hj_set_views(spdl_hj_ctx* ctx, const spdl_hj_view_group* groups, int32_t ngroups) {
+  if (!ctx || ngroups < 0) return SPDL_HJ_ERR_INVALID_ARG;
+  ctx->views = HeldViews{};
+  if (!groups || ngroups == 0) return SPDL_HJ_OK;
+  // (a broken limit is the consuming call's to report: spdl_hipjpeg.h)
+  ctx->views.bad = ngroups > views::kMaxGroups;
+  for (int g = 0; g < ngroups && !ctx->views.bad; g++) {
+    const spdl_hj_view_group& in = groups[g];
+    if (!in.views || in.nviews < 1) {
+      ctx->views.bad = true;
+      break;
+    }
+    ctx->views.groups.push_back({in.out, in.out_dev, in.out_bytes,
+                                 std::vector<spdl_hj_view>(in.views, in.views + in.nviews),
+                                 in.status});
+  }
+  return SPDL_HJ_OK;
 }
 
 int spdl_hj_set_crops(spdl_hj_ctx* ctx, const spdl_hj_rect* rects, int32_t n) {
@@ -1431,7 +1700,12 @@ int spdl_hj_decode_batch(spdl_hj_ctx* ctx, const uint8_t* const* data, const siz
   std::vector<spdl_hj_rect> held;
   const spdl_hj_rect* crops = nullptr;
   const int crc = ctx ? take_crops(ctx, n, out, &held, &crops, err, errlen) : 0;
-  if (!ctx || !data || !sizes || n <= 0 || !valid_output(out) || !out_dev) {
+  HeldViews vheld;
+  const HeldViews* hv = nullptr;
+  const int vrc = ctx ? take_views(ctx, n, out, out_dev, out_bytes, !held.empty(), &vheld, &hv,
+                                   err, errlen) : 0;
+  if (vrc) return vrc;
+  if (!ctx || !data || !sizes || n <= 0 || !valid_output(out) || (!out_dev && !hv)) {
     set_err(err, errlen, n <= 0 ? "the batch is empty" : "invalid argument");
     return SPDL_HJ_ERR_INVALID_ARG;
   }
@@ -1458,8 +1732,9 @@ int spdl_hj_decode_batch(spdl_hj_ctx* ctx, const uint8_t* const* data, const siz
     total += padded;
   }
   Layout L;
-  int rc = build_layout(offs.data(), szs.data(), infos.data(), n, out, ctx->sub_bits, ctx->piece_bytes, L, status, err,
-                        errlen, &ctx->plans, crops);
+  // (views: one entropy workgroup per image, so no hand-off can give up)
+  int rc = build_layout(offs.data(), szs.data(), infos.data(), n, out, ctx->sub_bits,
+                        hv ? 0 : ctx->piece_bytes, L, status, err, errlen, &ctx->plans, crops, hv);
   if (rc) return rc;
   L.ms_side = prog;
   L.ms_known = true;
@@ -1485,8 +1760,13 @@ int spdl_hj_decode_batch_device(spdl_hj_ctx* ctx, const uint8_t* dev_data, size_
   std::vector<spdl_hj_rect> held;
   const spdl_hj_rect* crops = nullptr;
   const int crc = ctx ? take_crops(ctx, n, out, &held, &crops, err, errlen) : 0;
+  HeldViews vheld;
+  const HeldViews* hv = nullptr;
+  const int vrc = ctx ? take_views(ctx, n, out, out_dev, out_bytes, !held.empty(), &vheld, &hv,
+                                   err, errlen) : 0;
+  if (vrc) return vrc;
   if (!ctx || !dev_data || !offsets || !sizes || !infos || n <= 0 || !valid_output(out) ||
-      !out_dev) {
+      (!out_dev && !hv)) {
     set_err(err, errlen, n <= 0 ? "the batch is empty" : "invalid argument");
     return SPDL_HJ_ERR_INVALID_ARG;
   }
@@ -1494,8 +1774,8 @@ int spdl_hj_decode_batch_device(spdl_hj_ctx* ctx, const uint8_t* dev_data, size_
   DeviceGuard g(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout L;
-  int rc = build_layout(offsets, sizes, infos, n, out, ctx->sub_bits, ctx->piece_bytes, L, status, err, errlen,
-                        &ctx->plans, crops);
+  int rc = build_layout(offsets, sizes, infos, n, out, ctx->sub_bits, hv ? 0 : ctx->piece_bytes, L,
+                        status, err, errlen, &ctx->plans, crops, hv);
   if (rc) return rc;
   // the caller's probe says which files take the multi-scan path (ABI 5)
   for (int i = 0; i < n; i++) L.ms_side = L.ms_side || infos[i].multiscan != 0;
@@ -1611,13 +1891,22 @@ int spdl_hj_decode_staged(spdl_hj_ctx* ctx, int64_t ticket, size_t len, const in
   std::vector<spdl_hj_rect> held;
   const spdl_hj_rect* crops = nullptr;
   const int crc = ctx ? take_crops(ctx, n, out, &held, &crops, err, errlen) : 0;
+  HeldViews vheld;
+  const HeldViews* hv = nullptr;
+  const int vrc = ctx ? take_views(ctx, n, out, out_dev, out_bytes, !held.empty(), &vheld, &hv,
+                                   err, errlen) : 0;
   Slot* s = ctx ? find_slot(ctx, ticket) : nullptr;
   if (!s || !s->staged) {
     set_err(err, errlen, "ticket %lld does not name an acquired staging slot", (long long)ticket);
     return SPDL_HJ_ERR_INVALID_ARG;
   }
   s->staged = false;  // the slot is consumed whatever happens below
-  if (!offsets || !sizes || n <= 0 || !valid_output(out) || !out_dev || len + 512 > s->pin_in.cap) {
+  if (vrc) {
+    s->ticket = 0;
+    return vrc;
+  }
+  if (!offsets || !sizes || n <= 0 || !valid_output(out) || (!out_dev && !hv) ||
+      len + 512 > s->pin_in.cap) {
     set_err(err, errlen, n <= 0 ? "the batch is empty" : "invalid argument");
     s->ticket = 0;
     return SPDL_HJ_ERR_INVALID_ARG;
@@ -1644,8 +1933,8 @@ int spdl_hj_decode_staged(spdl_hj_ctx* ctx, int64_t ticket, size_t len, const in
     }
   }
   Layout L;
-  int rc = build_layout(offsets, sizes, infos.data(), n, out, ctx->sub_bits, ctx->piece_bytes, L, status, err, errlen,
-                        &ctx->plans, crops);
+  int rc = build_layout(offsets, sizes, infos.data(), n, out, ctx->sub_bits,
+                        hv ? 0 : ctx->piece_bytes, L, status, err, errlen, &ctx->plans, crops, hv);
   if (rc) {
     s->ticket = 0;
     return rc;
@@ -2162,6 +2451,7 @@ int spdl_hj_get_param(spdl_hj_ctx* ctx, const char* name, int64_t* value) {
       {"xcd_order", ctx->xcd_order},
       {"handoff_retries", ctx->handoff_retries},
       {"idct_workgroups", ctx->idct_workgroups},
+      {"entropy_workgroups", ctx->entropy_workgroups},
   };
   for (const auto& t : tab)
     if (!strcmp(name, t.n)) {

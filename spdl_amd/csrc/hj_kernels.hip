@@ -278,7 +278,8 @@ __global__ void __launch_bounds__(256, 8) parse_kernel(const uint8_t* __restrict
                                                     uint32_t* __restrict__ ds_map,
                                                     uint32_t* __restrict__ idct_map,
                                                     uint32_t* __restrict__ hs_map,
-                                                    uint32_t* __restrict__ sws_map) {
+                                                    uint32_t* __restrict__ sws_map,
+                                                    const int ndesc) {
   __shared__ ParseScratch s;
   __shared__ int st;
   __shared__ __attribute__((aligned(16))) uint8_t hdr[kHdrBytes];
@@ -311,6 +312,21 @@ __global__ void __launch_bounds__(256, 8) parse_kernel(const uint8_t* __restrict
       tables[i] = host_tables[i];
     for (int i = img * blockDim.x + tid; i < nwork; i += gridDim.x * blockDim.x)
       work[i] = host_work[i];
+  }
+  // A views submission: descriptors [n, ndesc) are the views' (ImageDesc::src),
+  // which no workgroup parses.  The images' workgroups bring them over in turn
+  // and map their output workgroups.
+  for (int v = (int)gridDim.x + img; v < ndesc; v += (int)gridDim.x) {
+    const ImageDesc* sv = (host_desc ? host_desc : desc) + v;
+    if (host_desc) {
+      const uint64_t* src = reinterpret_cast<const uint64_t*>(sv);
+      uint64_t* dst = reinterpret_cast<uint64_t*>(desc + v);
+      for (int i = tid; i < (int)(sizeof(ImageDesc) / 8); i += blockDim.x) dst[i] = src[i];
+    }
+    const int hs0 = sv->hs_wg0, hsn = sv->hs_wgs, sw0 = sv->sws_wg0,
+              swn = sv->sws_bands * sv->sws_chunks;
+    for (int i = tid; i < hsn; i += blockDim.x) hs_map[hs0 + i] = (uint32_t)v;
+    for (int i = tid; i < swn; i += blockDim.x) sws_map[sw0 + i] = (uint32_t)v;
   }
   __syncthreads();
   const ImageDesc& dd = sdd;
@@ -5263,9 +5279,10 @@ __global__ void __launch_bounds__(256) hscale_kernel(const uint8_t* __restrict__
                                                      const uint32_t* __restrict__ hs_map,
                                                      int16_t* __restrict__ hbuf) {
   const int img = (int)hs_map[blockIdx.x];
-  const ImageInfo& in = infos[img];
-  if (in.status != kOk) return;
   const ImageDesc& dd = desc[img];
+  // (a view's descriptor: the status is its image's, ImageDesc::src)
+  const ImageInfo& in = infos[dd.src];
+  if (in.status != kOk) return;
   const SwsDesc& s = dd.sws;
   const int32_t* T = pool + dd.wt_off;
   const HsTiles ht = hs_tiles(s);
@@ -5362,7 +5379,8 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
                                                   void* __restrict__ out, const BatchParams p,
                                                   int32_t* __restrict__ host_status,
                                                   const int16_t* __restrict__ hbuf,
-                                                  const uint32_t* __restrict__ sws_map) {
+                                                  const uint32_t* __restrict__ sws_map,
+                                                  const int wg0) {
   extern __shared__ __attribute__((aligned(16))) int16_t sws_lds[];
   // (band, chunk, image) grid, or a flat grid over every image's own tiles
   // (sws_map: workgroup -> image) when the batch's plans differ widely
@@ -5371,15 +5389,21 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
   // whose source rows overlap, run on one XCD at about the same time
   uint32_t bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
   if (p.xcd_order & 1) xcd_order(bx, by, bz);
+  // (wg0: a views submission launches once per group, over that group's part
+  // of the map; 0 otherwise)
+  if (flat) bx += (uint32_t)wg0;
   const int img = flat ? (int)sws_map[bx] : (int)bz, tid = threadIdx.x, nt = blockDim.x;
   const ImageDesc& dd = desc[img];
   const int t = flat ? (int)bx - dd.sws_wg0 : (int)(bx * dd.sws_chunks + by);
   const int band = flat ? t / dd.sws_chunks : (int)bx;
   const int chunk = flat ? t - band * dd.sws_chunks : (int)by;
-  const ImageInfo& in = infos[img];
+  // (a view's descriptor reads its image's status, ImageDesc::src; an image's
+  // own names itself)
+  const ImageInfo& in = infos[dd.src];
   // the image's final status, straight into the slot's pinned status array
   if (host_status && t == 0 && tid == 0) host_status[img] = in.status;
-  if (in.status != kOk) return;
+  // (a view the host refused alone: nothing to do, its image's status stays clean)
+  if (in.status != kOk || dd.refuse) return;
   const SwsDesc& s = dd.sws;
   const int yo0 = band * s.rb, xo0 = chunk * s.col_chunk;
   if (yo0 >= dd.oh || xo0 >= dd.ow) return;
@@ -6210,11 +6234,12 @@ hipError_t launch_nv12(const uint8_t* src, uint8_t* dst, int frames, int height,
 
 hipError_t launch_parse(const BatchBuffers& b, const ImageDesc* host_desc, const void* host_tables,
                         int64_t table_bytes, int threads, hipStream_t st) {
-  const auto* host_work = host_desc ? reinterpret_cast<const uint32_t*>(host_desc + b.n) : nullptr;
+  const auto* host_work =
+      host_desc ? reinterpret_cast<const uint32_t*>(host_desc + b.ndesc) : nullptr;
   hipLaunchKernelGGL(parse_kernel, dim3(b.n), dim3(threads), 0, st, b.bytes, host_desc, b.desc,
                      b.infos, b.luts, static_cast<const uint4*>(host_tables),
                      reinterpret_cast<uint4*>(b.wts), (table_bytes + 15) / 16, host_work, b.work,
-                     b.nwork, b.chain, b.ds_map, b.idct_map, b.hs_map, b.sws_map);
+                     b.nwork, b.chain, b.ds_map, b.idct_map, b.hs_map, b.sws_map, b.ndesc);
   hipLaunchKernelGGL(lut_kernel, dim3(8, b.n), dim3(256), 0, st, b.bytes, b.desc, b.infos, b.luts);
   return hipGetLastError();
 }
@@ -6303,11 +6328,11 @@ static void launch_hscale(const BatchBuffers& b, int hs_wgs, hipStream_t st) {
 }
 hipError_t launch_sws(const BatchBuffers& b, void* out, const BatchParams& p, bool flat,
                       int sws_wgs, int bands, int chunks, int lds_bytes, int hs_wgs,
-                      int32_t* host_status, hipStream_t st) {
+                      int32_t* host_status, hipStream_t st, int wg0) {
   launch_hscale(b, hs_wgs, st);
   const dim3 grid = flat ? dim3(sws_wgs) : dim3(bands, chunks, b.n);
   hipLaunchKernelGGL(sws_kernel, grid, dim3(256), lds_bytes, st, b.planes, b.desc, b.infos, b.wts,
-                     out, p, host_status, b.hbuf, flat ? b.sws_map : nullptr);
+                     out, p, host_status, b.hbuf, flat ? b.sws_map : nullptr, wg0);
   return hipGetLastError();
 }
 hipError_t launch_yuv_planes(const BatchBuffers& b, void* out, int sws_wgs, int lds_bytes,

@@ -28,6 +28,10 @@ struct BatchBuffers {
   // launcher's `flat` picks that grid; else (largest image's tiles, image), no map
   uint32_t *ds_map, *idct_map, *hs_map, *sws_map;
   int n, nwork;  // images, entropy work items
+  // descriptors: n, or in a views submission the n images' and then the views'
+  // (ImageDesc::src).  The front-end kernels launch over n; parse_kernel also
+  // brings the views' descriptors over and maps their output workgroups.
+  int ndesc;
 };
 
 // parse_kernel + lut_kernel.  host_desc (descriptors, then the work list) and
@@ -52,10 +56,12 @@ hipError_t launch_rgb_unscaled(const BatchBuffers& b, void* out, const BatchPara
                                int64_t max_px, int32_t* host_status, hipStream_t st);
 hipError_t launch_idct_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int idct,
                            int tiles, int32_t* host_status, hipStream_t st);
-// hscale_kernel first when hs_wgs > 0; yuv_planes_kernel's grid is always flat
+// hscale_kernel first when hs_wgs > 0; yuv_planes_kernel's grid is always flat.
+// wg0 (flat grids): the launch's first workgroup in sws_map -- a views
+// submission launches sws_kernel once per group over that group's tiles.
 hipError_t launch_sws(const BatchBuffers& b, void* out, const BatchParams& p, bool flat,
                       int sws_wgs, int bands, int chunks, int lds_bytes, int hs_wgs,
-                      int32_t* host_status, hipStream_t st);
+                      int32_t* host_status, hipStream_t st, int wg0 = 0);
 hipError_t launch_yuv_planes(const BatchBuffers& b, void* out, int sws_wgs, int lds_bytes,
                              int hs_wgs, int32_t* host_status, hipStream_t st);
 // The video path's converter, outside any batch (spdl_hj_nv12_to_planar_rgb).

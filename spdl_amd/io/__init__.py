@@ -10,6 +10,7 @@ from ._image import (
     load_image,
     load_image_batch,
     load_image_batch_nvjpeg,
+    load_image_views,
 )
 from ._preprocessing import get_video_filter_desc, parse_image_filter
 from ._tar import TarImageStream, iter_tarfile
@@ -43,6 +44,7 @@ __all__ = [
     "load_image_batch",
     "load_image_batch_hip",
     "load_image_batch_nvjpeg",
+    "load_image_views",
     "nv12_to_bgr",
     "nv12_to_rgb",
     "parse_image_filter",

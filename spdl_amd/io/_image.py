@@ -381,6 +381,134 @@ def load_image_batch(
     return buf
 
 
+_VIEW_GROUP_KEYS = ("width", "height", "scale_algo", "scale_mode", "pix_fmt", "normalize", "dtype",
+                    "mean", "std", "crops")
+
+
+def _view_group_output(g) -> Output:
+    """The output chain of one ``load_image_views`` group: its image
+    arguments, as ``load_image_batch`` reads them."""
+    if not hasattr(g, "keys"):
+        raise ValueError("a group is a mapping of image arguments plus crops=")
+    unknown = sorted(set(g.keys()) - set(_VIEW_GROUP_KEYS))
+    if unknown:
+        raise ValueError(f"unknown group keys {unknown}; a group takes {list(_VIEW_GROUP_KEYS)}")
+    if "crops" not in g:
+        raise ValueError("a group needs crops=[[rect, ...] per image]")
+    pix_fmt = g.get("pix_fmt", "rgb24")
+    if pix_fmt not in ("rgb", "bgr", "rgb24", "bgr24"):
+        raise ValueError(f"a group's pix_fmt is rgb, bgr, rgb24 or bgr24, not {pix_fmt!r}")
+    desc = get_video_filter_desc(scale_width=g.get("width"), scale_height=g.get("height"),
+                                 scale_algo=g.get("scale_algo", "bicubic"),
+                                 scale_mode=g.get("scale_mode", "pad"), pix_fmt=pix_fmt)
+    out = parse_image_filter(desc, default_pix_fmt=pix_fmt)
+    if g.get("normalize", False):
+        dtype = g.get("dtype", "float16")
+        if dtype not in _lib.NORM_DTYPES:
+            raise ValueError(f"a normalised group's dtype is float16 or bfloat16, not {dtype!r}")
+        out = Output(**{**out.__dict__, "normalize": True,
+                        "mean": tuple(g.get("mean", Output.mean)),
+                        "std": tuple(g.get("std", Output.std)), "norm_dtype": dtype})
+    return out
+
+
+def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = True):
+    """Several crops and sizes of every image from one decode (an extension,
+    like ``crops=`` and ``normalize=``): multi-crop augmentation, a thumbnail
+    beside a training crop.  Every file is parsed and entropy-decoded once and
+    inverse-transformed over the rectangle its views cover; each group then
+    scales its views through its own chain into its own buffer.
+
+    ``groups``: mappings of ``load_image_batch``'s image arguments -- ``width``,
+    ``height``, ``scale_algo``, ``scale_mode``, ``pix_fmt``, ``normalize``,
+    ``dtype`` ("float16" / "bfloat16"), ``mean``, ``std`` -- plus
+    ``crops=[[rect, ...] per image]``: the source rectangles ``(x, y, w, h)``
+    (``None``: the whole frame) this group takes of each image, any number,
+    none included.  At most four groups.
+
+    Returns one ``(buffer, image_indices)`` per group: ``buffer`` is
+    ``[rows, H, W, 3]`` (``[rows, 3, H, W]`` planar) with rows in (image, rect)
+    order and ``image_indices[r]`` the image row r was made of.
+    ``strict=False`` drops the rows of failed images and refused rectangles
+    (``image_indices`` says what remains); ``strict=True`` raises, as
+    ``load_image_batch`` does."""
+    if not srcs:
+        raise ValueError("`srcs` must not be empty.")
+    if device_config is None:
+        raise ValueError("device_config must be provided.")
+    groups = list(groups)
+    if not 1 <= len(groups) <= 4:
+        raise ValueError(f"1 to 4 groups, not {len(groups)}")
+    outs = [_view_group_output(g) for g in groups]
+    for g in groups:
+        per_image = list(g["crops"])
+        if len(per_image) != len(srcs):
+            raise ValueError(f"{len(per_image)} crop lists for {len(srcs)} images")
+        for rects in per_image:
+            if isinstance(rects, (str, bytes)) or not hasattr(rects, "__iter__"):
+                raise ValueError("crops= is a list of rectangles per image")
+            for r in rects:
+                _lib._view_rect(r)
+    cfg = device_config
+    datas, keep, infos = [], [], []
+    for i, s in enumerate(srcs):
+        try:
+            d = _read(s)
+            infos.append(_lib.get_image_info(d))
+        except Exception as err:  # reference logs and skips (strict=False)
+            _LG.error("Failed to load image %d: %s", i, err)
+            continue
+        datas.append(d)
+        keep.append(i)
+    if strict and len(datas) != len(srcs):
+        raise RuntimeError("Failed to load some images.")
+    if not datas:
+        raise RuntimeError("Failed to load all the images.")
+    # one submission: every group's views of the surviving images, (image, rect) order
+    vgroups, bufs, rows = [], [], []
+    for g, out in zip(groups, outs):
+        per_image = list(g["crops"])
+        views, src_of, size = [], [], None
+        for k, i in enumerate(keep):
+            for r in per_image[i]:
+                views.append((k, r))
+                src_of.append(i)
+                if size is None:
+                    rc, rr = _lib.crop_rect(infos[k], r)
+                    if not rc:
+                        size = _lib.output_size(rr[2], rr[3], out)
+        if not views:
+            raise ValueError("a group without any rectangle")
+        if size is None:
+            raise RuntimeError("Failed to decode an image. (no rectangle of a group resolves)")
+        shape = (len(views), *_shape(out, *size))
+        buf = _alloc_out(cfg, shape, out.torch_dtype)
+        nbytes = int(np.prod(shape)) * (1 if out.torch_dtype == torch.uint8 else 2)
+        vgroups.append(_lib.ViewGroup(out, views, buf.data_ptr(), nbytes))
+        bufs.append(buf)
+        rows.append(src_of)
+    dec = _lib.thread_decoder(cfg.device_index)
+    # (of the call's own spec only the IDCT counts; strict: a failed image or a
+    # refused view raises here)
+    status = dec.decode_batch(datas, Output(pix_fmt="rgb24"), 0, 0, stream=_stream(cfg), sync=True,
+                              check=strict, views=vgroups)
+    result = []
+    from ._convert import to_torch
+
+    for vg, buf, src_of in zip(vgroups, bufs, rows):
+        ok = [r for r, ((k, _), st) in enumerate(zip(vg.views, vg.statuses))
+              if st == 0 and status[k] == 0]
+        if len(ok) != len(src_of):  # (strict=True raised above)
+            for r in sorted(set(range(len(src_of))) - set(ok)):
+                _LG.error("Failed to decode a view of image %d", src_of[r])
+            if not ok:
+                raise RuntimeError("Failed to load all the images.")
+            idx = torch.tensor(ok, device=f"cuda:{cfg.device_index}")
+            buf = CUDABuffer(to_torch(buf).index_select(0, idx), stream=cfg.stream)
+        result.append((buf, [src_of[r] for r in ok]))
+    return result
+
+
 _UNSUPPORTED_FRAMES = {2: "gbrp", 3: "gbrap", 4: "yuva444p", 5: "yuva444p"}  # by spdl_hj_color
 
 
