@@ -29,9 +29,9 @@
 #include "../../include/spdl_hipjpeg.h"
 #include "hj_common.h"
 #include "hj_launch.h"
+#include "hj_layout.h"
 #include "hj_probe.h"
 #include "hj_sws.h"
-#include "hj_sws_tile.h"
 #include "hj_views.h"
 
 using namespace hj;
@@ -50,25 +50,16 @@ void set_err(char* err, size_t errlen, const char* fmt, ...) {
   va_end(ap);
 }
 
-const char* status_str(int s) {
-  switch (s) {
-    case SPDL_HJ_OK: return "OK";
-    case SPDL_HJ_ERR_NOT_JPEG: return "not a JPEG";
-    case SPDL_HJ_ERR_UNSUPPORTED: return "unsupported JPEG (arithmetic, lossless, 12-bit or CMYK)";
-    case SPDL_HJ_ERR_BAD_HEADER: return "corrupt JPEG header";
-    case SPDL_HJ_ERR_BAD_HUFFMAN: return "corrupt entropy-coded data";
-    case SPDL_HJ_ERR_TRUNCATED: return "truncated entropy-coded data";
-    case SPDL_HJ_ERR_BAD_RESTART: return "restart marker mismatch";
-    case SPDL_HJ_ERR_BAD_GEOMETRY: return "invalid resize geometry";
-    case SPDL_HJ_ERR_INVALID_ARG: return "invalid argument";
-    case SPDL_HJ_ERR_HIP: return "HIP runtime error";
-    case SPDL_HJ_ERR_OOM: return "out of device memory";
-    case SPDL_HJ_ERR_HANDOFF: return "entropy piece hand-off gave up";
-    default: return "unknown error";
+// The batch's layout (hj_layout.h) with the entry points' error convention:
+// the text into err, the failing image's status into status[]
+int plan_batch(const LayoutRequest& rq, Layout& L, int32_t* status, char* err, size_t errlen) {
+  const LayoutResult r = build_layout(rq, L);
+  if (r.rc) {
+    if (status && r.image >= 0) status[r.image] = r.rc;
+    set_err(err, errlen, "%s", r.err);
   }
+  return r.rc;
 }
-
-inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
 // A grow-only device buffer.  Given a stream, a growth is stream-ordered
 // (hipFreeAsync / hipMallocAsync on it, after the work it already holds):
@@ -250,594 +241,6 @@ void parallel_pack(CopyPool* pool, uint8_t* base, const std::vector<CopyItem>& i
   };
   if (!pool || pool->workers() < 2 || total < (4 << 20)) body(0, 1);
   else pool->run(body);
-}
-
-// ---- geometry (FFmpeg scale/pad/crop semantics; see oracle jo_geometry) ----
-int64_t rescale_rnd(int64_t a, int64_t b, int64_t c) { return (a * b + c / 2) / c; }
-
-struct Geom {
-  int sw, sh, dx, dy, ow, oh;
-};
-
-// hs / vs: the chroma ratios of a planar destination (SPDL_HJ_FMT_YUV), which
-// pad and crop offsets and sizes must respect; 1 for every packed output
-int geometry(int w, int h, const spdl_hj_output* o, Geom* g, int hs = 1, int vs = 1) {
-  if (w <= 0 || h <= 0) return SPDL_HJ_ERR_BAD_GEOMETRY;
-  if (!o->resize) {
-    *g = {w, h, 0, 0, w, h};
-    return SPDL_HJ_OK;
-  }
-  if (o->pad_w < 0 || o->pad_h < 0 || o->crop_w < 0 || o->crop_h < 0)
-    return SPDL_HJ_ERR_BAD_GEOMETRY;
-  // vf_scale's ff_scale_adjust_dimensions: 0 is the input size; -n keeps the
-  // aspect ratio from the other side and makes the result divisible by n
-  // (av_rescale: nearest, ties away from zero); both negative: the input size
-  int64_t fw = o->fit_w ? o->fit_w : w, fh = o->fit_h ? o->fit_h : h;
-  const int64_t dw = fw < -1 ? -fw : 1, dh = fh < -1 ? -fh : 1;
-  if (fw < 0 && fh < 0) {
-    fw = w;
-    fh = h;
-  }
-  if (fw < 0) fw = rescale_rnd(fh, w, (int64_t)h * dw) * dw;
-  if (fh < 0) fh = rescale_rnd(fw, h, (int64_t)w * dh) * dh;
-  int64_t sw = fw, sh = fh;
-  if (o->aspect != SPDL_HJ_ASPECT_NONE) {
-    int64_t tw = rescale_rnd(fh, w, h), th = rescale_rnd(fw, h, w);
-    if (o->aspect == SPDL_HJ_ASPECT_DECREASE) {
-      sw = tw < fw ? tw : fw;
-      sh = th < fh ? th : fh;
-    } else {
-      sw = tw > fw ? tw : fw;
-      sh = th > fh ? th : fh;
-    }
-  }
-  if (sw < 1) sw = 1;
-  if (sh < 1) sh = 1;
-  int64_t cw = sw, ch = sh, px = 0, py = 0;
-  if (o->pad_w > 0 && o->pad_h > 0) {
-    cw = o->pad_w;
-    ch = o->pad_h;
-    if (cw < sw || ch < sh) return SPDL_HJ_ERR_BAD_GEOMETRY;
-    // a subsampled frame: vf_pad rounds an input or box size that is no
-    // multiple of the chroma ratio in ways not pinned here -- refused
-    if (sw % hs || cw % hs || sh % vs || ch % vs) return SPDL_HJ_ERR_BAD_GEOMETRY;
-    px = (cw - sw) / 2 / hs * hs;
-    py = (ch - sh) / 2 / vs * vs;
-  }
-  int64_t ow = cw, oh = ch, cx = 0, cy = 0;
-  if (o->crop_w > 0 && o->crop_h > 0) {
-    ow = o->crop_w;
-    oh = o->crop_h;
-    if (ow > cw || oh > ch) return SPDL_HJ_ERR_BAD_GEOMETRY;
-    // (vf_crop would shrink such a size to a multiple without saying so)
-    if (ow % hs || oh % vs) return SPDL_HJ_ERR_BAD_GEOMETRY;
-    cx = (cw - ow) / 2 / hs * hs;
-    cy = (ch - oh) / 2 / vs * vs;
-  }
-  if (sw > 65535 || sh > 65535 || ow > 65535 || oh > 65535) return SPDL_HJ_ERR_BAD_GEOMETRY;
-  *g = {(int)sw, (int)sh, (int)(px - cx), (int)(py - cy), (int)ow, (int)oh};
-  return SPDL_HJ_OK;
-}
-
-// The rectangle rules (chroma shifts, the source crop's rounding) are pure
-// arithmetic shared with views: hj_views.h.
-views::Frame frame_of(const spdl_hj_image_info& p) {
-  views::Frame f{p.width, p.height, p.ncomp, {}, {}};
-  for (int c = 0; c < kMaxComp; c++) {
-    f.h_samp[c] = p.h_samp[c];
-    f.v_samp[c] = p.v_samp[c];
-  }
-  return f;
-}
-
-int chroma_shifts(const spdl_hj_image_info& p, int* hs, int* vs) {
-  return views::chroma_shifts(frame_of(p), hs, vs);
-}
-
-bool rect_is_none(const spdl_hj_rect& r) { return !(r.x | r.y | r.w | r.h); }
-
-// ---- source crop (spdl_hipjpeg.h: libavfilter's crop, exact=0, on the
-// decoder's frame) -----------------------------------------------------------
-int crop_resolve(const spdl_hj_image_info& p, const spdl_hj_rect& in, spdl_hj_rect* out) {
-  views::Rect r;
-  const int rc = views::resolve(frame_of(p), views::Rect{in.x, in.y, in.w, in.h}, &r);
-  if (!rc) *out = {r.x, r.y, r.w, r.h};
-  return rc;
-}
-
-struct Layout {
-  std::vector<ImageDesc> desc;
-  std::vector<int32_t> tables;  // the batch's swscale table pool
-  int64_t total_blocks = 0, total_planes = 0, total_segs = 0, total_recs = 0;
-  int64_t out_elems_per_image = 0;
-  int max_blocks = 0;  // most blocks idct_kernel transforms of one image (ImageDesc::idct_blocks)
-  int64_t max_px = 0;
-  int64_t total_ds = 0;
-  int max_chunks = 0;
-  int ow = 0, oh = 0;
-  int sws_bands = 0, sws_chunks = 0, sws_lds = 0;
-  bool all_special = true;  // every image takes swscale's unscaled converter
-  bool fuse_ok = true;      // ... with standard 4:2:0 / 4:2:2 MCUs (idct_rgb_kernel)
-  int yuv_hs = 0, yuv_vs = 0;  // SPDL_HJ_FMT_YUV: image 0's chroma shifts, and whether it is
-  bool yuv_gray = false;      // gray -- the batch's plane layout
-  int64_t cmyk_px = 0;      // 4-component images needing cmyk_kernel's K transform: max pixels
-  int fused_tiles = 0;      // idct_rgb_kernel workgroups per image (max)
-  // entropy work items (image | piece << 24), the images with the most
-  // pieces first, and the granules of their hand-off records (hj_common.h)
-  std::vector<uint32_t> work;
-  int64_t chain_granules = 0;
-  // flat destuff / IDCT grids: workgroups over the whole batch
-  int64_t ds_wgs = 0, idct_wgs = 0;
-  // hscale_kernel (large downscales): workgroups and int16 rows
-  int64_t hs_wgs = 0, total_hbuf = 0;
-  int64_t sws_wgs = 0;  // sws_kernel tiles over the batch (per-image plans)
-  // a progressive (SOF2) image is in the batch: multiscan_kernel runs on a
-  // side stream beside destuff + entropy (only the host-bytes entry points
-  // see the headers; elsewhere it runs after entropy on the lane's stream)
-  bool ms_side = false;
-  // the entry point knows every image's scan structure (host probes, or the
-  // caller's ABI-5 image_info): a batch without multi-scan images may skip
-  // the multi-scan launch
-  bool ms_known = false;
-  // images decoded by several entropy workgroups (hand-offs): their probes,
-  // for a one-workgroup re-decode should a hand-off give up
-  std::vector<std::pair<int, spdl_hj_image_info>> multi;
-  // A views submission (spdl_hj_set_views): desc holds the n image
-  // descriptors, then every group's view descriptors (views::group_slices);
-  // the output stage runs once per group over its slice.  Empty otherwise.
-  struct Group {
-    spdl_hj_output out;
-    void* out_dev = nullptr;
-    int first = 0, count = 0;        // its view descriptors in desc
-    int sws_wg0 = 0, sws_wgs = 0;    // its tiles in the flat sws grid (sws_map)
-    int sws_lds = 0;
-    int ow = 0, oh = 0;              // every view's output size
-  };
-  std::vector<Group> groups;
-  int view_refused = 0;  // the first status the host gave a view alone (0: none)
-  int view_refused_group = 0, view_refused_index = 0;
-};
-
-// What spdl_hj_set_views left for the next submission: the groups, their view
-// arrays copied.  `bad`: the call's own arguments broke a limit (more groups
-// than views::kMaxGroups, a group without views) -- the consuming call says so.
-struct HeldViews {
-  struct Group {
-    spdl_hj_output out;
-    void* out_dev;
-    size_t out_bytes;
-    std::vector<spdl_hj_view> views;
-    int32_t* status;
-  };
-  std::vector<Group> groups;
-  bool bad = false;
-  bool any() const { return bad || !groups.empty(); }
-};
-
-int build_layout(const int64_t* offsets, const int64_t* sizes, const spdl_hj_image_info* infos,
-                 int n, const spdl_hj_output* out, int sub_bits, int64_t piece_bytes, Layout& L,
-                 int32_t* status, char* err, size_t errlen, PlanCache* plans,
-                 const spdl_hj_rect* crops = nullptr, const HeldViews* hv = nullptr) {
-  L.desc.assign(n, ImageDesc{});
-  // Views (validated by take_views): each one's rectangle, resolved with its
-  // image below; `vorder` lists them by image (image i's: [vstart[i], vstart[i + 1]))
-  struct ViewRes {
-    views::Rect in, r;
-    int rc;
-  };
-  std::vector<ViewRes> vres;
-  std::vector<int> vstart, vorder;
-  if (hv) {
-    vstart.assign(n + 1, 0);
-    for (const auto& g : hv->groups)
-      for (const spdl_hj_view& v : g.views) {
-        vstart[v.image + 1]++;
-        vres.push_back({{v.rect.x, v.rect.y, v.rect.w, v.rect.h}, {}, 0});
-      }
-    for (int i = 0; i < n; i++) vstart[i + 1] += vstart[i];
-    vorder.resize(vres.size());
-    std::vector<int> fill(vstart.begin(), vstart.end() - 1);
-    int q = 0;
-    for (const auto& g : hv->groups)
-      for (const spdl_hj_view& v : g.views) vorder[fill[v.image]++] = q++;
-    L.desc.reserve(n + vres.size());
-  }
-  const bool yuv = out->pix_fmt == SPDL_HJ_FMT_YUV;
-  bool have_size = false;  // L.ow x L.oh is set (by the first image that is not refused)
-  bool have_fmt = false;   // ... and the planar output's frame format
-  // an image the host refuses alone (ImageDesc::refuse): its one output
-  // workgroup reports the status, every other kernel skips it
-  auto refuse = [&](ImageDesc& d, int why) {
-    d.refuse = why;
-    d.sws_wg0 = (int32_t)L.sws_wgs++;
-    d.sws_bands = d.sws_chunks = 1;
-    L.sws_bands = std::max(L.sws_bands, 1);
-    L.sws_chunks = std::max(L.sws_chunks, 1);
-  };
-  // plan -> offset in L.tables.  `alive` holds every placed plan until the
-  // layout is built: the cache may evict (and free) a plan mid-batch, and a
-  // new plan at a recycled address must not match a stale `placed` entry
-  std::map<const PackedPlan*, int64_t> placed;
-  std::vector<std::shared_ptr<const PackedPlan>> alive;
-  auto fail = [&](int i, int rc, const char* what) {
-    if (status) status[i] = rc;
-    set_err(err, errlen, "Failed to decode an image. (image %d: %s)", i, what ? what : status_str(rc));
-    return rc;
-  };
-  for (int i = 0; i < n; i++) {
-    ImageDesc& d = L.desc[i];
-    const spdl_hj_image_info& p = infos[i];
-    d.in_off = offsets[i];
-    d.in_size = sizes[i];
-    d.width = p.width;
-    d.height = p.height;
-    d.ncomp = p.ncomp;
-    d.color = p.color;
-    if (p.ncomp == 4) {
-      // libjpeg's JFIF conversion has no CMYK -> RGB; the K transform
-      // (FFmpeg's, cmyk_kernel) runs unless the planes are YCbCr + K
-      if (out->csc == SPDL_HJ_CSC_JFIF) return fail(i, SPDL_HJ_ERR_UNSUPPORTED, "CMYK with csc=jfif");
-      if (p.color != kColorYcbcrk) L.cmyk_px = std::max(L.cmyk_px, (int64_t)p.width * p.height);
-    }
-    int hmax = 1, vmax = 1;
-    for (int c = 0; c < p.ncomp; c++) {
-      d.h_samp[c] = p.h_samp[c];
-      d.v_samp[c] = p.v_samp[c];
-      hmax = p.h_samp[c] > hmax ? p.h_samp[c] : hmax;
-      vmax = p.v_samp[c] > vmax ? p.v_samp[c] : vmax;
-    }
-    int bw[kMaxComp] = {}, bh[kMaxComp] = {};
-    int64_t nblocks;
-    int bpm = 0;
-    if (p.ncomp == 1) {
-      bw[0] = (p.width + 7) / 8;
-      bh[0] = (p.height + 7) / 8;
-      nblocks = (int64_t)bw[0] * bh[0];
-      bpm = hmax = vmax = 1;  // (a gray frame's factors mean nothing)
-    } else {
-      int mcux = (p.width + 8 * hmax - 1) / (8 * hmax), mcuy = (p.height + 8 * vmax - 1) / (8 * vmax);
-      for (int c = 0; c < p.ncomp; c++) {
-        if (hmax % p.h_samp[c] || vmax % p.v_samp[c]) return fail(i, SPDL_HJ_ERR_UNSUPPORTED, nullptr);
-        bw[c] = mcux * p.h_samp[c];
-        bh[c] = mcuy * p.v_samp[c];
-        bpm += p.h_samp[c] * p.v_samp[c];
-      }
-      if (bpm > kMaxBpm) return fail(i, SPDL_HJ_ERR_UNSUPPORTED, nullptr);
-      nblocks = (int64_t)mcux * mcuy * bpm;
-    }
-    // the entropy kernel's 32-bit byte offsets into an image's coefficient
-    // lists (4 bytes x 64 entries per block) must not wrap
-    if (nblocks >= (1 << 24)) return fail(i, SPDL_HJ_ERR_UNSUPPORTED, "image too large");
-    d.nblocks = (int)nblocks;
-    d.coef_off = L.total_blocks;
-    L.total_blocks += nblocks;
-    // The source crop: the frame every later step sees (src; the whole frame
-    // without one).  A rectangle that does not resolve refuses its image alone.
-    spdl_hj_rect src{0, 0, p.width, p.height};
-    const bool has_rect = crops && !rect_is_none(crops[i]);
-    int crop_rc = has_rect ? crop_resolve(p, crops[i], &src) : SPDL_HJ_OK;
-    if (crop_rc && crop_rc != SPDL_HJ_ERR_BAD_GEOMETRY) return fail(i, crop_rc, nullptr);
-    if (crop_rc) src = {0, 0, p.width, p.height};
-    d.idct_blocks = d.nblocks;
-    d.src = i;
-    if (hv) {
-      // idct_kernel visits the bounding MCU rectangle of the image's views over
-      // all groups (the whole grid if one of them is the whole frame; no view:
-      // no block).  A rectangle that does not resolve refuses its view alone.
-      const views::Frame f = frame_of(p);
-      const views::Grid grid{hmax, vmax, 0, 0, bpm};
-      views::McuRect bound{0, 0, 0, 0};
-      bool whole = false;
-      for (int q = vstart[i]; q < vstart[i + 1]; q++) {
-        ViewRes& vr = vres[vorder[q]];
-        vr.rc = views::resolve(f, vr.in, &vr.r);
-        if (vr.rc && vr.rc != SPDL_HJ_ERR_BAD_GEOMETRY) return fail(i, vr.rc, nullptr);
-        if (vr.rc) continue;
-        whole = whole || views::rect_is_none(vr.in);
-        views::mcu_union(&bound, views::mcu_rect(grid, vr.r));
-      }
-      if (!whole) {
-        d.idct_blocks = views::idct_blocks(grid, bound);
-        d.reg_mx0 = bound.mx0;
-        d.reg_my0 = bound.my0;
-        d.reg_mw = bound.mw;
-        d.reg_mh = bound.mh;
-        d.reg_mw_magic = idct_div_magic((uint32_t)std::max(bound.mw, 1));
-      }
-    } else if (has_rect && !crop_rc) {
-      // idct_kernel visits the MCUs the crop touches (gray: its blocks)
-      const int mw8 = 8 * hmax, mh8 = 8 * vmax;
-      d.reg_mx0 = src.x / mw8;
-      d.reg_my0 = src.y / mh8;
-      d.reg_mw = (src.x + src.w - 1) / mw8 - d.reg_mx0 + 1;
-      d.reg_mh = (src.y + src.h - 1) / mh8 - d.reg_my0 + 1;
-      d.reg_mw_magic = idct_div_magic((uint32_t)d.reg_mw);
-      d.idct_blocks = d.reg_mw * d.reg_mh * bpm;
-    }
-    if (d.idct_blocks > L.max_blocks) L.max_blocks = d.idct_blocks;
-    for (int c = 0; c < p.ncomp; c++) {
-      d.plane_stride[c] = bw[c] * 8;
-      d.plane_off[c] = L.total_planes;
-      L.total_planes += round_up((int64_t)bw[c] * 8 * bh[c] * 8, 256);
-      // component c's window: origin (x >> log2 hs_c, y >> log2 vs_c), size
-      // ceil(w / hs_c) x ceil(h / vs_c) -- the whole component without a crop
-      const int hsc = p.ncomp == 1 ? 1 : hmax / p.h_samp[c];
-      const int vsc = p.ncomp == 1 ? 1 : vmax / p.v_samp[c];
-      d.win_x[c] = src.x / hsc;
-      d.win_y[c] = src.y / vsc;
-      d.win_w[c] = (src.w + hsc - 1) / hsc;
-      d.win_h[c] = (src.h + vsc - 1) / vsc;
-    }
-    d.seg_cap = (int32_t)(sizes[i] / 2 + 2);
-    d.seg_off = L.total_segs;
-    L.total_segs += d.seg_cap;
-    d.ds_cap = (int32_t)(sizes[i] / kDsChunk + 2);
-    d.ds_off = L.total_ds;
-    L.total_ds += d.ds_cap;
-    d.ds_wg0 = (int32_t)L.ds_wgs;
-    L.ds_wgs += d.ds_cap;
-    d.idct_wg0 = (int32_t)L.idct_wgs;
-    L.idct_wgs += (d.idct_blocks + kIdctThreads - 1) / kIdctThreads;
-    if (d.ds_cap > L.max_chunks) L.max_chunks = d.ds_cap;
-    // size-adaptive entropy decode: a file larger than piece_bytes is
-    // decoded by ceil(size / piece_bytes) workgroups (progressive and
-    // multi-scan images take multiscan_kernel: one)
-    int pieces = 1;
-    if (piece_bytes > 0 && !p.multiscan && sizes[i] > piece_bytes)
-      pieces = (int)std::min<int64_t>(kMaxPieces, (sizes[i] + piece_bytes - 1) / piece_bytes);
-    d.pieces = pieces;
-    d.chain_off = pieces > 1 ? (int32_t)L.chain_granules : 0;
-    if (pieces > 1) {
-      L.chain_granules += (int64_t)pieces * kChainGranules;
-      L.multi.emplace_back(i, p);
-    }
-    // entropy slot state (u32 units): kMaxSlots uint4 + slack per piece
-    d.rec_cap = (int64_t)kMaxSlots * 8 * pieces;
-    d.rec_off = L.total_recs;
-    L.total_recs += d.rec_cap;
-    if (hv) continue;  // (the outputs are the views': their descriptors follow below)
-    if (has_rect) L.all_special = false;  // the full-resolution converters read whole planes
-    if (crop_rc) {
-      refuse(d, crop_rc);
-      continue;
-    }
-    Geom g;
-    int rc = geometry(src.w, src.h, out, &g);
-    if (rc) return fail(i, rc, nullptr);
-    d.dx = g.dx;
-    d.dy = g.dy;
-    d.ow = g.ow;
-    d.oh = g.oh;
-    if (!have_size) {
-      have_size = true;
-      L.ow = g.ow;
-      L.oh = g.oh;
-    } else if (g.ow != L.ow || g.oh != L.oh) {
-      set_err(err, errlen,
-              "all images of a batch must produce the same output size "
-              "(image 0: %dx%d, image %d: %dx%d); pass a resize target",
-              L.ow, L.oh, i, g.ow, g.oh);
-      return SPDL_HJ_ERR_INVALID_ARG;
-    }
-    int64_t px = (int64_t)g.ow * g.oh;
-    if (px > L.max_px) L.max_px = px;
-    if (!plans || out->csc == SPDL_HJ_CSC_JFIF) continue;
-    int hs, vs, mode;
-    if (yuv) {
-      // The frame's own planes: gray8 or yuvj444p / 422p / 420p, every image
-      // in image 0's format.  An image that is not, or whose pad / crop does
-      // not fall on its chroma grid, is refused alone (ImageDesc::refuse): one
-      // workgroup of the output kernel reports it, the others decode.
-      int why = chroma_shifts(p, &hs, &vs);
-      const bool gray = p.ncomp == 1;
-      if (!why && (p.ncomp == 4 || p.color == kColorRgb || hs > 1 || vs > hs))
-        why = SPDL_HJ_ERR_UNSUPPORTED;
-      // (image 0, or the first one after images whose source crop was refused)
-      if (!have_fmt) {
-        have_fmt = true;
-        if (why) return fail(i, why, "no planar output for this frame format");
-        L.yuv_hs = hs;
-        L.yuv_vs = vs;
-        L.yuv_gray = gray;
-      } else if (!why && (hs != L.yuv_hs || vs != L.yuv_vs || gray != L.yuv_gray)) {
-        why = SPDL_HJ_ERR_UNSUPPORTED;
-      }
-      if (!why) why = geometry(src.w, src.h, out, &g, 1 << hs, 1 << vs);
-      if (why) {
-        refuse(d, why);
-        continue;
-      }
-      d.dx = g.dx;
-      d.dy = g.dy;
-      mode = (gray ? kPlanGray : kPlanYuv) | kPlanPlanar;
-    } else {
-      if ((rc = chroma_shifts(p, &hs, &vs))) return fail(i, rc, nullptr);
-      // RGB planes (gbrp; CMYK after the K transform, gbrap) through the luma
-      // filters; YCCK after the transform and YCbCr + K are YCbCr 4:4:4
-      mode = p.ncomp == 1                                        ? kPlanGray
-             : p.color == kColorRgb || p.color == kColorCmyk ? kPlanGbr
-                                                              : kPlanYuv;
-    }
-    const PlanKey key{src.w, src.h, hs, vs, mode, out->resize ? out->filter : 0,
-                      g.sw, g.sh, g.dx, g.dy, g.ow, g.oh};
-    auto plan = plans->get(key, &rc);
-    if (!plan) return fail(i, rc, rc == SPDL_HJ_ERR_BAD_GEOMETRY ? "scale filter too long" : nullptr);
-    auto it = placed.find(plan.get());
-    if (it == placed.end()) {
-      it = placed.emplace(plan.get(), (int64_t)L.tables.size()).first;
-      alive.push_back(plan);
-      L.tables.insert(L.tables.end(), plan->blob.begin(), plan->blob.end());
-    }
-    d.wt_off = it->second;
-    d.sws = plan->d;
-    if (plan->d.pre) {  // hscale_kernel's tiles and rows (hj_sws_tile.h)
-      d.hs_wg0 = (int32_t)L.hs_wgs;
-      d.hs_wgs = hs_tiles(plan->d).wgs;
-      L.hs_wgs += d.hs_wgs;
-      d.hbuf_off = L.total_hbuf;
-      L.total_hbuf += hs_hbuf_size(plan->d);
-    }
-    L.all_special = L.all_special && plan->special;
-    // idct_rgb_kernel's MCU shapes: Y 2x2 or 2x1, U and V 1x1
-    if (p.ncomp == 3 && p.h_samp[0] == 2 && (p.v_samp[0] == 1 || p.v_samp[0] == 2) &&
-        p.h_samp[1] == 1 && p.v_samp[1] == 1 && p.h_samp[2] == 1 && p.v_samp[2] == 1) {
-      const int bpm = 2 * p.v_samp[0] + 2, tw = kFusedThreads / bpm;
-      const int mcux = (p.width + 15) / 16, mcuy = (p.height + 8 * p.v_samp[0] - 1) / (8 * p.v_samp[0]);
-      L.fused_tiles = std::max(L.fused_tiles, (mcux + tw - 1) / tw * mcuy);
-    } else {
-      L.fuse_ok = false;
-    }
-    L.sws_bands = std::max(L.sws_bands, plan->bands);
-    L.sws_chunks = std::max(L.sws_chunks, plan->chunks);
-    d.sws_wg0 = (int32_t)L.sws_wgs;  // flat sws grid: this image's tiles only
-    d.sws_bands = plan->bands;
-    d.sws_chunks = plan->chunks;
-    L.sws_wgs += (int64_t)plan->bands * plan->chunks;
-    L.sws_lds = std::max(L.sws_lds, plan->lds);
-  }
-  if (hv) {
-    // The view descriptors, group by group behind the images': each view a
-    // frame of its own (its window of image `src`'s planes, its geometry, its
-    // plan), tiled in its group's part of the flat sws grid.
-    L.all_special = L.fuse_ok = false;  // (the full-resolution converters read whole planes)
-    std::vector<int32_t> vstatus(vres.size(), SPDL_HJ_OK);
-    int32_t nviews[views::kMaxGroups];
-    views::Slice slice[views::kMaxGroups];
-    for (size_t gi = 0; gi < hv->groups.size(); gi++) nviews[gi] = (int32_t)hv->groups[gi].views.size();
-    views::group_slices(n, nviews, (int)hv->groups.size(), slice);
-    size_t q = 0;
-    for (size_t gi = 0; gi < hv->groups.size(); gi++) {
-      const HeldViews::Group& hg = hv->groups[gi];
-      Layout::Group G;
-      G.out = hg.out;
-      G.out_dev = hg.out_dev;
-      G.first = slice[gi].first;  // (== L.desc.size(): the descriptors are appended in this order)
-      G.count = slice[gi].count;
-      G.sws_wg0 = (int)L.sws_wgs;
-      bool sized = false;
-      for (size_t k = 0; k < hg.views.size(); k++, q++) {
-        const ViewRes& vr = vres[q];
-        const int img = hg.views[k].image;
-        const spdl_hj_image_info& p = infos[img];
-        ImageDesc v = L.desc[img];
-        v.src = img;
-        v.idct_blocks = 0;  // (the front-end and IDCT fields mean nothing here)
-        auto refuse_view = [&](int why) {
-          vstatus[q] = why;
-          if (!L.view_refused) {
-            L.view_refused = why;
-            L.view_refused_group = (int)gi;
-            L.view_refused_index = (int)k;
-          }
-          refuse(v, why);
-          L.desc.push_back(v);
-        };
-        if (vr.rc) {
-          refuse_view(vr.rc);
-          continue;
-        }
-        const views::Frame f = frame_of(p);
-        const views::Grid grid = views::grid_of(f);
-        for (int c = 0; c < p.ncomp; c++) {
-          const views::Window w = views::window(f, grid, vr.r, c);
-          v.win_x[c] = w.x;
-          v.win_y[c] = w.y;
-          v.win_w[c] = w.w;
-          v.win_h[c] = w.h;
-        }
-        Geom g;
-        int rc = geometry(vr.r.w, vr.r.h, &hg.out, &g);
-        if (rc == SPDL_HJ_ERR_BAD_GEOMETRY) {
-          refuse_view(rc);
-          continue;
-        }
-        if (rc) return fail(img, rc, nullptr);
-        if (!sized) {
-          sized = true;
-          G.ow = g.ow;
-          G.oh = g.oh;
-        } else if (g.ow != G.ow || g.oh != G.oh) {
-          set_err(err, errlen,
-                  "all views of a group must produce the same output size "
-                  "(group %zu: %dx%d, view %zu: %dx%d); pass a resize target",
-                  gi, G.ow, G.oh, k, g.ow, g.oh);
-          return SPDL_HJ_ERR_INVALID_ARG;
-        }
-        int hs, vs;
-        if ((rc = chroma_shifts(p, &hs, &vs))) return fail(img, rc, nullptr);
-        const int mode = p.ncomp == 1                                      ? kPlanGray
-                         : p.color == kColorRgb || p.color == kColorCmyk ? kPlanGbr
-                                                                          : kPlanYuv;
-        const PlanKey key{vr.r.w, vr.r.h, hs, vs, mode, hg.out.resize ? hg.out.filter : 0,
-                          g.sw, g.sh, g.dx, g.dy, g.ow, g.oh};
-        auto plan = plans->get(key, &rc);
-        if (!plan && rc == SPDL_HJ_ERR_BAD_GEOMETRY) {  // scale filter too long
-          refuse_view(rc);
-          continue;
-        }
-        if (!plan) return fail(img, rc, nullptr);
-        auto it = placed.find(plan.get());
-        if (it == placed.end()) {
-          it = placed.emplace(plan.get(), (int64_t)L.tables.size()).first;
-          alive.push_back(plan);
-          L.tables.insert(L.tables.end(), plan->blob.begin(), plan->blob.end());
-        }
-        v.dx = g.dx;
-        v.dy = g.dy;
-        v.ow = g.ow;
-        v.oh = g.oh;
-        v.wt_off = it->second;
-        v.sws = plan->d;
-        v.hs_wg0 = v.hs_wgs = 0;
-        v.hbuf_off = 0;
-        if (plan->d.pre) {  // hscale_kernel's tiles and rows, per view
-          v.hs_wg0 = (int32_t)L.hs_wgs;
-          v.hs_wgs = hs_tiles(plan->d).wgs;
-          L.hs_wgs += v.hs_wgs;
-          v.hbuf_off = L.total_hbuf;
-          L.total_hbuf += hs_hbuf_size(plan->d);
-        }
-        v.sws_wg0 = (int32_t)L.sws_wgs;
-        v.sws_bands = plan->bands;
-        v.sws_chunks = plan->chunks;
-        L.sws_wgs += (int64_t)plan->bands * plan->chunks;
-        G.sws_lds = std::max(G.sws_lds, plan->lds);
-        L.desc.push_back(v);
-      }
-      const int64_t per = (int64_t)G.ow * G.oh * 3;
-      const size_t esz = hg.out.dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
-      if ((size_t)(per * G.count) * esz > hg.out_bytes) {
-        set_err(err, errlen, "group %zu: output buffer too small: need %lld bytes, have %zu", gi,
-                (long long)(per * G.count * (int64_t)esz), hg.out_bytes);
-        return SPDL_HJ_ERR_INVALID_ARG;
-      }
-      for (int k = 0; k < G.count; k++) L.desc[G.first + k].out_off = (int64_t)k * per;
-      G.sws_wgs = (int)L.sws_wgs - G.sws_wg0;
-      L.groups.push_back(G);
-    }
-    // (nothing is written before every limit has held)
-    q = 0;
-    for (const HeldViews::Group& hg : hv->groups)
-      for (size_t k = 0; k < hg.views.size(); k++, q++)
-        if (hg.status) hg.status[k] = vstatus[q];
-  }
-  L.out_elems_per_image = (int64_t)L.ow * L.oh * 3;
-  if (yuv)  // Y, then U and V of ceil(ow / hs) x ceil(oh / vs) (gray: Y alone)
-    L.out_elems_per_image =
-        (int64_t)L.ow * L.oh + (L.yuv_gray ? 0
-                                           : 2 * (int64_t)(-((-L.ow) >> L.yuv_hs)) *
-                                                 (-((-L.oh) >> L.yuv_vs)));
-  for (int i = 0; i < n; i++) L.desc[i].out_off = (int64_t)i * L.out_elems_per_image;
-  // entropy work list: the images with the most pieces first (their pieces
-  // start early and in ticket order), each image's pieces in order
-  std::vector<int> order(n);
-  for (int i = 0; i < n; i++) order[i] = i;
-  std::stable_sort(order.begin(), order.end(),
-                   [&](int a, int b) { return L.desc[a].pieces > L.desc[b].pieces; });
-  L.work.clear();
-  for (int i : order)
-    for (int q = 0; q < L.desc[i].pieces; q++) L.work.push_back((uint32_t)i | ((uint32_t)q << 24));
-  return SPDL_HJ_OK;
 }
 
 }  // namespace
@@ -1172,13 +575,34 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
   return SPDL_HJ_OK;
 }
 
+// What a batch runs with besides its layout: its n images' bytes in HBM, the
+// output and the execution stream (exec_stream()).
+struct Submission {
+  const uint8_t* d_bytes;
+  size_t bytes_len;
+  int n;
+  const spdl_hj_output* out;
+  void* out_dev;
+  size_t out_bytes;
+  hipStream_t st;
+  int sync;
+  int32_t* status;
+  bool planes_only = false;             // stop at the planes (no output stage)
+  const spdl_hj_rect* crops = nullptr;  // the batch's source crops, for the retry record
+};
+
 // device pipeline over bytes already in HBM; `slot` provides the descriptor
-// and status staging and is marked done on `st` at the end.  `st` is the
-// execution stream (exec_stream()), the workspace is the slot's lane.
-int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t bytes_len,
-                 const Layout& L, int n, const spdl_hj_output* out, void* out_dev,
-                 size_t out_bytes, hipStream_t st, int sync, int32_t* status, char* err,
-                 size_t errlen, bool planes_only, const spdl_hj_rect* crops = nullptr) {
+// and status staging and is marked done on the stream at the end; the
+// workspace is the slot's lane.
+int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission& sub, char* err,
+                 size_t errlen) {
+  const uint8_t* const d_bytes = sub.d_bytes;
+  const size_t bytes_len = sub.bytes_len, out_bytes = sub.out_bytes;
+  const int n = sub.n;
+  const spdl_hj_output* const out = sub.out;
+  void* const out_dev = sub.out_dev;
+  const hipStream_t st = sub.st;
+  const bool planes_only = sub.planes_only;
   const size_t esz = out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
   const bool by_views = !L.groups.empty();  // (build_layout checked every group's buffer)
   if (!planes_only && !by_views && (size_t)L.out_elems_per_image * n * esz > out_bytes) {
@@ -1367,7 +791,7 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
   R.rect.clear();
   if (!planes_only) {
     for (const auto& m : L.multi) {
-      if (crops) R.rect.push_back(crops[m.first]);
+      if (sub.crops) R.rect.push_back(sub.crops[m.first]);
       R.idx.push_back(m.first);
       R.off.push_back(L.desc[m.first].in_off);
       R.size.push_back(L.desc[m.first].in_size);
@@ -1384,9 +808,9 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const uint8_t* d_bytes, size_t by
   slot.profiled = ctx->profiling;
   slot.profiled_stages = ctx->profile_stages;
   ctx->last_ticket = slot.ticket;
-  if (!sync) return SPDL_HJ_OK;
+  if (!sub.sync) return SPDL_HJ_OK;
   HJ_HIP(hipEventSynchronize(slot.done));
-  const int rc = collect_status(ctx, slot, status, err, errlen);
+  const int rc = collect_status(ctx, slot, sub.status, err, errlen);
   if (!rc && L.view_refused) {  // as a refused image fails a synchronous crop submission
     set_err(err, errlen, "Failed to decode an image. (group %d, view %d: %s)",
             L.view_refused_group, L.view_refused_index, status_str(L.view_refused));
@@ -1428,8 +852,9 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, int k) {
   const size_t errlen = sizeof(err);
   Layout L;
   int32_t st1 = SPDL_HJ_OK;
-  int rc = build_layout(&r.off[k], &r.size[k], &r.info[k], 1, &r.out, ctx->sub_bits, 0, L, &st1,
-                        err, errlen, &ctx->plans, r.rect.empty() ? nullptr : &r.rect[k]);
+  LayoutRequest rq{&r.off[k], &r.size[k], &r.info[k], 1, &r.out, 0, &ctx->plans};
+  rq.crops = r.rect.empty() ? nullptr : &r.rect[k];
+  int rc = plan_batch(rq, L, &st1, err, errlen);
   if (rc) return rc;
   // the spare slot, on the failed batch's lane (its workspace is free: the
   // batch has finished); the caller's last ticket is left as it was
@@ -1444,8 +869,10 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, int k) {
   ctx->handoff_retries++;
   const int64_t idct_wgs = ctx->idct_workgroups;  // (the batch's, not this re-decode's)
   const int64_t ent_wgs = ctx->entropy_workgroups;
-  rc = run_pipeline(ctx, *s, r.bytes, r.len, L, 1, &r.out, r.out_dev + (size_t)r.idx[k] * r.img_bytes,
-                    r.img_bytes, xs, 1, &st1, err, errlen, false);
+  rc = run_pipeline(ctx, *s, L,
+                    {r.bytes, r.len, 1, &r.out, r.out_dev + (size_t)r.idx[k] * r.img_bytes,
+                     r.img_bytes, xs, 1, &st1},
+                    err, errlen);
   ctx->idct_workgroups = idct_wgs;
   ctx->entropy_workgroups = ent_wgs;
   ctx->last_ticket = last;
@@ -1463,18 +890,6 @@ int stage_h2d(spdl_hj_ctx* ctx, Slot& s, size_t total, hipStream_t st, char* err
   HJ_HIP(hipEventRecord(s.h2d_done, ctx->copy));
   HJ_HIP(hipStreamWaitEvent(st, s.h2d_done, 0));
   return SPDL_HJ_OK;
-}
-
-bool valid_output(const spdl_hj_output* o) {
-  // the JFIF conversion has no scaler: full resolution only
-  // ... and the planar output is u8 planes of swscale's scaler alone
-  if (o && o->pix_fmt == SPDL_HJ_FMT_YUV &&
-      (o->dtype != SPDL_HJ_DTYPE_U8 || o->csc != SPDL_HJ_CSC_SWSCALE))
-    return false;
-  return o && o->pix_fmt >= 0 && o->pix_fmt <= SPDL_HJ_FMT_YUV && (o->dtype >= 0 && o->dtype <= 2) &&
-         (o->idct == 0 || o->idct == 1) && (o->filter >= 0 && o->filter <= 2) &&
-         o->aspect >= 0 && o->aspect <= 2 &&
-         (o->csc == SPDL_HJ_CSC_SWSCALE || (o->csc == SPDL_HJ_CSC_JFIF && !o->resize));
 }
 
 // ---- tar (ustar / GNU 'L' long names / pax 'x' path) ------------------------
@@ -1569,6 +984,42 @@ int take_views(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, const void* o
   *hv = held;
   return SPDL_HJ_OK;
 }
+
+// The prologue of the three batch entry points: the crops and views set for
+// this submission come off the context at once, whatever becomes of the call.
+struct Held {
+  std::vector<spdl_hj_rect> rects;
+  HeldViews views;
+  const spdl_hj_rect* crops = nullptr;  // null: none
+  const HeldViews* hv = nullptr;
+  int crc = 0, vrc = 0;
+  Held(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, const void* out_dev, size_t out_bytes,
+       char* err, size_t errlen) {
+    if (!ctx) return;
+    crc = take_crops(ctx, n, out, &rects, &crops, err, errlen);
+    vrc = take_views(ctx, n, out, out_dev, out_bytes, !rects.empty(), &views, &hv, err, errlen);
+  }
+  // The submission's first error: the views', then the call's own arguments
+  // (args_ok: the entry point's pointers and sizes), then the crops'
+  int check(bool args_ok, int n, const spdl_hj_output* out, const void* out_dev, char* err,
+            size_t errlen) const {
+    if (vrc) return vrc;
+    if (!args_ok || n <= 0 || !valid_output(out) || (!out_dev && !hv)) {
+      set_err(err, errlen, n <= 0 ? "the batch is empty" : "invalid argument");
+      return SPDL_HJ_ERR_INVALID_ARG;
+    }
+    return crc;  // (its text is still in err)
+  }
+};
+
+// An acquired staging slot is released (ticket 0) if its call ends before
+// run_pipeline has taken it
+struct SlotRelease {
+  Slot* s;
+  ~SlotRelease() {
+    if (s) s->ticket = 0;
+  }
+};
 
 }  // namespace
 
@@ -1697,19 +1148,8 @@ void spdl_hj_destroy(spdl_hj_ctx* c) {
 int spdl_hj_decode_batch(spdl_hj_ctx* ctx, const uint8_t* const* data, const size_t* sizes,
                          int32_t n, const spdl_hj_output* out, void* out_dev, size_t out_bytes,
                          void* stream, int32_t sync, int32_t* status, char* err, size_t errlen) {
-  std::vector<spdl_hj_rect> held;
-  const spdl_hj_rect* crops = nullptr;
-  const int crc = ctx ? take_crops(ctx, n, out, &held, &crops, err, errlen) : 0;
-  HeldViews vheld;
-  const HeldViews* hv = nullptr;
-  const int vrc = ctx ? take_views(ctx, n, out, out_dev, out_bytes, !held.empty(), &vheld, &hv,
-                                   err, errlen) : 0;
-  if (vrc) return vrc;
-  if (!ctx || !data || !sizes || n <= 0 || !valid_output(out) || (!out_dev && !hv)) {
-    set_err(err, errlen, n <= 0 ? "the batch is empty" : "invalid argument");
-    return SPDL_HJ_ERR_INVALID_ARG;
-  }
-  if (crc) return crc;
+  const Held held(ctx, n, out, out_dev, out_bytes, err, errlen);
+  if (int rc = held.check(ctx && data && sizes, n, out, out_dev, err, errlen)) return rc;
   DeviceGuard g(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   std::vector<spdl_hj_image_info> infos(n);
@@ -1733,8 +1173,9 @@ int spdl_hj_decode_batch(spdl_hj_ctx* ctx, const uint8_t* const* data, const siz
   }
   Layout L;
   // (views: one entropy workgroup per image, so no hand-off can give up)
-  int rc = build_layout(offs.data(), szs.data(), infos.data(), n, out, ctx->sub_bits,
-                        hv ? 0 : ctx->piece_bytes, L, status, err, errlen, &ctx->plans, crops, hv);
+  int rc = plan_batch({offs.data(), szs.data(), infos.data(), n, out,
+                       held.hv ? 0 : ctx->piece_bytes, &ctx->plans, held.crops, held.hv},
+                      L, status, err, errlen);
   if (rc) return rc;
   L.ms_side = prog;
   L.ms_known = true;
@@ -1747,8 +1188,10 @@ int spdl_hj_decode_batch(spdl_hj_ctx* ctx, const uint8_t* const* data, const siz
   rc = exec_stream(ctx, *s, st, &xs, err, errlen);
   if (!rc) rc = stage_h2d(ctx, *s, (size_t)total, xs, err, errlen);
   if (rc) return rc;
-  return run_pipeline(ctx, *s, static_cast<const uint8_t*>(s->bytes.p), (size_t)total, L, n, out,
-                      out_dev, out_bytes, xs, sync, status, err, errlen, false, crops);
+  return run_pipeline(ctx, *s, L,
+                      {static_cast<const uint8_t*>(s->bytes.p), (size_t)total, n, out, out_dev,
+                       out_bytes, xs, sync, status, false, held.crops},
+                      err, errlen);
 }
 
 int spdl_hj_decode_batch_device(spdl_hj_ctx* ctx, const uint8_t* dev_data, size_t dev_bytes,
@@ -1757,25 +1200,15 @@ int spdl_hj_decode_batch_device(spdl_hj_ctx* ctx, const uint8_t* dev_data, size_
                                 const spdl_hj_output* out, void* out_dev, size_t out_bytes,
                                 void* stream, int32_t sync, int32_t* status, char* err,
                                 size_t errlen) {
-  std::vector<spdl_hj_rect> held;
-  const spdl_hj_rect* crops = nullptr;
-  const int crc = ctx ? take_crops(ctx, n, out, &held, &crops, err, errlen) : 0;
-  HeldViews vheld;
-  const HeldViews* hv = nullptr;
-  const int vrc = ctx ? take_views(ctx, n, out, out_dev, out_bytes, !held.empty(), &vheld, &hv,
-                                   err, errlen) : 0;
-  if (vrc) return vrc;
-  if (!ctx || !dev_data || !offsets || !sizes || !infos || n <= 0 || !valid_output(out) ||
-      (!out_dev && !hv)) {
-    set_err(err, errlen, n <= 0 ? "the batch is empty" : "invalid argument");
-    return SPDL_HJ_ERR_INVALID_ARG;
-  }
-  if (crc) return crc;
+  const Held held(ctx, n, out, out_dev, out_bytes, err, errlen);
+  if (int rc = held.check(ctx && dev_data && offsets && sizes && infos, n, out, out_dev, err, errlen))
+    return rc;
   DeviceGuard g(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout L;
-  int rc = build_layout(offsets, sizes, infos, n, out, ctx->sub_bits, hv ? 0 : ctx->piece_bytes, L,
-                        status, err, errlen, &ctx->plans, crops, hv);
+  int rc = plan_batch({offsets, sizes, infos, n, out, held.hv ? 0 : ctx->piece_bytes, &ctx->plans,
+                       held.crops, held.hv},
+                      L, status, err, errlen);
   if (rc) return rc;
   // the caller's probe says which files take the multi-scan path (ABI 5)
   for (int i = 0; i < n; i++) L.ms_side = L.ms_side || infos[i].multiscan != 0;
@@ -1787,8 +1220,10 @@ int spdl_hj_decode_batch_device(spdl_hj_ctx* ctx, const uint8_t* dev_data, size_
   rc = exec_stream(ctx, *s, st, &xs, err, errlen);
   if (rc) return rc;
   mark(ctx, *s, 0, xs);
-  return run_pipeline(ctx, *s, dev_data, dev_bytes, L, n, out, out_dev, out_bytes, xs, sync,
-                      status, err, errlen, false, crops);
+  return run_pipeline(ctx, *s, L,
+                      {dev_data, dev_bytes, n, out, out_dev, out_bytes, xs, sync, status, false,
+                       held.crops},
+                      err, errlen);
 }
 
 int64_t spdl_hj_last_ticket(spdl_hj_ctx* ctx) { return ctx ? ctx->last_ticket : 0; }
@@ -1888,33 +1323,17 @@ int spdl_hj_decode_staged(spdl_hj_ctx* ctx, int64_t ticket, size_t len, const in
                           const int64_t* sizes, int32_t n, const spdl_hj_output* out,
                           void* out_dev, size_t out_bytes, void* stream, int32_t sync,
                           int32_t* status, char* err, size_t errlen) {
-  std::vector<spdl_hj_rect> held;
-  const spdl_hj_rect* crops = nullptr;
-  const int crc = ctx ? take_crops(ctx, n, out, &held, &crops, err, errlen) : 0;
-  HeldViews vheld;
-  const HeldViews* hv = nullptr;
-  const int vrc = ctx ? take_views(ctx, n, out, out_dev, out_bytes, !held.empty(), &vheld, &hv,
-                                   err, errlen) : 0;
+  const Held held(ctx, n, out, out_dev, out_bytes, err, errlen);
   Slot* s = ctx ? find_slot(ctx, ticket) : nullptr;
   if (!s || !s->staged) {
     set_err(err, errlen, "ticket %lld does not name an acquired staging slot", (long long)ticket);
     return SPDL_HJ_ERR_INVALID_ARG;
   }
   s->staged = false;  // the slot is consumed whatever happens below
-  if (vrc) {
-    s->ticket = 0;
-    return vrc;
-  }
-  if (!offsets || !sizes || n <= 0 || !valid_output(out) || (!out_dev && !hv) ||
-      len + 512 > s->pin_in.cap) {
-    set_err(err, errlen, n <= 0 ? "the batch is empty" : "invalid argument");
-    s->ticket = 0;
-    return SPDL_HJ_ERR_INVALID_ARG;
-  }
-  if (crc) {
-    s->ticket = 0;
-    return crc;
-  }
+  SlotRelease release{s};
+  if (int rc = held.check(offsets && sizes && len + 512 <= s->pin_in.cap, n, out, out_dev, err,
+                          errlen))
+    return rc;
   DeviceGuard g(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const uint8_t* host = static_cast<const uint8_t*>(s->pin_in.p);
@@ -1928,17 +1347,14 @@ int spdl_hj_decode_staged(spdl_hj_ctx* ctx, int64_t ticket, size_t len, const in
     if (status) status[i] = rc;
     if (rc) {
       set_err(err, errlen, "Failed to decode an image. (image %d: %s)", i, status_str(rc));
-      s->ticket = 0;
       return rc;
     }
   }
   Layout L;
-  int rc = build_layout(offsets, sizes, infos.data(), n, out, ctx->sub_bits,
-                        hv ? 0 : ctx->piece_bytes, L, status, err, errlen, &ctx->plans, crops, hv);
-  if (rc) {
-    s->ticket = 0;
-    return rc;
-  }
+  int rc = plan_batch({offsets, sizes, infos.data(), n, out, held.hv ? 0 : ctx->piece_bytes,
+                       &ctx->plans, held.crops, held.hv},
+                      L, status, err, errlen);
+  if (rc) return rc;
   L.ms_side = prog;
   L.ms_known = true;
   memset(static_cast<uint8_t*>(s->pin_in.p) + len, 0, 512);  // tail read slack
@@ -1946,8 +1362,11 @@ int spdl_hj_decode_staged(spdl_hj_ctx* ctx, int64_t ticket, size_t len, const in
   rc = exec_stream(ctx, *s, st, &xs, err, errlen);
   if (!rc) rc = stage_h2d(ctx, *s, len + 512, xs, err, errlen);
   if (rc) return rc;
-  return run_pipeline(ctx, *s, static_cast<const uint8_t*>(s->bytes.p), len + 512, L, n, out,
-                      out_dev, out_bytes, xs, sync, status, err, errlen, false, crops);
+  release.s = nullptr;  // (the slot is the pipeline's from here)
+  return run_pipeline(ctx, *s, L,
+                      {static_cast<const uint8_t*>(s->bytes.p), len + 512, n, out, out_dev,
+                       out_bytes, xs, sync, status, false, held.crops},
+                      err, errlen);
 }
 
 int spdl_hj_tar_index(const uint8_t* data, size_t size, size_t start, int32_t max_entries,
@@ -2060,8 +1479,7 @@ int spdl_hj_decode_planes(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
   // (a piece hand-off that gave up: once more in one entropy workgroup)
   for (int64_t piece_bytes : {ctx->piece_bytes, (int64_t)0}) {
     L = Layout{};
-    rc = build_layout(&off, &sz, &info, 1, &o, ctx->sub_bits, piece_bytes, L, nullptr, err, errlen,
-                      nullptr);
+    rc = plan_batch({&off, &sz, &info, 1, &o, piece_bytes, nullptr}, L, nullptr, err, errlen);
     if (rc) return rc;
     rc = acquire_slot(ctx, &s, err, errlen);
     if (rc) return rc;
@@ -2071,8 +1489,10 @@ int spdl_hj_decode_planes(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
     rc = exec_stream(ctx, *s, st, &xs, err, errlen);
     if (!rc) rc = stage_h2d(ctx, *s, (size_t)total, xs, err, errlen);
     if (rc) return rc;
-    rc = run_pipeline(ctx, *s, static_cast<const uint8_t*>(s->bytes.p), (size_t)total, L, 1, &o,
-                      nullptr, 0, xs, 1, nullptr, err, errlen, true);
+    rc = run_pipeline(ctx, *s, L,
+                      {static_cast<const uint8_t*>(s->bytes.p), (size_t)total, 1, &o, nullptr, 0, xs,
+                       1, nullptr, true},
+                      err, errlen);
     if (rc != SPDL_HJ_ERR_HANDOFF || piece_bytes == 0) break;
     ctx->handoff_retries++;
   }
@@ -2080,11 +1500,9 @@ int spdl_hj_decode_planes(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
   Workspace& W = ctx->ws[s->ticket % ctx->lanes];
   st = xs;
   const ImageDesc& d = L.desc[0];
-  int hmax = 1, vmax = 1;
-  for (int c = 0; c < info.ncomp; c++) {
-    hmax = info.h_samp[c] > hmax ? info.h_samp[c] : hmax;
-    vmax = info.v_samp[c] > vmax ? info.v_samp[c] : vmax;
-  }
+  FrameBlocks fb;
+  (void)frame_blocks(info, &fb);  // (the layout was built: the frame is supported)
+  const int hmax = fb.grid.hmax, vmax = fb.grid.vmax;
   for (int c = 0; c < info.ncomp; c++) {
     int w = info.ncomp == 1 ? info.width : (info.width * info.h_samp[c] + hmax - 1) / hmax;
     int h = info.ncomp == 1 ? info.height : (info.height * info.v_samp[c] + vmax - 1) / vmax;
@@ -2115,7 +1533,7 @@ int spdl_hj_debug_entropy(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
   spdl_hj_output o{};
   int64_t off = 0, sz = (int64_t)size, total = round_up(sz + 64, 256);
   Layout L;
-  rc = build_layout(&off, &sz, &info, 1, &o, ctx->sub_bits, ctx->piece_bytes, L, nullptr, err, errlen, nullptr);
+  rc = plan_batch({&off, &sz, &info, 1, &o, ctx->piece_bytes, nullptr}, L, nullptr, err, errlen);
   if (rc) return rc;
   Slot* s = nullptr;
   rc = acquire_slot(ctx, &s, err, errlen);
@@ -2127,8 +1545,10 @@ int spdl_hj_debug_entropy(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
   rc = exec_stream(ctx, *s, st, &xs, err, errlen);
   if (!rc) rc = stage_h2d(ctx, *s, (size_t)total, xs, err, errlen);
   if (rc) return rc;
-  (void)run_pipeline(ctx, *s, static_cast<const uint8_t*>(s->bytes.p), (size_t)total, L, 1, &o,
-                     nullptr, 0, xs, 1, nullptr, err, errlen, true);
+  (void)run_pipeline(ctx, *s, L,
+                     {static_cast<const uint8_t*>(s->bytes.p), (size_t)total, 1, &o, nullptr, 0, xs,
+                      1, nullptr, true},
+                     err, errlen);
   Workspace& W = ctx->ws[s->ticket % ctx->lanes];
   ImageInfo hi;
   HJ_HIP(hipMemcpy(&hi, W.info.p, sizeof(ImageInfo), hipMemcpyDeviceToHost));
