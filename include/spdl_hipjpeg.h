@@ -313,6 +313,44 @@ typedef struct {
 } spdl_hj_view_group;
 int spdl_hj_set_views(spdl_hj_ctx* ctx, const spdl_hj_view_group* groups, int32_t ngroups);
 
+/* ---- output flips (additive in ABI 7: one function, one enum; a binding
+ * finds it by symbol) -----------------------------------------------------------
+ * The random horizontal flip of a training recipe, in the store of the output
+ * kernel.  The flip is the LAST node of the chain: libavfilter's
+ *   scale=...[,pad=...][,crop=...][,format=...],hflip / vflip
+ * where format negotiates back to scale, so hflip and vflip run on the final
+ * pixel format.  With ow x oh the output size, for the bits that are set:
+ *   packed and planar RGB / BGR   out'(x, y) = out(ow - 1 - x, oh - 1 - y)
+ *   SPDL_HJ_FMT_YUV               every plane mirrored by its own width and
+ *                                 height (cw = ceil(ow / hs), ch = ceil(oh / vs)),
+ *                                 as vf_hflip / vf_vflip do; gray8 its one plane
+ * for every dtype, with and without resize, with source crops, and in views.
+ * Pad bytes belong to the image and move with it.  An image or view whose flip
+ * is 0 is byte-identical to the same submission without flips; a failed image
+ * or a refused view stays untouched.
+ *
+ * Not offered: a flip AHEAD of the scale.  Its pixels differ -- swscale's
+ * filter positions are not mirror-symmetric, and the chroma of an odd width
+ * pairs differently -- and nothing here pins them.
+ *
+ * Consumption follows spdl_hj_set_crops: the next spdl_hj_decode_batch,
+ * _device or _staged call consumes the flips, whether or not it succeeds;
+ * flips == NULL or n == 0 clears them; the library copies the array;
+ * spdl_hj_decode_planes and spdl_hj_debug_entropy neither use nor clear them.
+ * A plain or cropped submission takes n == the call's n.  A views submission
+ * takes one entry per view, the groups concatenated in group order (a refused
+ * view keeps its entry: the indexing never shifts).  A wrong count, a value
+ * above 3, or csc = JFIF with any non-zero flip give SPDL_HJ_ERR_INVALID_ARG
+ * from the consuming call, with nothing written.
+ *
+ * Cost.  With resize != 0 and for SPDL_HJ_FMT_YUV the flip is address
+ * arithmetic in the kernel that stores the tile.  A full-resolution (resize ==
+ * 0) RGB / BGR u8 submission with any flip set runs the generic output kernel
+ * ("output_path" 1, byte-identical pixels) instead of the unscaled converters,
+ * which is slower; all-zero flips keep the fast path. */
+enum { SPDL_HJ_FLIP_H = 1, SPDL_HJ_FLIP_V = 2 }; /* both: a rotation by 180 degrees */
+int spdl_hj_set_flips(spdl_hj_ctx* ctx, const uint8_t* flips, int32_t n);
+
 /* ABI version of the loaded library (== SPDL_HJ_ABI_VERSION). */
 int spdl_hj_abi_version(void);
 

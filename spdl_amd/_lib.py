@@ -56,6 +56,7 @@ EXPORTED = (
     "spdl_hj_crop_rect",
     "spdl_hj_set_crops",
     "spdl_hj_set_views",
+    "spdl_hj_set_flips",
 )
 
 
@@ -87,6 +88,23 @@ def _rect(r) -> Rect:
     x, y, w, h = r
     return Rect(CROP_CENTER if x is None else int(x), CROP_CENTER if y is None else int(y),
                 int(w), int(h))
+
+
+FLIP_H, FLIP_V = 1, 2  # SPDL_HJ_FLIP_H, SPDL_HJ_FLIP_V
+_FLIP_NAMES = {None: 0, "": 0, "h": FLIP_H, "v": FLIP_V, "hv": FLIP_H | FLIP_V,
+               "vh": FLIP_H | FLIP_V}
+
+
+def _flip(f) -> int:
+    """An output flip, ``0..3`` (bit 0 horizontal, bit 1 vertical), ``"h"``,
+    ``"v"``, ``"hv"`` or ``None`` -> SPDL_HJ_FLIP_* bits."""
+    if isinstance(f, (str, type(None))):
+        if f not in _FLIP_NAMES:
+            raise ValueError(f"a flip is 0..3, 'h', 'v', 'hv' or None, not {f!r}")
+        return _FLIP_NAMES[f]
+    if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f <= 3:
+        raise ValueError(f"a flip is 0..3, 'h', 'v', 'hv' or None, not {f!r}")
+    return int(f)
 
 
 def _view_rect(r) -> Rect:
@@ -142,6 +160,11 @@ class Output:
     or ``y`` of ``None`` is centred; include/spdl_hipjpeg.h "source crop").
     It is no field of the C output spec: the decoder passes it on through
     ``spdl_hj_set_crops``.
+
+    ``flip`` (``0..3``, ``"h"``, ``"v"``, ``"hv"``) mirrors every image's
+    output: the last node of the chain, ``...,hflip`` / ``vflip`` after scale,
+    pad and crop (include/spdl_hipjpeg.h "output flips").  It travels through
+    ``spdl_hj_set_flips`` as well.
     """
 
     pix_fmt: str = "rgb"
@@ -163,6 +186,7 @@ class Output:
     # yuvj -> rgb24); "jfif": IJG libjpeg tables, nearest chroma (full-res)
     csc: str = "swscale"
     src_crop: tuple | None = None
+    flip: int | str | None = None
 
     def to_c(self) -> OutputSpec:
         if self.pix_fmt not in PIX_FMTS:
@@ -231,8 +255,10 @@ class ViewGroupSpec(ctypes.Structure):  # spdl_hj_view_group
 
 class ViewGroup:
     """One group of a views submission (include/spdl_hipjpeg.h "views"): the
-    output chain ``out``, the views ``[(image, rect_or_None), ...]`` and the
-    device buffer ``[len(views), ...]`` they are written to in view order.
+    output chain ``out``, the views ``[(image, rect_or_None), ...]`` or
+    ``[(image, rect_or_None, flip), ...]`` and the device buffer
+    ``[len(views), ...]`` they are written to in view order.  A view without a
+    flip of its own has ``out.flip``.
     After the consuming call, ``statuses`` holds the per-view codes (0, or the
     status of a view the host refused alone); a view is valid when its own
     status and its image's are both 0."""
@@ -244,14 +270,20 @@ class ViewGroup:
             raise ValueError("views= and Output.src_crop are exclusive")
         self.out, self.out_ptr, self.out_bytes = out, int(out_ptr), int(out_bytes)
         self.views = []
+        self.flips = []  # per view, SPDL_HJ_FLIP_* bits
         for v in views:
+            what = f"a view is (image, rect_or_None) or (image, rect_or_None, flip 0..3), not {v!r}"
             try:
-                image, rect = v
+                image, rect, *flip = v
+                if len(flip) > 1:
+                    raise ValueError
+                flip = _flip(flip[0] if flip else out.flip)
             except (TypeError, ValueError):
-                raise ValueError(f"a view is (image, rect_or_None), not {v!r}") from None
+                raise ValueError(what) from None
             if isinstance(image, bool) or not isinstance(image, int):
-                raise ValueError(f"a view is (image, rect_or_None), not {v!r}")
+                raise ValueError(what)
             self.views.append((image, _view_rect(rect)))
+            self.flips.append(flip)
         n = len(self.views)
         self._views = (View * max(n, 1))(*[View(i, r) for i, r in self.views])
         self._status = (ctypes.c_int32 * max(n, 1))()
@@ -276,6 +308,12 @@ def _check_views(views, out: Output, crops, out_ptr, out_bytes) -> None:
     if out_ptr or out_bytes:
         raise ValueError("with views= the call's out_ptr and out_bytes must be 0: "
                          "every group has its own buffer")
+
+
+def _has_flips(out: Output, flips, views) -> bool:
+    """The submission names a flip somewhere (else no flip call is made)."""
+    return flips is not None or out.flip is not None or \
+        (views is not None and any(any(g.flips) for g in views))
 
 
 _LIB = None
@@ -349,6 +387,8 @@ def lib() -> ctypes.CDLL:
             L.spdl_hj_set_crops.argtypes = [vp, vp, i32]
         if hasattr(L, "spdl_hj_set_views"):  # (additive in ABI 7 as well)
             L.spdl_hj_set_views.argtypes = [vp, ctypes.POINTER(ViewGroupSpec), i32]
+        if hasattr(L, "spdl_hj_set_flips"):  # (likewise)
+            L.spdl_hj_set_flips.argtypes = [vp, vp, i32]
         ver = L.spdl_hj_abi_version()
         # (an explicitly chosen older build, ABI >= 5, loads for A/B runs)
         if ver != ABI_VERSION and not (os.environ.get("SPDL_AMD_LIB") and 5 <= ver < ABI_VERSION):
@@ -588,6 +628,37 @@ class Decoder:
         if lib().spdl_hj_set_views(self._h, arr if groups else None, len(groups)):
             raise ValueError("invalid views")
 
+    def set_flips(self, flips) -> None:
+        """The output flips of the next batch submission (spdl_hj_set_flips):
+        a sequence of ``0..3`` / ``"h"`` / ``"v"`` / ``"hv"`` / ``None``, one
+        per image, or per view with views; ``None`` or an empty one clears
+        them.  ``bytes`` go to the library as they are."""
+        if not isinstance(flips, (bytes, bytearray)):
+            flips = bytes(_flip(f) for f in flips) if flips is not None else b""
+        arr = (ctypes.c_uint8 * max(len(flips), 1))(*flips)
+        if lib().spdl_hj_set_flips(self._h, arr if flips else None, len(flips)):
+            raise ValueError("invalid flips")
+
+    def _flips(self, out: Output, flips, n: int, views=None) -> None:
+        """Hand the submission's flips to the context: ``flips`` per image, or
+        ``out.flip`` for every image; with views, each view's own.  A
+        submission without a flip makes no call."""
+        if views is not None:
+            if flips is not None:
+                raise ValueError("with views= a flip belongs to its view: (image, rect, flip)")
+            per = [f for g in views for f in g.flips]
+            if any(per):
+                self.set_flips(bytes(per))
+            return
+        if flips is not None and out.flip is not None:
+            raise ValueError("flips= and Output.flip are exclusive")
+        if flips is None and _flip(out.flip):
+            flips = [out.flip] * n
+        if flips is not None:
+            if len(flips) != n:
+                raise ValueError(f"{len(flips)} flips for a batch of {n} images")
+            self.set_flips(flips)
+
     def _crops(self, out: Output, crops, n: int) -> None:
         """Hand the submission's rectangles to the context: ``crops`` per
         image, or ``out.src_crop`` for every image."""
@@ -601,7 +672,8 @@ class Decoder:
             self.set_crops(crops)
 
     def decode_batch(self, datas, out: Output, out_ptr: int, out_bytes: int, stream=None,
-                     sync: bool = True, check: bool = True, crops=None, views=None) -> list[int]:
+                     sync: bool = True, check: bool = True, crops=None, views=None,
+                     flips=None) -> list[int]:
         """Per-image statuses.  A failed image raises RuntimeError unless
         ``check`` is False (synchronous calls), which returns the statuses.
         ``crops``: a source crop ``(x, y, w, h)`` or ``None`` per image.
@@ -609,7 +681,8 @@ class Decoder:
         image from one decode; ``out_ptr`` and ``out_bytes`` must then be 0 and
         of ``out`` only ``idct`` is used.  The per-view statuses are each
         group's ``statuses``; with ``check=False`` a refused view does not
-        raise either."""
+        raise either.  ``flips``: an output flip (``0..3``, ``"h"``, ``"v"``,
+        ``"hv"`` or ``None``) per image; with views, each view carries its own."""
         n = len(datas)
         if n == 0:
             raise RuntimeError("Failed to decode an image. (the batch is empty)")
@@ -618,6 +691,8 @@ class Decoder:
             self.set_views(views)
         else:
             self._crops(out, crops, n)
+        if _has_flips(out, flips, views):
+            self._flips(out, flips, n, views)
         # borrowed for the duration of the call, no copy (the reference binds
         # memoryviews as string_views, src/spdl/io/lib/cuda/memoryview_utils.h:17-20)
         keep = []
@@ -642,7 +717,7 @@ class Decoder:
     def decode_batch_device(self, dev_ptr: int, dev_bytes: int, offsets, sizes, infos,
                             out: Output, out_ptr: int, out_bytes: int, stream=None,
                             sync: bool = True, crops=None, check: bool = True,
-                            views=None) -> list[int]:
+                            views=None, flips=None) -> list[int]:
         """``offsets``/``sizes``: sequences or int64 numpy arrays; ``infos``: a
         sequence of ImageInfo or a prebuilt ``(ImageInfo * n)`` array (pass the
         same objects again to skip re-marshalling on every call)."""
@@ -654,6 +729,8 @@ class Decoder:
             self.set_views(views)
         elif crops is not None or out.src_crop is not None:
             self._crops(out, crops, n)
+        if _has_flips(out, flips, views):
+            self._flips(out, flips, n, views)
         offs = np.ascontiguousarray(offsets, dtype=np.int64)
         szs = np.ascontiguousarray(sizes, dtype=np.int64)
         inf = infos if isinstance(infos, ctypes.Array) else (ImageInfo * n)(*infos)
@@ -726,13 +803,15 @@ class Decoder:
 
     def decode_staged(self, ticket: int, nbytes: int, offsets, sizes, out: Output, out_ptr: int,
                       out_bytes: int, stream=None, sync: bool = True, crops=None,
-                      check: bool = True, views=None) -> list[int]:
+                      check: bool = True, views=None, flips=None) -> list[int]:
         n = len(offsets)
         if views is not None:
             _check_views(views, out, crops, out_ptr, out_bytes)
             self.set_views(views)
         else:
             self._crops(out, crops, n)
+        if _has_flips(out, flips, views):
+            self._flips(out, flips, n, views)
         offs = (ctypes.c_int64 * n)(*offsets)
         szs = (ctypes.c_int64 * n)(*sizes)
         status = (ctypes.c_int32 * max(n, 1))()

@@ -277,6 +277,7 @@ struct Slot {
     std::vector<int64_t> off, size;
     std::vector<spdl_hj_image_info> info;
     std::vector<spdl_hj_rect> rect;  // their source crops (empty: the batch had none)
+    std::vector<uint8_t> flip;       // their output flips (empty: the batch had none)
   } retry;
 };
 
@@ -386,6 +387,8 @@ struct spdl_hj_ctx {
   int64_t handoff_retries = 0;
   // spdl_hj_set_crops: the source crops of the next batch submission
   std::vector<spdl_hj_rect> crops;
+  // spdl_hj_set_flips: the output flips of the next batch submission
+  std::vector<uint8_t> flips;
   int64_t idct_workgroups = 0;  // IDCT workgroups the last submission launched
   int64_t entropy_workgroups = 0;  // ... and its entropy work items (images, or their pieces)
   // spdl_hj_set_views: the views of the next batch submission
@@ -556,8 +559,11 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
   HJ_HIP(grow(W.clean, (size_t)max_end + 512, st, &b->clean));
   HJ_HIP(grow(W.segs, (size_t)L.total_segs * 4 + 64, st, &b->segs));
   HJ_HIP(grow(W.dschunks, (size_t)L.total_ds * sizeof(DsChunk) + 64, st, &b->dschunks));
-  HJ_HIP(grow(W.desc, sizeof(ImageDesc) * b->ndesc + sizeof(uint32_t) * b->nwork, st, &b->desc));
-  b->work = reinterpret_cast<uint32_t*>(b->desc + b->ndesc);  // the work list follows the descriptors
+  // (the work list follows the descriptors, a flipped submission's flags the work list)
+  HJ_HIP(grow(W.desc, sizeof(ImageDesc) * b->ndesc + sizeof(uint32_t) * b->nwork + L.flips.size(),
+              st, &b->desc));
+  b->work = reinterpret_cast<uint32_t*>(b->desc + b->ndesc);
+  b->flips = L.flips.empty() ? nullptr : reinterpret_cast<const uint8_t*>(b->work + b->nwork);
   HJ_HIP(grow(W.chain, (size_t)(kChainHead + L.chain_granules) * 8 + 64, st, &b->chain));
   HJ_HIP(grow(W.maps, (size_t)(L.ds_wgs + L.idct_wgs + L.hs_wgs + L.sws_wgs) * 4 + 64, st,
               &b->ds_map));
@@ -589,6 +595,7 @@ struct Submission {
   int32_t* status;
   bool planes_only = false;             // stop at the planes (no output stage)
   const spdl_hj_rect* crops = nullptr;  // the batch's source crops, for the retry record
+  const uint8_t* flips = nullptr;       // ... and its output flips (one per image)
 };
 
 // device pipeline over bytes already in HBM; `slot` provides the descriptor
@@ -641,13 +648,17 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   const bool ds_flat = use_flat(L.ds_wgs, L.max_chunks);
   const bool idct_flat = use_flat(L.idct_wgs, (L.max_blocks + kIdctThreads - 1) / kIdctThreads);
   const bool sws_flat = use_flat(L.sws_wgs, (int64_t)L.sws_bands * L.sws_chunks);
-  const size_t desc_bytes = sizeof(ImageDesc) * B.ndesc + sizeof(uint32_t) * B.nwork;  // + work list
+  // + work list, + the flags of a flipped submission (one byte per descriptor)
+  const size_t work_end = sizeof(ImageDesc) * B.ndesc + sizeof(uint32_t) * B.nwork;
+  const size_t desc_bytes = work_end + L.flips.size();
   HJ_HIP(slot.pin_desc.ensure(desc_bytes));
   HJ_HIP(slot.pin_status.ensure(sizeof(int32_t) * n));
   slot.n = n;
   memcpy(slot.pin_desc.p, L.desc.data(), sizeof(ImageDesc) * B.ndesc);
   memcpy(static_cast<ImageDesc*>(slot.pin_desc.p) + B.ndesc, L.work.data(),
          sizeof(uint32_t) * B.nwork);
+  if (B.flips)
+    memcpy(static_cast<uint8_t*>(slot.pin_desc.p) + work_end, L.flips.data(), L.flips.size());
   // the batch's swscale tables travel with the descriptors
   const bool swscale = !planes_only && out->csc == SPDL_HJ_CSC_SWSCALE;
   const size_t tb = swscale ? L.tables.size() * 4 : 0;
@@ -657,6 +668,12 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   if (!hs) {
     HJ_HIP(hipMemcpyAsync(B.desc, slot.pin_desc.p, desc_bytes, hipMemcpyHostToDevice, st));
     if (tb) HJ_HIP(hipMemcpyAsync(B.wts, slot.pin_tables.p, tb, hipMemcpyHostToDevice, st));
+  } else if (B.flips) {
+    // (parse_kernel brings over the descriptors and the work list alone: the
+    // flags behind them take one small copy from the same pinned pages)
+    HJ_HIP(hipMemcpyAsync(const_cast<uint8_t*>(B.flips),
+                          static_cast<const uint8_t*>(slot.pin_desc.p) + work_end, L.flips.size(),
+                          hipMemcpyHostToDevice, st));
   }
   mark(ctx, slot, 1, st);
   HJ_HIP(launch_parse(B, hs ? static_cast<const ImageDesc*>(slot.pin_desc.dev) : nullptr,
@@ -789,9 +806,11 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   R.size.clear();
   R.info.clear();
   R.rect.clear();
+  R.flip.clear();
   if (!planes_only) {
     for (const auto& m : L.multi) {
       if (sub.crops) R.rect.push_back(sub.crops[m.first]);
+      if (sub.flips) R.flip.push_back(sub.flips[m.first]);
       R.idx.push_back(m.first);
       R.off.push_back(L.desc[m.first].in_off);
       R.size.push_back(L.desc[m.first].in_size);
@@ -854,6 +873,8 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, int k) {
   int32_t st1 = SPDL_HJ_OK;
   LayoutRequest rq{&r.off[k], &r.size[k], &r.info[k], 1, &r.out, 0, &ctx->plans};
   rq.crops = r.rect.empty() ? nullptr : &r.rect[k];
+  rq.flips = r.flip.empty() ? nullptr : &r.flip[k];
+  rq.nflips = r.flip.empty() ? 0 : 1;
   int rc = plan_batch(rq, L, &st1, err, errlen);
   if (rc) return rc;
   // the spare slot, on the failed batch's lane (its workspace is free: the
@@ -990,12 +1011,22 @@ int take_views(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, const void* o
 struct Held {
   std::vector<spdl_hj_rect> rects;
   HeldViews views;
+  std::vector<uint8_t> flipv;
   const spdl_hj_rect* crops = nullptr;  // null: none
   const HeldViews* hv = nullptr;
+  // (their count, values and chain are the planner's to check: build_layout)
+  const uint8_t* flips = nullptr;
+  int64_t nflips = 0;
   int crc = 0, vrc = 0;
   Held(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, const void* out_dev, size_t out_bytes,
        char* err, size_t errlen) {
     if (!ctx) return;
+    flipv.swap(ctx->flips);
+    ctx->flips.clear();
+    if (!flipv.empty()) {
+      flips = flipv.data();
+      nflips = (int64_t)flipv.size();
+    }
     crc = take_crops(ctx, n, out, &rects, &crops, err, errlen);
     vrc = take_views(ctx, n, out, out_dev, out_bytes, !rects.empty(), &views, &hv, err, errlen);
   }
@@ -1075,6 +1106,13 @@ int spdl_hj_set_crops(spdl_hj_ctx* ctx, const spdl_hj_rect* rects, int32_t n) {
   if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
   ctx->crops.clear();
   if (rects && n > 0) ctx->crops.assign(rects, rects + n);
+  return SPDL_HJ_OK;
+}
+
+int spdl_hj_set_flips(spdl_hj_ctx* ctx, const uint8_t* flips, int32_t n) {
+  if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
+  ctx->flips.clear();
+  if (flips && n > 0) ctx->flips.assign(flips, flips + n);
   return SPDL_HJ_OK;
 }
 
@@ -1174,7 +1212,8 @@ int spdl_hj_decode_batch(spdl_hj_ctx* ctx, const uint8_t* const* data, const siz
   Layout L;
   // (views: one entropy workgroup per image, so no hand-off can give up)
   int rc = plan_batch({offs.data(), szs.data(), infos.data(), n, out,
-                       held.hv ? 0 : ctx->piece_bytes, &ctx->plans, held.crops, held.hv},
+                       held.hv ? 0 : ctx->piece_bytes, &ctx->plans, held.crops, held.hv,
+                       held.flips, held.nflips},
                       L, status, err, errlen);
   if (rc) return rc;
   L.ms_side = prog;
@@ -1190,7 +1229,8 @@ int spdl_hj_decode_batch(spdl_hj_ctx* ctx, const uint8_t* const* data, const siz
   if (rc) return rc;
   return run_pipeline(ctx, *s, L,
                       {static_cast<const uint8_t*>(s->bytes.p), (size_t)total, n, out, out_dev,
-                       out_bytes, xs, sync, status, false, held.crops},
+                       out_bytes, xs, sync, status, false, held.crops,
+                       held.hv ? nullptr : held.flips},
                       err, errlen);
 }
 
@@ -1207,7 +1247,7 @@ int spdl_hj_decode_batch_device(spdl_hj_ctx* ctx, const uint8_t* dev_data, size_
   hipStream_t st = static_cast<hipStream_t>(stream);
   Layout L;
   int rc = plan_batch({offsets, sizes, infos, n, out, held.hv ? 0 : ctx->piece_bytes, &ctx->plans,
-                       held.crops, held.hv},
+                       held.crops, held.hv, held.flips, held.nflips},
                       L, status, err, errlen);
   if (rc) return rc;
   // the caller's probe says which files take the multi-scan path (ABI 5)
@@ -1222,7 +1262,7 @@ int spdl_hj_decode_batch_device(spdl_hj_ctx* ctx, const uint8_t* dev_data, size_
   mark(ctx, *s, 0, xs);
   return run_pipeline(ctx, *s, L,
                       {dev_data, dev_bytes, n, out, out_dev, out_bytes, xs, sync, status, false,
-                       held.crops},
+                       held.crops, held.hv ? nullptr : held.flips},
                       err, errlen);
 }
 
@@ -1352,7 +1392,7 @@ int spdl_hj_decode_staged(spdl_hj_ctx* ctx, int64_t ticket, size_t len, const in
   }
   Layout L;
   int rc = plan_batch({offsets, sizes, infos.data(), n, out, held.hv ? 0 : ctx->piece_bytes,
-                       &ctx->plans, held.crops, held.hv},
+                       &ctx->plans, held.crops, held.hv, held.flips, held.nflips},
                       L, status, err, errlen);
   if (rc) return rc;
   L.ms_side = prog;
@@ -1365,7 +1405,8 @@ int spdl_hj_decode_staged(spdl_hj_ctx* ctx, int64_t ticket, size_t len, const in
   release.s = nullptr;  // (the slot is the pipeline's from here)
   return run_pipeline(ctx, *s, L,
                       {static_cast<const uint8_t*>(s->bytes.p), len + 512, n, out, out_dev,
-                       out_bytes, xs, sync, status, false, held.crops},
+                       out_bytes, xs, sync, status, false, held.crops,
+                       held.hv ? nullptr : held.flips},
                       err, errlen);
 }
 

@@ -5380,7 +5380,8 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
                                                   int32_t* __restrict__ host_status,
                                                   const int16_t* __restrict__ hbuf,
                                                   const uint32_t* __restrict__ sws_map,
-                                                  const int wg0) {
+                                                  const int wg0,
+                                                  const uint8_t* __restrict__ flips) {
   extern __shared__ __attribute__((aligned(16))) int16_t sws_lds[];
   // (band, chunk, image) grid, or a flat grid over every image's own tiles
   // (sws_map: workgroup -> image) when the batch's plans differ widely
@@ -5413,6 +5414,12 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
   const int yo1 = win.yo1, xo1 = win.xo1, th = yo1 - yo0, tw = xo1 - xo0;
   const int ys0 = win.ys0, ys1 = win.ys1, xs0 = win.xs0, xs1 = win.xs1;
   const bool content = win.content;
+  // the output flip of this image or view (spdl_hj_set_flips), one byte per
+  // descriptor and uniform over the workgroup; null: the submission has none.
+  // It changes where the tile lands and where a pixel sits in it, nothing
+  // else (hj_sws_tile.h tile_flip)
+  const int flip = flips ? __builtin_amdgcn_readfirstlane((int)flips[img]) : 0;
+  const TileFlip tf = tile_flip(xo0, xo1, yo0, yo1, dd.ow, dd.oh, flip);
   const bool planar = p.pix_fmt == 0 || p.pix_fmt == 1;
   const bool swap = p.pix_fmt == 1 || p.pix_fmt == 3;
   const bool u8 = p.dtype == 0;
@@ -5463,21 +5470,22 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
   // one pixel, its three values in the output's channel order
   auto putc = [&](int xo, int yo, int c0v, int c1v, int c2v) {
     const int cv[3] = {c0v, c1v, c2v};
+    const int tx = tf.tx(xo), ty = tf.ty(yo);  // (in the mirrored tile)
     if (u8) {
 #pragma unroll
       for (int ch = 0; ch < 3; ch++) {
         const int v = cv[ch];
-        const int ti = planar ? (ch * th + (yo - yo0)) * tw + (xo - xo0)
-                              : ((yo - yo0) * tw + (xo - xo0)) * 3 + ch;
+        const int ti = planar ? (ch * th + ty) * tw + tx : (ty * tw + tx) * 3 + ch;
         tile[ti] = (uint8_t)v;
       }
       return;
     }
+    const int mx = tf.mx0 + tx, my = tf.my0 + ty;  // (in the flipped output)
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) {
       const int v = cv[ch];
       const int64_t oi =
-          dd.out_off + (planar ? ch * pl + (int64_t)yo * dd.ow + xo : ((int64_t)yo * dd.ow + xo) * 3 + ch);
+          dd.out_off + (planar ? ch * pl + (int64_t)my * dd.ow + mx : ((int64_t)my * dd.ow + mx) * 3 + ch);
       float f = __fdiv_rn((float)v, 255.0f);
       f = __fsub_rn(f, p.mean[ch]);
       f = __fdiv_rn(f, p.std[ch]);
@@ -5519,14 +5527,16 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
         }
         const int bpp = planar ? 1 : 3, np_ = planar ? 3 : 1;
         const int ps = th * tw;  // bytes of a planar tile's plane
+        // the rectangle's first row and column in the mirrored tile
+        const int r0 = min(tf.ty(ya), tf.ty(yb - 1)), k0 = min(tf.tx(xa), tf.tx(xb - 1));
         if (xb - xa == tw) {     // whole rows: one run per plane
           for (int pc = 0; pc < np_; pc++)
-            zrun((pc * ps + (ya - yo0) * tw) * bpp, (yb - ya) * tw * bpp, tid, nt);
+            zrun((pc * ps + r0 * tw) * bpp, (yb - ya) * tw * bpp, tid, nt);
           return;
         }
         for (int yo = ya + wave; yo < yb; yo += nw)
           for (int pc = 0; pc < np_; pc++)
-            zrun((pc * ps + (yo - yo0) * tw + (xa - xo0)) * bpp, (xb - xa) * bpp, lane, 64);
+            zrun((pc * ps + tf.ty(yo) * tw + k0) * bpp, (xb - xa) * bpp, lane, 64);
       };
       fill(yo0, cy0, xo0, xo1);
       fill(cy1, yo1, xo0, xo1);
@@ -5747,13 +5757,15 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
   if (!u8 || (p.debug_mask & kAblSwsStore)) return;
   __syncthreads();
   // the u8 tile out with wide stores: whole rows of an interleaved image are
-  // one contiguous run, planar ones three
+  // one contiguous run, planar ones three (a flipped output: the same tile at
+  // its mirrored origin)
   const int nplane = planar ? 3 : 1;
   const int run = planar ? th * tw : th * tw * 3;  // bytes per plane run
   for (int pc = 0; pc < nplane; pc++) {
     const uint8_t* src = tile + pc * run;
     uint8_t* dst = static_cast<uint8_t*>(out) + dd.out_off + pc * pl +
-                   (planar ? (int64_t)yo0 * dd.ow + xo0 : ((int64_t)yo0 * dd.ow + xo0) * 3);
+                   (planar ? (int64_t)tf.my0 * dd.ow + tf.mx0
+                           : ((int64_t)tf.my0 * dd.ow + tf.mx0) * 3);
     if (tw == dd.ow && ((uintptr_t)dst & 15) == 0 && (run & 15) == 0) {
       for (int i = tid; i < run / 16; i += nt)
         reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
@@ -5786,7 +5798,9 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
 // general: a run of the tile (the whole tile when it spans the plane's
 // width, else one row) sits in LDS at its destination's offset within 16
 // bytes, so after a head of single bytes both sides are 16-byte aligned for
-// dwordx4 stores, and a tail of single bytes ends it.
+// dwordx4 stores, and a tail of single bytes ends it.  A flipped image
+// (spdl_hj_set_flips) has that destination, and so that offset, from the
+// tile's mirrored origin.
 __global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restrict__ planes,
                                                          const ImageDesc* __restrict__ desc,
                                                          const ImageInfo* __restrict__ infos,
@@ -5794,7 +5808,8 @@ __global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restri
                                                          uint8_t* __restrict__ out,
                                                          int32_t* __restrict__ host_status,
                                                          const int16_t* __restrict__ hbuf,
-                                                         const uint32_t* __restrict__ sws_map) {
+                                                         const uint32_t* __restrict__ sws_map,
+                                                         const uint8_t* __restrict__ flips) {
   extern __shared__ __attribute__((aligned(16))) int16_t yuv_lds[];
   const int img = (int)sws_map[blockIdx.x], tid = threadIdx.x, nt = blockDim.x;
   const ImageDesc& dd = desc[img];
@@ -5831,6 +5846,11 @@ __global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restri
   const int ys0 = win.ys0, ys1 = win.ys1, xs0 = win.xs0, xs1 = win.xs1;
   const bool content = win.content;
   const int ncl = content ? xs1 - xs0 : 0;
+  // the image's output flip (as in sws_kernel): every plane is mirrored by its
+  // own width and height, so the tile of this plane lands at its mirrored
+  // origin in the plane and its pixels at their mirrored tile coordinates
+  const int flip = flips ? __builtin_amdgcn_readfirstlane((int)flips[img]) : 0;
+  const TileFlip tf = tile_flip(xo0, xo1, yo0, yo1, W, H, flip);
   const int32_t* T = pool + dd.wt_off;
   const int32_t* vpos = T + s.off[luma ? kVlPos : kVcPos];
   const uint32_t* vco = reinterpret_cast<const uint32_t*>(T + s.off[luma ? kVlCoef : kVcCoef]);
@@ -5847,7 +5867,7 @@ __global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restri
   uint8_t* tile = reinterpret_cast<uint8_t*>(yuv_lds) + lay.tile;
   // the tile's destination: one run when the tile spans the plane's width
   const int64_t pbase = dd.out_off + (luma ? 0 : (int64_t)dd.ow * dd.oh + (int64_t)(c - 1) * cw * ch);
-  uint8_t* dst = out + pbase + (int64_t)yo0 * W + xo0;
+  uint8_t* dst = out + pbase + (int64_t)tf.my0 * W + tf.mx0;
   const bool whole = tw == W;
   const int nrun = whole ? 1 : th, runlen = whole ? th * W : tw;
   const int pitch = lay.pitch;  // LDS bytes between the runs of a chunked tile
@@ -5858,7 +5878,7 @@ __global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restri
   // pad: tile pixels outside the scaled content
   for (int i = tid; i < th * tw; i += nt) {
     const int r = i / tw, k = i - r * tw;
-    const int ys = yo0 + r - pdy, xs = xo0 + k - pdx;
+    const int ys = tf.sy(r) - pdy, xs = tf.sx(k) - pdx;
     if (ys < 0 || ys >= psh || xs < 0 || xs >= psw) tile[tpos(r, k)] = (uint8_t)padv;
   }
   if (content && s.pre) {
@@ -5877,10 +5897,10 @@ __global__ void __launch_bounds__(256) yuv_planes_kernel(const uint8_t* __restri
     // row's first source row and taps are uniform: scalar loads)
     for (int cl = tid; cl < ncl; cl += nt) {
       const uint32_t* col = reinterpret_cast<const uint32_t*>(hcol + cl * cst);
-      const int k = xs0 + cl + pdx - xo0;
+      const int k = tf.tx(xs0 + cl + pdx);
       for (int ys = ys0; ys < ys1; ys++) {
         const int v = ((1 << 18) + vdot_pairs(col, vpos[ys] - r0, vco + (int64_t)ys * vnp, vnp)) >> 19;
-        tile[tpos(ys + pdy - yo0, k)] = (uint8_t)clip_i8(v);
+        tile[tpos(tf.ty(ys + pdy), k)] = (uint8_t)clip_i8(v);
       }
     }
   }
@@ -6332,7 +6352,7 @@ hipError_t launch_sws(const BatchBuffers& b, void* out, const BatchParams& p, bo
   launch_hscale(b, hs_wgs, st);
   const dim3 grid = flat ? dim3(sws_wgs) : dim3(bands, chunks, b.n);
   hipLaunchKernelGGL(sws_kernel, grid, dim3(256), lds_bytes, st, b.planes, b.desc, b.infos, b.wts,
-                     out, p, host_status, b.hbuf, flat ? b.sws_map : nullptr, wg0);
+                     out, p, host_status, b.hbuf, flat ? b.sws_map : nullptr, wg0, b.flips);
   return hipGetLastError();
 }
 hipError_t launch_yuv_planes(const BatchBuffers& b, void* out, int sws_wgs, int lds_bytes,
@@ -6340,7 +6360,8 @@ hipError_t launch_yuv_planes(const BatchBuffers& b, void* out, int sws_wgs, int 
   launch_hscale(b, hs_wgs, st);
   // (always the flat grid: every image's own tiles, three planes each)
   hipLaunchKernelGGL(yuv_planes_kernel, dim3(sws_wgs), dim3(256), lds_bytes, st, b.planes, b.desc,
-                     b.infos, b.wts, static_cast<uint8_t*>(out), host_status, b.hbuf, b.sws_map);
+                     b.infos, b.wts, static_cast<uint8_t*>(out), host_status, b.hbuf, b.sws_map,
+                     b.flips);
   return hipGetLastError();
 }
 

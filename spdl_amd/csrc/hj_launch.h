@@ -32,6 +32,10 @@ struct BatchBuffers {
   // (ImageDesc::src).  The front-end kernels launch over n; parse_kernel also
   // brings the views' descriptors over and maps their output workgroups.
   int ndesc;
+  // output flips (spdl_hj_set_flips): one byte per descriptor behind the work
+  // list; null when the submission sets none -- sws_kernel and
+  // yuv_planes_kernel then load nothing
+  const uint8_t* flips;
 };
 
 // parse_kernel + lut_kernel.  host_desc (descriptors, then the work list) and

@@ -566,6 +566,52 @@ struct Planner {
     return SPDL_HJ_OK;
   }
 
+  // The flips of the submission against its count, values and chain; nothing
+  // has been planned or written yet
+  int check_flips() {
+    if (!rq.flips) return SPDL_HJ_OK;
+    int64_t want = rq.n;
+    if (rq.views) {
+      want = 0;
+      for (const auto& g : rq.views->groups) want += (int64_t)g.views.size();
+    }
+    res.rc = SPDL_HJ_ERR_INVALID_ARG;
+    if (rq.nflips != want) {
+      snprintf(res.err, sizeof(res.err), "spdl_hj_set_flips gave %lld flips for %lld %s",
+               (long long)rq.nflips, (long long)want,
+               rq.views ? "views" : "images");
+      return res.rc;
+    }
+    bool any = false;
+    for (int64_t i = 0; i < want; i++) {
+      if (rq.flips[i] > 3) {
+        snprintf(res.err, sizeof(res.err), "spdl_hj_set_flips: flip %lld is %d (0 to 3)",
+                 (long long)i, (int)rq.flips[i]);
+        return res.rc;
+      }
+      any = any || rq.flips[i];
+    }
+    if (any && rq.out->csc == SPDL_HJ_CSC_JFIF) {
+      snprintf(res.err, sizeof(res.err), "a flip needs csc = swscale");
+      return res.rc;
+    }
+    res.rc = SPDL_HJ_OK;
+    return SPDL_HJ_OK;
+  }
+
+  // One flag per descriptor, once every descriptor stands; none when every
+  // flip is 0.  A flipped full-resolution batch takes the generic output
+  // kernel (the unscaled converters do not flip).
+  void place_flips() {
+    if (!rq.flips) return;
+    bool any = false;
+    for (int64_t i = 0; i < rq.nflips; i++) any = any || rq.flips[i];
+    if (!any) return;
+    L.flips.assign(L.desc.size(), 0);
+    std::copy(rq.flips, rq.flips + rq.nflips, L.flips.begin() + (rq.views ? rq.n : 0));
+    L.all_special = false;
+  }
+
   // Output offsets and the entropy work list, once every descriptor stands
   void finish() {
     const int n = rq.n;
@@ -594,12 +640,14 @@ struct Planner {
 
 LayoutResult build_layout(const LayoutRequest& rq, Layout& L) {
   Planner P{rq, L};
+  if (P.check_flips()) return P.res;
   L.desc.assign(rq.n, ImageDesc{});
   if (rq.views) P.index_views();
   for (int i = 0; i < rq.n; i++)
     if (P.plan_image(i)) return P.res;
   if (rq.views && P.plan_views()) return P.res;
   P.finish();
+  P.place_flips();
   return P.res;
 }
 

@@ -104,6 +104,11 @@ struct Layout {
     int ow = 0, oh = 0;              // every view's output size
   };
   std::vector<Group> groups;
+  // Output flips (spdl_hj_set_flips): one byte per descriptor (SPDL_HJ_FLIP_*;
+  // in a views submission 0 for the n image descriptors, the views carry
+  // theirs).  Empty when no flip of the submission is set: such a submission
+  // is the path without flips exactly.
+  std::vector<uint8_t> flips;
   int view_refused = 0;  // the first status the host gave a view alone (0: none)
   int view_refused_group = 0, view_refused_index = 0;
 };
@@ -128,7 +133,9 @@ struct HeldViews {
 // the batch's bytes with their probes.  piece_bytes: the size from which a
 // file is decoded by several entropy workgroups (0: never).  plans == nullptr:
 // no output stage (the raw planes surface).  crops (n rectangles) and views
-// are optional and exclude each other.
+// are optional and exclude each other.  flips (nflips bytes, SPDL_HJ_FLIP_*):
+// optional, one per image, or with views one per view, the groups
+// concatenated in group order.
 struct LayoutRequest {
   const int64_t* offsets;
   const int64_t* sizes;
@@ -139,6 +146,8 @@ struct LayoutRequest {
   PlanCache* plans;
   const spdl_hj_rect* crops = nullptr;
   const HeldViews* views = nullptr;
+  const uint8_t* flips = nullptr;
+  int64_t nflips = 0;
 };
 
 // rc, and on failure its text and the image it is the status of (-1: none --

@@ -29,6 +29,29 @@ inline HJ_HD SwsWindow sws_window(int yo0, int xo0, int rb, int col_chunk, int d
   return {yo1, xo1, ys0, ys1, xs0, xs1, ys0 < ys1 && xs0 < xs1};
 }
 
+// Output flips (spdl_hj_set_flips; bit 0 horizontal, bit 1 vertical): the
+// flip is the last node of the chain, so it changes no pixel, only where the
+// tile and each pixel in it land.  The tile [xo0, xo1) x [yo0, yo1) of the
+// unflipped W x H box is the tile at (mx0, my0), of the same size, of the
+// flipped one: mx0 = W - xo1, my0 = H - yo1 for a set bit.  Output pixel
+// (xo, yo) of the unflipped box has the tile coordinate (tx(xo), ty(yo)) there
+// -- (v ^ mask) + base: mask 0 and base -xo0 without the flip, mask -1 and base
+// xo1 with it, which is xo1 - 1 - xo -- and the box coordinate mx0 + tx(xo).
+// The inverse, from a tile coordinate back to the unflipped box, is sx / sy.
+struct TileFlip {
+  int mx0, my0;  // the mirrored tile's origin in the box
+  int xm, xb, ym, yb;
+  HJ_HD int tx(int xo) const { return (xo ^ xm) + xb; }
+  HJ_HD int ty(int yo) const { return (yo ^ ym) + yb; }
+  HJ_HD int sx(int k) const { return (k - xb) ^ xm; }
+  HJ_HD int sy(int r) const { return (r - yb) ^ ym; }
+};
+inline HJ_HD TileFlip tile_flip(int xo0, int xo1, int yo0, int yo1, int W, int H, int flip) {
+  const bool fh = flip & 1, fv = flip & 2;
+  return {fh ? W - xo1 : xo0, fv ? H - yo1 : yo0, fh ? -1 : 0, fh ? xo1 : -xo0,
+          fv ? -1 : 0,        fv ? yo1 : -yo0};
+}
+
 // The chroma columns under the luma columns [xs0, xs1) (xs0 < xs1): one per
 // column with SWS_FULL_CHR_H_INT, else one per pixel pair.
 struct SwsChromaCols {

@@ -88,14 +88,14 @@ def _alloc_out(cfg: CUDAConfig, shape, dtype) -> CUDABuffer:
 
 
 def _decode(datas: list, out: Output, cfg: CUDAConfig, shape_per_image, batched: bool,
-            dtype=torch.uint8, crops=None) -> CUDABuffer:
+            dtype=torch.uint8, crops=None, flips=None) -> CUDABuffer:
     n = len(datas)
     shape = (n, *shape_per_image) if batched else tuple(shape_per_image)
     buf = _alloc_out(cfg, shape, dtype)
     dec = _lib.thread_decoder(cfg.device_index)
     nbytes = int(np.prod(shape)) * (1 if dtype == torch.uint8 else 2)
     dec.decode_batch(datas, out, buf.data_ptr(), nbytes, stream=_stream(cfg), sync=True,
-                     crops=crops)
+                     crops=crops, flips=flips)
     return buf
 
 
@@ -256,6 +256,7 @@ def load_image_batch(
     std=(0.229, 0.224, 0.225),
     norm_dtype: str = "float16",
     crops=None,
+    flips=None,
     **kwargs,
 ):
     """Batch load images into one ``[B,H,W,3]`` buffer with the FFmpeg filter
@@ -277,7 +278,14 @@ def load_image_batch(
     chain -- RandomResizedCrop's per-image rectangles with ``width=224,
     height=224``; ``x`` or ``y`` of ``None`` is centred.  Exclusive with a
     positioned ``crop`` node ahead of ``scale`` in ``filter_desc``, which
-    crops every image alike."""
+    crops every image alike.
+
+    ``flips`` (an extension as well): one output flip per image -- ``0..3``
+    (bit 0 horizontal, bit 1 vertical), ``"h"``, ``"v"``, ``"hv"`` or ``None``
+    -- applied to the chain's result, as ``hflip`` / ``vflip`` at the end of
+    ``filter_desc`` do for every image alike (exclusive with those); a
+    RandomHorizontalFlip in the decode's own store.  A full-resolution batch
+    with a flip takes the generic output kernel."""
     if not srcs:
         raise ValueError("`srcs` must not be empty.")
     storage = kwargs.pop("storage", None)
@@ -295,6 +303,12 @@ def load_image_batch(
             raise ValueError(f"{len(crops)} crops for {len(srcs)} images")
         if filter_desc is None:
             raise ValueError("crops= needs a filter chain (width / height, filter_desc or pix_fmt)")
+    if flips is not None:
+        flips = [_lib._flip(f) for f in flips]
+        if len(flips) != len(srcs):
+            raise ValueError(f"{len(flips)} flips for {len(srcs)} images")
+        if filter_desc is None:
+            raise ValueError("flips= needs a filter chain (width / height, filter_desc or pix_fmt)")
     if filter_desc is None:
         # no scale and no output format: the decoder's own planes, batched as
         # the reference's convert_frames stacks them ([B, 3, H, W] yuvj444p,
@@ -325,6 +339,8 @@ def load_image_batch(
     out = parse_image_filter(filter_desc, default_pix_fmt=pix_fmt)
     if crops is not None and out.src_crop is not None:
         raise ValueError("crops= and a source crop in filter_desc are exclusive")
+    if flips is not None and out.flip is not None:
+        raise ValueError("flips= and hflip / vflip in filter_desc are exclusive")
     if normalize:
         if out.pix_fmt == "yuv":
             raise ValueError("normalize=True needs an RGB pix_fmt; pix_fmt=None keeps the "
@@ -348,6 +364,8 @@ def load_image_batch(
     info = _lib.get_image_info(datas[0])
     if crops is not None:
         crops = [crops[i] for i in keep]
+    if flips is not None:
+        flips = [flips[i] for i in keep]
     src = _src_size(info, crops[0] if crops is not None else out.src_crop)
     ow, oh = _lib.output_size(*src, out)
     dtype = out.torch_dtype
@@ -356,7 +374,7 @@ def load_image_batch(
     else:
         shape = _shape(out, ow, oh)
     try:
-        buf = _decode(datas, out, cfg, shape, True, dtype=dtype, crops=crops)
+        buf = _decode(datas, out, cfg, shape, True, dtype=dtype, crops=crops, flips=flips)
     except RuntimeError:
         if strict:
             raise
@@ -365,7 +383,8 @@ def load_image_batch(
         for k, d in enumerate(datas):
             try:
                 good.append(_decode([d], out, cfg, shape, True, dtype=dtype,
-                                    crops=None if crops is None else [crops[k]]))
+                                    crops=None if crops is None else [crops[k]],
+                                    flips=None if flips is None else [flips[k]]))
             except RuntimeError as err:
                 _LG.error("Failed to decode an image: %s", err)
         if not good:
@@ -382,7 +401,7 @@ def load_image_batch(
 
 
 _VIEW_GROUP_KEYS = ("width", "height", "scale_algo", "scale_mode", "pix_fmt", "normalize", "dtype",
-                    "mean", "std", "crops")
+                    "mean", "std", "crops", "flips")
 
 
 def _view_group_output(g) -> Output:
@@ -424,7 +443,9 @@ def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = 
     ``dtype`` ("float16" / "bfloat16"), ``mean``, ``std`` -- plus
     ``crops=[[rect, ...] per image]``: the source rectangles ``(x, y, w, h)``
     (``None``: the whole frame) this group takes of each image, any number,
-    none included.  At most four groups.
+    none included.  At most four groups.  ``flips=[[flip, ...] per image]``,
+    parallel to ``crops``, mirrors single views (``0..3``, ``"h"``, ``"v"``,
+    ``"hv"`` or ``None``; left out: no view of the group is flipped).
 
     Returns one ``(buffer, image_indices)`` per group: ``buffer`` is
     ``[rows, H, W, 3]`` (``[rows, 3, H, W]`` planar) with rows in (image, rect)
@@ -449,6 +470,13 @@ def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = 
                 raise ValueError("crops= is a list of rectangles per image")
             for r in rects:
                 _lib._view_rect(r)
+        if g.get("flips") is not None:
+            per_flip = [list(f) for f in g["flips"]]
+            if [len(f) for f in per_flip] != [len(list(r)) for r in per_image]:
+                raise ValueError("flips= is parallel to crops=: one flip per rectangle")
+            for f in per_flip:
+                for v in f:
+                    _lib._flip(v)
     cfg = device_config
     datas, keep, infos = [], [], []
     for i, s in enumerate(srcs):
@@ -468,10 +496,11 @@ def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = 
     vgroups, bufs, rows = [], [], []
     for g, out in zip(groups, outs):
         per_image = list(g["crops"])
+        per_flip = None if g.get("flips") is None else [list(f) for f in g["flips"]]
         views, src_of, size = [], [], None
         for k, i in enumerate(keep):
-            for r in per_image[i]:
-                views.append((k, r))
+            for j, r in enumerate(per_image[i]):
+                views.append((k, r) if per_flip is None else (k, r, per_flip[i][j]))
                 src_of.append(i)
                 if size is None:
                     rc, rr = _lib.crop_rect(infos[k], r)
@@ -553,6 +582,7 @@ def load_image(
     filter_desc: str | None = _FILTER_DESC_DEFAULT,
     device_config: CUDAConfig | None = None,
     pix_fmt: str | None = "rgb24",
+    flip=None,
     **kwargs,
 ):
     """Single image.  ``filter_desc=None`` returns the decoded planes in the
@@ -561,14 +591,19 @@ def load_image(
     ``[3, H, W]`` yuvj444p, ``[H, W, 1]`` gray; see :func:`_native_planes`);
     ``pix_fmt=None`` with a scale / pad / crop chain returns the same layout
     of the scaled planes (the chain runs on the frame's own format);
-    otherwise RGB per the filter."""
+    otherwise RGB per the filter.  ``flip`` (an extension; ``0..3``, ``"h"``,
+    ``"v"``, ``"hv"``) mirrors the chain's result, as ``hflip`` / ``vflip`` at
+    the end of ``filter_desc`` do (exclusive with those)."""
     kwargs.pop("name", None)  # only names the source in FFmpeg demux errors
     _ignore_ffmpeg_configs(kwargs)
     if kwargs:
         raise TypeError(f"unexpected arguments: {sorted(kwargs)}")
     cfg = device_config or _default_config()
     data = _read(src)
+    flip = _lib._flip(flip)
     if filter_desc is None:
+        if flip:
+            raise ValueError("flip= needs a filter chain (filter_desc or pix_fmt)")
         dec = _lib.thread_decoder(cfg.device_index)
         arr = _native_planes(dec.decode_planes(data, stream=_stream(cfg)), data)
         if device_config is not None:
@@ -577,6 +612,10 @@ def load_image(
     if filter_desc == _FILTER_DESC_DEFAULT:
         filter_desc = get_video_filter_desc(pix_fmt=pix_fmt)
     out = parse_image_filter(filter_desc, default_pix_fmt=pix_fmt)
+    if flip:
+        if out.flip is not None:
+            raise ValueError("flip= and hflip / vflip in filter_desc are exclusive")
+        out = Output(**{**out.__dict__, "flip": flip})
     info = _lib.get_image_info(data)
     src = _src_size(info, out.src_crop)
     if out.pix_fmt == "yuv":  # pix_fmt=None, no format node: the frame's planes

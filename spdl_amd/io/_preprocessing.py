@@ -98,17 +98,40 @@ def parse_image_filter(filter_desc: str | None, default_pix_fmt: str | None = "r
     """Translate an image filter chain into an :class:`Output` spec.
 
     ``default_pix_fmt=None``: a chain without a ``format`` node keeps the
-    decoder's own planar format (``pix_fmt="yuv"``), as libavfilter does."""
+    decoder's own planar format (``pix_fmt="yuv"``), as libavfilter does.
+
+    ``hflip`` / ``vflip`` are taken as the chain's last geometry nodes: after
+    ``scale`` and after the last ``pad`` / ``crop``, before or after ``format``
+    (``Output.flip``; repeated nodes toggle).  Anywhere else their pixels would
+    differ from the store-time flip, and they are refused."""
     spec = dict(pix_fmt=default_pix_fmt or "yuv", resize=False)
     if not filter_desc:
         return Output(**spec)
     have_scale = have_pad = False
+    flip = 0
     for part in filter_desc.split(","):
         part = part.strip()
         if not part:
             continue
         name, _, args = part.partition("=")
         kv = _kv(args)
+        if name in ("hflip", "vflip"):
+            if args:
+                raise ValueError(f"{name} takes no options: {part}")
+            if not have_scale:
+                raise ValueError(
+                    f"{name} ahead of scale is not supported: the pixels would differ from a flip "
+                    "of the scaled image (swscale's filter positions are not mirror-symmetric and "
+                    "odd-width chroma pairs differently); put it after scale, pad and crop, or "
+                    "pass flips= for a full-resolution decode")
+            flip ^= 1 if name == "hflip" else 2
+            continue
+        if flip and name in ("scale", "pad", "crop"):
+            raise ValueError(
+                f"hflip / vflip ahead of {name} is not supported: the pixels would differ from a "
+                "flip of the final image (the filter positions of a later scale, and the odd "
+                "remainder of a centred pad or crop, are not mirror-symmetric); put the flip "
+                "after the last scale, pad and crop")
         if name == "scale":
             # (negative sizes: vf_scale's -1 / -n, resolved by the library)
             w, h = int(kv.get("w", 0)), int(kv.get("h", 0))
@@ -165,4 +188,6 @@ def parse_image_filter(filter_desc: str | None, default_pix_fmt: str | None = "r
             spec["pix_fmt"] = pf
         else:
             raise ValueError(f"filter `{name}` is not supported by the image decode stage")
+    if flip:
+        spec["flip"] = flip
     return Output(**spec)
