@@ -686,6 +686,35 @@ class Decoder:
         n = len(datas)
         if n == 0:
             raise RuntimeError("Failed to decode an image. (the batch is empty)")
+        status = (ctypes.c_int32 * n)()
+
+        def call(err):
+            # borrowed for the duration of the call, no copy (the reference binds
+            # memoryviews as string_views, src/spdl/io/lib/cuda/memoryview_utils.h:17-20)
+            keep = []
+            ptrs = (ctypes.c_void_p * n)()
+            sizes = (ctypes.c_size_t * n)()
+            for i, d in enumerate(datas):
+                addr, size, k = buffer_address(d)
+                keep.append(k)
+                ptrs[i] = addr
+                sizes[i] = size
+            spec = out.to_c()
+            return lib().spdl_hj_decode_batch(
+                self._h, ptrs, sizes, n, ctypes.byref(spec), out_ptr, out_bytes,
+                _stream_handle(stream), int(bool(sync)), status, err, 1024,
+            )
+        return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
+                                    check, status, call))
+
+    def _submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync, check, status,
+                call):
+        """What the three batch submissions share: the views, crops and flips
+        go to the context, ``call(err)`` -- the method's own marshalling and
+        its native call -- returns the library's code, and a failure raises
+        unless ``check`` is False on a synchronous call that refused an image
+        (``status``) or a view.  (The methods reach it through the class: they
+        also run unbound, on objects that are no Decoder.)"""
         if views is not None:
             _check_views(views, out, crops, out_ptr, out_bytes)
             self.set_views(views)
@@ -693,26 +722,11 @@ class Decoder:
             self._crops(out, crops, n)
         if _has_flips(out, flips, views):
             self._flips(out, flips, n, views)
-        # borrowed for the duration of the call, no copy (the reference binds
-        # memoryviews as string_views, src/spdl/io/lib/cuda/memoryview_utils.h:17-20)
-        keep = []
-        ptrs = (ctypes.c_void_p * n)()
-        sizes = (ctypes.c_size_t * n)()
-        for i, d in enumerate(datas):
-            addr, size, k = buffer_address(d)
-            keep.append(k)
-            ptrs[i] = addr
-            sizes[i] = size
-        status = (ctypes.c_int32 * n)()
         err = ctypes.create_string_buffer(1024)
-        spec = out.to_c()
-        rc = lib().spdl_hj_decode_batch(
-            self._h, ptrs, sizes, n, ctypes.byref(spec), out_ptr, out_bytes,
-            _stream_handle(stream), int(bool(sync)), status, err, 1024,
-        )
+        rc = call(err)
         if rc and not (not check and sync and (any(status) or _refused(views, rc))):
             raise RuntimeError(err.value.decode() or f"Failed to decode an image. ({rc})")
-        return list(status)
+        return status
 
     def decode_batch_device(self, dev_ptr: int, dev_bytes: int, offsets, sizes, infos,
                             out: Output, out_ptr: int, out_bytes: int, stream=None,
@@ -724,27 +738,20 @@ class Decoder:
         import numpy as np
 
         n = len(offsets)
-        if views is not None:
-            _check_views(views, out, crops, out_ptr, out_bytes)
-            self.set_views(views)
-        elif crops is not None or out.src_crop is not None:
-            self._crops(out, crops, n)
-        if _has_flips(out, flips, views):
-            self._flips(out, flips, n, views)
-        offs = np.ascontiguousarray(offsets, dtype=np.int64)
-        szs = np.ascontiguousarray(sizes, dtype=np.int64)
-        inf = infos if isinstance(infos, ctypes.Array) else (ImageInfo * n)(*infos)
         status = np.zeros(n, np.int32)
-        err = ctypes.create_string_buffer(1024)
-        spec = self._spec(out)
-        rc = lib().spdl_hj_decode_batch_device(
-            self._h, dev_ptr, dev_bytes, offs.ctypes.data, szs.ctypes.data, inf, n,
-            ctypes.byref(spec), out_ptr, out_bytes, _stream_handle(stream), int(bool(sync)),
-            status.ctypes.data, err, 1024,
-        )
-        if rc and not (not check and sync and (status.any() or _refused(views, rc))):
-            raise RuntimeError(err.value.decode() or f"Failed to decode an image. ({rc})")
-        return status.tolist()
+
+        def call(err):
+            offs = np.ascontiguousarray(offsets, dtype=np.int64)
+            szs = np.ascontiguousarray(sizes, dtype=np.int64)
+            inf = infos if isinstance(infos, ctypes.Array) else (ImageInfo * n)(*infos)
+            spec = self._spec(out)
+            return lib().spdl_hj_decode_batch_device(
+                self._h, dev_ptr, dev_bytes, offs.ctypes.data, szs.ctypes.data, inf, n,
+                ctypes.byref(spec), out_ptr, out_bytes, _stream_handle(stream), int(bool(sync)),
+                status.ctypes.data, err, 1024,
+            )
+        return Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
+                               check, status, call).tolist()
 
     def _spec(self, out: Output) -> OutputSpec:
         cache = self.__dict__.setdefault("_spec_cache", {})
@@ -805,24 +812,17 @@ class Decoder:
                       out_bytes: int, stream=None, sync: bool = True, crops=None,
                       check: bool = True, views=None, flips=None) -> list[int]:
         n = len(offsets)
-        if views is not None:
-            _check_views(views, out, crops, out_ptr, out_bytes)
-            self.set_views(views)
-        else:
-            self._crops(out, crops, n)
-        if _has_flips(out, flips, views):
-            self._flips(out, flips, n, views)
-        offs = (ctypes.c_int64 * n)(*offsets)
-        szs = (ctypes.c_int64 * n)(*sizes)
         status = (ctypes.c_int32 * max(n, 1))()
-        err = ctypes.create_string_buffer(1024)
-        spec = out.to_c()
-        rc = lib().spdl_hj_decode_staged(
-            self._h, int(ticket), int(nbytes), offs, szs, n, ctypes.byref(spec), out_ptr,
-            out_bytes, _stream_handle(stream), int(bool(sync)), status, err, 1024)
-        if rc and not (not check and sync and (any(status) or _refused(views, rc))):
-            raise RuntimeError(err.value.decode() or f"Failed to decode an image. ({rc})")
-        return list(status)[:n]
+
+        def call(err):
+            offs = (ctypes.c_int64 * n)(*offsets)
+            szs = (ctypes.c_int64 * n)(*sizes)
+            spec = out.to_c()
+            return lib().spdl_hj_decode_staged(
+                self._h, int(ticket), int(nbytes), offs, szs, n, ctypes.byref(spec), out_ptr,
+                out_bytes, _stream_handle(stream), int(bool(sync)), status, err, 1024)
+        return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
+                                    check, status, call))[:n]
 
     def debug_entropy(self, data, nblocks: int):
         """Coefficients / destuffed bytes / diagnostics of one image (tests)."""

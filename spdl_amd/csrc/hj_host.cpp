@@ -8,30 +8,24 @@
 // hipMemcpyAsync from pinned staging.
 #include <hip/hip_runtime.h>
 
-#include <sched.h>
-#include <unistd.h>
-
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/spdl_hipjpeg.h"
 #include "hj_common.h"
 #include "hj_launch.h"
 #include "hj_layout.h"
+#include "hj_pack.h"
 #include "hj_probe.h"
 #include "hj_sws.h"
+#include "hj_tar.h"
 #include "hj_views.h"
 
 using namespace hj;
@@ -126,123 +120,6 @@ struct PinBuf {
   }
 };
 
-// Persistent host workers for the pinned-staging copies.  A 256-image batch
-// is ~28 MB; one core copies that at ~6-10 GB/s, slower than the GPU decodes
-// it, so the copy into pinned memory is split over a few threads.
-class CopyPool {
- public:
-  explicit CopyPool(int n) {
-    for (int i = 0; i < n; i++) th_.emplace_back([this, i] { loop(i + 1); });
-  }
-  ~CopyPool() {
-    {
-      std::lock_guard<std::mutex> g(m_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    for (auto& t : th_) t.join();
-  }
-  int workers() const { return (int)th_.size() + 1; }
-  // fn(part, nparts) runs for part = 0..nparts-1 (part 0 on the caller).
-  void run(const std::function<void(int, int)>& fn) {
-    const int np = workers();
-    {
-      std::lock_guard<std::mutex> g(m_);
-      fn_ = &fn;
-      pending_ = np - 1;
-      gen_++;
-    }
-    cv_.notify_all();
-    fn(0, np);
-    std::unique_lock<std::mutex> lk(m_);
-    done_cv_.wait(lk, [this] { return pending_ == 0; });
-    fn_ = nullptr;
-  }
-
- private:
-  void loop(int part) {
-    uint64_t seen = 0;
-    for (;;) {
-      const std::function<void(int, int)>* fn;
-      {
-        std::unique_lock<std::mutex> lk(m_);
-        cv_.wait(lk, [&] { return stop_ || gen_ != seen; });
-        if (stop_) return;
-        seen = gen_;
-        fn = fn_;
-      }
-      (*fn)(part, workers());
-      std::lock_guard<std::mutex> g(m_);
-      if (--pending_ == 0) done_cv_.notify_all();
-    }
-  }
-  std::vector<std::thread> th_;
-  std::mutex m_;
-  std::condition_variable cv_, done_cv_;
-  const std::function<void(int, int)>* fn_ = nullptr;
-  int pending_ = 0;
-  uint64_t gen_ = 0;
-  bool stop_ = false;
-};
-
-// Copier threads per context: the host cores this process may use (affinity,
-// capped by a cgroup v2 CPU quota) shared among the ranks of this node
-// (LOCAL_WORLD_SIZE), at most 8 with the caller; SPDL_HJ_COPY_THREADS
-// overrides.  8 ranks x 8 copiers would oversubscribe a 16-core share.
-int copy_workers() {
-  if (const char* e = getenv("SPDL_HJ_COPY_THREADS")) {
-    const int v = atoi(e);
-    return v < 1 ? 0 : (v > 16 ? 15 : v - 1);
-  }
-  int cores = (int)sysconf(_SC_NPROCESSORS_ONLN);
-  cpu_set_t set;
-  if (sched_getaffinity(0, sizeof(set), &set) == 0) cores = CPU_COUNT(&set);
-  if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-    char q[32] = {0};
-    long long per = 0;
-    if (fscanf(f, "%31s %lld", q, &per) == 2 && strcmp(q, "max") != 0 && per > 0) {
-      const long long c = atoll(q) / per;
-      if (c >= 1 && c < cores) cores = (int)c;
-    }
-    fclose(f);
-  }
-  int ranks = 1;
-  if (const char* e = getenv("LOCAL_WORLD_SIZE")) ranks = atoi(e) > 0 ? atoi(e) : 1;
-  const int share = cores / ranks;
-  return share <= 1 ? 0 : (share - 1 > 7 ? 7 : share - 1);
-}
-
-// Copy n items of (dst_off, src, len) into `base`, zero-filling each item's
-// tail [len, padded) -- split by bytes over the pool when the total is large.
-struct CopyItem {
-  int64_t dst_off;
-  const uint8_t* src;
-  int64_t len, padded;
-};
-
-void parallel_pack(CopyPool* pool, uint8_t* base, const std::vector<CopyItem>& items) {
-  int64_t total = 0;
-  for (const CopyItem& it : items) total += it.padded;
-  auto body = [&](int part, int np) {
-    // byte range [lo, hi) of the concatenated padded items
-    const int64_t lo = total * part / np, hi = total * (part + 1) / np;
-    int64_t acc = 0;
-    for (const CopyItem& it : items) {
-      const int64_t a = acc, b = acc + it.padded;
-      acc = b;
-      if (b <= lo) continue;
-      if (a >= hi) break;
-      const int64_t s = lo > a ? lo - a : 0, e = (hi < b ? hi : b) - a;
-      const int64_t cs = s, ce = e < it.len ? e : it.len;
-      if (ce > cs) memcpy(base + it.dst_off + cs, it.src + cs, (size_t)(ce - cs));
-      const int64_t zs = s > it.len ? s : it.len;
-      if (e > zs) memset(base + it.dst_off + zs, 0, (size_t)(e - zs));
-    }
-  };
-  if (!pool || pool->workers() < 2 || total < (4 << 20)) body(0, 1);
-  else pool->run(body);
-}
-
 }  // namespace
 
 // One in-flight batch: pinned staging + device copy of the JPEG bytes, the
@@ -273,11 +150,15 @@ struct Slot {
     spdl_hj_output out{};
     uint8_t* out_dev = nullptr;
     size_t img_bytes = 0;  // output bytes per image
-    std::vector<int> idx;
-    std::vector<int64_t> off, size;
-    std::vector<spdl_hj_image_info> info;
-    std::vector<spdl_hj_rect> rect;  // their source crops (empty: the batch had none)
-    std::vector<uint8_t> flip;       // their output flips (empty: the batch had none)
+    struct Item {  // one multi-piece image of the batch
+      int idx;
+      int64_t off, size;
+      spdl_hj_image_info info;
+      spdl_hj_rect rect;  // its source crop (has_rects)
+      uint8_t flip;       // its output flip (has_flips)
+    };
+    std::vector<Item> items;
+    bool has_rects = false, has_flips = false;  // the batch had crops / flips
   } retry;
 };
 
@@ -481,7 +362,7 @@ Slot* find_slot(spdl_hj_ctx* ctx, int64_t ticket) {
   return s.ticket == ticket ? &s : nullptr;
 }
 
-int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, int k);
+int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item& item);
 
 // Per-image statuses of a finished slot -> status[], first error -> err;
 // its stage timings -> ctx->timings when it was profiled.
@@ -502,15 +383,15 @@ int collect_status(spdl_hj_ctx* ctx, Slot& s, int32_t* status, char* err, size_t
   bool handoff = false;
   for (int i = 0; i < s.n && !handoff; i++) handoff = stv[i] == SPDL_HJ_ERR_HANDOFF;
   std::vector<int32_t> fixed;
-  if (handoff && !s.retry.idx.empty()) {
+  if (handoff && !s.retry.items.empty()) {
     // re-decode each image whose hand-off gave up in one workgroup (its
     // output lands where the batch's would have; the spare slot, statuses
     // copied first all the same)
     fixed.assign(stv, stv + s.n);
     Slot::Retry r = std::move(s.retry);
     s.retry = Slot::Retry{};
-    for (size_t k = 0; k < r.idx.size(); k++)
-      if (fixed[r.idx[k]] == SPDL_HJ_ERR_HANDOFF) fixed[r.idx[k]] = retry_image(ctx, r, (int)k);
+    for (const Slot::Retry::Item& it : r.items)
+      if (fixed[it.idx] == SPDL_HJ_ERR_HANDOFF) fixed[it.idx] = retry_image(ctx, r, it);
     stv = fixed.data();
   }
   const int n = fixed.empty() ? s.n : (int)fixed.size();
@@ -598,23 +479,32 @@ struct Submission {
   const uint8_t* flips = nullptr;       // ... and its output flips (one per image)
 };
 
+// An output chain's share of the output kernels' parameters: the batch's
+// spec and size, or a view group's
+void set_chain(BatchParams& p, const spdl_hj_output& o, int w, int h) {
+  p.pix_fmt = o.pix_fmt;
+  p.dtype = o.dtype;
+  p.resize = o.resize;
+  p.filter = o.filter;
+  p.out_w = w;
+  p.out_h = h;
+  memcpy(p.mean, o.mean, sizeof(p.mean));
+  memcpy(p.std, o.std, sizeof(p.std));
+}
+
 // device pipeline over bytes already in HBM; `slot` provides the descriptor
 // and status staging and is marked done on the stream at the end; the
 // workspace is the slot's lane.
 int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission& sub, char* err,
                  size_t errlen) {
-  const uint8_t* const d_bytes = sub.d_bytes;
-  const size_t bytes_len = sub.bytes_len, out_bytes = sub.out_bytes;
   const int n = sub.n;
   const spdl_hj_output* const out = sub.out;
-  void* const out_dev = sub.out_dev;
   const hipStream_t st = sub.st;
-  const bool planes_only = sub.planes_only;
   const size_t esz = out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
   const bool by_views = !L.groups.empty();  // (build_layout checked every group's buffer)
-  if (!planes_only && !by_views && (size_t)L.out_elems_per_image * n * esz > out_bytes) {
+  if (!sub.planes_only && !by_views && (size_t)L.out_elems_per_image * n * esz > sub.out_bytes) {
     set_err(err, errlen, "output buffer too small: need %lld bytes, have %zu",
-            (long long)(L.out_elems_per_image * n * esz), out_bytes);
+            (long long)(L.out_elems_per_image * n * esz), sub.out_bytes);
     return SPDL_HJ_ERR_INVALID_ARG;
   }
   int64_t max_end = 0;
@@ -625,7 +515,7 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
       return SPDL_HJ_ERR_INVALID_ARG;
     }
     int64_t e = L.desc[i].in_off + L.desc[i].in_size;
-    if (L.desc[i].in_off < 0 || L.desc[i].in_size < 0 || (size_t)e > bytes_len) {
+    if (L.desc[i].in_off < 0 || L.desc[i].in_size < 0 || (size_t)e > sub.bytes_len) {
       set_err(err, errlen, "image %d extends past the input buffer", i);
       return SPDL_HJ_ERR_INVALID_ARG;
     }
@@ -638,7 +528,7 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   W.last_st = st;
   W.used = true;
   BatchBuffers B;
-  if (int rc = workspace_buffers(W, L, n, d_bytes, max_end, st, &B, err, errlen)) return rc;
+  if (int rc = workspace_buffers(W, L, n, sub.d_bytes, max_end, st, &B, err, errlen)) return rc;
   // A grid is flat (one workgroup per image tile, through the map) when the
   // (max tiles) x images grid would be mostly empty; a batch of similar
   // images keeps the 2-D grid, whose workgroups need no map lookup
@@ -660,7 +550,7 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   if (B.flips)
     memcpy(static_cast<uint8_t*>(slot.pin_desc.p) + work_end, L.flips.data(), L.flips.size());
   // the batch's swscale tables travel with the descriptors
-  const bool swscale = !planes_only && out->csc == SPDL_HJ_CSC_SWSCALE;
+  const bool swscale = !sub.planes_only && out->csc == SPDL_HJ_CSC_SWSCALE;
   const size_t tb = swscale ? L.tables.size() * 4 : 0;
   HJ_HIP(slot.pin_tables.ensure(tb + 16));
   if (tb) memcpy(slot.pin_tables.p, L.tables.data(), tb);
@@ -737,29 +627,22 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   }
   // 4-component frames: FFmpeg's K transform on the planes (not on the raw
   // planes surface, which returns the IDCT output as the oracle does)
-  if (!planes_only && L.cmyk_px > 0) HJ_HIP(launch_cmyk(B, L.cmyk_px, st));
+  if (!sub.planes_only && L.cmyk_px > 0) HJ_HIP(launch_cmyk(B, L.cmyk_px, st));
   mark(ctx, slot, 5, st);
   BatchParams bp{};
   bp.n = n;
-  bp.pix_fmt = out->pix_fmt;
-  bp.dtype = out->dtype;
   bp.idct = out->idct;
-  bp.resize = out->resize;
-  bp.filter = out->filter;
-  bp.out_w = L.ow;
-  bp.out_h = L.oh;
+  set_chain(bp, *out, L.ow, L.oh);
   bp.sub_bits = ctx->sub_bits;
   bp.debug_mask = abl;
   bp.xcd_order = ctx->xcd_order;
-  memcpy(bp.mean, out->mean, sizeof(bp.mean));
-  memcpy(bp.std, out->std, sizeof(bp.std));
   bp.csc = sws_csc();
   // the output kernel writes each image's status into the pinned array itself
   // (not with views: their descriptors are no images; the statuses are copied below)
   int32_t* hstat =
-      hs && !planes_only && !by_views ? static_cast<int32_t*>(slot.pin_status.dev) : nullptr;
+      hs && !sub.planes_only && !by_views ? static_cast<int32_t*>(slot.pin_status.dev) : nullptr;
   mark(ctx, slot, 6, st);
-  if (!planes_only && !(abl & kAblNoOutput)) {
+  if (!sub.planes_only && !(abl & kAblNoOutput)) {
     const int sws_wgs = (int)L.sws_wgs, hs_wgs = (int)L.hs_wgs;
     if (by_views) {
       // once per group: its chain's parameters, its buffer, its slice of the
@@ -768,29 +651,22 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
       bool first = true;
       for (const Layout::Group& G : L.groups) {
         BatchParams gp = bp;
-        gp.pix_fmt = G.out.pix_fmt;
-        gp.dtype = G.out.dtype;
-        gp.resize = G.out.resize;
-        gp.filter = G.out.filter;
-        gp.out_w = G.ow;
-        gp.out_h = G.oh;
-        memcpy(gp.mean, G.out.mean, sizeof(gp.mean));
-        memcpy(gp.std, G.out.std, sizeof(gp.std));
+        set_chain(gp, G.out, G.ow, G.oh);
         HJ_HIP(launch_sws(B, G.out_dev, gp, true, G.sws_wgs, 1, 1, G.sws_lds,
                           first ? hs_wgs : 0, nullptr, st, G.sws_wg0));
         first = false;
       }
     } else if (yuv)
-      HJ_HIP(launch_yuv_planes(B, out_dev, sws_wgs, L.sws_lds, hs_wgs, hstat, st));
+      HJ_HIP(launch_yuv_planes(B, sub.out_dev, sws_wgs, L.sws_lds, hs_wgs, hstat, st));
     else if (fused)
-      HJ_HIP(launch_idct_rgb(B, out_dev, bp, idct_kind, L.fused_tiles, hstat, st));
+      HJ_HIP(launch_idct_rgb(B, sub.out_dev, bp, idct_kind, L.fused_tiles, hstat, st));
     else if (fast_rgb)  // swscale's unscaled converter needs no scaling passes
-      HJ_HIP(launch_rgb_unscaled(B, out_dev, bp, L.max_px, hstat, st));
+      HJ_HIP(launch_rgb_unscaled(B, sub.out_dev, bp, L.max_px, hstat, st));
     else if (swscale)
-      HJ_HIP(launch_sws(B, out_dev, bp, sws_flat, sws_wgs, L.sws_bands, L.sws_chunks, L.sws_lds,
+      HJ_HIP(launch_sws(B, sub.out_dev, bp, sws_flat, sws_wgs, L.sws_bands, L.sws_chunks, L.sws_lds,
                         hs_wgs, hstat, st));
     else
-      HJ_HIP(launch_csc(B, out_dev, bp, L.max_px, hstat, st));
+      HJ_HIP(launch_csc(B, sub.out_dev, bp, L.max_px, hstat, st));
   }
   mark(ctx, slot, 7, st);
   // per-image status: strided D2H of ImageInfo::status
@@ -801,26 +677,19 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   HJ_HIP(hipEventRecord(W.done, st));
   HJ_HIP(hipEventRecord(slot.done, st));
   Slot::Retry& R = slot.retry;
-  R.idx.clear();
-  R.off.clear();
-  R.size.clear();
-  R.info.clear();
-  R.rect.clear();
-  R.flip.clear();
-  if (!planes_only) {
-    for (const auto& m : L.multi) {
-      if (sub.crops) R.rect.push_back(sub.crops[m.first]);
-      if (sub.flips) R.flip.push_back(sub.flips[m.first]);
-      R.idx.push_back(m.first);
-      R.off.push_back(L.desc[m.first].in_off);
-      R.size.push_back(L.desc[m.first].in_size);
-      R.info.push_back(m.second);
-    }
+  R.items.clear();
+  if (!sub.planes_only) {
+    R.has_rects = sub.crops != nullptr;
+    R.has_flips = sub.flips != nullptr;
+    for (const auto& m : L.multi)
+      R.items.push_back({m.first, L.desc[m.first].in_off, L.desc[m.first].in_size, m.second,
+                         sub.crops ? sub.crops[m.first] : spdl_hj_rect{},
+                         sub.flips ? sub.flips[m.first] : (uint8_t)0});
     R.ticket = slot.ticket;
-    R.bytes = d_bytes;
-    R.len = bytes_len;
+    R.bytes = sub.d_bytes;
+    R.len = sub.bytes_len;
     R.out = *out;
-    R.out_dev = static_cast<uint8_t*>(out_dev);
+    R.out_dev = static_cast<uint8_t*>(sub.out_dev);
     R.img_bytes = (size_t)L.out_elems_per_image * esz;
   }
   slot.pending = true;
@@ -863,18 +732,18 @@ int exec_stream(spdl_hj_ctx* ctx, Slot& slot, hipStream_t st, hipStream_t* xs, c
   return SPDL_HJ_OK;
 }
 
-// Image r.idx[k] of a finished batch again, as a one-image batch decoded by
+// One image of a finished batch again, as a one-image batch decoded by
 // one entropy workgroup (no piece hand-off), synchronously, into its place in
 // the batch's output.  Returns its status.
-int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, int k) {
+int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item& item) {
   char err[256];
   const size_t errlen = sizeof(err);
   Layout L;
   int32_t st1 = SPDL_HJ_OK;
-  LayoutRequest rq{&r.off[k], &r.size[k], &r.info[k], 1, &r.out, 0, &ctx->plans};
-  rq.crops = r.rect.empty() ? nullptr : &r.rect[k];
-  rq.flips = r.flip.empty() ? nullptr : &r.flip[k];
-  rq.nflips = r.flip.empty() ? 0 : 1;
+  LayoutRequest rq{&item.off, &item.size, &item.info, 1, &r.out, 0, &ctx->plans};
+  rq.crops = r.has_rects ? &item.rect : nullptr;
+  rq.flips = r.has_flips ? &item.flip : nullptr;
+  rq.nflips = r.has_flips ? 1 : 0;
   int rc = plan_batch(rq, L, &st1, err, errlen);
   if (rc) return rc;
   // the spare slot, on the failed batch's lane (its workspace is free: the
@@ -891,7 +760,7 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, int k) {
   const int64_t idct_wgs = ctx->idct_workgroups;  // (the batch's, not this re-decode's)
   const int64_t ent_wgs = ctx->entropy_workgroups;
   rc = run_pipeline(ctx, *s, L,
-                    {r.bytes, r.len, 1, &r.out, r.out_dev + (size_t)r.idx[k] * r.img_bytes,
+                    {r.bytes, r.len, 1, &r.out, r.out_dev + (size_t)item.idx * r.img_bytes,
                      r.img_bytes, xs, 1, &st1},
                     err, errlen);
   ctx->idct_workgroups = idct_wgs;
@@ -911,45 +780,6 @@ int stage_h2d(spdl_hj_ctx* ctx, Slot& s, size_t total, hipStream_t st, char* err
   HJ_HIP(hipEventRecord(s.h2d_done, ctx->copy));
   HJ_HIP(hipStreamWaitEvent(st, s.h2d_done, 0));
   return SPDL_HJ_OK;
-}
-
-// ---- tar (ustar / GNU 'L' long names / pax 'x' path) ------------------------
-// Same member walk as the reference's InMemoryTarParserImpl::parse_next
-// (src/spdl/io/lib/archive/tar_iterator.cpp:125-195): a header that fails the
-// magic/checksum test is skipped 512 bytes at a time; an empty name ends the
-// archive; 'L' and 'x' records name the next regular file; other types are
-// skipped with their payload; a member running past the buffer ends the walk.
-uint64_t tar_octal(const uint8_t* s, size_t n) {
-  uint64_t r = 0;
-  for (size_t i = 0; i < n && s[i] != 0 && s[i] != ' '; i++)
-    if (s[i] >= '0' && s[i] <= '7') r = r * 8 + (s[i] - '0');
-  return r;
-}
-
-bool tar_header_ok(const uint8_t* h) {
-  if (memcmp(h + 257, "ustar", 5) != 0) return false;
-  uint32_t sum = 0;
-  for (int i = 0; i < 512; i++) sum += (i >= 148 && i < 156) ? (uint32_t)' ' : h[i];
-  return tar_octal(h + 148, 8) == sum;
-}
-
-std::string tar_pax_path(const uint8_t* d, size_t n) {
-  // records "<len> key=value\n"
-  size_t pos = 0;
-  while (pos < n) {
-    const void* sp = memchr(d + pos, ' ', n - pos);
-    if (!sp) break;
-    const size_t rs = (size_t)(static_cast<const uint8_t*>(sp) - d) + 1;
-    if (rs + 5 <= n && memcmp(d + rs, "path=", 5) == 0) {
-      const void* nl = memchr(d + rs + 5, '\n', n - rs - 5);
-      if (nl) return std::string((const char*)d + rs + 5,
-                                 (size_t)(static_cast<const uint8_t*>(nl) - (d + rs + 5)));
-    }
-    const void* nl = memchr(d + pos, '\n', n - pos);
-    if (!nl) break;
-    pos = (size_t)(static_cast<const uint8_t*>(nl) - d) + 1;
-  }
-  return std::string();
 }
 
 // The rectangles spdl_hj_set_crops left for this submission of n images:
@@ -1043,14 +873,120 @@ struct Held {
   }
 };
 
-// An acquired staging slot is released (ticket 0) if its call ends before
-// run_pipeline has taken it
+// An acquired slot is released (ticket 0) if its call ends before
+// run_pipeline has taken it: its `done` event is never recorded for the ticket
 struct SlotRelease {
-  Slot* s;
+  Slot* s = nullptr;
   ~SlotRelease() {
     if (s) s->ticket = 0;
   }
+  Slot& pass() {  // (the slot is the pipeline's from here)
+    Slot* p = s;
+    s = nullptr;
+    return *p;
+  }
 };
+
+// A batch submission, its arguments checked and its bytes located: image i is
+// sizes[i] bytes at offsets[i] of `len` bytes that lie in one of three places.
+struct Batch {
+  const int64_t* offsets;
+  const int64_t* sizes;
+  int n;
+  const spdl_hj_output* out;
+  void* out_dev;
+  size_t out_bytes;
+  hipStream_t st;
+  int sync;
+  int32_t* status;
+  size_t len;        // (an image reaching past it is refused)
+  size_t bytes_len;  // what the pipeline may read: len, and the tail slack when staged
+  const uint8_t* const* data = nullptr;       // host: image i at data[i] (packed by `fill`)
+  const uint8_t* host = nullptr;              // a staged slot's pinned bytes
+  const uint8_t* dev = nullptr;               // HBM, probed by the caller:
+  const spdl_hj_image_info* infos = nullptr;  // ... its probes
+};
+
+// From there to run_pipeline, for the three batch entry points.  Host bytes
+// are probed here.  Planning comes before a slot is taken (`slot` holds the
+// staged entry point's), so a probe or planning failure takes no ticket;
+// `fill(slot)` then completes the slot's pinned staging.
+template <class Fill>
+int submit(spdl_hj_ctx* ctx, const Held& held, const Batch& b, SlotRelease& slot, Fill fill,
+           char* err, size_t errlen) {
+  DeviceGuard g(ctx->device);
+  std::vector<spdl_hj_image_info> probed;
+  const spdl_hj_image_info* infos = b.infos;
+  if (!b.dev) {
+    probed.resize(b.n);
+    infos = probed.data();
+    for (int i = 0; i < b.n; i++) {
+      int rc = SPDL_HJ_ERR_INVALID_ARG;
+      if (b.offsets[i] >= 0 && b.sizes[i] >= 0 && (size_t)(b.offsets[i] + b.sizes[i]) <= b.len)
+        rc = probe(b.data ? b.data[i] : b.host + b.offsets[i], (size_t)b.sizes[i], &probed[i]);
+      if (b.status) b.status[i] = rc;
+      if (rc) {
+        set_err(err, errlen, "Failed to decode an image. (image %d: %s)", i, status_str(rc));
+        return rc;
+      }
+    }
+  }
+  Layout L;
+  // (views: one entropy workgroup per image, so no hand-off can give up)
+  int rc = plan_batch({b.offsets, b.sizes, infos, b.n, b.out, held.hv ? 0 : ctx->piece_bytes,
+                       &ctx->plans, held.crops, held.hv, held.flips, held.nflips},
+                      L, b.status, err, errlen);
+  if (rc) return rc;
+  // the probes (the caller's own with device bytes, ABI 5) say which files
+  // take the multi-scan path
+  for (int i = 0; i < b.n; i++) L.ms_side = L.ms_side || infos[i].multiscan != 0;
+  L.ms_known = true;
+  if (!slot.s && (rc = acquire_slot(ctx, &slot.s, err, errlen))) return rc;
+  if ((rc = fill(*slot.s))) return rc;
+  hipStream_t xs;
+  rc = exec_stream(ctx, *slot.s, b.st, &xs, err, errlen);
+  if (rc) return rc;
+  if (b.dev) mark(ctx, *slot.s, 0, xs);
+  else if ((rc = stage_h2d(ctx, *slot.s, b.bytes_len, xs, err, errlen))) return rc;
+  const uint8_t* bytes = b.dev ? b.dev : static_cast<const uint8_t*>(slot.s->bytes.p);
+  return run_pipeline(ctx, slot.pass(), L,
+                      {bytes, b.bytes_len, b.n, b.out, b.out_dev, b.out_bytes, xs, b.sync, b.status,
+                       false, held.crops, held.hv ? nullptr : held.flips},
+                      err, errlen);
+}
+
+// One host image, planes only, synchronous (spdl_hj_decode_planes,
+// spdl_hj_debug_entropy): what the caller reads the results with.
+struct OneImage {
+  Layout L;
+  Slot* slot = nullptr;
+  hipStream_t xs = nullptr;
+  bool ran = false;  // the pipeline was entered: the return code is its own
+};
+
+int decode_one(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, const spdl_hj_image_info& info,
+               const spdl_hj_output& o, int64_t piece_bytes, hipStream_t st, OneImage* r, char* err,
+               size_t errlen) {
+  const int64_t off = 0, sz = (int64_t)size, total = round_up(sz + 64, 256);
+  r->L = Layout{};
+  r->ran = false;
+  int rc = plan_batch({&off, &sz, &info, 1, &o, piece_bytes, nullptr}, r->L, nullptr, err, errlen);
+  if (rc) return rc;
+  SlotRelease slot;
+  if ((rc = acquire_slot(ctx, &slot.s, err, errlen))) return rc;
+  r->slot = slot.s;
+  HJ_HIP(slot.s->pin_in.ensure((size_t)total));
+  memcpy(slot.s->pin_in.p, data, size);
+  memset(static_cast<uint8_t*>(slot.s->pin_in.p) + size, 0, (size_t)(total - sz));
+  rc = exec_stream(ctx, *slot.s, st, &r->xs, err, errlen);
+  if (!rc) rc = stage_h2d(ctx, *slot.s, (size_t)total, r->xs, err, errlen);
+  if (rc) return rc;
+  r->ran = true;
+  return run_pipeline(ctx, slot.pass(), r->L,
+                      {static_cast<const uint8_t*>(r->slot->bytes.p), (size_t)total, 1, &o, nullptr,
+                       0, r->xs, 1, nullptr, true},
+                      err, errlen);
+}
 
 }  // namespace
 
@@ -1188,50 +1124,29 @@ int spdl_hj_decode_batch(spdl_hj_ctx* ctx, const uint8_t* const* data, const siz
                          void* stream, int32_t sync, int32_t* status, char* err, size_t errlen) {
   const Held held(ctx, n, out, out_dev, out_bytes, err, errlen);
   if (int rc = held.check(ctx && data && sizes, n, out, out_dev, err, errlen)) return rc;
-  DeviceGuard g(ctx->device);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  std::vector<spdl_hj_image_info> infos(n);
+  // the files, each with 64 bytes of slack, on 256-byte boundaries of the staging
   std::vector<int64_t> offs(n), szs(n);
   std::vector<CopyItem> items(n);
   int64_t total = 0;
-  bool prog = false;
   for (int i = 0; i < n; i++) {
-    int rc = probe(data[i], sizes[i], &infos[i]);
-    if (!rc) prog = prog || infos[i].multiscan;
-    if (status) status[i] = rc;
-    if (rc) {
-      set_err(err, errlen, "Failed to decode an image. (image %d: %s)", i, status_str(rc));
-      return rc;
-    }
     offs[i] = total;
     szs[i] = (int64_t)sizes[i];
     const int64_t padded = round_up((int64_t)sizes[i] + 64, 256);
     items[i] = {total, data[i], (int64_t)sizes[i], padded};
     total += padded;
   }
-  Layout L;
-  // (views: one entropy workgroup per image, so no hand-off can give up)
-  int rc = plan_batch({offs.data(), szs.data(), infos.data(), n, out,
-                       held.hv ? 0 : ctx->piece_bytes, &ctx->plans, held.crops, held.hv,
-                       held.flips, held.nflips},
-                      L, status, err, errlen);
-  if (rc) return rc;
-  L.ms_side = prog;
-  L.ms_known = true;
-  Slot* s = nullptr;
-  rc = acquire_slot(ctx, &s, err, errlen);
-  if (rc) return rc;
-  HJ_HIP(s->pin_in.ensure((size_t)total));
-  parallel_pack(copy_pool(ctx), static_cast<uint8_t*>(s->pin_in.p), items);
-  hipStream_t xs;
-  rc = exec_stream(ctx, *s, st, &xs, err, errlen);
-  if (!rc) rc = stage_h2d(ctx, *s, (size_t)total, xs, err, errlen);
-  if (rc) return rc;
-  return run_pipeline(ctx, *s, L,
-                      {static_cast<const uint8_t*>(s->bytes.p), (size_t)total, n, out, out_dev,
-                       out_bytes, xs, sync, status, false, held.crops,
-                       held.hv ? nullptr : held.flips},
-                      err, errlen);
+  Batch b{offs.data(), szs.data(), n, out, out_dev, out_bytes, static_cast<hipStream_t>(stream),
+          sync, status, (size_t)total, (size_t)total};
+  b.data = data;
+  SlotRelease slot;
+  return submit(
+      ctx, held, b, slot,
+      [&](Slot& s) -> int {
+        HJ_HIP(s.pin_in.ensure((size_t)total));
+        parallel_pack(copy_pool(ctx), static_cast<uint8_t*>(s.pin_in.p), items);
+        return SPDL_HJ_OK;
+      },
+      err, errlen);
 }
 
 int spdl_hj_decode_batch_device(spdl_hj_ctx* ctx, const uint8_t* dev_data, size_t dev_bytes,
@@ -1243,27 +1158,12 @@ int spdl_hj_decode_batch_device(spdl_hj_ctx* ctx, const uint8_t* dev_data, size_
   const Held held(ctx, n, out, out_dev, out_bytes, err, errlen);
   if (int rc = held.check(ctx && dev_data && offsets && sizes && infos, n, out, out_dev, err, errlen))
     return rc;
-  DeviceGuard g(ctx->device);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  Layout L;
-  int rc = plan_batch({offsets, sizes, infos, n, out, held.hv ? 0 : ctx->piece_bytes, &ctx->plans,
-                       held.crops, held.hv, held.flips, held.nflips},
-                      L, status, err, errlen);
-  if (rc) return rc;
-  // the caller's probe says which files take the multi-scan path (ABI 5)
-  for (int i = 0; i < n; i++) L.ms_side = L.ms_side || infos[i].multiscan != 0;
-  L.ms_known = true;
-  Slot* s = nullptr;
-  rc = acquire_slot(ctx, &s, err, errlen);
-  if (rc) return rc;
-  hipStream_t xs;
-  rc = exec_stream(ctx, *s, st, &xs, err, errlen);
-  if (rc) return rc;
-  mark(ctx, *s, 0, xs);
-  return run_pipeline(ctx, *s, L,
-                      {dev_data, dev_bytes, n, out, out_dev, out_bytes, xs, sync, status, false,
-                       held.crops, held.hv ? nullptr : held.flips},
-                      err, errlen);
+  Batch b{offsets, sizes, n, out, out_dev, out_bytes, static_cast<hipStream_t>(stream), sync,
+          status, dev_bytes, dev_bytes};
+  b.dev = dev_data;
+  b.infos = infos;
+  SlotRelease slot;
+  return submit(ctx, held, b, slot, [](Slot&) { return 0; }, err, errlen);
 }
 
 int64_t spdl_hj_last_ticket(spdl_hj_ctx* ctx) { return ctx ? ctx->last_ticket : 0; }
@@ -1333,25 +1233,9 @@ int spdl_hj_staging_read(spdl_hj_ctx* ctx, int64_t ticket, size_t dst_off, int f
     set_err(err, errlen, "invalid staging read (ticket %lld)", (long long)ticket);
     return SPDL_HJ_ERR_INVALID_ARG;
   }
-  uint8_t* base = static_cast<uint8_t*>(s->pin_in.p) + dst_off;
-  std::atomic<int> bad{0};
-  auto body = [&](int part, int np) {
-    // 64 KiB-aligned split so the page-cache copies stay sequential per thread
-    const size_t unit = 1 << 16, nu = (len + unit - 1) / unit;
-    size_t lo = nu * part / np * unit, hi = nu * (part + 1) / np * unit;
-    if (hi > len) hi = len;
-    while (lo < hi) {
-      const ssize_t r = pread(fd, base + lo, hi - lo, (off_t)(file_off + (int64_t)lo));
-      if (r <= 0) {
-        bad = 1;
-        return;
-      }
-      lo += (size_t)r;
-    }
-  };
-  if (len < (4u << 20) || copy_pool(ctx)->workers() < 2) body(0, 1);
-  else copy_pool(ctx)->run(body);
-  if (bad) {
+  // (a small read is one thread's: it does not create the pool)
+  if (!parallel_pread(len < (4u << 20) ? nullptr : copy_pool(ctx), fd, file_off,
+                      static_cast<uint8_t*>(s->pin_in.p) + dst_off, len)) {
     set_err(err, errlen, "pread failed or hit end of file (offset %lld, %zu bytes)",
             (long long)file_off, len);
     return SPDL_HJ_ERR_INVALID_ARG;
@@ -1370,44 +1254,20 @@ int spdl_hj_decode_staged(spdl_hj_ctx* ctx, int64_t ticket, size_t len, const in
     return SPDL_HJ_ERR_INVALID_ARG;
   }
   s->staged = false;  // the slot is consumed whatever happens below
-  SlotRelease release{s};
+  SlotRelease slot{s};
   if (int rc = held.check(offsets && sizes && len + 512 <= s->pin_in.cap, n, out, out_dev, err,
                           errlen))
     return rc;
-  DeviceGuard g(ctx->device);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const uint8_t* host = static_cast<const uint8_t*>(s->pin_in.p);
-  std::vector<spdl_hj_image_info> infos(n);
-  bool prog = false;
-  for (int i = 0; i < n; i++) {
-    int rc = SPDL_HJ_ERR_INVALID_ARG;
-    if (offsets[i] >= 0 && sizes[i] >= 0 && (size_t)(offsets[i] + sizes[i]) <= len)
-      rc = probe(host + offsets[i], (size_t)sizes[i], &infos[i]);
-    if (!rc) prog = prog || infos[i].multiscan;
-    if (status) status[i] = rc;
-    if (rc) {
-      set_err(err, errlen, "Failed to decode an image. (image %d: %s)", i, status_str(rc));
-      return rc;
-    }
-  }
-  Layout L;
-  int rc = plan_batch({offsets, sizes, infos.data(), n, out, held.hv ? 0 : ctx->piece_bytes,
-                       &ctx->plans, held.crops, held.hv, held.flips, held.nflips},
-                      L, status, err, errlen);
-  if (rc) return rc;
-  L.ms_side = prog;
-  L.ms_known = true;
-  memset(static_cast<uint8_t*>(s->pin_in.p) + len, 0, 512);  // tail read slack
-  hipStream_t xs;
-  rc = exec_stream(ctx, *s, st, &xs, err, errlen);
-  if (!rc) rc = stage_h2d(ctx, *s, len + 512, xs, err, errlen);
-  if (rc) return rc;
-  release.s = nullptr;  // (the slot is the pipeline's from here)
-  return run_pipeline(ctx, *s, L,
-                      {static_cast<const uint8_t*>(s->bytes.p), len + 512, n, out, out_dev,
-                       out_bytes, xs, sync, status, false, held.crops,
-                       held.hv ? nullptr : held.flips},
-                      err, errlen);
+  Batch b{offsets, sizes, n, out, out_dev, out_bytes, static_cast<hipStream_t>(stream), sync,
+          status, len, len + 512};
+  b.host = static_cast<const uint8_t*>(s->pin_in.p);
+  return submit(
+      ctx, held, b, slot,
+      [len](Slot& s) {
+        memset(static_cast<uint8_t*>(s.pin_in.p) + len, 0, 512);  // tail read slack
+        return 0;
+      },
+      err, errlen);
 }
 
 int spdl_hj_tar_index(const uint8_t* data, size_t size, size_t start, int32_t max_entries,
@@ -1415,85 +1275,8 @@ int spdl_hj_tar_index(const uint8_t* data, size_t size, size_t start, int32_t ma
                       size_t names_cap, int32_t* n_out, size_t* next_pos) {
   if (!data || !offsets || !sizes || !n_out || !next_pos || max_entries < 0)
     return SPDL_HJ_ERR_INVALID_ARG;
-  size_t pos = start, used = 0;
-  int32_t n = 0;
-  std::string pending;
-  bool at_end = false;
-  while (n < max_entries) {
-    const size_t entry_pos = pos;  // resume point if this entry does not fit
-    std::string path;
-    bool found = false;
-    pending.clear();
-    while (pos + 512 <= size) {
-      const uint8_t* h = data + pos;
-      if (!tar_header_ok(h)) {
-        pos += 512;
-        continue;
-      }
-      std::string fp;
-      if (h[0]) {
-        if (h[345]) {
-          fp.assign((const char*)h + 345, strnlen((const char*)h + 345, 155));
-          if (fp.back() != '/') fp += '/';
-        }
-        fp.append((const char*)h, strnlen((const char*)h, 100));
-      }
-      if (fp.empty() && pending.empty()) {
-        at_end = true;
-        break;
-      }
-      const uint64_t fsz = tar_octal(h + 124, 12);
-      const uint64_t padded = (fsz + 511) & ~511ull;
-      const char type = (char)h[156];
-      if (type == 'L' || type == 'x') {
-        pos += 512;
-        if (pos + fsz > size) {
-          at_end = true;
-          break;
-        }
-        if (type == 'L') {
-          pending.assign((const char*)data + pos, (size_t)fsz);
-          if (!pending.empty() && pending.back() == '\0') pending.pop_back();
-        } else {
-          pending = tar_pax_path(data + pos, (size_t)fsz);
-        }
-        pos += padded;
-        continue;
-      }
-      if (type == '0' || type == '\0') {
-        pos += 512;
-        if (!pending.empty()) fp = pending;
-        if (pos + fsz > size) {
-          at_end = true;
-          break;
-        }
-        path = fp;
-        offsets[n] = (int64_t)pos;
-        sizes[n] = (int64_t)fsz;
-        pos += padded;
-        found = true;
-        break;
-      }
-      pending.clear();
-      pos += 512 + padded;
-    }
-    if (!found) {
-      if (!at_end) pos = size;
-      break;
-    }
-    if (names && name_offs) {
-      if (used + path.size() + 1 > names_cap) {
-        pos = entry_pos;  // retry this entry with a fresh names buffer
-        break;
-      }
-      memcpy(names + used, path.c_str(), path.size() + 1);
-      name_offs[n] = (int64_t)used;
-      used += path.size() + 1;
-    }
-    n++;
-  }
-  *n_out = n;
-  *next_pos = at_end ? size : pos;
+  tar_index(data, size, start, max_entries, offsets, sizes, name_offs, names, names_cap, n_out,
+            next_pos);
   return SPDL_HJ_OK;
 }
 
@@ -1513,34 +1296,17 @@ int spdl_hj_decode_planes(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
   }
   spdl_hj_output o{};
   o.idct = idct;
-  int64_t off = 0, sz = (int64_t)size, total = round_up(sz + 64, 256);
-  Layout L;
-  Slot* s = nullptr;
-  hipStream_t xs;
+  OneImage one;
   // (a piece hand-off that gave up: once more in one entropy workgroup)
   for (int64_t piece_bytes : {ctx->piece_bytes, (int64_t)0}) {
-    L = Layout{};
-    rc = plan_batch({&off, &sz, &info, 1, &o, piece_bytes, nullptr}, L, nullptr, err, errlen);
-    if (rc) return rc;
-    rc = acquire_slot(ctx, &s, err, errlen);
-    if (rc) return rc;
-    HJ_HIP(s->pin_in.ensure((size_t)total));
-    memcpy(s->pin_in.p, data, size);
-    memset(static_cast<uint8_t*>(s->pin_in.p) + size, 0, (size_t)(total - sz));
-    rc = exec_stream(ctx, *s, st, &xs, err, errlen);
-    if (!rc) rc = stage_h2d(ctx, *s, (size_t)total, xs, err, errlen);
-    if (rc) return rc;
-    rc = run_pipeline(ctx, *s, L,
-                      {static_cast<const uint8_t*>(s->bytes.p), (size_t)total, 1, &o, nullptr, 0, xs,
-                       1, nullptr, true},
-                      err, errlen);
-    if (rc != SPDL_HJ_ERR_HANDOFF || piece_bytes == 0) break;
+    rc = decode_one(ctx, data, size, info, o, piece_bytes, st, &one, err, errlen);
+    if (rc != SPDL_HJ_ERR_HANDOFF || !one.ran || piece_bytes == 0) break;
     ctx->handoff_retries++;
   }
   if (rc) return rc;
-  Workspace& W = ctx->ws[s->ticket % ctx->lanes];
-  st = xs;
-  const ImageDesc& d = L.desc[0];
+  Workspace& W = ctx->ws[one.slot->ticket % ctx->lanes];
+  st = one.xs;
+  const ImageDesc& d = one.L.desc[0];
   FrameBlocks fb;
   (void)frame_blocks(info, &fb);  // (the layout was built: the frame is supported)
   const int hmax = fb.grid.hmax, vmax = fb.grid.vmax;
@@ -1564,7 +1330,6 @@ int spdl_hj_debug_entropy(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
     return SPDL_HJ_ERR_INVALID_ARG;
   }
   DeviceGuard g(ctx->device);
-  hipStream_t st = nullptr;
   spdl_hj_image_info info;
   int rc = probe(data, size, &info);
   if (rc) {
@@ -1572,25 +1337,11 @@ int spdl_hj_debug_entropy(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
     return rc;
   }
   spdl_hj_output o{};
-  int64_t off = 0, sz = (int64_t)size, total = round_up(sz + 64, 256);
-  Layout L;
-  rc = plan_batch({&off, &sz, &info, 1, &o, ctx->piece_bytes, nullptr}, L, nullptr, err, errlen);
-  if (rc) return rc;
-  Slot* s = nullptr;
-  rc = acquire_slot(ctx, &s, err, errlen);
-  if (rc) return rc;
-  HJ_HIP(s->pin_in.ensure((size_t)total));
-  memcpy(s->pin_in.p, data, size);
-  memset(static_cast<uint8_t*>(s->pin_in.p) + size, 0, (size_t)(total - sz));
-  hipStream_t xs;
-  rc = exec_stream(ctx, *s, st, &xs, err, errlen);
-  if (!rc) rc = stage_h2d(ctx, *s, (size_t)total, xs, err, errlen);
-  if (rc) return rc;
-  (void)run_pipeline(ctx, *s, L,
-                     {static_cast<const uint8_t*>(s->bytes.p), (size_t)total, 1, &o, nullptr, 0, xs,
-                      1, nullptr, true},
-                     err, errlen);
-  Workspace& W = ctx->ws[s->ticket % ctx->lanes];
+  OneImage one;
+  rc = decode_one(ctx, data, size, info, o, ctx->piece_bytes, nullptr, &one, err, errlen);
+  if (rc && !one.ran) return rc;  // (the pipeline's own code is not looked at: diag[0] says)
+  const Layout& L = one.L;
+  Workspace& W = ctx->ws[one.slot->ticket % ctx->lanes];
   ImageInfo hi;
   HJ_HIP(hipMemcpy(&hi, W.info.p, sizeof(ImageInfo), hipMemcpyDeviceToHost));
   diag[0] = hi.status;

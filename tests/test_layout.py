@@ -53,13 +53,21 @@ def test_layout_matches_golden_under_sanitizers(tmp_path):
 
 def test_planner_includes_no_hip_header():
     """hj_layout.h / .cpp stay free of HIP (and of the headers that pull it
-    in), and the dump program sees the planner through hj_layout.h alone."""
-    allowed = {"../../include/spdl_hipjpeg.h", "hj_common.h", "hj_sws.h", "hj_sws_tile.h",
+    in), and the dump program sees the planner through hj_layout.h alone.
+    The same holds for the other two host-only units, the tar walk and the
+    staging copier, which include nothing of the project but their own header;
+    and the kernels' file includes neither."""
+    planner = {"../../include/spdl_hipjpeg.h", "hj_common.h", "hj_sws.h", "hj_sws_tile.h",
                "hj_views.h", "hj_layout.h"}
-    for name in ("hj_layout.h", "hj_layout.cpp"):
+    allowed = {"hj_layout.h": planner, "hj_layout.cpp": planner,
+               "hj_tar.h": set(), "hj_tar.cpp": {"hj_tar.h"},
+               "hj_pack.h": set(), "hj_pack.cpp": {"hj_pack.h"}}
+    for name, ok in allowed.items():
         src = open(os.path.join(CSRC, name)).read()
         assert not HIP_INCLUDE.search(src), name
-        assert set(re.findall(r'#\s*include\s*"([^"]+)"', src)) <= allowed, name
+        assert set(re.findall(r'#\s*include\s*"([^"]+)"', src)) <= ok, name
+    kernels = open(os.path.join(CSRC, "hj_kernels.hip")).read()
+    assert not re.search(r'#\s*include\s*"hj_(tar|pack)\.h"', kernels)
     src = open(DUMP).read()
     assert re.findall(r'#\s*include\s*"([^"]+)"', src) == ["../../spdl_amd/csrc/hj_layout.h"]
     assert not HIP_INCLUDE.search(src)
