@@ -99,8 +99,11 @@ inline HJ_HD uint32_t slot_bits(uint32_t maxbits, int sub_bits, uint32_t budget 
 //   [12,19) z advance: DC 1, AC coefficient run+1, ZRL 16, EOB or any other
 //           size-0 AC symbol 64 (ends the block)
 //   [19]    the symbol yields a coefficient
-//   [20]    AC size-0 symbol other than EOB / ZRL (the sequential decoder
-//           rejects it)
+//   [20]    EOB or ZRL; an AC size-0 symbol other than these, which the
+//           sequential decoder rejects, has neither bit (nor has the invalid
+//           code's entry, 1): bits [19,21) << 6 bound the z a symbol may reach
+//           -- 64 a coefficient, 128 (any) EOB / ZRL, 0 what is refused.
+//           (HJ_ENT_RULES=0: [20] marks the rejected symbol instead)
 //   [21,32) Full: the value (int11); Sub: the sub-table index
 constexpr uint32_t kKindSlow = 0;  // invalid, or a sub-table that did not fit
 constexpr uint32_t kKindCode = 1;  // code resolved, value bits follow
@@ -111,6 +114,54 @@ constexpr int kSubBits = 16 - kLutBits;
 #define HJ_SUB_POOL 2048
 #endif
 constexpr int kSubPool = HJ_SUB_POOL;  // entropy LDS entries for the second-level tables of a scan
+// The entropy step's instruction cuts, one switch each (=0 builds the tree
+// without that cut, for the A/B of profiles/r15/entropy_step):
+//   SUBADDR    every LDS table slot owns a fixed kSubShare entries of the pool
+//              and a sub-table sits at its level-1 index modulo the share, so
+//              the speculative second-level address is the slot and nine
+//              stream bits (no 64-bit shift of a per-slot offset); a table with
+//              more than kSubShare >> kSubBits sub-tables sends its image to
+//              the wide path
+//   SUBMARK    a level-1 cell that continues in a sub-table holds kSubMark in
+//              LDS: the kind test is one compare
+//   MORE       decode_state's second step, when the first already reached the
+//              slot's end, decodes the null entry instead of masking its results
+//   RULES      the entry's flag bits bound the z a symbol may reach (above): the
+//              write step's three rules are one shift, one and, one compare
+//   WIN2       the second step of a window read takes its 32 bits by one funnel
+//              shift from the 64 bits at the first step's position
+//   STOREBASE  the write step's store bases and bounds in vector registers
+//   NEXTBS     the block-in-MCU counted downwards in the hot loops: subtract, min
+//   FASTSTOP   the write step's distance to the segment end against a bound
+//              made once
+#ifndef HJ_ENT_SUBADDR
+#define HJ_ENT_SUBADDR 1
+#endif
+#ifndef HJ_ENT_SUBMARK
+#define HJ_ENT_SUBMARK 1
+#endif
+#ifndef HJ_ENT_MORE
+#define HJ_ENT_MORE 1
+#endif
+#ifndef HJ_ENT_RULES
+#define HJ_ENT_RULES 1
+#endif
+#ifndef HJ_ENT_WIN2
+#define HJ_ENT_WIN2 1
+#endif
+#ifndef HJ_ENT_STOREBASE
+#define HJ_ENT_STOREBASE 1
+#endif
+#ifndef HJ_ENT_NEXTBS
+#define HJ_ENT_NEXTBS 1
+#endif
+#ifndef HJ_ENT_FASTSTOP
+#define HJ_ENT_FASTSTOP 1
+#endif
+constexpr int kSubShareBits = 9;  // log2(kSubPool / 4 LDS table slots)
+constexpr int kSubShare = 1 << kSubShareBits;
+constexpr uint32_t kSubMark = kKindSub << 5;  // kind Sub, every other field 0: no real entry
+static_assert(!HJ_ENT_SUBADDR || 4 * kSubShare == kSubPool, "four slots share the pool evenly");
 
 // idct_rgb_kernel workgroup size: one block per thread, so a tile is
 // kFusedThreads / bpm MCUs of one MCU row (host and kernel agree on it)
@@ -135,7 +186,8 @@ inline HJ_HD uint32_t hj_entry(uint32_t kind, int len, int sym, bool is_dc, int 
     bad = run != 0;
   }
   const uint32_t sz = kind == kKindFull ? 0u : (uint32_t)size;
-  return ((uint32_t)len + sz) | (kind << 5) | (sz << 7) | (zinc << 12) | (coef << 19) | (bad << 20) |
+  const uint32_t b20 = HJ_ENT_RULES ? (uint32_t)(!coef && !bad) : bad;
+  return ((uint32_t)len + sz) | (kind << 5) | (sz << 7) | (zinc << 12) | (coef << 19) | (b20 << 20) |
          (((uint32_t)v & 0x7FFu) << kEntHiShift);
 }
 

@@ -467,8 +467,9 @@ __global__ void __launch_bounds__(256, 8) parse_kernel(const uint8_t* __restrict
   __syncthreads();
   if (tid == 0) {
     // Which entropy instance decodes this scan: NTAB = 4 takes <= 4 distinct
-    // tables whose long codes all fit the LDS sub-table pool (no canonical
-    // fallback); NTAB = 6 the rest.  Decided once here, so the entropy
+    // tables whose long codes all fit the LDS sub-table pool, each table its
+    // slot's share of it (no canonical fallback); the wide path takes the
+    // rest.  Decided once here, so the entropy
     // kernels test one flag instead of walking the tables in HBM.
     int ns = 0, seen = 0, subs = 0, slow = 0;
     for (int c = 0; c < s.info.ncomp; c++)
@@ -478,6 +479,10 @@ __global__ void __launch_bounds__(256, 8) parse_kernel(const uint8_t* __restrict
           ns++;
           subs += tab_nsub[slot];
           slow |= (tab_slow >> slot) & 1;
+#if HJ_ENT_SUBADDR
+          // (the LDS-only loops give every table slot kSubShare entries)
+          slow |= tab_nsub[slot] > (kSubShare >> kSubBits);
+#endif
         }
         seen |= 1 << slot;
       }
@@ -1001,9 +1006,13 @@ struct TabMap {
   uint32_t amap;    // ... of its AC table
   uint32_t cmap;    // its component
   uint32_t bs_end;  // 3 * blocks per MCU
-  // per LDS table slot t (16 bits each): (pool base - sub_lo) * 64, so a
-  // code's second-level entry is sub[(top 16 bits + soff_t) mod pool] --
-  // computable from the bits alone, without the level-1 entry
+#if HJ_ENT_NEXTBS
+  uint32_t rdmap, ramap;  // dmap / amap packed in reverse: block b at bit bs_end - 3 - 3b
+#endif
+  // HJ_ENT_SUBADDR=0 only (else 0: a slot's sub-tables sit in its fixed share
+  // of the pool, lookup<false>) -- per LDS table slot t (16 bits each): (pool
+  // base - sub_lo) * 64, so a code's second-level entry is sub[(top 16 bits +
+  // soff_t) mod pool], computable from the bits alone, without the level-1 entry
   uint64_t soff;
 };
 
@@ -1075,12 +1084,43 @@ __device__ __forceinline__ uint32_t dec_peek3(Dec& d, uint32_t* win, const uint3
   return rel & 31u;
 }
 
+// The second step's 32 bits: (hi, lo) are the 64 bits at pos, the first step
+// took nbits of them -- every entry takes 1..31 bits (an invalid code's one),
+// so the funnel shift's count 32 - nbits is in 1..31.
+__device__ __forceinline__ uint32_t win_next(uint32_t hi, uint32_t lo, uint32_t nbits) {
+  return __builtin_amdgcn_alignbit(hi, lo, 32u - nbits);
+}
+
 // the LDS table of the next symbol, and the block-in-MCU advance at a block end
 __device__ __forceinline__ uint32_t tab_slot(const TabMap& m, const Dec& d, bool is_dc) {
   return __builtin_amdgcn_ubfe(is_dc ? m.dmap : m.amap, d.bs, 3);
 }
 __device__ __forceinline__ uint32_t next_bs(const TabMap& m, uint32_t bs) {
   return bs + 3u == m.bs_end ? 0u : bs + 3u;
+}
+// decode_state and decode_write count the block-in-MCU downwards while they
+// run (Dec::bs = bs_end - 3 - 3b there, flipped on entry and on return; the
+// maps packed in reverse): the advance is a subtract and an unsigned min --
+// below 0 it wraps past every bound, to the MCU's first block.
+// HJ_ENT_NEXTBS=0: upwards, compare and select.
+__device__ __forceinline__ void hot_flip(const TabMap& m, Dec& d) {
+#if HJ_ENT_NEXTBS
+  d.bs = m.bs_end - 3u - d.bs;
+#endif
+}
+__device__ __forceinline__ uint32_t hot_tab(const TabMap& m, const Dec& d, bool is_dc) {
+#if HJ_ENT_NEXTBS
+  return __builtin_amdgcn_ubfe(is_dc ? m.rdmap : m.ramap, d.bs, 3);
+#else
+  return tab_slot(m, d, is_dc);
+#endif
+}
+__device__ __forceinline__ uint32_t hot_next(const TabMap& m, uint32_t bs) {
+#if HJ_ENT_NEXTBS
+  return min(bs - 3u, m.bs_end - 3u);
+#else
+  return next_bs(m, bs);
+#endif
 }
 
 // Canonical decode of a code that is not fully resolved by the LUT (longer
@@ -1126,9 +1166,19 @@ __device__ __forceinline__ uint32_t lookup(const SH& S, uint32_t t, uint32_t hi,
     // both levels read back to back (the second address from the bits and
     // the slot's offset, not from the first entry), one LDS latency per
     // symbol instead of two whenever any lane of the wave has a long code
+#if HJ_ENT_SUBADDR
+    // slot t's share of the pool, the sub-table at its level-1 index modulo
+    // the share (entropy_image's table load): slot bits above nine stream bits
+    const uint32_t a2 = (t << kSubShareBits) | ((hi >> 16) & (uint32_t)(kSubShare - 1));
+#else
     const uint32_t a2 = ((hi >> 16) + (uint32_t)(soff >> (16u * t))) & (uint32_t)(kSubPool - 1);
+#endif
     const uint32_t e2 = S.sub[a2];
+#if HJ_ENT_SUBMARK
+    return e == kSubMark ? e2 : e;
+#else
     return ((e >> 5) & 3) == kKindSub ? e2 : e;
+#endif
   }
   if (((e >> 5) & 3) == kKindSub)
     e = S.sub[((e >> kEntHiShift) << kSubBits) |
@@ -1180,6 +1230,7 @@ __device__ int decode_state(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
   // the start): counting ends is one add per step
   int nend = 0;
   const int open0 = d.z != 0u;
+  hot_flip(m, d);
   // two symbol steps per window read (a step takes <= 31 bits, so both lie in
   // the three words from the one holding pos): the second step's LUT read
   // waits for the first entry only, not for another window read
@@ -1187,10 +1238,17 @@ __device__ int decode_state(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
     uint64_t p01, p12;
     const uint32_t r = dec_peek3<NT>(d, win, words, p01, p12);
     uint32_t nbits;
+#if HJ_ENT_WIN2
+    const uint32_t hi0 = (uint32_t)((p01 << r) >> 32), lo0 = (uint32_t)((p12 << r) >> 32);
+#endif
     {
+#if HJ_ENT_WIN2
+      const uint32_t hi = hi0;
+#else
       const uint32_t hi = (uint32_t)((p01 << r) >> 32);
+#endif
       const uint32_t z = d.z;
-      const uint32_t t = tab_slot(m, d, z == 0u);
+      const uint32_t t = hot_tab(m, d, z == 0u);
       const uint32_t e = lookup<SLOW>(S, t, hi, z == 0u, m.soff);
       // an invalid code's entry (1) takes one bit, advances nothing and
       // starts no block
@@ -1199,28 +1257,47 @@ __device__ int decode_state(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
       const uint32_t zn = z + __builtin_amdgcn_ubfe(e, 12, 7);
       const bool bend = zn >= 64u;
       nend += bend ? 1 : 0;
-      const uint32_t bsn = next_bs(m, d.bs);
+      const uint32_t bsn = hot_next(m, d.bs);
       d.z = bend ? 0u : zn;
       d.bs = bend ? bsn : d.bs;
     }
     {
       const bool more = d.pos < end;
+#if HJ_ENT_WIN2
+      const uint32_t hi = win_next(hi0, lo0, nbits);
+#else
       const uint32_t r2 = r + nbits;  // < 63
       const uint64_t pr = r2 < 32u ? p01 : p12;
       const uint32_t hi = (uint32_t)((pr << (r2 & 31u)) >> 32);
+#endif
       const uint32_t z = d.z;
-      const uint32_t t = tab_slot(m, d, z == 0u);
+      const uint32_t t = hot_tab(m, d, z == 0u);
+#if HJ_ENT_MORE
+      // past the end: the null entry (no bits, no advance, so no block end)
+      // in place of the symbol's -- one select instead of three masked results
+      const uint32_t es = lookup<SLOW>(S, t, hi, z == 0u, m.soff);
+      const uint32_t e = more ? es : 0u;
+      dec_skip(d, e & 31u);
+      const uint32_t zn = z + __builtin_amdgcn_ubfe(e, 12, 7);
+      const bool bend = zn >= 64u;
+      nend += bend ? 1 : 0;
+      const uint32_t bsn = hot_next(m, d.bs);
+      d.z = bend ? 0u : zn;
+      d.bs = bend ? bsn : d.bs;
+#else
       const uint32_t e = lookup<SLOW>(S, t, hi, z == 0u, m.soff);
       const uint32_t n2 = more ? (e & 31u) : 0u;
       dec_skip(d, n2);
       const uint32_t zn = z + __builtin_amdgcn_ubfe(e, 12, 7);
       const bool bend = more && zn >= 64u;
       nend += bend ? 1 : 0;
-      const uint32_t bsn = next_bs(m, d.bs);
+      const uint32_t bsn = hot_next(m, d.bs);
       d.z = bend ? 0u : (more ? zn : z);
       d.bs = bend ? bsn : d.bs;
+#endif
     }
   }
+  hot_flip(m, d);
   return nend + (d.z != 0u ? 1 : 0) - open0;
 }
 
@@ -1388,6 +1465,7 @@ __device__ int decode_write(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
                             const TabMap& m, const uint32_t end, const uint32_t seg_end,
                             const int seg_end_blk, BlockOut& o, int& nb, bool& done) {
   int rc = kOk;
+  hot_flip(m, d);
   // Fast path, straight-line: a symbol that can trigger none of the rules
   // below -- a valid code, no run past coefficient 63, not within 32 bits of
   // the segment end, not a DC symbol once the segment's last block started
@@ -1400,10 +1478,20 @@ __device__ int decode_write(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
   auto fast_step = [&](const uint32_t hi) -> bool {
     const uint32_t z = d.z;
     const bool is_dc = z == 0;
-    const uint32_t e = lookup<SLOW>(S, tab_slot(m, d, is_dc), hi, is_dc, m.soff);
+    const uint32_t e = lookup<SLOW>(S, hot_tab(m, d, is_dc), hi, is_dc, m.soff);
     const uint32_t sz = __builtin_amdgcn_ubfe(e, 7, 5);
     const uint32_t nbits = e & 31u;
     const uint32_t zn = z + __builtin_amdgcn_ubfe(e, 12, 7);
+#if HJ_ENT_RULES
+    // One unsigned test for the three rules: the entry's flag bits bound the
+    // z its symbol may reach (hj_common.h) -- 64 a coefficient (none past
+    // 63), 128 an EOB / ZRL (zn <= 127: any), 0 an invalid code or an AC
+    // size-0 symbol other than these (zn - 1 wraps for the invalid code at z
+    // = 0, which advances nothing).
+    const uint32_t lim = (e >> 13) & 0xC0u;
+    const bool coef = lim == 64u;
+    if (zn - 1u >= lim) return false;
+#else
     const bool coef = (e >> 19) & 1u;
     // One unsigned test for the three rules: the entry is valid (kind !=
     // Slow) and not an AC size-0 symbol other than EOB / ZRL -- (e & (bad |
@@ -1413,6 +1501,7 @@ __device__ int decode_write(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
     const uint32_t rules =
         ((64u - zn) & ((e & 0x80000u) << 12)) | ((e & 0x100060u) - 0x20u);
     if (rules > 0x40u) return false;
+#endif
     const int v = sym_value(e, hi, nbits, sz);
     dec_skip(d, nbits);
     const bool ac = coef & !is_dc;
@@ -1423,26 +1512,42 @@ __device__ int decode_write(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
     nb += is_dc ? 1 : 0;
     const bool bend = zn >= 64u;
     if (bend) close_block(o, nb - 1);
-    const uint32_t bsn = next_bs(m, d.bs);
+    const uint32_t bsn = hot_next(m, d.bs);
     d.z = bend ? 0u : zn;
     d.bs = bend ? bsn : d.bs;
     return true;
   };
+#if HJ_ENT_FASTSTOP
+  // (pos + 32 > seg_end as one compare with a bound made once: pos >= seg_end - 31)
+  const uint32_t near_end = seg_end >= 31u ? seg_end - 31u : 0u;
+  auto fast_stop = [&]() -> bool {
+    const bool is_dc = d.z == 0u;
+    return (is_dc & ((d.pos >= end) | (nb >= seg_end_blk))) | (d.pos >= near_end);
+  };
+#else
   auto fast_stop = [&]() -> bool {
     const bool is_dc = d.z == 0u;
     return (is_dc & ((d.pos >= end) | (nb >= seg_end_blk))) | (d.pos + 32u > seg_end);
   };
+#endif
   // two steps per window read (as decode_state)
   for (;;) {
     if (fast_stop()) break;
     uint64_t p01, p12;
     const uint32_t r = dec_peek3<NT>(d, win, words, p01, p12);
     const uint32_t pos0 = d.pos;
+#if HJ_ENT_WIN2
+    const uint32_t hi0 = (uint32_t)((p01 << r) >> 32), lo0 = (uint32_t)((p12 << r) >> 32);
+    if (!fast_step(hi0)) break;
+    if (fast_stop()) break;
+    if (!fast_step(win_next(hi0, lo0, d.pos - pos0))) break;  // (a step taken took >= 1 bit)
+#else
     if (!fast_step((uint32_t)((p01 << r) >> 32))) break;
     if (fast_stop()) break;
     const uint32_t r2 = r + (d.pos - pos0);  // < 63
     const uint64_t pr = r2 < 32u ? p01 : p12;
     if (!fast_step((uint32_t)((pr << (r2 & 31u)) >> 32))) break;
+#endif
   }
   // a block in progress is this run's only if the fast path started it (a
   // run that entered inside the previous run's block -- skip_open_block
@@ -1452,7 +1557,7 @@ __device__ int decode_write(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
     const uint32_t hi = dec_peek<NT>(d, win, words);
     const uint32_t z = d.z;
     const bool is_dc = z == 0;
-    const uint32_t e = lookup<SLOW>(S, tab_slot(m, d, is_dc), hi, is_dc, m.soff);
+    const uint32_t e = lookup<SLOW>(S, hot_tab(m, d, is_dc), hi, is_dc, m.soff);
     const bool valid = (e & 0x60u) != 0u;
     const uint32_t sz = __builtin_amdgcn_ubfe(e, 7, 5);
     const uint32_t nbits = e & 31u;
@@ -1460,7 +1565,9 @@ __device__ int decode_write(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
     dec_skip(d, nbits);
     const uint32_t zinc = __builtin_amdgcn_ubfe(e, 12, 7);
     const bool coef = valid && ((e >> 19) & 1u);
-    const bool bad = !valid || (coef && z + zinc > 64u) || ((e >> 20) & 1u);
+    // (the rejected AC size-0 symbol: valid with neither flag bit, hj_common.h)
+    const bool refused = HJ_ENT_RULES ? (e & 0x180000u) == 0u : ((e >> 20) & 1u) != 0u;
+    const bool bad = !valid || (coef && z + zinc > 64u) || refused;
     // The sequential decoder's rules, branch-free (the lanes of a wave sit
     // at unrelated symbols): it stops at the segment's last block and never
     // reads what follows; anything else that is invalid is an error.
@@ -1485,12 +1592,13 @@ __device__ int decode_write(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
     rc = (bad && !past_a) ? kErrBadHuffman : ((trunc && !past_b) ? kErrTruncated : kOk);
     const bool bend = zn >= 64u;
     if (bend && !stop && o.open) close_block(o, nb - 1);
-    const uint32_t bsn = next_bs(m, d.bs);
+    const uint32_t bsn = hot_next(m, d.bs);
     d.z = bend ? 0u : zn;
     d.bs = bend ? bsn : d.bs;
   }
   // the segment ended (or failed) inside a block: keep what it decoded
   if (o.open && d.z != 0u) close_block(o, nb - 1);
+  hot_flip(m, d);
   return rc;
 }
 
@@ -1933,7 +2041,7 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
   // table slots and components per block-in-MCU (TabMap); the DC pass
   // keeps a 2-bit component map
   uint32_t bcomp = 0;  // 2-bit component per block-in-MCU (DC pass)
-  TabMap tm{0u, 0u, 0u, 0u, 0ull};
+  TabMap tm{};
   {
     int slots[kMaxTabs], ns = 0, ldc[kMaxComp] = {}, lac[kMaxComp] = {};
     for (int c = 0; c < in.ncomp; c++) {
@@ -1959,19 +2067,33 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       }
       const HuffTable& T = luts[ref];
       const int nsub = T.nsub;
-      const bool fits = (pool + nsub) << kSubBits <= kSubPool;
+      // the LDS-only loops (lookup<false>): slot i's sub-tables in its share
+      // of the pool, each at its level-1 index modulo the share -- they are
+      // consecutive level-1 cells and parse_kernel sent a table with more of
+      // them than the share holds to the wide path, so no two collide
+      constexpr bool kShared = HJ_ENT_SUBADDR && !kSlow;
+      const bool fits = kShared ? nsub << kSubBits <= kSubShare
+                                : (pool + nsub) << kSubBits <= kSubPool;
       const int base = pool;
-      if (fits) pool += nsub;
-      if (fits && nsub > 0)
+      if (fits && !kShared) pool += nsub;
+      if (!HJ_ENT_SUBADDR && fits && nsub > 0)
         tm.soff |= (uint64_t)((uint32_t)((base - T.sub_lo) << kSubBits) & 0xFFFFu) << (16 * i);
       for (int k = tid; k < kLutSize; k += NT) {
         uint32_t e = T.lut[k];
-        if ((e >> 5 & 3) == kKindSub) e = fits ? e + ((uint32_t)base << kEntHiShift) : 1u;
+        if ((e >> 5 & 3) == kKindSub) {
+          if (!fits) e = 1u;
+          else if (HJ_ENT_SUBMARK && !kSlow) e = kSubMark;
+          else e += (uint32_t)base << kEntHiShift;
+        }
         S.lut[i][k] = e;
       }
-      if (fits)
+      if (fits && kShared) {
+        for (int k = tid; k < nsub << kSubBits; k += NT)
+          S.sub[(i << kSubShareBits) + (((T.sub_lo << kSubBits) + k) & (kSubShare - 1))] = T.sub[k];
+      } else if (fits) {
         for (int k = tid; k < nsub << kSubBits; k += NT)
           S.sub[(base << kSubBits) + k] = T.sub[k];
+      }
       if (tid < 18) S.maxcode[i][tid] = T.maxcode[tid];
       if (tid < 17) S.valoff[i][tid] = T.valoff[tid];
       for (int k = tid; k < 256; k += NT) S.vals[i][k] = T.vals[k];
@@ -1983,6 +2105,10 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       tm.dmap |= (uint32_t)ldc[c] << (3 * b);
       tm.amap |= (uint32_t)lac[c] << (3 * b);
       tm.cmap |= (uint32_t)c << (3 * b);
+#if HJ_ENT_NEXTBS
+      tm.rdmap |= (uint32_t)ldc[c] << (3 * (bpm - 1 - b));
+      tm.ramap |= (uint32_t)lac[c] << (3 * (bpm - 1 - b));
+#endif
     }
     tm.bs_end = 3u * (uint32_t)bpm;
     if (tid == 0) {
@@ -2384,6 +2510,13 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       o.cur = (uint32_t)b0 * 64u;
       o.last = (uint32_t)nblocks * 64u - 1u;
       o.nblk = (uint32_t)nblocks;
+#if HJ_ENT_STOREBASE
+      // The store bases and bounds are uniform, and the kernel has no scalar
+      // register left for them: kept there, each store of the write step
+      // fetched them back from spill lanes (v_readlane + wait states).  As
+      // vector registers they cost the step nothing.
+      asm volatile("" : "+v"(o.ents), "+v"(o.bdesc), "+v"(o.last), "+v"(o.nblk));
+#endif
 #if HJ_ABLATIONS
       o.no_list = (ablate & kAblEntList) != 0;
       o.no_desc = (ablate & kAblEntDesc) != 0;
