@@ -351,6 +351,76 @@ int spdl_hj_set_views(spdl_hj_ctx* ctx, const spdl_hj_view_group* groups, int32_
 enum { SPDL_HJ_FLIP_H = 1, SPDL_HJ_FLIP_V = 2 }; /* both: a rotation by 180 degrees */
 int spdl_hj_set_flips(spdl_hj_ctx* ctx, const uint8_t* flips, int32_t n);
 
+/* ---- output orientation (additive in ABI 7: three functions, one enum; a
+ * binding finds them by symbol) ------------------------------------------------
+ * The other four orientations of a rectangle -- transpose, transverse and the
+ * two quarter turns -- and with them what a JPEG's EXIF tag 0x0112 asks for,
+ * in the store of the output kernel.  An orientation code is 0..7: bits 0 and
+ * 1 are the flips above, bit 2 is a transpose applied BEFORE them.  With C the
+ * chain's result, cw wide and ch tall:
+ *   with T      A(x, y) = C(y, x), ch wide and cw tall;   without   A = C
+ *   then        out(x, y) = A(H ? aw - 1 - x : x, V ? ah - 1 - y : y)
+ * with aw x ah the size of A.  Codes 0..3 are exactly the flips.
+ *
+ * The output spec describes the FINAL output.  For an image or view with T,
+ * the chain ahead of the transpose is the spdl_hj_output with each pair
+ * swapped -- (fit_w, fit_h), (pad_w, pad_h), (crop_w, crop_h) -- so a final
+ * W x H is libavfilter's
+ *   scale=w=H:h=W...,pad=w=PH:h=PW,crop=w=CH:h=CW,transpose=dir
+ * A source crop rectangle and a view's rectangle stay in the stored frame's
+ * coordinates: they are not swapped.  Every image of a batch and every view of
+ * a group so still produces one shape and one byte count, whatever its code;
+ * spdl_hj_output_size is unchanged -- for a T image pass it the stored
+ * frame's (h, w).  With resize == 0 the "one size" rule is about final sizes:
+ * a stored 640x480 frame with code 0 and a stored 480x640 frame with code 5
+ * share a batch.  Like a flip, the orientation changes no pixel: the bytes are
+ * the chain's, permuted, pad included.
+ *
+ * Not offered: a transpose AHEAD of the scale.  swscale's horizontal pass (to
+ * 15 bits) and its vertical pass round differently, so rotating the source
+ * first has other pixels, and nothing here pins them.  The geometry is the
+ * same; the pixels are those of the stored frame's chain.  Nor a transposed
+ * SPDL_HJ_FMT_YUV: a transposed 4:2:2 frame is another pixel format.
+ *
+ * Consumption, counts, the indexing with views (one entry per view, the
+ * groups concatenated), NULL clearing and "spdl_hj_decode_planes and
+ * spdl_hj_debug_entropy neither use nor clear" are exactly as for
+ * spdl_hj_set_flips.  SPDL_HJ_ERR_INVALID_ARG from the consuming call, with
+ * nothing written: a value above 7; a wrong count; csc = JFIF with any
+ * non-zero code; a T code with SPDL_HJ_FMT_YUV; orients together with flips
+ * on one submission.  Codes 0..3 with SPDL_HJ_FMT_YUV behave as flips do.  An
+ * all-zero array is byte-identical to no call and keeps the fused
+ * full-resolution path; any non-zero code at full resolution takes the
+ * generic output kernel, as a flip does.
+ *
+ * Cost.  A submission without a T code runs the kernels of a flipped one.  One
+ * with a T code runs another instantiation of the output kernel, whose u8
+ * tile leaves as row segments of 4-byte stores with byte ends: for the 256
+ * bench images into 224 x 224 rgb24 on one lane, 0.97 of the unoriented rate
+ * with the eight codes dealt evenly and 0.96 with every image turned, where
+ * a torch pass after an unoriented decode leaves 0.74. */
+enum { SPDL_HJ_ORIENT_H = 1, SPDL_HJ_ORIENT_V = 2, SPDL_HJ_ORIENT_T = 4 };
+int spdl_hj_set_orients(spdl_hj_ctx* ctx, const uint8_t* orients, int32_t n);
+
+/* The EXIF orientation (tag 0x0112) of a JPEG, 1..8, host only.  The walk goes
+ * from SOI to the first SOS and takes the first APP1 whose payload starts
+ * "Exif\0\0"; its TIFF header is "II*\0" or "MM\0*"; in IFD0, at its offset,
+ * the tag counts when its type is SHORT or LONG, its count 1 and its value in
+ * 1..8.  Every read is checked against the segment.  Anything else -- no APP1,
+ * XMP in APP1, a truncated segment, an offset outside it, another type or
+ * count, a value of 0 or 9 -- is orientation 1 with return 0: EXIF never fails
+ * an image.  The function fails only for what spdl_hj_get_image_info fails
+ * for (spdl_hj_image_info itself does not grow: callers pass arrays of it). */
+int spdl_hj_get_orientation(const uint8_t* data, size_t size, int32_t* exif);
+
+/* EXIF orientation -> orientation code (-1 outside 1..8):
+ *   1 -> 0       2 -> 1 (H)     3 -> 3 (HV)      4 -> 2 (V)
+ *   5 -> 4 (T)   6 -> 5 (T|H)   7 -> 7 (T|H|V)   8 -> 6 (T|V)
+ * so the decoded output is the image as a viewer shows it (Pillow's
+ * ImageOps.exif_transpose).  A flip of the displayed image composes as
+ * code ^ flip bits. */
+int spdl_hj_orient_code(int32_t exif);
+
 /* ABI version of the loaded library (== SPDL_HJ_ABI_VERSION). */
 int spdl_hj_abi_version(void);
 

@@ -57,6 +57,9 @@ EXPORTED = (
     "spdl_hj_set_crops",
     "spdl_hj_set_views",
     "spdl_hj_set_flips",
+    "spdl_hj_set_orients",
+    "spdl_hj_get_orientation",
+    "spdl_hj_orient_code",
 )
 
 
@@ -105,6 +108,36 @@ def _flip(f) -> int:
     if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f <= 3:
         raise ValueError(f"a flip is 0..3, 'h', 'v', 'hv' or None, not {f!r}")
     return int(f)
+
+
+ORIENT_H, ORIENT_V, ORIENT_T = 1, 2, 4  # SPDL_HJ_ORIENT_*
+# (the transposes by libavfilter's names for transpose=dir)
+_ORIENT_NAMES = {**_FLIP_NAMES, "t": 4, "cclock_flip": 4, "clock": 5, "cclock": 6, "clock_flip": 7}
+_ORIENT_WHAT = ("an orientation is 0..7, 'h', 'v', 'hv', 't', 'cclock_flip', 'clock', 'cclock', "
+                "'clock_flip' or None")
+# EXIF orientation (tag 0x0112) -> orientation code: the output is the image
+# as a viewer shows it (spdl_hj_orient_code states the same table)
+_EXIF_CODES = {1: 0, 2: 1, 3: 3, 4: 2, 5: 4, 6: 5, 7: 7, 8: 6}
+
+
+def _orient(o) -> int:
+    """An output orientation: ``0..7`` (bit 0 horizontal flip, bit 1 vertical,
+    bit 2 a transpose ahead of them), a flip spelling, ``"t"`` or one of
+    ``transpose``'s direction names -> SPDL_HJ_ORIENT_* bits."""
+    if isinstance(o, (str, type(None))):
+        if o not in _ORIENT_NAMES:
+            raise ValueError(f"{_ORIENT_WHAT}, not {o!r}")
+        return _ORIENT_NAMES[o]
+    if isinstance(o, bool) or not isinstance(o, int) or not 0 <= o <= 7:
+        raise ValueError(f"{_ORIENT_WHAT}, not {o!r}")
+    return int(o)
+
+
+def exif_code(exif: int) -> int:
+    """The orientation code of EXIF orientation ``1..8``."""
+    if isinstance(exif, bool) or not isinstance(exif, int) or exif not in _EXIF_CODES:
+        raise ValueError(f"an EXIF orientation is 1..8, not {exif!r}")
+    return _EXIF_CODES[exif]
 
 
 def _view_rect(r) -> Rect:
@@ -165,6 +198,12 @@ class Output:
     output: the last node of the chain, ``...,hflip`` / ``vflip`` after scale,
     pad and crop (include/spdl_hipjpeg.h "output flips").  It travels through
     ``spdl_hj_set_flips`` as well.
+
+    ``orient`` (``0..7`` or a spelling of :func:`_orient`) is the whole
+    orientation, a transpose included (include/spdl_hipjpeg.h "output
+    orientation"): the spec then describes the FINAL output, and an image with
+    the transpose bit runs the chain with ``fit``, ``pad`` and ``crop`` swapped.
+    It travels through ``spdl_hj_set_orients`` and excludes ``flip``.
     """
 
     pix_fmt: str = "rgb"
@@ -187,6 +226,7 @@ class Output:
     csc: str = "swscale"
     src_crop: tuple | None = None
     flip: int | str | None = None
+    orient: int | str | None = None
 
     def to_c(self) -> OutputSpec:
         if self.pix_fmt not in PIX_FMTS:
@@ -258,7 +298,10 @@ class ViewGroup:
     output chain ``out``, the views ``[(image, rect_or_None), ...]`` or
     ``[(image, rect_or_None, flip), ...]`` and the device buffer
     ``[len(views), ...]`` they are written to in view order.  A view without a
-    flip of its own has ``out.flip``.
+    flip of its own has ``out.flip``.  A fourth element is the view's
+    orientation, ``(image, rect_or_None, None, orient)`` (``0..7``; its flip
+    is then ``None``); a view without one has ``out.orient``.  A submission
+    with any orientation goes through ``spdl_hj_set_orients``.
     After the consuming call, ``statuses`` holds the per-view codes (0, or the
     status of a view the host refused alone); a view is valid when its own
     status and its image's are both 0."""
@@ -271,19 +314,26 @@ class ViewGroup:
         self.out, self.out_ptr, self.out_bytes = out, int(out_ptr), int(out_bytes)
         self.views = []
         self.flips = []  # per view, SPDL_HJ_FLIP_* bits
+        self.orients = []  # per view, SPDL_HJ_ORIENT_* bits; None: no orientation of its own
+        if out.flip is not None and out.orient is not None:
+            raise ValueError("Output.flip and Output.orient are exclusive")
         for v in views:
-            what = f"a view is (image, rect_or_None) or (image, rect_or_None, flip 0..3), not {v!r}"
+            what = ("a view is (image, rect_or_None), (image, rect_or_None, flip 0..3) or "
+                    f"(image, rect_or_None, None, orient 0..7), not {v!r}")
             try:
-                image, rect, *flip = v
-                if len(flip) > 1:
+                image, rect, *rest = v
+                if len(rest) > 2 or (len(rest) == 2 and rest[0] is not None):
                     raise ValueError
-                flip = _flip(flip[0] if flip else out.flip)
+                orient = rest[1] if len(rest) == 2 else out.orient
+                flip = _flip(rest[0] if len(rest) == 1 else None if orient is not None else out.flip)
+                orient = None if orient is None else _orient(orient)
             except (TypeError, ValueError):
                 raise ValueError(what) from None
             if isinstance(image, bool) or not isinstance(image, int):
                 raise ValueError(what)
             self.views.append((image, _view_rect(rect)))
             self.flips.append(flip)
+            self.orients.append(orient)
         n = len(self.views)
         self._views = (View * max(n, 1))(*[View(i, r) for i, r in self.views])
         self._status = (ctypes.c_int32 * max(n, 1))()
@@ -314,6 +364,13 @@ def _has_flips(out: Output, flips, views) -> bool:
     """The submission names a flip somewhere (else no flip call is made)."""
     return flips is not None or out.flip is not None or \
         (views is not None and any(any(g.flips) for g in views))
+
+
+def _has_orients(out: Output, orients, views) -> bool:
+    """The submission names an orientation somewhere: it then goes through
+    ``spdl_hj_set_orients``, its flips with it (codes 0..3)."""
+    return orients is not None or out.orient is not None or \
+        (views is not None and any(o is not None for g in views for o in g.orients))
 
 
 _LIB = None
@@ -389,6 +446,10 @@ def lib() -> ctypes.CDLL:
             L.spdl_hj_set_views.argtypes = [vp, ctypes.POINTER(ViewGroupSpec), i32]
         if hasattr(L, "spdl_hj_set_flips"):  # (likewise)
             L.spdl_hj_set_flips.argtypes = [vp, vp, i32]
+        if hasattr(L, "spdl_hj_set_orients"):  # (likewise)
+            L.spdl_hj_set_orients.argtypes = [vp, vp, i32]
+            L.spdl_hj_get_orientation.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(i32)]
+            L.spdl_hj_orient_code.argtypes = [i32]
         ver = L.spdl_hj_abi_version()
         # (an explicitly chosen older build, ABI >= 5, loads for A/B runs)
         if ver != ABI_VERSION and not (os.environ.get("SPDL_AMD_LIB") and 5 <= ver < ABI_VERSION):
@@ -406,6 +467,19 @@ def get_image_info(data) -> ImageInfo:
     if rc:
         raise RuntimeError(f"Failed to decode an image. (header probe: status {rc})")
     return info
+
+
+def get_orientation(data) -> int:
+    """The EXIF orientation ``1..8`` of a JPEG (spdl_hj_get_orientation; host
+    only): 1 for whatever is absent or malformed -- EXIF never fails an image;
+    what fails :func:`get_image_info` fails here."""
+    addr, size, keep = buffer_address(data)
+    exif = ctypes.c_int32(1)
+    rc = lib().spdl_hj_get_orientation(addr, size, ctypes.byref(exif))
+    del keep
+    if rc:
+        raise RuntimeError(f"Failed to decode an image. (header probe: status {rc})")
+    return int(exif.value)
 
 
 def crop_rect(info: ImageInfo, rect) -> tuple[int, tuple | None]:
@@ -659,6 +733,41 @@ class Decoder:
                 raise ValueError(f"{len(flips)} flips for a batch of {n} images")
             self.set_flips(flips)
 
+    def set_orients(self, orients) -> None:
+        """The output orientations of the next batch submission
+        (spdl_hj_set_orients): a sequence of ``0..7`` or spellings of
+        :func:`_orient`, one per image, or per view with views; ``None`` or an
+        empty one clears them.  ``bytes`` go to the library as they are."""
+        if not isinstance(orients, (bytes, bytearray)):
+            orients = bytes(_orient(o) for o in orients) if orients is not None else b""
+        arr = (ctypes.c_uint8 * max(len(orients), 1))(*orients)
+        if lib().spdl_hj_set_orients(self._h, arr if orients else None, len(orients)):
+            raise ValueError("invalid orientations")
+
+    def _orients(self, out: Output, orients, n: int, views=None, flips=None) -> None:
+        """Hand the submission's orientations to the context: ``orients`` per
+        image, or ``out.orient`` for every image; with views, each view's own
+        (a view that has only a flip goes as that flip's code)."""
+        if flips is not None:
+            raise ValueError("flips= and orients= are exclusive: an orientation code holds the "
+                             "flip bits")
+        if views is not None:
+            if orients is not None:
+                raise ValueError("with views= an orientation belongs to its view: "
+                                 "(image, rect, None, orient)")
+            self.set_orients(bytes(f if o is None else o
+                                   for g in views for f, o in zip(g.flips, g.orients)))
+            return
+        if out.flip is not None:
+            raise ValueError("Output.flip and an orientation are exclusive")
+        if orients is not None and out.orient is not None:
+            raise ValueError("orients= and Output.orient are exclusive")
+        if orients is None:
+            orients = [out.orient] * n
+        if len(orients) != n:
+            raise ValueError(f"{len(orients)} orients for a batch of {n} images")
+        self.set_orients(orients)
+
     def _crops(self, out: Output, crops, n: int) -> None:
         """Hand the submission's rectangles to the context: ``crops`` per
         image, or ``out.src_crop`` for every image."""
@@ -673,7 +782,7 @@ class Decoder:
 
     def decode_batch(self, datas, out: Output, out_ptr: int, out_bytes: int, stream=None,
                      sync: bool = True, check: bool = True, crops=None, views=None,
-                     flips=None) -> list[int]:
+                     flips=None, orients=None) -> list[int]:
         """Per-image statuses.  A failed image raises RuntimeError unless
         ``check`` is False (synchronous calls), which returns the statuses.
         ``crops``: a source crop ``(x, y, w, h)`` or ``None`` per image.
@@ -682,7 +791,9 @@ class Decoder:
         of ``out`` only ``idct`` is used.  The per-view statuses are each
         group's ``statuses``; with ``check=False`` a refused view does not
         raise either.  ``flips``: an output flip (``0..3``, ``"h"``, ``"v"``,
-        ``"hv"`` or ``None``) per image; with views, each view carries its own."""
+        ``"hv"`` or ``None``) per image; with views, each view carries its own.
+        ``orients``: an orientation (``0..7`` or a spelling of :func:`_orient`)
+        per image instead of ``flips`` (spdl_hj_set_orients)."""
         n = len(datas)
         if n == 0:
             raise RuntimeError("Failed to decode an image. (the batch is empty)")
@@ -705,12 +816,12 @@ class Decoder:
                 _stream_handle(stream), int(bool(sync)), status, err, 1024,
             )
         return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                                    check, status, call))
+                                    check, status, call, orients))
 
     def _submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync, check, status,
-                call):
+                call, orients=None):
         """What the three batch submissions share: the views, crops and flips
-        go to the context, ``call(err)`` -- the method's own marshalling and
+        (or orientations) go to the context, ``call(err)`` -- the method's own marshalling and
         its native call -- returns the library's code, and a failure raises
         unless ``check`` is False on a synchronous call that refused an image
         (``status``) or a view.  (The methods reach it through the class: they
@@ -720,7 +831,9 @@ class Decoder:
             self.set_views(views)
         else:
             self._crops(out, crops, n)
-        if _has_flips(out, flips, views):
+        if _has_orients(out, orients, views):
+            Decoder._orients(self, out, orients, n, views, flips)
+        elif _has_flips(out, flips, views):
             self._flips(out, flips, n, views)
         err = ctypes.create_string_buffer(1024)
         rc = call(err)
@@ -731,7 +844,7 @@ class Decoder:
     def decode_batch_device(self, dev_ptr: int, dev_bytes: int, offsets, sizes, infos,
                             out: Output, out_ptr: int, out_bytes: int, stream=None,
                             sync: bool = True, crops=None, check: bool = True,
-                            views=None, flips=None) -> list[int]:
+                            views=None, flips=None, orients=None) -> list[int]:
         """``offsets``/``sizes``: sequences or int64 numpy arrays; ``infos``: a
         sequence of ImageInfo or a prebuilt ``(ImageInfo * n)`` array (pass the
         same objects again to skip re-marshalling on every call)."""
@@ -751,7 +864,7 @@ class Decoder:
                 status.ctypes.data, err, 1024,
             )
         return Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                               check, status, call).tolist()
+                               check, status, call, orients).tolist()
 
     def _spec(self, out: Output) -> OutputSpec:
         cache = self.__dict__.setdefault("_spec_cache", {})
@@ -810,7 +923,7 @@ class Decoder:
 
     def decode_staged(self, ticket: int, nbytes: int, offsets, sizes, out: Output, out_ptr: int,
                       out_bytes: int, stream=None, sync: bool = True, crops=None,
-                      check: bool = True, views=None, flips=None) -> list[int]:
+                      check: bool = True, views=None, flips=None, orients=None) -> list[int]:
         n = len(offsets)
         status = (ctypes.c_int32 * max(n, 1))()
 
@@ -822,7 +935,7 @@ class Decoder:
                 self._h, int(ticket), int(nbytes), offs, szs, n, ctypes.byref(spec), out_ptr,
                 out_bytes, _stream_handle(stream), int(bool(sync)), status, err, 1024)
         return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                                    check, status, call))[:n]
+                                    check, status, call, orients))[:n]
 
     def debug_entropy(self, data, nblocks: int):
         """Coefficients / destuffed bytes / diagnostics of one image (tests)."""

@@ -155,10 +155,11 @@ struct Slot {
       int64_t off, size;
       spdl_hj_image_info info;
       spdl_hj_rect rect;  // its source crop (has_rects)
-      uint8_t flip;       // its output flip (has_flips)
+      uint8_t flip;       // its output flip or orientation code (has_flips)
     };
     std::vector<Item> items;
     bool has_rects = false, has_flips = false;  // the batch had crops / flips
+    bool oriented = false;  // ... the flips came as orientation codes (spdl_hj_set_orients)
   } retry;
 };
 
@@ -270,6 +271,8 @@ struct spdl_hj_ctx {
   std::vector<spdl_hj_rect> crops;
   // spdl_hj_set_flips: the output flips of the next batch submission
   std::vector<uint8_t> flips;
+  // spdl_hj_set_orients: its orientation codes (both set: the planner refuses)
+  std::vector<uint8_t> orients;
   int64_t idct_workgroups = 0;  // IDCT workgroups the last submission launched
   int64_t entropy_workgroups = 0;  // ... and its entropy work items (images, or their pieces)
   // spdl_hj_set_views: the views of the next batch submission
@@ -445,6 +448,7 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
               st, &b->desc));
   b->work = reinterpret_cast<uint32_t*>(b->desc + b->ndesc);
   b->flips = L.flips.empty() ? nullptr : reinterpret_cast<const uint8_t*>(b->work + b->nwork);
+  b->transposed = L.transposed;
   HJ_HIP(grow(W.chain, (size_t)(kChainHead + L.chain_granules) * 8 + 64, st, &b->chain));
   HJ_HIP(grow(W.maps, (size_t)(L.ds_wgs + L.idct_wgs + L.hs_wgs + L.sws_wgs) * 4 + 64, st,
               &b->ds_map));
@@ -477,6 +481,7 @@ struct Submission {
   bool planes_only = false;             // stop at the planes (no output stage)
   const spdl_hj_rect* crops = nullptr;  // the batch's source crops, for the retry record
   const uint8_t* flips = nullptr;       // ... and its output flips (one per image)
+  bool oriented = false;                // (they are orientation codes)
 };
 
 // An output chain's share of the output kernels' parameters: the batch's
@@ -681,6 +686,7 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   if (!sub.planes_only) {
     R.has_rects = sub.crops != nullptr;
     R.has_flips = sub.flips != nullptr;
+    R.oriented = sub.oriented;
     for (const auto& m : L.multi)
       R.items.push_back({m.first, L.desc[m.first].in_off, L.desc[m.first].in_size, m.second,
                          sub.crops ? sub.crops[m.first] : spdl_hj_rect{},
@@ -742,8 +748,13 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
   int32_t st1 = SPDL_HJ_OK;
   LayoutRequest rq{&item.off, &item.size, &item.info, 1, &r.out, 0, &ctx->plans};
   rq.crops = r.has_rects ? &item.rect : nullptr;
-  rq.flips = r.has_flips ? &item.flip : nullptr;
-  rq.nflips = r.has_flips ? 1 : 0;
+  if (r.has_flips && r.oriented) {
+    rq.orients = &item.flip;
+    rq.norients = 1;
+  } else if (r.has_flips) {
+    rq.flips = &item.flip;
+    rq.nflips = 1;
+  }
   int rc = plan_batch(rq, L, &st1, err, errlen);
   if (rc) return rc;
   // the spare slot, on the failed batch's lane (its workspace is free: the
@@ -841,12 +852,14 @@ int take_views(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, const void* o
 struct Held {
   std::vector<spdl_hj_rect> rects;
   HeldViews views;
-  std::vector<uint8_t> flipv;
+  std::vector<uint8_t> flipv, orientv;
   const spdl_hj_rect* crops = nullptr;  // null: none
   const HeldViews* hv = nullptr;
   // (their count, values and chain are the planner's to check: build_layout)
   const uint8_t* flips = nullptr;
   int64_t nflips = 0;
+  const uint8_t* orients = nullptr;
+  int64_t norients = 0;
   int crc = 0, vrc = 0;
   Held(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, const void* out_dev, size_t out_bytes,
        char* err, size_t errlen) {
@@ -856,6 +869,12 @@ struct Held {
     if (!flipv.empty()) {
       flips = flipv.data();
       nflips = (int64_t)flipv.size();
+    }
+    orientv.swap(ctx->orients);
+    ctx->orients.clear();
+    if (!orientv.empty()) {
+      orients = orientv.data();
+      norients = (int64_t)orientv.size();
     }
     crc = take_crops(ctx, n, out, &rects, &crops, err, errlen);
     vrc = take_views(ctx, n, out, out_dev, out_bytes, !rects.empty(), &views, &hv, err, errlen);
@@ -934,7 +953,8 @@ int submit(spdl_hj_ctx* ctx, const Held& held, const Batch& b, SlotRelease& slot
   Layout L;
   // (views: one entropy workgroup per image, so no hand-off can give up)
   int rc = plan_batch({b.offsets, b.sizes, infos, b.n, b.out, held.hv ? 0 : ctx->piece_bytes,
-                       &ctx->plans, held.crops, held.hv, held.flips, held.nflips},
+                       &ctx->plans, held.crops, held.hv, held.flips, held.nflips, held.orients,
+                       held.norients},
                       L, b.status, err, errlen);
   if (rc) return rc;
   // the probes (the caller's own with device bytes, ABI 5) say which files
@@ -951,7 +971,9 @@ int submit(spdl_hj_ctx* ctx, const Held& held, const Batch& b, SlotRelease& slot
   const uint8_t* bytes = b.dev ? b.dev : static_cast<const uint8_t*>(slot.s->bytes.p);
   return run_pipeline(ctx, slot.pass(), L,
                       {bytes, b.bytes_len, b.n, b.out, b.out_dev, b.out_bytes, xs, b.sync, b.status,
-                       false, held.crops, held.hv ? nullptr : held.flips},
+                       false, held.crops,
+                       held.hv ? nullptr : held.orients ? held.orients : held.flips,
+                       held.orients != nullptr},
                       err, errlen);
 }
 
@@ -1049,6 +1071,13 @@ int spdl_hj_set_flips(spdl_hj_ctx* ctx, const uint8_t* flips, int32_t n) {
   if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
   ctx->flips.clear();
   if (flips && n > 0) ctx->flips.assign(flips, flips + n);
+  return SPDL_HJ_OK;
+}
+
+int spdl_hj_set_orients(spdl_hj_ctx* ctx, const uint8_t* orients, int32_t n) {
+  if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
+  ctx->orients.clear();
+  if (orients && n > 0) ctx->orients.assign(orients, orients + n);
   return SPDL_HJ_OK;
 }
 

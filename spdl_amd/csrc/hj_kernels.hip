@@ -5505,6 +5505,12 @@ __device__ __forceinline__ void hbuf_stage(const int16_t* __restrict__ src, int 
   }
 }
 
+// kOrient: the instantiation a submission with a transposed descriptor
+// launches (spdl_hj_set_orients, a code with bit 2).  Its tile lands in the
+// final box (hj_sws_tile.h tile_orient), the u8 tile in LDS is in landed
+// layout, and the store below takes row segments of any width.  Without it
+// the kernel is the one before orientations, flips included.
+template <bool kOrient>
 __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ planes,
                                                   const ImageDesc* __restrict__ desc,
                                                   const ImageInfo* __restrict__ infos,
@@ -5553,6 +5559,18 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
   // else (hj_sws_tile.h tile_flip)
   const int flip = flips ? __builtin_amdgcn_readfirstlane((int)flips[img]) : 0;
   const TileFlip tf = tile_flip(xo0, xo1, yo0, yo1, dd.ow, dd.oh, flip);
+  // (kOrient: codes 0..7; the landed tile lw x lh at (mx0, my0) of the final
+  // box, whose rows are fw apart)
+  TileOrient to{};  // (sws_kernel<false> never computes it: tf is all it has)
+  int lw = 0, lh = 0, fw = 0, mx0 = 0, my0 = 0;  // (of sws_kernel<true> alone)
+  if constexpr (kOrient) {
+    to = tile_orient(xo0, xo1, yo0, yo1, dd.ow, dd.oh, flip);
+    lw = to.lw;
+    lh = to.lh;
+    fw = to.fw;
+    mx0 = to.mx0();
+    my0 = to.my0();
+  }
   const bool planar = p.pix_fmt == 0 || p.pix_fmt == 1;
   const bool swap = p.pix_fmt == 1 || p.pix_fmt == 3;
   const bool u8 = p.dtype == 0;
@@ -5603,22 +5621,36 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
   // one pixel, its three values in the output's channel order
   auto putc = [&](int xo, int yo, int c0v, int c1v, int c2v) {
     const int cv[3] = {c0v, c1v, c2v};
-    const int tx = tf.tx(xo), ty = tf.ty(yo);  // (in the mirrored tile)
+    // (in the mirrored tile; kOrient: in the landed one)
+    int tx, ty;
+    if constexpr (kOrient) {
+      tx = to.lx(xo, yo);
+      ty = to.ly(xo, yo);
+    } else {
+      tx = tf.tx(xo);
+      ty = tf.ty(yo);
+    }
     if (u8) {
 #pragma unroll
       for (int ch = 0; ch < 3; ch++) {
         const int v = cv[ch];
-        const int ti = planar ? (ch * th + ty) * tw + tx : (ty * tw + tx) * 3 + ch;
+        int ti;
+        if constexpr (kOrient) ti = planar ? (ch * lh + ty) * lw + tx : (ty * lw + tx) * 3 + ch;
+        else ti = planar ? (ch * th + ty) * tw + tx : (ty * tw + tx) * 3 + ch;
         tile[ti] = (uint8_t)v;
       }
       return;
     }
-    const int mx = tf.mx0 + tx, my = tf.my0 + ty;  // (in the flipped output)
+    // (in the flipped output; kOrient: in the final one, whose rows are fw apart)
+    const int mx = (kOrient ? mx0 : tf.mx0) + tx, my = (kOrient ? my0 : tf.my0) + ty;
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) {
       const int v = cv[ch];
-      const int64_t oi =
-          dd.out_off + (planar ? ch * pl + (int64_t)my * dd.ow + mx : ((int64_t)my * dd.ow + mx) * 3 + ch);
+      int64_t oi;
+      if constexpr (kOrient)
+        oi = dd.out_off + (planar ? ch * pl + (int64_t)my * fw + mx : ((int64_t)my * fw + mx) * 3 + ch);
+      else
+        oi = dd.out_off + (planar ? ch * pl + (int64_t)my * dd.ow + mx : ((int64_t)my * dd.ow + mx) * 3 + ch);
       float f = __fdiv_rn((float)v, 255.0f);
       f = __fsub_rn(f, p.mean[ch]);
       f = __fdiv_rn(f, p.std[ch]);
@@ -5660,6 +5692,20 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
         }
         const int bpp = planar ? 1 : 3, np_ = planar ? 3 : 1;
         const int ps = th * tw;  // bytes of a planar tile's plane
+        if constexpr (kOrient) {
+          // the rectangle in the landed tile, kw x rh at (k0, r0): a pad row
+          // of a transposed descriptor is a column there
+          const int k0 = min(to.lx(xa, ya), to.lx(xb - 1, yb - 1));
+          const int r0 = min(to.ly(xa, ya), to.ly(xb - 1, yb - 1));
+          const int kw = to.t ? yb - ya : xb - xa, rh = to.t ? xb - xa : yb - ya;
+          if (kw == lw) {  // whole rows: one run per plane
+            for (int pc = 0; pc < np_; pc++) zrun((pc * ps + r0 * lw) * bpp, rh * lw * bpp, tid, nt);
+            return;
+          }
+          for (int r = r0 + wave; r < r0 + rh; r += nw)
+            for (int pc = 0; pc < np_; pc++) zrun((pc * ps + r * lw + k0) * bpp, kw * bpp, lane, 64);
+          return;
+        }
         // the rectangle's first row and column in the mirrored tile
         const int r0 = min(tf.ty(ya), tf.ty(yb - 1)), k0 = min(tf.tx(xa), tf.tx(xb - 1));
         if (xb - xa == tw) {     // whole rows: one run per plane
@@ -5894,6 +5940,49 @@ __global__ void __launch_bounds__(256) sws_kernel(const uint8_t* __restrict__ pl
   // its mirrored origin)
   const int nplane = planar ? 3 : 1;
   const int run = planar ? th * tw : th * tw * 3;  // bytes per plane run
+  if constexpr (kOrient) {
+    // The landed tile leaves as row segments, lh per plane, rowb bytes each
+    // and ostride apart in the final box.  A segment is cut at the 4-byte
+    // words of its DESTINATION: a word that lies inside the segment is one
+    // dword store, assembled from the two aligned LDS words its bytes straddle
+    // (the LDS side is at another offset within 4 bytes: no unaligned access);
+    // the words at a segment's two ends hold one to three of its bytes, which
+    // leave one by one -- the byte head and the byte tail.  The work items are
+    // (segment, word): a segment shorter than the wave wastes no lanes.
+    const int rowb = planar ? lw : lw * 3;
+    const int64_t ostride = planar ? fw : (int64_t)fw * 3;
+    uint8_t* dst0 = static_cast<uint8_t*>(out) + dd.out_off +
+                    (planar ? (int64_t)my0 * fw + mx0 : ((int64_t)my0 * fw + mx0) * 3);
+    if (lw == fw && ((uintptr_t)dst0 & 15) == 0 && (run & 15) == 0 && (!planar || (pl & 15) == 0)) {
+      // (whole rows of the final box: one aligned run per plane, as below)
+      for (int pc = 0; pc < nplane; pc++)
+        for (int i = tid; i < run / 16; i += nt)
+          reinterpret_cast<uint4*>(dst0 + pc * pl)[i] =
+              reinterpret_cast<const uint4*>(tile + pc * run)[i];
+      return;
+    }
+    const int wps = (rowb + 6) >> 2;  // the most destination words a segment touches
+    const int nseg = nplane * lh;
+    const uint32_t* tw32 = reinterpret_cast<const uint32_t*>(tile);  // (16-byte aligned)
+    for (int i = tid; i < nseg * wps; i += nt) {
+      const int seg = i / wps, j = i - seg * wps;
+      const int pc = seg / lh, r = seg - pc * lh;
+      const int so = pc * run + r * rowb;  // the segment in the LDS tile
+      uint8_t* d = dst0 + pc * pl + r * ostride;
+      const int k0 = 4 * j - (int)((uintptr_t)d & 3);  // this word's first byte in the segment
+      if (k0 >= rowb) continue;
+      if (k0 >= 0 && k0 + 4 <= rowb) {
+        const int o = so + k0;
+        // (an aligned word needs no second one: the last word of the tile is
+        // then never followed by a read past the tile's region)
+        const uint32_t lo = tw32[o >> 2], hi = (o & 3) ? tw32[(o >> 2) + 1] : 0u;
+        *reinterpret_cast<uint32_t*>(d + k0) = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(o & 3));
+      } else {
+        for (int k = max(k0, 0); k < min(k0 + 4, rowb); k++) d[k] = tile[so + k];
+      }
+    }
+    return;
+  }
   for (int pc = 0; pc < nplane; pc++) {
     const uint8_t* src = tile + pc * run;
     uint8_t* dst = static_cast<uint8_t*>(out) + dd.out_off + pc * pl +
@@ -6484,8 +6573,10 @@ hipError_t launch_sws(const BatchBuffers& b, void* out, const BatchParams& p, bo
                       int32_t* host_status, hipStream_t st, int wg0) {
   launch_hscale(b, hs_wgs, st);
   const dim3 grid = flat ? dim3(sws_wgs) : dim3(bands, chunks, b.n);
-  hipLaunchKernelGGL(sws_kernel, grid, dim3(256), lds_bytes, st, b.planes, b.desc, b.infos, b.wts,
-                     out, p, host_status, b.hbuf, flat ? b.sws_map : nullptr, wg0, b.flips);
+  // (a submission with a transposed descriptor: the orienting instantiation)
+  hipLaunchKernelGGL(b.transposed ? sws_kernel<true> : sws_kernel<false>, grid, dim3(256), lds_bytes,
+                     st, b.planes, b.desc, b.infos, b.wts, out, p, host_status, b.hbuf,
+                     flat ? b.sws_map : nullptr, wg0, b.flips);
   return hipGetLastError();
 }
 hipError_t launch_yuv_planes(const BatchBuffers& b, void* out, int sws_wgs, int lds_bytes,

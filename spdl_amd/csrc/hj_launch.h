@@ -36,6 +36,9 @@ struct BatchBuffers {
   // list; null when the submission sets none -- sws_kernel and
   // yuv_planes_kernel then load nothing
   const uint8_t* flips;
+  // ... or its orientation codes (spdl_hj_set_orients, 0..7) in the same place;
+  // transposed: one of them has bit 2, and sws_kernel<true> runs
+  bool transposed;
 };
 
 // parse_kernel + lut_kernel.  host_desc (descriptors, then the work list) and

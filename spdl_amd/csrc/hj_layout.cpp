@@ -192,6 +192,15 @@ struct Planner {
   BoxSize size;           // the images' output size (L.ow x L.oh)
   bool have_fmt = false;  // the planar output's frame format is set (L.yuv_*)
 
+  // The submission's orientation codes (orients, else flips) and descriptor
+  // k's: image k of a plain submission, or view k - n of a views submission
+  const uint8_t* codes() const { return rq.orients ? rq.orients : rq.flips; }
+  int64_t ncodes() const { return rq.orients ? rq.norients : rq.nflips; }
+  int code_of(int64_t k) const {
+    const int64_t q = rq.views ? k - rq.n : k;
+    return codes() && q >= 0 && q < ncodes() ? codes()[q] : 0;
+  }
+
   int fail(int i, int rc, const char* what) {
     res.rc = rc;
     res.image = i;
@@ -202,7 +211,8 @@ struct Planner {
   // (what place_output left in d.ow x d.oh against the box it had to match)
   int size_mismatch(const char* fmt, const BoxSize& box, size_t a, size_t b, const ImageDesc& d) {
     res.rc = SPDL_HJ_ERR_INVALID_ARG;
-    snprintf(res.err, sizeof(res.err), fmt, a, box.ow, box.oh, b, d.ow, d.oh);
+    const bool t = code_of(&d - L.desc.data()) & 4;  // (a transposed output: its final box)
+    snprintf(res.err, sizeof(res.err), fmt, a, box.ow, box.oh, b, t ? d.oh : d.ow, t ? d.ow : d.oh);
     return res.rc;
   }
 
@@ -312,8 +322,13 @@ struct Planner {
   // size `box` -- its geometry, its plan (placed once in L.tables), its
   // hscale_kernel and sws_kernel tiles.  What a refusal costs is the caller's
   // to say (refused_alone).
+  // `code`: the output's orientation (0..7).  With its transpose bit the
+  // chain is `out0` with its pairs swapped, d keeps that chain's box, and
+  // `box` is matched against the final one, oh x ow.
   Placement place_output(ImageDesc& d, int w, int h, const views::Frame& f, int color,
-                         const spdl_hj_output& out, BoxSize& box) {
+                         const spdl_hj_output& out0, BoxSize& box, int code) {
+    const bool t = code & 4;
+    const spdl_hj_output out = t ? swapped_chain(out0) : out0;
     Geom g;
     int rc = geometry(w, h, &out, &g);
     if (rc) return {rc, kAtGeometry, nullptr};
@@ -321,8 +336,9 @@ struct Planner {
     d.dy = g.dy;
     d.ow = g.ow;
     d.oh = g.oh;
-    if (!box.set) box = {true, g.ow, g.oh};
-    else if (g.ow != box.ow || g.oh != box.oh) return {SPDL_HJ_ERR_INVALID_ARG, kAtSize, nullptr};
+    const int fw = t ? g.oh : g.ow, fh = t ? g.ow : g.oh;
+    if (!box.set) box = {true, fw, fh};
+    else if (fw != box.ow || fh != box.oh) return {SPDL_HJ_ERR_INVALID_ARG, kAtSize, nullptr};
     if (!rq.plans || out.csc == SPDL_HJ_CSC_JFIF) return {SPDL_HJ_OK, kPlaced, nullptr};
     int hs, vs, mode;
     rc = views::chroma_shifts(f, &hs, &vs);
@@ -460,7 +476,7 @@ struct Planner {
       refuse(d, crop_rc);
       return SPDL_HJ_OK;
     }
-    const Placement pl = place_output(d, src.w, src.h, f, p.color, out, size);
+    const Placement pl = place_output(d, src.w, src.h, f, p.color, out, size, code_of(i));
     if (pl.at != kAtGeometry) L.max_px = std::max(L.max_px, (int64_t)d.ow * d.oh);
     if (pl.rc && refused_alone(false, pl)) {
       refuse(d, pl.rc);
@@ -523,7 +539,8 @@ struct Planner {
         if (!vr.rc) {
           const views::Frame f = frame_of(p);
           set_windows(v, f, views::grid_of(f), vr.r);
-          pl = place_output(v, vr.r.w, vr.r.h, f, p.color, hg.out, gsize);
+          pl = place_output(v, vr.r.w, vr.r.h, f, p.color, hg.out, gsize,
+                            code_of((int64_t)L.desc.size() - 1));
         }
         if (pl.rc && (vr.rc || refused_alone(true, pl))) {
           vstatus[q] = pl.rc;
@@ -569,6 +586,14 @@ struct Planner {
   // The flips of the submission against its count, values and chain; nothing
   // has been planned or written yet
   int check_flips() {
+    res.rc = SPDL_HJ_ERR_INVALID_ARG;
+    if (rq.flips && rq.orients) {
+      snprintf(res.err, sizeof(res.err),
+               "spdl_hj_set_flips and spdl_hj_set_orients on one submission");
+      return res.rc;
+    }
+    res.rc = SPDL_HJ_OK;
+    if (rq.orients) return check_orients();
     if (!rq.flips) return SPDL_HJ_OK;
     int64_t want = rq.n;
     if (rq.views) {
@@ -599,16 +624,69 @@ struct Planner {
     return SPDL_HJ_OK;
   }
 
+  // The orientations likewise: codes 0 to 7, no code with csc = JFIF, no
+  // transpose of the planar YUV output (a transposed 4:2:2 frame is another
+  // pixel format)
+  int check_orients() {
+    int64_t want = rq.n;
+    if (rq.views) {
+      want = 0;
+      for (const auto& g : rq.views->groups) want += (int64_t)g.views.size();
+    }
+    res.rc = SPDL_HJ_ERR_INVALID_ARG;
+    if (rq.norients != want) {
+      snprintf(res.err, sizeof(res.err), "spdl_hj_set_orients gave %lld codes for %lld %s",
+               (long long)rq.norients, (long long)want, rq.views ? "views" : "images");
+      return res.rc;
+    }
+    bool any = false;
+    for (int64_t i = 0; i < want; i++) {
+      const int c = rq.orients[i];
+      if (c > 7) {
+        snprintf(res.err, sizeof(res.err), "spdl_hj_set_orients: code %lld is %d (0 to 7)",
+                 (long long)i, c);
+        return res.rc;
+      }
+      if (c & 4) {
+        // (views: each group has its own chain)
+        bool yuv = rq.out->pix_fmt == SPDL_HJ_FMT_YUV;
+        if (rq.views) {
+          int64_t q = i;
+          for (const auto& g : rq.views->groups) {
+            if (q < (int64_t)g.views.size()) {
+              yuv = g.out.pix_fmt == SPDL_HJ_FMT_YUV;
+              break;
+            }
+            q -= (int64_t)g.views.size();
+          }
+        }
+        if (yuv) {
+          snprintf(res.err, sizeof(res.err),
+                   "spdl_hj_set_orients: code %lld transposes the planar YUV output", (long long)i);
+          return res.rc;
+        }
+      }
+      any = any || c;
+    }
+    if (any && rq.out->csc == SPDL_HJ_CSC_JFIF) {
+      snprintf(res.err, sizeof(res.err), "an orientation needs csc = swscale");
+      return res.rc;
+    }
+    res.rc = SPDL_HJ_OK;
+    return SPDL_HJ_OK;
+  }
+
   // One flag per descriptor, once every descriptor stands; none when every
   // flip is 0.  A flipped full-resolution batch takes the generic output
   // kernel (the unscaled converters do not flip).
   void place_flips() {
-    if (!rq.flips) return;
-    bool any = false;
-    for (int64_t i = 0; i < rq.nflips; i++) any = any || rq.flips[i];
+    if (!codes()) return;
+    int any = 0;
+    for (int64_t i = 0; i < ncodes(); i++) any |= codes()[i];
     if (!any) return;
     L.flips.assign(L.desc.size(), 0);
-    std::copy(rq.flips, rq.flips + rq.nflips, L.flips.begin() + (rq.views ? rq.n : 0));
+    std::copy(codes(), codes() + ncodes(), L.flips.begin() + (rq.views ? rq.n : 0));
+    L.transposed = any & 4;
     L.all_special = false;
   }
 

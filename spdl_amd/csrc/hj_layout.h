@@ -109,6 +109,12 @@ struct Layout {
   // theirs).  Empty when no flip of the submission is set: such a submission
   // is the path without flips exactly.
   std::vector<uint8_t> flips;
+  // Output orientations (spdl_hj_set_orients) travel in `flips` as well, one
+  // code 0..7 per descriptor (bit 2: transposed).  A transposed descriptor's
+  // ow / oh / dx / dy stay the chain's box, planned from the swapped spec; its
+  // final box is oh x ow, and ow / oh above, every group's and the "one size"
+  // rule are about final boxes.  transposed: some descriptor has bit 2.
+  bool transposed = false;
   int view_refused = 0;  // the first status the host gave a view alone (0: none)
   int view_refused_group = 0, view_refused_index = 0;
 };
@@ -135,7 +141,8 @@ struct HeldViews {
 // no output stage (the raw planes surface).  crops (n rectangles) and views
 // are optional and exclude each other.  flips (nflips bytes, SPDL_HJ_FLIP_*):
 // optional, one per image, or with views one per view, the groups
-// concatenated in group order.
+// concatenated in group order.  orients (norients bytes, 0..7): the same
+// places and counts; flips and orients on one request are refused.
 struct LayoutRequest {
   const int64_t* offsets;
   const int64_t* sizes;
@@ -148,7 +155,18 @@ struct LayoutRequest {
   const HeldViews* views = nullptr;
   const uint8_t* flips = nullptr;
   int64_t nflips = 0;
+  const uint8_t* orients = nullptr;
+  int64_t norients = 0;
 };
+
+// The chain that runs ahead of a transpose: the output spec describes the
+// final output, so fit, pad and crop each have their pair swapped.
+inline spdl_hj_output swapped_chain(spdl_hj_output o) {
+  std::swap(o.fit_w, o.fit_h);
+  std::swap(o.pad_w, o.pad_h);
+  std::swap(o.crop_w, o.crop_h);
+  return o;
+}
 
 // rc, and on failure its text and the image it is the status of (-1: none --
 // the call's own arguments).  The statuses of views the planner refuses alone

@@ -19,4 +19,13 @@ int first_scan_components(const uint8_t* d, size_t size, size_t pos);
 // and whether the multi-scan path decodes the file.
 int probe(const uint8_t* d, size_t size, spdl_hj_image_info* info);
 
+// The EXIF orientation of a file, 1..8 (spdl_hj_get_orientation's rules):
+// tag 0x0112 of IFD0 of the first Exif APP1 ahead of the first SOS; 1 for
+// whatever is absent, malformed or out of range.  It never fails and reads
+// nothing outside [d, d + size).
+int exif_orientation(const uint8_t* d, size_t size);
+
+// EXIF orientation 1..8 -> orientation code 0..7 (spdl_hj_orient_code); -1 else.
+int orient_code(int exif);
+
 }  // namespace hj

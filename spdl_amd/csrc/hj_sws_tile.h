@@ -52,6 +52,35 @@ inline HJ_HD TileFlip tile_flip(int xo0, int xo1, int yo0, int yo1, int W, int H
           fv ? -1 : 0,        fv ? yo1 : -yo0};
 }
 
+// Output orientation (spdl_hj_set_orients; bits 0 and 1 as the flips, bit 2 a
+// transpose ahead of them): with C the chain's ow x oh box, A(x, y) = C(y, x)
+// for a transposed descriptor (else A = C), and the final box is A mirrored.
+// The final box is fw x fh (oh x ow when transposed), its row pitch fw.  The
+// tile [xo0, xo1) x [yo0, yo1) of the chain's box lands as the lw x lh tile at
+// (mx0, my0) of the final box -- th x tw when transposed -- and chain pixel
+// (xo, yo) at (lx, ly) of the landed tile; cx / cy lead from a landed
+// coordinate back to the chain's box.  It is tile_flip over the final box's
+// axes: the final x axis is the chain's y axis when transposed.
+struct TileOrient {
+  TileFlip f;  // over (u, v): the chain coordinates that run along final x and y
+  bool t;
+  int fw, fh;  // the final box
+  int lw, lh;  // the landed tile
+  HJ_HD int mx0() const { return f.mx0; }
+  HJ_HD int my0() const { return f.my0; }
+  HJ_HD int lx(int xo, int yo) const { return f.tx(t ? yo : xo); }
+  HJ_HD int ly(int xo, int yo) const { return f.ty(t ? xo : yo); }
+  HJ_HD int cx(int kx, int ky) const { return t ? f.sy(ky) : f.sx(kx); }
+  HJ_HD int cy(int kx, int ky) const { return t ? f.sx(kx) : f.sy(ky); }
+};
+inline HJ_HD TileOrient tile_orient(int xo0, int xo1, int yo0, int yo1, int ow, int oh, int code) {
+  const bool t = code & 4;
+  const int fw = t ? oh : ow, fh = t ? ow : oh;
+  const TileFlip f = t ? tile_flip(yo0, yo1, xo0, xo1, fw, fh, code & 3)
+                       : tile_flip(xo0, xo1, yo0, yo1, fw, fh, code & 3);
+  return {f, t, fw, fh, t ? yo1 - yo0 : xo1 - xo0, t ? xo1 - xo0 : yo1 - yo0};
+}
+
 // The chroma columns under the luma columns [xs0, xs1) (xs0 < xs1): one per
 // column with SWS_FULL_CHR_H_INT, else one per pixel pair.
 struct SwsChromaCols {

@@ -88,15 +88,35 @@ def _alloc_out(cfg: CUDAConfig, shape, dtype) -> CUDABuffer:
 
 
 def _decode(datas: list, out: Output, cfg: CUDAConfig, shape_per_image, batched: bool,
-            dtype=torch.uint8, crops=None, flips=None) -> CUDABuffer:
+            dtype=torch.uint8, crops=None, flips=None, orients=None) -> CUDABuffer:
     n = len(datas)
     shape = (n, *shape_per_image) if batched else tuple(shape_per_image)
     buf = _alloc_out(cfg, shape, dtype)
     dec = _lib.thread_decoder(cfg.device_index)
     nbytes = int(np.prod(shape)) * (1 if dtype == torch.uint8 else 2)
     dec.decode_batch(datas, out, buf.data_ptr(), nbytes, stream=_stream(cfg), sync=True,
-                     crops=crops, flips=flips)
+                     crops=crops, flips=flips, orients=orients)
     return buf
+
+
+def _oriented_size(src, out: Output, code: int):
+    """The final ``(ow, oh)`` of a ``src = (w, h)`` frame under orientation
+    ``code``: a transposed image is sized from the stored frame's ``(h, w)``."""
+    return _lib.output_size(*(src[::-1] if code & 4 else src), out)
+
+
+def _exif_codes(datas, out: Output, flips):
+    """``exif_orientation=True``: each file's EXIF orientation as its code, the
+    caller's flip on top -- it acts on the displayed image, so the bits xor --
+    and ``out`` without its flip, which the codes now hold."""
+    if out.orient is not None:
+        raise ValueError("exif_orientation= and transpose in filter_desc are exclusive")
+    every = _lib._flip(out.flip)
+    codes = [_lib.exif_code(_lib.get_orientation(d)) ^ (every if flips is None else flips[k])
+             for k, d in enumerate(datas)]
+    if out.flip is not None:
+        out = Output(**{**out.__dict__, "flip": None})
+    return out, codes
 
 
 def _src_size(info, rect) -> tuple[int, int]:
@@ -257,6 +277,7 @@ def load_image_batch(
     norm_dtype: str = "float16",
     crops=None,
     flips=None,
+    exif_orientation: bool = False,
     **kwargs,
 ):
     """Batch load images into one ``[B,H,W,3]`` buffer with the FFmpeg filter
@@ -285,7 +306,15 @@ def load_image_batch(
     -- applied to the chain's result, as ``hflip`` / ``vflip`` at the end of
     ``filter_desc`` do for every image alike (exclusive with those); a
     RandomHorizontalFlip in the decode's own store.  A full-resolution batch
-    with a flip takes the generic output kernel."""
+    with a flip takes the generic output kernel.
+
+    ``exif_orientation=True`` (an extension; torchvision's
+    ``apply_exif_orientation``, Pillow's ``exif_transpose``) reads each file's
+    EXIF orientation and decodes the image as a viewer shows it: ``width`` and
+    ``height`` are those of the displayed image, a rotated file runs the chain
+    sideways, and every image of the batch has one shape.  ``flips`` then act
+    on the displayed image.  A ``transpose`` at the end of ``filter_desc``
+    turns every image alike (exclusive with ``exif_orientation``)."""
     if not srcs:
         raise ValueError("`srcs` must not be empty.")
     storage = kwargs.pop("storage", None)
@@ -309,6 +338,9 @@ def load_image_batch(
             raise ValueError(f"{len(flips)} flips for {len(srcs)} images")
         if filter_desc is None:
             raise ValueError("flips= needs a filter chain (width / height, filter_desc or pix_fmt)")
+    if exif_orientation and filter_desc is None:
+        raise ValueError("exif_orientation= needs a filter chain (width / height, filter_desc or "
+                         "pix_fmt)")
     if filter_desc is None:
         # no scale and no output format: the decoder's own planes, batched as
         # the reference's convert_frames stacks them ([B, 3, H, W] yuvj444p,
@@ -366,15 +398,20 @@ def load_image_batch(
         crops = [crops[i] for i in keep]
     if flips is not None:
         flips = [flips[i] for i in keep]
+    orients = None
+    if exif_orientation:
+        out, orients = _exif_codes(datas, out, flips)
+        flips = None
     src = _src_size(info, crops[0] if crops is not None else out.src_crop)
-    ow, oh = _lib.output_size(*src, out)
+    ow, oh = _oriented_size(src, out, orients[0] if orients else _lib._orient(out.orient))
     dtype = out.torch_dtype
     if out.pix_fmt == "yuv":
         shape = _yuv_shape([_lib.get_image_info(d) for d in datas], out, src)
     else:
         shape = _shape(out, ow, oh)
     try:
-        buf = _decode(datas, out, cfg, shape, True, dtype=dtype, crops=crops, flips=flips)
+        buf = _decode(datas, out, cfg, shape, True, dtype=dtype, crops=crops, flips=flips,
+                      orients=orients)
     except RuntimeError:
         if strict:
             raise
@@ -384,7 +421,8 @@ def load_image_batch(
             try:
                 good.append(_decode([d], out, cfg, shape, True, dtype=dtype,
                                     crops=None if crops is None else [crops[k]],
-                                    flips=None if flips is None else [flips[k]]))
+                                    flips=None if flips is None else [flips[k]],
+                                    orients=None if orients is None else [orients[k]]))
             except RuntimeError as err:
                 _LG.error("Failed to decode an image: %s", err)
         if not good:
@@ -431,7 +469,8 @@ def _view_group_output(g) -> Output:
     return out
 
 
-def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = True):
+def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = True,
+                     exif_orientation: bool = False):
     """Several crops and sizes of every image from one decode (an extension,
     like ``crops=`` and ``normalize=``): multi-crop augmentation, a thumbnail
     beside a training crop.  Every file is parsed and entropy-decoded once and
@@ -446,6 +485,10 @@ def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = 
     none included.  At most four groups.  ``flips=[[flip, ...] per image]``,
     parallel to ``crops``, mirrors single views (``0..3``, ``"h"``, ``"v"``,
     ``"hv"`` or ``None``; left out: no view of the group is flipped).
+    ``exif_orientation=True`` reads each image's EXIF orientation and applies
+    it to every view of that image (the rectangles stay in the stored frame's
+    coordinates; ``width`` / ``height`` are the displayed view's; a view's flip
+    acts on the displayed view).
 
     Returns one ``(buffer, image_indices)`` per group: ``buffer`` is
     ``[rows, H, W, 3]`` (``[rows, 3, H, W]`` planar) with rows in (image, rect)
@@ -493,6 +536,7 @@ def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = 
     if not datas:
         raise RuntimeError("Failed to load all the images.")
     # one submission: every group's views of the surviving images, (image, rect) order
+    exif = [_lib.exif_code(_lib.get_orientation(d)) for d in datas] if exif_orientation else None
     vgroups, bufs, rows = [], [], []
     for g, out in zip(groups, outs):
         per_image = list(g["crops"])
@@ -500,12 +544,16 @@ def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = 
         views, src_of, size = [], [], None
         for k, i in enumerate(keep):
             for j, r in enumerate(per_image[i]):
-                views.append((k, r) if per_flip is None else (k, r, per_flip[i][j]))
+                f = None if per_flip is None else per_flip[i][j]
+                if exif is not None:
+                    views.append((k, r, None, exif[k] ^ _lib._flip(f)))
+                else:
+                    views.append((k, r) if per_flip is None else (k, r, f))
                 src_of.append(i)
                 if size is None:
                     rc, rr = _lib.crop_rect(infos[k], r)
                     if not rc:
-                        size = _lib.output_size(rr[2], rr[3], out)
+                        size = _oriented_size((rr[2], rr[3]), out, exif[k] if exif else 0)
         if not views:
             raise ValueError("a group without any rectangle")
         if size is None:
@@ -583,6 +631,7 @@ def load_image(
     device_config: CUDAConfig | None = None,
     pix_fmt: str | None = "rgb24",
     flip=None,
+    exif_orientation: bool = False,
     **kwargs,
 ):
     """Single image.  ``filter_desc=None`` returns the decoded planes in the
@@ -593,7 +642,10 @@ def load_image(
     of the scaled planes (the chain runs on the frame's own format);
     otherwise RGB per the filter.  ``flip`` (an extension; ``0..3``, ``"h"``,
     ``"v"``, ``"hv"``) mirrors the chain's result, as ``hflip`` / ``vflip`` at
-    the end of ``filter_desc`` do (exclusive with those)."""
+    the end of ``filter_desc`` do (exclusive with those).
+    ``exif_orientation=True`` (an extension) applies the file's EXIF
+    orientation, as in :func:`load_image_batch`; ``flip`` then acts on the
+    displayed image."""
     kwargs.pop("name", None)  # only names the source in FFmpeg demux errors
     _ignore_ffmpeg_configs(kwargs)
     if kwargs:
@@ -602,8 +654,9 @@ def load_image(
     data = _read(src)
     flip = _lib._flip(flip)
     if filter_desc is None:
-        if flip:
-            raise ValueError("flip= needs a filter chain (filter_desc or pix_fmt)")
+        if flip or exif_orientation:
+            raise ValueError("flip= and exif_orientation= need a filter chain (filter_desc or "
+                             "pix_fmt)")
         dec = _lib.thread_decoder(cfg.device_index)
         arr = _native_planes(dec.decode_planes(data, stream=_stream(cfg)), data)
         if device_config is not None:
@@ -616,12 +669,15 @@ def load_image(
         if out.flip is not None:
             raise ValueError("flip= and hflip / vflip in filter_desc are exclusive")
         out = Output(**{**out.__dict__, "flip": flip})
+    if exif_orientation:
+        out, (code,) = _exif_codes([data], out, None)
+        out = Output(**{**out.__dict__, "orient": code})
     info = _lib.get_image_info(data)
     src = _src_size(info, out.src_crop)
     if out.pix_fmt == "yuv":  # pix_fmt=None, no format node: the frame's planes
         shape = _yuv_shape([info], out, src)
     else:
-        shape = _shape(out, *_lib.output_size(*src, out))
+        shape = _shape(out, *_oriented_size(src, out, _lib._orient(out.orient)))
     buf = _decode([data], out, cfg, shape, False)
     if device_config is None:
         return _to_host(buf)

@@ -94,6 +94,32 @@ def _size(kv: dict, key: str, part: str, required: bool = False) -> int:
     return v
 
 
+_TRANSPOSE_DIRS = {"0": 4, "cclock_flip": 4, "1": 5, "clock": 5, "2": 6, "cclock": 6,
+                   "3": 7, "clock_flip": 7}  # -> orientation code (include/spdl_hipjpeg.h)
+
+
+def _oriented(code: int, img):
+    """Rows ``img`` under orientation ``code``: the transpose, then the flips."""
+    if code & 4:
+        img = [list(r) for r in zip(*img)]
+    if code & 1:
+        img = [r[::-1] for r in img]
+    if code & 2:
+        img = img[::-1]
+    return [list(r) for r in img]
+
+
+def _then(code: int, node: int) -> int:
+    """The one code of orientation ``code`` followed by orientation ``node``:
+    the eight orientations form a group, and instead of its multiplication
+    table both are applied to a 3 x 2 image of distinct labels, on which the
+    eight codes give eight different results -- the one that matches names the
+    product."""
+    base = [[0, 1, 2], [3, 4, 5]]
+    want = _oriented(node, _oriented(code, base))
+    return next(k for k in range(8) if _oriented(k, base) == want)
+
+
 def parse_image_filter(filter_desc: str | None, default_pix_fmt: str | None = "rgb24") -> Output:
     """Translate an image filter chain into an :class:`Output` spec.
 
@@ -103,18 +129,48 @@ def parse_image_filter(filter_desc: str | None, default_pix_fmt: str | None = "r
     ``hflip`` / ``vflip`` are taken as the chain's last geometry nodes: after
     ``scale`` and after the last ``pad`` / ``crop``, before or after ``format``
     (``Output.flip``; repeated nodes toggle).  Anywhere else their pixels would
-    differ from the store-time flip, and they are refused."""
+    differ from the store-time flip, and they are refused.
+
+    ``transpose=dir`` (``0..3`` or ``cclock_flip`` / ``clock`` / ``cclock`` /
+    ``clock_flip``) is taken in the same places and composes with the flips in
+    chain order.  A chain whose orientation holds a transpose gives
+    ``Output.orient`` and the FINAL-output form of the spec: the ``scale``,
+    ``pad`` and ``crop`` sizes parsed ahead of it with each pair swapped."""
     spec = dict(pix_fmt=default_pix_fmt or "yuv", resize=False)
     if not filter_desc:
         return Output(**spec)
     have_scale = have_pad = False
-    flip = 0
+    flip = 0  # the orientation code of the flips and transposes so far
+    oriented = False  # a transpose node was among them
     for part in filter_desc.split(","):
         part = part.strip()
         if not part:
             continue
         name, _, args = part.partition("=")
         kv = _kv(args)
+        if name == "transpose":
+            # transpose=dir=clock, or positional: transpose=clock (its own parse: _kv names
+            # positional arguments after scale's w:h)
+            items = [a for a in args.split(":") if a]
+            kv = dict(a.split("=", 1) if "=" in a else ("dir", a) for a in items[:1])
+            kv.update(a.split("=", 1) if "=" in a else ("passthrough", a) for a in items[1:])
+            extra = sorted(set(kv) - {"dir"})
+            if extra:  # passthrough=portrait / landscape skips the node by the frame's shape
+                raise ValueError(f"transpose options not supported: {extra} (a transpose that "
+                                 f"depends on the frame's shape cannot be planned ahead): {part}")
+            d = kv.get("dir", "0")
+            if d not in _TRANSPOSE_DIRS:
+                raise ValueError(f"transpose takes dir=0..3, cclock_flip, clock, cclock or "
+                                 f"clock_flip: {part}")
+            if not have_scale:
+                raise ValueError(
+                    "transpose ahead of scale is not supported: the pixels would differ from a "
+                    "transpose of the scaled image (swscale's horizontal and vertical passes "
+                    "round differently); put it after scale, pad and crop, or pass orients= for "
+                    "a full-resolution decode")
+            flip = _then(flip, _TRANSPOSE_DIRS[d])
+            oriented = True
+            continue
         if name in ("hflip", "vflip"):
             if args:
                 raise ValueError(f"{name} takes no options: {part}")
@@ -124,8 +180,14 @@ def parse_image_filter(filter_desc: str | None, default_pix_fmt: str | None = "r
                     "of the scaled image (swscale's filter positions are not mirror-symmetric and "
                     "odd-width chroma pairs differently); put it after scale, pad and crop, or "
                     "pass flips= for a full-resolution decode")
-            flip ^= 1 if name == "hflip" else 2
+            flip = _then(flip, 1 if name == "hflip" else 2)
             continue
+        if oriented and name in ("scale", "pad", "crop"):
+            raise ValueError(
+                f"transpose ahead of {name} is not supported: the pixels would differ from a "
+                "transpose of the final image (a later scale rounds its two passes differently, "
+                "and a centred pad or crop is placed by the sizes it sees); put the transpose "
+                "after the last scale, pad and crop")
         if flip and name in ("scale", "pad", "crop"):
             raise ValueError(
                 f"hflip / vflip ahead of {name} is not supported: the pixels would differ from a "
@@ -188,6 +250,15 @@ def parse_image_filter(filter_desc: str | None, default_pix_fmt: str | None = "r
             spec["pix_fmt"] = pf
         else:
             raise ValueError(f"filter `{name}` is not supported by the image decode stage")
-    if flip:
+    if flip & 4:
+        if spec["pix_fmt"] == "yuv":
+            raise ValueError("transpose of the decoder's planar format is not supported (a "
+                             "transposed 4:2:2 frame is another pixel format); name an RGB pix_fmt")
+        # the spec describes the final output: the pairs parsed ahead of the transpose, swapped
+        for a, b in (("fit_w", "fit_h"), ("pad_w", "pad_h"), ("crop_w", "crop_h")):
+            if a in spec or b in spec:
+                spec[a], spec[b] = spec.get(b, 0), spec.get(a, 0)
+        spec["orient"] = flip
+    elif flip:
         spec["flip"] = flip
     return Output(**spec)
