@@ -103,19 +103,17 @@ inline HJ_HD uint32_t slot_bits(uint32_t maxbits, int sub_bits, uint32_t budget 
 //           sequential decoder rejects, has neither bit (nor has the invalid
 //           code's entry, 1): bits [19,21) << 6 bound the z a symbol may reach
 //           -- 64 a coefficient, 128 (any) EOB / ZRL, 0 what is refused.
-//           (HJ_ENT_RULES=0: [20] marks the rejected symbol instead)
 //   [21,32) Full: the value (int11); Sub: the sub-table index
 constexpr uint32_t kKindSlow = 0;  // invalid, or a sub-table that did not fit
 constexpr uint32_t kKindCode = 1;  // code resolved, value bits follow
 constexpr uint32_t kKindFull = 2;  // code + value resolved
 constexpr uint32_t kKindSub = 3;   // code longer than kLutBits: look up sub[idx][next 6 bits]
 constexpr int kSubBits = 16 - kLutBits;
-#ifndef HJ_SUB_POOL
-#define HJ_SUB_POOL 2048
-#endif
-constexpr int kSubPool = HJ_SUB_POOL;  // entropy LDS entries for the second-level tables of a scan
-// The entropy step's instruction cuts, one switch each (=0 builds the tree
-// without that cut, for the A/B of profiles/r15/entropy_step):
+constexpr int kSubPool = 2048;  // entropy LDS entries for the second-level tables of a scan
+// The entropy symbol step is written for instruction count.  Each of these
+// was measured against the form it replaced, which is gone from the tree; the
+// numbers are in profiles/r15/entropy_step (ab.txt, and per cut
+// counters_summary_no_<NAME>.txt):
 //   SUBADDR    every LDS table slot owns a fixed kSubShare entries of the pool
 //              and a sub-table sits at its level-1 index modulo the share, so
 //              the speculative second-level address is the slot and nine
@@ -134,41 +132,14 @@ constexpr int kSubPool = HJ_SUB_POOL;  // entropy LDS entries for the second-lev
 //   NEXTBS     the block-in-MCU counted downwards in the hot loops: subtract, min
 //   FASTSTOP   the write step's distance to the segment end against a bound
 //              made once
-#ifndef HJ_ENT_SUBADDR
-#define HJ_ENT_SUBADDR 1
-#endif
-#ifndef HJ_ENT_SUBMARK
-#define HJ_ENT_SUBMARK 1
-#endif
-#ifndef HJ_ENT_MORE
-#define HJ_ENT_MORE 1
-#endif
-#ifndef HJ_ENT_RULES
-#define HJ_ENT_RULES 1
-#endif
-#ifndef HJ_ENT_WIN2
-#define HJ_ENT_WIN2 1
-#endif
-#ifndef HJ_ENT_STOREBASE
-#define HJ_ENT_STOREBASE 1
-#endif
-#ifndef HJ_ENT_NEXTBS
-#define HJ_ENT_NEXTBS 1
-#endif
-#ifndef HJ_ENT_FASTSTOP
-#define HJ_ENT_FASTSTOP 1
-#endif
 constexpr int kSubShareBits = 9;  // log2(kSubPool / 4 LDS table slots)
 constexpr int kSubShare = 1 << kSubShareBits;
 constexpr uint32_t kSubMark = kKindSub << 5;  // kind Sub, every other field 0: no real entry
-static_assert(!HJ_ENT_SUBADDR || 4 * kSubShare == kSubPool, "four slots share the pool evenly");
+static_assert(4 * kSubShare == kSubPool, "four slots share the pool evenly");
 
 // idct_rgb_kernel workgroup size: one block per thread, so a tile is
 // kFusedThreads / bpm MCUs of one MCU row (host and kernel agree on it)
-#ifndef HJ_FUSED_THREADS
-#define HJ_FUSED_THREADS 256
-#endif
-constexpr int kFusedThreads = HJ_FUSED_THREADS;
+constexpr int kFusedThreads = 256;
 constexpr int kMaxSub = 16;        // 64-entry sub-tables per Huffman table
 constexpr int kEntHiShift = 21;    // value / sub-table index field
 
@@ -186,7 +157,7 @@ inline HJ_HD uint32_t hj_entry(uint32_t kind, int len, int sym, bool is_dc, int 
     bad = run != 0;
   }
   const uint32_t sz = kind == kKindFull ? 0u : (uint32_t)size;
-  const uint32_t b20 = HJ_ENT_RULES ? (uint32_t)(!coef && !bad) : bad;
+  const uint32_t b20 = !coef && !bad;
   return ((uint32_t)len + sz) | (kind << 5) | (sz << 7) | (zinc << 12) | (coef << 19) | (b20 << 20) |
          (((uint32_t)v & 0x7FFu) << kEntHiShift);
 }
@@ -291,10 +262,7 @@ struct ImageDesc {      // host-filled per image
 // tile and the vertical tables; the host picks the tallest band that fits.
 // 32 KiB: the 2-lane schedule runs 3.6 % faster than at 48 KiB (smaller bands
 // leave room for the other lane's workgroups; r02 A/B, 24 and 64 KiB slower)
-#ifndef HJ_SWS_LDS_KB
-#define HJ_SWS_LDS_KB 32
-#endif
-constexpr int kSwsLdsBudget = HJ_SWS_LDS_KB * 1024;
+constexpr int kSwsLdsBudget = 32 * 1024;
 constexpr int kSwsMaxCols = 256;  // output columns per workgroup
 // sws_kernel's LDS holds the horizontal pass column-major: a column of `rows`
 // int16 samples (+ 4 slack rows read by zero taps) takes an odd number of
@@ -342,16 +310,11 @@ struct ImageInfo {      // device-filled by the parse kernel
 // m d = 2^32 - e with 1 <= e <= d, so n m / 2^32 = n / d - (n / 2^32)(e / d)
 // falls short of n / d by less than 1 for every n < 2^32: the high word of
 // n m is the quotient or one below it, which the remainder tells.
-// HJ_IDCT_INDEX=0: the plain divisions.
-#ifndef HJ_IDCT_INDEX
-#define HJ_IDCT_INDEX 1
-#endif
 inline HJ_HD uint32_t idct_div_magic(uint32_t d) { return 0xFFFFFFFFu / d; }  // d >= 1
 struct IdctDivMod {
   uint32_t q, r;
 };
 inline HJ_HD IdctDivMod idct_divmod(uint32_t n, uint32_t d, uint32_t magic) {
-#if HJ_IDCT_INDEX
   uint32_t q = (uint32_t)(((uint64_t)n * magic) >> 32);
   uint32_t r = n - q * d;
   if (r >= d) {
@@ -359,9 +322,6 @@ inline HJ_HD IdctDivMod idct_divmod(uint32_t n, uint32_t d, uint32_t magic) {
     r -= d;
   }
   return {q, r};
-#else
-  return {n / d, n % d};
-#endif
 }
 struct IdctBlockPos {
   int c, bx, by;
@@ -391,10 +351,7 @@ inline HJ_HD uint32_t idct_region_block(const ImageInfo& in, int mx0, int my0, i
 // destuff: chunk-parallel over kDsChunk-byte chunks; per-chunk counts and prefixes
 constexpr int kDsChunk = 4096;
 // idct_kernel: one block per thread, kIdctThreads blocks per workgroup
-#ifndef HJ_IDCT_THREADS
-#define HJ_IDCT_THREADS 256
-#endif
-constexpr int kIdctThreads = HJ_IDCT_THREADS;
+constexpr int kIdctThreads = 256;
 // hscale_kernel: source rows of one plane per workgroup
 constexpr int kHsRows = 16;
 struct DsChunk {

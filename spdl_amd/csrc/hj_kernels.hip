@@ -479,10 +479,8 @@ __global__ void __launch_bounds__(256, 8) parse_kernel(const uint8_t* __restrict
           ns++;
           subs += tab_nsub[slot];
           slow |= (tab_slow >> slot) & 1;
-#if HJ_ENT_SUBADDR
           // (the LDS-only loops give every table slot kSubShare entries)
           slow |= tab_nsub[slot] > (kSubShare >> kSubBits);
-#endif
         }
         seen |= 1 << slot;
       }
@@ -900,14 +898,6 @@ __global__ void __launch_bounds__(kDsThreads) destuff_write_kernel(
 // entropy_kernel
 // ---------------------------------------------------------------------------
 
-typedef unsigned short hj_u16x2 __attribute__((ext_vector_type(2)));
-// low 16 bits of two u16 products at once (v_pk_mul_lo_u16, full rate; a
-// 32-bit multiply is quarter rate)
-__device__ __forceinline__ uint32_t pk_mul_lo16(uint32_t a, uint32_t b) {
-  return __builtin_bit_cast(uint32_t,
-                            __builtin_bit_cast(hj_u16x2, a) * __builtin_bit_cast(hj_u16x2, b));
-}
-
 constexpr int kMaxTabs = 2 * kMaxComp;  // distinct (DC, AC) tables of a scan
 // The coefficient lists' index field: a coefficient's slot in the IDCT's
 // LDS block, not its natural index: each row stored as the pairs (x0, x2),
@@ -919,12 +909,9 @@ __constant__ uint8_t kSlotOrder[64] = {
     0,  4,  8,  16, 12, 1,  5,  9,  20, 24, 32, 28, 17, 13, 2,  6,  10, 21, 25, 36, 40, 48,
     44, 33, 29, 18, 14, 3,  7,  11, 22, 26, 37, 41, 52, 56, 60, 49, 45, 34, 30, 19, 15, 23,
     27, 38, 42, 53, 57, 61, 50, 46, 35, 31, 39, 43, 54, 58, 62, 51, 47, 55, 59, 63};
-#ifndef HJ_WIN_WORDS
-#define HJ_WIN_WORDS 12
-#endif
 // bit-reader window per thread (words): 12 restages a lane every ~8-11 words
 // (r04 A/B, 4-lane bench: 8 words 507.5k img/s, 12 515.1k, 16 514.1k)
-constexpr int kWinWords = HJ_WIN_WORDS;
+constexpr int kWinWords = 12;
 
 // NTAB = distinct Huffman tables the workgroup holds in LDS: 4 covers luma +
 // chroma DC/AC (gray: 2) and keeps three entropy workgroups per CU; a scan
@@ -1006,14 +993,8 @@ struct TabMap {
   uint32_t amap;    // ... of its AC table
   uint32_t cmap;    // its component
   uint32_t bs_end;  // 3 * blocks per MCU
-#if HJ_ENT_NEXTBS
   uint32_t rdmap, ramap;  // dmap / amap packed in reverse: block b at bit bs_end - 3 - 3b
-#endif
-  // HJ_ENT_SUBADDR=0 only (else 0: a slot's sub-tables sit in its fixed share
-  // of the pool, lookup<false>) -- per LDS table slot t (16 bits each): (pool
-  // base - sub_lo) * 64, so a code's second-level entry is sub[(top 16 bits +
-  // soff_t) mod pool], computable from the bits alone, without the level-1 entry
-  uint64_t soff;
+  uint64_t unused_;       // unused (always 0): without it the chain walk's scalar copies reorder
 };
 
 template <int NT>
@@ -1102,25 +1083,12 @@ __device__ __forceinline__ uint32_t next_bs(const TabMap& m, uint32_t bs) {
 // run (Dec::bs = bs_end - 3 - 3b there, flipped on entry and on return; the
 // maps packed in reverse): the advance is a subtract and an unsigned min --
 // below 0 it wraps past every bound, to the MCU's first block.
-// HJ_ENT_NEXTBS=0: upwards, compare and select.
-__device__ __forceinline__ void hot_flip(const TabMap& m, Dec& d) {
-#if HJ_ENT_NEXTBS
-  d.bs = m.bs_end - 3u - d.bs;
-#endif
-}
+__device__ __forceinline__ void hot_flip(const TabMap& m, Dec& d) { d.bs = m.bs_end - 3u - d.bs; }
 __device__ __forceinline__ uint32_t hot_tab(const TabMap& m, const Dec& d, bool is_dc) {
-#if HJ_ENT_NEXTBS
   return __builtin_amdgcn_ubfe(is_dc ? m.rdmap : m.ramap, d.bs, 3);
-#else
-  return tab_slot(m, d, is_dc);
-#endif
 }
 __device__ __forceinline__ uint32_t hot_next(const TabMap& m, uint32_t bs) {
-#if HJ_ENT_NEXTBS
   return min(bs - 3u, m.bs_end - 3u);
-#else
-  return next_bs(m, bs);
-#endif
 }
 
 // Canonical decode of a code that is not fully resolved by the LUT (longer
@@ -1148,8 +1116,7 @@ __device__ __attribute__((noinline)) uint32_t slow_symbol(const SH& S, int t, ui
 // SLOW = false: every table's long codes are in LDS sub-tables, so a Slow
 // entry is 0 (invalid code) and the canonical fallback is not needed.
 template <bool SLOW, class SH>
-__device__ __forceinline__ uint32_t lookup(const SH& S, uint32_t t, uint32_t hi, bool is_dc,
-                                           uint64_t soff) {
+__device__ __forceinline__ uint32_t lookup(const SH& S, uint32_t t, uint32_t hi, bool is_dc) {
   if constexpr (SLOW) {
     if (t >= (uint32_t)SH::kTabs) {  // a table past the LDS slots: its HBM copy
       const HuffTable& G = S.gtab[S.gslot[t]];
@@ -1164,21 +1131,13 @@ __device__ __forceinline__ uint32_t lookup(const SH& S, uint32_t t, uint32_t hi,
   uint32_t e = S.lut[t][hi >> (32 - kLutBits)];
   if constexpr (!SLOW) {
     // both levels read back to back (the second address from the bits and
-    // the slot's offset, not from the first entry), one LDS latency per
-    // symbol instead of two whenever any lane of the wave has a long code
-#if HJ_ENT_SUBADDR
+    // the slot, not from the first entry), one LDS latency per symbol
+    // instead of two whenever any lane of the wave has a long code:
     // slot t's share of the pool, the sub-table at its level-1 index modulo
     // the share (entropy_image's table load): slot bits above nine stream bits
     const uint32_t a2 = (t << kSubShareBits) | ((hi >> 16) & (uint32_t)(kSubShare - 1));
-#else
-    const uint32_t a2 = ((hi >> 16) + (uint32_t)(soff >> (16u * t))) & (uint32_t)(kSubPool - 1);
-#endif
     const uint32_t e2 = S.sub[a2];
-#if HJ_ENT_SUBMARK
     return e == kSubMark ? e2 : e;
-#else
-    return ((e >> 5) & 3) == kKindSub ? e2 : e;
-#endif
   }
   if (((e >> 5) & 3) == kKindSub)
     e = S.sub[((e >> kEntHiShift) << kSubBits) |
@@ -1194,8 +1153,7 @@ __device__ __forceinline__ uint32_t lookup(const SH& S, uint32_t t, uint32_t hi,
 // window, most of them no symbol start, and leave the rare Slow symbol that
 // the walk actually meets to one uniform lookup())
 template <bool SLOW, class SH>
-__device__ __forceinline__ uint32_t lookup_fast(const SH& S, uint32_t t, uint32_t hi,
-                                                uint64_t soff) {
+__device__ __forceinline__ uint32_t lookup_fast(const SH& S, uint32_t t, uint32_t hi) {
   if constexpr (SLOW) {
     if (t >= (uint32_t)SH::kTabs) {
       const HuffTable& G = S.gtab[S.gslot[t]];
@@ -1211,7 +1169,7 @@ __device__ __forceinline__ uint32_t lookup_fast(const SH& S, uint32_t t, uint32_
                 ((hi >> (32 - kLutBits - kSubBits)) & ((1u << kSubBits) - 1))];
     return e;
   } else {
-    return lookup<false>(S, t, hi, false, soff);
+    return lookup<false>(S, t, hi, false);
   }
 }
 
@@ -1238,18 +1196,11 @@ __device__ int decode_state(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
     uint64_t p01, p12;
     const uint32_t r = dec_peek3<NT>(d, win, words, p01, p12);
     uint32_t nbits;
-#if HJ_ENT_WIN2
     const uint32_t hi0 = (uint32_t)((p01 << r) >> 32), lo0 = (uint32_t)((p12 << r) >> 32);
-#endif
     {
-#if HJ_ENT_WIN2
-      const uint32_t hi = hi0;
-#else
-      const uint32_t hi = (uint32_t)((p01 << r) >> 32);
-#endif
       const uint32_t z = d.z;
       const uint32_t t = hot_tab(m, d, z == 0u);
-      const uint32_t e = lookup<SLOW>(S, t, hi, z == 0u, m.soff);
+      const uint32_t e = lookup<SLOW>(S, t, hi0, z == 0u);
       // an invalid code's entry (1) takes one bit, advances nothing and
       // starts no block
       nbits = e & 31u;  // code + value bits, <= 31
@@ -1263,19 +1214,12 @@ __device__ int decode_state(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
     }
     {
       const bool more = d.pos < end;
-#if HJ_ENT_WIN2
       const uint32_t hi = win_next(hi0, lo0, nbits);
-#else
-      const uint32_t r2 = r + nbits;  // < 63
-      const uint64_t pr = r2 < 32u ? p01 : p12;
-      const uint32_t hi = (uint32_t)((pr << (r2 & 31u)) >> 32);
-#endif
       const uint32_t z = d.z;
       const uint32_t t = hot_tab(m, d, z == 0u);
-#if HJ_ENT_MORE
       // past the end: the null entry (no bits, no advance, so no block end)
       // in place of the symbol's -- one select instead of three masked results
-      const uint32_t es = lookup<SLOW>(S, t, hi, z == 0u, m.soff);
+      const uint32_t es = lookup<SLOW>(S, t, hi, z == 0u);
       const uint32_t e = more ? es : 0u;
       dec_skip(d, e & 31u);
       const uint32_t zn = z + __builtin_amdgcn_ubfe(e, 12, 7);
@@ -1284,17 +1228,6 @@ __device__ int decode_state(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
       const uint32_t bsn = hot_next(m, d.bs);
       d.z = bend ? 0u : zn;
       d.bs = bend ? bsn : d.bs;
-#else
-      const uint32_t e = lookup<SLOW>(S, t, hi, z == 0u, m.soff);
-      const uint32_t n2 = more ? (e & 31u) : 0u;
-      dec_skip(d, n2);
-      const uint32_t zn = z + __builtin_amdgcn_ubfe(e, 12, 7);
-      const bool bend = more && zn >= 64u;
-      nend += bend ? 1 : 0;
-      const uint32_t bsn = hot_next(m, d.bs);
-      d.z = bend ? 0u : (more ? zn : z);
-      d.bs = bend ? bsn : d.bs;
-#endif
     }
   }
   hot_flip(m, d);
@@ -1310,7 +1243,7 @@ __device__ void skip_open_block(const SH& S, Dec& d, uint32_t* win, const uint32
   while (d.z != 0u && d.pos < seg_end) {
     const uint32_t hi = dec_peek<NT>(d, win, words);
     const uint32_t z = d.z;
-    const uint32_t e = lookup<SLOW>(S, tab_slot(m, d, false), hi, false, m.soff);
+    const uint32_t e = lookup<SLOW>(S, tab_slot(m, d, false), hi, false);
     const uint32_t nbits = e & 31u;
     dec_skip(d, nbits);
     const uint32_t zn = z + __builtin_amdgcn_ubfe(e, 12, 7);
@@ -1343,9 +1276,6 @@ __device__ __forceinline__ int sym_value(uint32_t e, uint32_t hi, uint32_t nbits
   return ((int32_t)e >> kEntHiShift) + (int)(raw - neg);
 }
 
-#ifndef HJ_DESC_PAIRS
-#define HJ_DESC_PAIRS 0
-#endif
 struct BlockOut {
   uint32_t* ents;
   uint2* bdesc;
@@ -1356,10 +1286,6 @@ struct BlockOut {
   int dcv;          // its DC difference
   bool open;        // a block of this run is being decoded
   uint32_t pk[4];   // the last four entries (a shift register: pk[3] the newest)
-#if HJ_DESC_PAIRS
-  uint2 held;       // the descriptor of block hblk (the low half of a 16-byte pair), not stored yet
-  int hblk;         // -1: none held
-#endif
 #if HJ_OWN_CHECK
   int lo, hi;       // the run's blocks by the block scan, [lo, hi)
   uint32_t viol;    // descriptor stores outside them
@@ -1398,40 +1324,9 @@ __device__ __forceinline__ void close_block(BlockOut& o, int blk) {
 #if HJ_OWN_CHECK
     o.viol += (blk < o.lo || blk >= o.hi) ? 1u : 0u;
 #endif
-    const uint2 dv = make_uint2(o.bstart, (o.cur - o.bstart) | ((uint32_t)o.dcv << 16));
-#if HJ_DESC_PAIRS
-    // descriptors leave in 16-byte pairs (the even and odd block of the
-    // 16-byte aligned grid) when a run closes both: half the partial-line
-    // writes.  (Only a held block pairs: an image's first block at an odd
-    // position never does.)
-    uint2* p = o.bdesc + blk;
-    const bool hi = ((uintptr_t)p & 8u) != 0;
-    if (hi && o.hblk >= 0 && o.hblk == blk - 1) {
-      *reinterpret_cast<uint4*>(p - 1) = make_uint4(o.held.x, o.held.y, dv.x, dv.y);
-      o.hblk = -1;
-    } else {
-      if (o.hblk >= 0) o.bdesc[o.hblk] = o.held;
-      if (hi) {
-        *p = dv;
-        o.hblk = -1;
-      } else {
-        o.held = dv;
-        o.hblk = blk;
-      }
-    }
-#else
-    o.bdesc[blk] = dv;
-#endif
+    o.bdesc[blk] = make_uint2(o.bstart, (o.cur - o.bstart) | ((uint32_t)o.dcv << 16));
   }
   o.open = false;
-}
-
-// a descriptor still held for pairing, out (the run's end)
-__device__ __forceinline__ void flush_desc(BlockOut& o) {
-#if HJ_DESC_PAIRS
-  if (o.hblk >= 0) o.bdesc[o.hblk] = o.held;
-  o.hblk = -1;
-#endif
 }
 
 // the run's last r = cur & 3 entries, pk[4 - r .. 3], to the group at cur & ~3
@@ -1478,11 +1373,10 @@ __device__ int decode_write(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
   auto fast_step = [&](const uint32_t hi) -> bool {
     const uint32_t z = d.z;
     const bool is_dc = z == 0;
-    const uint32_t e = lookup<SLOW>(S, hot_tab(m, d, is_dc), hi, is_dc, m.soff);
+    const uint32_t e = lookup<SLOW>(S, hot_tab(m, d, is_dc), hi, is_dc);
     const uint32_t sz = __builtin_amdgcn_ubfe(e, 7, 5);
     const uint32_t nbits = e & 31u;
     const uint32_t zn = z + __builtin_amdgcn_ubfe(e, 12, 7);
-#if HJ_ENT_RULES
     // One unsigned test for the three rules: the entry's flag bits bound the
     // z its symbol may reach (hj_common.h) -- 64 a coefficient (none past
     // 63), 128 an EOB / ZRL (zn <= 127: any), 0 an invalid code or an AC
@@ -1491,17 +1385,6 @@ __device__ int decode_write(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
     const uint32_t lim = (e >> 13) & 0xC0u;
     const bool coef = lim == 64u;
     if (zn - 1u >= lim) return false;
-#else
-    const bool coef = (e >> 19) & 1u;
-    // One unsigned test for the three rules: the entry is valid (kind !=
-    // Slow) and not an AC size-0 symbol other than EOB / ZRL -- (e & (bad |
-    // kind)) - 0x20 in {0, 0x20, 0x40} -- and a coefficient does not run
-    // past 63: bit 31 of (64 - zn) & (e << 12) is (zn > 64) & coef (an EOB
-    // also has zn > 64: only bit 31 counts).
-    const uint32_t rules =
-        ((64u - zn) & ((e & 0x80000u) << 12)) | ((e & 0x100060u) - 0x20u);
-    if (rules > 0x40u) return false;
-#endif
     const int v = sym_value(e, hi, nbits, sz);
     dec_skip(d, nbits);
     const bool ac = coef & !is_dc;
@@ -1517,37 +1400,22 @@ __device__ int decode_write(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
     d.bs = bend ? bsn : d.bs;
     return true;
   };
-#if HJ_ENT_FASTSTOP
   // (pos + 32 > seg_end as one compare with a bound made once: pos >= seg_end - 31)
   const uint32_t near_end = seg_end >= 31u ? seg_end - 31u : 0u;
   auto fast_stop = [&]() -> bool {
     const bool is_dc = d.z == 0u;
     return (is_dc & ((d.pos >= end) | (nb >= seg_end_blk))) | (d.pos >= near_end);
   };
-#else
-  auto fast_stop = [&]() -> bool {
-    const bool is_dc = d.z == 0u;
-    return (is_dc & ((d.pos >= end) | (nb >= seg_end_blk))) | (d.pos + 32u > seg_end);
-  };
-#endif
   // two steps per window read (as decode_state)
   for (;;) {
     if (fast_stop()) break;
     uint64_t p01, p12;
     const uint32_t r = dec_peek3<NT>(d, win, words, p01, p12);
     const uint32_t pos0 = d.pos;
-#if HJ_ENT_WIN2
     const uint32_t hi0 = (uint32_t)((p01 << r) >> 32), lo0 = (uint32_t)((p12 << r) >> 32);
     if (!fast_step(hi0)) break;
     if (fast_stop()) break;
     if (!fast_step(win_next(hi0, lo0, d.pos - pos0))) break;  // (a step taken took >= 1 bit)
-#else
-    if (!fast_step((uint32_t)((p01 << r) >> 32))) break;
-    if (fast_stop()) break;
-    const uint32_t r2 = r + (d.pos - pos0);  // < 63
-    const uint64_t pr = r2 < 32u ? p01 : p12;
-    if (!fast_step((uint32_t)((pr << (r2 & 31u)) >> 32))) break;
-#endif
   }
   // a block in progress is this run's only if the fast path started it (a
   // run that entered inside the previous run's block -- skip_open_block
@@ -1557,7 +1425,7 @@ __device__ int decode_write(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
     const uint32_t hi = dec_peek<NT>(d, win, words);
     const uint32_t z = d.z;
     const bool is_dc = z == 0;
-    const uint32_t e = lookup<SLOW>(S, hot_tab(m, d, is_dc), hi, is_dc, m.soff);
+    const uint32_t e = lookup<SLOW>(S, hot_tab(m, d, is_dc), hi, is_dc);
     const bool valid = (e & 0x60u) != 0u;
     const uint32_t sz = __builtin_amdgcn_ubfe(e, 7, 5);
     const uint32_t nbits = e & 31u;
@@ -1566,7 +1434,7 @@ __device__ int decode_write(const SH& S, Dec& d, uint32_t* win, const uint32_t* 
     const uint32_t zinc = __builtin_amdgcn_ubfe(e, 12, 7);
     const bool coef = valid && ((e >> 19) & 1u);
     // (the rejected AC size-0 symbol: valid with neither flag bit, hj_common.h)
-    const bool refused = HJ_ENT_RULES ? (e & 0x180000u) == 0u : ((e >> 20) & 1u) != 0u;
+    const bool refused = (e & 0x180000u) == 0u;
     const bool bad = !valid || (coef && z + zinc > 64u) || refused;
     // The sequential decoder's rules, branch-free (the lanes of a wave sit
     // at unrelated symbols): it stops at the segment's last block and never
@@ -1892,7 +1760,7 @@ __device__ __forceinline__ void chain_sweep(SH& S, uint4* sst, const uint32_t* _
     const uint32_t hi = (uint32_t)((pr << (r & 31u)) >> 32);
     const bool dc = lane == 0 && z == 0u;
     const uint32_t e =
-        lookup_fast<kSlow>(S, __builtin_amdgcn_ubfe(dc ? tm.dmap : tm.amap, bs, 3), hi, tm.soff);
+        lookup_fast<kSlow>(S, __builtin_amdgcn_ubfe(dc ? tm.dmap : tm.amap, bs, 3), hi);
     // a Slow entry (a code the LDS tables do not resolve): nx = 128 + l makes
     // the walk stop there with o >= 128, and the symbol takes lookup()
     const bool slow = ((e >> 5) & 3u) == kKindSlow;
@@ -1956,8 +1824,8 @@ __device__ __forceinline__ void chain_sweep(SH& S, uint4* sst, const uint32_t* _
         const uint64_t pr = ((uint64_t)cw[r >> 5] << 32) | cw[(r >> 5) + 1];
         const uint32_t hi = (uint32_t)((pr << (r & 31u)) >> 32);
         const bool isdc = z == 0u;
-        const uint32_t e = rfl(lookup<kSlow>(
-            S, __builtin_amdgcn_ubfe(isdc ? tm.dmap : tm.amap, bs, 3), hi, isdc, tm.soff));
+        const uint32_t e =
+            rfl(lookup<kSlow>(S, __builtin_amdgcn_ubfe(isdc ? tm.dmap : tm.amap, bs, 3), hi, isdc));
         pos += e & 31u;
         const uint32_t zn = z + __builtin_amdgcn_ubfe(e, 12, 7);
         if (zn >= 64u) {
@@ -2071,18 +1939,16 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       // of the pool, each at its level-1 index modulo the share -- they are
       // consecutive level-1 cells and parse_kernel sent a table with more of
       // them than the share holds to the wide path, so no two collide
-      constexpr bool kShared = HJ_ENT_SUBADDR && !kSlow;
+      constexpr bool kShared = !kSlow;
       const bool fits = kShared ? nsub << kSubBits <= kSubShare
                                 : (pool + nsub) << kSubBits <= kSubPool;
       const int base = pool;
       if (fits && !kShared) pool += nsub;
-      if (!HJ_ENT_SUBADDR && fits && nsub > 0)
-        tm.soff |= (uint64_t)((uint32_t)((base - T.sub_lo) << kSubBits) & 0xFFFFu) << (16 * i);
       for (int k = tid; k < kLutSize; k += NT) {
         uint32_t e = T.lut[k];
         if ((e >> 5 & 3) == kKindSub) {
           if (!fits) e = 1u;
-          else if (HJ_ENT_SUBMARK && !kSlow) e = kSubMark;
+          else if (kShared) e = kSubMark;
           else e += (uint32_t)base << kEntHiShift;
         }
         S.lut[i][k] = e;
@@ -2105,10 +1971,8 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       tm.dmap |= (uint32_t)ldc[c] << (3 * b);
       tm.amap |= (uint32_t)lac[c] << (3 * b);
       tm.cmap |= (uint32_t)c << (3 * b);
-#if HJ_ENT_NEXTBS
       tm.rdmap |= (uint32_t)ldc[c] << (3 * (bpm - 1 - b));
       tm.ramap |= (uint32_t)lac[c] << (3 * (bpm - 1 - b));
-#endif
     }
     tm.bs_end = 3u * (uint32_t)bpm;
     if (tid == 0) {
@@ -2510,13 +2374,11 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       o.cur = (uint32_t)b0 * 64u;
       o.last = (uint32_t)nblocks * 64u - 1u;
       o.nblk = (uint32_t)nblocks;
-#if HJ_ENT_STOREBASE
       // The store bases and bounds are uniform, and the kernel has no scalar
       // register left for them: kept there, each store of the write step
       // fetched them back from spill lanes (v_readlane + wait states).  As
       // vector registers they cost the step nothing.
       asm volatile("" : "+v"(o.ents), "+v"(o.bdesc), "+v"(o.last), "+v"(o.nblk));
-#endif
 #if HJ_ABLATIONS
       o.no_list = (ablate & kAblEntList) != 0;
       o.no_desc = (ablate & kAblEntDesc) != 0;
@@ -2524,10 +2386,6 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
       o.bstart = o.cur;
       o.dcv = 0;
       o.open = false;
-#if HJ_DESC_PAIRS
-      o.hblk = -1;
-      o.held = make_uint2(0u, 0u);
-#endif
 #if HJ_OWN_CHECK
       o.lo = b0;
       o.hi = b1;
@@ -2571,7 +2429,6 @@ __device__ __forceinline__ void entropy_image(EntShared<NT, NTAB>& S, const int 
         k = k2 + 1;
       }
       flush_tail(o);
-      flush_desc(o);
 #if HJ_OWN_CHECK
       if (o.viol) atomicAdd(&S.own_viol, o.viol);
 #endif
@@ -2757,9 +2614,7 @@ entropy_kernel(const uint8_t* __restrict__ clean, const uint32_t* __restrict__ s
 //     chunk start.
 // ---------------------------------------------------------------------------
 
-#ifndef HJ_MS_PRIO
-#define HJ_MS_PRIO 3
-#endif
+constexpr int kMsPrio = 3;  // multiscan_kernel's wave priority (the A/B: where it is set)
 constexpr int kMsMaxScans = 64;
 constexpr int kMsMaxMarks = 512;
 
@@ -4183,7 +4038,7 @@ __global__ void __launch_bounds__(256) multiscan_kernel(const uint8_t* __restric
   // other waves -- the other lanes' kernels take the issue cycles they leave
   // (r05 A/B, one progressive image per pipelined batch: 3.71 -> 3.61 ms per
   // batch, profiles/r05/ab/multiscan_prio.txt)
-  __builtin_amdgcn_s_setprio(HJ_MS_PRIO);
+  __builtin_amdgcn_s_setprio(kMsPrio);
   const ImageDesc& dd = desc[img];
   const uint8_t* d = bytes + dd.in_off;
   const int size = (int)dd.in_size;
@@ -4495,10 +4350,10 @@ __global__ void __launch_bounds__(256) multiscan_kernel(const uint8_t* __restric
   // ---- decoder waves: each takes the first ready scan, decodes it and marks
   // it done ----
   const int lane = tid & 63;
-#ifndef HJ_MS_WAVES
-#define HJ_MS_WAVES 4
-#endif
-  if ((__builtin_amdgcn_readfirstlane(tid) >> 6) < HJ_MS_WAVES) {
+  // (four of them; one wave, the scans one after another, decoded the
+  // dominant scan no faster: profiles/r05/prog/)
+  constexpr int kMsWaves = 4;
+  if ((__builtin_amdgcn_readfirstlane(tid) >> 6) < kMsWaves) {
     __builtin_amdgcn_s_setprio(2);  // the serial bit chains: first in issue
     const bool progu = ms_i(prog) != 0;
     const int sizeu = ms_i(size);
@@ -4668,29 +4523,16 @@ typedef int16_t __attribute__((may_alias)) hj_i16_alias;
 typedef __attribute__((address_space(3))) hj_i16_alias hj_lds_i16;
 typedef __attribute__((address_space(3))) uint32_t hj_lds_u32;
 
-// idct_kernel<simple>'s instruction cuts, one switch each (default on; a
-// variant build without one measures it: make variant DEFS=-DHJ_IDCT_SEED=0):
+// idct_kernel<simple> is written for instruction count.  Each of these was
+// measured against the form it replaced, which is gone from the tree; the
+// numbers are in profiles/r09/idct (ab.txt, counters_summary_no_<NAME>.txt):
 //   SEED     the first dot2 of a chain takes its bias as the third operand
 //   DCBIAS   the DC-only row shortcut as a bias of the full sums
 //   PACK     column sums shifted, clipped and packed two at a time
 //   SCATTER  half-word operand selects in the list scatter
 //   GATHER   a group's 16 dequantisation-table reads ahead of its 16 stores
 //   INDEX    block -> (MCU, block of MCU, MCU column, row) by multiplication
-#ifndef HJ_IDCT_SEED
-#define HJ_IDCT_SEED 1
-#endif
-#ifndef HJ_IDCT_DCBIAS
-#define HJ_IDCT_DCBIAS 1
-#endif
-#ifndef HJ_IDCT_PACK
-#define HJ_IDCT_PACK 1
-#endif
-#ifndef HJ_IDCT_SCATTER
-#define HJ_IDCT_SCATTER 1
-#endif
-#ifndef HJ_IDCT_GATHER
-#define HJ_IDCT_GATHER 1
-#endif
+//            (idct_divmod, hj_common.h)
 
 // byte offset of IDCT slot s (kSlotOrder) in the word-major block of NT threads
 template <int NT>
@@ -4720,27 +4562,20 @@ __device__ __forceinline__ void list_block(const uint32_t* __restrict__ ents, co
                                            const uint32_t* sqc, uint32_t* b32) {
 #pragma unroll
   for (int w = 0; w < kBlkWords; w++) b32[w * NT] = w == 0 ? (bd.y >> 16) : 0u;
-#if HJ_IDCT_SCATTER
   // (b32 points into the kernel's LDS: 32-bit LDS addresses)
   const uint32_t blk_a = (uint32_t)(uintptr_t)(hj_lds_u32*)b32;
   const uint32_t dummy_a = blk_a + (uint32_t)(kBlkWords * NT * 4);
-#else
-  uint8_t* blk = reinterpret_cast<uint8_t*>(b32);
-  uint8_t* dummy = reinterpret_cast<uint8_t*>(b32 + kBlkWords * NT);
-#endif
   const uint32_t cap = (uint32_t)nblocks * 64u;
   const uint32_t lo = bd.x & 3u, start = bd.x & ~3u;
   uint32_t count = min(bd.y & 0xFFFFu, 63u);
   if (start > cap - 64u) count = 0;  // only an unwritten list (a failed scan)
-  const uint32_t hi_e = lo + count;
   const uint4* e4 = reinterpret_cast<const uint4*>(ents + (size_t)coef_off * 64 + start);
-  const uint32_t n4 = (hi_e + 3u) >> 2;
+  const uint32_t n4 = (lo + count + 3u) >> 2;
   for (uint32_t i = 0; i < n4; i += 4) {
     // unconditional loads (index clamped into the list), then the scatter
     uint4 q[4];
 #pragma unroll
     for (int u = 0; u < 4; u++) q[u] = e4[min(i + u, n4 - 1u)];
-#if HJ_IDCT_GATHER
     // the 16 table words ahead of the 16 stores: a store may alias the table
     // for all the compiler knows, so read entry by entry each table read
     // waits for the store before it and each store for its read -- 16 LDS
@@ -4753,19 +4588,13 @@ __device__ __forceinline__ void list_block(const uint32_t* __restrict__ ents, co
       qsv[4 * u + 2] = sqc[q[u].z & 63u];
       qsv[4 * u + 3] = sqc[q[u].w & 63u];
     }
-#endif
 #pragma unroll
     for (int u = 0; u < 4; u++) {
       const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
 #pragma unroll
       for (int h = 0; h < 4; h++) {  // (outside the list: into the dummy word)
         const uint32_t k = 4u * (i + u) + h;
-#if HJ_IDCT_GATHER
         const uint32_t qs = qsv[4 * u + h];
-#else
-        const uint32_t qs = sqc[w[h] & 63u];
-#endif
-#if HJ_IDCT_SCATTER
         // the entry's and the table word's halves picked by the instructions
         // themselves (SDWA): level x quantiser from the high halves, block
         // address + slot offset from the low half; k in [lo, lo + count) as
@@ -4781,11 +4610,6 @@ __device__ __forceinline__ void list_block(const uint32_t* __restrict__ ents, co
             : "v"(w[h]), "v"(qs));
         const uint32_t a32 = k - lo < count ? in_a : dummy_a;
         *reinterpret_cast<hj_lds_i16*>(a32) = (int16_t)prod;
-#else
-        uint8_t* dst = k >= lo && k < hi_e ? blk + (qs & 0xFFFFu) : dummy;
-        // (16-bit multiply: the low half is the sequential decoder's int16 product)
-        *reinterpret_cast<hj_i16_alias*>(dst) = (int16_t)pk_mul_lo16(w[h] >> 16, qs >> 16);
-#endif
       }
     }
   }
@@ -4813,22 +4637,14 @@ __device__ __forceinline__ uint32_t pack_lo16(uint32_t lo, uint32_t hi) {
 // (or of 0) per chain; the three-operand form reads the bias where it is.  Its
 // weight is an SGPR (VOP3: one constant-bus operand, no literal).
 __device__ __forceinline__ int32_t dot2_seed(uint32_t a, uint32_t w, int32_t c) {
-#if HJ_IDCT_SEED
   int32_t d;
   asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(w), "v"(c));
   return d;
-#else
-  return dot2(a, w, c);
-#endif
 }
 __device__ __forceinline__ int32_t dot2_seed0(uint32_t a, uint32_t w) {
-#if HJ_IDCT_SEED
   int32_t d;
   asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(d) : "v"(a), "s"(w));
   return d;
-#else
-  return dot2(a, w, 0);
-#endif
 }
 // an 8-point pass: a[k] even sums (+ bias), b[k] odd sums
 __device__ __forceinline__ void sidct8(uint32_t e0, uint32_t e1, uint32_t o0, uint32_t o1,
@@ -4863,22 +4679,12 @@ __device__ __forceinline__ void simple_idct_rows(const uint32_t* b32, uint32_t (
     const uint4 q = blk_row<NT>(b32, i);
     int32_t a[4], b[4];
     const bool dc_only = ((q.x >> 16) | q.y | q.z | q.w) == 0u;
-#if HJ_IDCT_DCBIAS
     sidct8(q.x, q.y, q.z, q.w, (1 << 10) + (dc_only ? sext16(q.x) : 0), a, b);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       r[i][k] = (uint32_t)((int32_t)((uint32_t)a[k] + (uint32_t)b[k]) >> 11);
       r[i][7 - k] = (uint32_t)((int32_t)((uint32_t)a[k] - (uint32_t)b[k]) >> 11);
     }
-#else
-    sidct8(q.x, q.y, q.z, q.w, 1 << 10, a, b);
-    const uint32_t dc = q.x << 3;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      r[i][k] = dc_only ? dc : (uint32_t)((int32_t)((uint32_t)a[k] + (uint32_t)b[k]) >> 11);
-      r[i][7 - k] = dc_only ? dc : (uint32_t)((int32_t)((uint32_t)a[k] - (uint32_t)b[k]) >> 11);
-    }
-#endif
   }
 }
 // column k of the row pass's output: s[j] = the sum of row j before >> 20.
@@ -4892,19 +4698,6 @@ __device__ __forceinline__ void simple_idct_col(const uint32_t (&r)[8][8], int k
   for (int u = 0; u < 4; u++) {
     s[u] = (int32_t)((uint32_t)a[u] + (uint32_t)b[u]);
     s[7 - u] = (int32_t)((uint32_t)a[u] - (uint32_t)b[u]);
-  }
-}
-// px: 64 pixels, row-major
-template <int NT>
-__device__ __forceinline__ void simple_idct_slots(const uint32_t* b32, int32_t (&px)[64]) {
-  uint32_t r[8][8];
-  simple_idct_rows<NT>(b32, r);
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    int32_t s[8];
-    simple_idct_col(r, k, s);
-#pragma unroll
-    for (int j = 0; j < 8; j++) px[8 * j + k] = clip_u8_opaque(s[j] >> 20);
   }
 }
 
@@ -4940,13 +4733,10 @@ __device__ __forceinline__ void simple_idct_packed(const uint32_t* b32, uint2 (&
 }
 
 // The thread's LDS block (b32: its word 0) -> 8x8 pixels (u8 values in
-// int32), row-major.
+// int32), row-major: the islow transform (IDCT 1) or none (2).
 template <int NT, int IDCT>
 __device__ __forceinline__ void idct_block(const uint32_t* b32, int32_t (&px)[64]) {
-  if (IDCT == 0) {
-    simple_idct_slots<NT>(b32, px);
-    return;
-  }
+  static_assert(IDCT == 1 || IDCT == 2, "the simple IDCT packs its own rows (simple_idct_packed)");
   // natural order from the slot layout (a compile-time permutation)
   int32_t blk[64];
 #pragma unroll
@@ -4972,20 +4762,18 @@ __device__ __forceinline__ void idct_block(const uint32_t* b32, int32_t (&px)[64
 // The same as the 8 pixel rows a kernel stores (bytes in x order).
 template <int NT, int IDCT>
 __device__ __forceinline__ void idct_block_rows(const uint32_t* b32, uint2 (&rows)[8]) {
-#if HJ_IDCT_PACK
-  if (IDCT == 0) {
+  if constexpr (IDCT == 0) {
     simple_idct_packed<NT>(b32, rows);
-    return;
-  }
-#endif
-  int32_t px[64];
-  idct_block<NT, IDCT>(b32, px);
+  } else {
+    int32_t px[64];
+    idct_block<NT, IDCT>(b32, px);
 #pragma unroll
-  for (int r = 0; r < 8; r++) {
-    rows[r].x = (uint32_t)px[8 * r] | ((uint32_t)px[8 * r + 1] << 8) |
-                ((uint32_t)px[8 * r + 2] << 16) | ((uint32_t)px[8 * r + 3] << 24);
-    rows[r].y = (uint32_t)px[8 * r + 4] | ((uint32_t)px[8 * r + 5] << 8) |
-                ((uint32_t)px[8 * r + 6] << 16) | ((uint32_t)px[8 * r + 7] << 24);
+    for (int r = 0; r < 8; r++) {
+      rows[r].x = (uint32_t)px[8 * r] | ((uint32_t)px[8 * r + 1] << 8) |
+                  ((uint32_t)px[8 * r + 2] << 16) | ((uint32_t)px[8 * r + 3] << 24);
+      rows[r].y = (uint32_t)px[8 * r + 4] | ((uint32_t)px[8 * r + 5] << 8) |
+                  ((uint32_t)px[8 * r + 6] << 16) | ((uint32_t)px[8 * r + 7] << 24);
+    }
   }
 }
 

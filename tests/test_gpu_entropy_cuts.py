@@ -1,5 +1,6 @@
 """GPU parity of entropy_kernel where the instruction cuts of its symbol step
-(hj_common.h HJ_ENT_*: the second-level address from a fixed share of the
+(listed in hj_common.h above kSubShare; the forms they replaced were measured
+and removed, profiles/r15/entropy_step: the second-level address from a fixed share of the
 sub-table pool, the level-1 mark, the entry's flag bits as a bound on z, the
 funnel-shifted second step of a window read) could go wrong, on hand-written
 streams (tests/jpeg_writer.py).  Bit-exact against the oracle:

@@ -71,3 +71,21 @@ def test_planner_includes_no_hip_header():
     src = open(DUMP).read()
     assert re.findall(r'#\s*include\s*"([^"]+)"', src) == ["../../spdl_amd/csrc/hj_layout.h"]
     assert not HIP_INCLUDE.search(src)
+
+
+def test_no_ab_switch_in_the_native_sources():
+    """The only HJ_* names a preprocessor conditional of spdl_amd/csrc may test
+    are the host / device qualifier, the IDCT header's guard and the
+    diagnostic builds (instruments that bench.py, tools/ and the tests use)."""
+    allowed = {"HJ_HD", "HJ_DC_BIAS_DEFINED", "HJ_ABLATIONS", "HJ_OWN_CHECK", "HJ_PARSE_PROF",
+               "HJ_MS_PROF", "HJ_MS_COUNT", "HJ_MS_COUNT2"}
+    found = set()
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith((".hip", ".h", ".cpp")):
+            for line in open(os.path.join(CSRC, name)):
+                if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                    found |= set(re.findall(r"\bHJ_\w+", line))
+    assert found == allowed, (
+        f"conditionals on {sorted(found - allowed)} added, on {sorted(allowed - found)} gone: "
+        "an A/B switch does not stay in the tree -- decide it, record the measurement under "
+        "profiles/ and remove the switch with the losing arm")
