@@ -136,7 +136,13 @@ enum spdl_hj_csc { SPDL_HJ_CSC_SWSCALE = 0, SPDL_HJ_CSC_JFIF = 1 };
  *         in a way nothing here can pin, and a refusal is better than a guess
  *   pad bytes (color=black): yuvj Y = 0, U = V = 128; gray8 16 (drawutils
  *         uses the limited-range luma of black for gray8)
- * Gray and 4:4:4 have ratio 1: none of the rounding applies to them. */
+ * Gray and 4:4:4 have ratio 1: none of the rounding applies to them.
+ *
+ * Limits of the scale (each SPDL_HJ_ERR_BAD_GEOMETRY for that image): no
+ * scaled or output side over 65535; no axis, luma or chroma, whose filter
+ * reaches swscale's 256 taps (it would cascade two contexts); and no axis
+ * whose ratio src / dst reaches 32768, where swscale's own increment
+ * ((src << 16) / dst, an int) no longer fits. */
 typedef struct spdl_hj_output {
   int32_t pix_fmt;      /* spdl_hj_pix_fmt */
   int32_t dtype;        /* spdl_hj_dtype; F16/BF16 apply (x/255 - mean)/std */

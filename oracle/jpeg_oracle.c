@@ -1327,6 +1327,7 @@ int jo_sws_axis(int src, int dst, int kind, int align, int one, int src_pos, int
   if (src <= 0 || dst <= 0) return -1;
   const int64_t inc = (((int64_t)src << 16) + (dst >> 1)) / dst;
   jo_sws_filter f;
+  if (inc > INT32_MAX) return -1;  /* swscale's xInc is an int (see jo_sws_init) */
   if (jo_sws_init_filter((int)inc, src, dst, align, one, kind, src_pos, dst_pos, &f)) return -1;
   int size = f.size;
   if ((int64_t)size * dst > cap) {

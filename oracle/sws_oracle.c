@@ -373,6 +373,12 @@ int jo_sws_init(jo_sws* s, int srcW, int srcH, int hsub, int vsub, int gray, int
   s->chrDstH = dstH;
   const int64_t chrXInc = (((int64_t)s->chrSrcW << 16) + (s->chrDstW >> 1)) / s->chrDstW;
   const int64_t chrYInc = (((int64_t)s->chrSrcH << 16) + (s->chrDstH >> 1)) / s->chrDstH;
+  /* swscale keeps every increment in an int.  A ratio of 32768 or more does
+   * not fit; what libswscale makes of the wrapped value is nothing to pin, so
+   * the geometry is refused, on the chroma axes' own ratios too. */
+  if (lumXInc > INT32_MAX || lumYInc > INT32_MAX ||
+      (!gray && (chrXInc > INT32_MAX || chrYInc > INT32_MAX)))
+    return -1;
   if (jo_sws_init_filter((int)lumXInc, srcW, dstW, 4, 1 << 14, kind, local_pos(0, 0),
                     local_pos(0, 0), &s->hl) ||
       jo_sws_init_filter((int)lumYInc, srcH, dstH, 2, 1 << 12, kind, local_pos(0, 0),

@@ -211,6 +211,10 @@ bool build_axis(int src, int dst, int align, int one, int kind, int src_pos, int
   using Key = std::tuple<int, int, int, int, int, int, int>;
   thread_local std::map<Key, std::shared_ptr<const SwsAxis>> memo;
   const Key key{src, dst, align, one, kind, src_pos, dst_pos};
+  // swscale keeps xInc in an int: a ratio of 32768 or more does not fit, and
+  // what the wrapped value would select (an upscale's few taps) is nothing to
+  // pin.  Refused, like every filter swscale would cascade.
+  if (xinc(src, dst) > INT32_MAX) return false;
   auto it = memo.find(key);
   if (it == memo.end()) {
     auto a = std::make_shared<SwsAxis>();

@@ -11,6 +11,7 @@ all-reduce of elapsed time (bench.py), or a SUM of counts.
 
 from __future__ import annotations
 
+import atexit
 import os
 import socket
 import subprocess
@@ -109,7 +110,19 @@ def init_host_group() -> tuple[int, int, int]:
 
         if not dist.is_initialized():
             dist.init_process_group("gloo", rank=rank, world_size=world)
+            # A group that is still alive at interpreter exit is torn down by
+            # static destructors, in a race with gloo's own threads (the rank
+            # then aborts: "terminate called without an active exception").
+            # The rank that made the group ends it while the interpreter is whole.
+            atexit.register(_destroy_host_group)
     return rank, world, local
+
+
+def _destroy_host_group() -> None:
+    import torch.distributed as dist
+
+    if dist.is_available() and dist.is_initialized():
+        dist.destroy_process_group()
 
 
 def barrier() -> None:

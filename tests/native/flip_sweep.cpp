@@ -9,6 +9,7 @@
 //    once, every pixel lands at its mirrored coordinate, the tile coordinate
 //    stays inside the tile, and the inverse map finds the pixel again -- for
 //    the box and for a 4:2:0 chroma plane of it, ceil(ow / 2) x ceil(oh / 2).
+//    The same for boxes with one side of 32768 or 65535 and the other 1 or 17.
 // 2. The planner's rules (hj_layout.h build_layout): counts, values, the JFIF
 //    refusal, all-zero flips being no flips, and the flag vector of a views
 //    submission with a refused view in the middle.
@@ -93,6 +94,26 @@ void sweep_tiles() {
             boxes += 2;
           }
   printf("tiles: %lld boxes, %lld pixels\n", boxes, px);
+}
+
+// The same at the format's limit (printed after the planner's line)
+void sweep_extreme_tiles() {
+  std::vector<uint8_t> seen;
+  long long px = 0, boxes = 0;
+  // boxes at the format's limit: one side of 65535 (and 32768), the other 1 or
+  // 17, with their chroma planes
+  for (int L : {32768, 65535})
+    for (int S : {1, 17})
+      for (int wide = 0; wide < 2; wide++)
+        for (int cc : {16, 256})
+          for (int rb : {1, 64})
+            for (int flip = 0; flip < 4; flip++) {
+              const int ow = wide ? L : S, oh = wide ? S : L;
+              px += sweep_box(ow, oh, rb, cc, flip, seen);
+              px += sweep_box((ow + 1) / 2, (oh + 1) / 2, rb, cc, flip, seen);
+              boxes += 2;
+            }
+  printf("extreme tiles: %lld boxes, %lld pixels\n", boxes, px);
 }
 
 // ---- 2. the planner ---------------------------------------------------------------
@@ -240,6 +261,7 @@ void planner_rules() {
 int main() {
   sweep_tiles();
   planner_rules();
+  sweep_extreme_tiles();
   if (failures) {
     fprintf(stderr, "%d checks failed\n", failures);
     return 1;

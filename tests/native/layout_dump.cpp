@@ -4,8 +4,8 @@
 //       -static-libasan -static-libubsan tests/native/layout_dump.cpp
 //       spdl_amd/csrc/hj_layout.cpp spdl_amd/csrc/hj_sws.cpp -o layout_dump
 // A fixed table of submissions built from hand-filled probes (no JPEG bytes):
-// frame formats, front-end sizes, output chains, planar YUV, source crops and
-// views.  One line per case: the return code, the error text, the statuses the
+// frame formats, front-end sizes, output chains, planar YUV, source crops,
+// views and frames at the format's limits.  One line per case: the return code, the error text, the statuses the
 // planner wrote (per image: i:rc; per view group: every entry, -7 = untouched)
 // and, for a layout that was built, every scalar of Layout and FNV-1a hashes of
 // the raw bytes of desc, tables and work -- the bytes the device gets.
@@ -398,6 +398,55 @@ void eviction_case() {
   dump(s, &cache);
 }
 
+// Frames at the format's limits (printed last: the lines above stay in place):
+// sides of 65535 among ordinary images, the three limits of the scale (output
+// sides over 65535, 256 taps, a ratio of 32768), nblocks >= 2^24 beside
+// ordinary neighbours, and rectangles at the far end of a 65535-pixel side.
+void extreme_cases() {
+  const spdl_hj_output full = chain(), r32 = fit(32, 32), v24 = fit(24, 24);
+  dump(sub("ext-wide-444", {y420(64, 48), y444(65535, 8), y420(64, 48)}, fit(2048, 8)), nullptr);
+  dump(sub("ext-tall-420", {y420(64, 48), y420(17, 65535), y420(64, 48)}, fit(17, 2048)), nullptr);
+  dump(sub("ext-tall-411", {y411(16, 65535)}, fit(16, 4096)), nullptr);
+  dump(sub("ext-wide-440", {y440(65535, 17)}, fit(4096, 17)), nullptr);
+  dump(sub("ext-full-gray", {gray(65535, 1), gray(65535, 1)}, full), nullptr);
+  dump(sub("ext-full-420-odd", {y420(65535, 16)}, full), nullptr);
+  dump(sub("ext-full-420-even", {y420(65534, 16)}, full), nullptr);
+  dump(sub("ext-full-tall-422", {y422(8, 65535)}, full), nullptr);
+  dump(sub("ext-f16-planar", {y444(1, 65535)}, with(with(chain(SPDL_HJ_FMT_RGB), &spdl_hj_output::dtype,
+                                                         SPDL_HJ_DTYPE_F16), &spdl_hj_output::resize, 0)),
+       nullptr);
+  dump(sub("ext-yuv-420", {y420(65534, 16)}, fit(2048, 16, 0, SPDL_HJ_FMT_YUV)), nullptr);
+  dump(sub("ext-yuv-full", {y420(65535, 17)}, chain(SPDL_HJ_FMT_YUV)), nullptr);
+  // the limits of the scale: 40 -> 1 is the only one swscale takes (a refused
+  // scale fails its call, so one call each)
+  dump(sub("ext-ratio-40", {gray(40, 16), gray(16, 40)}, fit(1, 1)), nullptr);
+  for (int src : {32767, 32768, 32769, 40000, 65535}) {
+    dump(sub(("ext-ratio-h-" + std::to_string(src)).c_str(), {gray(40, 16), gray(src, 16)}, fit(1, 16)), nullptr);
+    dump(sub(("ext-ratio-v-" + std::to_string(src)).c_str(), {gray(16, 40), gray(16, src)}, fit(16, 1)), nullptr);
+  }
+  dump(sub("ext-ratio-chroma", {y422(64, 16), y422(65535, 16)}, fit(2, 16)), nullptr);
+  dump(sub("ext-out-65535", {gray(32768, 8)}, fit(65535, 8)), nullptr);
+  dump(sub("ext-out-over-upscale", {gray(64, 8), gray(32768, 8)}, fit(65536, 8)), nullptr);
+  dump(sub("ext-out-over-pad", {gray(32768, 8)}, pad(fit(65535, 8), 65536, 8)), nullptr);
+  // nblocks >= 2^24 and its neighbours
+  dump(sub("ext-too-large-first", {y444(65535, 65535), y420(64, 48)}, r32), nullptr);
+  dump(sub("ext-too-large-middle", {y420(64, 48), y444(65535, 65535), y420(64, 48)}, r32), nullptr);
+  dump(viewed(sub("ext-too-large-viewed", {y420(64, 48), y444(65535, 65535)}, full),
+              {vg(v24, 24, 24, {{0, {4, 4, 30, 30}}, {1, {0, 0, 64, 64}}})}),
+       nullptr);
+  // rectangles at the far end
+  dump(cropped(sub("ext-crop-far", {y420(65535, 17), y411(17, 65535), gray(65535, 8), y420(64, 48)}, r32),
+               {{65535 - 70, 0, 64, 8}, {0, 65535 - 70, 8, 64}, {65535 - 9, 0, 64, 8}, kNone}),
+       nullptr);
+  dump(cropped(sub("ext-crop-whole-span", {y444(65535, 8), y444(65535, 8)}, fit(2048, 8)),
+               {{0, 0, 65535, 8}, kNone}),
+       nullptr);
+  dump(viewed(sub("ext-view-ends", {y444(65535, 8), y420(64, 48), y420(16, 65535)}, full),
+              {vg(v24, 24, 24, {{0, {0, 0, 64, 8}}, {0, {65535 - 64, 0, 64, 8}}, {1, kNone},
+                                {2, {0, 65535 - 65, 8, 64}}, {2, {0, 0, 8, 64}}})}),
+       nullptr);
+}
+
 // ---- --time ---------------------------------------------------------------------------
 double ns_per_call(const Sub& s, int reps) {
   const int n = (int)s.infos.size();
@@ -460,5 +509,6 @@ int main(int argc, char** argv) {
   for (const Sub& s : cases()) dump(s, nullptr);
   shared_cache_cases();
   eviction_case();
+  extreme_cases();
   return 0;
 }

@@ -8,7 +8,8 @@
 //    and the eight codes: the landed tiles partition the final box exactly
 //    once, every chain pixel lands where the header's formula says, the landed
 //    coordinate stays inside the landed tile, and the inverse map finds the
-//    pixel again.  Codes 0..3 agree with tile_flip.
+//    pixel again.  Codes 0..3 agree with tile_flip.  The same for boxes with
+//    one side of 32768 or 65535 and the other 1 or 17.
 // 2. The planner's rules (hj_layout.h build_layout): a transposed image is
 //    planned from the swapped chain and keeps that chain's box, the "one size"
 //    rule is about final boxes, the refusals (count, value, JFIF, planar YUV
@@ -114,6 +115,24 @@ void sweep_tiles() {
             boxes++;
           }
   printf("tiles: %lld boxes, %lld pixels\n", boxes, px);
+}
+
+// The same at the format's limit (printed after the planner's line)
+void sweep_extreme_tiles() {
+  std::vector<uint8_t> seen;
+  long long px = 0, boxes = 0;
+  // boxes at the format's limit: one side of 65535 (and 32768), the other 1 or
+  // 17 -- a transposing code makes the long side the other one
+  for (int L : {32768, 65535})
+    for (int S : {1, 17})
+      for (int wide = 0; wide < 2; wide++)
+        for (int cc : {16, 256})
+          for (int rb : {1, 64})
+            for (int code = 0; code < 8; code++) {
+              px += sweep_box(wide ? L : S, wide ? S : L, rb, cc, code, seen);
+              boxes++;
+            }
+  printf("extreme tiles: %lld boxes, %lld pixels\n", boxes, px);
 }
 
 // ---- 2. the planner ---------------------------------------------------------------
@@ -333,6 +352,7 @@ void planner_rules() {
 int main() {
   sweep_tiles();
   planner_rules();
+  sweep_extreme_tiles();
   if (failures) {
     fprintf(stderr, "%d checks failed\n", failures);
     return 1;

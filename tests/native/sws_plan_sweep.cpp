@@ -5,7 +5,7 @@
 //       -static-libasan -static-libubsan \
 //       tests/native/sws_plan_sweep.cpp spdl_amd/csrc/hj_sws.cpp -o sws_plan_sweep
 // About 45 000 plans: sources and destinations from 1 pixel up, every chroma
-// shift pair, the three filters.  Beside what the sanitizers see, every accepted
+// shift pair, the three filters; and some 250 with a side of 32768 or 65535.  Beside what the sanitizers see, every accepted
 // plan is checked to keep its taps inside the source and its rows normalised;
 // then it is packed and tiled under four placements (trivial, a pad with odd
 // offsets, a crop with negative odd offsets, a pad that holds whole tiles) and
@@ -315,6 +315,32 @@ int main() {
                       !one_plan(f, kSrc[a], hs, vs, gray, f == 40 ? 37 : f, kDst[b], kind, planar))
                     return 1;
                 }
+  // Frames at the format's limit: one side of 32768 or 65535 against 17, to
+  // itself, to 1/63 (the longest filters swscale takes) and to one sample
+  // (refused: the ratio leaves swscale's int).
+  static const int kLong[] = {32768, 65535};
+  const long before = g_refused;
+  for (int kind = 0; kind < 3; kind++)
+    for (int sub = 0; sub < 4; sub++) {  // gray, 4:4:4, 4:2:0, 4:1:1
+      const int hs = sub == 3 ? 2 : sub == 2 ? 1 : 0, vs = sub == 2 ? 1 : 0, gray = sub == 0;
+      for (int planar = 0; planar <= (sub < 3 ? 1 : 0); planar++)
+        for (int L : kLong)
+          for (int S : {17}) {
+            const int dst[] = {L, (L + 62) / 63, 1};
+            for (int d : dst)
+              if (!one_plan(L, S, hs, vs, gray, d, S, kind, planar) ||
+                  !one_plan(S, L, hs, vs, gray, S, d, kind, planar))
+                return 1;
+            // (the last two, L -> 1, were refused)
+            hj::SwsPlan p;
+            if (hj::sws_plan(L, S, hs, vs, gray, 1, S, kind, &p) != 7 /* BAD_GEOMETRY */ ||
+                hj::sws_plan_planar(S, L, hs, vs, gray, S, 1, kind, &p) != 7) {
+              fprintf(stderr, "%d -> 1 is accepted (filter %d, sub %d%d)\n", L, kind, hs, vs);
+              return 1;
+            }
+          }
+    }
+  if (g_refused - before < 3 * 4 * 2 * 2) return 1;
   printf("plans %ld refused %ld (packed %ld, tiles %ld)\n", g_plans, g_refused, g_packed, g_tiles);
   return g_refused > 0 && g_refused < g_plans && g_tiles > g_packed ? 0 : 1;
 }

@@ -13,9 +13,11 @@
 //     bounding rectangle writes, and inside the component's plane;
 //   a view that does not resolve adds nothing; no view at all: zero blocks;
 //   a whole-frame view makes it the whole grid.
+// The same properties on frames with one side of 32768, 65500 and 65535 for
+// rectangles within 16 samples of the far end (sweep_far_end).
 // And for the descriptor slices: the groups' slices follow the n images, in
-// order, without gap or overlap.  Prints "sets N checks M" and exits 0, or 1
-// at the first failure.
+// order, without gap or overlap.  Prints "sets N checks M", then "far-end sets
+// N checks M", and exits 0, or 1 at the first failure.
 #include <stdio.h>
 
 #include <vector>
@@ -118,11 +120,41 @@ bool check_set(const Frame& f, const Grid& g, const View* const* set, int n) {
   return true;
 }
 
+// One candidate resolved and checked: the rectangle inside the frame and on the
+// chroma grid, its MCU rectangle the one its corners fall in
+bool resolve_view(const Format& fmt, const Frame& f, const Grid& g, View& v, bool* refused) {
+  int hsub, vsub;
+  CHECK(chroma_shifts(f, &hsub, &vsub) == hj::kOk, "%s: chroma shifts", fmt.name);
+  const int hs = 1 << hsub, vs = 1 << vsub, mw8 = 8 * g.hmax, mh8 = 8 * g.vmax;
+  const int W = f.width, H = f.height;
+  v.rc = resolve(f, v.in, &v.r);
+  if (v.rc) {
+    CHECK(v.rc == hj::kErrBadGeometry, "resolve: status %d", v.rc);
+    *refused = true;
+    return true;
+  }
+  CHECK(v.r.x >= 0 && v.r.y >= 0 && v.r.w >= 1 && v.r.h >= 1 && v.r.x + v.r.w <= W &&
+            v.r.y + v.r.h <= H && v.r.x % hs == 0 && v.r.y % vs == 0 &&
+            // (the whole frame is taken as it is, odd sizes included)
+            (rect_is_none(v.in) || (v.r.w % hs == 0 && v.r.h % vs == 0)),
+        "%s %dx%d: (%d, %d, %d, %d) resolved to (%d, %d, %d, %d)", fmt.name, W, H, v.in.x, v.in.y,
+        v.in.w, v.in.h, v.r.x, v.r.y, v.r.w, v.r.h);
+  v.m = mcu_rect(g, v.r);
+  // the MCU rectangle is the one the rectangle's corners fall in
+  CHECK(v.m.mx0 * mw8 <= v.r.x && v.r.x < (v.m.mx0 + 1) * mw8 &&
+            (v.m.mx0 + v.m.mw - 1) * mw8 <= v.r.x + v.r.w - 1 &&
+            v.r.x + v.r.w - 1 < (v.m.mx0 + v.m.mw) * mw8 && v.m.my0 * mh8 <= v.r.y &&
+            v.r.y < (v.m.my0 + 1) * mh8 && (v.m.my0 + v.m.mh - 1) * mh8 <= v.r.y + v.r.h - 1 &&
+            v.r.y + v.r.h - 1 < (v.m.my0 + v.m.mh) * mh8,
+        "%s: MCU rectangle of (%d, %d, %d, %d)", fmt.name, v.r.x, v.r.y, v.r.w, v.r.h);
+  return true;
+}
+
 bool sweep_frame(const Format& fmt, const Frame& f) {
   const Grid g = grid_of(f);
   int hsub, vsub;
   CHECK(chroma_shifts(f, &hsub, &vsub) == hj::kOk, "%s: chroma shifts", fmt.name);
-  const int hs = 1 << hsub, vs = 1 << vsub, mw8 = 8 * g.hmax, mh8 = 8 * g.vmax;
+  const int hs = 1 << hsub, mw8 = 8 * g.hmax, mh8 = 8 * g.vmax;
   // axis candidates: (origin, size), on and off the grids, clamped and centred
   const int W = f.width, H = f.height;
   const int xs[][2] = {{0, W}, {1, W / 2 + 1}, {mw8 - 1, 2}, {mw8, mw8}, {W - 1, 1}, {kCenter, hs}};
@@ -138,28 +170,8 @@ bool sweep_frame(const Format& fmt, const Frame& f) {
     }
   cand.push_back({{0, 0, W + hs, 1}, {}, 0, {}});  // wider than the frame: does not resolve
   bool refused = false;
-  for (View& v : cand) {
-    v.rc = resolve(f, v.in, &v.r);
-    if (v.rc) {
-      CHECK(v.rc == hj::kErrBadGeometry, "resolve: status %d", v.rc);
-      refused = true;
-      continue;
-    }
-    CHECK(v.r.x >= 0 && v.r.y >= 0 && v.r.w >= 1 && v.r.h >= 1 && v.r.x + v.r.w <= W &&
-              v.r.y + v.r.h <= H && v.r.x % hs == 0 && v.r.y % vs == 0 &&
-              // (the whole frame is taken as it is, odd sizes included)
-              (rect_is_none(v.in) || (v.r.w % hs == 0 && v.r.h % vs == 0)),
-          "%s %dx%d: (%d, %d, %d, %d) resolved to (%d, %d, %d, %d)", fmt.name, W, H, v.in.x, v.in.y,
-          v.in.w, v.in.h, v.r.x, v.r.y, v.r.w, v.r.h);
-    v.m = mcu_rect(g, v.r);
-    // the MCU rectangle is the one the rectangle's corners fall in
-    CHECK(v.m.mx0 * mw8 <= v.r.x && v.r.x < (v.m.mx0 + 1) * mw8 &&
-              (v.m.mx0 + v.m.mw - 1) * mw8 <= v.r.x + v.r.w - 1 &&
-              v.r.x + v.r.w - 1 < (v.m.mx0 + v.m.mw) * mw8 && v.m.my0 * mh8 <= v.r.y &&
-              v.r.y < (v.m.my0 + 1) * mh8 && (v.m.my0 + v.m.mh - 1) * mh8 <= v.r.y + v.r.h - 1 &&
-              v.r.y + v.r.h - 1 < (v.m.my0 + v.m.mh) * mh8,
-          "%s: MCU rectangle of (%d, %d, %d, %d)", fmt.name, v.r.x, v.r.y, v.r.w, v.r.h);
-  }
+  for (View& v : cand)
+    if (!resolve_view(fmt, f, g, v, &refused)) return false;
   CHECK(refused, "no candidate was refused");
   const View* set[3];
   if (!check_set(f, g, set, 0)) return false;  // an image without views
@@ -176,6 +188,52 @@ bool sweep_frame(const Format& fmt, const Frame& f) {
       }
     }
   }
+  return true;
+}
+
+// Frames at the format's limit: one side of 65535 pixels (and 32768, where a
+// 16-bit sign would first matter), the other 1, 8 or 17.  Rectangles whose
+// origin lies within 16 samples of the far end, of sizes on and off the grids
+// (resolve clamps them into the frame), alone and together with one at the near
+// end and the whole frame: the same properties as above.
+bool sweep_far_end(const Format& fmt, int W, int H) {
+  Frame f{};
+  f.ncomp = fmt.ncomp;
+  for (int c = 0; c < fmt.ncomp; c++) f.h_samp[c] = f.v_samp[c] = 1;
+  f.h_samp[0] = fmt.h0;
+  f.v_samp[0] = fmt.v0;
+  f.width = W;
+  f.height = H;
+  const Grid g = grid_of(f);
+  CHECK((int64_t)g.mcux * g.mcuy * g.bpm < (1 << 24), "%s %dx%d: too many blocks", fmt.name, W, H);
+  const bool wide = W > H;
+  const int L = wide ? W : H, S = wide ? H : W;
+  const int sizes[] = {1, 2, 3, 8, 16, 17, 64};
+  View near{wide ? Rect{0, 0, 64, S} : Rect{0, 0, S, 64}, {}, 0, {}};
+  View whole{{0, 0, 0, 0}, {}, 0, {}};
+  bool refused = false, accepted = false;
+  if (!resolve_view(fmt, f, g, near, &refused) || !resolve_view(fmt, f, g, whole, &refused))
+    return false;
+  for (int back = 1; back <= 16; back++)
+    for (int n : sizes)
+      for (int across : {1, S}) {
+        View v{wide ? Rect{L - back, 0, n, across} : Rect{0, L - back, across, n}, {}, 0, {}};
+        if (!resolve_view(fmt, f, g, v, &refused)) return false;
+        if (!v.rc) {
+          accepted = true;
+          CHECK((wide ? v.r.x + v.r.w : v.r.y + v.r.h) <= L && (wide ? v.r.x : v.r.y) >= L - 16 - n - 8,
+                "%s %dx%d: (%d, %d, %d, %d) moved away from the far end", fmt.name, W, H, v.r.x,
+                v.r.y, v.r.w, v.r.h);
+        }
+        const View* set[3] = {&v, &near, &whole};
+        for (int k = 1; k <= 3; k++)
+          if (!check_set(f, g, set, k)) return false;
+      }
+  // (a short side under the chroma ratio holds no rectangle but the whole frame)
+  int hsub, vsub;
+  CHECK(chroma_shifts(f, &hsub, &vsub) == hj::kOk, "%s: chroma shifts", fmt.name);
+  CHECK(accepted == (S >= 1 << (wide ? vsub : hsub)), "%s %dx%d: far-end rectangles resolved: %d",
+        fmt.name, W, H, (int)accepted);
   return true;
 }
 
@@ -214,5 +272,11 @@ int main() {
           if (!sweep_frame(fmt, frame(fmt, mcux, mcuy, partial & 1, partial & 2))) return 1;
   if (!sweep_slices()) return 1;
   printf("sets %ld checks %ld\n", g_sets, g_checks);
+  g_sets = g_checks = 0;
+  for (const Format& fmt : kFormats)
+    for (int L : {32768, 65500, 65535})
+      for (int S : {1, 8, 17})
+        if (!sweep_far_end(fmt, L, S) || !sweep_far_end(fmt, S, L)) return 1;
+  printf("far-end sets %ld checks %ld\n", g_sets, g_checks);
   return 0;
 }

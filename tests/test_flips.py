@@ -243,6 +243,9 @@ def test_flip_sweep_under_sanitizers(tmp_path):
     m = re.fullmatch(r"tiles: (\d+) boxes, (\d+) pixels", lines[0])
     # 70 x 70 sizes x 3 chunks x 4 bands x 4 flips, the box and its chroma plane
     assert m and int(m.group(1)) == 70 * 70 * 3 * 4 * 4 * 2
+    # sides of 32768 and 65535 x 1 and 17, both ways, 2 chunks x 2 bands x 4 flips, with chroma
+    m = re.fullmatch(r"extreme tiles: (\d+) boxes, (\d+) pixels", lines[2])
+    assert m and int(m.group(1)) == 2 * 2 * 2 * 2 * 2 * 4 * 2
 
 
 def test_sweep_sees_the_library_through_host_headers_alone():

@@ -424,6 +424,9 @@ def test_orient_sweep_under_sanitizers(tmp_path):
     m = re.fullmatch(r"tiles: (\d+) boxes, (\d+) pixels", lines[0])
     # 70 x 70 sizes x 3 chunks x 4 bands x 8 codes
     assert m and int(m.group(1)) == 70 * 70 * 3 * 4 * 8
+    # sides of 32768 and 65535 x 1 and 17, both ways, 2 chunks x 2 bands x 8 codes
+    m = re.fullmatch(r"extreme tiles: (\d+) boxes, (\d+) pixels", lines[2])
+    assert m and int(m.group(1)) == 2 * 2 * 2 * 2 * 2 * 8
 
 
 def test_orient_sweep_sees_the_library_through_host_headers_alone():

@@ -206,6 +206,11 @@ def test_views_arithmetic_sweep_under_sanitizers(tmp_path):
     # 400 frames (5 formats, 20 grids, 4 edge variants), 25 rectangles each:
     # the empty set and C(25, 1) + C(25, 2) + C(25, 3) = 2625 more
     assert sets == 400 * 2626 and checks > 5 * sets
+    # frames with a side of 32768, 65500 and 65535 (5 formats, 3 x 3 sizes, both ways): 16
+    # origins x 7 sizes x 2 extents at the far end, each in sets of 1, 2 and 3
+    far = r.stdout.splitlines()[1].split()
+    assert far[:2] == ["far-end", "sets"] and int(far[2]) == 5 * 18 * 16 * 7 * 2 * 3
+    assert int(far[4]) > 5 * int(far[2])
 
 
 def test_sweep_includes_only_the_two_host_headers():
