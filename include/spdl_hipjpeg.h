@@ -103,8 +103,9 @@ enum spdl_hj_idct { SPDL_HJ_IDCT_SIMPLE = 0, SPDL_HJ_IDCT_ISLOW = 1 };
 enum spdl_hj_csc { SPDL_HJ_CSC_SWSCALE = 0, SPDL_HJ_CSC_JFIF = 1 };
 
 /* Output specification.  resize == 0: full resolution, every image in the
- * batch must have the same size.  Otherwise the FFmpeg filter chain SPDL
- * builds (src/spdl/io/_preprocessing.py:214-234) is applied per image:
+ * batch must have the same size (but see "ragged batches").  Otherwise the
+ * FFmpeg filter chain SPDL builds (src/spdl/io/_preprocessing.py:214-234) is
+ * applied per image:
  *   scale=w=fit_w:h=fit_h[:force_original_aspect_ratio=decrease|increase]
  *   [,pad=w=pad_w:h=pad_h:x=-1:y=-1:color=black][,crop=w=crop_w:h=crop_h]
  * fit_w/fit_h == 0 mean "input size"; pad/crop == 0 mean "absent"; a
@@ -427,6 +428,75 @@ int spdl_hj_get_orientation(const uint8_t* data, size_t size, int32_t* exif);
  * code ^ flip bits. */
 int spdl_hj_orient_code(int32_t exif);
 
+/* ---- ragged batches (additive in ABI 7: two functions, two read-only
+ * parameters; a binding finds them by symbol) ----------------------------------
+ * Every image of one submission its own output size: full-resolution decode
+ * of files as they come, and aspect-preserving resizes ("shorter side to 256",
+ * scale=256:-1), which the "one size" rule leaves to one call per image.
+ *
+ * spdl_hj_ragged_layout is host arithmetic, no context and no device.  It
+ * resolves each image alone -- crops[i] (NULL or all zero: none) by
+ * spdl_hj_crop_rect's rule, the chain by spdl_hj_output_size's, orients[i]
+ * (NULL: 0) by the orientation section's, so ow[i] x oh[i] is the FINAL box --
+ * and packs image i at offsets[i], a multiple of align_bytes, behind image
+ * i - 1; offsets[n] is the size of the buffer.  align_bytes is a multiple of
+ * the element size (1 for u8, 2 for f16 / bf16) and at least that.  An image
+ * whose crop or geometry does not resolve gets its status in status[i], a
+ * 0 x 0 box and no bytes; the call itself fails (INVALID_ARG) only for its own
+ * arguments: a NULL array, an invalid spec, or one this extension refuses.
+ *
+ * spdl_hj_set_ragged gives the NEXT spdl_hj_decode_batch / _device / _staged
+ * call n byte offsets; that call consumes them whether or not it succeeds, and
+ * NULL / 0 clears them (spdl_hj_set_crops' rule; spdl_hj_decode_planes and
+ * spdl_hj_debug_entropy neither use nor clear).  The call then lifts the "one
+ * size" rule and writes image i at byte offsets[i] of out_dev in the layout
+ * of its own final box: [oh][ow][3] for RGB24 / BGR24, [3][oh][ow] for the
+ * planar formats, u8, f16 or bf16.  Nothing else of the buffer is written.
+ * The offsets need not come from spdl_hj_ragged_layout and need not ascend;
+ * two images placed over each other are the caller's business -- the call
+ * checks each image against the buffer, not against its neighbours.
+ *
+ * Accepted: the four RGB / BGR formats, the three dtypes, resize 0 and 1,
+ * source crops, flips and orientation codes (the latter two take the generic
+ * output kernel, as in a plain batch; EXIF-oriented full-resolution batches of
+ * mixed portrait and landscape files fit one submission this way).  An image
+ * whose chain has no geometry, or a size the scaler has no filter for
+ * (SPDL_HJ_ERR_BAD_GEOMETRY; the latter is the plan's to say, so
+ * spdl_hj_ragged_layout still gives it a box), is refused alone, as one whose
+ * crop rounds to nothing is: its bytes stay untouched, its status says so,
+ * the rest of the batch decodes.  Every other per-image failure is what it is
+ * in a plain batch.
+ *
+ * SPDL_HJ_ERR_INVALID_ARG from the consuming call, with nothing written: a
+ * count other than the batch's n; SPDL_HJ_FMT_YUV; csc = JFIF; views on the
+ * same submission; an offset that is negative or no multiple of the element
+ * size; an image whose extent reaches past out_bytes.
+ *
+ * Output kernels.  A plain batch chooses one output kernel for all its images;
+ * a ragged one chooses per image.  An image takes the fused IDCT + unscaled
+ * converter (idct_rgb_kernel, over a flat grid of the eligible images' tiles
+ * alone) when, by itself, it meets what a plain batch must meet as a whole:
+ * u8 output, full resolution without crop, flip or orientation, standard
+ * 4:2:0 with even width and height or 4:2:2 with even width, "output_path" 0.  Every
+ * other image of the same submission goes through idct_kernel and the generic
+ * sws_kernel.  "output_path" 1 and 2 both send every image of a ragged
+ * submission there (the separate unscaled converter has no ragged launch).
+ * The read-only parameters "fused_workgroups" and "generic_workgroups" report
+ * what the last ragged submission launched of each (0 after a plain one).
+ *
+ * Cost (256 images of mixed sizes and samplings at native size to rgb24, one
+ * lane / four lanes): one ragged submission 179 k / 254 k img/s, the same
+ * images as 256 single-image submissions 2.5 k / 7.9 k, the ragged submission
+ * with every image on the generic kernel 166 k / 232 k.  A uniform batch
+ * submitted ragged runs the fused kernel over the flat grid at 0.993 to 0.999
+ * of the plain batch's rate, within run-to-run spread
+ * (tools/ragged_bench.py, profiles/r18/ragged/README.md). */
+int spdl_hj_ragged_layout(const spdl_hj_image_info* infos, int32_t n, const spdl_hj_output* out,
+                          const spdl_hj_rect* crops, const uint8_t* orients, int64_t align_bytes,
+                          int64_t* offsets /* n + 1 */, int32_t* ow, int32_t* oh /* n each */,
+                          int32_t* status /* n */);
+int spdl_hj_set_ragged(spdl_hj_ctx* ctx, const int64_t* offsets, int32_t n);
+
 /* ABI version of the loaded library (== SPDL_HJ_ABI_VERSION). */
 int spdl_hj_abi_version(void);
 
@@ -674,7 +744,11 @@ const char* spdl_hj_stage_name(int32_t i);
  * crop's region-only IDCT shows here; "entropy_workgroups" (with views), the
  * entropy work items of the last submission (one per image, or per piece of
  * a multi-piece image): with "idct_workgroups" it shows that a views
- * submission ran the front end once per image.
+ * submission ran the front end once per image; "fused_workgroups" and
+ * "generic_workgroups" (with ragged batches), the workgroups of the fused
+ * full-resolution kernel and of the generic output kernel in the last ragged
+ * submission, which chooses between them per image (0 and 0 after a plain
+ * submission).
  * Builds with -DHJ_ABLATIONS=1 also take "debug_mask" (timing ablations that
  * skip kernel phases; outputs wrong); release builds reject it. */
 int spdl_hj_set_param(spdl_hj_ctx* ctx, const char* name, int64_t value);

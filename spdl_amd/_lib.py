@@ -60,6 +60,8 @@ EXPORTED = (
     "spdl_hj_set_orients",
     "spdl_hj_get_orientation",
     "spdl_hj_orient_code",
+    "spdl_hj_ragged_layout",
+    "spdl_hj_set_ragged",
 )
 
 
@@ -450,6 +452,10 @@ def lib() -> ctypes.CDLL:
             L.spdl_hj_set_orients.argtypes = [vp, vp, i32]
             L.spdl_hj_get_orientation.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(i32)]
             L.spdl_hj_orient_code.argtypes = [i32]
+        if hasattr(L, "spdl_hj_set_ragged"):  # (likewise)
+            L.spdl_hj_ragged_layout.argtypes = [vp, i32, ctypes.POINTER(OutputSpec), vp, vp, i64,
+                                                vp, vp, vp, vp]
+            L.spdl_hj_set_ragged.argtypes = [vp, vp, i32]
         ver = L.spdl_hj_abi_version()
         # (an explicitly chosen older build, ABI >= 5, loads for A/B runs)
         if ver != ABI_VERSION and not (os.environ.get("SPDL_AMD_LIB") and 5 <= ver < ABI_VERSION):
@@ -499,6 +505,37 @@ def output_size(width: int, height: int, out: Output) -> tuple[int, int]:
     if rc:
         raise RuntimeError(f"invalid output geometry for {width}x{height} ({rc})")
     return ow.value, oh.value
+
+
+def ragged_layout(infos, out: Output, crops=None, orients=None,
+                  align: int = 256) -> tuple[list[int], list[tuple[int, int]], list[int]]:
+    """``(offsets, sizes, statuses)`` of a ragged batch (spdl_hj_ragged_layout;
+    host only): every image's final ``(ow, oh)`` resolved alone -- its source
+    crop, the chain of ``out``, its orientation -- and packed at multiples of
+    ``align`` bytes.  ``offsets`` has ``n + 1`` entries, the last the buffer's
+    size.  An image whose crop or geometry does not resolve has its status, a
+    ``(0, 0)`` size and no bytes.  ``infos``: a sequence of ImageInfo."""
+    n = len(infos)
+    inf = infos if isinstance(infos, ctypes.Array) else (ImageInfo * max(n, 1))(*infos)
+    rects = None
+    if crops is not None:
+        if len(crops) != n:
+            raise ValueError(f"{len(crops)} crops for a batch of {n} images")
+        rects = (Rect * max(n, 1))(*[_rect(r) for r in crops])
+    codes = None
+    if orients is not None:
+        if len(orients) != n:
+            raise ValueError(f"{len(orients)} orients for a batch of {n} images")
+        codes = (ctypes.c_uint8 * max(n, 1))(*[_orient(o) for o in orients])
+    offs = (ctypes.c_int64 * (n + 1))()
+    ow, oh, st = ((ctypes.c_int32 * max(n, 1))() for _ in range(3))
+    spec = out.to_c()
+    rc = lib().spdl_hj_ragged_layout(inf, n, ctypes.byref(spec), rects, codes, int(align), offs,
+                                     ow, oh, st)
+    if rc:
+        raise ValueError(f"no ragged layout for this output (pix_fmt {out.pix_fmt!r}, csc "
+                         f"{out.csc!r}, align {align}): status {rc}")
+    return list(offs), [(ow[i], oh[i]) for i in range(n)], list(st)[:n]
 
 
 PLAN_MODES = {"yuv": 0, "gray": 1, "gbr": 2}
@@ -768,6 +805,21 @@ class Decoder:
             raise ValueError(f"{len(orients)} orients for a batch of {n} images")
         self.set_orients(orients)
 
+    def set_ragged(self, offsets) -> None:
+        """The byte offsets of the next batch submission's images in its
+        output (spdl_hj_set_ragged): that submission is a ragged one, every
+        image in the layout of its own size.  ``None`` or an empty sequence
+        clears them.  A prebuilt ``(c_int64 * n)`` array is passed as it is (no
+        marshalling per call)."""
+        if isinstance(offsets, ctypes.Array):
+            if lib().spdl_hj_set_ragged(self._h, offsets, len(offsets)):
+                raise ValueError("invalid ragged offsets")
+            return
+        offsets = [int(o) for o in offsets] if offsets is not None else []
+        arr = (ctypes.c_int64 * max(len(offsets), 1))(*offsets)
+        if lib().spdl_hj_set_ragged(self._h, arr if offsets else None, len(offsets)):
+            raise ValueError("invalid ragged offsets")
+
     def _crops(self, out: Output, crops, n: int) -> None:
         """Hand the submission's rectangles to the context: ``crops`` per
         image, or ``out.src_crop`` for every image."""
@@ -782,7 +834,7 @@ class Decoder:
 
     def decode_batch(self, datas, out: Output, out_ptr: int, out_bytes: int, stream=None,
                      sync: bool = True, check: bool = True, crops=None, views=None,
-                     flips=None, orients=None) -> list[int]:
+                     flips=None, orients=None, ragged=None) -> list[int]:
         """Per-image statuses.  A failed image raises RuntimeError unless
         ``check`` is False (synchronous calls), which returns the statuses.
         ``crops``: a source crop ``(x, y, w, h)`` or ``None`` per image.
@@ -793,7 +845,10 @@ class Decoder:
         raise either.  ``flips``: an output flip (``0..3``, ``"h"``, ``"v"``,
         ``"hv"`` or ``None``) per image; with views, each view carries its own.
         ``orients``: an orientation (``0..7`` or a spelling of :func:`_orient`)
-        per image instead of ``flips`` (spdl_hj_set_orients)."""
+        per image instead of ``flips`` (spdl_hj_set_orients).  ``ragged``:
+        one byte offset per image (the first ``n`` of :func:`ragged_layout`'s)
+        -- every image its own size, written at its offset of ``out_ptr``
+        (include/spdl_hipjpeg.h "ragged batches")."""
         n = len(datas)
         if n == 0:
             raise RuntimeError("Failed to decode an image. (the batch is empty)")
@@ -816,10 +871,10 @@ class Decoder:
                 _stream_handle(stream), int(bool(sync)), status, err, 1024,
             )
         return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                                    check, status, call, orients))
+                                    check, status, call, orients, ragged))
 
     def _submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync, check, status,
-                call, orients=None):
+                call, orients=None, ragged=None):
         """What the three batch submissions share: the views, crops and flips
         (or orientations) go to the context, ``call(err)`` -- the method's own marshalling and
         its native call -- returns the library's code, and a failure raises
@@ -835,6 +890,8 @@ class Decoder:
             Decoder._orients(self, out, orients, n, views, flips)
         elif _has_flips(out, flips, views):
             self._flips(out, flips, n, views)
+        if ragged is not None:  # (its count is the consuming call's to check)
+            Decoder.set_ragged(self, ragged)
         err = ctypes.create_string_buffer(1024)
         rc = call(err)
         if rc and not (not check and sync and (any(status) or _refused(views, rc))):
@@ -844,7 +901,7 @@ class Decoder:
     def decode_batch_device(self, dev_ptr: int, dev_bytes: int, offsets, sizes, infos,
                             out: Output, out_ptr: int, out_bytes: int, stream=None,
                             sync: bool = True, crops=None, check: bool = True,
-                            views=None, flips=None, orients=None) -> list[int]:
+                            views=None, flips=None, orients=None, ragged=None) -> list[int]:
         """``offsets``/``sizes``: sequences or int64 numpy arrays; ``infos``: a
         sequence of ImageInfo or a prebuilt ``(ImageInfo * n)`` array (pass the
         same objects again to skip re-marshalling on every call)."""
@@ -864,7 +921,7 @@ class Decoder:
                 status.ctypes.data, err, 1024,
             )
         return Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                               check, status, call, orients).tolist()
+                               check, status, call, orients, ragged).tolist()
 
     def _spec(self, out: Output) -> OutputSpec:
         cache = self.__dict__.setdefault("_spec_cache", {})
@@ -923,7 +980,8 @@ class Decoder:
 
     def decode_staged(self, ticket: int, nbytes: int, offsets, sizes, out: Output, out_ptr: int,
                       out_bytes: int, stream=None, sync: bool = True, crops=None,
-                      check: bool = True, views=None, flips=None, orients=None) -> list[int]:
+                      check: bool = True, views=None, flips=None, orients=None,
+                      ragged=None) -> list[int]:
         n = len(offsets)
         status = (ctypes.c_int32 * max(n, 1))()
 
@@ -935,7 +993,7 @@ class Decoder:
                 self._h, int(ticket), int(nbytes), offs, szs, n, ctypes.byref(spec), out_ptr,
                 out_bytes, _stream_handle(stream), int(bool(sync)), status, err, 1024)
         return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                                    check, status, call, orients))[:n]
+                                    check, status, call, orients, ragged))[:n]
 
     def debug_entropy(self, data, nblocks: int):
         """Coefficients / destuffed bytes / diagnostics of one image (tests)."""

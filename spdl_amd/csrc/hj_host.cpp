@@ -149,9 +149,11 @@ struct Slot {
     size_t len = 0;
     spdl_hj_output out{};
     uint8_t* out_dev = nullptr;
-    size_t img_bytes = 0;  // output bytes per image
     struct Item {  // one multi-piece image of the batch
       int idx;
+      // its place in the batch's output: idx x the one size of a plain batch,
+      // its own offset and extent in a ragged one (bytes)
+      size_t out_off, out_bytes;
       int64_t off, size;
       spdl_hj_image_info info;
       spdl_hj_rect rect;  // its source crop (has_rects)
@@ -275,8 +277,13 @@ struct spdl_hj_ctx {
   std::vector<uint8_t> orients;
   int64_t idct_workgroups = 0;  // IDCT workgroups the last submission launched
   int64_t entropy_workgroups = 0;  // ... and its entropy work items (images, or their pieces)
+  // ... the fused-eligible images' idct_rgb_kernel workgroups, and those of
+  // the generic output kernel (sws_kernel)
+  int64_t fused_workgroups = 0, generic_workgroups = 0;
   // spdl_hj_set_views: the views of the next batch submission
   HeldViews views;
+  // spdl_hj_set_ragged: the images' byte offsets in the next batch submission's output
+  std::vector<int64_t> ragged;
 };
 
 namespace {
@@ -482,6 +489,7 @@ struct Submission {
   const spdl_hj_rect* crops = nullptr;  // the batch's source crops, for the retry record
   const uint8_t* flips = nullptr;       // ... and its output flips (one per image)
   bool oriented = false;                // (they are orientation codes)
+  const int64_t* ragged = nullptr;      // a ragged submission's byte offsets (the planner checked them)
 };
 
 // An output chain's share of the output kernels' parameters: the batch's
@@ -507,7 +515,8 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   const hipStream_t st = sub.st;
   const size_t esz = out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
   const bool by_views = !L.groups.empty();  // (build_layout checked every group's buffer)
-  if (!sub.planes_only && !by_views && (size_t)L.out_elems_per_image * n * esz > sub.out_bytes) {
+  if (!sub.planes_only && !by_views && !L.ragged &&
+      (size_t)L.out_elems_per_image * n * esz > sub.out_bytes) {
     set_err(err, errlen, "output buffer too small: need %lld bytes, have %zu",
             (long long)(L.out_elems_per_image * n * esz), sub.out_bytes);
     return SPDL_HJ_ERR_INVALID_ARG;
@@ -621,10 +630,16 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   const bool fast_rgb = swscale && !yuv && L.all_special && out->dtype == SPDL_HJ_DTYPE_U8 &&
                         ctx->output_path != 1;
   const bool fused = fast_rgb && L.fuse_ok && L.fused_tiles > 0 && ctx->output_path != 2;
-  ctx->idct_workgroups = 0;
+  // A ragged submission chose per image (the planner: Layout::ragged): the
+  // fused kernel over the first part of the flat sws grid, the generic kernel
+  // over the rest, idct_kernel for the latter's images alone.  (The fused
+  // grid is flat for a uniform batch as well: measured against the (tile,
+  // image) grid there, it costs nothing -- profiles/r18/ragged)
+  const int ragged_fused = L.ragged ? (int)L.fused_wgs : 0;
+  ctx->idct_workgroups = ctx->fused_workgroups = ctx->generic_workgroups = 0;
   ctx->entropy_workgroups = B.nwork;
   // (a views submission whose views were all refused has no block to transform)
-  if (!(abl & kAblNoIdct) && !fused && L.max_blocks > 0) {
+  if (!(abl & kAblNoIdct) && (L.ragged || !fused) && L.max_blocks > 0) {
     HJ_HIP(launch_idct(B, idct_kind, idct_flat, (int)L.idct_wgs, L.max_blocks,
                        (ctx->xcd_order >> 1) & 1, st));
     ctx->idct_workgroups =
@@ -661,6 +676,15 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
                           first ? hs_wgs : 0, nullptr, st, G.sws_wg0));
         first = false;
       }
+    } else if (L.ragged) {
+      // (each image has one writer of its status: tile 0 of its own kernel)
+      if (ragged_fused)
+        HJ_HIP(launch_idct_rgb_flat(B, sub.out_dev, bp, idct_kind, ragged_fused, hstat, st));
+      if (sws_wgs > ragged_fused)
+        HJ_HIP(launch_sws(B, sub.out_dev, bp, true, sws_wgs - ragged_fused, 1, 1, L.sws_lds, hs_wgs,
+                          hstat, st, ragged_fused));
+      ctx->fused_workgroups = ragged_fused;
+      ctx->generic_workgroups = sws_wgs - ragged_fused;
     } else if (yuv)
       HJ_HIP(launch_yuv_planes(B, sub.out_dev, sws_wgs, L.sws_lds, hs_wgs, hstat, st));
     else if (fused)
@@ -687,16 +711,20 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
     R.has_rects = sub.crops != nullptr;
     R.has_flips = sub.flips != nullptr;
     R.oriented = sub.oriented;
-    for (const auto& m : L.multi)
-      R.items.push_back({m.first, L.desc[m.first].in_off, L.desc[m.first].in_size, m.second,
+    const size_t img_bytes = (size_t)L.out_elems_per_image * esz;
+    for (const auto& m : L.multi) {
+      const ImageDesc& d = L.desc[m.first];
+      R.items.push_back({m.first, sub.ragged ? (size_t)sub.ragged[m.first] : m.first * img_bytes,
+                         sub.ragged ? (size_t)d.ow * d.oh * 3 * esz : img_bytes,
+                         d.in_off, d.in_size, m.second,
                          sub.crops ? sub.crops[m.first] : spdl_hj_rect{},
                          sub.flips ? sub.flips[m.first] : (uint8_t)0});
+    }
     R.ticket = slot.ticket;
     R.bytes = sub.d_bytes;
     R.len = sub.bytes_len;
     R.out = *out;
     R.out_dev = static_cast<uint8_t*>(sub.out_dev);
-    R.img_bytes = (size_t)L.out_elems_per_image * esz;
   }
   slot.pending = true;
   slot.profiled = ctx->profiling;
@@ -770,12 +798,15 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
   ctx->handoff_retries++;
   const int64_t idct_wgs = ctx->idct_workgroups;  // (the batch's, not this re-decode's)
   const int64_t ent_wgs = ctx->entropy_workgroups;
+  const int64_t fused_wgs = ctx->fused_workgroups, generic_wgs = ctx->generic_workgroups;
   rc = run_pipeline(ctx, *s, L,
-                    {r.bytes, r.len, 1, &r.out, r.out_dev + (size_t)item.idx * r.img_bytes,
-                     r.img_bytes, xs, 1, &st1},
+                    {r.bytes, r.len, 1, &r.out, r.out_dev + item.out_off, item.out_bytes, xs, 1,
+                     &st1},
                     err, errlen);
   ctx->idct_workgroups = idct_wgs;
   ctx->entropy_workgroups = ent_wgs;
+  ctx->fused_workgroups = fused_wgs;
+  ctx->generic_workgroups = generic_wgs;
   ctx->last_ticket = last;
   return rc ? rc : st1;
 }
@@ -853,6 +884,8 @@ struct Held {
   std::vector<spdl_hj_rect> rects;
   HeldViews views;
   std::vector<uint8_t> flipv, orientv;
+  std::vector<int64_t> raggedv;
+  const int64_t* ragged = nullptr;      // null: a plain submission
   const spdl_hj_rect* crops = nullptr;  // null: none
   const HeldViews* hv = nullptr;
   // (their count, values and chain are the planner's to check: build_layout)
@@ -876,8 +909,11 @@ struct Held {
       orients = orientv.data();
       norients = (int64_t)orientv.size();
     }
+    raggedv.swap(ctx->ragged);
+    ctx->ragged.clear();
     crc = take_crops(ctx, n, out, &rects, &crops, err, errlen);
     vrc = take_views(ctx, n, out, out_dev, out_bytes, !rects.empty(), &views, &hv, err, errlen);
+    if (!raggedv.empty()) ragged = raggedv.data();  // (check() holds its count against n)
   }
   // The submission's first error: the views', then the call's own arguments
   // (args_ok: the entry point's pointers and sizes), then the crops'
@@ -888,7 +924,13 @@ struct Held {
       set_err(err, errlen, n <= 0 ? "the batch is empty" : "invalid argument");
       return SPDL_HJ_ERR_INVALID_ARG;
     }
-    return crc;  // (its text is still in err)
+    if (crc) return crc;  // (its text is still in err)
+    if (!raggedv.empty() && (int64_t)raggedv.size() != n) {
+      set_err(err, errlen, "spdl_hj_set_ragged gave %zu offsets for a batch of %d images",
+              raggedv.size(), n);
+      return SPDL_HJ_ERR_INVALID_ARG;
+    }
+    return SPDL_HJ_OK;
   }
 };
 
@@ -954,7 +996,7 @@ int submit(spdl_hj_ctx* ctx, const Held& held, const Batch& b, SlotRelease& slot
   // (views: one entropy workgroup per image, so no hand-off can give up)
   int rc = plan_batch({b.offsets, b.sizes, infos, b.n, b.out, held.hv ? 0 : ctx->piece_bytes,
                        &ctx->plans, held.crops, held.hv, held.flips, held.nflips, held.orients,
-                       held.norients},
+                       held.norients, held.ragged, (int64_t)b.out_bytes, ctx->output_path},
                       L, b.status, err, errlen);
   if (rc) return rc;
   // the probes (the caller's own with device bytes, ABI 5) say which files
@@ -973,7 +1015,7 @@ int submit(spdl_hj_ctx* ctx, const Held& held, const Batch& b, SlotRelease& slot
                       {bytes, b.bytes_len, b.n, b.out, b.out_dev, b.out_bytes, xs, b.sync, b.status,
                        false, held.crops,
                        held.hv ? nullptr : held.orients ? held.orients : held.flips,
-                       held.orients != nullptr},
+                       held.orients != nullptr, held.ragged},
                       err, errlen);
 }
 
@@ -1064,6 +1106,19 @@ int spdl_hj_set_crops(spdl_hj_ctx* ctx, const spdl_hj_rect* rects, int32_t n) {
   if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
   ctx->crops.clear();
   if (rects && n > 0) ctx->crops.assign(rects, rects + n);
+  return SPDL_HJ_OK;
+}
+
+int spdl_hj_ragged_layout(const spdl_hj_image_info* infos, int32_t n, const spdl_hj_output* out,
+                          const spdl_hj_rect* crops, const uint8_t* orients, int64_t align_bytes,
+                          int64_t* offsets, int32_t* ow, int32_t* oh, int32_t* status) {
+  return ragged_layout(infos, n, out, crops, orients, align_bytes, offsets, ow, oh, status);
+}
+
+int spdl_hj_set_ragged(spdl_hj_ctx* ctx, const int64_t* offsets, int32_t n) {
+  if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
+  ctx->ragged.clear();
+  if (offsets && n > 0) ctx->ragged.assign(offsets, offsets + n);
   return SPDL_HJ_OK;
 }
 
@@ -1692,6 +1747,8 @@ int spdl_hj_get_param(spdl_hj_ctx* ctx, const char* name, int64_t* value) {
       {"xcd_order", ctx->xcd_order},
       {"handoff_retries", ctx->handoff_retries},
       {"idct_workgroups", ctx->idct_workgroups},
+      {"fused_workgroups", ctx->fused_workgroups},
+      {"generic_workgroups", ctx->generic_workgroups},
       {"entropy_workgroups", ctx->entropy_workgroups},
   };
   for (const auto& t : tab)

@@ -6075,26 +6075,48 @@ __global__ void __launch_bounds__(256) rgb_unscaled_kernel(const uint8_t* __rest
 // (rgbu_group) -- the planes never go through HBM.  Standard 4:2:0 / 4:2:2
 // MCUs only (Y 2x2 or 2x1 blocks, then U, V 1x1: bpm 6 or 4); the host checks
 // the sampling (Layout::fuse_ok).  u8 output.
-template <int IDCT>
+//
+// Grid: (tile, image) for a batch whose images all take this path and have
+// one size.  With the trailing sws_map argument (Map: one pointer) it is the
+// flat grid over the fused-eligible images of a ragged submission
+// (spdl_hj_set_ragged): workgroup g is tile g - sws_wg0 of image sws_map[g],
+// the map's first part (Layout::fused_wgs entries; hj_layout.h) -- no empty
+// workgroup, whatever the images' sizes.  The argument is a pack so that the
+// instantiation without it is the kernel as it was, signature and code.  A
+// tile shares nothing with its neighbours (its coefficients in, its rows
+// out), so the order the flat grid's workgroups take over the XCDs is left as
+// the dispatcher has it.
+template <class T, class... R>
+__device__ __forceinline__ T first_arg(T a, R...) {
+  return a;
+}
+template <int IDCT, class... Map>
 __global__ void __launch_bounds__(kFusedThreads) idct_rgb_kernel(const uint32_t* __restrict__ ents,
                                                        const uint2* __restrict__ bdesc,
                                                        const ImageDesc* __restrict__ desc,
                                                        const ImageInfo* __restrict__ infos,
                                                        uint8_t* __restrict__ out,
                                                        const BatchParams p,
-                                                       int32_t* __restrict__ host_status) {
+                                                       int32_t* __restrict__ host_status,
+                                                       const Map... sws_map) {
   __shared__ __attribute__((aligned(16))) uint32_t sblk[kBlkWords + 1][kFusedThreads];
   __shared__ uint32_t sq[kMaxComp][64];
-  const int img = blockIdx.y, tid = threadIdx.x;
+  constexpr bool flat = sizeof...(Map) != 0;
+  int img = blockIdx.y, bx = blockIdx.x;
+  const int tid = threadIdx.x;
+  if constexpr (flat) {
+    img = (int)first_arg(sws_map...)[blockIdx.x];
+    bx -= desc[img].sws_wg0;
+  }
   const ImageInfo& in = infos[img];
-  if (host_status && blockIdx.x == 0 && tid == 0) host_status[img] = in.status;
+  if (host_status && bx == 0 && tid == 0) host_status[img] = in.status;
   if (in.status != kOk) return;
   const ImageDesc& dd = desc[img];
   const int bpm = in.bpm;   // 6 or 4
   const int tw = kFusedThreads / bpm;  // MCUs per tile
   const int tiles_x = (in.mcux + tw - 1) / tw;
-  if ((int)blockIdx.x >= tiles_x * in.mcuy) return;
-  const int my = (int)blockIdx.x / tiles_x, mx0 = ((int)blockIdx.x - my * tiles_x) * tw;
+  if (bx >= tiles_x * in.mcuy) return;
+  const int my = bx / tiles_x, mx0 = (bx - my * tiles_x) * tw;
   const int nm = min(tw, in.mcux - mx0);
   const int hy = 8 * in.comp_v[0];                    // luma rows of the MCU row: 16 or 8
   const int ys = tw * 16, cs = tw * 8;                 // tile row strides (bytes)
@@ -6327,6 +6349,23 @@ hipError_t launch_idct_rgb(const BatchBuffers& b, void* out, const BatchParams& 
                            int tiles, int32_t* host_status, hipStream_t st) {
   HJ_IDCT_KIND(idct_rgb_kernel, idct, dim3(tiles, b.n), dim3(kFusedThreads), 0, st, b.ents, b.bdesc,
                b.desc, b.infos, static_cast<uint8_t*>(out), p, host_status);
+  return hipGetLastError();
+}
+hipError_t launch_idct_rgb_flat(const BatchBuffers& b, void* out, const BatchParams& p, int idct,
+                                int fused_wgs, int32_t* host_status, hipStream_t st) {
+  const uint32_t* map = b.sws_map;
+  const dim3 grid(fused_wgs), wg(kFusedThreads);
+  uint8_t* o = static_cast<uint8_t*>(out);
+  // (HJ_IDCT_KIND takes a kernel with one template argument)
+  if (idct == 2)
+    hipLaunchKernelGGL((idct_rgb_kernel<2, const uint32_t*>), grid, wg, 0, st, b.ents, b.bdesc,
+                       b.desc, b.infos, o, p, host_status, map);
+  else if (idct == 1)
+    hipLaunchKernelGGL((idct_rgb_kernel<1, const uint32_t*>), grid, wg, 0, st, b.ents, b.bdesc,
+                       b.desc, b.infos, o, p, host_status, map);
+  else
+    hipLaunchKernelGGL((idct_rgb_kernel<0, const uint32_t*>), grid, wg, 0, st, b.ents, b.bdesc,
+                       b.desc, b.infos, o, p, host_status, map);
   return hipGetLastError();
 }
 #undef HJ_IDCT_KIND

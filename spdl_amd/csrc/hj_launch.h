@@ -63,6 +63,10 @@ hipError_t launch_rgb_unscaled(const BatchBuffers& b, void* out, const BatchPara
                                int64_t max_px, int32_t* host_status, hipStream_t st);
 hipError_t launch_idct_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int idct,
                            int tiles, int32_t* host_status, hipStream_t st);
+// idct_rgb_kernel over its flat grid: the fused-eligible images of a ragged submission, the
+// first fused_wgs workgroups of sws_map (Layout::fused_wgs)
+hipError_t launch_idct_rgb_flat(const BatchBuffers& b, void* out, const BatchParams& p, int idct,
+                                int fused_wgs, int32_t* host_status, hipStream_t st);
 // hscale_kernel first when hs_wgs > 0; yuv_planes_kernel's grid is always flat.
 // wg0 (flat grids): the launch's first workgroup in sws_map -- a views
 // submission launches sws_kernel once per group over that group's tiles.

@@ -179,6 +179,8 @@ struct Placement {
 // the chain cannot take -- BAD_GEOMETRY from geometry(), or a scale filter too
 // long -- is refused alone as well; the same two fail an image's call, as
 // does everything else.
+// (An image of a ragged submission has a box of its own, so it is refused
+// alone where a view is.)
 bool refused_alone(bool view, const Placement& pl) {
   return pl.at == kAtPlanar ||
          (view && pl.rc == SPDL_HJ_ERR_BAD_GEOMETRY && (pl.at == kAtGeometry || pl.at == kAtFilter));
@@ -191,6 +193,7 @@ struct Planner {
   TablePool pool;
   BoxSize size;           // the images' output size (L.ow x L.oh)
   bool have_fmt = false;  // the planar output's frame format is set (L.yuv_*)
+  std::vector<uint8_t> fused_image;  // a ragged submission's fused-eligible images
 
   // The submission's orientation codes (orients, else flips) and descriptor
   // k's: image k of a plain submission, or view k - n of a views submission
@@ -250,6 +253,13 @@ struct Planner {
     }
   }
 
+  // d's workgroups in the flat IDCT grid, in image order (d.idct_blocks is set)
+  void idct_share(ImageDesc& d) {
+    if (d.idct_blocks > L.max_blocks) L.max_blocks = d.idct_blocks;
+    d.idct_wg0 = (int32_t)L.idct_wgs;
+    L.idct_wgs += (d.idct_blocks + kIdctThreads - 1) / kIdctThreads;
+  }
+
   // Image i's share of what the front end and the IDCT work on: coefficient
   // lists, planes, segments, destuff chunks, entropy pieces and records, and
   // its workgroups in the flat destuff and IDCT grids (d.idct_blocks is set)
@@ -262,7 +272,6 @@ struct Planner {
     d.nblocks = (int)fb.nblocks;
     d.coef_off = L.total_blocks;
     L.total_blocks += fb.nblocks;
-    if (d.idct_blocks > L.max_blocks) L.max_blocks = d.idct_blocks;
     for (int c = 0; c < p.ncomp; c++) {
       d.plane_stride[c] = fb.bw[c] * 8;
       d.plane_off[c] = L.total_planes;
@@ -276,8 +285,9 @@ struct Planner {
     L.total_ds += d.ds_cap;
     d.ds_wg0 = (int32_t)L.ds_wgs;
     L.ds_wgs += d.ds_cap;
-    d.idct_wg0 = (int32_t)L.idct_wgs;
-    L.idct_wgs += (d.idct_blocks + kIdctThreads - 1) / kIdctThreads;
+    // (a ragged submission decides idct_blocks with each image's output path:
+    // its IDCT workgroups are counted in finish_ragged)
+    if (!rq.ragged) idct_share(d);
     if (d.ds_cap > L.max_chunks) L.max_chunks = d.ds_cap;
     // size-adaptive entropy decode: a file larger than piece_bytes is
     // decoded by ceil(size / piece_bytes) workgroups (progressive and
@@ -330,15 +340,18 @@ struct Planner {
     const bool t = code & 4;
     const spdl_hj_output out = t ? swapped_chain(out0) : out0;
     Geom g;
-    int rc = geometry(w, h, &out, &g);
+    int fw, fh;
+    int rc = final_box(w, h, out0, code, &g, &fw, &fh);
     if (rc) return {rc, kAtGeometry, nullptr};
     d.dx = g.dx;
     d.dy = g.dy;
     d.ow = g.ow;
     d.oh = g.oh;
-    const int fw = t ? g.oh : g.ow, fh = t ? g.ow : g.oh;
-    if (!box.set) box = {true, fw, fh};
-    else if (fw != box.ow || fh != box.oh) return {SPDL_HJ_ERR_INVALID_ARG, kAtSize, nullptr};
+    // (a ragged submission's images each have their box: `box` stays unset)
+    if (!rq.ragged) {
+      if (!box.set) box = {true, fw, fh};
+      else if (fw != box.ow || fh != box.oh) return {SPDL_HJ_ERR_INVALID_ARG, kAtSize, nullptr};
+    }
     if (!rq.plans || out.csc == SPDL_HJ_CSC_JFIF) return {SPDL_HJ_OK, kPlaced, nullptr};
     int hs, vs, mode;
     rc = views::chroma_shifts(f, &hs, &vs);
@@ -462,8 +475,7 @@ struct Planner {
     if (rq.views) {
       if (int rc = views_region(i, d, f, fb.grid)) return rc;
     } else if (has_rect) {
-      const spdl_hj_rect& in = rq.crops[i];
-      crop_rc = views::resolve(f, views::Rect{in.x, in.y, in.w, in.h}, &src);
+      crop_rc = source_frame(p, &rq.crops[i], &src);
       if (crop_rc && crop_rc != SPDL_HJ_ERR_BAD_GEOMETRY) return fail(i, crop_rc, nullptr);
       if (crop_rc) src = whole;
       else set_region(d, fb.grid, views::mcu_rect(fb.grid, src));
@@ -478,7 +490,8 @@ struct Planner {
     }
     const Placement pl = place_output(d, src.w, src.h, f, p.color, out, size, code_of(i));
     if (pl.at != kAtGeometry) L.max_px = std::max(L.max_px, (int64_t)d.ow * d.oh);
-    if (pl.rc && refused_alone(false, pl)) {
+    if (pl.rc && refused_alone(rq.ragged != nullptr, pl)) {
+      if (pl.at == kAtGeometry) d.dx = d.dy = d.ow = d.oh = 0;  // (placed nowhere)
       refuse(d, pl.rc);
       return SPDL_HJ_OK;
     }
@@ -494,12 +507,23 @@ struct Planner {
     if (!pl.plan) return SPDL_HJ_OK;
     L.all_special = L.all_special && pl.plan->special;
     // idct_rgb_kernel's MCU shapes: Y 2x2 or 2x1, U and V 1x1
-    if (p.ncomp == 3 && p.h_samp[0] == 2 && (p.v_samp[0] == 1 || p.v_samp[0] == 2) &&
-        p.h_samp[1] == 1 && p.v_samp[1] == 1 && p.h_samp[2] == 1 && p.v_samp[2] == 1) {
-      const int tw = kFusedThreads / fb.grid.bpm;
-      L.fused_tiles = std::max(L.fused_tiles, (fb.grid.mcux + tw - 1) / tw * fb.grid.mcuy);
-    } else {
-      L.fuse_ok = false;
+    const bool fusable = p.ncomp == 3 && p.h_samp[0] == 2 && (p.v_samp[0] == 1 || p.v_samp[0] == 2) &&
+                         p.h_samp[1] == 1 && p.v_samp[1] == 1 && p.h_samp[2] == 1 && p.v_samp[2] == 1;
+    const int tw = kFusedThreads / fb.grid.bpm;
+    const int tiles_x = (fb.grid.mcux + tw - 1) / tw;
+    if (fusable) L.fused_tiles = std::max(L.fused_tiles, tiles_x * fb.grid.mcuy);
+    else L.fuse_ok = false;
+    // A ragged submission chooses per image what a plain one chooses per batch
+    // (hj_host.cpp run_pipeline): a fused-eligible image leaves idct_kernel and
+    // sws_kernel nothing, its idct_rgb_kernel tiles stand in the sws fields
+    // (finish_ragged numbers them)
+    if (rq.ragged && fusable && pl.plan->special && !pl.plan->d.pre &&
+        out.dtype == SPDL_HJ_DTYPE_U8 && !has_rect && !code_of(i) && rq.output_path == 0) {
+      d.idct_blocks = 0;
+      d.sws_bands = fb.grid.mcuy;
+      d.sws_chunks = tiles_x;
+      fused_image[i] = 1;
+      return SPDL_HJ_OK;
     }
     L.sws_bands = std::max(L.sws_bands, pl.plan->bands);
     L.sws_chunks = std::max(L.sws_chunks, pl.plan->chunks);
@@ -690,6 +714,61 @@ struct Planner {
     L.all_special = false;
   }
 
+  // A ragged request against what the extension takes (spdl_hipjpeg.h "ragged
+  // batches"); nothing has been planned or written yet
+  int check_ragged() {
+    if (!rq.ragged) return SPDL_HJ_OK;
+    const char* what = nullptr;
+    if (rq.views) what = "views and spdl_hj_set_ragged on one submission";
+    else if (!rq.plans) what = "spdl_hj_set_ragged needs an output stage";
+    else if (rq.out->pix_fmt == SPDL_HJ_FMT_YUV) what = "no ragged planar YUV output";
+    else if (rq.out->csc != SPDL_HJ_CSC_SWSCALE) what = "a ragged submission needs csc = swscale";
+    const int64_t esz = rq.out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
+    for (int i = 0; i < rq.n && !what; i++)
+      if (rq.ragged[i] < 0 || rq.ragged[i] % esz)
+        what = "spdl_hj_set_ragged: an offset is negative or no multiple of the element size";
+    if (!what) return SPDL_HJ_OK;
+    res.rc = SPDL_HJ_ERR_INVALID_ARG;
+    snprintf(res.err, sizeof(res.err), "%s", what);
+    return res.rc;
+  }
+
+  // A ragged submission once every descriptor stands: each image at its own
+  // offset, inside the buffer; the IDCT grid of the images idct_kernel
+  // transforms; the flat sws grid with the fused-eligible images' tiles
+  // first, [0, L.fused_wgs), then every other image's
+  int finish_ragged() {
+    const int n = rq.n;
+    const int64_t esz = rq.out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
+    for (int i = 0; i < n; i++) {
+      ImageDesc& d = L.desc[i];
+      const int64_t extent = (int64_t)d.ow * d.oh * 3 * esz;  // (a refused image: none)
+      if (rq.ragged[i] > rq.out_bytes || extent > rq.out_bytes - rq.ragged[i]) {
+        res.rc = SPDL_HJ_ERR_INVALID_ARG;
+        res.image = i;
+        snprintf(res.err, sizeof(res.err),
+                 "image %d: %dx%d at byte %lld reaches past the output buffer of %lld bytes", i,
+                 code_of(i) & 4 ? d.oh : d.ow, code_of(i) & 4 ? d.ow : d.oh, (long long)rq.ragged[i],
+                 (long long)rq.out_bytes);
+        return res.rc;
+      }
+      d.out_off = rq.ragged[i] / esz;
+      idct_share(d);
+    }
+    int64_t wg = 0;
+    for (int pass = 0; pass < 2; pass++) {
+      for (int i = 0; i < n; i++)
+        if ((fused_image[i] != 0) == (pass == 0)) {
+          L.desc[i].sws_wg0 = (int32_t)wg;
+          wg += (int64_t)L.desc[i].sws_bands * L.desc[i].sws_chunks;
+        }
+      if (pass == 0) L.fused_wgs = wg;
+    }
+    L.sws_wgs = wg;
+    L.ragged = true;
+    return SPDL_HJ_OK;
+  }
+
   // Output offsets and the entropy work list, once every descriptor stands
   void finish() {
     const int n = rq.n;
@@ -718,15 +797,65 @@ struct Planner {
 
 LayoutResult build_layout(const LayoutRequest& rq, Layout& L) {
   Planner P{rq, L};
-  if (P.check_flips()) return P.res;
+  if (P.check_flips() || P.check_ragged()) return P.res;
   L.desc.assign(rq.n, ImageDesc{});
+  if (rq.ragged) P.fused_image.assign(rq.n, 0);
   if (rq.views) P.index_views();
   for (int i = 0; i < rq.n; i++)
     if (P.plan_image(i)) return P.res;
   if (rq.views && P.plan_views()) return P.res;
   P.finish();
+  if (rq.ragged && P.finish_ragged()) return P.res;
   P.place_flips();
   return P.res;
+}
+
+int source_frame(const spdl_hj_image_info& p, const spdl_hj_rect* in, views::Rect* src) {
+  *src = views::Rect{0, 0, p.width, p.height};
+  if (!in || rect_is_none(*in)) return SPDL_HJ_OK;
+  return views::resolve(frame_of(p), views::Rect{in->x, in->y, in->w, in->h}, src);
+}
+
+int final_box(int w, int h, const spdl_hj_output& out, int code, Geom* g, int* fw, int* fh) {
+  const bool t = code & 4;
+  const spdl_hj_output chain = t ? swapped_chain(out) : out;
+  if (const int rc = geometry(w, h, &chain, g)) return rc;
+  *fw = t ? g->oh : g->ow;
+  *fh = t ? g->ow : g->oh;
+  return SPDL_HJ_OK;
+}
+
+int ragged_layout(const spdl_hj_image_info* infos, int n, const spdl_hj_output* out,
+                  const spdl_hj_rect* crops, const uint8_t* orients, int64_t align_bytes,
+                  int64_t* offsets, int32_t* ow, int32_t* oh, int32_t* status) {
+  if (!infos || n < 0 || !valid_output(out) || !offsets || !ow || !oh || !status)
+    return SPDL_HJ_ERR_INVALID_ARG;
+  const int64_t esz = out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
+  if (out->pix_fmt == SPDL_HJ_FMT_YUV || out->csc != SPDL_HJ_CSC_SWSCALE || align_bytes < esz ||
+      align_bytes % esz)
+    return SPDL_HJ_ERR_INVALID_ARG;
+  int64_t end = 0;
+  for (int i = 0; i < n; i++) {
+    const spdl_hj_image_info& p = infos[i];
+    views::Rect src;
+    Geom g;
+    int fw = 0, fh = 0;
+    int rc = orients && orients[i] > 7 ? SPDL_HJ_ERR_INVALID_ARG : SPDL_HJ_OK;
+    if (!rc && p.ncomp != 1 && p.ncomp != 3 && p.ncomp != 4) rc = SPDL_HJ_ERR_INVALID_ARG;
+    for (int c = 0; !rc && c < p.ncomp; c++)  // (as spdl_hj_crop_rect asks of a probe)
+      if (p.h_samp[c] < 1 || p.h_samp[c] > 4 || p.v_samp[c] < 1 || p.v_samp[c] > 4)
+        rc = SPDL_HJ_ERR_INVALID_ARG;
+    if (!rc) rc = source_frame(p, crops ? &crops[i] : nullptr, &src);
+    if (!rc) rc = final_box(src.w, src.h, *out, orients ? orients[i] : 0, &g, &fw, &fh);
+    if (rc) fw = fh = 0;
+    status[i] = rc;
+    ow[i] = fw;
+    oh[i] = fh;
+    offsets[i] = round_up(end, align_bytes);
+    end = offsets[i] + (int64_t)fw * fh * 3 * esz;
+  }
+  offsets[n] = end;
+  return SPDL_HJ_OK;
 }
 
 }  // namespace hj

@@ -117,6 +117,16 @@ struct Layout {
   bool transposed = false;
   int view_refused = 0;  // the first status the host gave a view alone (0: none)
   int view_refused_group = 0, view_refused_index = 0;
+  // A ragged submission (spdl_hj_set_ragged): every image its own box at its
+  // own offset, so ow / oh / out_elems_per_image above address nothing, and
+  // the output path is chosen per image.  The flat sws grid (sws_map) holds
+  // the tiles of the fused-eligible images first, [0, fused_wgs): those images
+  // have idct_blocks == 0 and their idct_rgb_kernel tiles in sws_wg0,
+  // sws_bands (MCU rows) and sws_chunks (tiles per MCU row).  The tiles of
+  // every other image (and the one workgroup of a refused one) follow,
+  // [fused_wgs, sws_wgs): sws_kernel's.
+  bool ragged = false;
+  int64_t fused_wgs = 0;
 };
 
 // What spdl_hj_set_views left for the next submission: the groups, their view
@@ -143,6 +153,10 @@ struct HeldViews {
 // optional, one per image, or with views one per view, the groups
 // concatenated in group order.  orients (norients bytes, 0..7): the same
 // places and counts; flips and orients on one request are refused.
+// ragged (n byte offsets into an output of out_bytes bytes): optional, lifts
+// the one-size rule (spdl_hipjpeg.h "ragged batches"); output_path: the
+// context's knob, which in a ragged submission decides per image (0: the
+// fused kernel where an image is eligible; else the generic kernel alone).
 struct LayoutRequest {
   const int64_t* offsets;
   const int64_t* sizes;
@@ -157,6 +171,9 @@ struct LayoutRequest {
   int64_t nflips = 0;
   const uint8_t* orients = nullptr;
   int64_t norients = 0;
+  const int64_t* ragged = nullptr;
+  int64_t out_bytes = 0;
+  int output_path = 0;
 };
 
 // The chain that runs ahead of a transpose: the output spec describes the
@@ -178,5 +195,21 @@ struct LayoutResult {
 };
 
 LayoutResult build_layout(const LayoutRequest& rq, Layout& L);
+
+// The frame image p's output chain reads: the whole frame, or its source crop
+// `in` resolved (null or all zero: none).  0, or why the crop does not resolve.
+int source_frame(const spdl_hj_image_info& p, const spdl_hj_rect* in, views::Rect* src);
+
+// The box of a w x h frame through chain `out` under orientation `code`
+// (0..7): g is the geometry of the chain that runs ahead of the transpose
+// (swapped_chain with bit 2), *fw x *fh the final box -- g's, swapped with bit 2.
+int final_box(int w, int h, const spdl_hj_output& out, int code, Geom* g, int* fw, int* fh);
+
+// spdl_hj_ragged_layout (spdl_hipjpeg.h): each image's final box resolved
+// alone, packed at multiples of align_bytes.  The planner resolves a ragged
+// submission's boxes through the same two functions above.
+int ragged_layout(const spdl_hj_image_info* infos, int n, const spdl_hj_output* out,
+                  const spdl_hj_rect* crops, const uint8_t* orients, int64_t align_bytes,
+                  int64_t* offsets, int32_t* ow, int32_t* oh, int32_t* status);
 
 }  // namespace hj

@@ -10,6 +10,7 @@ from ._image import (
     load_image,
     load_image_batch,
     load_image_batch_nvjpeg,
+    load_image_list,
     load_image_views,
 )
 from ._preprocessing import get_video_filter_desc, parse_image_filter
@@ -44,6 +45,7 @@ __all__ = [
     "load_image_batch",
     "load_image_batch_hip",
     "load_image_batch_nvjpeg",
+    "load_image_list",
     "load_image_views",
     "nv12_to_bgr",
     "nv12_to_rgb",

@@ -38,11 +38,15 @@ class CUDABuffer:
     Exposes ``__cuda_array_interface__`` (version 2, typestr of the element
     type, strides None) and ``device_index`` like the reference, and owns
     its memory either through a torch tensor (default) or through the
-    allocator pair of :func:`spdl_amd.io.cuda_config`."""
+    allocator pair of :func:`spdl_amd.io.cuda_config`.  ``owner``: the buffer
+    whose memory ``tensor`` is a view of (``load_image_list``'s one
+    allocation), kept alive as long as this one lives."""
 
     def __init__(self, tensor: torch.Tensor | None = None, *, ptr: int = 0, shape=(),
-                 dtype=torch.uint8, device_index: int = 0, stream: int = 0, deleter=None):
+                 dtype=torch.uint8, device_index: int = 0, stream: int = 0, deleter=None,
+                 owner=None):
         self._tensor = tensor
+        self._owner = owner
         self._ptr = ptr
         self._shape = tuple(tensor.shape) if tensor is not None else tuple(shape)
         self._dtype = tensor.dtype if tensor is not None else dtype

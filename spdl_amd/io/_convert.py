@@ -10,10 +10,13 @@ from ._buffer import CPUBuffer, CUDABuffer
 
 class _Iface:
     """An interface dict re-exported with another typestr (bfloat16 buffers
-    are handed to torch as int16 and viewed back, zero-copy)."""
+    are handed to torch as int16 and viewed back, zero-copy).  It keeps the
+    buffer it was made of: the tensor holds this object, and with it the
+    memory's owner, as a tensor made of the buffer itself does."""
 
-    def __init__(self, iface: dict, typestr: str):
+    def __init__(self, iface: dict, typestr: str, owner=None):
         self.__cuda_array_interface__ = {**iface, "typestr": typestr}
+        self._owner = owner
 
 
 def to_torch(buffer) -> torch.Tensor:
@@ -26,7 +29,7 @@ def to_torch(buffer) -> torch.Tensor:
         ptr = iface["data"][0]
         dev = f"cuda:{buffer.device_index}"
         if iface["typestr"] == "<V2":  # bfloat16
-            t = torch.as_tensor(_Iface(iface, "<i2"), device=dev).view(torch.bfloat16)
+            t = torch.as_tensor(_Iface(iface, "<i2", buffer), device=dev).view(torch.bfloat16)
         else:
             t = torch.as_tensor(buffer, device=dev)
         if t.data_ptr() != ptr:

@@ -586,6 +586,167 @@ def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = 
     return result
 
 
+_LIST_ASPECT = {None: None, "fit": "decrease", "cover": "increase"}
+
+
+def _list_filter_desc(width, height, scale_mode, scale_algo: str, pix_fmt: str) -> str:
+    """The chain of ``load_image_list``'s image arguments: one ``scale`` node
+    (none at native size) and the format.  ``scale_mode=None``: exactly
+    ``scale=w:h``, a missing side ``-1`` (vf_scale: keep the aspect).  ``"fit"``
+    and ``"cover"``: ``force_original_aspect_ratio=decrease`` / ``increase``
+    with neither the pad nor the crop that bring ``load_image_batch``'s images
+    to one box -- a missing side is the other one, a square box."""
+    if scale_mode not in _LIST_ASPECT:
+        raise ValueError(f"scale_mode must be 'fit', 'cover' or None, got {scale_mode!r}")
+    if width is None and height is None:
+        if scale_mode is not None:
+            raise ValueError(f"scale_mode={scale_mode!r} needs a width or a height")
+        return get_video_filter_desc(pix_fmt=pix_fmt)
+    ratio = _LIST_ASPECT[scale_mode]
+    if ratio is None:
+        w, h = (-1 if v is None else int(v) for v in (width, height))
+        if w < 0 and h < 0:
+            raise ValueError("one of width and height must be a size")
+        extra = ""
+    else:
+        w, h = (int(width if width is not None else height),
+                int(height if height is not None else width))
+        if w <= 0 or h <= 0:
+            raise ValueError(f"scale_mode={scale_mode!r} needs a positive box, not {w}x{h}")
+        extra = f":force_original_aspect_ratio={ratio}"
+    return f"scale=w={w}:h={h}:flags={scale_algo}{extra},format=pix_fmts={pix_fmt}"
+
+
+def load_image_list(
+    srcs,
+    *,
+    width: int | None = None,
+    height: int | None = None,
+    scale_mode: str | None = None,
+    scale_algo: str = "bicubic",
+    pix_fmt: str | None = "rgb24",
+    filter_desc: str | None = _FILTER_DESC_DEFAULT,
+    device_config: CUDAConfig | None = None,
+    strict: bool = True,
+    normalize: bool = False,
+    mean=(0.485, 0.456, 0.406),
+    std=(0.229, 0.224, 0.225),
+    norm_dtype: str = "float16",
+    crops=None,
+    flips=None,
+    exif_orientation: bool = False,
+    align: int = 256,
+    csc: str = "swscale",
+):
+    """Every image at its own size from one submission (an extension, like
+    :func:`load_image_views`; include/spdl_hipjpeg.h "ragged batches"): native
+    resolution, or an aspect-preserving resize, neither of which
+    :func:`load_image_batch` can hold in one ``[B,H,W,3]``.
+
+    ``width = height = None`` keeps every file's size.  Otherwise
+    ``scale_mode=None`` is exactly ``scale=w:h`` with a ``None`` or ``-1`` /
+    ``-n`` side following the aspect ratio (vf_scale); ``"fit"`` scales the
+    image into the box (the longer side meets it) and ``"cover"`` over it (the
+    shorter side meets it, torchvision's ``Resize(int)``) -- ``load_image_batch``'s
+    ``"pad"`` and ``"crop"`` without the pad and the crop.  A ``filter_desc``
+    is any chain ``load_image_batch`` takes.  ``crops``, ``flips``,
+    ``exif_orientation``, ``normalize`` are ``load_image_batch``'s.
+
+    Returns ``(buffers, image_indices)``: one allocation, every buffer a view
+    of it with its image's own shape (``[H,W,3]``, or ``[3,H,W]`` for ``rgb`` /
+    ``bgr``) starting at a multiple of ``align`` bytes, and the index in
+    ``srcs`` of each.  ``strict=False`` drops failed images (``image_indices``
+    says what remains); ``strict=True`` raises.  Without a ``device_config``
+    the buffers are host copies."""
+    if not srcs:
+        raise ValueError("`srcs` must not be empty.")
+    if pix_fmt is None:
+        raise ValueError("load_image_list needs an RGB pix_fmt: no ragged planar YUV output")
+    if csc != "swscale":
+        raise ValueError(f"load_image_list converts with csc='swscale' only, not {csc!r}")
+    if filter_desc == _FILTER_DESC_DEFAULT:
+        filter_desc = _list_filter_desc(width, height, scale_mode, scale_algo, pix_fmt)
+    elif (width, height, scale_mode) != (None, None, None):
+        raise ValueError("filter_desc= and width / height / scale_mode are exclusive")
+    if filter_desc is None:
+        raise ValueError("load_image_list needs a filter chain")
+    n_src = len(srcs)
+    for name, per in (("crops", crops), ("flips", flips)):
+        if per is not None and len(per) != n_src:
+            raise ValueError(f"{len(per)} {name} for {n_src} images")
+    if flips is not None:
+        flips = [_lib._flip(f) for f in flips]
+    out = parse_image_filter(filter_desc, default_pix_fmt=pix_fmt)
+    if out.pix_fmt == "yuv":
+        raise ValueError("load_image_list needs an RGB pix_fmt: no ragged planar YUV output")
+    if crops is not None and out.src_crop is not None:
+        raise ValueError("crops= and a source crop in filter_desc are exclusive")
+    if flips is not None and (out.flip is not None or out.orient is not None):
+        raise ValueError("flips= and hflip / vflip / transpose in filter_desc are exclusive")
+    if normalize:
+        out = Output(**{**out.__dict__, "normalize": True, "mean": tuple(mean),
+                        "std": tuple(std), "norm_dtype": norm_dtype})
+    cfg = device_config or _default_config()
+    datas, keep, infos = [], [], []
+    for i, s in enumerate(srcs):
+        try:
+            d = _read(s)
+            infos.append(_lib.get_image_info(d))
+        except Exception as err:  # reference logs and skips (strict=False)
+            _LG.error("Failed to load image %d: %s", i, err)
+            continue
+        datas.append(d)
+        keep.append(i)
+    if strict and len(datas) != n_src:
+        raise RuntimeError("Failed to load some images.")
+    if not datas:
+        raise RuntimeError("Failed to load all the images.")
+    n = len(datas)
+    if crops is not None:
+        crops = [crops[i] for i in keep]
+    elif out.src_crop is not None:
+        crops = [out.src_crop] * n
+    if flips is not None:
+        flips = [flips[i] for i in keep]
+    # one code per image: the file's EXIF orientation, the chain's transpose, a flip
+    if exif_orientation:
+        out, codes = _exif_codes(datas, out, flips)
+    else:
+        every = _lib._orient(out.orient) if out.orient is not None else _lib._flip(out.flip)
+        codes = [every if flips is None else flips[k] for k in range(n)]
+    out = Output(**{**out.__dict__, "src_crop": None, "flip": None, "orient": None})
+    codes = codes if any(codes) else None
+    offsets, sizes, planned = _lib.ragged_layout(infos, out, crops, codes, align)
+    esz = 1 if out.torch_dtype == torch.uint8 else 2
+    # (every offset and every extent is a multiple of the element size)
+    total = _alloc_out(cfg, (max(offsets[n] // esz, 1),), out.torch_dtype)
+    dec = _lib.thread_decoder(cfg.device_index)
+    status = dec.decode_batch(datas, out, total.data_ptr(), offsets[n], stream=_stream(cfg),
+                              sync=True, check=False, crops=crops, orients=codes,
+                              ragged=offsets[:n])
+    from ._convert import to_torch
+
+    flat = to_torch(total)
+    bufs, idx = [], []
+    for k in range(n):
+        if status[k] or planned[k]:
+            _LG.error("Failed to decode image %d: status %d", keep[k], status[k] or planned[k])
+            continue
+        shape = _shape(out, *sizes[k])
+        first = offsets[k] // esz
+        t = flat[first:first + int(np.prod(shape))].view(shape)
+        # (every view holds the allocation: with an allocator pair its deleter
+        # runs when the last of them is gone)
+        view = CUDABuffer(t, stream=cfg.stream, owner=total)
+        bufs.append(view if device_config is not None else _to_host(view))
+        idx.append(keep[k])
+    if strict and len(bufs) != n:
+        raise RuntimeError("Failed to load some images.")
+    if not bufs:
+        raise RuntimeError("Failed to load all the images.")
+    return bufs, idx
+
+
 _UNSUPPORTED_FRAMES = {2: "gbrp", 3: "gbrap", 4: "yuva444p", 5: "yuva444p"}  # by spdl_hj_color
 
 
