@@ -497,6 +497,37 @@ int spdl_hj_ragged_layout(const spdl_hj_image_info* infos, int32_t n, const spdl
                           int32_t* status /* n */);
 int spdl_hj_set_ragged(spdl_hj_ctx* ctx, const int64_t* offsets, int32_t n);
 
+/* ---- reduced-size decode (additive in ABI 7: one function; a binding finds
+ * it by symbol) ------------------------------------------------------------
+ * FFmpeg's mjpeg decoder option `lowres` 1..3 (the reference passes it as
+ * decode_config(decoder_options={"lowres": ...})): level L inverse-transforms
+ * only the low (8 >> L) x (8 >> L) corner of each block, so the decoder's
+ * frame is ceil(width / 2^L) x ceil(height / 2^L) and component c's plane
+ * ceil(W' h_c / hmax) x ceil(H' v_c / vmax).  Scale plans, geometry, pad and
+ * crop rules, ragged boxes, flips and orientations all take that frame, as
+ * FFmpeg's filter graph does.  The pixels are NOT those of the full decode
+ * scaled down; the transforms are restated from libavcodec/jrevdct.c
+ * (ff_j_rev_dct4 / 2 / 1) whatever `idct` says.
+ *
+ * levels[i] in 0..3 is image i's level in the next spdl_hj_decode_batch /
+ * _device / _staged call, which consumes them whether or not it succeeds;
+ * n == that call's n; NULL / 0 clears (spdl_hj_set_flips' rules).  An image of
+ * level 0 in such a submission gives the bytes it gives without the call, and
+ * all-zero levels are the submission without the call exactly.
+ * spdl_hj_decode_planes consumes a one-element setting as well and then
+ * returns the reduced planes, tightly packed at the reduced component sizes.
+ * spdl_hj_output_size and spdl_hj_ragged_layout know nothing of levels: hand
+ * them the reduced width and height.
+ *
+ * SPDL_HJ_ERR_INVALID_ARG from the consuming call, with nothing written: a
+ * count other than n; a level above 3; any level above 0 together with source
+ * crops, with views, or with csc = JFIF.  An RGB-coded or 4-component frame
+ * with a level above 0 is refused alone (SPDL_HJ_ERR_UNSUPPORTED); the rest of
+ * the batch decodes.  The read-only parameter "lowres_images" reports the
+ * images with a level above 0 in the last submission, "planes_bytes" the
+ * component planes it laid out in the workspace. */
+int spdl_hj_set_lowres(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n);
+
 /* ABI version of the loaded library (== SPDL_HJ_ABI_VERSION). */
 int spdl_hj_abi_version(void);
 
@@ -748,7 +779,9 @@ const char* spdl_hj_stage_name(int32_t i);
  * "generic_workgroups" (with ragged batches), the workgroups of the fused
  * full-resolution kernel and of the generic output kernel in the last ragged
  * submission, which chooses between them per image (0 and 0 after a plain
- * submission).
+ * submission); "lowres_images" and "planes_bytes" (with the reduced-size
+ * decode), the images of the last submission with a level above 0 and the
+ * bytes of the component planes it laid out in the workspace.
  * Builds with -DHJ_ABLATIONS=1 also take "debug_mask" (timing ablations that
  * skip kernel phases; outputs wrong); release builds reject it. */
 int spdl_hj_set_param(spdl_hj_ctx* ctx, const char* name, int64_t value);

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPDL_AMD_LIB") or os.path.join(_HERE, "lib", "libspdl_hipjpeg.so")
@@ -62,6 +62,7 @@ EXPORTED = (
     "spdl_hj_orient_code",
     "spdl_hj_ragged_layout",
     "spdl_hj_set_ragged",
+    "spdl_hj_set_lowres",
 )
 
 
@@ -456,6 +457,8 @@ def lib() -> ctypes.CDLL:
             L.spdl_hj_ragged_layout.argtypes = [vp, i32, ctypes.POINTER(OutputSpec), vp, vp, i64,
                                                 vp, vp, vp, vp]
             L.spdl_hj_set_ragged.argtypes = [vp, vp, i32]
+        if hasattr(L, "spdl_hj_set_lowres"):  # (likewise)
+            L.spdl_hj_set_lowres.argtypes = [vp, vp, i32]
         ver = L.spdl_hj_abi_version()
         # (an explicitly chosen older build, ABI >= 5, loads for A/B runs)
         if ver != ABI_VERSION and not (os.environ.get("SPDL_AMD_LIB") and 5 <= ver < ABI_VERSION):
@@ -507,15 +510,77 @@ def output_size(width: int, height: int, out: Output) -> tuple[int, int]:
     return ow.value, oh.value
 
 
-def ragged_layout(infos, out: Output, crops=None, orients=None,
-                  align: int = 256) -> tuple[list[int], list[tuple[int, int]], list[int]]:
+def lowres_size(width: int, height: int, level: int) -> tuple[int, int]:
+    """The frame the decoder emits at reduced-size level ``level`` (FFmpeg's
+    ``lowres``): ``ceil(width / 2^level) x ceil(height / 2^level)``."""
+    return -(-width >> level), -(-height >> level)
+
+
+def auto_lowres(width: int, height: int, out: Output) -> int:
+    """``lowres="auto"`` for a ``width x height`` frame through ``out``: the
+    largest level ``<= 3`` whose frame is, on both sides, no smaller than the
+    scaled content the chain makes of the full frame (its size before pad and
+    crop) -- the decode never goes below the size it scales to.  0 for a
+    native-size decode."""
+    if not out.resize:
+        return 0
+    sw, sh = output_size(width, height, replace(out, pad_w=0, pad_h=0, crop_w=0, crop_h=0))
+    level = 0
+    while level < 3 and all(a >= b for a, b in zip(lowres_size(width, height, level + 1), (sw, sh))):
+        level += 1
+    return level
+
+
+def lowres_levels(lowres, infos, out: Output, orients=None) -> list[int] | None:
+    """``lowres=`` as one level per image: an int ``0..3`` for every image, a
+    sequence with one entry per image, or ``"auto"`` (:func:`auto_lowres` from
+    each probe of ``infos``; a transposed image against the swapped chain).
+    ``None`` when it asks for nothing: ``None`` itself or all zeros."""
+    n = len(infos)
+    if lowres is None:
+        return None
+    if isinstance(lowres, str) and lowres != "auto":
+        raise ValueError(f'lowres= takes 0..3, a sequence of them or "auto", not {lowres!r}')
+
+    def one(v, k):
+        if v == "auto":
+            i, code = infos[k], (_orient(orients[k]) if orients is not None else _orient(out.orient))
+            return auto_lowres(*((i.height, i.width) if code & 4 else (i.width, i.height)), out)
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 3:
+            raise ValueError(f"lowres level {v!r} is not in 0..3")
+        return v
+    if isinstance(lowres, (str, int)):
+        levels = [one(lowres, k) for k in range(n)]
+    else:
+        try:
+            levels = list(lowres)
+        except TypeError:
+            raise ValueError(f"lowres level {lowres!r} is not in 0..3") from None
+        if len(levels) != n:
+            raise ValueError(f"{len(levels)} lowres levels for a batch of {n} images")
+        levels = [one(v, k) for k, v in enumerate(levels)]
+    return levels if any(levels) else None
+
+
+def ragged_layout(infos, out: Output, crops=None, orients=None, align: int = 256,
+                  lowres=None) -> tuple[list[int], list[tuple[int, int]], list[int]]:
     """``(offsets, sizes, statuses)`` of a ragged batch (spdl_hj_ragged_layout;
     host only): every image's final ``(ow, oh)`` resolved alone -- its source
     crop, the chain of ``out``, its orientation -- and packed at multiples of
     ``align`` bytes.  ``offsets`` has ``n + 1`` entries, the last the buffer's
     size.  An image whose crop or geometry does not resolve has its status, a
-    ``(0, 0)`` size and no bytes.  ``infos``: a sequence of ImageInfo."""
+    ``(0, 0)`` size and no bytes.  ``infos``: a sequence of ImageInfo.
+    ``lowres`` (:func:`lowres_levels`): the boxes are those of the reduced
+    frames."""
     n = len(infos)
+    levels = lowres_levels(lowres, infos, out, orients)
+    if levels is not None:  # (the library sizes boxes from the probes: hand it reduced ones)
+        reduced = []
+        for i, lv in zip(infos, levels):
+            r = ImageInfo.from_buffer_copy(i)
+            r.width, r.height = lowres_size(i.width, i.height, lv)
+            reduced.append(r)
+        infos = reduced
     inf = infos if isinstance(infos, ctypes.Array) else (ImageInfo * max(n, 1))(*infos)
     rects = None
     if crops is not None:
@@ -805,6 +870,15 @@ class Decoder:
             raise ValueError(f"{len(orients)} orients for a batch of {n} images")
         self.set_orients(orients)
 
+    def set_lowres(self, levels) -> None:
+        """The reduced-size levels of the next batch submission
+        (spdl_hj_set_lowres): one ``0..3`` per image; ``None`` or an empty
+        sequence clears them.  :meth:`decode_planes` consumes one level too."""
+        levels = bytes(int(v) for v in levels) if levels is not None else b""
+        arr = (ctypes.c_uint8 * max(len(levels), 1))(*levels)
+        if lib().spdl_hj_set_lowres(self._h, arr if levels else None, len(levels)):
+            raise ValueError("invalid lowres levels")
+
     def set_ragged(self, offsets) -> None:
         """The byte offsets of the next batch submission's images in its
         output (spdl_hj_set_ragged): that submission is a ragged one, every
@@ -834,7 +908,7 @@ class Decoder:
 
     def decode_batch(self, datas, out: Output, out_ptr: int, out_bytes: int, stream=None,
                      sync: bool = True, check: bool = True, crops=None, views=None,
-                     flips=None, orients=None, ragged=None) -> list[int]:
+                     flips=None, orients=None, ragged=None, lowres=None) -> list[int]:
         """Per-image statuses.  A failed image raises RuntimeError unless
         ``check`` is False (synchronous calls), which returns the statuses.
         ``crops``: a source crop ``(x, y, w, h)`` or ``None`` per image.
@@ -848,7 +922,9 @@ class Decoder:
         per image instead of ``flips`` (spdl_hj_set_orients).  ``ragged``:
         one byte offset per image (the first ``n`` of :func:`ragged_layout`'s)
         -- every image its own size, written at its offset of ``out_ptr``
-        (include/spdl_hipjpeg.h "ragged batches")."""
+        (include/spdl_hipjpeg.h "ragged batches").  ``lowres``: a reduced-size
+        level ``0..3`` per image (spdl_hj_set_lowres; resolve ``"auto"`` or a
+        single int with :func:`lowres_levels` first)."""
         n = len(datas)
         if n == 0:
             raise RuntimeError("Failed to decode an image. (the batch is empty)")
@@ -871,10 +947,10 @@ class Decoder:
                 _stream_handle(stream), int(bool(sync)), status, err, 1024,
             )
         return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                                    check, status, call, orients, ragged))
+                                    check, status, call, orients, ragged, lowres))
 
     def _submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync, check, status,
-                call, orients=None, ragged=None):
+                call, orients=None, ragged=None, lowres=None):
         """What the three batch submissions share: the views, crops and flips
         (or orientations) go to the context, ``call(err)`` -- the method's own marshalling and
         its native call -- returns the library's code, and a failure raises
@@ -892,6 +968,8 @@ class Decoder:
             self._flips(out, flips, n, views)
         if ragged is not None:  # (its count is the consuming call's to check)
             Decoder.set_ragged(self, ragged)
+        if lowres is not None:  # (count and values likewise)
+            Decoder.set_lowres(self, lowres)
         err = ctypes.create_string_buffer(1024)
         rc = call(err)
         if rc and not (not check and sync and (any(status) or _refused(views, rc))):
@@ -901,7 +979,8 @@ class Decoder:
     def decode_batch_device(self, dev_ptr: int, dev_bytes: int, offsets, sizes, infos,
                             out: Output, out_ptr: int, out_bytes: int, stream=None,
                             sync: bool = True, crops=None, check: bool = True,
-                            views=None, flips=None, orients=None, ragged=None) -> list[int]:
+                            views=None, flips=None, orients=None, ragged=None,
+                            lowres=None) -> list[int]:
         """``offsets``/``sizes``: sequences or int64 numpy arrays; ``infos``: a
         sequence of ImageInfo or a prebuilt ``(ImageInfo * n)`` array (pass the
         same objects again to skip re-marshalling on every call)."""
@@ -921,7 +1000,7 @@ class Decoder:
                 status.ctypes.data, err, 1024,
             )
         return Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                               check, status, call, orients, ragged).tolist()
+                               check, status, call, orients, ragged, lowres).tolist()
 
     def _spec(self, out: Output) -> OutputSpec:
         cache = self.__dict__.setdefault("_spec_cache", {})
@@ -981,7 +1060,7 @@ class Decoder:
     def decode_staged(self, ticket: int, nbytes: int, offsets, sizes, out: Output, out_ptr: int,
                       out_bytes: int, stream=None, sync: bool = True, crops=None,
                       check: bool = True, views=None, flips=None, orients=None,
-                      ragged=None) -> list[int]:
+                      ragged=None, lowres=None) -> list[int]:
         n = len(offsets)
         status = (ctypes.c_int32 * max(n, 1))()
 
@@ -993,7 +1072,7 @@ class Decoder:
                 self._h, int(ticket), int(nbytes), offs, szs, n, ctypes.byref(spec), out_ptr,
                 out_bytes, _stream_handle(stream), int(bool(sync)), status, err, 1024)
         return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                                    check, status, call, orients, ragged))[:n]
+                                    check, status, call, orients, ragged, lowres))[:n]
 
     def debug_entropy(self, data, nblocks: int):
         """Coefficients / destuffed bytes / diagnostics of one image (tests)."""
@@ -1016,23 +1095,28 @@ class Decoder:
             "dbg": [int(x) for x in diag[8:12]],
             "scans": [tuple(int(x) for x in diag[12 + 3 * s:15 + 3 * s]) for s in range(16)]}
 
-    def decode_planes(self, data, idct: str = "simple", stream=None):
+    def decode_planes(self, data, idct: str = "simple", stream=None, lowres: int = 0):
+        """The decoder's own planes; ``lowres`` 1..3: the reduced planes, at the
+        reduced frame's component sizes."""
         import numpy as np
 
         info = get_image_info(data)
+        fw, fh = lowres_size(info.width, info.height, lowres if 0 <= lowres <= 3 else 0)
         hmax = max(info.h_samp[c] for c in range(info.ncomp))
         vmax = max(info.v_samp[c] for c in range(info.ncomp))
         planes = []
         for c in range(info.ncomp):
             if info.ncomp == 1:
-                w, h = info.width, info.height
+                w, h = fw, fh
             else:
-                w = -(-info.width * info.h_samp[c] // hmax)
-                h = -(-info.height * info.v_samp[c] // vmax)
+                w = -(-fw * info.h_samp[c] // hmax)
+                h = -(-fh * info.v_samp[c] // vmax)
             planes.append(np.zeros((h, w), np.uint8))
         ptrs = (ctypes.c_void_p * 4)(*([p.ctypes.data for p in planes] + [None] * (4 - len(planes))))
         addr, size, keep = buffer_address(data)
         err = ctypes.create_string_buffer(1024)
+        if lowres:
+            Decoder.set_lowres(self, [lowres])
         rc = lib().spdl_hj_decode_planes(self._h, addr, size, IDCT[idct],
                                          ptrs, _stream_handle(stream), err, 1024)
         if rc:

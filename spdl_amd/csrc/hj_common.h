@@ -237,7 +237,11 @@ struct ImageDesc {      // host-filled per image
   int32_t refuse;
   // idct_kernel's blocks of this image: nblocks, or those of the MCU rectangle
   // covering a source crop (reg_mw x reg_mh MCUs from (reg_mx0, reg_my0);
-  // reg_mw == 0: no crop -- the image's own order and grid)
+  // reg_mw == 0: no crop -- the image's own order and grid).  In a submission
+  // with reduced-size levels (spdl_hj_set_lowres; one byte per image beside
+  // the descriptors, hj_launch.h) an image of level L > 0 counts
+  // idct_lowres_kernel's lanes here, sum over c of ceil(bw_c / 2^L) bh_c, and
+  // its plane_stride, planes and windows are the reduced frame's.
   int32_t idct_blocks;
   int32_t reg_mx0, reg_my0, reg_mw, reg_mh;
   uint32_t reg_mw_magic;  // idct_div_magic(reg_mw)

@@ -158,6 +158,7 @@ struct Slot {
       spdl_hj_image_info info;
       spdl_hj_rect rect;  // its source crop (has_rects)
       uint8_t flip;       // its output flip or orientation code (has_flips)
+      uint8_t lowres;     // its reduced-size level
     };
     std::vector<Item> items;
     bool has_rects = false, has_flips = false;  // the batch had crops / flips
@@ -275,6 +276,11 @@ struct spdl_hj_ctx {
   std::vector<uint8_t> flips;
   // spdl_hj_set_orients: its orientation codes (both set: the planner refuses)
   std::vector<uint8_t> orients;
+  // spdl_hj_set_lowres: its reduced-size levels, and the images with one
+  // above 0 in the last submission
+  std::vector<uint8_t> lowres;
+  int64_t lowres_images = 0;
+  int64_t planes_bytes = 0;  // the planes the last submission laid out in the workspace
   int64_t idct_workgroups = 0;  // IDCT workgroups the last submission launched
   int64_t entropy_workgroups = 0;  // ... and its entropy work items (images, or their pieces)
   // ... the fused-eligible images' idct_rgb_kernel workgroups, and those of
@@ -451,11 +457,17 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
   HJ_HIP(grow(W.segs, (size_t)L.total_segs * 4 + 64, st, &b->segs));
   HJ_HIP(grow(W.dschunks, (size_t)L.total_ds * sizeof(DsChunk) + 64, st, &b->dschunks));
   // (the work list follows the descriptors, a flipped submission's flags the work list)
-  HJ_HIP(grow(W.desc, sizeof(ImageDesc) * b->ndesc + sizeof(uint32_t) * b->nwork + L.flips.size(),
+  HJ_HIP(grow(W.desc,
+              sizeof(ImageDesc) * b->ndesc + sizeof(uint32_t) * b->nwork + L.flips.size() +
+                  L.lowres.size(),
               st, &b->desc));
   b->work = reinterpret_cast<uint32_t*>(b->desc + b->ndesc);
   b->flips = L.flips.empty() ? nullptr : reinterpret_cast<const uint8_t*>(b->work + b->nwork);
   b->transposed = L.transposed;
+  // (... and a reduced-size submission's levels the flags)
+  b->lowres = L.lowres.empty()
+                  ? nullptr
+                  : reinterpret_cast<const uint8_t*>(b->work + b->nwork) + L.flips.size();
   HJ_HIP(grow(W.chain, (size_t)(kChainHead + L.chain_granules) * 8 + 64, st, &b->chain));
   HJ_HIP(grow(W.maps, (size_t)(L.ds_wgs + L.idct_wgs + L.hs_wgs + L.sws_wgs) * 4 + 64, st,
               &b->ds_map));
@@ -550,11 +562,13 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
     return (double)max_tiles * n > 1.25 * (double)flat_wgs;
   };
   const bool ds_flat = use_flat(L.ds_wgs, L.max_chunks);
-  const bool idct_flat = use_flat(L.idct_wgs, (L.max_blocks + kIdctThreads - 1) / kIdctThreads);
+  // (idct_lowres_kernel has the flat grid alone)
+  const bool idct_flat = B.lowres != nullptr ||
+                         use_flat(L.idct_wgs, (L.max_blocks + kIdctThreads - 1) / kIdctThreads);
   const bool sws_flat = use_flat(L.sws_wgs, (int64_t)L.sws_bands * L.sws_chunks);
   // + work list, + the flags of a flipped submission (one byte per descriptor)
   const size_t work_end = sizeof(ImageDesc) * B.ndesc + sizeof(uint32_t) * B.nwork;
-  const size_t desc_bytes = work_end + L.flips.size();
+  const size_t desc_bytes = work_end + L.flips.size() + L.lowres.size();
   HJ_HIP(slot.pin_desc.ensure(desc_bytes));
   HJ_HIP(slot.pin_status.ensure(sizeof(int32_t) * n));
   slot.n = n;
@@ -563,6 +577,9 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
          sizeof(uint32_t) * B.nwork);
   if (B.flips)
     memcpy(static_cast<uint8_t*>(slot.pin_desc.p) + work_end, L.flips.data(), L.flips.size());
+  if (B.lowres)
+    memcpy(static_cast<uint8_t*>(slot.pin_desc.p) + work_end + L.flips.size(), L.lowres.data(),
+           L.lowres.size());
   // the batch's swscale tables travel with the descriptors
   const bool swscale = !sub.planes_only && out->csc == SPDL_HJ_CSC_SWSCALE;
   const size_t tb = swscale ? L.tables.size() * 4 : 0;
@@ -572,12 +589,12 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   if (!hs) {
     HJ_HIP(hipMemcpyAsync(B.desc, slot.pin_desc.p, desc_bytes, hipMemcpyHostToDevice, st));
     if (tb) HJ_HIP(hipMemcpyAsync(B.wts, slot.pin_tables.p, tb, hipMemcpyHostToDevice, st));
-  } else if (B.flips) {
+  } else if (B.flips || B.lowres) {
     // (parse_kernel brings over the descriptors and the work list alone: the
-    // flags behind them take one small copy from the same pinned pages)
-    HJ_HIP(hipMemcpyAsync(const_cast<uint8_t*>(B.flips),
-                          static_cast<const uint8_t*>(slot.pin_desc.p) + work_end, L.flips.size(),
-                          hipMemcpyHostToDevice, st));
+    // flags and levels behind them take one small copy from the same pinned pages)
+    HJ_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(B.work + B.nwork),
+                          static_cast<const uint8_t*>(slot.pin_desc.p) + work_end,
+                          desc_bytes - work_end, hipMemcpyHostToDevice, st));
   }
   mark(ctx, slot, 1, st);
   HJ_HIP(launch_parse(B, hs ? static_cast<const ImageDesc*>(slot.pin_desc.dev) : nullptr,
@@ -638,10 +655,14 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   const int ragged_fused = L.ragged ? (int)L.fused_wgs : 0;
   ctx->idct_workgroups = ctx->fused_workgroups = ctx->generic_workgroups = 0;
   ctx->entropy_workgroups = B.nwork;
+  ctx->lowres_images = L.lowres_images;
+  ctx->planes_bytes = L.total_planes;
   // (a views submission whose views were all refused has no block to transform)
   if (!(abl & kAblNoIdct) && (L.ragged || !fused) && L.max_blocks > 0) {
-    HJ_HIP(launch_idct(B, idct_kind, idct_flat, (int)L.idct_wgs, L.max_blocks,
-                       (ctx->xcd_order >> 1) & 1, st));
+    if (B.lowres) HJ_HIP(launch_idct_lowres(B, idct_kind, (int)L.idct_wgs, st));
+    else
+      HJ_HIP(launch_idct(B, idct_kind, idct_flat, (int)L.idct_wgs, L.max_blocks,
+                         (ctx->xcd_order >> 1) & 1, st));
     ctx->idct_workgroups =
         idct_flat ? L.idct_wgs : (int64_t)((L.max_blocks + kIdctThreads - 1) / kIdctThreads) * n;
   }
@@ -718,7 +739,8 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
                          sub.ragged ? (size_t)d.ow * d.oh * 3 * esz : img_bytes,
                          d.in_off, d.in_size, m.second,
                          sub.crops ? sub.crops[m.first] : spdl_hj_rect{},
-                         sub.flips ? sub.flips[m.first] : (uint8_t)0});
+                         sub.flips ? sub.flips[m.first] : (uint8_t)0,
+                         L.lowres.empty() ? (uint8_t)0 : L.lowres[m.first]});
     }
     R.ticket = slot.ticket;
     R.bytes = sub.d_bytes;
@@ -783,6 +805,10 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
     rq.flips = &item.flip;
     rq.nflips = 1;
   }
+  if (item.lowres) {
+    rq.lowres = &item.lowres;
+    rq.nlowres = 1;
+  }
   int rc = plan_batch(rq, L, &st1, err, errlen);
   if (rc) return rc;
   // the spare slot, on the failed batch's lane (its workspace is free: the
@@ -799,6 +825,7 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
   const int64_t idct_wgs = ctx->idct_workgroups;  // (the batch's, not this re-decode's)
   const int64_t ent_wgs = ctx->entropy_workgroups;
   const int64_t fused_wgs = ctx->fused_workgroups, generic_wgs = ctx->generic_workgroups;
+  const int64_t lowres_images = ctx->lowres_images, planes_bytes = ctx->planes_bytes;
   rc = run_pipeline(ctx, *s, L,
                     {r.bytes, r.len, 1, &r.out, r.out_dev + item.out_off, item.out_bytes, xs, 1,
                      &st1},
@@ -807,6 +834,8 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
   ctx->entropy_workgroups = ent_wgs;
   ctx->fused_workgroups = fused_wgs;
   ctx->generic_workgroups = generic_wgs;
+  ctx->lowres_images = lowres_images;
+  ctx->planes_bytes = planes_bytes;
   ctx->last_ticket = last;
   return rc ? rc : st1;
 }
@@ -883,7 +912,7 @@ int take_views(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, const void* o
 struct Held {
   std::vector<spdl_hj_rect> rects;
   HeldViews views;
-  std::vector<uint8_t> flipv, orientv;
+  std::vector<uint8_t> flipv, orientv, lowresv;
   std::vector<int64_t> raggedv;
   const int64_t* ragged = nullptr;      // null: a plain submission
   const spdl_hj_rect* crops = nullptr;  // null: none
@@ -893,6 +922,8 @@ struct Held {
   int64_t nflips = 0;
   const uint8_t* orients = nullptr;
   int64_t norients = 0;
+  const uint8_t* lowres = nullptr;  // reduced-size levels (the planner's to check as well)
+  int64_t nlowres = 0;
   int crc = 0, vrc = 0;
   Held(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, const void* out_dev, size_t out_bytes,
        char* err, size_t errlen) {
@@ -908,6 +939,12 @@ struct Held {
     if (!orientv.empty()) {
       orients = orientv.data();
       norients = (int64_t)orientv.size();
+    }
+    lowresv.swap(ctx->lowres);
+    ctx->lowres.clear();
+    if (!lowresv.empty()) {
+      lowres = lowresv.data();
+      nlowres = (int64_t)lowresv.size();
     }
     raggedv.swap(ctx->ragged);
     ctx->ragged.clear();
@@ -996,7 +1033,8 @@ int submit(spdl_hj_ctx* ctx, const Held& held, const Batch& b, SlotRelease& slot
   // (views: one entropy workgroup per image, so no hand-off can give up)
   int rc = plan_batch({b.offsets, b.sizes, infos, b.n, b.out, held.hv ? 0 : ctx->piece_bytes,
                        &ctx->plans, held.crops, held.hv, held.flips, held.nflips, held.orients,
-                       held.norients, held.ragged, (int64_t)b.out_bytes, ctx->output_path},
+                       held.norients, held.ragged, (int64_t)b.out_bytes, ctx->output_path,
+                       held.lowres, held.nlowres},
                       L, b.status, err, errlen);
   if (rc) return rc;
   // the probes (the caller's own with device bytes, ABI 5) say which files
@@ -1030,11 +1068,16 @@ struct OneImage {
 
 int decode_one(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, const spdl_hj_image_info& info,
                const spdl_hj_output& o, int64_t piece_bytes, hipStream_t st, OneImage* r, char* err,
-               size_t errlen) {
+               size_t errlen, uint8_t lowres = 0) {
   const int64_t off = 0, sz = (int64_t)size, total = round_up(sz + 64, 256);
   r->L = Layout{};
   r->ran = false;
-  int rc = plan_batch({&off, &sz, &info, 1, &o, piece_bytes, nullptr}, r->L, nullptr, err, errlen);
+  LayoutRequest rq{&off, &sz, &info, 1, &o, piece_bytes, nullptr};
+  if (lowres) {
+    rq.lowres = &lowres;
+    rq.nlowres = 1;
+  }
+  int rc = plan_batch(rq, r->L, nullptr, err, errlen);
   if (rc) return rc;
   SlotRelease slot;
   if ((rc = acquire_slot(ctx, &slot.s, err, errlen))) return rc;
@@ -1126,6 +1169,13 @@ int spdl_hj_set_flips(spdl_hj_ctx* ctx, const uint8_t* flips, int32_t n) {
   if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
   ctx->flips.clear();
   if (flips && n > 0) ctx->flips.assign(flips, flips + n);
+  return SPDL_HJ_OK;
+}
+
+int spdl_hj_set_lowres(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n) {
+  if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
+  ctx->lowres.clear();
+  if (levels && n > 0) ctx->lowres.assign(levels, levels + n);
   return SPDL_HJ_OK;
 }
 
@@ -1370,6 +1420,14 @@ int spdl_hj_decode_planes(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
     set_err(err, errlen, "invalid argument");
     return SPDL_HJ_ERR_INVALID_ARG;
   }
+  // (a one-element spdl_hj_set_lowres: consumed whatever becomes of the call)
+  std::vector<uint8_t> levels;
+  levels.swap(ctx->lowres);
+  if (levels.size() > 1 || (levels.size() == 1 && levels[0] > 3)) {
+    set_err(err, errlen, "spdl_hj_set_lowres: one level, 0 to 3, for spdl_hj_decode_planes");
+    return SPDL_HJ_ERR_INVALID_ARG;
+  }
+  const int lv = levels.empty() ? 0 : levels[0];
   DeviceGuard g(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   spdl_hj_image_info info;
@@ -1383,7 +1441,7 @@ int spdl_hj_decode_planes(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
   OneImage one;
   // (a piece hand-off that gave up: once more in one entropy workgroup)
   for (int64_t piece_bytes : {ctx->piece_bytes, (int64_t)0}) {
-    rc = decode_one(ctx, data, size, info, o, piece_bytes, st, &one, err, errlen);
+    rc = decode_one(ctx, data, size, info, o, piece_bytes, st, &one, err, errlen, (uint8_t)lv);
     if (rc != SPDL_HJ_ERR_HANDOFF || !one.ran || piece_bytes == 0) break;
     ctx->handoff_retries++;
   }
@@ -1395,8 +1453,10 @@ int spdl_hj_decode_planes(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
   (void)frame_blocks(info, &fb);  // (the layout was built: the frame is supported)
   const int hmax = fb.grid.hmax, vmax = fb.grid.vmax;
   for (int c = 0; c < info.ncomp; c++) {
-    int w = info.ncomp == 1 ? info.width : (info.width * info.h_samp[c] + hmax - 1) / hmax;
-    int h = info.ncomp == 1 ? info.height : (info.height * info.v_samp[c] + vmax - 1) / vmax;
+    // (the reduced frame's component sizes at a level above 0)
+    const int fw = lowres_side(info.width, lv), fh = lowres_side(info.height, lv);
+    int w = info.ncomp == 1 ? fw : (fw * info.h_samp[c] + hmax - 1) / hmax;
+    int h = info.ncomp == 1 ? fh : (fh * info.v_samp[c] + vmax - 1) / vmax;
     HJ_HIP(hipMemcpy2DAsync(planes[c], (size_t)w,
                             static_cast<const uint8_t*>(W.planes.p) + d.plane_off[c],
                             (size_t)d.plane_stride[c], (size_t)w, (size_t)h,
@@ -1747,6 +1807,8 @@ int spdl_hj_get_param(spdl_hj_ctx* ctx, const char* name, int64_t* value) {
       {"xcd_order", ctx->xcd_order},
       {"handoff_retries", ctx->handoff_retries},
       {"idct_workgroups", ctx->idct_workgroups},
+      {"lowres_images", ctx->lowres_images},
+      {"planes_bytes", ctx->planes_bytes},
       {"fused_workgroups", ctx->fused_workgroups},
       {"generic_workgroups", ctx->generic_workgroups},
       {"entropy_workgroups", ctx->entropy_workgroups},

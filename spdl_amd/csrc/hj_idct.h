@@ -231,5 +231,59 @@ HJ_HD inline void islow_block(int32_t* in, int32_t* out) {
   }
 }
 
+// Reduced-size transforms (FFmpeg's lowres 3, 2, 1: libavcodec/jrevdct.c
+// ff_j_rev_dct1 / 2 / 4 followed by the clipping put), restated.  b: the
+// block's top-left corner, dequantised, natural order, row stride `bs`, DC
+// with the +1024 bias; o: the (8 >> L)^2 pixels, row stride `os`.
+HJ_HD inline int32_t lowres_idct1(int32_t dc) { return clip_u8_opaque((dc + 4) >> 3); }
+
+HJ_HD inline void lowres_idct2(const int32_t* b, int bs, int32_t* o, int os) {
+  const int32_t b00 = b[0] + 4;
+  const int32_t d00 = b00 + b[1], d01 = b00 - b[1];
+  const int32_t d10 = b[bs] + b[bs + 1], d11 = b[bs] - b[bs + 1];
+  o[0] = clip_u8_opaque((d00 + d10) >> 3);
+  o[1] = clip_u8_opaque((d01 + d11) >> 3);
+  o[os] = clip_u8_opaque((d00 - d10) >> 3);
+  o[os + 1] = clip_u8_opaque((d01 - d11) >> 3);
+}
+
+// The even half of jrevdct's 8-point pass on (d0, d2, d4, d6).  jrevdct
+// branches on zero operands with constants of their own:
+//   d6 != 0, d2 != 0   z1 = (d2 + d6) 4433; t2 = z1 - d6 15137; t3 = z1 + d2 6270
+//   d6 != 0, d2 == 0   t2 = -d6 10703; t3 = d6 4433
+//   d6 == 0, d2 != 0   t2 = d2 4433;   t3 = d2 10703
+//   both zero          t2 = t3 = 0
+// The first line gives the other three whenever its operand is zero (4433 +
+// 6270 = 10703) except t2 with d2 == 0, where 15137 - 4433 = 10704 is not
+// 10703: that one case is the select below, the rest is the first line
+// (tests/native/lowres_sweep.cpp holds this against the branches as written).
+HJ_HD inline void lowres_pass4(int32_t d0, int32_t d2, int32_t d4, int32_t d6, int32_t* o) {
+  const int32_t z1 = (d2 + d6) * F0541;
+  const int32_t t2 = d2 ? z1 - d6 * F1847 : -d6 * 10703;
+  const int32_t t3 = z1 + d2 * F0765;
+  // (a left shift of a negative int32 written as the multiplication it is)
+  const int32_t t0 = (d0 + d4) * 8192, t1 = (d0 - d4) * 8192;
+  o[0] = t0 + t3;
+  o[1] = t1 + t2;
+  o[2] = t1 - t2;
+  o[3] = t0 - t3;
+}
+
+HJ_HD inline void lowres_idct4(const int32_t* b, int bs, int32_t* o, int os) {
+  int32_t ws[16], t[4];
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int32_t* p = b + r * bs;
+    lowres_pass4(p[0] + (r == 0 ? 4 : 0), p[1], p[2], p[3], t);
+#pragma unroll
+    for (int k = 0; k < 4; k++) ws[4 * r + k] = sext16((uint32_t)((t[k] + (1 << 10)) >> 11));
+  }
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    lowres_pass4(ws[c], ws[4 + c], ws[8 + c], ws[12 + c], t);
+#pragma unroll
+    for (int k = 0; k < 4; k++) o[k * os + c] = clip_u8_opaque(t[k] >> 18);
+  }
+}
 
 }  // namespace hj

@@ -4835,6 +4835,221 @@ __global__ void __launch_bounds__(kIdctThreads) idct_kernel(const uint32_t* __re
 }
 
 // ---------------------------------------------------------------------------
+// idct_lowres_kernel: the IDCT stage of a submission with reduced-size images
+// (spdl_hj_set_lowres; FFmpeg's lowres 1..3, hj_idct.h lowres_idct4 / 2 / 1)
+// ---------------------------------------------------------------------------
+//
+// A block yields P x P samples, P = 8 >> L, so one thread per block would
+// store 4, 2 or 1 bytes a row.  The levels are organised by output instead: a
+// lane owns 8 consecutive bytes of each of the P plane rows of one block row
+// and fetches the 2^L blocks under them, so every store of every level is 8
+// bytes (uint2) at an 8-byte aligned address, P of them per lane -- the store
+// width of idct_kernel.  A plane's stride is 8 bytes a lane
+// (hj_layout.h lowres_lanes_row): the lanes of a block row tile the stride
+// exactly, blocks past the component's last one are written as zeros, and so
+// the stage writes every byte of every plane it lays out.
+//
+// Read set per block: L = 3 its descriptor alone (the DC is final there);
+// L = 2 / 1 the list entries up to the first whose zig-zag index is above 4 /
+// 24 -- the last index of the 2x2 / 4x4 corner; the lists are in zig-zag order
+// -- of which those in the 4x4 corner are dequantised and scattered into the
+// lane's corner in LDS (word-major like idct_kernel's block: word w of lane t
+// at [w][t], word 16 a dummy for the entries outside the corner).
+//
+// The level is per image, so workgroup-uniform (the flat grid's idct_map).
+// An image of level 0 is transformed as idct_kernel transforms it.
+
+// sq for the reduced levels, per component and zig-zag index: the
+// coefficient's corner word (row * 4 + column; 16 outside the 4x4 corner) |
+// quantiser << 16
+__device__ __forceinline__ void load_dequant_corner(uint32_t (&sq)[kMaxComp][64], const ImageInfo& in,
+                                                    int tid) {
+  for (int k = tid; k < kMaxComp * 64; k += kIdctThreads) {
+    const uint32_t slot = kSlotOrder[k & 63], r = slot >> 3, s = slot & 7u;
+    const uint32_t col = ((s & 3u) << 1) | (s >> 2);  // (kSlotOrder's pairing undone)
+    const uint32_t word = r < 4u && col < 4u ? r * 4u + col : 16u;
+    sq[k >> 6][k & 63] = word | ((uint32_t)in.qt[k >> 6][k & 63] << 16);
+  }
+}
+
+// A block's list as the corner walk reads it: the 16-byte groups from the
+// one its first entry lies in (a run's lists are packed back to back, so a
+// list may start inside a group: entries [lo, lo + count) of the groups), the
+// first NQ of them loaded here -- ahead of any use, so that a lane's blocks
+// have their loads in flight together.
+template <int NQ>
+struct CornerList {
+  const uint4* e4;
+  uint32_t lo, count, n4;
+  uint4 q[NQ];
+};
+template <int NQ>
+__device__ __forceinline__ CornerList<NQ> corner_list(const uint32_t* __restrict__ ents,
+                                                      const uint2 bd, const int64_t coef_off,
+                                                      const int nblocks) {
+  CornerList<NQ> l;
+  const uint32_t cap = (uint32_t)nblocks * 64u, start = bd.x & ~3u;
+  l.lo = bd.x & 3u;
+  l.count = min(bd.y & 0xFFFFu, 63u);
+  l.e4 = reinterpret_cast<const uint4*>(ents + (size_t)coef_off * 64 + start);
+  l.n4 = (l.lo + l.count + 3u) >> 2;
+  if (start > cap - 64u) l.count = l.n4 = 0;  // only an unwritten list (a failed scan)
+#pragma unroll
+  for (int u = 0; u < NQ; u++)
+    l.q[u] = l.n4 ? l.e4[min((uint32_t)u, l.n4 - 1u)] : make_uint4(0u, 0u, 0u, 0u);
+  return l;
+}
+
+// The corner's AC coefficients of list `l` into the lane's LDS words (col: the
+// lane's word 0; stride kIdctThreads words), zeroed first.  ZMAX: the corner's
+// last zig-zag index.  The entries are in zig-zag order, so one test per entry
+// (in the list, index <= ZMAX) leaves out what lies behind the corner, and a
+// trip whose last entry is past ZMAX is the last: most blocks take one trip of
+// NQ groups, every load of it unconditional and issued together.
+template <int ZMAX, int NQ>
+__device__ __forceinline__ void corner_scatter(const CornerList<NQ>& l, const uint32_t* sqc,
+                                               uint32_t* col) {
+#pragma unroll
+  for (int w = 1; w < 16; w++)
+    if (ZMAX > 4 || w == 1 || w == 4 || w == 5) col[w * kIdctThreads] = 0u;
+  for (uint32_t i = 0; i < l.n4; i += NQ) {
+    uint4 q[NQ];
+#pragma unroll
+    for (int u = 0; u < NQ; u++) q[u] = i == 0 ? l.q[u] : l.e4[min(i + u, l.n4 - 1u)];
+#pragma unroll
+    for (int u = 0; u < NQ; u++) {
+      const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+#pragma unroll
+      for (int h = 0; h < 4; h++) {
+        const uint32_t k = 4u * (i + u) + h, zz = w[h] & 63u;
+        const uint32_t qs = sqc[zz];
+        const bool take = k - l.lo < l.count && zz <= (uint32_t)ZMAX;
+        // (the int16 product the sequential decoder stores; outside: the dummy word)
+        col[(take ? (qs & 0xFFFFu) : 16u) * kIdctThreads] = (uint32_t)sext16((w[h] >> 16) * (qs >> 16));
+      }
+    }
+    if ((q[NQ - 1].w & 63u) > (uint32_t)ZMAX) break;
+  }
+}
+
+// One lane of level LV: lane `j` of the image's lanes, components in order,
+// each plane's block rows top to bottom, ceil(bw / 2^LV) lanes to a block row.
+template <int LV>
+__device__ __forceinline__ void lowres_lane(const uint32_t* __restrict__ ents,
+                                            const uint2* __restrict__ bdesc, const ImageDesc& dd,
+                                            const ImageInfo& in, uint8_t* __restrict__ planes,
+                                            const uint32_t (&sq)[kMaxComp][64], uint32_t* col, int j) {
+  constexpr int NB = 1 << LV, P = 8 >> LV;
+  int c = 0, base = 0, lr = 0;
+  for (; c < in.ncomp; c++) {
+    lr = (in.comp_bw[c] + NB - 1) >> LV;
+    const int cnt = lr * in.comp_bh[c];
+    if (j < cnt) break;
+    j -= cnt;
+    base += in.comp_h[c] * in.comp_v[c];
+  }
+  if (c >= in.ncomp) return;  // (the planner counted the same lanes: never)
+  const int by = j / lr, gx = j - by * lr;
+  const int bw = in.comp_bw[c], hc = in.comp_h[c], vc = in.comp_v[c];
+  uint32_t lo[P], hi[P];
+#pragma unroll
+  for (int r = 0; r < P; r++) lo[r] = hi[r] = 0u;
+  // the lane's descriptors, then (levels 1 and 2) the head of every list, all
+  // ahead of the first transform: 16 / 8 entries cover most corners
+  constexpr int ZMAX = LV == 1 ? 24 : 4, NQ = LV == 1 ? 4 : 2;
+  uint2 bd[NB];
+#pragma unroll
+  for (int k = 0; k < NB; k++) {
+    const int bx = min(gx * NB + k, bw - 1);  // (past the last block: its neighbour, unused)
+    // block (bx, by) of component c in the image's MCU order
+    const int jb = in.ncomp == 1 ? by * in.mcux + bx
+                                 : ((by / vc) * in.mcux + bx / hc) * in.bpm + base + (by % vc) * hc +
+                                       bx % hc;
+    bd[k] = bdesc[(size_t)dd.coef_off + jb];
+  }
+  CornerList<NQ> lists[LV == 3 ? 1 : NB];
+  if constexpr (LV != 3) {
+#pragma unroll
+    for (int k = 0; k < NB; k++) lists[k] = corner_list<NQ>(ents, bd[k], dd.coef_off, in.nblocks);
+  }
+#pragma unroll
+  for (int k = 0; k < NB; k++) {
+    if (gx * NB + k >= bw) continue;  // (past the component's last block: zeros)
+    int32_t px[P * P];
+    if constexpr (LV == 3) {
+      px[0] = lowres_idct1(sext16(bd[k].y >> 16));
+    } else {
+      corner_scatter<ZMAX, NQ>(lists[k], sq[c], col);
+      int32_t b[16];
+      b[0] = sext16(bd[k].y >> 16);
+#pragma unroll
+      for (int w = 1; w < 16; w++)
+        b[w] = (LV == 1 || w == 1 || w == 4 || w == 5) ? (int32_t)col[w * kIdctThreads] : 0;
+      if constexpr (LV == 1) lowres_idct4(b, 4, px, 4);
+      else lowres_idct2(b, 4, px, 2);
+    }
+    // its P bytes of each row: bytes [k P, k P + P) of the lane's eight
+#pragma unroll
+    for (int r = 0; r < P; r++)
+#pragma unroll
+      for (int x = 0; x < P; x++) {
+        const int byte = k * P + x;
+        const uint32_t v = (uint32_t)px[r * P + x] << (8 * (byte & 3));
+        if (byte < 4) lo[r] |= v;
+        else hi[r] |= v;
+      }
+  }
+  const int stride = dd.plane_stride[c];
+  uint8_t* dst = planes + dd.plane_off[c] + (size_t)by * P * stride + gx * 8;
+#pragma unroll
+  for (int r = 0; r < P; r++)
+    *reinterpret_cast<uint2*>(dst + (size_t)r * stride) = make_uint2(lo[r], hi[r]);
+}
+
+template <int IDCT>
+__global__ void __launch_bounds__(kIdctThreads) idct_lowres_kernel(
+    const uint32_t* __restrict__ ents, const uint2* __restrict__ bdesc,
+    const ImageDesc* __restrict__ desc, const ImageInfo* __restrict__ infos,
+    uint8_t* __restrict__ planes, const uint32_t* __restrict__ idct_map,
+    const uint8_t* __restrict__ levels) {
+  __shared__ __attribute__((aligned(16))) uint32_t sblk[kBlkWords + 1][kIdctThreads];
+  __shared__ uint32_t sq[kMaxComp][64];
+  const int img = (int)idct_map[blockIdx.x];
+  const ImageInfo& in = infos[img];
+  const ImageDesc& dd = desc[img];
+  const int tile = (int)blockIdx.x - dd.idct_wg0;
+  const int nb = dd.idct_blocks;  // (the image's lanes: hj_layout.h Layout::lowres)
+  const int lv = levels[img];
+  if (in.status != kOk || tile * kIdctThreads >= nb) return;
+  const int j = tile * kIdctThreads + threadIdx.x;
+  uint32_t* b32 = &sblk[0][threadIdx.x];
+  if (lv == 0) {
+    load_dequant<kIdctThreads>(sq, in, threadIdx.x);
+    __syncthreads();
+    if (j >= nb) return;
+    const IdctBlockPos bp = idct_block_pos(in, (uint32_t)j);
+    const int c = bp.c;
+    list_block<kIdctThreads>(ents, bdesc[(size_t)dd.coef_off + j], dd.coef_off, in.nblocks, sq[c],
+                             b32);
+    uint2 rows[8];
+    idct_block_rows<kIdctThreads, IDCT>(b32, rows);
+    const int stride = dd.plane_stride[c];
+    uint8_t* dst = planes + dd.plane_off[c] + (size_t)bp.by * 8 * stride + bp.bx * 8;
+#pragma unroll
+    for (int r = 0; r < 8; r++) *reinterpret_cast<uint2*>(dst + (size_t)r * stride) = rows[r];
+    return;
+  }
+  if (lv < 3) {  // (level 3 reads no list: no table)
+    load_dequant_corner(sq, in, threadIdx.x);
+    __syncthreads();
+  }
+  if (j >= nb) return;
+  if (lv == 1) lowres_lane<1>(ents, bdesc, dd, in, planes, sq, b32, j);
+  else if (lv == 2) lowres_lane<2>(ents, bdesc, dd, in, planes, sq, b32, j);
+  else lowres_lane<3>(ents, bdesc, dd, in, planes, sq, b32, j);
+}
+
+// ---------------------------------------------------------------------------
 // colour conversion (IJG jdcolor.c / jdmerge.c integer tables, SCALEBITS 16)
 // ---------------------------------------------------------------------------
 
@@ -6343,6 +6558,11 @@ hipError_t launch_idct(const BatchBuffers& b, int idct, bool flat, int idct_wgs,
   const dim3 grid = flat ? dim3(idct_wgs) : dim3(max_tiles, b.n);
   HJ_IDCT_KIND(idct_kernel, idct, grid, dim3(kIdctThreads), 0, st, b.ents, b.bdesc, b.desc, b.infos,
                b.planes, flat ? b.idct_map : nullptr, xcd);
+  return hipGetLastError();
+}
+hipError_t launch_idct_lowres(const BatchBuffers& b, int idct, int idct_wgs, hipStream_t st) {
+  HJ_IDCT_KIND(idct_lowres_kernel, idct, dim3(idct_wgs), dim3(kIdctThreads), 0, st, b.ents, b.bdesc,
+               b.desc, b.infos, b.planes, b.idct_map, b.lowres);
   return hipGetLastError();
 }
 hipError_t launch_idct_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int idct,

@@ -39,6 +39,9 @@ struct BatchBuffers {
   // ... or its orientation codes (spdl_hj_set_orients, 0..7) in the same place;
   // transposed: one of them has bit 2, and sws_kernel<true> runs
   bool transposed;
+  // reduced-size levels (spdl_hj_set_lowres): one byte per image behind the
+  // flips; null when every level is 0 -- idct_kernel then runs as ever
+  const uint8_t* lowres;
 };
 
 // parse_kernel + lut_kernel.  host_desc (descriptors, then the work list) and
@@ -55,6 +58,9 @@ hipError_t launch_multiscan(const BatchBuffers& b, hipStream_t st);
 // idct_kernel<idct> (0 simple, 1 islow, 2 kAblIdctNone); xcd: XCD-aware tile order
 hipError_t launch_idct(const BatchBuffers& b, int idct, bool flat, int idct_wgs, int max_blocks,
                        int xcd, hipStream_t st);
+// idct_lowres_kernel<idct> over the flat IDCT grid: every image of a submission
+// with reduced-size levels (b.lowres), the level-0 ones as idct_kernel does
+hipError_t launch_idct_lowres(const BatchBuffers& b, int idct, int idct_wgs, hipStream_t st);
 hipError_t launch_cmyk(const BatchBuffers& b, int64_t max_px, hipStream_t st);
 // Output kernels.  host_status: the slot's pinned status array (device view) or null
 hipError_t launch_csc(const BatchBuffers& b, void* out, const BatchParams& p, int64_t max_px,

@@ -263,7 +263,7 @@ struct Planner {
   // Image i's share of what the front end and the IDCT work on: coefficient
   // lists, planes, segments, destuff chunks, entropy pieces and records, and
   // its workgroups in the flat destuff and IDCT grids (d.idct_blocks is set)
-  void front_end(int i, const FrameBlocks& fb) {
+  void front_end(int i, const FrameBlocks& fb, int lv) {
     ImageDesc& d = L.desc[i];
     const spdl_hj_image_info& p = rq.infos[i];
     const int64_t bytes = rq.sizes[i];
@@ -273,9 +273,11 @@ struct Planner {
     d.coef_off = L.total_blocks;
     L.total_blocks += fb.nblocks;
     for (int c = 0; c < p.ncomp; c++) {
-      d.plane_stride[c] = fb.bw[c] * 8;
+      // (a reduced plane: 8 >> L samples a block, each row padded to 8 bytes
+      // a lane of idct_lowres_kernel, which writes the padding as well)
+      d.plane_stride[c] = lv ? lowres_lanes_row(fb.bw[c], lv) * 8 : fb.bw[c] * 8;
       d.plane_off[c] = L.total_planes;
-      L.total_planes += round_up((int64_t)fb.bw[c] * 8 * fb.bh[c] * 8, 256);
+      L.total_planes += round_up((int64_t)d.plane_stride[c] * fb.bh[c] * (8 >> lv), 256);
     }
     d.seg_cap = (int32_t)(bytes / 2 + 2);
     d.seg_off = L.total_segs;
@@ -472,6 +474,15 @@ struct Planner {
     int crop_rc = SPDL_HJ_OK;
     d.idct_blocks = (int)fb.nblocks;
     d.src = i;
+    // Reduced-size decode: every later step sees the frame FFmpeg's decoder
+    // emits at this level, and the IDCT stage is counted in lanes
+    const int lv = level_of(i);
+    if (lv) {
+      src = views::Rect{0, 0, lowres_side(p.width, lv), lowres_side(p.height, lv)};
+      d.idct_blocks = 0;
+      for (int c = 0; c < p.ncomp; c++) d.idct_blocks += lowres_lanes_row(fb.bw[c], lv) * fb.bh[c];
+      L.lowres_images++;
+    }
     if (rq.views) {
       if (int rc = views_region(i, d, f, fb.grid)) return rc;
     } else if (has_rect) {
@@ -481,9 +492,20 @@ struct Planner {
       else set_region(d, fb.grid, views::mcu_rect(fb.grid, src));
     }
     set_windows(d, f, fb.grid, src);
-    front_end(i, fb);
+    front_end(i, fb, lv);
     if (rq.views) return SPDL_HJ_OK;  // (the outputs are the views': plan_views)
     if (has_rect) L.all_special = false;  // the full-resolution converters read whole planes
+    if (lv) {
+      // (the unscaled converters and the fused kernel address by the file's size)
+      L.all_special = L.fuse_ok = false;
+      // cmyk_kernel addresses by the file's size as well: no reduced RGB-coded
+      // or 4-component frame
+      if (p.ncomp == 4 || p.color == kColorRgb) {
+        if (!rq.plans) return fail(i, SPDL_HJ_ERR_UNSUPPORTED, "lowres of an RGB or 4-component frame");
+        refuse(d, SPDL_HJ_ERR_UNSUPPORTED);
+        return SPDL_HJ_OK;
+      }
+    }
     if (crop_rc) {
       refuse(d, crop_rc);
       return SPDL_HJ_OK;
@@ -518,7 +540,7 @@ struct Planner {
     // sws_kernel nothing, its idct_rgb_kernel tiles stand in the sws fields
     // (finish_ragged numbers them)
     if (rq.ragged && fusable && pl.plan->special && !pl.plan->d.pre &&
-        out.dtype == SPDL_HJ_DTYPE_U8 && !has_rect && !code_of(i) && rq.output_path == 0) {
+        out.dtype == SPDL_HJ_DTYPE_U8 && !has_rect && !code_of(i) && !lv && rq.output_path == 0) {
       d.idct_blocks = 0;
       d.sws_bands = fb.grid.mcuy;
       d.sws_chunks = tiles_x;
@@ -700,6 +722,41 @@ struct Planner {
     return SPDL_HJ_OK;
   }
 
+  // The levels of the submission against its count, values and what else it
+  // asks for; nothing has been planned or written yet
+  int check_lowres() {
+    if (!rq.lowres) return SPDL_HJ_OK;
+    const char* what = nullptr;
+    char buf[96];
+    int any = 0;
+    if (rq.nlowres != rq.n) {
+      snprintf(buf, sizeof(buf), "spdl_hj_set_lowres gave %lld levels for %d images",
+               (long long)rq.nlowres, rq.n);
+      what = buf;
+    }
+    for (int64_t i = 0; !what && i < rq.nlowres; i++) {
+      if (rq.lowres[i] > 3) {
+        snprintf(buf, sizeof(buf), "spdl_hj_set_lowres: level %lld is %d (0 to 3)", (long long)i,
+                 (int)rq.lowres[i]);
+        what = buf;
+      }
+      any |= rq.lowres[i];
+    }
+    if (!what && any) {
+      if (rq.crops) what = "spdl_hj_set_lowres and spdl_hj_set_crops on one submission";
+      else if (rq.views) what = "spdl_hj_set_lowres and views on one submission";
+      else if (rq.out->csc == SPDL_HJ_CSC_JFIF) what = "a reduced-size decode needs csc = swscale";
+    }
+    if (!what) {
+      if (any) L.lowres.assign(rq.lowres, rq.lowres + rq.nlowres);
+      return SPDL_HJ_OK;
+    }
+    res.rc = SPDL_HJ_ERR_INVALID_ARG;
+    snprintf(res.err, sizeof(res.err), "%s", what);
+    return res.rc;
+  }
+  int level_of(int i) const { return L.lowres.empty() ? 0 : L.lowres[i]; }
+
   // One flag per descriptor, once every descriptor stands; none when every
   // flip is 0.  A flipped full-resolution batch takes the generic output
   // kernel (the unscaled converters do not flip).
@@ -797,7 +854,7 @@ struct Planner {
 
 LayoutResult build_layout(const LayoutRequest& rq, Layout& L) {
   Planner P{rq, L};
-  if (P.check_flips() || P.check_ragged()) return P.res;
+  if (P.check_flips() || P.check_ragged() || P.check_lowres()) return P.res;
   L.desc.assign(rq.n, ImageDesc{});
   if (rq.ragged) P.fused_image.assign(rq.n, 0);
   if (rq.views) P.index_views();

@@ -127,7 +127,23 @@ struct Layout {
   // [fused_wgs, sws_wgs): sws_kernel's.
   bool ragged = false;
   int64_t fused_wgs = 0;
+  // Reduced-size decode (spdl_hj_set_lowres): one level 0..3 per image.  Empty
+  // when every level of the submission is 0: such a submission is the path
+  // without the call exactly.  Otherwise idct_lowres_kernel transforms every
+  // image over the flat IDCT grid: ImageDesc::idct_blocks counts its lanes --
+  // the blocks of a level-0 image, lowres_lanes() of any other -- and the
+  // planes, windows and plans of an image with L > 0 are the reduced frame's.
+  std::vector<uint8_t> lowres;
+  int lowres_images = 0;  // images with L > 0
 };
+
+// The frame FFmpeg's decoder emits at lowres L: ceil(x / 2^L) a side
+inline int lowres_side(int x, int lv) { return (x + (1 << lv) - 1) >> lv; }
+// idct_lowres_kernel's lanes of component plane bw x bh blocks at level L > 0:
+// a lane owns 8 bytes of each of the 8 >> L plane rows of one block row --
+// the 2^L blocks under them -- so a block row takes ceil(bw / 2^L) lanes and
+// the plane's stride is 8 bytes a lane
+inline int lowres_lanes_row(int bw, int lv) { return (bw + (1 << lv) - 1) >> lv; }
 
 // What spdl_hj_set_views left for the next submission: the groups, their view
 // arrays copied.  `bad`: the call's own arguments broke a limit (more groups
@@ -151,7 +167,8 @@ struct HeldViews {
 // no output stage (the raw planes surface).  crops (n rectangles) and views
 // are optional and exclude each other.  flips (nflips bytes, SPDL_HJ_FLIP_*):
 // optional, one per image, or with views one per view, the groups
-// concatenated in group order.  orients (norients bytes, 0..7): the same
+// concatenated in group order.  lowres (nlowres bytes, 0..3): optional, one
+// level per image; excludes crops and views.  orients (norients bytes, 0..7): the same
 // places and counts; flips and orients on one request are refused.
 // ragged (n byte offsets into an output of out_bytes bytes): optional, lifts
 // the one-size rule (spdl_hipjpeg.h "ragged batches"); output_path: the
@@ -174,6 +191,9 @@ struct LayoutRequest {
   const int64_t* ragged = nullptr;
   int64_t out_bytes = 0;
   int output_path = 0;
+  // spdl_hj_set_lowres: nlowres levels (0..3), one per image; null: none
+  const uint8_t* lowres = nullptr;
+  int64_t nlowres = 0;
 };
 
 // The chain that runs ahead of a transpose: the output spec describes the

@@ -6,6 +6,8 @@ from ._color import nv12_to_bgr, nv12_to_rgb
 from ._config import CUDAConfig, cuda_config
 from ._convert import to_numpy, to_torch
 from ._image import (
+    DecodeConfig,
+    decode_config,
     decode_image_nvjpeg,
     load_image,
     load_image_batch,
@@ -33,9 +35,11 @@ __all__ = [
     "CPUStorage",
     "CUDABuffer",
     "CUDAConfig",
+    "DecodeConfig",
     "convert_array",
     "cpu_storage",
     "cuda_config",
+    "decode_config",
     "decode_image_hip",
     "decode_image_nvjpeg",
     "get_video_filter_desc",

@@ -13,7 +13,8 @@ from __future__ import annotations
 import logging
 import os
 import warnings
-from collections.abc import Sequence
+from collections.abc import Mapping, Sequence
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -74,6 +75,50 @@ def _ignore_ffmpeg_configs(kwargs: dict) -> None:
                           f"stage does not use; it is ignored", RuntimeWarning, stacklevel=3)
 
 
+@dataclass(frozen=True)
+class DecodeConfig:
+    """The reference's ``spdl.io.DecodeConfig``, the two fields the image path
+    reads: of ``decoder_options`` the GPU decoder honours ``"lowres"``."""
+
+    decoder: str | None = None
+    decoder_options: dict | None = None
+
+
+def decode_config(decoder: str | None = None, decoder_options: dict | None = None) -> DecodeConfig:
+    """``spdl.io.decode_config``: ``decode_config(decoder_options={"lowres": "1"})``
+    asks for FFmpeg's reduced-size decode, here ``lowres=1``."""
+    return DecodeConfig(decoder, decoder_options)
+
+
+def _ffmpeg_configs(kwargs: dict, lowres):
+    """``demux_config`` / ``decode_config`` off ``kwargs``.  Of the decoder's
+    options ``"lowres"`` (a str or an int, FFmpeg's 0..3) is honoured and
+    returned as ``lowres=`` -- which it must equal when both are given; every
+    other option, a decoder name and ``demux_config`` keep the once-only
+    warning of :func:`_ignore_ffmpeg_configs`."""
+    cfg = kwargs.get("decode_config")
+    opts = None if cfg is None else (cfg.get("decoder_options") if isinstance(cfg, Mapping)
+                                     else getattr(cfg, "decoder_options", None))
+    level = None
+    if opts is not None and "lowres" in opts:
+        try:
+            level = int(opts["lowres"])
+        except (TypeError, ValueError):
+            raise ValueError(f"decoder_options['lowres'] = {opts['lowres']!r} is no integer") from None
+        if lowres is not None and lowres != level:
+            raise ValueError(f"lowres={lowres!r} and decode_config's lowres {level} disagree")
+        named = cfg.get("decoder") if isinstance(cfg, Mapping) else getattr(cfg, "decoder", None)
+        if named is None and len(opts) == 1:
+            kwargs.pop("decode_config")  # (nothing in it goes unused: no warning)
+    _ignore_ffmpeg_configs(kwargs)
+    return lowres if level is None else level
+
+
+def _no_crops_with_lowres(levels, crops, out: Output) -> None:
+    if levels is not None and (crops is not None or out.src_crop is not None):
+        raise ValueError("lowres= and a source crop are exclusive")
+
+
 def _alloc_out(cfg: CUDAConfig, shape, dtype) -> CUDABuffer:
     nbytes = int(np.prod(shape)) * (1 if dtype == torch.uint8 else 2)
     if cfg.allocator is None:
@@ -88,14 +133,14 @@ def _alloc_out(cfg: CUDAConfig, shape, dtype) -> CUDABuffer:
 
 
 def _decode(datas: list, out: Output, cfg: CUDAConfig, shape_per_image, batched: bool,
-            dtype=torch.uint8, crops=None, flips=None, orients=None) -> CUDABuffer:
+            dtype=torch.uint8, crops=None, flips=None, orients=None, lowres=None) -> CUDABuffer:
     n = len(datas)
     shape = (n, *shape_per_image) if batched else tuple(shape_per_image)
     buf = _alloc_out(cfg, shape, dtype)
     dec = _lib.thread_decoder(cfg.device_index)
     nbytes = int(np.prod(shape)) * (1 if dtype == torch.uint8 else 2)
     dec.decode_batch(datas, out, buf.data_ptr(), nbytes, stream=_stream(cfg), sync=True,
-                     crops=crops, flips=flips, orients=orients)
+                     crops=crops, flips=flips, orients=orients, lowres=lowres)
     return buf
 
 
@@ -173,6 +218,7 @@ def decode_image_nvjpeg(
     pix_fmt: str = "rgb",
     sync: bool = True,
     scale_algo: str = "lanczos",
+    lowres=None,
 ) -> CUDABuffer:
     """Decode JPEG(s) on the GPU.  Same contract as the reference: a single
     source gives ``[3,H,W]`` (``"rgb"``/``"bgr"``) or ``[H,W,3]``
@@ -183,7 +229,8 @@ def decode_image_nvjpeg(
     the resampling kernel.  The default ``"lanczos"`` is Lanczos-3, the
     kernel of the reference's ``resize_npp`` (NPPI_INTER_LANCZOS,
     src/libspdl/cuda/npp/detail/resize.cpp:36-116); ``"bicubic"`` /
-    ``"bilinear"`` are the CPU path's swscale flags."""
+    ``"bilinear"`` are the CPU path's swscale flags.  ``lowres`` (an addition
+    as well): the reduced-size decode of :func:`load_image_batch`."""
     if device_config is None:
         raise ValueError("device_config must be provided.")
     if scale_algo not in _lib.FILTERS:
@@ -206,17 +253,25 @@ def decode_image_nvjpeg(
                 f"Failed to allocate the output buffer: invalid size {scale_width}x{scale_height}.")
         out = Output(pix_fmt=pix_fmt, resize=True, fit_w=scale_width, fit_h=scale_height,
                      filter=scale_algo)
-        return _decode(datas, out, device_config, _shape(out, scale_width, scale_height), True)
+        levels = None
+        if lowres is not None:
+            levels = _lib.lowres_levels(lowres, [_lib.get_image_info(d) for d in datas], out)
+        return _decode(datas, out, device_config, _shape(out, scale_width, scale_height), True,
+                       lowres=levels)
     data = _read(src)
+    info = _lib.get_image_info(data) if lowres is not None else None
     if scale_width > 0 and scale_height > 0:
         out = Output(pix_fmt=pix_fmt, resize=True, fit_w=scale_width, fit_h=scale_height,
                      filter=scale_algo)
         w, h = scale_width, scale_height
     else:
         out = Output(pix_fmt=pix_fmt)
-        info = _lib.get_image_info(data)
+        info = info or _lib.get_image_info(data)
         w, h = info.width, info.height
-    return _decode([data], out, device_config, _shape(out, w, h), False)
+    levels = None if lowres is None else _lib.lowres_levels(lowres, [info], out)
+    if levels is not None and not out.resize:
+        w, h = _lib.lowres_size(w, h, levels[0])
+    return _decode([data], out, device_config, _shape(out, w, h), False, lowres=levels)
 
 
 def load_image_batch_nvjpeg(
@@ -227,10 +282,11 @@ def load_image_batch_nvjpeg(
     height: int,
     pix_fmt: str = "rgb",
     scale_algo: str = "lanczos",
+    lowres=None,
 ) -> CUDABuffer:
     """Batch load + resize (reference _composite.py:486-524): stretch to
     ``width`` x ``height`` with the ``resize_npp`` kernel (Lanczos-3) unless
-    ``scale_algo`` says otherwise."""
+    ``scale_algo`` says otherwise.  ``lowres``: :func:`load_image_batch`'s."""
     return decode_image_nvjpeg(
         [_read(s) for s in srcs],
         scale_width=width,
@@ -238,6 +294,7 @@ def load_image_batch_nvjpeg(
         device_config=device_config,
         pix_fmt=pix_fmt,
         scale_algo=scale_algo,
+        lowres=lowres,
     )
 
 
@@ -278,6 +335,7 @@ def load_image_batch(
     crops=None,
     flips=None,
     exif_orientation: bool = False,
+    lowres=None,
     **kwargs,
 ):
     """Batch load images into one ``[B,H,W,3]`` buffer with the FFmpeg filter
@@ -314,11 +372,21 @@ def load_image_batch(
     ``height`` are those of the displayed image, a rotated file runs the chain
     sideways, and every image of the batch has one shape.  ``flips`` then act
     on the displayed image.  A ``transpose`` at the end of ``filter_desc``
-    turns every image alike (exclusive with ``exif_orientation``)."""
+    turns every image alike (exclusive with ``exif_orientation``).
+
+    ``lowres``: FFmpeg's reduced-size decode, which the reference reaches
+    through ``decode_config=decode_config(decoder_options={"lowres": "1"})``
+    (honoured here as well; the two must agree).  Level ``L`` in ``1..3``
+    inverse-transforms only the low ``(8 >> L)`` corner of each block: the
+    decoder's frame is ``ceil(w / 2^L) x ceil(h / 2^L)`` and the chain runs on
+    it -- other pixels than the full decode's, for a fraction of the IDCT and
+    output work.  An int for every image, a list per image, or ``"auto"`` (an
+    extension): per image the largest level that keeps the frame no smaller
+    than what the chain scales it to.  Exclusive with source crops."""
     if not srcs:
         raise ValueError("`srcs` must not be empty.")
     storage = kwargs.pop("storage", None)
-    _ignore_ffmpeg_configs(kwargs)
+    lowres = _ffmpeg_configs(kwargs, lowres)
     if kwargs:
         raise TypeError(f"unexpected arguments: {sorted(kwargs)}")
     if filter_desc == _FILTER_DESC_DEFAULT:
@@ -350,7 +418,10 @@ def load_image_batch(
         for i, s in enumerate(srcs):
             try:
                 data = _read(s)
-                arrs.append(_native_planes(dec.decode_planes(data, stream=_stream(cfg)), data))
+                lv = _lib.lowres_levels(lowres if isinstance(lowres, (int, str, type(None)))
+                                        else [lowres[i]], [_lib.get_image_info(data)], Output())
+                arrs.append(_native_planes(dec.decode_planes(data, stream=_stream(cfg),
+                                                             lowres=lv[0] if lv else 0), data))
             except Exception as err:  # reference: log, skip, raise later if strict
                 _LG.error("Failed to load image %d: %s", i, err)
         if strict and len(arrs) != len(srcs):
@@ -402,16 +473,25 @@ def load_image_batch(
     if exif_orientation:
         out, orients = _exif_codes(datas, out, flips)
         flips = None
+    infos = [_lib.get_image_info(d) for d in datas]
+    if lowres is not None and not isinstance(lowres, (int, str)):
+        if len(lowres) != len(srcs):
+            raise ValueError(f"{len(lowres)} lowres levels for {len(srcs)} images")
+        lowres = [lowres[i] for i in keep]
+    levels = _lib.lowres_levels(lowres, infos, out, orients)
+    _no_crops_with_lowres(levels, crops, out)
     src = _src_size(info, crops[0] if crops is not None else out.src_crop)
+    if levels is not None:  # (the chain sees the reduced frame)
+        src = _lib.lowres_size(*src, levels[0])
     ow, oh = _oriented_size(src, out, orients[0] if orients else _lib._orient(out.orient))
     dtype = out.torch_dtype
     if out.pix_fmt == "yuv":
-        shape = _yuv_shape([_lib.get_image_info(d) for d in datas], out, src)
+        shape = _yuv_shape(infos, out, src)
     else:
         shape = _shape(out, ow, oh)
     try:
         buf = _decode(datas, out, cfg, shape, True, dtype=dtype, crops=crops, flips=flips,
-                      orients=orients)
+                      orients=orients, lowres=levels)
     except RuntimeError:
         if strict:
             raise
@@ -422,7 +502,8 @@ def load_image_batch(
                 good.append(_decode([d], out, cfg, shape, True, dtype=dtype,
                                     crops=None if crops is None else [crops[k]],
                                     flips=None if flips is None else [flips[k]],
-                                    orients=None if orients is None else [orients[k]]))
+                                    orients=None if orients is None else [orients[k]],
+                                    lowres=None if levels is None else [levels[k]]))
             except RuntimeError as err:
                 _LG.error("Failed to decode an image: %s", err)
         if not good:
@@ -637,6 +718,7 @@ def load_image_list(
     exif_orientation: bool = False,
     align: int = 256,
     csc: str = "swscale",
+    lowres=None,
 ):
     """Every image at its own size from one submission (an extension, like
     :func:`load_image_views`; include/spdl_hipjpeg.h "ragged batches"): native
@@ -650,7 +732,8 @@ def load_image_list(
     shorter side meets it, torchvision's ``Resize(int)``) -- ``load_image_batch``'s
     ``"pad"`` and ``"crop"`` without the pad and the crop.  A ``filter_desc``
     is any chain ``load_image_batch`` takes.  ``crops``, ``flips``,
-    ``exif_orientation``, ``normalize`` are ``load_image_batch``'s.
+    ``exif_orientation``, ``normalize`` and ``lowres`` are
+    ``load_image_batch``'s; every box is sized from its image's reduced frame.
 
     Returns ``(buffers, image_indices)``: one allocation, every buffer a view
     of it with its image's own shape (``[H,W,3]``, or ``[3,H,W]`` for ``rgb`` /
@@ -671,7 +754,8 @@ def load_image_list(
     if filter_desc is None:
         raise ValueError("load_image_list needs a filter chain")
     n_src = len(srcs)
-    for name, per in (("crops", crops), ("flips", flips)):
+    per_lowres = None if lowres is None or isinstance(lowres, (int, str)) else lowres
+    for name, per in (("crops", crops), ("flips", flips), ("lowres levels", per_lowres)):
         if per is not None and len(per) != n_src:
             raise ValueError(f"{len(per)} {name} for {n_src} images")
     if flips is not None:
@@ -716,14 +800,18 @@ def load_image_list(
         codes = [every if flips is None else flips[k] for k in range(n)]
     out = Output(**{**out.__dict__, "src_crop": None, "flip": None, "orient": None})
     codes = codes if any(codes) else None
-    offsets, sizes, planned = _lib.ragged_layout(infos, out, crops, codes, align)
+    if per_lowres is not None:
+        lowres = [per_lowres[i] for i in keep]
+    levels = _lib.lowres_levels(lowres, infos, out, codes)
+    _no_crops_with_lowres(levels, crops, out)
+    offsets, sizes, planned = _lib.ragged_layout(infos, out, crops, codes, align, lowres=levels)
     esz = 1 if out.torch_dtype == torch.uint8 else 2
     # (every offset and every extent is a multiple of the element size)
     total = _alloc_out(cfg, (max(offsets[n] // esz, 1),), out.torch_dtype)
     dec = _lib.thread_decoder(cfg.device_index)
     status = dec.decode_batch(datas, out, total.data_ptr(), offsets[n], stream=_stream(cfg),
                               sync=True, check=False, crops=crops, orients=codes,
-                              ragged=offsets[:n])
+                              ragged=offsets[:n], lowres=levels)
     from ._convert import to_torch
 
     flat = to_torch(total)
@@ -793,6 +881,7 @@ def load_image(
     pix_fmt: str | None = "rgb24",
     flip=None,
     exif_orientation: bool = False,
+    lowres=None,
     **kwargs,
 ):
     """Single image.  ``filter_desc=None`` returns the decoded planes in the
@@ -806,9 +895,11 @@ def load_image(
     the end of ``filter_desc`` do (exclusive with those).
     ``exif_orientation=True`` (an extension) applies the file's EXIF
     orientation, as in :func:`load_image_batch`; ``flip`` then acts on the
-    displayed image."""
+    displayed image.  ``lowres`` (``0..3`` or ``"auto"``) and a
+    ``decode_config`` with the ``"lowres"`` decoder option: the reduced-size
+    decode of :func:`load_image_batch`."""
     kwargs.pop("name", None)  # only names the source in FFmpeg demux errors
-    _ignore_ffmpeg_configs(kwargs)
+    lowres = _ffmpeg_configs(kwargs, lowres)
     if kwargs:
         raise TypeError(f"unexpected arguments: {sorted(kwargs)}")
     cfg = device_config or _default_config()
@@ -819,7 +910,9 @@ def load_image(
             raise ValueError("flip= and exif_orientation= need a filter chain (filter_desc or "
                              "pix_fmt)")
         dec = _lib.thread_decoder(cfg.device_index)
-        arr = _native_planes(dec.decode_planes(data, stream=_stream(cfg)), data)
+        lv = _lib.lowres_levels(lowres, [_lib.get_image_info(data)], Output())
+        arr = _native_planes(dec.decode_planes(data, stream=_stream(cfg),
+                                               lowres=lv[0] if lv else 0), data)
         if device_config is not None:
             return CUDABuffer(torch.from_numpy(arr).to(f"cuda:{cfg.device_index}"))
         return CPUBuffer(arr)
@@ -834,12 +927,16 @@ def load_image(
         out, (code,) = _exif_codes([data], out, None)
         out = Output(**{**out.__dict__, "orient": code})
     info = _lib.get_image_info(data)
+    levels = _lib.lowres_levels(lowres, [info], out)
+    _no_crops_with_lowres(levels, None, out)
     src = _src_size(info, out.src_crop)
+    if levels is not None:  # (the chain sees the reduced frame)
+        src = _lib.lowres_size(*src, levels[0])
     if out.pix_fmt == "yuv":  # pix_fmt=None, no format node: the frame's planes
         shape = _yuv_shape([info], out, src)
     else:
         shape = _shape(out, *_oriented_size(src, out, _lib._orient(out.orient)))
-    buf = _decode([data], out, cfg, shape, False)
+    buf = _decode([data], out, cfg, shape, False, lowres=levels)
     if device_config is None:
         return _to_host(buf)
     return buf
