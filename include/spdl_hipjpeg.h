@@ -99,8 +99,12 @@ enum spdl_hj_idct { SPDL_HJ_IDCT_SIMPLE = 0, SPDL_HJ_IDCT_ISLOW = 1 };
  * (one context: bicubic/bilinear/lanczos scale + yuvj -> rgb24, BT.601 full
  * range, swscale's chroma siting and fixed-point arithmetic; FilterGraphImpl,
  * src/libspdl/core/detail/ffmpeg/filter_graph.cpp:280-313).  JFIF is IJG
- * libjpeg's integer YCbCr -> RGB with nearest chroma (full resolution only). */
-enum spdl_hj_csc { SPDL_HJ_CSC_SWSCALE = 0, SPDL_HJ_CSC_JFIF = 1 };
+ * libjpeg's integer YCbCr -> RGB with nearest chroma (full resolution only).
+ * TURBO (additive in ABI 7) is libjpeg-turbo's default decoder, what Pillow,
+ * OpenCV and torchvision decode with: islow IDCT, triangle ("fancy") chroma
+ * upsampling and the libjpeg 6b colour tables, full resolution only -- see
+ * "Pillow-exact decode" below. */
+enum spdl_hj_csc { SPDL_HJ_CSC_SWSCALE = 0, SPDL_HJ_CSC_JFIF = 1, SPDL_HJ_CSC_TURBO = 2 };
 
 /* Output specification.  resize == 0: full resolution, every image in the
  * batch must have the same size (but see "ragged batches").  Otherwise the
@@ -528,6 +532,68 @@ int spdl_hj_set_ragged(spdl_hj_ctx* ctx, const int64_t* offsets, int32_t n);
  * component planes it laid out in the workspace. */
 int spdl_hj_set_lowres(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n);
 
+/* ---- Pillow-exact decode (additive in ABI 7: one value of spdl_hj_csc, one
+ * read-only parameter) -----------------------------------------------------------
+ * csc = SPDL_HJ_CSC_TURBO is libjpeg-turbo's decoder at its defaults, full
+ * resolution: for a 1- or 3-component file the output is
+ *   np.asarray(PIL.Image.open(f).convert("RGB"))
+ * byte for byte (Pillow linked against libjpeg-turbo), in any of the four
+ * RGB / BGR layouts; F16 / BF16 normalise those bytes as every output does.
+ * The rules are restated here; no library source is involved.
+ *
+ * 1. IDCT.  islow, whatever spdl_hj_output.idct says: the field is not
+ *    consulted in this mode.
+ *
+ * 2. Upsampling.  Component c is brought to the frame's size by its own ratio
+ *    (hr, vr) = (hmax / h_c, vmax / v_c) from its TRUE plane of
+ *    cw x ch = ceil(W h_c / hmax) x ceil(H v_c / vmax) samples.  A neighbour
+ *    outside that plane is the edge sample, on both axes; the padded columns
+ *    and rows the IDCT wrote behind cw / ch are never neighbours.  With p the
+ *    plane, a and b its rows above and below:
+ *      (1,1)             copy
+ *      (2,1), cw > 2     out[2i]     = (3 p[i] + p[i-1] + 1) >> 2
+ *                        out[2i + 1] = (3 p[i] + p[i+1] + 2) >> 2
+ *      (1,2)             out[2j]     = (3 p + a + 1) >> 2
+ *                        out[2j + 1] = (3 p + b + 2) >> 2
+ *      (2,2), cw > 2     s = 3 p + a (upper output row) or 3 p + b (lower), then
+ *                        out[2i]     = (3 s[i] + s[i-1] + 8) >> 4
+ *                        out[2i + 1] = (3 s[i] + s[i+1] + 7) >> 4
+ *      anything else     box replication, as csc = JFIF: (2,1) and (2,2) with
+ *                        cw <= 2, and the ratios (4,1), (4,2), (1,4) ...
+ *    (with the edge rule the first and last columns of (2,1) are p[0] and
+ *    p[cw-1] unchanged, those of (2,2) (4 s + 8) >> 4 and (4 s + 7) >> 4).  The
+ *    result is cropped to W x H.  The rules apply to every component, luma
+ *    included: a frame whose luma is sampled below its chroma -- (1x1, 2x2,
+ *    2x2) -- is accepted and pinned as well.
+ *
+ * 3. Colour.  With cb, cr centred on 128 and arithmetic right shifts:
+ *      R = Y + ((91881 cr + 32768) >> 16)
+ *      B = Y + ((116130 cb + 32768) >> 16)
+ *      G = Y + ((-22554 cb + 32768 - 46802 cr) >> 16)
+ *    clipped to 0..255 (libjpeg 6b's green table, FIX(0.34414) = 22554; csc =
+ *    JFIF keeps libjpeg 9's 22553).  Gray replicates Y; an RGB-coded frame is a
+ *    copy of its three planes.
+ *
+ * Accepted: plain submissions (one size per batch) and ragged ones
+ * (spdl_hj_set_ragged and spdl_hj_ragged_layout take this csc: files of every
+ * size at native size in one submission); the four RGB / BGR formats; the
+ * three dtypes; baseline, progressive and non-interleaved files, gray, and
+ * every sampling the front end decodes.
+ *
+ * SPDL_HJ_ERR_INVALID_ARG, nothing written: resize != 0; SPDL_HJ_FMT_YUV;
+ * source crops; views; any non-zero flip, orientation code or reduced-size
+ * level.  A 4-component frame is refused with SPDL_HJ_ERR_UNSUPPORTED, as
+ * with csc = JFIF.
+ *
+ * Not pinned: a progressive file whose script leaves low AC coefficients
+ * unrefined (libjpeg smooths block edges there; this decoder does not), and
+ * damaged files.
+ *
+ * One kernel, turbo_rgb_kernel, converts every image of the submission over a
+ * flat grid of 128 x 32 pixel tiles; the read-only parameter
+ * "turbo_workgroups" reports its workgroups in the last submission (0 for any
+ * other csc). */
+
 /* ABI version of the loaded library (== SPDL_HJ_ABI_VERSION). */
 int spdl_hj_abi_version(void);
 
@@ -781,7 +847,9 @@ const char* spdl_hj_stage_name(int32_t i);
  * submission, which chooses between them per image (0 and 0 after a plain
  * submission); "lowres_images" and "planes_bytes" (with the reduced-size
  * decode), the images of the last submission with a level above 0 and the
- * bytes of the component planes it laid out in the workspace.
+ * bytes of the component planes it laid out in the workspace;
+ * "turbo_workgroups" (with the Pillow-exact decode), the workgroups of
+ * turbo_rgb_kernel in the last submission.
  * Builds with -DHJ_ABLATIONS=1 also take "debug_mask" (timing ablations that
  * skip kernel phases; outputs wrong); release builds reject it. */
 int spdl_hj_set_param(spdl_hj_ctx* ctx, const char* name, int64_t value);

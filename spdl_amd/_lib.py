@@ -23,7 +23,7 @@ PIX_FMTS = {"rgb": 0, "bgr": 1, "rgb24": 2, "bgr24": 3, "yuv": 4}
 ASPECT = {None: 0, "none": 0, "decrease": 1, "increase": 2}
 FILTERS = {"bicubic": 0, "bilinear": 1, "lanczos": 2}
 IDCT = {"simple": 0, "islow": 1}
-CSC = {"swscale": 0, "jfif": 1}
+CSC = {"swscale": 0, "jfif": 1, "turbo": 2}
 DTYPE_U8, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
 NORM_DTYPES = {"float16": DTYPE_F16, "bfloat16": DTYPE_BF16}
 
@@ -225,7 +225,10 @@ class Output:
     std: tuple = (0.229, 0.224, 0.225)
     norm_dtype: str = "float16"  # or "bfloat16"
     # "swscale": the reference CPU path's libswscale arithmetic (scale +
-    # yuvj -> rgb24); "jfif": IJG libjpeg tables, nearest chroma (full-res)
+    # yuvj -> rgb24); "jfif": IJG libjpeg tables, nearest chroma (full-res);
+    # "turbo": libjpeg-turbo's default decoder -- islow, triangle chroma
+    # upsampling, 6b colour tables: Pillow's pixels (full-res; ``idct`` is not
+    # consulted; include/spdl_hipjpeg.h "Pillow-exact decode")
     csc: str = "swscale"
     src_crop: tuple | None = None
     flip: int | str | None = None

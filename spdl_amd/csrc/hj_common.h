@@ -140,6 +140,9 @@ static_assert(4 * kSubShare == kSubPool, "four slots share the pool evenly");
 // idct_rgb_kernel workgroup size: one block per thread, so a tile is
 // kFusedThreads / bpm MCUs of one MCU row (host and kernel agree on it)
 constexpr int kFusedThreads = 256;
+// turbo_rgb_kernel's tile (csc = TURBO): 256 threads, each 8 output pixels of
+// two output rows, 16 threads to a row (host and kernel agree on it)
+constexpr int kTurboTileW = 128, kTurboTileH = 32;
 constexpr int kMaxSub = 16;        // 64-entry sub-tables per Huffman table
 constexpr int kEntHiShift = 21;    // value / sub-table index field
 

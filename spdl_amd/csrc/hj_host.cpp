@@ -286,6 +286,7 @@ struct spdl_hj_ctx {
   // ... the fused-eligible images' idct_rgb_kernel workgroups, and those of
   // the generic output kernel (sws_kernel)
   int64_t fused_workgroups = 0, generic_workgroups = 0;
+  int64_t turbo_workgroups = 0;  // turbo_rgb_kernel's in the last submission (csc = TURBO)
   // spdl_hj_set_views: the views of the next batch submission
   HeldViews views;
   // spdl_hj_set_ragged: the images' byte offsets in the next batch submission's output
@@ -641,7 +642,9 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   // full resolution u8 through swscale's unscaled converter: IDCT and
   // conversion in one kernel (output_path 1: the generic sws_kernel, 2:
   // separate IDCT + rgb_unscaled_kernel)
-  const int idct_kind = (abl & kAblIdctNone) ? 2 : out->idct;
+  // (csc = TURBO is libjpeg-turbo's default decoder: islow, whatever the spec's idct says)
+  const bool turbo = !sub.planes_only && out->csc == SPDL_HJ_CSC_TURBO;
+  const int idct_kind = (abl & kAblIdctNone) ? 2 : turbo ? SPDL_HJ_IDCT_ISLOW : out->idct;
   // (the planar output, SPDL_HJ_FMT_YUV, has one kernel of its own)
   const bool yuv = swscale && out->pix_fmt == SPDL_HJ_FMT_YUV;
   const bool fast_rgb = swscale && !yuv && L.all_special && out->dtype == SPDL_HJ_DTYPE_U8 &&
@@ -654,6 +657,7 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   // image) grid there, it costs nothing -- profiles/r18/ragged)
   const int ragged_fused = L.ragged ? (int)L.fused_wgs : 0;
   ctx->idct_workgroups = ctx->fused_workgroups = ctx->generic_workgroups = 0;
+  ctx->turbo_workgroups = 0;
   ctx->entropy_workgroups = B.nwork;
   ctx->lowres_images = L.lowres_images;
   ctx->planes_bytes = L.total_planes;
@@ -685,7 +689,15 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   mark(ctx, slot, 6, st);
   if (!sub.planes_only && !(abl & kAblNoOutput)) {
     const int sws_wgs = (int)L.sws_wgs, hs_wgs = (int)L.hs_wgs;
-    if (by_views) {
+    if (turbo) {
+      // one flat launch over every image's own tiles, plain and ragged alike
+      // (an image's box and offset are its descriptor's).  Every image has at
+      // least one tile -- a box is 1 x 1 or larger, a refused image has the one
+      // workgroup of refuse() -- so sws_wgs >= n > 0 and tile 0 of each image
+      // writes its status into hstat, as in the ragged swscale launch below
+      if (sws_wgs > 0) HJ_HIP(launch_turbo_rgb(B, sub.out_dev, bp, sws_wgs, hstat, st));
+      ctx->turbo_workgroups = sws_wgs;
+    } else if (by_views) {
       // once per group: its chain's parameters, its buffer, its slice of the
       // flat sws grid (hscale_kernel, which takes no parameters of the chain,
       // runs once over every group's pre-pass rows)
@@ -825,6 +837,7 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
   const int64_t idct_wgs = ctx->idct_workgroups;  // (the batch's, not this re-decode's)
   const int64_t ent_wgs = ctx->entropy_workgroups;
   const int64_t fused_wgs = ctx->fused_workgroups, generic_wgs = ctx->generic_workgroups;
+  const int64_t turbo_wgs = ctx->turbo_workgroups;
   const int64_t lowres_images = ctx->lowres_images, planes_bytes = ctx->planes_bytes;
   rc = run_pipeline(ctx, *s, L,
                     {r.bytes, r.len, 1, &r.out, r.out_dev + item.out_off, item.out_bytes, xs, 1,
@@ -834,6 +847,7 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
   ctx->entropy_workgroups = ent_wgs;
   ctx->fused_workgroups = fused_wgs;
   ctx->generic_workgroups = generic_wgs;
+  ctx->turbo_workgroups = turbo_wgs;
   ctx->lowres_images = lowres_images;
   ctx->planes_bytes = planes_bytes;
   ctx->last_ticket = last;
@@ -866,7 +880,7 @@ int take_crops(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, std::vector<s
             held->size(), n);
     return SPDL_HJ_ERR_INVALID_ARG;
   }
-  if (out && out->csc == SPDL_HJ_CSC_JFIF) {
+  if (out && out->csc != SPDL_HJ_CSC_SWSCALE) {
     set_err(err, errlen, "a source crop needs csc = swscale");
     return SPDL_HJ_ERR_INVALID_ARG;
   }
@@ -1811,6 +1825,7 @@ int spdl_hj_get_param(spdl_hj_ctx* ctx, const char* name, int64_t* value) {
       {"planes_bytes", ctx->planes_bytes},
       {"fused_workgroups", ctx->fused_workgroups},
       {"generic_workgroups", ctx->generic_workgroups},
+      {"turbo_workgroups", ctx->turbo_workgroups},
       {"entropy_workgroups", ctx->entropy_workgroups},
   };
   for (const auto& t : tab)

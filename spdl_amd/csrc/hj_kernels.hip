@@ -30,6 +30,7 @@
 #include "hj_idct.h"
 #include "hj_launch.h"
 #include "hj_sws_tile.h"
+#include "hj_upsample.h"
 
 namespace hj {
 
@@ -6496,6 +6497,245 @@ hipError_t launch_nv12(const uint8_t* src, uint8_t* dst, int frames, int height,
 }
 
 // ---------------------------------------------------------------------------
+// turbo_rgb_kernel: csc = TURBO (spdl_hipjpeg.h "Pillow-exact decode") -- the
+// islow planes through libjpeg-turbo's per-component upsampling and 6b colour
+// tables (hj_upsample.h) into the caller's layout, at full resolution.
+//
+// Grid: flat over (image, tile) through sws_map (workgroup g is tile
+// g - sws_wg0 of image sws_map[g]; the planner counts an image's tiles from its
+// own size, ImageDesc::sws_bands x sws_chunks of kTurboTileW x kTurboTileH
+// pixels), so a plain and a ragged submission are one launch each.  A thread
+// owns 8 consecutive pixels of two output rows -- one chroma row under a
+// vertical ratio of 2, whose triple products serve both rows.  Planes are read
+// as aligned words (a neighbour sample from the neighbouring word, clamped at
+// the plane's true edge); a row segment leaves as dwords from the first
+// 4-byte boundary on, with byte stores for the head and tail: a row of odd
+// width and a ragged offset start anywhere, and a ragged neighbour may start
+// at the next byte, so no byte outside the segment is written.  Each
+// component's rule is uniform over the image (a scalar branch).
+// ---------------------------------------------------------------------------
+
+typedef uint32_t hj_u32x2a __attribute__((ext_vector_type(2), aligned(4)));
+
+// N dwords to a 4-byte aligned address, 16 bytes at a time
+template <int N>
+__device__ __forceinline__ void store_words(uint8_t* q, const uint32_t (&w)[N]) {
+#pragma unroll
+  for (int i = 0; i + 4 <= N; i += 4) {
+    hj_u32x4a v;
+    v.x = w[i];
+    v.y = w[i + 1];
+    v.z = w[i + 2];
+    v.w = w[i + 3];
+    *reinterpret_cast<hj_u32x4a*>(q + 4 * i) = v;
+  }
+  if constexpr (N % 4 >= 2) {
+    constexpr int j = N / 4 * 4;
+    hj_u32x2a v;
+    v.x = w[j];
+    v.y = w[j + 1];
+    *reinterpret_cast<hj_u32x2a*>(q + 4 * j) = v;
+  }
+  if constexpr (N % 2 == 1) *reinterpret_cast<uint32_t*>(q + 4 * (N - 1)) = w[N - 1];
+}
+
+// Bytes [K, nbytes) of the byte stream b, one store each (every index a
+// constant: the words stay in registers)
+template <int K, int NW>
+__device__ __forceinline__ void store_bytes(uint8_t* dst, const uint32_t (&b)[NW], int nbytes) {
+  if constexpr (K < 4 * NW) {
+    if (K < nbytes) dst[K] = (uint8_t)(b[K >> 2] >> (8 * (K & 3)));
+    store_bytes<K + 1, NW>(dst, b, nbytes);
+  }
+}
+
+// The first nbytes (<= 4 NW) of the byte stream b to dst, of any alignment,
+// and nothing else.  A whole segment: the bytes up to the first 4-byte
+// boundary, NW - 1 (or NW) realigned dwords, the bytes behind them.  A partial
+// one (the last of a row whose width is no multiple of 8): bytes.
+template <int NW>
+__device__ __forceinline__ void store_run(uint8_t* dst, const uint32_t (&b)[NW], int nbytes) {
+  const uint32_t mis = (uint32_t)reinterpret_cast<uintptr_t>(dst) & 3u;
+  if (nbytes == 4 * NW) {
+    if (mis == 0) {
+      store_words<NW>(dst, b);
+      return;
+    }
+    const uint32_t head = 4u - mis;
+#pragma unroll
+    for (uint32_t k = 0; k < 3; k++)
+      if (k < head) dst[k] = (uint8_t)(b[0] >> (8 * k));
+    uint32_t m[NW - 1];
+#pragma unroll
+    for (int j = 0; j < NW - 1; j++) m[j] = __builtin_amdgcn_alignbyte(b[j + 1], b[j], head);
+    store_words<NW - 1>(dst + head, m);
+    const uint32_t tail = b[NW - 1] >> (8 * head);
+    uint8_t* q = dst + head + 4 * (NW - 1);
+#pragma unroll
+    for (uint32_t k = 0; k < 3; k++)
+      if (k < mis) q[k] = (uint8_t)(tail >> (8 * k));
+    return;
+  }
+  store_bytes<0, NW>(dst, b, nbytes);
+}
+
+// (x / 255 - mean) / std as store_rgb has it, to f16 / bf16 bits
+__device__ __forceinline__ uint32_t turbo_norm(int v, float mean, float sd, int dtype) {
+  float f = __fdiv_rn((float)v, 255.0f);
+  f = __fsub_rn(f, mean);
+  f = __fdiv_rn(f, sd);
+  return to_f16_bits(f, dtype);
+}
+
+// One row segment of a thread: 8 pixels, c0 / c1 / c2 in the output's channel
+// order, npx of them inside the frame, to row y from column x0 of an image
+// whose first element is `base`
+__device__ __forceinline__ void turbo_store_row(void* out, int64_t base, const BatchParams& p,
+                                                int W, int H, int x0, int y, int npx,
+                                                const int (&c0)[8], const int (&c1)[8],
+                                                const int (&c2)[8]) {
+  const bool planar = p.pix_fmt == 0 || p.pix_fmt == 1;
+  const int64_t pl = (int64_t)W * H, at = (int64_t)y * W + x0;
+  if (p.dtype == 0) {
+    uint8_t* o = static_cast<uint8_t*>(out) + base;
+    if (planar) {
+      uint32_t b[3][2];
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        b[0][h] = (uint32_t)c0[4 * h] | (uint32_t)c0[4 * h + 1] << 8 | (uint32_t)c0[4 * h + 2] << 16 |
+                  (uint32_t)c0[4 * h + 3] << 24;
+        b[1][h] = (uint32_t)c1[4 * h] | (uint32_t)c1[4 * h + 1] << 8 | (uint32_t)c1[4 * h + 2] << 16 |
+                  (uint32_t)c1[4 * h + 3] << 24;
+        b[2][h] = (uint32_t)c2[4 * h] | (uint32_t)c2[4 * h + 1] << 8 | (uint32_t)c2[4 * h + 2] << 16 |
+                  (uint32_t)c2[4 * h + 3] << 24;
+      }
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) store_run<2>(o + ch * pl + at, b[ch], npx);
+    } else {
+      // 8 pixels x 3 bytes: four pixels make three dwords
+      uint32_t b[6];
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const int k = 4 * h;
+        b[3 * h] = (uint32_t)c0[k] | (uint32_t)c1[k] << 8 | (uint32_t)c2[k] << 16 |
+                   (uint32_t)c0[k + 1] << 24;
+        b[3 * h + 1] = (uint32_t)c1[k + 1] | (uint32_t)c2[k + 1] << 8 | (uint32_t)c0[k + 2] << 16 |
+                       (uint32_t)c1[k + 2] << 24;
+        b[3 * h + 2] = (uint32_t)c2[k + 2] | (uint32_t)c0[k + 3] << 8 | (uint32_t)c1[k + 3] << 16 |
+                       (uint32_t)c2[k + 3] << 24;
+      }
+      store_run<6>(o + at * 3, b, npx * 3);
+    }
+    return;
+  }
+  uint8_t* o = static_cast<uint8_t*>(out) + base * 2;
+  if (planar) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+      uint32_t b[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int va = ch == 0 ? c0[2 * k] : ch == 1 ? c1[2 * k] : c2[2 * k];
+        const int vb = ch == 0 ? c0[2 * k + 1] : ch == 1 ? c1[2 * k + 1] : c2[2 * k + 1];
+        b[k] = turbo_norm(va, p.mean[ch], p.std[ch], p.dtype) |
+               turbo_norm(vb, p.mean[ch], p.std[ch], p.dtype) << 16;
+      }
+      store_run<4>(o + (ch * pl + at) * 2, b, npx * 2);
+    }
+  } else {
+    // 8 pixels x 3 halves: two pixels make three dwords
+    uint32_t b[12];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      uint32_t e[6];
+      e[0] = turbo_norm(c0[2 * k], p.mean[0], p.std[0], p.dtype);
+      e[1] = turbo_norm(c1[2 * k], p.mean[1], p.std[1], p.dtype);
+      e[2] = turbo_norm(c2[2 * k], p.mean[2], p.std[2], p.dtype);
+      e[3] = turbo_norm(c0[2 * k + 1], p.mean[0], p.std[0], p.dtype);
+      e[4] = turbo_norm(c1[2 * k + 1], p.mean[1], p.std[1], p.dtype);
+      e[5] = turbo_norm(c2[2 * k + 1], p.mean[2], p.std[2], p.dtype);
+      b[3 * k] = e[0] | e[1] << 16;
+      b[3 * k + 1] = e[2] | e[3] << 16;
+      b[3 * k + 2] = e[4] | e[5] << 16;
+    }
+    store_run<12>(o + at * 6, b, npx * 6);
+  }
+}
+
+// One output row of a thread from its three components' samples: the colour
+// model, the channel order, the store
+__device__ __forceinline__ void turbo_row(void* out, const ImageDesc& dd, const BatchParams& p,
+                                          int x0, int y, const int (&v0)[8], const int (&v1)[8],
+                                          const int (&v2)[8]) {
+  const bool swap = p.pix_fmt == 1 || p.pix_fmt == 3;
+  int c0[8], c1[8], c2[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    int rgb[3];
+    if (dd.ncomp == 1) {
+      rgb[0] = rgb[1] = rgb[2] = v0[k];
+    } else if (dd.color == kColorRgb) {  // an RGB-coded frame: a copy of its planes
+      rgb[0] = v0[k];
+      rgb[1] = v1[k];
+      rgb[2] = v2[k];
+    } else {
+      up::ycc_rgb(v0[k], v1[k], v2[k], rgb);
+    }
+    c0[k] = swap ? rgb[2] : rgb[0];
+    c1[k] = rgb[1];
+    c2[k] = swap ? rgb[0] : rgb[2];
+  }
+  turbo_store_row(out, dd.out_off, p, dd.ow, dd.oh, x0, y, min(8, dd.ow - x0), c0, c1, c2);
+}
+
+__global__ void __launch_bounds__(256) turbo_rgb_kernel(const uint8_t* __restrict__ planes,
+                                                        const ImageDesc* __restrict__ desc,
+                                                        const ImageInfo* __restrict__ infos,
+                                                        void* __restrict__ out, const BatchParams p,
+                                                        int32_t* __restrict__ host_status,
+                                                        const uint32_t* __restrict__ sws_map) {
+  const int img = (int)sws_map[blockIdx.x], tid = threadIdx.x;
+  const ImageDesc& dd = desc[img];
+  const int t = (int)blockIdx.x - dd.sws_wg0;
+  const ImageInfo& in = infos[img];
+  if (host_status && t == 0 && tid == 0) host_status[img] = in.status;
+  if (in.status != kOk || dd.refuse) return;
+  const int W = dd.ow, H = dd.oh;
+  const int ty = t / dd.sws_chunks, tx = t - ty * dd.sws_chunks;
+  const int x0 = tx * kTurboTileW + (tid & 15) * 8;
+  const int y0 = ty * kTurboTileH + (tid >> 4) * 2;
+  if (x0 >= W || y0 >= H) return;
+  // the ratios, from the sampling factors the planner laid the planes out by
+  int hmax = 1, vmax = 1;
+  if (dd.ncomp > 1) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      hmax = max(hmax, dd.h_samp[c]);
+      vmax = max(vmax, dd.v_samp[c]);
+    }
+  }
+  int v[3][2][8];
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    if (c < dd.ncomp) {
+      const int hr = dd.ncomp > 1 ? hmax / dd.h_samp[c] : 1;
+      const int vr = dd.ncomp > 1 ? vmax / dd.v_samp[c] : 1;
+      const int cw = dd.win_w[c], ch = dd.win_h[c];
+      up::run8x2(planes + dd.plane_off[c], dd.plane_stride[c], cw, ch, up::mode_of(hr, vr, cw), hr,
+                 vr, x0, y0, v[c][0], v[c][1]);
+    } else {  // (gray: every channel is Y)
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        v[c][0][k] = v[0][0][k];
+        v[c][1][k] = v[0][1][k];
+      }
+    }
+  }
+  turbo_row(out, dd, p, x0, y0, v[0][0], v[1][0], v[2][0]);
+  if (y0 + 1 < H) turbo_row(out, dd, p, x0, y0 + 1, v[0][1], v[1][1], v[2][1]);
+}
+
+// ---------------------------------------------------------------------------
 // launchers (host side, same TU; declared in hj_launch.h)
 // ---------------------------------------------------------------------------
 
@@ -6600,6 +6840,12 @@ hipError_t launch_csc(const BatchBuffers& b, void* out, const BatchParams& p, in
   const int gx = (int)std::min<int64_t>((max_px + 255) / 256, 4096);
   hipLaunchKernelGGL(csc_kernel, dim3(gx, b.n), dim3(256), 0, st, b.planes, b.desc, b.infos, out, p,
                      host_status);
+  return hipGetLastError();
+}
+hipError_t launch_turbo_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int turbo_wgs,
+                            int32_t* host_status, hipStream_t st) {
+  hipLaunchKernelGGL(turbo_rgb_kernel, dim3(turbo_wgs), dim3(256), 0, st, b.planes, b.desc, b.infos,
+                     out, p, host_status, b.sws_map);
   return hipGetLastError();
 }
 hipError_t launch_rgb_unscaled(const BatchBuffers& b, void* out, const BatchParams& p,

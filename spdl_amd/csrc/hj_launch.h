@@ -65,6 +65,10 @@ hipError_t launch_cmyk(const BatchBuffers& b, int64_t max_px, hipStream_t st);
 // Output kernels.  host_status: the slot's pinned status array (device view) or null
 hipError_t launch_csc(const BatchBuffers& b, void* out, const BatchParams& p, int64_t max_px,
                       int32_t* host_status, hipStream_t st);
+// turbo_rgb_kernel (csc = TURBO) over its flat grid: every image's own tiles, the first
+// turbo_wgs workgroups of sws_map (Layout::sws_wgs), plain and ragged submissions alike
+hipError_t launch_turbo_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int turbo_wgs,
+                            int32_t* host_status, hipStream_t st);
 hipError_t launch_rgb_unscaled(const BatchBuffers& b, void* out, const BatchParams& p,
                                int64_t max_px, int32_t* host_status, hipStream_t st);
 hipError_t launch_idct_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int idct,

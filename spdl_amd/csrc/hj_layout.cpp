@@ -91,7 +91,7 @@ int geometry(int w, int h, const spdl_hj_output* o, Geom* g, int hs, int vs) {
 }
 
 bool valid_output(const spdl_hj_output* o) {
-  // the JFIF conversion has no scaler: full resolution only
+  // the JFIF and TURBO conversions have no scaler: full resolution only
   // ... and the planar output is u8 planes of swscale's scaler alone
   if (o && o->pix_fmt == SPDL_HJ_FMT_YUV &&
       (o->dtype != SPDL_HJ_DTYPE_U8 || o->csc != SPDL_HJ_CSC_SWSCALE))
@@ -99,7 +99,8 @@ bool valid_output(const spdl_hj_output* o) {
   return o && o->pix_fmt >= 0 && o->pix_fmt <= SPDL_HJ_FMT_YUV && (o->dtype >= 0 && o->dtype <= 2) &&
          (o->idct == 0 || o->idct == 1) && (o->filter >= 0 && o->filter <= 2) &&
          o->aspect >= 0 && o->aspect <= 2 &&
-         (o->csc == SPDL_HJ_CSC_SWSCALE || (o->csc == SPDL_HJ_CSC_JFIF && !o->resize));
+         (o->csc == SPDL_HJ_CSC_SWSCALE ||
+          ((o->csc == SPDL_HJ_CSC_JFIF || o->csc == SPDL_HJ_CSC_TURBO) && !o->resize));
 }
 
 views::Frame frame_of(const spdl_hj_image_info& p) {
@@ -355,6 +356,15 @@ struct Planner {
       else if (fw != box.ow || fh != box.oh) return {SPDL_HJ_ERR_INVALID_ARG, kAtSize, nullptr};
     }
     if (!rq.plans || out.csc == SPDL_HJ_CSC_JFIF) return {SPDL_HJ_OK, kPlaced, nullptr};
+    if (out.csc == SPDL_HJ_CSC_TURBO) {
+      // no plan: turbo_rgb_kernel's tiles of this image's own box, in the flat
+      // grid the sws fields map (rows of tiles x tiles per row)
+      d.sws_wg0 = (int32_t)L.sws_wgs;
+      d.sws_bands = (g.oh + kTurboTileH - 1) / kTurboTileH;
+      d.sws_chunks = (g.ow + kTurboTileW - 1) / kTurboTileW;
+      L.sws_wgs += (int64_t)d.sws_bands * d.sws_chunks;
+      return {SPDL_HJ_OK, kPlaced, nullptr};
+    }
     int hs, vs, mode;
     rc = views::chroma_shifts(f, &hs, &vs);
     if (out.pix_fmt == SPDL_HJ_FMT_YUV) {
@@ -453,6 +463,8 @@ struct Planner {
       // libjpeg's JFIF conversion has no CMYK -> RGB; the K transform
       // (FFmpeg's, cmyk_kernel) runs unless the planes are YCbCr + K
       if (out.csc == SPDL_HJ_CSC_JFIF) return fail(i, SPDL_HJ_ERR_UNSUPPORTED, "CMYK with csc=jfif");
+      // ... and csc = TURBO is pinned for 1- and 3-component files alone
+      if (out.csc == SPDL_HJ_CSC_TURBO) return fail(i, SPDL_HJ_ERR_UNSUPPORTED, "CMYK with csc=turbo");
       if (p.color != kColorYcbcrk) L.cmyk_px = std::max(L.cmyk_px, (int64_t)p.width * p.height);
     }
     for (int c = 0; c < p.ncomp; c++) {
@@ -662,7 +674,7 @@ struct Planner {
       }
       any = any || rq.flips[i];
     }
-    if (any && rq.out->csc == SPDL_HJ_CSC_JFIF) {
+    if (any && rq.out->csc != SPDL_HJ_CSC_SWSCALE) {
       snprintf(res.err, sizeof(res.err), "a flip needs csc = swscale");
       return res.rc;
     }
@@ -714,7 +726,7 @@ struct Planner {
       }
       any = any || c;
     }
-    if (any && rq.out->csc == SPDL_HJ_CSC_JFIF) {
+    if (any && rq.out->csc != SPDL_HJ_CSC_SWSCALE) {
       snprintf(res.err, sizeof(res.err), "an orientation needs csc = swscale");
       return res.rc;
     }
@@ -745,7 +757,7 @@ struct Planner {
     if (!what && any) {
       if (rq.crops) what = "spdl_hj_set_lowres and spdl_hj_set_crops on one submission";
       else if (rq.views) what = "spdl_hj_set_lowres and views on one submission";
-      else if (rq.out->csc == SPDL_HJ_CSC_JFIF) what = "a reduced-size decode needs csc = swscale";
+      else if (rq.out->csc != SPDL_HJ_CSC_SWSCALE) what = "a reduced-size decode needs csc = swscale";
     }
     if (!what) {
       if (any) L.lowres.assign(rq.lowres, rq.lowres + rq.nlowres);
@@ -756,6 +768,20 @@ struct Planner {
     return res.rc;
   }
   int level_of(int i) const { return L.lowres.empty() ? 0 : L.lowres[i]; }
+
+  // csc = TURBO is the whole frame as stored (spdl_hipjpeg.h "Pillow-exact
+  // decode"): no source crop and no views; flips, orientations and levels are
+  // refused by their own checks, a resize and the planar output by valid_output
+  int check_turbo() {
+    if (rq.out->csc != SPDL_HJ_CSC_TURBO) return SPDL_HJ_OK;
+    const char* what = nullptr;
+    if (rq.crops) what = "a source crop needs csc = swscale";
+    else if (rq.views) what = "views need csc = swscale";
+    if (!what) return SPDL_HJ_OK;
+    res.rc = SPDL_HJ_ERR_INVALID_ARG;
+    snprintf(res.err, sizeof(res.err), "%s", what);
+    return res.rc;
+  }
 
   // One flag per descriptor, once every descriptor stands; none when every
   // flip is 0.  A flipped full-resolution batch takes the generic output
@@ -779,7 +805,7 @@ struct Planner {
     if (rq.views) what = "views and spdl_hj_set_ragged on one submission";
     else if (!rq.plans) what = "spdl_hj_set_ragged needs an output stage";
     else if (rq.out->pix_fmt == SPDL_HJ_FMT_YUV) what = "no ragged planar YUV output";
-    else if (rq.out->csc != SPDL_HJ_CSC_SWSCALE) what = "a ragged submission needs csc = swscale";
+    else if (rq.out->csc == SPDL_HJ_CSC_JFIF) what = "a ragged submission needs csc = swscale or turbo";
     const int64_t esz = rq.out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
     for (int i = 0; i < rq.n && !what; i++)
       if (rq.ragged[i] < 0 || rq.ragged[i] % esz)
@@ -854,7 +880,7 @@ struct Planner {
 
 LayoutResult build_layout(const LayoutRequest& rq, Layout& L) {
   Planner P{rq, L};
-  if (P.check_flips() || P.check_ragged() || P.check_lowres()) return P.res;
+  if (P.check_flips() || P.check_ragged() || P.check_lowres() || P.check_turbo()) return P.res;
   L.desc.assign(rq.n, ImageDesc{});
   if (rq.ragged) P.fused_image.assign(rq.n, 0);
   if (rq.views) P.index_views();
@@ -888,9 +914,14 @@ int ragged_layout(const spdl_hj_image_info* infos, int n, const spdl_hj_output* 
   if (!infos || n < 0 || !valid_output(out) || !offsets || !ow || !oh || !status)
     return SPDL_HJ_ERR_INVALID_ARG;
   const int64_t esz = out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
-  if (out->pix_fmt == SPDL_HJ_FMT_YUV || out->csc != SPDL_HJ_CSC_SWSCALE || align_bytes < esz ||
+  if (out->pix_fmt == SPDL_HJ_FMT_YUV || out->csc == SPDL_HJ_CSC_JFIF || align_bytes < esz ||
       align_bytes % esz)
     return SPDL_HJ_ERR_INVALID_ARG;
+  // csc = TURBO is the whole frame as stored: no crop, no orientation code
+  if (out->csc == SPDL_HJ_CSC_TURBO)
+    for (int i = 0; i < n; i++)
+      if ((crops && !rect_is_none(crops[i])) || (orients && orients[i]))
+        return SPDL_HJ_ERR_INVALID_ARG;
   int64_t end = 0;
   for (int i = 0; i < n; i++) {
     const spdl_hj_image_info& p = infos[i];

@@ -319,6 +319,60 @@ def _to_host(buf: CUDABuffer, storage=None) -> CPUBuffer:
     return transfer_buffer_cpu(buf, storage=storage)
 
 
+_LOAD_CSC = ("swscale", "turbo")
+
+
+def _check_csc(csc: str, *, width=None, height=None, crops=None, flips=None,
+               exif_orientation: bool = False, lowres=None, pix_fmt="rgb24") -> None:
+    """``csc=`` of the ``load_image*`` functions, held before anything is read
+    or submitted.  ``"turbo"`` is the whole frame at its own size
+    (include/spdl_hipjpeg.h "Pillow-exact decode"): no scale, crop, flip,
+    orientation or reduced-size level (all-zero levels are none), and an RGB
+    ``pix_fmt``.  These functions take ``"swscale"`` and ``"turbo"``;
+    ``"jfif"`` stays with :class:`Output` and the ``Decoder``."""
+    if csc not in _LOAD_CSC:
+        raise ValueError(f"csc must be one of {list(_LOAD_CSC)}, not {csc!r}")
+    if csc != "turbo":
+        return
+    bad = None
+    if width is not None or height is not None:
+        bad = "width= / height= (it does not scale)"
+    elif crops is not None:
+        bad = "crops="
+    elif flips is not None:
+        bad = "flips="
+    elif exif_orientation:
+        bad = "exif_orientation="
+    elif isinstance(lowres, str) or np.any(np.asarray(0 if lowres is None else lowres) != 0):
+        bad = "lowres="
+    elif pix_fmt is None:
+        bad = "pix_fmt=None (it converts to RGB)"
+    if bad:
+        raise ValueError(f"csc='turbo' is the full-resolution decode alone: it takes no {bad}")
+
+
+def _csc_pix_fmt(filter_desc, pix_fmt):
+    """The ``pix_fmt`` :func:`_check_csc` judges: none without a chain; the
+    argument with the default chain; with a chain of the caller's the chain
+    decides (its format node, else ``pix_fmt``), and :func:`_with_csc` holds
+    the parsed result."""
+    if filter_desc is None:
+        return None
+    return pix_fmt if filter_desc == _FILTER_DESC_DEFAULT else "rgb24"
+
+
+def _with_csc(out: Output, csc: str) -> Output:
+    """``out`` converting with ``csc``; a chain ``"turbo"`` cannot run (a scale,
+    pad, crop, flip or transpose node, no format) is refused here."""
+    if csc == "swscale":
+        return out
+    if csc == "turbo" and (out.resize or out.src_crop is not None or out.flip is not None or
+                           out.orient is not None or out.pix_fmt == "yuv"):
+        raise ValueError("csc='turbo' is the full-resolution decode alone: filter_desc may hold "
+                         "a format node and nothing else")
+    return Output(**{**out.__dict__, "csc": csc})
+
+
 def load_image_batch(
     srcs,
     *,
@@ -336,6 +390,7 @@ def load_image_batch(
     flips=None,
     exif_orientation: bool = False,
     lowres=None,
+    csc: str = "swscale",
     **kwargs,
 ):
     """Batch load images into one ``[B,H,W,3]`` buffer with the FFmpeg filter
@@ -382,13 +437,22 @@ def load_image_batch(
     it -- other pixels than the full decode's, for a fraction of the IDCT and
     output work.  An int for every image, a list per image, or ``"auto"`` (an
     extension): per image the largest level that keeps the frame no smaller
-    than what the chain scales it to.  Exclusive with source crops."""
+    than what the chain scales it to.  Exclusive with source crops.
+
+    ``csc="turbo"`` (an extension): Pillow's pixels -- libjpeg-turbo's default
+    decoder, ``np.asarray(PIL.Image.open(f).convert("RGB"))`` byte for byte --
+    for files of one size at that size: ``width=None, height=None``, an RGB
+    ``pix_fmt``, and none of ``crops``, ``flips``, ``exif_orientation``,
+    ``lowres`` (files of mixed sizes: :func:`load_image_list`)."""
     if not srcs:
         raise ValueError("`srcs` must not be empty.")
     storage = kwargs.pop("storage", None)
     lowres = _ffmpeg_configs(kwargs, lowres)
     if kwargs:
         raise TypeError(f"unexpected arguments: {sorted(kwargs)}")
+    _check_csc(csc, width=width, height=height, crops=crops, flips=flips,
+               exif_orientation=exif_orientation, lowres=lowres,
+               pix_fmt=_csc_pix_fmt(filter_desc, pix_fmt))
     if filter_desc == _FILTER_DESC_DEFAULT:
         filter_desc = get_video_filter_desc(
             scale_width=width, scale_height=height, pix_fmt=pix_fmt
@@ -439,7 +503,7 @@ def load_image_batch(
             return convert_array(arr, storage=storage)
         return CPUBuffer(arr)
     # (no format node and pix_fmt=None: the decoder's own planes, scaled)
-    out = parse_image_filter(filter_desc, default_pix_fmt=pix_fmt)
+    out = _with_csc(parse_image_filter(filter_desc, default_pix_fmt=pix_fmt), csc)
     if crops is not None and out.src_crop is not None:
         raise ValueError("crops= and a source crop in filter_desc are exclusive")
     if flips is not None and out.flip is not None:
@@ -734,6 +798,9 @@ def load_image_list(
     is any chain ``load_image_batch`` takes.  ``crops``, ``flips``,
     ``exif_orientation``, ``normalize`` and ``lowres`` are
     ``load_image_batch``'s; every box is sized from its image's reduced frame.
+    ``csc="turbo"``: Pillow's pixels (libjpeg-turbo's default decoder, byte
+    for byte) of every file at its native size -- no ``width`` / ``height``,
+    ``crops``, ``flips``, ``exif_orientation`` or ``lowres`` with it.
 
     Returns ``(buffers, image_indices)``: one allocation, every buffer a view
     of it with its image's own shape (``[H,W,3]``, or ``[3,H,W]`` for ``rgb`` /
@@ -745,8 +812,11 @@ def load_image_list(
         raise ValueError("`srcs` must not be empty.")
     if pix_fmt is None:
         raise ValueError("load_image_list needs an RGB pix_fmt: no ragged planar YUV output")
-    if csc != "swscale":
-        raise ValueError(f"load_image_list converts with csc='swscale' only, not {csc!r}")
+    if csc not in ("swscale", "turbo"):
+        raise ValueError(f"load_image_list converts with csc='swscale' only, or with csc='turbo' "
+                         f"at native size, not {csc!r}")
+    _check_csc(csc, width=width, height=height, crops=crops, flips=flips,
+               exif_orientation=exif_orientation, lowres=lowres, pix_fmt=pix_fmt)
     if filter_desc == _FILTER_DESC_DEFAULT:
         filter_desc = _list_filter_desc(width, height, scale_mode, scale_algo, pix_fmt)
     elif (width, height, scale_mode) != (None, None, None):
@@ -760,7 +830,7 @@ def load_image_list(
             raise ValueError(f"{len(per)} {name} for {n_src} images")
     if flips is not None:
         flips = [_lib._flip(f) for f in flips]
-    out = parse_image_filter(filter_desc, default_pix_fmt=pix_fmt)
+    out = _with_csc(parse_image_filter(filter_desc, default_pix_fmt=pix_fmt), csc)
     if out.pix_fmt == "yuv":
         raise ValueError("load_image_list needs an RGB pix_fmt: no ragged planar YUV output")
     if crops is not None and out.src_crop is not None:
@@ -882,6 +952,7 @@ def load_image(
     flip=None,
     exif_orientation: bool = False,
     lowres=None,
+    csc: str = "swscale",
     **kwargs,
 ):
     """Single image.  ``filter_desc=None`` returns the decoded planes in the
@@ -897,11 +968,16 @@ def load_image(
     orientation, as in :func:`load_image_batch`; ``flip`` then acts on the
     displayed image.  ``lowres`` (``0..3`` or ``"auto"``) and a
     ``decode_config`` with the ``"lowres"`` decoder option: the reduced-size
-    decode of :func:`load_image_batch`."""
+    decode of :func:`load_image_batch`.  ``csc="turbo"`` (an extension):
+    ``np.asarray(PIL.Image.open(f).convert("RGB"))`` byte for byte, in the
+    ``pix_fmt``'s layout -- libjpeg-turbo's default decoder; no scaling chain,
+    ``flip``, ``exif_orientation`` or ``lowres`` with it."""
     kwargs.pop("name", None)  # only names the source in FFmpeg demux errors
     lowres = _ffmpeg_configs(kwargs, lowres)
     if kwargs:
         raise TypeError(f"unexpected arguments: {sorted(kwargs)}")
+    _check_csc(csc, flips=flip or None, exif_orientation=exif_orientation, lowres=lowres,
+               pix_fmt=_csc_pix_fmt(filter_desc, pix_fmt))
     cfg = device_config or _default_config()
     data = _read(src)
     flip = _lib._flip(flip)
@@ -918,7 +994,7 @@ def load_image(
         return CPUBuffer(arr)
     if filter_desc == _FILTER_DESC_DEFAULT:
         filter_desc = get_video_filter_desc(pix_fmt=pix_fmt)
-    out = parse_image_filter(filter_desc, default_pix_fmt=pix_fmt)
+    out = _with_csc(parse_image_filter(filter_desc, default_pix_fmt=pix_fmt), csc)
     if flip:
         if out.flip is not None:
             raise ValueError("flip= and hflip / vflip in filter_desc are exclusive")
