@@ -594,6 +594,74 @@ int spdl_hj_set_lowres(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n);
  * "turbo_workgroups" reports its workgroups in the last submission (0 for any
  * other csc). */
 
+/* ---- Pillow-exact resize (additive in ABI 7: one call, one debug entry, one
+ * read-only parameter) -----------------------------------------------------------
+ * spdl_hj_set_resample makes the NEXT batch submission (spdl_hj_decode_batch,
+ * _device or _staged) a resampled one: every image's Pillow-exact decode is
+ * resized as Pillow's Image.resize does it and leaves as one out_w x out_h
+ * box, whatever the file's size:
+ *   np.asarray(Image.open(f).convert("RGB").crop(box).resize((rw, rh), filter))
+ *     [oy : oy + out_h, ox : ox + out_w]
+ * byte for byte.  The submission's spec has csc = SPDL_HJ_CSC_TURBO,
+ * resize = 0 and an RGB / BGR pix_fmt; the three dtypes are taken (F16 / BF16
+ * normalise the resized bytes).  filter is a spdl_hj_filter.  items: n records,
+ * one per image, or NULL: the whole frame into out_w x out_h.  One kernel,
+ * resample_kernel, goes from the islow planes to the box: neither the
+ * full-size RGB frame nor the horizontal pass's picture touches device memory.
+ *
+ * The rules, restated from Pillow's 8-bit resampling (no library source is
+ * involved).  An axis of inSize samples into outSize, filter f of support s,
+ * in double arithmetic in this order, nothing fused:
+ *   scale = inSize / outSize;  fs = max(scale, 1);  support = s fs;  ss = 1 / fs
+ *   center = (xx + 0.5) scale
+ *   xmin = max((int)(center - support + 0.5), 0)
+ *   xmax = min((int)(center + support + 0.5), inSize)
+ *   w[x] = f((x + xmin - center + 0.5) ss), x < xmax - xmin;  k[x] = w[x] / sum w
+ *   K[x] = (int)(k[x] 4194304 -+ 0.5)            (away from zero; 1 << 22)
+ * with f bilinear (s = 1: 1 - |x|), bicubic (s = 2, a = -0.5) or lanczos
+ * (s = 3: sinc(x) sinc(x / 3) on [-3, 3)).  A pass computes, per channel,
+ *   clip8((2097152 + sum K[x] p[xmin + x]) >> 22)
+ * in int32 with an arithmetic shift.  The horizontal pass runs first; the
+ * vertical pass reads its u8 result.  A pass whose axis keeps its size has
+ * identity coefficients and is run all the same.  The source is the Pillow-exact
+ * decode's W x H RGB (rules 1-3 above); a box is a frame of its own
+ * (inSize = box.w, samples at box.x + xmin + x), any integer rectangle inside
+ * the frame -- not rounded to the chroma ratio; chroma upsampling sees the
+ * frame's own neighbours across the box's edge, as Pillow crops after it
+ * decodes.
+ *
+ * SPDL_HJ_ERR_INVALID_ARG from the consuming call, nothing written: any other
+ * csc; SPDL_HJ_FMT_YUV; together with spdl_hj_set_ragged, views, source
+ * crops, non-zero flips, orientations or levels; n not the batch size; out_w
+ * or out_h outside 1..65535; an unknown filter.  SPDL_HJ_ERR_BAD_GEOMETRY for
+ * that image alone, its box untouched, the rest decoded: a box that is empty
+ * or reaches outside the frame; rw / rh outside 1..65535 or a window reaching
+ * outside rw x rh; an axis on which one output sample takes more than
+ * SPDL_HJ_RESAMPLE_MAX_TAPS source samples (lanczos: a ratio above 42).
+ *
+ * The read-only parameter "resample_workgroups" reports resample_kernel's
+ * workgroups in the last submission; "turbo_workgroups" is 0 for it.
+ *
+ * Out of scope: Pillow's fractional box= and reducing_gap; the BOX, HAMMING
+ * and NEAREST filters; ragged output sizes; an IDCT of the MCUs a box touches
+ * alone (the whole frame is transformed); flips and orientations on a
+ * resampled submission; gamma-aware or float resampling. */
+#define SPDL_HJ_RESAMPLE_MAX_TAPS 256
+typedef struct spdl_hj_resample_item {
+  spdl_hj_rect box;      /* source rectangle of the W x H frame; w == 0: the whole frame */
+  int32_t rw, rh;        /* the resized picture; 0: out_w / out_h */
+  int32_t ox, oy;        /* the out_w x out_h window of it that is written */
+} spdl_hj_resample_item;
+int spdl_hj_set_resample(spdl_hj_ctx* ctx, int32_t filter, int32_t out_w, int32_t out_h,
+                         const spdl_hj_resample_item* items, int64_t n);
+
+/* One axis's tables as the library builds them (no device, no context):
+ * xmin[outSize], n[outSize] and K[outSize * (*ksize)], *ksize the axis's most
+ * taps.  cap: the ints K can hold; call with K == NULL for *ksize alone.
+ * SPDL_HJ_ERR_BAD_GEOMETRY: more than SPDL_HJ_RESAMPLE_MAX_TAPS taps. */
+int spdl_hj_debug_resample_axis(int32_t in_size, int32_t out_size, int32_t filter, int32_t* xmin,
+                                int32_t* n, int32_t* K, int64_t cap, int32_t* ksize);
+
 /* ABI version of the loaded library (== SPDL_HJ_ABI_VERSION). */
 int spdl_hj_abi_version(void);
 
@@ -849,7 +917,8 @@ const char* spdl_hj_stage_name(int32_t i);
  * decode), the images of the last submission with a level above 0 and the
  * bytes of the component planes it laid out in the workspace;
  * "turbo_workgroups" (with the Pillow-exact decode), the workgroups of
- * turbo_rgb_kernel in the last submission.
+ * turbo_rgb_kernel in the last submission; "resample_workgroups" (with the
+ * Pillow-exact resize), those of resample_kernel.
  * Builds with -DHJ_ABLATIONS=1 also take "debug_mask" (timing ablations that
  * skip kernel phases; outputs wrong); release builds reject it. */
 int spdl_hj_set_param(spdl_hj_ctx* ctx, const char* name, int64_t value);

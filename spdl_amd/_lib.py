@@ -63,6 +63,8 @@ EXPORTED = (
     "spdl_hj_ragged_layout",
     "spdl_hj_set_ragged",
     "spdl_hj_set_lowres",
+    "spdl_hj_set_resample",
+    "spdl_hj_debug_resample_axis",
 )
 
 
@@ -462,12 +464,70 @@ def lib() -> ctypes.CDLL:
             L.spdl_hj_set_ragged.argtypes = [vp, vp, i32]
         if hasattr(L, "spdl_hj_set_lowres"):  # (likewise)
             L.spdl_hj_set_lowres.argtypes = [vp, vp, i32]
+        if hasattr(L, "spdl_hj_set_resample"):  # (likewise)
+            L.spdl_hj_set_resample.argtypes = [vp, i32, i32, i32, vp, i64]
+            L.spdl_hj_debug_resample_axis.argtypes = [i32, i32, i32, vp, vp, vp, i64,
+                                                      ctypes.POINTER(i32)]
         ver = L.spdl_hj_abi_version()
         # (an explicitly chosen older build, ABI >= 5, loads for A/B runs)
         if ver != ABI_VERSION and not (os.environ.get("SPDL_AMD_LIB") and 5 <= ver < ABI_VERSION):
             raise RuntimeError(f"libspdl_hipjpeg ABI {ver} != expected {ABI_VERSION}")
         _LIB = L
     return _LIB
+
+
+class ResampleItem(ctypes.Structure):  # spdl_hj_resample_item
+    _fields_ = [("box", Rect), ("rw", ctypes.c_int32), ("rh", ctypes.c_int32),
+                ("ox", ctypes.c_int32), ("oy", ctypes.c_int32)]
+
+
+@dataclass(frozen=True)
+class Resample:
+    """A resampled submission (spdl_hj_set_resample): Pillow's ``Image.resize``
+    with ``filter`` (``"bilinear"``, ``"bicubic"``, ``"lanczos"``) of every
+    image into one ``out_w x out_h`` box.  ``items``: per image ``(box, (rw,
+    rh), (ox, oy))`` -- the source rectangle ``(x, y, w, h)`` or ``None`` for
+    the whole frame, the resized picture (``0``: the box's side) and the window
+    of it that is written; ``None``: every whole frame into the box."""
+    filter: str
+    out_w: int
+    out_h: int
+    items: tuple | None = None
+
+
+def _resample_c(resample: Resample) -> tuple:
+    """spdl_hj_set_resample's arguments behind the context; ``ValueError`` for
+    an unknown filter name or a malformed item."""
+    if resample.filter not in FILTERS:
+        raise ValueError(f"filter must be one of {sorted(FILTERS)}, not {resample.filter!r}")
+    items, arr = resample.items, None
+    if items is not None:
+        arr = (ResampleItem * max(len(items), 1))()
+        try:
+            for a, (box, (rw, rh), (ox, oy)) in zip(arr, items):
+                a.box = Rect(*(box or (0, 0, 0, 0)))
+                a.rw, a.rh, a.ox, a.oy = int(rw), int(rh), int(ox), int(oy)
+        except (TypeError, ValueError) as err:
+            raise ValueError(f"a resample item is (box | None, (rw, rh), (ox, oy)): {err}") from None
+    return (FILTERS[resample.filter], int(resample.out_w), int(resample.out_h), arr,
+            0 if items is None else len(items))
+
+
+def resample_axis(in_size: int, out_size: int, filter: str):
+    """One axis's tables as the library builds them (no device): ``(xmin, n,
+    K)`` with ``K`` of shape ``[out_size, ksize]`` (spdl_hj_debug_resample_axis)."""
+    import numpy as np
+
+    ks = ctypes.c_int32()
+    xmin, cnt = np.zeros(out_size, np.int32), np.zeros(out_size, np.int32)
+    rc = lib().spdl_hj_debug_resample_axis(in_size, out_size, FILTERS[filter], xmin.ctypes.data,
+                                           cnt.ctypes.data, None, 0, ctypes.byref(ks))
+    if rc:
+        raise RuntimeError(f"spdl_hj_debug_resample_axis: {rc}")
+    K = np.zeros((out_size, ks.value), np.int32)
+    lib().spdl_hj_debug_resample_axis(in_size, out_size, FILTERS[filter], None, None,
+                                      K.ctypes.data, K.size, ctypes.byref(ks))
+    return xmin, cnt, K
 
 
 def get_image_info(data) -> ImageInfo:
@@ -882,6 +942,18 @@ class Decoder:
         if lib().spdl_hj_set_lowres(self._h, arr if levels else None, len(levels)):
             raise ValueError("invalid lowres levels")
 
+    def set_resample(self, resample: "Resample | None") -> None:
+        """Make the next batch submission a resampled one
+        (spdl_hj_set_resample, include/spdl_hipjpeg.h "Pillow-exact resize")."""
+        if resample is not None:
+            Decoder._set_resample_c(self, _resample_c(resample))
+
+    def _set_resample_c(self, args) -> None:
+        if not hasattr(lib(), "spdl_hj_set_resample"):
+            raise RuntimeError("this libspdl_hipjpeg build has no spdl_hj_set_resample")
+        if lib().spdl_hj_set_resample(self._h, *args):
+            raise ValueError("invalid resample request")
+
     def set_ragged(self, offsets) -> None:
         """The byte offsets of the next batch submission's images in its
         output (spdl_hj_set_ragged): that submission is a ragged one, every
@@ -911,7 +983,8 @@ class Decoder:
 
     def decode_batch(self, datas, out: Output, out_ptr: int, out_bytes: int, stream=None,
                      sync: bool = True, check: bool = True, crops=None, views=None,
-                     flips=None, orients=None, ragged=None, lowres=None) -> list[int]:
+                     flips=None, orients=None, ragged=None, lowres=None,
+                     resample=None) -> list[int]:
         """Per-image statuses.  A failed image raises RuntimeError unless
         ``check`` is False (synchronous calls), which returns the statuses.
         ``crops``: a source crop ``(x, y, w, h)`` or ``None`` per image.
@@ -927,7 +1000,9 @@ class Decoder:
         -- every image its own size, written at its offset of ``out_ptr``
         (include/spdl_hipjpeg.h "ragged batches").  ``lowres``: a reduced-size
         level ``0..3`` per image (spdl_hj_set_lowres; resolve ``"auto"`` or a
-        single int with :func:`lowres_levels` first)."""
+        single int with :func:`lowres_levels` first).  ``resample``: a
+        :class:`Resample` -- Pillow's ``Image.resize`` of every image's
+        ``csc="turbo"`` decode into one ``out_w x out_h`` box."""
         n = len(datas)
         if n == 0:
             raise RuntimeError("Failed to decode an image. (the batch is empty)")
@@ -950,16 +1025,18 @@ class Decoder:
                 _stream_handle(stream), int(bool(sync)), status, err, 1024,
             )
         return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                                    check, status, call, orients, ragged, lowres))
+                                    check, status, call, orients, ragged, lowres, resample))
 
     def _submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync, check, status,
-                call, orients=None, ragged=None, lowres=None):
+                call, orients=None, ragged=None, lowres=None, resample=None):
         """What the three batch submissions share: the views, crops and flips
         (or orientations) go to the context, ``call(err)`` -- the method's own marshalling and
         its native call -- returns the library's code, and a failure raises
         unless ``check`` is False on a synchronous call that refused an image
         (``status``) or a view.  (The methods reach it through the class: they
         also run unbound, on objects that are no Decoder.)"""
+        # (marshalled first: a malformed request raises before anything is on the context)
+        rs = None if resample is None else _resample_c(resample)
         if views is not None:
             _check_views(views, out, crops, out_ptr, out_bytes)
             self.set_views(views)
@@ -973,6 +1050,8 @@ class Decoder:
             Decoder.set_ragged(self, ragged)
         if lowres is not None:  # (count and values likewise)
             Decoder.set_lowres(self, lowres)
+        if rs is not None:  # (what it excludes likewise)
+            Decoder._set_resample_c(self, rs)
         err = ctypes.create_string_buffer(1024)
         rc = call(err)
         if rc and not (not check and sync and (any(status) or _refused(views, rc))):
@@ -983,7 +1062,7 @@ class Decoder:
                             out: Output, out_ptr: int, out_bytes: int, stream=None,
                             sync: bool = True, crops=None, check: bool = True,
                             views=None, flips=None, orients=None, ragged=None,
-                            lowres=None) -> list[int]:
+                            lowres=None, resample=None) -> list[int]:
         """``offsets``/``sizes``: sequences or int64 numpy arrays; ``infos``: a
         sequence of ImageInfo or a prebuilt ``(ImageInfo * n)`` array (pass the
         same objects again to skip re-marshalling on every call)."""
@@ -1003,7 +1082,7 @@ class Decoder:
                 status.ctypes.data, err, 1024,
             )
         return Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                               check, status, call, orients, ragged, lowres).tolist()
+                               check, status, call, orients, ragged, lowres, resample).tolist()
 
     def _spec(self, out: Output) -> OutputSpec:
         cache = self.__dict__.setdefault("_spec_cache", {})
@@ -1063,7 +1142,7 @@ class Decoder:
     def decode_staged(self, ticket: int, nbytes: int, offsets, sizes, out: Output, out_ptr: int,
                       out_bytes: int, stream=None, sync: bool = True, crops=None,
                       check: bool = True, views=None, flips=None, orients=None,
-                      ragged=None, lowres=None) -> list[int]:
+                      ragged=None, lowres=None, resample=None) -> list[int]:
         n = len(offsets)
         status = (ctypes.c_int32 * max(n, 1))()
 
@@ -1075,7 +1154,7 @@ class Decoder:
                 self._h, int(ticket), int(nbytes), offs, szs, n, ctypes.byref(spec), out_ptr,
                 out_bytes, _stream_handle(stream), int(bool(sync)), status, err, 1024)
         return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                                    check, status, call, orients, ragged, lowres))[:n]
+                                    check, status, call, orients, ragged, lowres, resample))[:n]
 
     def debug_entropy(self, data, nblocks: int):
         """Coefficients / destuffed bytes / diagnostics of one image (tests)."""

@@ -276,6 +276,63 @@ constexpr int kSwsMaxCols = 256;  // output columns per workgroup
 // words, so the 64 columns of a wave fall on distinct banks.  In int16 units.
 inline HJ_HD int sws_col_stride(int rows) { return 2 * (((rows + 5) >> 1) | 1); }
 
+// ---- Pillow-exact resize (spdl_hj_set_resample; hj_resample.h holds the rule,
+// the axis tables and the tiler): what planner, tiler and resample_kernel share
+namespace rs {
+constexpr int kCoefBits = 22;  // K = round(k << 22)
+
+// What resample_kernel knows of one image beside its ImageDesc (whose ow x oh
+// is the output box and sws_wg0 / sws_bands / sws_chunks its tiles): int32
+// alone, uploaded behind the descriptors.
+struct ResampleDesc {
+  int32_t bx, by;      // the box's origin in the frame
+  int32_t ox, oy;      // the written window's origin in the resized picture
+  int32_t tw, th, sr;  // tile columns (a multiple of 8), tile rows, strip rows (even)
+  int32_t kh, kv;      // the two axes' ksize
+  int32_t pitch;       // a strip row in LDS, words: odd, >= the widest tile's columns
+  int32_t rows;        // intermediate rows in LDS: the tallest tile's source rows
+  int32_t hx, hn, hk, vx, vn, vk;  // the tables in the pool (int32 units)
+};
+
+// The LDS of a workgroup, in words, in this order: the tile's horizontal xmin,
+// n and K rows, the vertical ones, the strip (packed pixels, sr x pitch), the
+// intermediate (packed pixels, rows x tw)
+struct LdsLayout {
+  int hx, hn, hk, vx, vn, vk, strip, inter, words;
+};
+inline HJ_HD LdsLayout lds_layout(const ResampleDesc& d) {
+  LdsLayout l;
+  l.hx = 0;
+  l.hn = l.hx + d.tw;
+  l.hk = l.hn + d.tw;
+  l.vx = l.hk + d.tw * d.kh;
+  l.vn = l.vx + d.th;
+  l.vk = l.vn + d.th;
+  l.strip = l.vk + d.th * d.kv;
+  l.inter = l.strip + d.sr * d.pitch;
+  l.words = l.inter + d.rows * d.tw;
+  return l;
+}
+
+// The source window of output tile t of an axis whose window starts at output
+// `o0` and is `ow` wide, tiles of `tile`: samples [lo, hi) of the frame, the
+// box origin `b0` added, lo rounded down to a multiple of `align` (the
+// producer's unit: 8 columns, 2 rows).  Host and kernel agree on it.
+struct Window {
+  int lo, hi;
+};
+inline HJ_HD Window tile_window(const int32_t* xmin, const int32_t* n, int b0, int o0, int ow,
+                                int tile, int t, int align) {
+  const int first = o0 + t * tile;
+  const int last = o0 + (ow < (t + 1) * tile ? ow : (t + 1) * tile) - 1;
+  Window w;
+  w.lo = (b0 + xmin[first]) & ~(align - 1);
+  w.hi = b0 + xmin[last] + n[last];
+  return w;
+}
+
+}  // namespace rs
+
 struct ImageInfo {      // device-filled by the parse kernel
   int32_t status;
   int32_t width, height, ncomp, hmax, vmax, mcux, mcuy, bpm, nblocks, ri;

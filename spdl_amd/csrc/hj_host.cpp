@@ -24,6 +24,7 @@
 #include "hj_layout.h"
 #include "hj_pack.h"
 #include "hj_probe.h"
+#include "hj_resample.h"
 #include "hj_sws.h"
 #include "hj_tar.h"
 #include "hj_views.h"
@@ -159,9 +160,13 @@ struct Slot {
       spdl_hj_rect rect;  // its source crop (has_rects)
       uint8_t flip;       // its output flip or orientation code (has_flips)
       uint8_t lowres;     // its reduced-size level
+      spdl_hj_resample_item resample;  // its item of a resampled batch (has_resample)
     };
     std::vector<Item> items;
     bool has_rects = false, has_flips = false;  // the batch had crops / flips
+    // the batch was a resampled one (spdl_hj_set_resample): its filter and box
+    bool has_resample = false;
+    int32_t rs_filter = 0, rs_ow = 0, rs_oh = 0;
     bool oriented = false;  // ... the flips came as orientation codes (spdl_hj_set_orients)
   } retry;
 };
@@ -287,6 +292,15 @@ struct spdl_hj_ctx {
   // the generic output kernel (sws_kernel)
   int64_t fused_workgroups = 0, generic_workgroups = 0;
   int64_t turbo_workgroups = 0;  // turbo_rgb_kernel's in the last submission (csc = TURBO)
+  int64_t resample_workgroups = 0;  // resample_kernel's (spdl_hj_set_resample)
+  // spdl_hj_set_resample: the next batch submission's filter, box and items
+  // (has_items: one per image; else every whole frame), and the axes it made
+  struct HeldResample {
+    bool set = false, has_items = false;
+    int32_t filter = 0, out_w = 0, out_h = 0;
+    std::vector<spdl_hj_resample_item> items;
+  } resample;
+  rs::AxisCache axes;
   // spdl_hj_set_views: the views of the next batch submission
   HeldViews views;
   // spdl_hj_set_ragged: the images' byte offsets in the next batch submission's output
@@ -460,7 +474,7 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
   // (the work list follows the descriptors, a flipped submission's flags the work list)
   HJ_HIP(grow(W.desc,
               sizeof(ImageDesc) * b->ndesc + sizeof(uint32_t) * b->nwork + L.flips.size() +
-                  L.lowres.size(),
+                  L.lowres.size() + L.resample.size() * sizeof(rs::ResampleDesc),
               st, &b->desc));
   b->work = reinterpret_cast<uint32_t*>(b->desc + b->ndesc);
   b->flips = L.flips.empty() ? nullptr : reinterpret_cast<const uint8_t*>(b->work + b->nwork);
@@ -469,6 +483,11 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
   b->lowres = L.lowres.empty()
                   ? nullptr
                   : reinterpret_cast<const uint8_t*>(b->work + b->nwork) + L.flips.size();
+  // (... and a resampled submission's records, which come with neither: they
+  // stand at the work list's end, 4-byte aligned)
+  b->resample = L.resample.empty()
+                    ? nullptr
+                    : reinterpret_cast<const rs::ResampleDesc*>(b->work + b->nwork);
   HJ_HIP(grow(W.chain, (size_t)(kChainHead + L.chain_granules) * 8 + 64, st, &b->chain));
   HJ_HIP(grow(W.maps, (size_t)(L.ds_wgs + L.idct_wgs + L.hs_wgs + L.sws_wgs) * 4 + 64, st,
               &b->ds_map));
@@ -503,6 +522,7 @@ struct Submission {
   const uint8_t* flips = nullptr;       // ... and its output flips (one per image)
   bool oriented = false;                // (they are orientation codes)
   const int64_t* ragged = nullptr;      // a ragged submission's byte offsets (the planner checked them)
+  const ResampleRequest* resample = nullptr;  // a resampled submission's request, for the retry record
 };
 
 // An output chain's share of the output kernels' parameters: the batch's
@@ -569,7 +589,8 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   const bool sws_flat = use_flat(L.sws_wgs, (int64_t)L.sws_bands * L.sws_chunks);
   // + work list, + the flags of a flipped submission (one byte per descriptor)
   const size_t work_end = sizeof(ImageDesc) * B.ndesc + sizeof(uint32_t) * B.nwork;
-  const size_t desc_bytes = work_end + L.flips.size() + L.lowres.size();
+  const size_t rs_bytes = L.resample.size() * sizeof(rs::ResampleDesc);
+  const size_t desc_bytes = work_end + L.flips.size() + L.lowres.size() + rs_bytes;
   HJ_HIP(slot.pin_desc.ensure(desc_bytes));
   HJ_HIP(slot.pin_status.ensure(sizeof(int32_t) * n));
   slot.n = n;
@@ -581,16 +602,24 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   if (B.lowres)
     memcpy(static_cast<uint8_t*>(slot.pin_desc.p) + work_end + L.flips.size(), L.lowres.data(),
            L.lowres.size());
-  // the batch's swscale tables travel with the descriptors
+  if (B.resample) {
+    if (!L.flips.empty() || !L.lowres.empty()) {  // (the planner refuses them together)
+      set_err(err, errlen, "a resampled submission with flips or levels");
+      return SPDL_HJ_ERR_INVALID_ARG;
+    }
+    memcpy(static_cast<uint8_t*>(slot.pin_desc.p) + work_end, L.resample.data(), rs_bytes);
+  }
+  // the batch's swscale tables travel with the descriptors (a resampled
+  // submission's axis tables likewise)
   const bool swscale = !sub.planes_only && out->csc == SPDL_HJ_CSC_SWSCALE;
-  const size_t tb = swscale ? L.tables.size() * 4 : 0;
+  const size_t tb = swscale || B.resample ? L.tables.size() * 4 : 0;
   HJ_HIP(slot.pin_tables.ensure(tb + 16));
   if (tb) memcpy(slot.pin_tables.p, L.tables.data(), tb);
   const bool hs = ctx->host_staging != 0;  // parse_kernel pulls them from the pinned pages
   if (!hs) {
     HJ_HIP(hipMemcpyAsync(B.desc, slot.pin_desc.p, desc_bytes, hipMemcpyHostToDevice, st));
     if (tb) HJ_HIP(hipMemcpyAsync(B.wts, slot.pin_tables.p, tb, hipMemcpyHostToDevice, st));
-  } else if (B.flips || B.lowres) {
+  } else if (B.flips || B.lowres || B.resample) {
     // (parse_kernel brings over the descriptors and the work list alone: the
     // flags and levels behind them take one small copy from the same pinned pages)
     HJ_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(B.work + B.nwork),
@@ -657,7 +686,7 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   // image) grid there, it costs nothing -- profiles/r18/ragged)
   const int ragged_fused = L.ragged ? (int)L.fused_wgs : 0;
   ctx->idct_workgroups = ctx->fused_workgroups = ctx->generic_workgroups = 0;
-  ctx->turbo_workgroups = 0;
+  ctx->turbo_workgroups = ctx->resample_workgroups = 0;
   ctx->entropy_workgroups = B.nwork;
   ctx->lowres_images = L.lowres_images;
   ctx->planes_bytes = L.total_planes;
@@ -689,7 +718,12 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   mark(ctx, slot, 6, st);
   if (!sub.planes_only && !(abl & kAblNoOutput)) {
     const int sws_wgs = (int)L.sws_wgs, hs_wgs = (int)L.hs_wgs;
-    if (turbo) {
+    if (turbo && B.resample) {
+      // resample_kernel over every image's own tiles, as turbo_rgb_kernel's below
+      if (sws_wgs > 0)
+        HJ_HIP(launch_resample(B, sub.out_dev, bp, sws_wgs, L.resample_lds, hstat, st));
+      ctx->resample_workgroups = sws_wgs;
+    } else if (turbo) {
       // one flat launch over every image's own tiles, plain and ragged alike
       // (an image's box and offset are its descriptor's).  Every image has at
       // least one tile -- a box is 1 x 1 or larger, a refused image has the one
@@ -744,6 +778,12 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
     R.has_rects = sub.crops != nullptr;
     R.has_flips = sub.flips != nullptr;
     R.oriented = sub.oriented;
+    R.has_resample = sub.resample != nullptr;
+    if (sub.resample) {
+      R.rs_filter = sub.resample->filter;
+      R.rs_ow = sub.resample->out_w;
+      R.rs_oh = sub.resample->out_h;
+    }
     const size_t img_bytes = (size_t)L.out_elems_per_image * esz;
     for (const auto& m : L.multi) {
       const ImageDesc& d = L.desc[m.first];
@@ -752,7 +792,9 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
                          d.in_off, d.in_size, m.second,
                          sub.crops ? sub.crops[m.first] : spdl_hj_rect{},
                          sub.flips ? sub.flips[m.first] : (uint8_t)0,
-                         L.lowres.empty() ? (uint8_t)0 : L.lowres[m.first]});
+                         L.lowres.empty() ? (uint8_t)0 : L.lowres[m.first],
+                         sub.resample && sub.resample->items ? sub.resample->items[m.first]
+                                                             : spdl_hj_resample_item{}});
     }
     R.ticket = slot.ticket;
     R.bytes = sub.d_bytes;
@@ -821,6 +863,8 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
     rq.lowres = &item.lowres;
     rq.nlowres = 1;
   }
+  const ResampleRequest one{r.rs_filter, r.rs_ow, r.rs_oh, &item.resample, 1, &ctx->axes, &rs::place_into};
+  if (r.has_resample) rq.resample = &one;
   int rc = plan_batch(rq, L, &st1, err, errlen);
   if (rc) return rc;
   // the spare slot, on the failed batch's lane (its workspace is free: the
@@ -837,17 +881,18 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
   const int64_t idct_wgs = ctx->idct_workgroups;  // (the batch's, not this re-decode's)
   const int64_t ent_wgs = ctx->entropy_workgroups;
   const int64_t fused_wgs = ctx->fused_workgroups, generic_wgs = ctx->generic_workgroups;
-  const int64_t turbo_wgs = ctx->turbo_workgroups;
+  const int64_t turbo_wgs = ctx->turbo_workgroups, resample_wgs = ctx->resample_workgroups;
   const int64_t lowres_images = ctx->lowres_images, planes_bytes = ctx->planes_bytes;
   rc = run_pipeline(ctx, *s, L,
                     {r.bytes, r.len, 1, &r.out, r.out_dev + item.out_off, item.out_bytes, xs, 1,
-                     &st1},
+                     &st1, false, nullptr, nullptr, false, nullptr, rq.resample},
                     err, errlen);
   ctx->idct_workgroups = idct_wgs;
   ctx->entropy_workgroups = ent_wgs;
   ctx->fused_workgroups = fused_wgs;
   ctx->generic_workgroups = generic_wgs;
   ctx->turbo_workgroups = turbo_wgs;
+  ctx->resample_workgroups = resample_wgs;
   ctx->lowres_images = lowres_images;
   ctx->planes_bytes = planes_bytes;
   ctx->last_ticket = last;
@@ -938,6 +983,10 @@ struct Held {
   int64_t norients = 0;
   const uint8_t* lowres = nullptr;  // reduced-size levels (the planner's to check as well)
   int64_t nlowres = 0;
+  // spdl_hj_set_resample's request (null: a plain submission; the planner's to check)
+  spdl_hj_ctx::HeldResample resamplev;
+  ResampleRequest resample_rq{};
+  const ResampleRequest* resample = nullptr;
   int crc = 0, vrc = 0;
   Held(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, const void* out_dev, size_t out_bytes,
        char* err, size_t errlen) {
@@ -962,6 +1011,14 @@ struct Held {
     }
     raggedv.swap(ctx->ragged);
     ctx->ragged.clear();
+    std::swap(resamplev, ctx->resample);
+    ctx->resample = {};
+    if (resamplev.set) {
+      resample_rq = {resamplev.filter, resamplev.out_w, resamplev.out_h,
+                     resamplev.has_items ? resamplev.items.data() : nullptr,
+                     (int64_t)resamplev.items.size(), &ctx->axes, &rs::place_into};
+      resample = &resample_rq;
+    }
     crc = take_crops(ctx, n, out, &rects, &crops, err, errlen);
     vrc = take_views(ctx, n, out, out_dev, out_bytes, !rects.empty(), &views, &hv, err, errlen);
     if (!raggedv.empty()) ragged = raggedv.data();  // (check() holds its count against n)
@@ -1048,7 +1105,7 @@ int submit(spdl_hj_ctx* ctx, const Held& held, const Batch& b, SlotRelease& slot
   int rc = plan_batch({b.offsets, b.sizes, infos, b.n, b.out, held.hv ? 0 : ctx->piece_bytes,
                        &ctx->plans, held.crops, held.hv, held.flips, held.nflips, held.orients,
                        held.norients, held.ragged, (int64_t)b.out_bytes, ctx->output_path,
-                       held.lowres, held.nlowres},
+                       held.lowres, held.nlowres, held.resample},
                       L, b.status, err, errlen);
   if (rc) return rc;
   // the probes (the caller's own with device bytes, ABI 5) say which files
@@ -1067,7 +1124,7 @@ int submit(spdl_hj_ctx* ctx, const Held& held, const Batch& b, SlotRelease& slot
                       {bytes, b.bytes_len, b.n, b.out, b.out_dev, b.out_bytes, xs, b.sync, b.status,
                        false, held.crops,
                        held.hv ? nullptr : held.orients ? held.orients : held.flips,
-                       held.orients != nullptr, held.ragged},
+                       held.orients != nullptr, held.ragged, held.resample},
                       err, errlen);
 }
 
@@ -1190,6 +1247,37 @@ int spdl_hj_set_lowres(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n) {
   if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
   ctx->lowres.clear();
   if (levels && n > 0) ctx->lowres.assign(levels, levels + n);
+  return SPDL_HJ_OK;
+}
+
+int spdl_hj_set_resample(spdl_hj_ctx* ctx, int32_t filter, int32_t out_w, int32_t out_h,
+                         const spdl_hj_resample_item* items, int64_t n) {
+  if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
+  // (a filter, a box or a count the submission cannot take is that call's to
+  // refuse: the setting is consumed there, with nothing written)
+  ctx->resample = {};
+  ctx->resample.set = true;
+  ctx->resample.filter = filter;
+  ctx->resample.out_w = out_w;
+  ctx->resample.out_h = out_h;
+  ctx->resample.has_items = items != nullptr;
+  if (items) ctx->resample.items.assign(items, items + n);
+  return SPDL_HJ_OK;
+}
+
+int spdl_hj_debug_resample_axis(int32_t in_size, int32_t out_size, int32_t filter, int32_t* xmin,
+                                int32_t* n, int32_t* K, int64_t cap, int32_t* ksize) {
+  if (!ksize) return SPDL_HJ_ERR_INVALID_ARG;
+  int rc = SPDL_HJ_OK;
+  const auto a = rs::make_axis(in_size, out_size, filter, &rc);
+  if (!a) return rc;
+  *ksize = a->ksize;
+  if (xmin) memcpy(xmin, a->xmin(), sizeof(int32_t) * a->out);
+  if (n) memcpy(n, a->n(), sizeof(int32_t) * a->out);
+  if (K) {
+    if (cap < (int64_t)a->out * a->ksize) return SPDL_HJ_ERR_INVALID_ARG;
+    memcpy(K, a->K(), sizeof(int32_t) * (size_t)a->out * a->ksize);
+  }
   return SPDL_HJ_OK;
 }
 
@@ -1826,6 +1914,7 @@ int spdl_hj_get_param(spdl_hj_ctx* ctx, const char* name, int64_t* value) {
       {"fused_workgroups", ctx->fused_workgroups},
       {"generic_workgroups", ctx->generic_workgroups},
       {"turbo_workgroups", ctx->turbo_workgroups},
+      {"resample_workgroups", ctx->resample_workgroups},
       {"entropy_workgroups", ctx->entropy_workgroups},
   };
   for (const auto& t : tab)

@@ -6663,7 +6663,9 @@ __device__ __forceinline__ void turbo_store_row(void* out, int64_t base, const B
 }
 
 // One output row of a thread from its three components' samples: the colour
-// model, the channel order, the store
+// model, the channel order, the store.  (The colour-model branch exists a
+// second time as turbo_pixel, for resample_kernel: change both together, or
+// the resize stops being the resize of this decode.)
 __device__ __forceinline__ void turbo_row(void* out, const ImageDesc& dd, const BatchParams& p,
                                           int x0, int y, const int (&v0)[8], const int (&v1)[8],
                                           const int (&v2)[8]) {
@@ -6705,6 +6707,9 @@ __global__ void __launch_bounds__(256) turbo_rgb_kernel(const uint8_t* __restric
   const int x0 = tx * kTurboTileW + (tid & 15) * 8;
   const int y0 = ty * kTurboTileH + (tid >> 4) * 2;
   if (x0 >= W || y0 >= H) return;
+  // (from here to turbo_row: the same steps as turbo_samples below, which
+  // resample_kernel calls -- a change to the ratios or the per-component
+  // rule goes into both)
   // the ratios, from the sampling factors the planner laid the planes out by
   int hmax = 1, vmax = 1;
   if (dd.ncomp > 1) {
@@ -6733,6 +6738,206 @@ __global__ void __launch_bounds__(256) turbo_rgb_kernel(const uint8_t* __restric
   }
   turbo_row(out, dd, p, x0, y0, v[0][0], v[1][0], v[2][0]);
   if (y0 + 1 < H) turbo_row(out, dd, p, x0, y0 + 1, v[0][1], v[1][1], v[2][1]);
+}
+
+// ---------------------------------------------------------------------------
+// resample_kernel: the Pillow-exact resize (spdl_hipjpeg.h "Pillow-exact
+// resize", hj_resample.h) -- from the islow planes to an image's out_w x out_h
+// box in one workgroup per output tile; neither the full-size RGB frame nor
+// the horizontal pass's picture is written to device memory.
+//
+// Grid: flat over (image, tile) through sws_map, tiles of rd.tw x rd.th output
+// pixels as rs::tile() sized them for this image.  A workgroup
+//  1. takes its source window from the tables -- rows [r0, r1) of the vertical
+//     axis, columns [c0, c1) of the horizontal one, the box origin added, r0
+//     even and c0 a multiple of 8 (turbo_samples' unit) -- and stages its
+//     tw + th coefficient rows in LDS once;
+//  2. walks the rows in strips of rd.sr: a thread upsamples and converts 8 x 2
+//     pixels (turbo_samples, turbo_pixel: what turbo_rgb_kernel runs) into the
+//     strip, one word a pixel (R | G << 8 | B << 16); the horizontal pass then
+//     reduces every strip row to the tile's columns, u8 again, into the
+//     intermediate of (r1 - r0) x tw words;
+//  3. runs the vertical pass over the intermediate, a thread 8 consecutive
+//     columns of a row, and stores through turbo_store_row.
+// The horizontal pass runs its lanes along the strip's ROWS: item i is row
+// i % sr of column i / sr, and a strip row's pitch is odd, so the lanes of a
+// column read distinct banks whatever the scale (lanes along columns would
+// read `scale` words apart: a conflict on every downscale) and share their
+// coefficient, which is one broadcast read.  Both passes multiply in full 32
+// bits and accumulate modulo 2^32 from 1 << 21: a coefficient can exceed
+// 1 << 22 where an edge cuts negative lobes off, so the 24-bit forms are not
+// exact here.
+// ---------------------------------------------------------------------------
+
+// turbo_rgb_kernel's producer as functions.  (turbo_rgb_kernel itself keeps
+// its body: folded onto these two it compiles to other code, and the existing
+// kernels' code objects are held unchanged -- DESIGN.md section 3.)
+// One pixel's RGB from its three components' samples, by the frame's colour model
+__device__ __forceinline__ void turbo_pixel(const ImageDesc& dd, int v0, int v1, int v2,
+                                            int (&rgb)[3]) {
+  if (dd.ncomp == 1) {
+    rgb[0] = rgb[1] = rgb[2] = v0;
+  } else if (dd.color == kColorRgb) {  // an RGB-coded frame: a copy of its planes
+    rgb[0] = v0;
+    rgb[1] = v1;
+    rgb[2] = v2;
+  } else {
+    up::ycc_rgb(v0, v1, v2, rgb);
+  }
+}
+
+// The frame's samples x0 .. x0 + 7 of rows y0 and y0 + 1 (x0 a multiple of 8
+// below the width, y0 even and below the height), every component upsampled by
+// its own rule: v[c][row][k].  Gray: every channel is Y.
+__device__ __forceinline__ void turbo_samples(const uint8_t* __restrict__ planes,
+                                              const ImageDesc& dd, int x0, int y0,
+                                              int (&v)[3][2][8]) {
+  // the ratios, from the sampling factors the planner laid the planes out by
+  int hmax = 1, vmax = 1;
+  if (dd.ncomp > 1) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      hmax = max(hmax, dd.h_samp[c]);
+      vmax = max(vmax, dd.v_samp[c]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    if (c < dd.ncomp) {
+      const int hr = dd.ncomp > 1 ? hmax / dd.h_samp[c] : 1;
+      const int vr = dd.ncomp > 1 ? vmax / dd.v_samp[c] : 1;
+      const int cw = dd.win_w[c], ch = dd.win_h[c];
+      up::run8x2(planes + dd.plane_off[c], dd.plane_stride[c], cw, ch, up::mode_of(hr, vr, cw), hr,
+                 vr, x0, y0, v[c][0], v[c][1]);
+    } else {  // (gray: every channel is Y)
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        v[c][0][k] = v[0][0][k];
+        v[c][1][k] = v[0][1][k];
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ uint32_t rs_clip8(uint32_t acc) {
+  const int v = (int)acc >> rs::kCoefBits;
+  return (uint32_t)min(max(v, 0), 255);
+}
+
+__global__ void __launch_bounds__(256) resample_kernel(const uint8_t* __restrict__ planes,
+                                                       const ImageDesc* __restrict__ desc,
+                                                       const ImageInfo* __restrict__ infos,
+                                                       const rs::ResampleDesc* __restrict__ rdesc,
+                                                       const int32_t* __restrict__ tables,
+                                                       void* __restrict__ out, const BatchParams p,
+                                                       int32_t* __restrict__ host_status,
+                                                       const uint32_t* __restrict__ sws_map) {
+  extern __shared__ uint32_t rs_lds[];
+  const int img = (int)sws_map[blockIdx.x], tid = threadIdx.x;
+  const ImageDesc& dd = desc[img];
+  const int t = (int)blockIdx.x - dd.sws_wg0;
+  const ImageInfo& in = infos[img];
+  if (host_status && t == 0 && tid == 0) host_status[img] = in.status;
+  if (in.status != kOk || dd.refuse) return;
+  const rs::ResampleDesc rd = rdesc[img];
+  const rs::LdsLayout l = rs::lds_layout(rd);
+  const int ty = t / dd.sws_chunks, tx = t - ty * dd.sws_chunks;
+  const int ncol = min(rd.tw, dd.ow - tx * rd.tw), nrow = min(rd.th, dd.oh - ty * rd.th);
+  // 1. the windows and the tile's coefficient rows
+  const rs::Window wc =
+      rs::tile_window(tables + rd.hx, tables + rd.hn, rd.bx, rd.ox, dd.ow, rd.tw, tx, 8);
+  const rs::Window wr =
+      rs::tile_window(tables + rd.vx, tables + rd.vn, rd.by, rd.oy, dd.oh, rd.th, ty, 2);
+  const int c0 = wc.lo, r0 = wr.lo, r1 = wr.hi;
+  const int units_x = (wc.hi - c0 + 7) >> 3;  // 8-column units of a strip row
+  const int hcol0 = rd.ox + tx * rd.tw, vrow0 = rd.oy + ty * rd.th;
+  int32_t* const lds = reinterpret_cast<int32_t*>(rs_lds);
+  for (int i = tid; i < ncol; i += 256) {
+    lds[l.hx + i] = tables[rd.hx + hcol0 + i] + rd.bx - c0;  // (relative to the strip)
+    lds[l.hn + i] = tables[rd.hn + hcol0 + i];
+  }
+  for (int i = tid; i < ncol * rd.kh; i += 256)
+    lds[l.hk + i] = tables[rd.hk + (int64_t)hcol0 * rd.kh + i];
+  for (int i = tid; i < nrow; i += 256) {
+    lds[l.vx + i] = tables[rd.vx + vrow0 + i] + rd.by - r0;  // (relative to the intermediate)
+    lds[l.vn + i] = tables[rd.vn + vrow0 + i];
+  }
+  for (int i = tid; i < nrow * rd.kv; i += 256)
+    lds[l.vk + i] = tables[rd.vk + (int64_t)vrow0 * rd.kv + i];
+  uint32_t* const strip = rs_lds + l.strip;
+  uint32_t* const inter = rs_lds + l.inter;
+  const int sr_shift = __builtin_ctz((unsigned)rd.sr);
+  // 2. strips
+  for (int s0 = r0; s0 < r1; s0 += rd.sr) {
+    const int srows = min(rd.sr, r1 - s0);
+    __syncthreads();  // (the coefficient rows stand; the last strip is consumed)
+    const int units = units_x * ((srows + 1) >> 1);
+    for (int u = tid; u < units; u += 256) {
+      const int uy = u / units_x, ux = u - uy * units_x;
+      int v[3][2][8];
+      turbo_samples(planes, dd, c0 + 8 * ux, s0 + 2 * uy, v);
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        uint32_t* q = strip + (2 * uy + j) * rd.pitch + 8 * ux;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          int rgb[3];
+          turbo_pixel(dd, v[0][j][k], v[1][j][k], v[2][j][k], rgb);
+          q[k] = (uint32_t)rgb[0] | (uint32_t)rgb[1] << 8 | (uint32_t)rgb[2] << 16;
+        }
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < (ncol << sr_shift); i += 256) {
+      const int row = i & (rd.sr - 1), col = i >> sr_shift;
+      if (row >= srows) continue;
+      const int n = lds[l.hn + col];
+      const uint32_t* px = strip + row * rd.pitch + lds[l.hx + col];
+      const int32_t* kk = lds + l.hk + col * rd.kh;
+      uint32_t a0 = 1u << (rs::kCoefBits - 1), a1 = a0, a2 = a0;
+      for (int k = 0; k < n; k++) {
+        const uint32_t w = (uint32_t)kk[k], q = px[k];
+        a0 += w * (q & 255u);
+        a1 += w * ((q >> 8) & 255u);
+        a2 += w * (q >> 16);
+      }
+      inter[(s0 - r0 + row) * rd.tw + col] = rs_clip8(a0) | rs_clip8(a1) << 8 | rs_clip8(a2) << 16;
+    }
+  }
+  __syncthreads();
+  // 3. the vertical pass, the channel order and the store
+  const bool swap = p.pix_fmt == 1 || p.pix_fmt == 3;
+  const int groups = (ncol + 7) >> 3;
+  for (int i = tid; i < groups * nrow; i += 256) {
+    const int y = i / groups, g = i - y * groups;
+    const int n = lds[l.vn + y];
+    const uint32_t* px = inter + lds[l.vx + y] * rd.tw + 8 * g;
+    const int32_t* kk = lds + l.vk + y * rd.kv;
+    uint32_t a[3][8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) a[0][j] = a[1][j] = a[2][j] = 1u << (rs::kCoefBits - 1);
+    for (int k = 0; k < n; k++) {
+      const uint32_t w = (uint32_t)kk[k];
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const uint32_t q = px[k * rd.tw + j];
+        a[0][j] += w * (q & 255u);
+        a[1][j] += w * ((q >> 8) & 255u);
+        a[2][j] += w * (q >> 16);
+      }
+    }
+    int c0v[8], c1v[8], c2v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const int r = (int)rs_clip8(a[0][j]), b = (int)rs_clip8(a[2][j]);
+      c0v[j] = swap ? b : r;
+      c1v[j] = (int)rs_clip8(a[1][j]);
+      c2v[j] = swap ? r : b;
+    }
+    const int x = tx * rd.tw + 8 * g;
+    turbo_store_row(out, dd.out_off, p, dd.ow, dd.oh, x, ty * rd.th + y, min(8, dd.ow - x), c0v, c1v,
+                    c2v);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -6846,6 +7051,12 @@ hipError_t launch_turbo_rgb(const BatchBuffers& b, void* out, const BatchParams&
                             int32_t* host_status, hipStream_t st) {
   hipLaunchKernelGGL(turbo_rgb_kernel, dim3(turbo_wgs), dim3(256), 0, st, b.planes, b.desc, b.infos,
                      out, p, host_status, b.sws_map);
+  return hipGetLastError();
+}
+hipError_t launch_resample(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
+                           int lds_bytes, int32_t* host_status, hipStream_t st) {
+  hipLaunchKernelGGL(resample_kernel, dim3(wgs), dim3(256), lds_bytes, st, b.planes, b.desc,
+                     b.infos, b.resample, b.wts, out, p, host_status, b.sws_map);
   return hipGetLastError();
 }
 hipError_t launch_rgb_unscaled(const BatchBuffers& b, void* out, const BatchParams& p,

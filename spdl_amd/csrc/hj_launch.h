@@ -42,6 +42,9 @@ struct BatchBuffers {
   // reduced-size levels (spdl_hj_set_lowres): one byte per image behind the
   // flips; null when every level is 0 -- idct_kernel then runs as ever
   const uint8_t* lowres;
+  // a resampled submission's records (spdl_hj_set_resample): one per image
+  // behind the work list; null otherwise
+  const rs::ResampleDesc* resample;
 };
 
 // parse_kernel + lut_kernel.  host_desc (descriptors, then the work list) and
@@ -69,6 +72,11 @@ hipError_t launch_csc(const BatchBuffers& b, void* out, const BatchParams& p, in
 // turbo_wgs workgroups of sws_map (Layout::sws_wgs), plain and ragged submissions alike
 hipError_t launch_turbo_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int turbo_wgs,
                             int32_t* host_status, hipStream_t st);
+// resample_kernel (spdl_hj_set_resample) over the same flat grid: every image's tiles as
+// rs::tile() laid them, b.resample its records, b.wts the axis tables; lds_bytes: the
+// submission's largest tile (Layout::resample_lds)
+hipError_t launch_resample(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
+                           int lds_bytes, int32_t* host_status, hipStream_t st);
 hipError_t launch_rgb_unscaled(const BatchBuffers& b, void* out, const BatchParams& p,
                                int64_t max_px, int32_t* host_status, hipStream_t st);
 hipError_t launch_idct_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int idct,

@@ -522,6 +522,16 @@ struct Planner {
       refuse(d, crop_rc);
       return SPDL_HJ_OK;
     }
+    if (rq.resample) {
+      // every image's box is the request's, whatever its frame; an image the
+      // resample cannot take is refused alone, its box untouched
+      size = {true, rq.resample->out_w, rq.resample->out_h};
+      d.ow = size.ow;
+      d.oh = size.oh;
+      L.max_px = std::max(L.max_px, (int64_t)d.ow * d.oh);
+      if (const int rc = place_resample(i, d, p)) refuse(d, rc);
+      return SPDL_HJ_OK;
+    }
     const Placement pl = place_output(d, src.w, src.h, f, p.color, out, size, code_of(i));
     if (pl.at != kAtGeometry) L.max_px = std::max(L.max_px, (int64_t)d.ow * d.oh);
     if (pl.rc && refused_alone(rq.ragged != nullptr, pl)) {
@@ -783,6 +793,49 @@ struct Planner {
     return res.rc;
   }
 
+  // A resampled request against what the extension takes (spdl_hipjpeg.h
+  // "Pillow-exact resize"); crops and views are check_turbo's to refuse, flips,
+  // orientations and levels their own checks' (the csc is TURBO)
+  int check_resample() {
+    if (!rq.resample) return SPDL_HJ_OK;
+    const ResampleRequest& r = *rq.resample;
+    const char* what = nullptr;
+    if (rq.out->csc != SPDL_HJ_CSC_TURBO) what = "spdl_hj_set_resample needs csc = turbo";
+    else if (!rq.plans || !r.cache || !r.place) what = "spdl_hj_set_resample needs an output stage";
+    else if (rq.out->pix_fmt == SPDL_HJ_FMT_YUV) what = "no resampled planar YUV output";
+    else if (rq.ragged) what = "spdl_hj_set_resample and spdl_hj_set_ragged on one submission";
+    else if (r.items && r.n != rq.n) what = "spdl_hj_set_resample: one item per image of the batch";
+    else if (r.out_w < 1 || r.out_w > 65535 || r.out_h < 1 || r.out_h > 65535)
+      what = "spdl_hj_set_resample: out_w and out_h are 1 to 65535";
+    else if (r.filter < 0 || r.filter > SPDL_HJ_FILTER_LANCZOS)
+      what = "spdl_hj_set_resample: unknown filter";
+    if (!what) return SPDL_HJ_OK;
+    res.rc = SPDL_HJ_ERR_INVALID_ARG;
+    snprintf(res.err, sizeof(res.err), "%s", what);
+    return res.rc;
+  }
+
+  // Image i of a resampled submission: its box, resized picture and window
+  // resolved, the two axes' tables placed once in L.tables, its record and
+  // its resample_kernel tiles in the flat sws grid.  0, or why it is refused
+  // alone (SPDL_HJ_ERR_BAD_GEOMETRY).
+  ResamplePool rs_pool;
+  int place_resample(int i, ImageDesc& d, const spdl_hj_image_info& p) {
+    const ResampleRequest& r = *rq.resample;
+    rs::ResampleDesc t;
+    int bands, chunks;
+    if (const int rc = r.place(r.cache, r.filter, r.items ? &r.items[i] : nullptr, p.width, p.height,
+                               r.out_w, r.out_h, L.tables, rs_pool, &t, &bands, &chunks))
+      return rc;
+    L.resample[i] = t;
+    L.resample_lds = std::max(L.resample_lds, rs::lds_layout(t).words * 4);
+    d.sws_wg0 = (int32_t)L.sws_wgs;
+    d.sws_bands = bands;
+    d.sws_chunks = chunks;
+    L.sws_wgs += (int64_t)bands * chunks;
+    return SPDL_HJ_OK;
+  }
+
   // One flag per descriptor, once every descriptor stands; none when every
   // flip is 0.  A flipped full-resolution batch takes the generic output
   // kernel (the unscaled converters do not flip).
@@ -880,8 +933,11 @@ struct Planner {
 
 LayoutResult build_layout(const LayoutRequest& rq, Layout& L) {
   Planner P{rq, L};
-  if (P.check_flips() || P.check_ragged() || P.check_lowres() || P.check_turbo()) return P.res;
+  if (P.check_flips() || P.check_ragged() || P.check_lowres() || P.check_turbo() ||
+      P.check_resample())
+    return P.res;
   L.desc.assign(rq.n, ImageDesc{});
+  if (rq.resample) L.resample.assign(rq.n, rs::ResampleDesc{});
   if (rq.ragged) P.fused_image.assign(rq.n, 0);
   if (rq.views) P.index_views();
   for (int i = 0; i < rq.n; i++)

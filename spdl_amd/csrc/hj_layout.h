@@ -8,6 +8,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <map>
 #include <memory>
 #include <utility>
 #include <vector>
@@ -135,6 +136,12 @@ struct Layout {
   // planes, windows and plans of an image with L > 0 are the reduced frame's.
   std::vector<uint8_t> lowres;
   int lowres_images = 0;  // images with L > 0
+  // A resampled submission (spdl_hj_set_resample): one record per image for
+  // resample_kernel, whose tiles stand in the flat sws grid and whose axis
+  // tables lie in `tables`; resample_lds: the most LDS a tile of it takes
+  // (bytes).  Empty otherwise.
+  std::vector<rs::ResampleDesc> resample;
+  int resample_lds = 0;
 };
 
 // The frame FFmpeg's decoder emits at lowres L: ceil(x / 2^L) a side
@@ -159,6 +166,30 @@ struct HeldViews {
   std::vector<Group> groups;
   bool bad = false;
   bool any() const { return bad || !groups.empty(); }
+};
+
+// What spdl_hj_set_resample left for the next submission: the filter, the one
+// output box, and n items (items null: every image's whole frame).  The
+// coefficient rule and the tiler live in hj_resample.cpp, which the planner
+// reaches through `place` (rs::place_into, with `cache` its rs::AxisCache) --
+// a pointer, so that hj_layout.cpp links without that unit, as its older
+// stand-alone programs build it.  place: image `it` of a W x H frame into
+// out_w x out_h -- its record with the tables' offsets, its tiles; the axes'
+// tables appended to `tables`, each once per submission (pool).  0, or why
+// the image is refused alone.
+struct ResamplePool {
+  std::map<const void*, int64_t> placed;
+  std::vector<std::shared_ptr<const void>> alive;
+};
+using ResamplePlaceFn = int (*)(void* cache, int filter, const spdl_hj_resample_item* it, int W,
+                                int H, int out_w, int out_h, std::vector<int32_t>& tables,
+                                ResamplePool& pool, rs::ResampleDesc* d, int* bands, int* chunks);
+struct ResampleRequest {
+  int filter, out_w, out_h;
+  const spdl_hj_resample_item* items;
+  int64_t n;
+  void* cache;
+  ResamplePlaceFn place;
 };
 
 // One submission as the planner sees it: n images at offsets[i], sizes[i] of
@@ -194,6 +225,8 @@ struct LayoutRequest {
   // spdl_hj_set_lowres: nlowres levels (0..3), one per image; null: none
   const uint8_t* lowres = nullptr;
   int64_t nlowres = 0;
+  // spdl_hj_set_resample: the submission is a resampled one (null: not)
+  const ResampleRequest* resample = nullptr;
 };
 
 // The chain that runs ahead of a transpose: the output spec describes the

@@ -1,0 +1,257 @@
+// hj_resample.cpp -- the coefficient rule, the axis cache and the tiler of the
+// Pillow-exact resize (hj_resample.h).  Built with -ffp-contract=off: the
+// rule's doubles are evaluated in the order written, nothing fused.
+#include "hj_resample.h"
+
+#include <math.h>
+
+#include <algorithm>
+
+namespace hj {
+namespace rs {
+namespace {
+
+double f_bilinear(double x) {
+  if (x < 0.0) x = -x;
+  return x < 1.0 ? 1.0 - x : 0.0;
+}
+double f_bicubic(double x) {
+  const double a = -0.5;
+  if (x < 0.0) x = -x;
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+  return 0.0;
+}
+double sinc(double x) {
+  if (x == 0.0) return 1.0;
+  x = x * M_PI;
+  return sin(x) / x;
+}
+double f_lanczos(double x) { return -3.0 <= x && x < 3.0 ? sinc(x) * sinc(x / 3) : 0.0; }
+
+struct Filter {
+  double (*f)(double);
+  double support;
+};
+bool filter_of(int filter, Filter* out) {
+  switch (filter) {
+    case SPDL_HJ_FILTER_BILINEAR: *out = {f_bilinear, 1.0}; return true;
+    case SPDL_HJ_FILTER_BICUBIC: *out = {f_bicubic, 2.0}; return true;
+    case SPDL_HJ_FILTER_LANCZOS: *out = {f_lanczos, 3.0}; return true;
+  }
+  return false;
+}
+
+// Output xx's sample range [xmin, xmax) and its centre
+struct Span {
+  int xmin, xmax;
+  double center;
+};
+Span span_of(int xx, int in, double scale, double support) {
+  const double center = 0.0 + (xx + 0.5) * scale;
+  Span s;
+  s.center = center;
+  s.xmin = std::max((int)(center - support + 0.5), 0);
+  s.xmax = std::min((int)(center + support + 0.5), in);
+  return s;
+}
+bool sizes_ok(int in, int out) { return in >= 1 && in <= 65535 && out >= 1 && out <= 65535; }
+
+}  // namespace
+
+int axis_taps(int in, int out, int filter) {
+  Filter flt;
+  if (!sizes_ok(in, out) || !filter_of(filter, &flt)) return 0;
+  const double scale = (double)(in - 0) / out;
+  const double support = flt.support * std::max(scale, 1.0);
+  int taps = 0;
+  for (int xx = 0; xx < out; xx++) {
+    const Span s = span_of(xx, in, scale, support);
+    taps = std::max(taps, s.xmax - s.xmin);
+  }
+  return taps;
+}
+
+std::shared_ptr<const Axis> make_axis(int in, int out, int filter, int* rc) {
+  Filter flt;
+  if (!sizes_ok(in, out) || !filter_of(filter, &flt)) {
+    *rc = SPDL_HJ_ERR_INVALID_ARG;
+    return nullptr;
+  }
+  const int ksize = axis_taps(in, out, filter);
+  if (ksize < 1 || ksize > kMaxTaps) {
+    *rc = SPDL_HJ_ERR_BAD_GEOMETRY;
+    return nullptr;
+  }
+  auto a = std::make_shared<Axis>();
+  a->in = in;
+  a->out = out;
+  a->filter = filter;
+  a->ksize = ksize;
+  a->blob.assign(2 * (size_t)out + (size_t)out * ksize, 0);
+  int32_t* xmin = a->blob.data();
+  int32_t* n = xmin + out;
+  int32_t* K = n + out;
+  const double scale = (double)(in - 0) / out;
+  const double filterscale = std::max(scale, 1.0);
+  const double support = flt.support * filterscale;
+  const double ss = 1.0 / filterscale;
+  std::vector<double> w(ksize);
+  for (int xx = 0; xx < out; xx++) {
+    const Span s = span_of(xx, in, scale, support);
+    const int cnt = s.xmax - s.xmin;
+    double ww = 0.0;
+    for (int x = 0; x < cnt; x++) {
+      w[x] = flt.f((x + s.xmin - s.center + 0.5) * ss);
+      ww += w[x];
+    }
+    xmin[xx] = s.xmin;
+    n[xx] = cnt;
+    for (int x = 0; x < cnt; x++) {
+      const double k = ww != 0.0 ? w[x] / ww : w[x];
+      K[(size_t)xx * ksize + x] = k < 0 ? (int)(-0.5 + k * (double)(1 << kCoefBits))
+                                        : (int)(0.5 + k * (double)(1 << kCoefBits));
+    }
+  }
+  *rc = SPDL_HJ_OK;
+  return a;
+}
+
+std::shared_ptr<const Axis> AxisCache::get(int in, int out, int filter, int* rc) {
+  const auto key = std::make_tuple(in, out, filter);
+  auto it = held.find(key);
+  if (it != held.end()) {
+    *rc = SPDL_HJ_OK;
+    return it->second;
+  }
+  auto a = make_axis(in, out, filter, rc);
+  if (!a) return nullptr;
+  if (held.size() >= kCap) held.clear();
+  held.emplace(key, a);
+  return a;
+}
+
+int resolve(const spdl_hj_resample_item* it, int W, int H, int out_w, int out_h, Geo* g) {
+  *g = Geo{0, 0, W, H, out_w, out_h, 0, 0};
+  if (!it) return SPDL_HJ_OK;
+  if (it->box.w != 0) {
+    const spdl_hj_rect& b = it->box;
+    if (b.x < 0 || b.y < 0 || b.w < 1 || b.h < 1 || b.x > W - b.w || b.y > H - b.h)
+      return SPDL_HJ_ERR_BAD_GEOMETRY;
+    g->bx = b.x;
+    g->by = b.y;
+    g->bw = b.w;
+    g->bh = b.h;
+  }
+  if (it->rw) g->rw = it->rw;
+  if (it->rh) g->rh = it->rh;
+  g->ox = it->ox;
+  g->oy = it->oy;
+  if (g->rw < 1 || g->rw > 65535 || g->rh < 1 || g->rh > 65535 || g->ox < 0 || g->oy < 0 ||
+      g->ox > g->rw - out_w || g->oy > g->rh - out_h)
+    return SPDL_HJ_ERR_BAD_GEOMETRY;
+  return SPDL_HJ_OK;
+}
+
+int tile(const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h, ResampleDesc* d,
+         int* bands, int* chunks) {
+  ResampleDesc t{};
+  t.bx = g.bx;
+  t.by = g.by;
+  t.ox = g.ox;
+  t.oy = g.oy;
+  t.kh = H.ksize;
+  t.kv = V.ksize;
+  t.tw = 8;  // (8, 16, 32 or 64: halving keeps it a multiple of the store's 8 columns)
+  while (t.tw < kTileW && t.tw < out_w) t.tw *= 2;
+  t.th = kTileH;
+  while (t.th > 1 && t.th / 2 >= out_h) t.th /= 2;
+  t.sr = kStripRows;
+  for (;;) {
+    // the widest and the tallest source window of a tile of this size
+    const int nx = (out_w + t.tw - 1) / t.tw, ny = (out_h + t.th - 1) / t.th;
+    int cols = 0, rows = 0;
+    for (int i = 0; i < nx; i++) {
+      const Window w = tile_window(H.xmin(), H.n(), g.bx, g.ox, out_w, t.tw, i, 8);
+      cols = std::max(cols, w.hi - w.lo);
+    }
+    for (int j = 0; j < ny; j++) {
+      const Window w = tile_window(V.xmin(), V.n(), g.by, g.oy, out_h, t.th, j, 2);
+      rows = std::max(rows, w.hi - w.lo);
+    }
+    while (t.sr > 2 && t.sr / 2 >= rows) t.sr /= 2;  // (no strip taller than the window)
+    t.pitch = ((cols + 7) & ~7) | 1;
+    t.rows = rows;
+    const LdsLayout l = lds_layout(t);
+    if (l.words * 4 <= kLdsBudget) {
+      *d = t;
+      *bands = ny;
+      *chunks = nx;
+      return SPDL_HJ_OK;
+    }
+    // shrink what takes the most: the strip by its rows (down to 16: a wave's
+    // lanes run along them) and then by the tile's columns, the intermediate
+    // and the coefficient rows by the tile's rows first
+    const int strip = t.sr * t.pitch, rest = l.words - strip;
+    if (strip >= rest) {
+      if (t.sr > 16) t.sr /= 2;
+      else if (t.tw > 8) t.tw /= 2;
+      else if (t.sr > 2) t.sr /= 2;
+      else if (t.th > 1) t.th /= 2;
+      else break;
+    } else {
+      if (t.th > 1) t.th /= 2;
+      else if (t.tw > 8) t.tw /= 2;
+      else if (t.sr > 2) t.sr /= 2;
+      else break;
+    }
+  }
+  *d = ResampleDesc{};
+  *bands = *chunks = 0;
+  return SPDL_HJ_ERR_BAD_GEOMETRY;
+}
+
+int place(AxisCache& cache, int filter, const spdl_hj_resample_item* it, int W, int H, int out_w,
+          int out_h, Placed* out) {
+  Geo g;
+  int rc = resolve(it, W, H, out_w, out_h, &g);
+  if (rc) return rc;
+  out->H = cache.get(g.bw, g.rw, filter, &rc);
+  if (!out->H) return rc;
+  out->V = cache.get(g.bh, g.rh, filter, &rc);
+  if (!out->V) return rc;
+  return tile(*out->H, *out->V, g, out_w, out_h, &out->d, &out->bands, &out->chunks);
+}
+
+int place_into(void* cache, int filter, const spdl_hj_resample_item* it, int W, int H, int out_w,
+               int out_h, std::vector<int32_t>& tables, ResamplePool& pool, ResampleDesc* d,
+               int* bands, int* chunks) {
+  Placed pl;
+  if (const int rc = place(*static_cast<AxisCache*>(cache), filter, it, W, H, out_w, out_h, &pl))
+    return rc;
+  int64_t at[2];
+  const std::shared_ptr<const Axis> axes[2] = {pl.H, pl.V};
+  for (int k = 0; k < 2; k++) {
+    auto f = pool.placed.find(axes[k].get());
+    if (f == pool.placed.end()) {
+      f = pool.placed.emplace(axes[k].get(), (int64_t)tables.size()).first;
+      pool.alive.push_back(axes[k]);  // (the cache may let go of it before the submission ends)
+      tables.insert(tables.end(), axes[k]->blob.begin(), axes[k]->blob.end());
+    }
+    at[k] = f->second;
+  }
+  if ((int64_t)tables.size() > INT32_MAX) return SPDL_HJ_ERR_BAD_GEOMETRY;
+  *d = pl.d;
+  d->hx = (int32_t)at[0];
+  d->hn = d->hx + pl.H->out;
+  d->hk = d->hn + pl.H->out;
+  d->vx = (int32_t)at[1];
+  d->vn = d->vx + pl.V->out;
+  d->vk = d->vn + pl.V->out;
+  *bands = pl.bands;
+  *chunks = pl.chunks;
+  return SPDL_HJ_OK;
+}
+
+}  // namespace rs
+}  // namespace hj

@@ -14,6 +14,7 @@ from ._image import (
     load_image_batch_nvjpeg,
     load_image_list,
     load_image_views,
+    pil_resize,
 )
 from ._preprocessing import get_video_filter_desc, parse_image_filter
 from ._tar import TarImageStream, iter_tarfile
@@ -54,6 +55,7 @@ __all__ = [
     "nv12_to_bgr",
     "nv12_to_rgb",
     "parse_image_filter",
+    "pil_resize",
     "to_numpy",
     "to_torch",
     "transfer_buffer",

@@ -133,14 +133,15 @@ def _alloc_out(cfg: CUDAConfig, shape, dtype) -> CUDABuffer:
 
 
 def _decode(datas: list, out: Output, cfg: CUDAConfig, shape_per_image, batched: bool,
-            dtype=torch.uint8, crops=None, flips=None, orients=None, lowres=None) -> CUDABuffer:
+            dtype=torch.uint8, crops=None, flips=None, orients=None, lowres=None,
+            resample=None) -> CUDABuffer:
     n = len(datas)
     shape = (n, *shape_per_image) if batched else tuple(shape_per_image)
     buf = _alloc_out(cfg, shape, dtype)
     dec = _lib.thread_decoder(cfg.device_index)
     nbytes = int(np.prod(shape)) * (1 if dtype == torch.uint8 else 2)
     dec.decode_batch(datas, out, buf.data_ptr(), nbytes, stream=_stream(cfg), sync=True,
-                     crops=crops, flips=flips, orients=orients, lowres=lowres)
+                     crops=crops, flips=flips, orients=orients, lowres=lowres, resample=resample)
     return buf
 
 
@@ -351,6 +352,81 @@ def _check_csc(csc: str, *, width=None, height=None, crops=None, flips=None,
         raise ValueError(f"csc='turbo' is the full-resolution decode alone: it takes no {bad}")
 
 
+@dataclass(frozen=True)
+class PilResize:
+    """What :func:`pil_resize` returns: ``resample=`` of :func:`load_image` and
+    :func:`load_image_batch`."""
+    size: tuple
+    filter: str = "bilinear"
+    boxes: tuple | None = None
+    shorter: int | None = None
+
+    def geometry(self, width: int, height: int, box=None):
+        """One image's item ``(box, (rw, rh), (ox, oy))`` for a ``width x
+        height`` frame: ``box`` (or the frame) resized to ``size``; with
+        ``shorter`` its shorter side resized to that, the other to ``int(shorter
+        * long / short)``, and the centred ``size`` window written -- its
+        corner ``int(round((rh - h) / 2.0))``, ``int(round((rw - w) / 2.0))``.
+        These restate torchvision's ``Resize(int)`` and ``CenterCrop`` on a PIL
+        image; a window larger than the resized picture is refused by the
+        decoder (torchvision would pad)."""
+        w, h = self.size
+        if self.shorter is None:
+            return box, (w, h), (0, 0)
+        sw, sh = (box[2], box[3]) if box is not None else (width, height)
+        if sw <= sh:
+            rw, rh = self.shorter, int(self.shorter * sh / sw)
+        else:
+            rw, rh = int(self.shorter * sw / sh), self.shorter
+        return box, (rw, rh), (int(round((rw - w) / 2.0)), int(round((rh - h) / 2.0)))
+
+
+def pil_resize(size, filter: str = "bilinear", boxes=None, shorter=None) -> PilResize:
+    """Pillow's ``Image.resize`` on the GPU, for ``csc="turbo"``: the output is
+    ``np.asarray(Image.open(f).convert("RGB").crop(box).resize(size, filter))``
+    byte for byte (include/spdl_hipjpeg.h "Pillow-exact resize").  ``size=(w,
+    h)``: every image's output.  ``filter``: ``"bilinear"``, ``"bicubic"`` or
+    ``"lanczos"``.  ``boxes``: per image a source rectangle ``(x, y, w, h)`` or
+    ``None`` -- ``RandomResizedCrop``'s crop.  ``shorter``: resize the shorter
+    side to this and write the centred ``size`` window -- ``Resize(shorter)``
+    then ``CenterCrop(size)`` (:meth:`PilResize.geometry`)."""
+    if len(size) != 2 or any(int(v) != v or not 1 <= v <= 65535 for v in size):
+        raise ValueError(f"size is (width, height), each 1..65535, not {size!r}")
+    if filter not in _lib.FILTERS:
+        raise ValueError(f"filter must be one of {sorted(_lib.FILTERS)}, not {filter!r}")
+    if shorter is not None and (int(shorter) != shorter or not 1 <= shorter <= 65535):
+        raise ValueError(f"shorter is 1..65535, not {shorter!r}")
+    if boxes is not None:
+        boxes = tuple(None if b is None else tuple(int(v) for v in b) for b in boxes)
+        if any(b is not None and len(b) != 4 for b in boxes):
+            raise ValueError("a box is (x, y, w, h) or None")
+    return PilResize((int(size[0]), int(size[1])), filter, boxes,
+                     None if shorter is None else int(shorter))
+
+
+def _check_resample(resample, csc, n_src, filter_desc, pix_fmt) -> None:
+    """``resample=`` against what goes with it, before anything is read; what
+    ``csc="turbo"`` excludes is :func:`_check_csc`'s to refuse."""
+    if resample is None:
+        return
+    if not isinstance(resample, PilResize):
+        raise ValueError("resample= takes what pil_resize() returns")
+    if csc != "turbo":
+        raise ValueError(f"resample= needs csc='turbo', not {csc!r}")
+    if resample.boxes is not None and len(resample.boxes) != n_src:
+        raise ValueError(f"{len(resample.boxes)} boxes for {n_src} images")
+    if filter_desc is not None and filter_desc != _FILTER_DESC_DEFAULT:
+        _with_csc(parse_image_filter(filter_desc, default_pix_fmt=pix_fmt), csc)
+
+
+def _resample_of(resample: PilResize, infos, keep) -> _lib.Resample:
+    """The decoder's request for the images ``keep`` of the sources."""
+    boxes = resample.boxes
+    items = tuple(resample.geometry(i.width, i.height, None if boxes is None else boxes[k])
+                  for i, k in zip(infos, keep))
+    return _lib.Resample(resample.filter, *resample.size, items)
+
+
 def _csc_pix_fmt(filter_desc, pix_fmt):
     """The ``pix_fmt`` :func:`_check_csc` judges: none without a chain; the
     argument with the default chain; with a chain of the caller's the chain
@@ -391,6 +467,7 @@ def load_image_batch(
     exif_orientation: bool = False,
     lowres=None,
     csc: str = "swscale",
+    resample=None,
     **kwargs,
 ):
     """Batch load images into one ``[B,H,W,3]`` buffer with the FFmpeg filter
@@ -443,7 +520,10 @@ def load_image_batch(
     decoder, ``np.asarray(PIL.Image.open(f).convert("RGB"))`` byte for byte --
     for files of one size at that size: ``width=None, height=None``, an RGB
     ``pix_fmt``, and none of ``crops``, ``flips``, ``exif_orientation``,
-    ``lowres`` (files of mixed sizes: :func:`load_image_list`)."""
+    ``lowres`` (files of mixed sizes: :func:`load_image_list`).
+    ``resample=pil_resize(size, ...)`` with it: every file, whatever its size,
+    through Pillow's ``Image.resize`` into one ``[B, h, w, 3]`` buffer
+    (:func:`pil_resize`)."""
     if not srcs:
         raise ValueError("`srcs` must not be empty.")
     storage = kwargs.pop("storage", None)
@@ -453,6 +533,7 @@ def load_image_batch(
     _check_csc(csc, width=width, height=height, crops=crops, flips=flips,
                exif_orientation=exif_orientation, lowres=lowres,
                pix_fmt=_csc_pix_fmt(filter_desc, pix_fmt))
+    _check_resample(resample, csc, len(srcs), filter_desc, pix_fmt)
     if filter_desc == _FILTER_DESC_DEFAULT:
         filter_desc = get_video_filter_desc(
             scale_width=width, scale_height=height, pix_fmt=pix_fmt
@@ -553,9 +634,13 @@ def load_image_batch(
         shape = _yuv_shape(infos, out, src)
     else:
         shape = _shape(out, ow, oh)
+    rs = None
+    if resample is not None:  # (every image leaves at the request's size)
+        rs = _resample_of(resample, infos, keep)
+        shape = _shape(out, *resample.size)
     try:
         buf = _decode(datas, out, cfg, shape, True, dtype=dtype, crops=crops, flips=flips,
-                      orients=orients, lowres=levels)
+                      orients=orients, lowres=levels, resample=rs)
     except RuntimeError:
         if strict:
             raise
@@ -567,7 +652,9 @@ def load_image_batch(
                                     crops=None if crops is None else [crops[k]],
                                     flips=None if flips is None else [flips[k]],
                                     orients=None if orients is None else [orients[k]],
-                                    lowres=None if levels is None else [levels[k]]))
+                                    lowres=None if levels is None else [levels[k]],
+                                    resample=rs and _lib.Resample(rs.filter, rs.out_w, rs.out_h,
+                                                                  (rs.items[k],))))
             except RuntimeError as err:
                 _LG.error("Failed to decode an image: %s", err)
         if not good:
@@ -953,6 +1040,7 @@ def load_image(
     exif_orientation: bool = False,
     lowres=None,
     csc: str = "swscale",
+    resample=None,
     **kwargs,
 ):
     """Single image.  ``filter_desc=None`` returns the decoded planes in the
@@ -971,13 +1059,18 @@ def load_image(
     decode of :func:`load_image_batch`.  ``csc="turbo"`` (an extension):
     ``np.asarray(PIL.Image.open(f).convert("RGB"))`` byte for byte, in the
     ``pix_fmt``'s layout -- libjpeg-turbo's default decoder; no scaling chain,
-    ``flip``, ``exif_orientation`` or ``lowres`` with it."""
+    ``flip``, ``exif_orientation`` or ``lowres`` with it;
+    ``resample=pil_resize(size, ...)`` resizes it as Pillow's ``Image.resize``
+    does (:func:`pil_resize`)."""
     kwargs.pop("name", None)  # only names the source in FFmpeg demux errors
     lowres = _ffmpeg_configs(kwargs, lowres)
     if kwargs:
         raise TypeError(f"unexpected arguments: {sorted(kwargs)}")
     _check_csc(csc, flips=flip or None, exif_orientation=exif_orientation, lowres=lowres,
                pix_fmt=_csc_pix_fmt(filter_desc, pix_fmt))
+    _check_resample(resample, csc, 1, filter_desc, pix_fmt)
+    if resample is not None and filter_desc is None:
+        raise ValueError("resample= needs an RGB pix_fmt: it converts to RGB")
     cfg = device_config or _default_config()
     data = _read(src)
     flip = _lib._flip(flip)
@@ -1012,7 +1105,11 @@ def load_image(
         shape = _yuv_shape([info], out, src)
     else:
         shape = _shape(out, *_oriented_size(src, out, _lib._orient(out.orient)))
-    buf = _decode([data], out, cfg, shape, False, lowres=levels)
+    rs = None
+    if resample is not None:
+        rs = _resample_of(resample, [info], [0])
+        shape = _shape(out, *resample.size)
+    buf = _decode([data], out, cfg, shape, False, lowres=levels, resample=rs)
     if device_config is None:
         return _to_host(buf)
     return buf
