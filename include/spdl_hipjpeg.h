@@ -662,6 +662,39 @@ int spdl_hj_set_resample(spdl_hj_ctx* ctx, int32_t filter, int32_t out_w, int32_
 int spdl_hj_debug_resample_axis(int32_t in_size, int32_t out_size, int32_t filter, int32_t* xmin,
                                 int32_t* n, int32_t* K, int64_t cap, int32_t* ksize);
 
+/* ---- Pillow-exact draft (additive in ABI 7: one call, one parameter) ----
+ * libjpeg-turbo's scaled decode, scale_num / scale_denom = (8 >> L) / 8, which
+ * Pillow reaches through Image.draft() and Image.thumbnail(): one level 0..3
+ * per image of the NEXT batch submission (one-shot, like spdl_hj_set_lowres),
+ * with csc = SPDL_HJ_CSC_TURBO alone.  The frame of an image at level L is
+ * ceil(W P / 8) x ceil(H P / 8), P = 8 >> L, byte for byte what Pillow 12 /
+ * libjpeg-turbo 3 decode after im.draft():
+ *  - the transform size is per component: a component (h, v) of a frame with
+ *    factors (hmax, vmax) starts at P and doubles while it is below 8 and
+ *    (hmax P) % (2 h P_c) == 0 and (vmax P) % (2 v P_c) == 0 -- a subsampled
+ *    component's IDCT is enlarged instead of its plane upsampled.  P_c = 8 is
+ *    the islow transform, 4 / 2 / 1 jidctred.c's reduced ones, which read rows
+ *    and columns {0,1,2,3,5,6,7} / {0,1,3,5,7} / the DC of the block;
+ *  - what ratio remains, (hmax P) / (h P_c) an axis, takes the upsampling
+ *    rules of csc = TURBO, except at level 3, where every ratio replicates;
+ *  - the colour tables are unchanged.
+ * Taken: plain submissions (every draft frame one size), ragged submissions,
+ * and submissions with spdl_hj_set_resample, whose boxes and sizes are then in
+ * the draft frame's coordinates, as after im.draft() in Pillow; the RGB / BGR
+ * formats in u8 / f16 / bf16; baseline, progressive and non-interleaved files;
+ * gray, every sampling csc = TURBO takes, RGB-coded files.  A 4-component
+ * frame stays SPDL_HJ_ERR_UNSUPPORTED.
+ * Refused by the submission with SPDL_HJ_ERR_INVALID_ARG, nothing written: a
+ * level above 3, a count other than the batch's, any other csc, and crops,
+ * views, flips, orientations or spdl_hj_set_lowres together with it.
+ * All-zero levels are the submission without the call: the same plan, the
+ * same launches.  The read-only parameter "draft_images" reports the images
+ * with a level above 0 in the last submission, "planes_bytes" its planes.
+ * Out of scope: libjpeg's block smoothing (it acts on progressive files whose
+ * scans stop short, which fail here), Pillow's reducing_gap and float boxes,
+ * scales other than 1/2, 1/4, 1/8. */
+int spdl_hj_set_draft(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n);
+
 /* ABI version of the loaded library (== SPDL_HJ_ABI_VERSION). */
 int spdl_hj_abi_version(void);
 
@@ -918,7 +951,9 @@ const char* spdl_hj_stage_name(int32_t i);
  * bytes of the component planes it laid out in the workspace;
  * "turbo_workgroups" (with the Pillow-exact decode), the workgroups of
  * turbo_rgb_kernel in the last submission; "resample_workgroups" (with the
- * Pillow-exact resize), those of resample_kernel.
+ * Pillow-exact resize), those of resample_kernel; "draft_images" (with the
+ * Pillow-exact draft), the images of the last submission with a draft level
+ * above 0.
  * Builds with -DHJ_ABLATIONS=1 also take "debug_mask" (timing ablations that
  * skip kernel phases; outputs wrong); release builds reject it. */
 int spdl_hj_set_param(spdl_hj_ctx* ctx, const char* name, int64_t value);

@@ -65,6 +65,7 @@ EXPORTED = (
     "spdl_hj_set_lowres",
     "spdl_hj_set_resample",
     "spdl_hj_debug_resample_axis",
+    "spdl_hj_set_draft",
 )
 
 
@@ -468,6 +469,8 @@ def lib() -> ctypes.CDLL:
             L.spdl_hj_set_resample.argtypes = [vp, i32, i32, i32, vp, i64]
             L.spdl_hj_debug_resample_axis.argtypes = [i32, i32, i32, vp, vp, vp, i64,
                                                       ctypes.POINTER(i32)]
+        if hasattr(L, "spdl_hj_set_draft"):  # (likewise)
+            L.spdl_hj_set_draft.argtypes = [vp, vp, i32]
         ver = L.spdl_hj_abi_version()
         # (an explicitly chosen older build, ABI >= 5, loads for A/B runs)
         if ver != ABI_VERSION and not (os.environ.get("SPDL_AMD_LIB") and 5 <= ver < ABI_VERSION):
@@ -625,8 +628,64 @@ def lowres_levels(lowres, infos, out: Output, orients=None) -> list[int] | None:
     return levels if any(levels) else None
 
 
+def draft_size(width: int, height: int, level: int) -> tuple[int, int]:
+    """The frame libjpeg-turbo decodes at draft level ``level`` (scale
+    ``(8 >> level) / 8``): ``ceil(width P / 8) x ceil(height P / 8)``."""
+    p = 8 >> level
+    return (width * p + 7) // 8, (height * p + 7) // 8
+
+
+def draft_level(width: int, height: int, rw: int, rh: int) -> int:
+    """The level Pillow's ``Image.draft(mode, (rw, rh))`` takes for a ``width x
+    height`` file: the largest scale of 8, 4, 2, 1 not above
+    ``min(width // rw, height // rh)``."""
+    if rw < 1 or rh < 1:
+        raise ValueError(f"a draft request is (w, h) with both at least 1, not {(rw, rh)!r}")
+    s = min(width // rw, height // rh)
+    return 3 if s >= 8 else 2 if s >= 4 else 1 if s >= 2 else 0
+
+
+def draft_levels(draft, infos, sizes=None) -> list[int] | None:
+    """``draft=`` as one level per image: an int ``0..3`` for every image, a
+    list with one entry per image, a ``(w, h)`` tuple -- Pillow's request,
+    resolved per image by :func:`draft_level` -- or ``"auto"``, which needs
+    ``sizes`` (per image the ``(w, h)`` its output must be covered by: the
+    largest level whose frame is no smaller on either side, ``thumbnail``'s
+    rule without ``reducing_gap``).  ``None`` when it asks for nothing."""
+    n = len(infos)
+    if draft is None:
+        return None
+
+    def check(v):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 3:
+            raise ValueError(f"draft level {v!r} is not in 0..3")
+        return v
+    if isinstance(draft, str):
+        if draft != "auto":
+            raise ValueError(f'draft= takes 0..3, a list of them, a (w, h) request or "auto", not {draft!r}')
+        if sizes is None:
+            raise ValueError('draft="auto" needs resample=pil_resize(...): it covers the requested output')
+        levels = []
+        for i, (w, h) in zip(infos, sizes):
+            lv = 0
+            while lv < 3 and all(a >= b for a, b in zip(draft_size(i.width, i.height, lv + 1), (w, h))):
+                lv += 1
+            levels.append(lv)
+    elif isinstance(draft, tuple):
+        if len(draft) != 2:
+            raise ValueError(f"a draft request is (w, h), not {draft!r}")
+        levels = [draft_level(i.width, i.height, int(draft[0]), int(draft[1])) for i in infos]
+    elif isinstance(draft, int):
+        levels = [check(draft)] * n
+    else:
+        levels = [check(v) for v in draft]
+        if len(levels) != n:
+            raise ValueError(f"{len(levels)} draft levels for a batch of {n} images")
+    return levels if any(levels) else None
+
+
 def ragged_layout(infos, out: Output, crops=None, orients=None, align: int = 256,
-                  lowres=None) -> tuple[list[int], list[tuple[int, int]], list[int]]:
+                  lowres=None, draft=None) -> tuple[list[int], list[tuple[int, int]], list[int]]:
     """``(offsets, sizes, statuses)`` of a ragged batch (spdl_hj_ragged_layout;
     host only): every image's final ``(ow, oh)`` resolved alone -- its source
     crop, the chain of ``out``, its orientation -- and packed at multiples of
@@ -634,14 +693,19 @@ def ragged_layout(infos, out: Output, crops=None, orients=None, align: int = 256
     size.  An image whose crop or geometry does not resolve has its status, a
     ``(0, 0)`` size and no bytes.  ``infos``: a sequence of ImageInfo.
     ``lowres`` (:func:`lowres_levels`): the boxes are those of the reduced
-    frames."""
+    frames; ``draft`` (levels, one per image): those of the draft frames."""
     n = len(infos)
     levels = lowres_levels(lowres, infos, out, orients)
+    size_of = lowres_size
+    if draft is not None:
+        if levels is not None:
+            raise ValueError("lowres= and draft= are exclusive")
+        levels, size_of = list(draft), draft_size
     if levels is not None:  # (the library sizes boxes from the probes: hand it reduced ones)
         reduced = []
         for i, lv in zip(infos, levels):
             r = ImageInfo.from_buffer_copy(i)
-            r.width, r.height = lowres_size(i.width, i.height, lv)
+            r.width, r.height = size_of(i.width, i.height, lv)
             reduced.append(r)
         infos = reduced
     inf = infos if isinstance(infos, ctypes.Array) else (ImageInfo * max(n, 1))(*infos)
@@ -942,6 +1006,15 @@ class Decoder:
         if lib().spdl_hj_set_lowres(self._h, arr if levels else None, len(levels)):
             raise ValueError("invalid lowres levels")
 
+    def set_draft(self, levels) -> None:
+        """The draft levels of the next batch submission (spdl_hj_set_draft,
+        include/spdl_hipjpeg.h "Pillow-exact draft"): one ``0..3`` per image;
+        ``None`` or an empty sequence clears them."""
+        levels = bytes(int(v) for v in levels) if levels is not None else b""
+        arr = (ctypes.c_uint8 * max(len(levels), 1))(*levels)
+        if lib().spdl_hj_set_draft(self._h, arr if levels else None, len(levels)):
+            raise ValueError("invalid draft levels")
+
     def set_resample(self, resample: "Resample | None") -> None:
         """Make the next batch submission a resampled one
         (spdl_hj_set_resample, include/spdl_hipjpeg.h "Pillow-exact resize")."""
@@ -984,7 +1057,7 @@ class Decoder:
     def decode_batch(self, datas, out: Output, out_ptr: int, out_bytes: int, stream=None,
                      sync: bool = True, check: bool = True, crops=None, views=None,
                      flips=None, orients=None, ragged=None, lowres=None,
-                     resample=None) -> list[int]:
+                     resample=None, draft=None) -> list[int]:
         """Per-image statuses.  A failed image raises RuntimeError unless
         ``check`` is False (synchronous calls), which returns the statuses.
         ``crops``: a source crop ``(x, y, w, h)`` or ``None`` per image.
@@ -1002,7 +1075,10 @@ class Decoder:
         level ``0..3`` per image (spdl_hj_set_lowres; resolve ``"auto"`` or a
         single int with :func:`lowres_levels` first).  ``resample``: a
         :class:`Resample` -- Pillow's ``Image.resize`` of every image's
-        ``csc="turbo"`` decode into one ``out_w x out_h`` box."""
+        ``csc="turbo"`` decode into one ``out_w x out_h`` box.  ``draft``: a
+        draft level ``0..3`` per image (spdl_hj_set_draft, ``csc="turbo"``
+        alone; :func:`draft_levels` resolves requests); a resample's items are
+        then in the draft frame's coordinates."""
         n = len(datas)
         if n == 0:
             raise RuntimeError("Failed to decode an image. (the batch is empty)")
@@ -1025,10 +1101,11 @@ class Decoder:
                 _stream_handle(stream), int(bool(sync)), status, err, 1024,
             )
         return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                                    check, status, call, orients, ragged, lowres, resample))
+                                    check, status, call, orients, ragged, lowres, resample,
+                                    draft))
 
     def _submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync, check, status,
-                call, orients=None, ragged=None, lowres=None, resample=None):
+                call, orients=None, ragged=None, lowres=None, resample=None, draft=None):
         """What the three batch submissions share: the views, crops and flips
         (or orientations) go to the context, ``call(err)`` -- the method's own marshalling and
         its native call -- returns the library's code, and a failure raises
@@ -1052,6 +1129,8 @@ class Decoder:
             Decoder.set_lowres(self, lowres)
         if rs is not None:  # (what it excludes likewise)
             Decoder._set_resample_c(self, rs)
+        if draft is not None:  # (likewise)
+            Decoder.set_draft(self, draft)
         err = ctypes.create_string_buffer(1024)
         rc = call(err)
         if rc and not (not check and sync and (any(status) or _refused(views, rc))):
@@ -1062,7 +1141,7 @@ class Decoder:
                             out: Output, out_ptr: int, out_bytes: int, stream=None,
                             sync: bool = True, crops=None, check: bool = True,
                             views=None, flips=None, orients=None, ragged=None,
-                            lowres=None, resample=None) -> list[int]:
+                            lowres=None, resample=None, draft=None) -> list[int]:
         """``offsets``/``sizes``: sequences or int64 numpy arrays; ``infos``: a
         sequence of ImageInfo or a prebuilt ``(ImageInfo * n)`` array (pass the
         same objects again to skip re-marshalling on every call)."""
@@ -1082,7 +1161,8 @@ class Decoder:
                 status.ctypes.data, err, 1024,
             )
         return Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                               check, status, call, orients, ragged, lowres, resample).tolist()
+                               check, status, call, orients, ragged, lowres, resample,
+                               draft).tolist()
 
     def _spec(self, out: Output) -> OutputSpec:
         cache = self.__dict__.setdefault("_spec_cache", {})
@@ -1142,7 +1222,7 @@ class Decoder:
     def decode_staged(self, ticket: int, nbytes: int, offsets, sizes, out: Output, out_ptr: int,
                       out_bytes: int, stream=None, sync: bool = True, crops=None,
                       check: bool = True, views=None, flips=None, orients=None,
-                      ragged=None, lowres=None, resample=None) -> list[int]:
+                      ragged=None, lowres=None, resample=None, draft=None) -> list[int]:
         n = len(offsets)
         status = (ctypes.c_int32 * max(n, 1))()
 
@@ -1154,7 +1234,8 @@ class Decoder:
                 self._h, int(ticket), int(nbytes), offs, szs, n, ctypes.byref(spec), out_ptr,
                 out_bytes, _stream_handle(stream), int(bool(sync)), status, err, 1024)
         return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
-                                    check, status, call, orients, ragged, lowres, resample))[:n]
+                                    check, status, call, orients, ragged, lowres, resample,
+                                    draft))[:n]
 
     def debug_entropy(self, data, nblocks: int):
         """Coefficients / destuffed bytes / diagnostics of one image (tests)."""

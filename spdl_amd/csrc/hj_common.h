@@ -333,6 +333,31 @@ inline HJ_HD Window tile_window(const int32_t* xmin, const int32_t* n, int b0, i
 
 }  // namespace rs
 
+// ---- Pillow-exact draft (spdl_hj_set_draft; libjpeg-turbo's scale_num / 8) ----
+namespace draft {
+// Component (h, v) of a frame with factors (hmax, vmax) at frame scale P / 8
+// (P = 8 >> level): its transform size.  jdmaster.c enlarges a subsampled
+// component's IDCT instead of upsampling it, while the ratio stays whole.
+inline HJ_HD int comp_size(int P, int h, int v, int hmax, int vmax) {
+  int pc = P;
+  while (pc < 8 && (hmax * P) % (h * pc * 2) == 0 && (vmax * P) % (v * pc * 2) == 0) pc *= 2;
+  return pc;
+}
+// ceil(x num / den): a frame's or a component plane's side
+inline HJ_HD int scaled_side(int x, int num, int den) {
+  return (int)(((int64_t)x * num + den - 1) / den);
+}
+// idct_draft_kernel's lanes of a block row: 8 output bytes each
+inline HJ_HD int lanes_row(int bw, int pc) { return (bw * pc + 7) >> 3; }
+
+// One image of a draft submission, 16 bytes behind the descriptors: its level,
+// each component's transform size (8 at level 0) and the upsampling ratio
+// that remains for the output kernels, (hmax P) / (h_c P_c) an axis.
+struct Desc {
+  uint8_t level, pc[3], hr[3], vr[3], pad[6];
+};
+}  // namespace draft
+
 struct ImageInfo {      // device-filled by the parse kernel
   int32_t status;
   int32_t width, height, ncomp, hmax, vmax, mcux, mcuy, bpm, nblocks, ri;

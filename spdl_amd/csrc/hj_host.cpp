@@ -161,6 +161,7 @@ struct Slot {
       uint8_t flip;       // its output flip or orientation code (has_flips)
       uint8_t lowres;     // its reduced-size level
       spdl_hj_resample_item resample;  // its item of a resampled batch (has_resample)
+      uint8_t draft;      // its draft level (spdl_hj_set_draft)
     };
     std::vector<Item> items;
     bool has_rects = false, has_flips = false;  // the batch had crops / flips
@@ -285,6 +286,10 @@ struct spdl_hj_ctx {
   // above 0 in the last submission
   std::vector<uint8_t> lowres;
   int64_t lowres_images = 0;
+  // spdl_hj_set_draft: its draft levels, and the images with one above 0 in
+  // the last submission
+  std::vector<uint8_t> draft;
+  int64_t draft_images = 0;
   int64_t planes_bytes = 0;  // the planes the last submission laid out in the workspace
   int64_t idct_workgroups = 0;  // IDCT workgroups the last submission launched
   int64_t entropy_workgroups = 0;  // ... and its entropy work items (images, or their pieces)
@@ -474,7 +479,8 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
   // (the work list follows the descriptors, a flipped submission's flags the work list)
   HJ_HIP(grow(W.desc,
               sizeof(ImageDesc) * b->ndesc + sizeof(uint32_t) * b->nwork + L.flips.size() +
-                  L.lowres.size() + L.resample.size() * sizeof(rs::ResampleDesc),
+                  L.lowres.size() + L.resample.size() * sizeof(rs::ResampleDesc) +
+                  L.draft.size() * sizeof(draft::Desc),
               st, &b->desc));
   b->work = reinterpret_cast<uint32_t*>(b->desc + b->ndesc);
   b->flips = L.flips.empty() ? nullptr : reinterpret_cast<const uint8_t*>(b->work + b->nwork);
@@ -488,6 +494,13 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
   b->resample = L.resample.empty()
                     ? nullptr
                     : reinterpret_cast<const rs::ResampleDesc*>(b->work + b->nwork);
+  // (... and a draft submission's records behind those; it has neither flags
+  // nor levels, so they stand 4-byte aligned as well)
+  b->draft = L.draft.empty()
+                 ? nullptr
+                 : reinterpret_cast<const draft::Desc*>(
+                       reinterpret_cast<const uint8_t*>(b->work + b->nwork) +
+                       L.resample.size() * sizeof(rs::ResampleDesc));
   HJ_HIP(grow(W.chain, (size_t)(kChainHead + L.chain_granules) * 8 + 64, st, &b->chain));
   HJ_HIP(grow(W.maps, (size_t)(L.ds_wgs + L.idct_wgs + L.hs_wgs + L.sws_wgs) * 4 + 64, st,
               &b->ds_map));
@@ -584,13 +597,14 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   };
   const bool ds_flat = use_flat(L.ds_wgs, L.max_chunks);
   // (idct_lowres_kernel has the flat grid alone)
-  const bool idct_flat = B.lowres != nullptr ||
+  const bool idct_flat = B.lowres != nullptr || B.draft != nullptr ||
                          use_flat(L.idct_wgs, (L.max_blocks + kIdctThreads - 1) / kIdctThreads);
   const bool sws_flat = use_flat(L.sws_wgs, (int64_t)L.sws_bands * L.sws_chunks);
   // + work list, + the flags of a flipped submission (one byte per descriptor)
   const size_t work_end = sizeof(ImageDesc) * B.ndesc + sizeof(uint32_t) * B.nwork;
   const size_t rs_bytes = L.resample.size() * sizeof(rs::ResampleDesc);
-  const size_t desc_bytes = work_end + L.flips.size() + L.lowres.size() + rs_bytes;
+  const size_t draft_bytes = L.draft.size() * sizeof(draft::Desc);
+  const size_t desc_bytes = work_end + L.flips.size() + L.lowres.size() + rs_bytes + draft_bytes;
   HJ_HIP(slot.pin_desc.ensure(desc_bytes));
   HJ_HIP(slot.pin_status.ensure(sizeof(int32_t) * n));
   slot.n = n;
@@ -609,6 +623,13 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
     }
     memcpy(static_cast<uint8_t*>(slot.pin_desc.p) + work_end, L.resample.data(), rs_bytes);
   }
+  if (B.draft) {
+    if (!L.flips.empty() || !L.lowres.empty()) {  // (the planner refuses them together)
+      set_err(err, errlen, "a draft submission with flips or levels");
+      return SPDL_HJ_ERR_INVALID_ARG;
+    }
+    memcpy(static_cast<uint8_t*>(slot.pin_desc.p) + work_end + rs_bytes, L.draft.data(), draft_bytes);
+  }
   // the batch's swscale tables travel with the descriptors (a resampled
   // submission's axis tables likewise)
   const bool swscale = !sub.planes_only && out->csc == SPDL_HJ_CSC_SWSCALE;
@@ -619,7 +640,7 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   if (!hs) {
     HJ_HIP(hipMemcpyAsync(B.desc, slot.pin_desc.p, desc_bytes, hipMemcpyHostToDevice, st));
     if (tb) HJ_HIP(hipMemcpyAsync(B.wts, slot.pin_tables.p, tb, hipMemcpyHostToDevice, st));
-  } else if (B.flips || B.lowres || B.resample) {
+  } else if (B.flips || B.lowres || B.resample || B.draft) {
     // (parse_kernel brings over the descriptors and the work list alone: the
     // flags and levels behind them take one small copy from the same pinned pages)
     HJ_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(B.work + B.nwork),
@@ -689,10 +710,12 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   ctx->turbo_workgroups = ctx->resample_workgroups = 0;
   ctx->entropy_workgroups = B.nwork;
   ctx->lowres_images = L.lowres_images;
+  ctx->draft_images = L.draft_images;
   ctx->planes_bytes = L.total_planes;
   // (a views submission whose views were all refused has no block to transform)
   if (!(abl & kAblNoIdct) && (L.ragged || !fused) && L.max_blocks > 0) {
     if (B.lowres) HJ_HIP(launch_idct_lowres(B, idct_kind, (int)L.idct_wgs, st));
+    else if (B.draft) HJ_HIP(launch_idct_draft(B, (int)L.idct_wgs, st));
     else
       HJ_HIP(launch_idct(B, idct_kind, idct_flat, (int)L.idct_wgs, L.max_blocks,
                          (ctx->xcd_order >> 1) & 1, st));
@@ -794,7 +817,8 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
                          sub.flips ? sub.flips[m.first] : (uint8_t)0,
                          L.lowres.empty() ? (uint8_t)0 : L.lowres[m.first],
                          sub.resample && sub.resample->items ? sub.resample->items[m.first]
-                                                             : spdl_hj_resample_item{}});
+                                                             : spdl_hj_resample_item{},
+                         L.draft.empty() ? (uint8_t)0 : L.draft[m.first].level});
     }
     R.ticket = slot.ticket;
     R.bytes = sub.d_bytes;
@@ -863,6 +887,10 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
     rq.lowres = &item.lowres;
     rq.nlowres = 1;
   }
+  if (item.draft) {
+    rq.draft = &item.draft;
+    rq.ndraft = 1;
+  }
   const ResampleRequest one{r.rs_filter, r.rs_ow, r.rs_oh, &item.resample, 1, &ctx->axes, &rs::place_into};
   if (r.has_resample) rq.resample = &one;
   int rc = plan_batch(rq, L, &st1, err, errlen);
@@ -883,6 +911,7 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
   const int64_t fused_wgs = ctx->fused_workgroups, generic_wgs = ctx->generic_workgroups;
   const int64_t turbo_wgs = ctx->turbo_workgroups, resample_wgs = ctx->resample_workgroups;
   const int64_t lowres_images = ctx->lowres_images, planes_bytes = ctx->planes_bytes;
+  const int64_t draft_images = ctx->draft_images;
   rc = run_pipeline(ctx, *s, L,
                     {r.bytes, r.len, 1, &r.out, r.out_dev + item.out_off, item.out_bytes, xs, 1,
                      &st1, false, nullptr, nullptr, false, nullptr, rq.resample},
@@ -894,6 +923,7 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
   ctx->turbo_workgroups = turbo_wgs;
   ctx->resample_workgroups = resample_wgs;
   ctx->lowres_images = lowres_images;
+  ctx->draft_images = draft_images;
   ctx->planes_bytes = planes_bytes;
   ctx->last_ticket = last;
   return rc ? rc : st1;
@@ -971,7 +1001,7 @@ int take_views(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, const void* o
 struct Held {
   std::vector<spdl_hj_rect> rects;
   HeldViews views;
-  std::vector<uint8_t> flipv, orientv, lowresv;
+  std::vector<uint8_t> flipv, orientv, lowresv, draftv;
   std::vector<int64_t> raggedv;
   const int64_t* ragged = nullptr;      // null: a plain submission
   const spdl_hj_rect* crops = nullptr;  // null: none
@@ -983,6 +1013,8 @@ struct Held {
   int64_t norients = 0;
   const uint8_t* lowres = nullptr;  // reduced-size levels (the planner's to check as well)
   int64_t nlowres = 0;
+  const uint8_t* draft = nullptr;  // draft levels (the planner's to check as well)
+  int64_t ndraft = 0;
   // spdl_hj_set_resample's request (null: a plain submission; the planner's to check)
   spdl_hj_ctx::HeldResample resamplev;
   ResampleRequest resample_rq{};
@@ -1008,6 +1040,12 @@ struct Held {
     if (!lowresv.empty()) {
       lowres = lowresv.data();
       nlowres = (int64_t)lowresv.size();
+    }
+    draftv.swap(ctx->draft);
+    ctx->draft.clear();
+    if (!draftv.empty()) {
+      draft = draftv.data();
+      ndraft = (int64_t)draftv.size();
     }
     raggedv.swap(ctx->ragged);
     ctx->ragged.clear();
@@ -1105,7 +1143,7 @@ int submit(spdl_hj_ctx* ctx, const Held& held, const Batch& b, SlotRelease& slot
   int rc = plan_batch({b.offsets, b.sizes, infos, b.n, b.out, held.hv ? 0 : ctx->piece_bytes,
                        &ctx->plans, held.crops, held.hv, held.flips, held.nflips, held.orients,
                        held.norients, held.ragged, (int64_t)b.out_bytes, ctx->output_path,
-                       held.lowres, held.nlowres, held.resample},
+                       held.lowres, held.nlowres, held.resample, held.draft, held.ndraft},
                       L, b.status, err, errlen);
   if (rc) return rc;
   // the probes (the caller's own with device bytes, ABI 5) say which files
@@ -1247,6 +1285,13 @@ int spdl_hj_set_lowres(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n) {
   if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
   ctx->lowres.clear();
   if (levels && n > 0) ctx->lowres.assign(levels, levels + n);
+  return SPDL_HJ_OK;
+}
+
+int spdl_hj_set_draft(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n) {
+  if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
+  ctx->draft.clear();
+  if (levels && n > 0) ctx->draft.assign(levels, levels + n);
   return SPDL_HJ_OK;
 }
 
@@ -1522,6 +1567,7 @@ int spdl_hj_decode_planes(spdl_hj_ctx* ctx, const uint8_t* data, size_t size, in
     set_err(err, errlen, "invalid argument");
     return SPDL_HJ_ERR_INVALID_ARG;
   }
+  ctx->draft.clear();  // (draft levels are a batch submission's: none here)
   // (a one-element spdl_hj_set_lowres: consumed whatever becomes of the call)
   std::vector<uint8_t> levels;
   levels.swap(ctx->lowres);
@@ -1910,6 +1956,7 @@ int spdl_hj_get_param(spdl_hj_ctx* ctx, const char* name, int64_t* value) {
       {"handoff_retries", ctx->handoff_retries},
       {"idct_workgroups", ctx->idct_workgroups},
       {"lowres_images", ctx->lowres_images},
+      {"draft_images", ctx->draft_images},
       {"planes_bytes", ctx->planes_bytes},
       {"fused_workgroups", ctx->fused_workgroups},
       {"generic_workgroups", ctx->generic_workgroups},

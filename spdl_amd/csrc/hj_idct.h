@@ -286,4 +286,87 @@ HJ_HD inline void lowres_idct4(const int32_t* b, int bs, int32_t* o, int os) {
   }
 }
 
+// libjpeg-turbo's scaled decode (spdl_hipjpeg.h "Pillow-exact draft"): the
+// reduced transforms of jidctred.c, restated from their rules -- CONST_BITS 13,
+// PASS1_BITS 2, columns first, the same 1-D rule in both passes, the range
+// limit of islow_limit.  Unlike FFmpeg's they read outside the corner: the 4x4
+// takes rows and columns {0,1,2,3,5,6,7} of the block, the 2x2 {0,1,3,5,7}.
+// b: that operand set, dequantised, row-major 7x7 / 5x5 (b[0] the DC without
+// its +1024 bias); o: the P x P samples, row stride `os`.  Sums wrap modulo
+// 2^32 (the reference's are wider; they agree on every coefficient a JPEG file
+// can code).  The zero-column shortcut of the source is the rule itself:
+// DESCALE(r0 << 14, 12) = 4 r0 (tests/native/draft_sweep.cpp).
+constexpr int D0211 = 1730, D0509 = 4176, D0601 = 4926, D0720 = 5906, D0850 = 6967,
+              D0899 = 7373, D1061 = 8697, D1272 = 10426, D1451 = 11893, D2172 = 17799,
+              D2562 = 20995, D3624 = 29692;
+HJ_HD inline int32_t draft_mul(int32_t a, int32_t k) { return (int32_t)((uint32_t)a * (uint32_t)k); }
+HJ_HD inline int32_t draft_descale(uint32_t x, int n) {
+  return (int32_t)(x + (1u << (n - 1))) >> n;
+}
+HJ_HD inline int32_t draft_limit(int32_t v) { return islow_limit(v + 512); }
+
+HJ_HD inline int32_t draft_idct1(int32_t dc) { return draft_limit(draft_descale((uint32_t)dc, 3)); }
+
+// one 1-D pass of the 4x4: r[0..6] = r0 r1 r2 r3 r5 r6 r7 -> o[0..3], descaled by s
+HJ_HD inline void draft_pass4(const int32_t (&r)[7], int s, int32_t (&o)[4]) {
+  const uint32_t t0 = (uint32_t)r[0] << 14;
+  const uint32_t t2 = (uint32_t)draft_mul(r[2], F1847) - (uint32_t)draft_mul(r[5], F0765);
+  const uint32_t t10 = t0 + t2, t12 = t0 - t2;
+  const uint32_t a = (uint32_t)draft_mul(r[1], D1061) - (uint32_t)draft_mul(r[3], D2172) +
+                     (uint32_t)draft_mul(r[4], D1451) - (uint32_t)draft_mul(r[6], D0211);
+  const uint32_t c = (uint32_t)draft_mul(r[1], D2562) + (uint32_t)draft_mul(r[3], D0899) -
+                     (uint32_t)draft_mul(r[4], D0601) - (uint32_t)draft_mul(r[6], D0509);
+  o[0] = draft_descale(t10 + c, s);
+  o[1] = draft_descale(t12 + a, s);
+  o[2] = draft_descale(t12 - a, s);
+  o[3] = draft_descale(t10 - c, s);
+}
+
+HJ_HD inline void draft_idct4(const int32_t* b, int32_t* o, int os) {
+  int32_t ws[4][7];
+#pragma unroll
+  for (int c = 0; c < 7; c++) {
+    const int32_t r[7] = {b[c], b[7 + c], b[14 + c], b[21 + c], b[28 + c], b[35 + c], b[42 + c]};
+    int32_t t[4];
+    draft_pass4(r, 12, t);
+#pragma unroll
+    for (int k = 0; k < 4; k++) ws[k][c] = t[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    int32_t t[4];
+    draft_pass4(ws[k], 19, t);
+#pragma unroll
+    for (int x = 0; x < 4; x++) o[k * os + x] = draft_limit(t[x]);
+  }
+}
+
+// one 1-D pass of the 2x2: r[0..4] = r0 r1 r3 r5 r7 -> o[0..1], descaled by s
+HJ_HD inline void draft_pass2(const int32_t (&r)[5], int s, int32_t (&o)[2]) {
+  const uint32_t t10 = (uint32_t)r[0] << 15;
+  const uint32_t t0 = (uint32_t)draft_mul(r[1], D3624) - (uint32_t)draft_mul(r[2], D1272) +
+                      (uint32_t)draft_mul(r[3], D0850) - (uint32_t)draft_mul(r[4], D0720);
+  o[0] = draft_descale(t10 + t0, s);
+  o[1] = draft_descale(t10 - t0, s);
+}
+
+HJ_HD inline void draft_idct2(const int32_t* b, int32_t* o, int os) {
+  int32_t ws[2][5];
+#pragma unroll
+  for (int c = 0; c < 5; c++) {
+    const int32_t r[5] = {b[c], b[5 + c], b[10 + c], b[15 + c], b[20 + c]};
+    int32_t t[2];
+    draft_pass2(r, 13, t);
+    ws[0][c] = t[0];
+    ws[1][c] = t[1];
+  }
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    int32_t t[2];
+    draft_pass2(ws[k], 20, t);
+    o[k * os] = draft_limit(t[0]);
+    o[k * os + 1] = draft_limit(t[1]);
+  }
+}
+
 }  // namespace hj

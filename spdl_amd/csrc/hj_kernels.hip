@@ -5051,6 +5051,198 @@ __global__ void __launch_bounds__(kIdctThreads) idct_lowres_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// idct_draft_kernel: the IDCT stage of a submission with draft levels
+// (spdl_hj_set_draft; libjpeg-turbo's scale 1/2, 1/4, 1/8 under csc = TURBO,
+// hj_idct.h draft_idct4 / 2 / 1)
+// ---------------------------------------------------------------------------
+//
+// The transform size is per COMPONENT (draft::comp_size): a 4:2:0 file at 1/2
+// has 4x4 luma and full 8x8 chroma.  Lanes are organised by output, a lane
+// owning 8 consecutive bytes of the P_c rows of one block row of one plane --
+// 8 / P_c blocks, or the one block of a component with P_c = 8, which takes
+// idct_kernel's path and yields idct_kernel's bytes.  An image's lanes are its
+// components' in order, sum over c of ceil(bw_c P_c / 8) bh_c; the first three
+// threads of a workgroup leave each component's lanes per block row and the
+// magic of the division by it in LDS, so a lane finds (component, block row,
+// 8-byte column) with two compares and one multiplication.
+//
+// The reduced transforms read outside the corner -- rows and columns
+// {0,1,2,3,5,6,7} (4x4), {0,1,3,5,7} (2x2) -- so the whole list of a block is
+// walked, by list_block with another table: per component and zig-zag index
+// the entry's half-word in the OPERAND SET (7x7 or 5x5, row-major, two
+// operands a word, word-major over the lanes like idct_kernel's block), or the
+// dummy word for an entry in a row or column the transform does not read.  No
+// register array is indexed by data.  The 1x1 reads the descriptor alone.
+//
+// A plane's stride is 8 bytes a lane: blocks past a component's last one are
+// written as zeros, and the stage writes every byte of every plane laid out.
+
+// byte offset of operand k (two a word) in the word-major block
+__device__ __forceinline__ uint32_t draft_op_byte(uint32_t k) {
+  return (k >> 1) * (uint32_t)kIdctThreads * 4u + ((k & 1u) << 1);
+}
+// natural index 0..7 -> its place in the 4x4's / 2x2's operand rows (8: not read)
+__device__ __forceinline__ uint32_t draft_idx4(uint32_t i) { return i < 4u ? i : i == 4u ? 8u : i - 1u; }
+__device__ __forceinline__ uint32_t draft_idx2(uint32_t i) {
+  return i == 0u ? 0u : (i & 1u) ? (i + 1u) >> 1 : 8u;
+}
+
+__device__ __forceinline__ void load_dequant_draft(uint32_t (&sq)[kMaxComp][64], const ImageInfo& in,
+                                                   const draft::Desc& dr, int tid) {
+  constexpr uint32_t kDummy = (uint32_t)(kBlkWords * kIdctThreads * 4);
+  for (int k = tid; k < kMaxComp * 64; k += kIdctThreads) {
+    const int c = k >> 6;
+    const uint32_t slot = kSlotOrder[k & 63], r = slot >> 3, s = slot & 7u;
+    const uint32_t col = ((s & 3u) << 1) | (s >> 2);  // (kSlotOrder's pairing undone)
+    const int pc = c < 3 ? dr.pc[c] : 8;
+    uint32_t off = kDummy;
+    if (pc == 8) {
+      off = slot_byte<kIdctThreads>(slot);
+    } else if (pc == 4) {
+      const uint32_t ri = draft_idx4(r), ci = draft_idx4(col);
+      if (ri < 8u && ci < 8u) off = draft_op_byte(ri * 7u + ci);
+    } else if (pc == 2) {
+      const uint32_t ri = draft_idx2(r), ci = draft_idx2(col);
+      if (ri < 8u && ci < 8u) off = draft_op_byte(ri * 5u + ci);
+    }
+    sq[c][k & 63] = off | ((uint32_t)in.qt[c][k & 63] << 16);
+  }
+}
+
+// The lane's 8 / PC blocks at transform size PC (4, 2, 1): lane column gx of
+// block row by of component c, whose first block of an MCU is `base`.
+template <int PC>
+__device__ __forceinline__ void draft_lane(const uint32_t* __restrict__ ents,
+                                           const uint2* __restrict__ bdesc, const ImageDesc& dd,
+                                           const ImageInfo& in, uint8_t* __restrict__ planes,
+                                           const uint32_t* sqc, uint32_t* b32, int c, int base, int by,
+                                           int gx) {
+  constexpr int NB = 8 / PC, NOP = PC == 4 ? 49 : 25;
+  const int bw = in.comp_bw[c], hc = in.comp_h[c], vc = in.comp_v[c];
+  uint64_t acc[PC];
+#pragma unroll
+  for (int r = 0; r < PC; r++) acc[r] = 0ull;
+  uint2 bd[NB];
+#pragma unroll
+  for (int k = 0; k < NB; k++) {
+    const int bx = min(gx * NB + k, bw - 1);  // (past the last block: its neighbour, unused)
+    const int jb = in.ncomp == 1 ? by * in.mcux + bx
+                                 : ((by / vc) * in.mcux + bx / hc) * in.bpm + base + (by % vc) * hc +
+                                       bx % hc;
+    bd[k] = bdesc[(size_t)dd.coef_off + jb];
+  }
+#pragma unroll
+  for (int k = 0; k < NB; k++) {
+    if (gx * NB + k >= bw) continue;  // (past the component's last block: zeros)
+    // (the DC without its bias, as islow_block takes it)
+    const int32_t dc = sext16((uint32_t)(sext16(bd[k].y >> 16) - 1024));
+    int32_t px[PC * PC];
+    if constexpr (PC == 1) {
+      px[0] = draft_idct1(dc);
+    } else {
+      list_block<kIdctThreads>(ents, bd[k], dd.coef_off, in.nblocks, sqc, b32);
+      int32_t b[NOP + 1];
+#pragma unroll
+      for (int w = 0; w < (NOP + 1) / 2; w++) {
+        const uint32_t q = b32[w * kIdctThreads];
+        b[2 * w] = sext16(q);
+        b[2 * w + 1] = sext16(q >> 16);
+      }
+      b[0] = dc;
+      if constexpr (PC == 4) draft_idct4(b, px, 4);
+      else draft_idct2(b, px, 2);
+    }
+    // its PC bytes of each row: bytes [k PC, k PC + PC) of the lane's eight
+#pragma unroll
+    for (int r = 0; r < PC; r++) {
+      uint32_t bits = 0u;
+#pragma unroll
+      for (int x = 0; x < PC; x++) bits |= (uint32_t)px[r * PC + x] << (8 * x);
+      acc[r] |= (uint64_t)bits << (8 * k * PC);
+    }
+  }
+  const int stride = dd.plane_stride[c];
+  uint8_t* dst = planes + dd.plane_off[c] + (size_t)by * PC * stride + gx * 8;
+#pragma unroll
+  for (int r = 0; r < PC; r++)
+    *reinterpret_cast<uint2*>(dst + (size_t)r * stride) =
+        make_uint2((uint32_t)acc[r], (uint32_t)(acc[r] >> 32));
+}
+
+__global__ void __launch_bounds__(kIdctThreads) idct_draft_kernel(
+    const uint32_t* __restrict__ ents, const uint2* __restrict__ bdesc,
+    const ImageDesc* __restrict__ desc, const ImageInfo* __restrict__ infos,
+    uint8_t* __restrict__ planes, const uint32_t* __restrict__ idct_map,
+    const draft::Desc* __restrict__ drafts) {
+  __shared__ __attribute__((aligned(16))) uint32_t sblk[kBlkWords + 1][kIdctThreads];
+  __shared__ uint32_t sq[kMaxComp][64];
+  __shared__ uint32_t s_lr[3], s_magic[3];
+  const int img = (int)idct_map[blockIdx.x];
+  const ImageInfo& in = infos[img];
+  const ImageDesc& dd = desc[img];
+  const int tile = (int)blockIdx.x - dd.idct_wg0;
+  const int nb = dd.idct_blocks;  // (the image's lanes: hj_layout.h Layout::draft)
+  const draft::Desc& dr = drafts[img];  // (read where it lies: no byte of it is indexed in registers)
+  if (in.status != kOk || tile * kIdctThreads >= nb) return;
+  const int j = tile * kIdctThreads + threadIdx.x;
+  uint32_t* b32 = &sblk[0][threadIdx.x];
+  if (dr.level == 0) {  // as idct_kernel<islow> transforms it
+    load_dequant<kIdctThreads>(sq, in, threadIdx.x);
+    __syncthreads();
+    if (j >= nb) return;
+    const IdctBlockPos bp = idct_block_pos(in, (uint32_t)j);
+    list_block<kIdctThreads>(ents, bdesc[(size_t)dd.coef_off + j], dd.coef_off, in.nblocks,
+                             sq[bp.c], b32);
+    uint2 rows[8];
+    idct_block_rows<kIdctThreads, 1>(b32, rows);
+    const int stride = dd.plane_stride[bp.c];
+    uint8_t* dst = planes + dd.plane_off[bp.c] + (size_t)bp.by * 8 * stride + bp.bx * 8;
+#pragma unroll
+    for (int r = 0; r < 8; r++) *reinterpret_cast<uint2*>(dst + (size_t)r * stride) = rows[r];
+    return;
+  }
+  load_dequant_draft(sq, in, dr, threadIdx.x);
+  if (threadIdx.x < 3) {
+    const int c = threadIdx.x;
+    const uint32_t lr = c < in.ncomp ? (uint32_t)draft::lanes_row(in.comp_bw[c], dr.pc[c]) : 1u;
+    s_lr[c] = lr;
+    s_magic[c] = idct_div_magic(lr);
+  }
+  __syncthreads();
+  if (j >= nb) return;
+  int c = 0, base = 0, l = j;
+  for (; c < in.ncomp && c < 3; c++) {
+    const int cnt = (int)s_lr[c] * in.comp_bh[c];
+    if (l < cnt) break;
+    l -= cnt;
+    base += in.comp_h[c] * in.comp_v[c];
+  }
+  if (c >= in.ncomp || c >= 3) return;  // (the planner counted the same lanes: never)
+  const IdctDivMod m = idct_divmod((uint32_t)l, s_lr[c], s_magic[c]);
+  const int by = (int)m.q, gx = (int)m.r, pc = dr.pc[c];
+  if (pc == 8) {  // one block a lane, idct_kernel's path and bytes
+    const int hc = in.comp_h[c], vc = in.comp_v[c];
+    const int jb = in.ncomp == 1 ? by * in.mcux + gx
+                                 : ((by / vc) * in.mcux + gx / hc) * in.bpm + base + (by % vc) * hc +
+                                       gx % hc;
+    list_block<kIdctThreads>(ents, bdesc[(size_t)dd.coef_off + jb], dd.coef_off, in.nblocks, sq[c],
+                             b32);
+    uint2 rows[8];
+    idct_block_rows<kIdctThreads, 1>(b32, rows);
+    const int stride = dd.plane_stride[c];
+    uint8_t* dst = planes + dd.plane_off[c] + (size_t)by * 8 * stride + gx * 8;
+#pragma unroll
+    for (int r = 0; r < 8; r++) *reinterpret_cast<uint2*>(dst + (size_t)r * stride) = rows[r];
+  } else if (pc == 4) {
+    draft_lane<4>(ents, bdesc, dd, in, planes, sq[c], b32, c, base, by, gx);
+  } else if (pc == 2) {
+    draft_lane<2>(ents, bdesc, dd, in, planes, sq[c], b32, c, base, by, gx);
+  } else {
+    draft_lane<1>(ents, bdesc, dd, in, planes, sq[c], b32, c, base, by, gx);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // colour conversion (IJG jdcolor.c / jdmerge.c integer tables, SCALEBITS 16)
 // ---------------------------------------------------------------------------
 
@@ -6819,11 +7011,62 @@ __device__ __forceinline__ void turbo_samples(const uint8_t* __restrict__ planes
   }
 }
 
+// The same of a draft frame (spdl_hj_set_draft): the planes are the sizes the
+// per-component transforms left (the descriptor's windows and strides), the
+// ratios what remains for upsampling (dr), and a frame of scale 1/8 replicates.
+__device__ __forceinline__ void turbo_samples_draft(const uint8_t* __restrict__ planes,
+                                                    const ImageDesc& dd, const draft::Desc& dr,
+                                                    int x0, int y0, int (&v)[3][2][8]) {
+  const bool fancy = dr.level != 3;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    if (c < dd.ncomp) {
+      const int hr = dr.hr[c], vr = dr.vr[c];
+      const int cw = dd.win_w[c], ch = dd.win_h[c];
+      up::run8x2(planes + dd.plane_off[c], dd.plane_stride[c], cw, ch,
+                 up::mode_of(hr, vr, cw, fancy), hr, vr, x0, y0, v[c][0], v[c][1]);
+    } else {  // (gray: every channel is Y)
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        v[c][0][k] = v[0][0][k];
+        v[c][1][k] = v[0][1][k];
+      }
+    }
+  }
+}
+
+// turbo_rgb_kernel over a submission with draft levels: the same grid, tiles,
+// colour step and stores; an image of level 0 has ratios hmax / h_c in its record
+__global__ void __launch_bounds__(256) turbo_rgb_draft_kernel(
+    const uint8_t* __restrict__ planes, const ImageDesc* __restrict__ desc,
+    const ImageInfo* __restrict__ infos, void* __restrict__ out, const BatchParams p,
+    int32_t* __restrict__ host_status, const uint32_t* __restrict__ sws_map,
+    const draft::Desc* __restrict__ drafts) {
+  const int img = (int)sws_map[blockIdx.x], tid = threadIdx.x;
+  const ImageDesc& dd = desc[img];
+  const int t = (int)blockIdx.x - dd.sws_wg0;
+  const ImageInfo& in = infos[img];
+  if (host_status && t == 0 && tid == 0) host_status[img] = in.status;
+  if (in.status != kOk || dd.refuse) return;
+  const int W = dd.ow, H = dd.oh;
+  const int ty = t / dd.sws_chunks, tx = t - ty * dd.sws_chunks;
+  const int x0 = tx * kTurboTileW + (tid & 15) * 8;
+  const int y0 = ty * kTurboTileH + (tid >> 4) * 2;
+  if (x0 >= W || y0 >= H) return;
+  int v[3][2][8];
+  turbo_samples_draft(planes, dd, drafts[img], x0, y0, v);
+  turbo_row(out, dd, p, x0, y0, v[0][0], v[1][0], v[2][0]);
+  if (y0 + 1 < H) turbo_row(out, dd, p, x0, y0 + 1, v[0][1], v[1][1], v[2][1]);
+}
+
 __device__ __forceinline__ uint32_t rs_clip8(uint32_t acc) {
   const int v = (int)acc >> rs::kCoefBits;
   return (uint32_t)min(max(v, 0), 255);
 }
 
+// DRAFT: the frame is a draft frame (spdl_hj_set_draft; `drafts` its records,
+// null otherwise): the producer is turbo_samples_draft, everything else as it is
+template <bool DRAFT>
 __global__ void __launch_bounds__(256) resample_kernel(const uint8_t* __restrict__ planes,
                                                        const ImageDesc* __restrict__ desc,
                                                        const ImageInfo* __restrict__ infos,
@@ -6831,7 +7074,8 @@ __global__ void __launch_bounds__(256) resample_kernel(const uint8_t* __restrict
                                                        const int32_t* __restrict__ tables,
                                                        void* __restrict__ out, const BatchParams p,
                                                        int32_t* __restrict__ host_status,
-                                                       const uint32_t* __restrict__ sws_map) {
+                                                       const uint32_t* __restrict__ sws_map,
+                                                       const draft::Desc* __restrict__ drafts) {
   extern __shared__ uint32_t rs_lds[];
   const int img = (int)sws_map[blockIdx.x], tid = threadIdx.x;
   const ImageDesc& dd = desc[img];
@@ -6875,7 +7119,8 @@ __global__ void __launch_bounds__(256) resample_kernel(const uint8_t* __restrict
     for (int u = tid; u < units; u += 256) {
       const int uy = u / units_x, ux = u - uy * units_x;
       int v[3][2][8];
-      turbo_samples(planes, dd, c0 + 8 * ux, s0 + 2 * uy, v);
+      if constexpr (DRAFT) turbo_samples_draft(planes, dd, drafts[img], c0 + 8 * ux, s0 + 2 * uy, v);
+      else turbo_samples(planes, dd, c0 + 8 * ux, s0 + 2 * uy, v);
 #pragma unroll
       for (int j = 0; j < 2; j++) {
         uint32_t* q = strip + (2 * uy + j) * rd.pitch + 8 * ux;
@@ -7010,6 +7255,11 @@ hipError_t launch_idct_lowres(const BatchBuffers& b, int idct, int idct_wgs, hip
                b.desc, b.infos, b.planes, b.idct_map, b.lowres);
   return hipGetLastError();
 }
+hipError_t launch_idct_draft(const BatchBuffers& b, int idct_wgs, hipStream_t st) {
+  hipLaunchKernelGGL(idct_draft_kernel, dim3(idct_wgs), dim3(kIdctThreads), 0, st, b.ents, b.bdesc,
+                     b.desc, b.infos, b.planes, b.idct_map, b.draft);
+  return hipGetLastError();
+}
 hipError_t launch_idct_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int idct,
                            int tiles, int32_t* host_status, hipStream_t st) {
   HJ_IDCT_KIND(idct_rgb_kernel, idct, dim3(tiles, b.n), dim3(kFusedThreads), 0, st, b.ents, b.bdesc,
@@ -7049,14 +7299,22 @@ hipError_t launch_csc(const BatchBuffers& b, void* out, const BatchParams& p, in
 }
 hipError_t launch_turbo_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int turbo_wgs,
                             int32_t* host_status, hipStream_t st) {
-  hipLaunchKernelGGL(turbo_rgb_kernel, dim3(turbo_wgs), dim3(256), 0, st, b.planes, b.desc, b.infos,
-                     out, p, host_status, b.sws_map);
+  if (b.draft)
+    hipLaunchKernelGGL(turbo_rgb_draft_kernel, dim3(turbo_wgs), dim3(256), 0, st, b.planes, b.desc,
+                       b.infos, out, p, host_status, b.sws_map, b.draft);
+  else
+    hipLaunchKernelGGL(turbo_rgb_kernel, dim3(turbo_wgs), dim3(256), 0, st, b.planes, b.desc, b.infos,
+                       out, p, host_status, b.sws_map);
   return hipGetLastError();
 }
 hipError_t launch_resample(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
                            int lds_bytes, int32_t* host_status, hipStream_t st) {
-  hipLaunchKernelGGL(resample_kernel, dim3(wgs), dim3(256), lds_bytes, st, b.planes, b.desc,
-                     b.infos, b.resample, b.wts, out, p, host_status, b.sws_map);
+  if (b.draft)
+    hipLaunchKernelGGL(resample_kernel<true>, dim3(wgs), dim3(256), lds_bytes, st, b.planes, b.desc,
+                       b.infos, b.resample, b.wts, out, p, host_status, b.sws_map, b.draft);
+  else
+    hipLaunchKernelGGL(resample_kernel<false>, dim3(wgs), dim3(256), lds_bytes, st, b.planes, b.desc,
+                       b.infos, b.resample, b.wts, out, p, host_status, b.sws_map, b.draft);
   return hipGetLastError();
 }
 hipError_t launch_rgb_unscaled(const BatchBuffers& b, void* out, const BatchParams& p,

@@ -45,6 +45,10 @@ struct BatchBuffers {
   // a resampled submission's records (spdl_hj_set_resample): one per image
   // behind the work list; null otherwise
   const rs::ResampleDesc* resample;
+  // draft levels (spdl_hj_set_draft): one record per image behind all of the
+  // above; null when every level is 0 -- the kernels of such a submission are
+  // those of one without the call
+  const draft::Desc* draft;
 };
 
 // parse_kernel + lut_kernel.  host_desc (descriptors, then the work list) and
@@ -64,11 +68,15 @@ hipError_t launch_idct(const BatchBuffers& b, int idct, bool flat, int idct_wgs,
 // idct_lowres_kernel<idct> over the flat IDCT grid: every image of a submission
 // with reduced-size levels (b.lowres), the level-0 ones as idct_kernel does
 hipError_t launch_idct_lowres(const BatchBuffers& b, int idct, int idct_wgs, hipStream_t st);
+// idct_draft_kernel (islow and libjpeg-turbo's reduced transforms) over the flat IDCT grid:
+// every image of a submission with draft levels (b.draft)
+hipError_t launch_idct_draft(const BatchBuffers& b, int idct_wgs, hipStream_t st);
 hipError_t launch_cmyk(const BatchBuffers& b, int64_t max_px, hipStream_t st);
 // Output kernels.  host_status: the slot's pinned status array (device view) or null
 hipError_t launch_csc(const BatchBuffers& b, void* out, const BatchParams& p, int64_t max_px,
                       int32_t* host_status, hipStream_t st);
-// turbo_rgb_kernel (csc = TURBO) over its flat grid: every image's own tiles, the first
+// turbo_rgb_kernel (csc = TURBO; with b.draft its draft instantiation, as launch_resample's)
+// over its flat grid: every image's own tiles, the first
 // turbo_wgs workgroups of sws_map (Layout::sws_wgs), plain and ragged submissions alike
 hipError_t launch_turbo_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int turbo_wgs,
                             int32_t* host_status, hipStream_t st);

@@ -264,7 +264,7 @@ struct Planner {
   // Image i's share of what the front end and the IDCT work on: coefficient
   // lists, planes, segments, destuff chunks, entropy pieces and records, and
   // its workgroups in the flat destuff and IDCT grids (d.idct_blocks is set)
-  void front_end(int i, const FrameBlocks& fb, int lv) {
+  void front_end(int i, const FrameBlocks& fb, int lv, const draft::Desc* dr = nullptr) {
     ImageDesc& d = L.desc[i];
     const spdl_hj_image_info& p = rq.infos[i];
     const int64_t bytes = rq.sizes[i];
@@ -277,8 +277,11 @@ struct Planner {
       // (a reduced plane: 8 >> L samples a block, each row padded to 8 bytes
       // a lane of idct_lowres_kernel, which writes the padding as well)
       d.plane_stride[c] = lv ? lowres_lanes_row(fb.bw[c], lv) * 8 : fb.bw[c] * 8;
+      // (a draft plane: P_c samples a block, 8 bytes a lane of idct_draft_kernel)
+      const int rows = dr ? dr->pc[c] : 8 >> lv;
+      if (dr) d.plane_stride[c] = draft::lanes_row(fb.bw[c], dr->pc[c]) * 8;
       d.plane_off[c] = L.total_planes;
-      L.total_planes += round_up((int64_t)d.plane_stride[c] * fb.bh[c] * (8 >> lv), 256);
+      L.total_planes += round_up((int64_t)d.plane_stride[c] * fb.bh[c] * rows, 256);
     }
     d.seg_cap = (int32_t)(bytes / 2 + 2);
     d.seg_off = L.total_segs;
@@ -495,6 +498,20 @@ struct Planner {
       for (int c = 0; c < p.ncomp; c++) d.idct_blocks += lowres_lanes_row(fb.bw[c], lv) * fb.bh[c];
       L.lowres_images++;
     }
+    // A draft submission: every later step sees the frame libjpeg-turbo emits
+    // at this image's scale, each component's plane at its own transform size
+    const draft::Desc* dr = nullptr;
+    int dpw[kMaxComp], dph[kMaxComp];
+    if (!L.draft.empty()) {
+      if (p.ncomp == 4) return fail(i, SPDL_HJ_ERR_UNSUPPORTED, "draft of a 4-component frame");
+      L.draft[i] = draft_plan(p, rq.draft[i], &src.w, &src.h, dpw, dph);
+      dr = &L.draft[i];
+      if (dr->level) {
+        d.idct_blocks = 0;
+        for (int c = 0; c < p.ncomp; c++) d.idct_blocks += draft_lanes(fb.bw[c], fb.bh[c], dr->pc[c]);
+        L.draft_images++;
+      }
+    }
     if (rq.views) {
       if (int rc = views_region(i, d, f, fb.grid)) return rc;
     } else if (has_rect) {
@@ -504,7 +521,13 @@ struct Planner {
       else set_region(d, fb.grid, views::mcu_rect(fb.grid, src));
     }
     set_windows(d, f, fb.grid, src);
-    front_end(i, fb, lv);
+    if (dr)
+      for (int c = 0; c < p.ncomp; c++) {
+        d.win_x[c] = d.win_y[c] = 0;
+        d.win_w[c] = dpw[c];
+        d.win_h[c] = dph[c];
+      }
+    front_end(i, fb, lv, dr);
     if (rq.views) return SPDL_HJ_OK;  // (the outputs are the views': plan_views)
     if (has_rect) L.all_special = false;  // the full-resolution converters read whole planes
     if (lv) {
@@ -529,7 +552,7 @@ struct Planner {
       d.ow = size.ow;
       d.oh = size.oh;
       L.max_px = std::max(L.max_px, (int64_t)d.ow * d.oh);
-      if (const int rc = place_resample(i, d, p)) refuse(d, rc);
+      if (const int rc = place_resample(i, d, src.w, src.h)) refuse(d, rc);
       return SPDL_HJ_OK;
     }
     const Placement pl = place_output(d, src.w, src.h, f, p.color, out, size, code_of(i));
@@ -779,6 +802,44 @@ struct Planner {
   }
   int level_of(int i) const { return L.lowres.empty() ? 0 : L.lowres[i]; }
 
+  // The draft levels likewise (spdl_hipjpeg.h "Pillow-exact draft"): csc =
+  // TURBO alone, whose own check refuses crops and views; flips, orientations
+  // and reduced-size levels with it are refused here, whatever their values
+  int check_draft() {
+    if (!rq.draft) return SPDL_HJ_OK;
+    const char* what = nullptr;
+    char buf[96];
+    int any = 0;
+    if (rq.ndraft != rq.n) {
+      snprintf(buf, sizeof(buf), "spdl_hj_set_draft gave %lld levels for %d images",
+               (long long)rq.ndraft, rq.n);
+      what = buf;
+    }
+    for (int64_t i = 0; !what && i < rq.ndraft; i++) {
+      if (rq.draft[i] > 3) {
+        snprintf(buf, sizeof(buf), "spdl_hj_set_draft: level %lld is %d (0 to 3)", (long long)i,
+                 (int)rq.draft[i]);
+        what = buf;
+      }
+      any |= rq.draft[i];
+    }
+    if (!what) {
+      if (rq.out->csc != SPDL_HJ_CSC_TURBO) what = "spdl_hj_set_draft needs csc = turbo";
+      else if (rq.crops) what = "spdl_hj_set_draft and spdl_hj_set_crops on one submission";
+      else if (rq.views) what = "spdl_hj_set_draft and views on one submission";
+      else if (rq.flips || rq.orients) what = "spdl_hj_set_draft and flips or orientations on one submission";
+      else if (rq.lowres) what = "spdl_hj_set_draft and spdl_hj_set_lowres on one submission";
+      else if (!rq.plans) what = "spdl_hj_set_draft needs an output stage";
+    }
+    if (!what) {
+      if (any) L.draft.assign(rq.n, draft::Desc{});
+      return SPDL_HJ_OK;
+    }
+    res.rc = SPDL_HJ_ERR_INVALID_ARG;
+    snprintf(res.err, sizeof(res.err), "%s", what);
+    return res.rc;
+  }
+
   // csc = TURBO is the whole frame as stored (spdl_hipjpeg.h "Pillow-exact
   // decode"): no source crop and no views; flips, orientations and levels are
   // refused by their own checks, a resize and the planar output by valid_output
@@ -820,11 +881,11 @@ struct Planner {
   // its resample_kernel tiles in the flat sws grid.  0, or why it is refused
   // alone (SPDL_HJ_ERR_BAD_GEOMETRY).
   ResamplePool rs_pool;
-  int place_resample(int i, ImageDesc& d, const spdl_hj_image_info& p) {
+  int place_resample(int i, ImageDesc& d, int W, int H) {
     const ResampleRequest& r = *rq.resample;
     rs::ResampleDesc t;
     int bands, chunks;
-    if (const int rc = r.place(r.cache, r.filter, r.items ? &r.items[i] : nullptr, p.width, p.height,
+    if (const int rc = r.place(r.cache, r.filter, r.items ? &r.items[i] : nullptr, W, H,
                                r.out_w, r.out_h, L.tables, rs_pool, &t, &bands, &chunks))
       return rc;
     L.resample[i] = t;
@@ -933,7 +994,7 @@ struct Planner {
 
 LayoutResult build_layout(const LayoutRequest& rq, Layout& L) {
   Planner P{rq, L};
-  if (P.check_flips() || P.check_ragged() || P.check_lowres() || P.check_turbo() ||
+  if (P.check_flips() || P.check_ragged() || P.check_lowres() || P.check_draft() || P.check_turbo() ||
       P.check_resample())
     return P.res;
   L.desc.assign(rq.n, ImageDesc{});
@@ -947,6 +1008,31 @@ LayoutResult build_layout(const LayoutRequest& rq, Layout& L) {
   if (rq.ragged && P.finish_ragged()) return P.res;
   P.place_flips();
   return P.res;
+}
+
+draft::Desc draft_plan(const spdl_hj_image_info& p, int lv, int* fw, int* fh, int* pw, int* ph) {
+  draft::Desc r{};
+  const int P = 8 >> lv;
+  r.level = (uint8_t)lv;
+  int hmax = 1, vmax = 1;
+  if (p.ncomp > 1)
+    for (int c = 0; c < p.ncomp && c < 3; c++) {
+      hmax = std::max(hmax, (int)p.h_samp[c]);
+      vmax = std::max(vmax, (int)p.v_samp[c]);
+    }
+  *fw = draft::scaled_side(p.width, P, 8);
+  *fh = draft::scaled_side(p.height, P, 8);
+  for (int c = 0; c < p.ncomp && c < 3; c++) {
+    // (gray: its factors mean nothing)
+    const int h = p.ncomp > 1 ? p.h_samp[c] : 1, v = p.ncomp > 1 ? p.v_samp[c] : 1;
+    const int pc = draft::comp_size(P, h, v, hmax, vmax);
+    r.pc[c] = (uint8_t)pc;
+    r.hr[c] = (uint8_t)(hmax * P / (h * pc));
+    r.vr[c] = (uint8_t)(vmax * P / (v * pc));
+    pw[c] = draft::scaled_side(p.width, h * pc, 8 * hmax);
+    ph[c] = draft::scaled_side(p.height, v * pc, 8 * vmax);
+  }
+  return r;
 }
 
 int source_frame(const spdl_hj_image_info& p, const spdl_hj_rect* in, views::Rect* src) {

@@ -142,7 +142,22 @@ struct Layout {
   // (bytes).  Empty otherwise.
   std::vector<rs::ResampleDesc> resample;
   int resample_lds = 0;
+  // Pillow-exact draft (spdl_hj_set_draft): one record per image.  Empty when
+  // every level of the submission is 0: such a submission is the path without
+  // the call exactly.  Otherwise idct_draft_kernel transforms every image over
+  // the flat IDCT grid -- ImageDesc::idct_blocks counts its lanes,
+  // draft_lanes() -- and the planes, windows, box and (with a resample) the
+  // items' coordinates of an image with L > 0 are the draft frame's.
+  std::vector<draft::Desc> draft;
+  int draft_images = 0;  // images with L > 0
 };
+
+// Image p at draft level lv (0..3), as libjpeg-turbo's scale (8 >> lv) / 8
+// decodes it: the record of its components, the frame and each component's
+// plane (pw x ph samples; arrays of kMaxComp, the frame's components set).
+draft::Desc draft_plan(const spdl_hj_image_info& p, int lv, int* fw, int* fh, int* pw, int* ph);
+// idct_draft_kernel's lanes of a component plane of bw x bh blocks at transform size pc
+inline int draft_lanes(int bw, int bh, int pc) { return draft::lanes_row(bw, pc) * bh; }
 
 // The frame FFmpeg's decoder emits at lowres L: ceil(x / 2^L) a side
 inline int lowres_side(int x, int lv) { return (x + (1 << lv) - 1) >> lv; }
@@ -199,7 +214,9 @@ struct ResampleRequest {
 // are optional and exclude each other.  flips (nflips bytes, SPDL_HJ_FLIP_*):
 // optional, one per image, or with views one per view, the groups
 // concatenated in group order.  lowres (nlowres bytes, 0..3): optional, one
-// level per image; excludes crops and views.  orients (norients bytes, 0..7): the same
+// level per image; excludes crops and views.  draft (ndraft bytes, 0..3):
+// optional, one level per image, csc = TURBO alone (spdl_hipjpeg.h
+// "Pillow-exact draft").  orients (norients bytes, 0..7): the same
 // places and counts; flips and orients on one request are refused.
 // ragged (n byte offsets into an output of out_bytes bytes): optional, lifts
 // the one-size rule (spdl_hipjpeg.h "ragged batches"); output_path: the
@@ -227,6 +244,9 @@ struct LayoutRequest {
   int64_t nlowres = 0;
   // spdl_hj_set_resample: the submission is a resampled one (null: not)
   const ResampleRequest* resample = nullptr;
+  // spdl_hj_set_draft: ndraft levels (0..3), one per image; null: none
+  const uint8_t* draft = nullptr;
+  int64_t ndraft = 0;
 };
 
 // The chain that runs ahead of a transpose: the output spec describes the

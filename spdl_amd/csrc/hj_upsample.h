@@ -22,8 +22,11 @@ namespace up {
 // a horizontal part need more than two columns; every other ratio, (4,1),
 // (4,2), (1,4) and the like, replicates.
 enum Mode { kCopy = 0, kH2V1, kH1V2, kH2V2, kBox };
-HJ_HD inline int mode_of(int hr, int vr, int cw) {
+// fancy = false: a draft frame of scale 1/8 (spdl_hj_set_draft level 3), where
+// libjpeg-turbo turns the triangle rules off and every remaining ratio replicates.
+HJ_HD inline int mode_of(int hr, int vr, int cw, bool fancy = true) {
   if (hr == 1 && vr == 1) return kCopy;
+  if (!fancy) return kBox;
   if (hr == 2 && vr == 1 && cw > 2) return kH2V1;
   if (hr == 1 && vr == 2) return kH1V2;
   if (hr == 2 && vr == 2 && cw > 2) return kH2V2;

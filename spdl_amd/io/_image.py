@@ -14,6 +14,7 @@ import logging
 import os
 import warnings
 from collections.abc import Mapping, Sequence
+from types import SimpleNamespace
 from dataclasses import dataclass
 
 import numpy as np
@@ -134,14 +135,15 @@ def _alloc_out(cfg: CUDAConfig, shape, dtype) -> CUDABuffer:
 
 def _decode(datas: list, out: Output, cfg: CUDAConfig, shape_per_image, batched: bool,
             dtype=torch.uint8, crops=None, flips=None, orients=None, lowres=None,
-            resample=None) -> CUDABuffer:
+            resample=None, draft=None) -> CUDABuffer:
     n = len(datas)
     shape = (n, *shape_per_image) if batched else tuple(shape_per_image)
     buf = _alloc_out(cfg, shape, dtype)
     dec = _lib.thread_decoder(cfg.device_index)
     nbytes = int(np.prod(shape)) * (1 if dtype == torch.uint8 else 2)
     dec.decode_batch(datas, out, buf.data_ptr(), nbytes, stream=_stream(cfg), sync=True,
-                     crops=crops, flips=flips, orients=orients, lowres=lowres, resample=resample)
+                     crops=crops, flips=flips, orients=orients, lowres=lowres, resample=resample,
+                     draft=draft)
     return buf
 
 
@@ -419,12 +421,54 @@ def _check_resample(resample, csc, n_src, filter_desc, pix_fmt) -> None:
         _with_csc(parse_image_filter(filter_desc, default_pix_fmt=pix_fmt), csc)
 
 
-def _resample_of(resample: PilResize, infos, keep) -> _lib.Resample:
-    """The decoder's request for the images ``keep`` of the sources."""
+def _resample_of(resample: PilResize, infos, keep, levels=None) -> _lib.Resample:
+    """The decoder's request for the images ``keep`` of the sources; with draft
+    ``levels`` every frame is its draft frame, as after ``im.draft()``."""
     boxes = resample.boxes
-    items = tuple(resample.geometry(i.width, i.height, None if boxes is None else boxes[k])
-                  for i, k in zip(infos, keep))
+    sizes = [(i.width, i.height) if levels is None else _lib.draft_size(i.width, i.height, lv)
+             for i, lv in zip(infos, levels or [0] * len(infos))]
+    items = tuple(resample.geometry(w, h, None if boxes is None else boxes[k])
+                  for (w, h), k in zip(sizes, keep))
     return _lib.Resample(resample.filter, *resample.size, items)
+
+
+def _check_draft(draft, csc, resample, n_src) -> None:
+    """``draft=`` against what goes with it, before anything is read
+    (include/spdl_hipjpeg.h "Pillow-exact draft"); what ``csc="turbo"``
+    excludes is :func:`_check_csc`'s to refuse."""
+    if draft is None:
+        return
+    if csc != "turbo":
+        raise ValueError(f"draft= needs csc='turbo', not {csc!r}")
+    if isinstance(draft, str):
+        if draft != "auto":
+            raise ValueError(f'draft= takes 0..3, a list of them, a (w, h) request or "auto", not {draft!r}')
+        if resample is None:
+            raise ValueError('draft="auto" needs resample=pil_resize(...): it covers the requested output')
+        if resample.boxes is not None:
+            raise ValueError('draft="auto" and boxes: a box is in the draft frame\'s coordinates, '
+                             "so the level comes first")
+    elif isinstance(draft, list) and len(draft) != n_src:
+        raise ValueError(f"{len(draft)} draft levels for {n_src} images")
+    elif not isinstance(draft, (int, tuple, list)) or isinstance(draft, bool):
+        raise ValueError(f'draft= takes 0..3, a list of them, a (w, h) request or "auto", not {draft!r}')
+    else:  # (values as well: a frame of 1 x 1 stands in for the files, which are not read yet)
+        _lib.draft_levels(draft, [SimpleNamespace(width=1, height=1)] * n_src)
+
+
+def _draft_levels(draft, infos, keep, resample):
+    """One level per kept image (``None``: all zero).  ``"auto"``: the largest
+    level whose frame covers ``resample``'s output -- both sides of ``size``,
+    and with ``shorter`` its shorter side that."""
+    if draft is None:
+        return None
+    if isinstance(draft, list):
+        draft = [draft[i] for i in keep]
+    sizes = None
+    if isinstance(draft, str):
+        need = max(resample.shorter or 0, min(resample.size))
+        sizes = [tuple(max(v, need) for v in resample.size)] * len(infos)
+    return _lib.draft_levels(draft, infos, sizes)
 
 
 def _csc_pix_fmt(filter_desc, pix_fmt):
@@ -468,6 +512,7 @@ def load_image_batch(
     lowres=None,
     csc: str = "swscale",
     resample=None,
+    draft=None,
     **kwargs,
 ):
     """Batch load images into one ``[B,H,W,3]`` buffer with the FFmpeg filter
@@ -523,7 +568,14 @@ def load_image_batch(
     ``lowres`` (files of mixed sizes: :func:`load_image_list`).
     ``resample=pil_resize(size, ...)`` with it: every file, whatever its size,
     through Pillow's ``Image.resize`` into one ``[B, h, w, 3]`` buffer
-    (:func:`pil_resize`)."""
+    (:func:`pil_resize`).  ``draft`` with ``csc="turbo"``: Pillow's
+    ``Image.draft()`` -- libjpeg-turbo's decode at 1/2, 1/4 or 1/8, byte for
+    byte -- as a level ``0..3`` for every image, a list with one per image, or
+    a ``(w, h)`` request resolved per image as Pillow resolves it
+    (:func:`spdl_amd._lib.draft_level`).  A ``resample`` then acts on the draft
+    frame, as after ``im.draft()``; ``draft="auto"`` with it picks per image
+    the largest level whose frame still covers the requested output
+    (``thumbnail``'s rule without ``reducing_gap``)."""
     if not srcs:
         raise ValueError("`srcs` must not be empty.")
     storage = kwargs.pop("storage", None)
@@ -534,6 +586,7 @@ def load_image_batch(
                exif_orientation=exif_orientation, lowres=lowres,
                pix_fmt=_csc_pix_fmt(filter_desc, pix_fmt))
     _check_resample(resample, csc, len(srcs), filter_desc, pix_fmt)
+    _check_draft(draft, csc, resample, len(srcs))
     if filter_desc == _FILTER_DESC_DEFAULT:
         filter_desc = get_video_filter_desc(
             scale_width=width, scale_height=height, pix_fmt=pix_fmt
@@ -628,6 +681,9 @@ def load_image_batch(
     src = _src_size(info, crops[0] if crops is not None else out.src_crop)
     if levels is not None:  # (the chain sees the reduced frame)
         src = _lib.lowres_size(*src, levels[0])
+    dlevels = _draft_levels(draft, infos, keep, resample)
+    if dlevels is not None:  # (the output is the draft frame)
+        src = _lib.draft_size(*src, dlevels[0])
     ow, oh = _oriented_size(src, out, orients[0] if orients else _lib._orient(out.orient))
     dtype = out.torch_dtype
     if out.pix_fmt == "yuv":
@@ -636,11 +692,11 @@ def load_image_batch(
         shape = _shape(out, ow, oh)
     rs = None
     if resample is not None:  # (every image leaves at the request's size)
-        rs = _resample_of(resample, infos, keep)
+        rs = _resample_of(resample, infos, keep, dlevels)
         shape = _shape(out, *resample.size)
     try:
         buf = _decode(datas, out, cfg, shape, True, dtype=dtype, crops=crops, flips=flips,
-                      orients=orients, lowres=levels, resample=rs)
+                      orients=orients, lowres=levels, resample=rs, draft=dlevels)
     except RuntimeError:
         if strict:
             raise
@@ -654,7 +710,8 @@ def load_image_batch(
                                     orients=None if orients is None else [orients[k]],
                                     lowres=None if levels is None else [levels[k]],
                                     resample=rs and _lib.Resample(rs.filter, rs.out_w, rs.out_h,
-                                                                  (rs.items[k],))))
+                                                                  (rs.items[k],)),
+                                    draft=None if dlevels is None else [dlevels[k]]))
             except RuntimeError as err:
                 _LG.error("Failed to decode an image: %s", err)
         if not good:
@@ -870,6 +927,7 @@ def load_image_list(
     align: int = 256,
     csc: str = "swscale",
     lowres=None,
+    draft=None,
 ):
     """Every image at its own size from one submission (an extension, like
     :func:`load_image_views`; include/spdl_hipjpeg.h "ragged batches"): native
@@ -887,7 +945,9 @@ def load_image_list(
     ``load_image_batch``'s; every box is sized from its image's reduced frame.
     ``csc="turbo"``: Pillow's pixels (libjpeg-turbo's default decoder, byte
     for byte) of every file at its native size -- no ``width`` / ``height``,
-    ``crops``, ``flips``, ``exif_orientation`` or ``lowres`` with it.
+    ``crops``, ``flips``, ``exif_orientation`` or ``lowres`` with it;
+    ``draft`` (``load_image_batch``'s, without ``"auto"``) decodes each file at
+    its own level, every box its draft frame.
 
     Returns ``(buffers, image_indices)``: one allocation, every buffer a view
     of it with its image's own shape (``[H,W,3]``, or ``[3,H,W]`` for ``rgb`` /
@@ -904,6 +964,7 @@ def load_image_list(
                          f"at native size, not {csc!r}")
     _check_csc(csc, width=width, height=height, crops=crops, flips=flips,
                exif_orientation=exif_orientation, lowres=lowres, pix_fmt=pix_fmt)
+    _check_draft(draft, csc, None, len(srcs))
     if filter_desc == _FILTER_DESC_DEFAULT:
         filter_desc = _list_filter_desc(width, height, scale_mode, scale_algo, pix_fmt)
     elif (width, height, scale_mode) != (None, None, None):
@@ -961,14 +1022,16 @@ def load_image_list(
         lowres = [per_lowres[i] for i in keep]
     levels = _lib.lowres_levels(lowres, infos, out, codes)
     _no_crops_with_lowres(levels, crops, out)
-    offsets, sizes, planned = _lib.ragged_layout(infos, out, crops, codes, align, lowres=levels)
+    dlevels = _draft_levels(draft, infos, keep, None)
+    offsets, sizes, planned = _lib.ragged_layout(infos, out, crops, codes, align, lowres=levels,
+                                                 draft=dlevels)
     esz = 1 if out.torch_dtype == torch.uint8 else 2
     # (every offset and every extent is a multiple of the element size)
     total = _alloc_out(cfg, (max(offsets[n] // esz, 1),), out.torch_dtype)
     dec = _lib.thread_decoder(cfg.device_index)
     status = dec.decode_batch(datas, out, total.data_ptr(), offsets[n], stream=_stream(cfg),
                               sync=True, check=False, crops=crops, orients=codes,
-                              ragged=offsets[:n], lowres=levels)
+                              ragged=offsets[:n], lowres=levels, draft=dlevels)
     from ._convert import to_torch
 
     flat = to_torch(total)
@@ -1041,6 +1104,7 @@ def load_image(
     lowres=None,
     csc: str = "swscale",
     resample=None,
+    draft=None,
     **kwargs,
 ):
     """Single image.  ``filter_desc=None`` returns the decoded planes in the
@@ -1061,7 +1125,9 @@ def load_image(
     ``pix_fmt``'s layout -- libjpeg-turbo's default decoder; no scaling chain,
     ``flip``, ``exif_orientation`` or ``lowres`` with it;
     ``resample=pil_resize(size, ...)`` resizes it as Pillow's ``Image.resize``
-    does (:func:`pil_resize`)."""
+    does (:func:`pil_resize`); ``draft`` (``0..3``, a ``(w, h)`` request, or
+    ``"auto"`` with a ``resample``) is Pillow's ``Image.draft()`` ahead of both,
+    as in :func:`load_image_batch`."""
     kwargs.pop("name", None)  # only names the source in FFmpeg demux errors
     lowres = _ffmpeg_configs(kwargs, lowres)
     if kwargs:
@@ -1069,6 +1135,7 @@ def load_image(
     _check_csc(csc, flips=flip or None, exif_orientation=exif_orientation, lowres=lowres,
                pix_fmt=_csc_pix_fmt(filter_desc, pix_fmt))
     _check_resample(resample, csc, 1, filter_desc, pix_fmt)
+    _check_draft(draft, csc, resample, 1)
     if resample is not None and filter_desc is None:
         raise ValueError("resample= needs an RGB pix_fmt: it converts to RGB")
     cfg = device_config or _default_config()
@@ -1105,11 +1172,14 @@ def load_image(
         shape = _yuv_shape([info], out, src)
     else:
         shape = _shape(out, *_oriented_size(src, out, _lib._orient(out.orient)))
+    dlevels = _draft_levels(draft, [info], [0], resample)
+    if dlevels is not None:  # (the output is the draft frame)
+        shape = _shape(out, *_lib.draft_size(*src, dlevels[0]))
     rs = None
     if resample is not None:
-        rs = _resample_of(resample, [info], [0])
+        rs = _resample_of(resample, [info], [0], dlevels)
         shape = _shape(out, *resample.size)
-    buf = _decode([data], out, cfg, shape, False, lowres=levels, resample=rs)
+    buf = _decode([data], out, cfg, shape, False, lowres=levels, resample=rs, draft=dlevels)
     if device_config is None:
         return _to_host(buf)
     return buf
