@@ -642,7 +642,7 @@ int spdl_hj_set_lowres(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n);
  * The read-only parameter "resample_workgroups" reports resample_kernel's
  * workgroups in the last submission; "turbo_workgroups" is 0 for it.
  *
- * Out of scope: Pillow's fractional box= and reducing_gap; the BOX, HAMMING
+ * Out of scope: the BOX, HAMMING
  * and NEAREST filters; ragged output sizes; an IDCT of the MCUs a box touches
  * alone (the whole frame is transformed); flips and orientations on a
  * resampled submission; gamma-aware or float resampling. */
@@ -691,9 +691,94 @@ int spdl_hj_debug_resample_axis(int32_t in_size, int32_t out_size, int32_t filte
  * same launches.  The read-only parameter "draft_images" reports the images
  * with a level above 0 in the last submission, "planes_bytes" its planes.
  * Out of scope: libjpeg's block smoothing (it acts on progressive files whose
- * scans stop short, which fail here), Pillow's reducing_gap and float boxes,
- * scales other than 1/2, 1/4, 1/8. */
+ * scans stop short, which fail here), scales other than 1/2, 1/4, 1/8. */
 int spdl_hj_set_draft(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n);
+
+/* ---- Pillow-exact thumbnail: float boxes, Image.reduce and reducing_gap
+ * (additive in ABI 7: one call, two debug entries, one read-only parameter) ----
+ * spdl_hj_set_resample_box is spdl_hj_set_resample with Pillow's own box= and
+ * reducing_gap=: the next submission's image i leaves as
+ *   np.asarray(im.resize((rw, rh), filter, box=(x0, y0, x1, y1), reducing_gap=g))
+ *     [oy : oy + out_h, ox : ox + out_w]
+ * byte for byte, im the Pillow-exact decode (after im.draft() with
+ * spdl_hj_set_draft: the box is then in the draft frame's coordinates).  One-shot,
+ * exclusive with spdl_hj_set_resample (the later call holds), with the same
+ * exclusions.  reducing_gap 0: none.
+ *
+ * A float box.  The axis rule above with
+ *   scale = (in1 - in0) / outSize;  center = in0 + (xx + 0.5) scale
+ * where in0 and in1 are first rounded to single precision and subtracted
+ * there, as Pillow takes a box (the rest stays in doubles),
+ * and xmin / xmax clamped to the WHOLE frame [0, inSize), not to the box: taps
+ * reach past the box's edge, which .crop(box).resize() -- spdl_hj_set_resample's
+ * integer box -- does not do.  The integer rule is the case in0 = 0,
+ * in1 = inSize of a cropped frame.
+ *
+ * reducing_gap g >= 1, a W x H frame into (rw, rh), s = support(f) - 0.5:
+ *   fx = (int)((x1 - x0) / rw / g) or 1;  fy likewise;  both 1: nothing more
+ *   sx = s (x1 - x0) / rw;  sy likewise
+ *   q = (max(0, (int)(x0 - sx)), max(0, (int)(y0 - sy)),
+ *        min(W, ceil(x1 + sx)), min(H, ceil(y1 + sy)))              the safe box
+ *   the picture becomes reduce((fx, fy), box = q), the box
+ *   ((x0 - q0) / fx, (y0 - q1) / fy, (x1 - q0) / fx, (y1 - q1) / fy)
+ * and the float-box resize runs on the reduced picture.
+ *
+ * Image.reduce, 8 bits: ceil(qw / fx) x ceil(qh / fy) cells counted from the
+ * safe box's origin; a cell of d pixels (fx fy inside, fewer in the right
+ * column, the bottom row and the corner) gives per channel
+ *   ((sum + d / 2) floor(2^24 / d)) >> 24          in uint32.
+ *
+ * With any factor above 1 in the submission, resample_reduce_kernel replaces
+ * resample_kernel: a producer thread adds its 8 x 2 pixels into 16-bit cell
+ * sums in LDS, which are divided into the strip the horizontal pass reads, so
+ * neither the full-size RGB nor the reduced picture touches device memory.
+ * For the sums to fit, fx fy <= SPDL_HJ_REDUCE_MAX_CELL.  Without a factor
+ * above 1 the submission launches resample_kernel, with other tables.
+ *
+ * SPDL_HJ_ERR_INVALID_ARG from the consuming call, nothing written: what
+ * spdl_hj_set_resample refuses; a gap below 1 other than 0; a box that is
+ * empty or reaches outside the (draft) frame.  SPDL_HJ_ERR_BAD_GEOMETRY for
+ * that image alone: rw / rh / the window as above; more than
+ * SPDL_HJ_RESAMPLE_MAX_TAPS taps on an axis of the REDUCED picture (so lanczos
+ * above 42 : 1 decodes with a gap, as in Pillow); fx fy above the cap; a frame
+ * with H > 100 W whose height shrinks (Pillow resizes such a frame in another
+ * order, which is not restated).
+ *
+ * Image.thumbnail(size, f, reducing_gap) is this call after spdl_hj_set_draft:
+ * draft for ((int)(w g), (int)(h g)), the box (0, 0, W / scale, H / scale) of
+ * the draft frame, (rw, rh) Pillow's aspect-preserving size -- the Python
+ * layer's pil_thumbnail restates it.
+ *
+ * The read-only parameter "reduce_images" reports the images with a factor
+ * above 1 in the last submission.  Out of scope: thumbnails of several sizes in
+ * one submission (ragged resampled output). */
+#define SPDL_HJ_REDUCE_MAX_CELL 256
+typedef struct spdl_hj_resample_box_item {
+  double x0, y0, x1, y1; /* Pillow's box= in the frame; all zero: the whole frame */
+  int32_t rw, rh;        /* the resized picture; 0: out_w / out_h */
+  int32_t ox, oy;        /* the out_w x out_h window of it that is written */
+} spdl_hj_resample_box_item;
+int spdl_hj_set_resample_box(spdl_hj_ctx* ctx, int32_t filter, int32_t out_w, int32_t out_h,
+                             double reducing_gap, const spdl_hj_resample_box_item* items,
+                             int64_t n);
+
+/* spdl_hj_debug_resample_axis for a float box [in0, in1) of in_size samples:
+ * xmin is absolute in the frame. */
+int spdl_hj_debug_resample_axis_box(int32_t in_size, double in0, double in1, int32_t out_size,
+                                    int32_t filter, int32_t* xmin, int32_t* n, int32_t* K,
+                                    int64_t cap, int32_t* ksize);
+/* What reducing_gap resolves to for one image (no device, no context): the
+ * factors, the safe box (x0, y0, x1, y1), the reduced picture, the box in it,
+ * and the divisor and multiplier of the four cell classes -- interior, right
+ * column, bottom row, corner.  The return value is the image's status. */
+typedef struct spdl_hj_reduce_plan {
+  int32_t fx, fy, q[4], cw, ch;
+  double box[4];
+  int32_t div[4], mult[4];
+} spdl_hj_reduce_plan;
+int spdl_hj_debug_reduce_plan(int32_t W, int32_t H, const spdl_hj_resample_box_item* item,
+                              int32_t out_w, int32_t out_h, int32_t filter, double reducing_gap,
+                              spdl_hj_reduce_plan* plan);
 
 /* ABI version of the loaded library (== SPDL_HJ_ABI_VERSION). */
 int spdl_hj_abi_version(void);
@@ -953,7 +1038,8 @@ const char* spdl_hj_stage_name(int32_t i);
  * turbo_rgb_kernel in the last submission; "resample_workgroups" (with the
  * Pillow-exact resize), those of resample_kernel; "draft_images" (with the
  * Pillow-exact draft), the images of the last submission with a draft level
- * above 0.
+ * above 0; "reduce_images" (with spdl_hj_set_resample_box), those with a
+ * reduce factor above 1.
  * Builds with -DHJ_ABLATIONS=1 also take "debug_mask" (timing ablations that
  * skip kernel phases; outputs wrong); release builds reject it. */
 int spdl_hj_set_param(spdl_hj_ctx* ctx, const char* name, int64_t value);

@@ -66,6 +66,9 @@ EXPORTED = (
     "spdl_hj_set_resample",
     "spdl_hj_debug_resample_axis",
     "spdl_hj_set_draft",
+    "spdl_hj_set_resample_box",
+    "spdl_hj_debug_resample_axis_box",
+    "spdl_hj_debug_reduce_plan",
 )
 
 
@@ -471,6 +474,12 @@ def lib() -> ctypes.CDLL:
                                                       ctypes.POINTER(i32)]
         if hasattr(L, "spdl_hj_set_draft"):  # (likewise)
             L.spdl_hj_set_draft.argtypes = [vp, vp, i32]
+        if hasattr(L, "spdl_hj_set_resample_box"):  # (likewise)
+            f64 = ctypes.c_double
+            L.spdl_hj_set_resample_box.argtypes = [vp, i32, i32, i32, f64, vp, i64]
+            L.spdl_hj_debug_resample_axis_box.argtypes = [i32, f64, f64, i32, i32, vp, vp, vp, i64,
+                                                          ctypes.POINTER(i32)]
+            L.spdl_hj_debug_reduce_plan.argtypes = [i32, i32, vp, i32, i32, i32, f64, vp]
         ver = L.spdl_hj_abi_version()
         # (an explicitly chosen older build, ABI >= 5, loads for A/B runs)
         if ver != ABI_VERSION and not (os.environ.get("SPDL_AMD_LIB") and 5 <= ver < ABI_VERSION):
@@ -484,6 +493,18 @@ class ResampleItem(ctypes.Structure):  # spdl_hj_resample_item
                 ("ox", ctypes.c_int32), ("oy", ctypes.c_int32)]
 
 
+class ResampleBoxItem(ctypes.Structure):  # spdl_hj_resample_box_item
+    _fields_ = [("x0", ctypes.c_double), ("y0", ctypes.c_double), ("x1", ctypes.c_double),
+                ("y1", ctypes.c_double), ("rw", ctypes.c_int32), ("rh", ctypes.c_int32),
+                ("ox", ctypes.c_int32), ("oy", ctypes.c_int32)]
+
+
+class ReducePlan(ctypes.Structure):  # spdl_hj_reduce_plan
+    _fields_ = [("fx", ctypes.c_int32), ("fy", ctypes.c_int32), ("q", ctypes.c_int32 * 4),
+                ("cw", ctypes.c_int32), ("ch", ctypes.c_int32), ("box", ctypes.c_double * 4),
+                ("div", ctypes.c_int32 * 4), ("mult", ctypes.c_int32 * 4)]
+
+
 @dataclass(frozen=True)
 class Resample:
     """A resampled submission (spdl_hj_set_resample): Pillow's ``Image.resize``
@@ -491,11 +512,15 @@ class Resample:
     image into one ``out_w x out_h`` box.  ``items``: per image ``(box, (rw,
     rh), (ox, oy))`` -- the source rectangle ``(x, y, w, h)`` or ``None`` for
     the whole frame, the resized picture (``0``: the box's side) and the window
-    of it that is written; ``None``: every whole frame into the box."""
+    of it that is written; ``None``: every whole frame into the box.
+    ``by_box`` (spdl_hj_set_resample_box): a box is Pillow's float ``box=``,
+    ``(x0, y0, x1, y1)``, and ``reducing_gap`` Pillow's (``None``: none)."""
     filter: str
     out_w: int
     out_h: int
     items: tuple | None = None
+    by_box: bool = False
+    reducing_gap: float | None = None
 
 
 def _resample_c(resample: Resample) -> tuple:
@@ -504,6 +529,18 @@ def _resample_c(resample: Resample) -> tuple:
     if resample.filter not in FILTERS:
         raise ValueError(f"filter must be one of {sorted(FILTERS)}, not {resample.filter!r}")
     items, arr = resample.items, None
+    if resample.by_box:
+        if items is not None:
+            arr = (ResampleBoxItem * max(len(items), 1))()
+            try:
+                for a, (box, (rw, rh), (ox, oy)) in zip(arr, items):
+                    a.x0, a.y0, a.x1, a.y1 = (float(v) for v in (box or (0, 0, 0, 0)))
+                    a.rw, a.rh, a.ox, a.oy = int(rw), int(rh), int(ox), int(oy)
+            except (TypeError, ValueError) as err:
+                raise ValueError("a box resample item is ((x0, y0, x1, y1) | None, (rw, rh), "
+                                 f"(ox, oy)): {err}") from None
+        return ("box", FILTERS[resample.filter], int(resample.out_w), int(resample.out_h),
+                float(resample.reducing_gap or 0.0), arr, 0 if items is None else len(items))
     if items is not None:
         arr = (ResampleItem * max(len(items), 1))()
         try:
@@ -516,21 +553,40 @@ def _resample_c(resample: Resample) -> tuple:
             0 if items is None else len(items))
 
 
-def resample_axis(in_size: int, out_size: int, filter: str):
+def resample_axis(in_size: int, out_size: int, filter: str, box=None):
     """One axis's tables as the library builds them (no device): ``(xmin, n,
-    K)`` with ``K`` of shape ``[out_size, ksize]`` (spdl_hj_debug_resample_axis)."""
+    K)`` with ``K`` of shape ``[out_size, ksize]`` (spdl_hj_debug_resample_axis);
+    ``box=(in0, in1)``: a float box's, ``xmin`` absolute in the frame."""
     import numpy as np
 
     ks = ctypes.c_int32()
     xmin, cnt = np.zeros(out_size, np.int32), np.zeros(out_size, np.int32)
-    rc = lib().spdl_hj_debug_resample_axis(in_size, out_size, FILTERS[filter], xmin.ctypes.data,
-                                           cnt.ctypes.data, None, 0, ctypes.byref(ks))
+    if box is None:
+        def call(*tail):
+            return lib().spdl_hj_debug_resample_axis(in_size, out_size, FILTERS[filter], *tail)
+    else:
+        def call(*tail):
+            return lib().spdl_hj_debug_resample_axis_box(in_size, float(box[0]), float(box[1]),
+                                                         out_size, FILTERS[filter], *tail)
+    rc = call(xmin.ctypes.data, cnt.ctypes.data, None, 0, ctypes.byref(ks))
     if rc:
         raise RuntimeError(f"spdl_hj_debug_resample_axis: {rc}")
     K = np.zeros((out_size, ks.value), np.int32)
-    lib().spdl_hj_debug_resample_axis(in_size, out_size, FILTERS[filter], None, None,
-                                      K.ctypes.data, K.size, ctypes.byref(ks))
+    call(None, None, K.ctypes.data, K.size, ctypes.byref(ks))
     return xmin, cnt, K
+
+
+def reduce_plan(width: int, height: int, size, filter: str, reducing_gap: float, box=None):
+    """What ``Image.resize(size, filter, box, reducing_gap)`` of a ``width x
+    height`` frame resolves to (spdl_hj_debug_reduce_plan): ``(status, plan)``
+    with the :class:`ReducePlan` of its factors, safe box, reduced picture,
+    box in it and the four cell classes' divisors and multipliers."""
+    item = ResampleBoxItem(*(float(v) for v in (box or (0, 0, 0, 0))), 0, 0, 0, 0)
+    plan = ReducePlan()
+    rc = lib().spdl_hj_debug_reduce_plan(width, height, ctypes.byref(item), int(size[0]),
+                                         int(size[1]), FILTERS[filter], float(reducing_gap or 0.0),
+                                         ctypes.byref(plan))
+    return rc, plan
 
 
 def get_image_info(data) -> ImageInfo:
@@ -650,8 +706,9 @@ def draft_levels(draft, infos, sizes=None) -> list[int] | None:
     list with one entry per image, a ``(w, h)`` tuple -- Pillow's request,
     resolved per image by :func:`draft_level` -- or ``"auto"``, which needs
     ``sizes`` (per image the ``(w, h)`` its output must be covered by: the
-    largest level whose frame is no smaller on either side, ``thumbnail``'s
-    rule without ``reducing_gap``).  ``None`` when it asks for nothing."""
+    largest level whose frame is no smaller on either side; Pillow's
+    ``thumbnail`` itself, ``reducing_gap`` included, is ``pil_thumbnail``).
+    ``None`` when it asks for nothing."""
     n = len(infos)
     if draft is None:
         return None
@@ -1024,7 +1081,12 @@ class Decoder:
     def _set_resample_c(self, args) -> None:
         if not hasattr(lib(), "spdl_hj_set_resample"):
             raise RuntimeError("this libspdl_hipjpeg build has no spdl_hj_set_resample")
-        if lib().spdl_hj_set_resample(self._h, *args):
+        if args[0] == "box":
+            if not hasattr(lib(), "spdl_hj_set_resample_box"):
+                raise RuntimeError("this libspdl_hipjpeg build has no spdl_hj_set_resample_box")
+            if lib().spdl_hj_set_resample_box(self._h, *args[1:]):
+                raise ValueError("invalid resample request")
+        elif lib().spdl_hj_set_resample(self._h, *args):
             raise ValueError("invalid resample request")
 
     def set_ragged(self, offsets) -> None:

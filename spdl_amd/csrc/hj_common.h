@@ -331,6 +331,27 @@ inline HJ_HD Window tile_window(const int32_t* xmin, const int32_t* n, int b0, i
   return w;
 }
 
+// ---- Image.reduce ahead of the resize (spdl_hj_set_resample_box with a
+// reducing_gap): what resample_reduce_kernel knows of one image beside its
+// ResampleDesc, whose tables then describe the reduced picture (bx = by = 0).
+// One record per image behind the draft records, in submissions where some
+// image has a factor above 1; an image without one has fx = fy = 1.
+constexpr int kReduceMaxCell = 256;  // fx fy at most: 255 d fits a cell sum's 16 bits
+struct ReduceDesc {
+  int32_t qx, qy, qw, qh;  // the safe box in the frame: cells count from its origin
+  int32_t fx, fy;          // the factors
+  int32_t cw, ch;          // the reduced picture: ceil(qw / fx) x ceil(qh / fy)
+  // a cell's rounding term d / 2 and multiplier floor(2^24 / d) by its class,
+  // (bottom row) << 1 | (right column): d = fx fy inside, fewer where the safe
+  // box ends inside the cell
+  uint32_t amend[4], mult[4];
+};
+// resample_reduce_kernel's LDS in words: lds_layout()'s, whose strip holds the
+// R | G << 16 sums and then the packed pixels, and behind it the B sums
+inline HJ_HD int reduce_lds_words(const ResampleDesc& d) {
+  return lds_layout(d).words + d.sr * d.pitch;
+}
+
 }  // namespace rs
 
 // ---- Pillow-exact draft (spdl_hj_set_draft; libjpeg-turbo's scale_num / 8) ----

@@ -162,12 +162,15 @@ struct Slot {
       uint8_t lowres;     // its reduced-size level
       spdl_hj_resample_item resample;  // its item of a resampled batch (has_resample)
       uint8_t draft;      // its draft level (spdl_hj_set_draft)
+      spdl_hj_resample_box_item rsbox;  // its item of a box request (rs_by_box)
     };
     std::vector<Item> items;
     bool has_rects = false, has_flips = false;  // the batch had crops / flips
     // the batch was a resampled one (spdl_hj_set_resample): its filter and box
     bool has_resample = false;
     int32_t rs_filter = 0, rs_ow = 0, rs_oh = 0;
+    bool rs_by_box = false;  // ... by spdl_hj_set_resample_box, with this gap
+    double rs_gap = 0;
     bool oriented = false;  // ... the flips came as orientation codes (spdl_hj_set_orients)
   } retry;
 };
@@ -298,12 +301,17 @@ struct spdl_hj_ctx {
   int64_t fused_workgroups = 0, generic_workgroups = 0;
   int64_t turbo_workgroups = 0;  // turbo_rgb_kernel's in the last submission (csc = TURBO)
   int64_t resample_workgroups = 0;  // resample_kernel's (spdl_hj_set_resample)
+  int64_t reduce_images = 0;  // images with a reduce factor above 1 (spdl_hj_set_resample_box)
   // spdl_hj_set_resample: the next batch submission's filter, box and items
   // (has_items: one per image; else every whole frame), and the axes it made
   struct HeldResample {
     bool set = false, has_items = false;
     int32_t filter = 0, out_w = 0, out_h = 0;
     std::vector<spdl_hj_resample_item> items;
+    // spdl_hj_set_resample_box: its items and gap in their place
+    bool by_box = false;
+    double gap = 0;
+    std::vector<spdl_hj_resample_box_item> box_items;
   } resample;
   rs::AxisCache axes;
   // spdl_hj_set_views: the views of the next batch submission
@@ -480,7 +488,7 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
   HJ_HIP(grow(W.desc,
               sizeof(ImageDesc) * b->ndesc + sizeof(uint32_t) * b->nwork + L.flips.size() +
                   L.lowres.size() + L.resample.size() * sizeof(rs::ResampleDesc) +
-                  L.draft.size() * sizeof(draft::Desc),
+                  L.draft.size() * sizeof(draft::Desc) + L.reduce.size() * sizeof(rs::ReduceDesc),
               st, &b->desc));
   b->work = reinterpret_cast<uint32_t*>(b->desc + b->ndesc);
   b->flips = L.flips.empty() ? nullptr : reinterpret_cast<const uint8_t*>(b->work + b->nwork);
@@ -501,6 +509,13 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
                  : reinterpret_cast<const draft::Desc*>(
                        reinterpret_cast<const uint8_t*>(b->work + b->nwork) +
                        L.resample.size() * sizeof(rs::ResampleDesc));
+  // (... and the reduce records of a box request behind those)
+  b->reduce = L.reduce.empty()
+                  ? nullptr
+                  : reinterpret_cast<const rs::ReduceDesc*>(
+                        reinterpret_cast<const uint8_t*>(b->work + b->nwork) +
+                        L.resample.size() * sizeof(rs::ResampleDesc) +
+                        L.draft.size() * sizeof(draft::Desc));
   HJ_HIP(grow(W.chain, (size_t)(kChainHead + L.chain_granules) * 8 + 64, st, &b->chain));
   HJ_HIP(grow(W.maps, (size_t)(L.ds_wgs + L.idct_wgs + L.hs_wgs + L.sws_wgs) * 4 + 64, st,
               &b->ds_map));
@@ -604,7 +619,9 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   const size_t work_end = sizeof(ImageDesc) * B.ndesc + sizeof(uint32_t) * B.nwork;
   const size_t rs_bytes = L.resample.size() * sizeof(rs::ResampleDesc);
   const size_t draft_bytes = L.draft.size() * sizeof(draft::Desc);
-  const size_t desc_bytes = work_end + L.flips.size() + L.lowres.size() + rs_bytes + draft_bytes;
+  const size_t reduce_bytes = L.reduce.size() * sizeof(rs::ReduceDesc);
+  const size_t desc_bytes =
+      work_end + L.flips.size() + L.lowres.size() + rs_bytes + draft_bytes + reduce_bytes;
   HJ_HIP(slot.pin_desc.ensure(desc_bytes));
   HJ_HIP(slot.pin_status.ensure(sizeof(int32_t) * n));
   slot.n = n;
@@ -630,6 +647,9 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
     }
     memcpy(static_cast<uint8_t*>(slot.pin_desc.p) + work_end + rs_bytes, L.draft.data(), draft_bytes);
   }
+  if (B.reduce)  // (a resampled submission's: checked with it above)
+    memcpy(static_cast<uint8_t*>(slot.pin_desc.p) + work_end + rs_bytes + draft_bytes,
+           L.reduce.data(), reduce_bytes);
   // the batch's swscale tables travel with the descriptors (a resampled
   // submission's axis tables likewise)
   const bool swscale = !sub.planes_only && out->csc == SPDL_HJ_CSC_SWSCALE;
@@ -711,6 +731,7 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   ctx->entropy_workgroups = B.nwork;
   ctx->lowres_images = L.lowres_images;
   ctx->draft_images = L.draft_images;
+  ctx->reduce_images = L.reduce_images;
   ctx->planes_bytes = L.total_planes;
   // (a views submission whose views were all refused has no block to transform)
   if (!(abl & kAblNoIdct) && (L.ragged || !fused) && L.max_blocks > 0) {
@@ -743,7 +764,9 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
     const int sws_wgs = (int)L.sws_wgs, hs_wgs = (int)L.hs_wgs;
     if (turbo && B.resample) {
       // resample_kernel over every image's own tiles, as turbo_rgb_kernel's below
-      if (sws_wgs > 0)
+      if (sws_wgs > 0 && B.reduce)
+        HJ_HIP(launch_resample_reduce(B, sub.out_dev, bp, sws_wgs, L.resample_lds, hstat, st));
+      else if (sws_wgs > 0)
         HJ_HIP(launch_resample(B, sub.out_dev, bp, sws_wgs, L.resample_lds, hstat, st));
       ctx->resample_workgroups = sws_wgs;
     } else if (turbo) {
@@ -806,6 +829,8 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
       R.rs_filter = sub.resample->filter;
       R.rs_ow = sub.resample->out_w;
       R.rs_oh = sub.resample->out_h;
+      R.rs_by_box = sub.resample->place_box != nullptr;
+      R.rs_gap = sub.resample->gap;
     }
     const size_t img_bytes = (size_t)L.out_elems_per_image * esz;
     for (const auto& m : L.multi) {
@@ -818,7 +843,9 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
                          L.lowres.empty() ? (uint8_t)0 : L.lowres[m.first],
                          sub.resample && sub.resample->items ? sub.resample->items[m.first]
                                                              : spdl_hj_resample_item{},
-                         L.draft.empty() ? (uint8_t)0 : L.draft[m.first].level});
+                         L.draft.empty() ? (uint8_t)0 : L.draft[m.first].level,
+                         sub.resample && sub.resample->box_items ? sub.resample->box_items[m.first]
+                                                                 : spdl_hj_resample_box_item{}});
     }
     R.ticket = slot.ticket;
     R.bytes = sub.d_bytes;
@@ -891,7 +918,15 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
     rq.draft = &item.draft;
     rq.ndraft = 1;
   }
-  const ResampleRequest one{r.rs_filter, r.rs_ow, r.rs_oh, &item.resample, 1, &ctx->axes, &rs::place_into};
+  ResampleRequest one{r.rs_filter, r.rs_ow, r.rs_oh, &item.resample, 1, &ctx->axes, &rs::place_into};
+  if (r.rs_by_box) {
+    one.items = nullptr;
+    one.place = nullptr;
+    one.box_items = &item.rsbox;
+    one.gap = r.rs_gap;
+    one.place_box = &rs::place_box_into;
+    one.probe_box = &rs::probe_box;
+  }
   if (r.has_resample) rq.resample = &one;
   int rc = plan_batch(rq, L, &st1, err, errlen);
   if (rc) return rc;
@@ -911,7 +946,7 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
   const int64_t fused_wgs = ctx->fused_workgroups, generic_wgs = ctx->generic_workgroups;
   const int64_t turbo_wgs = ctx->turbo_workgroups, resample_wgs = ctx->resample_workgroups;
   const int64_t lowres_images = ctx->lowres_images, planes_bytes = ctx->planes_bytes;
-  const int64_t draft_images = ctx->draft_images;
+  const int64_t draft_images = ctx->draft_images, reduce_images = ctx->reduce_images;
   rc = run_pipeline(ctx, *s, L,
                     {r.bytes, r.len, 1, &r.out, r.out_dev + item.out_off, item.out_bytes, xs, 1,
                      &st1, false, nullptr, nullptr, false, nullptr, rq.resample},
@@ -924,6 +959,7 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
   ctx->resample_workgroups = resample_wgs;
   ctx->lowres_images = lowres_images;
   ctx->draft_images = draft_images;
+  ctx->reduce_images = reduce_images;
   ctx->planes_bytes = planes_bytes;
   ctx->last_ticket = last;
   return rc ? rc : st1;
@@ -1055,6 +1091,15 @@ struct Held {
       resample_rq = {resamplev.filter, resamplev.out_w, resamplev.out_h,
                      resamplev.has_items ? resamplev.items.data() : nullptr,
                      (int64_t)resamplev.items.size(), &ctx->axes, &rs::place_into};
+      if (resamplev.by_box) {
+        resample_rq.items = nullptr;
+        resample_rq.place = nullptr;
+        resample_rq.box_items = resamplev.has_items ? resamplev.box_items.data() : nullptr;
+        resample_rq.n = (int64_t)resamplev.box_items.size();
+        resample_rq.gap = resamplev.gap;
+        resample_rq.place_box = &rs::place_box_into;
+        resample_rq.probe_box = &rs::probe_box;
+      }
       resample = &resample_rq;
     }
     crc = take_crops(ctx, n, out, &rects, &crops, err, errlen);
@@ -1310,11 +1355,51 @@ int spdl_hj_set_resample(spdl_hj_ctx* ctx, int32_t filter, int32_t out_w, int32_
   return SPDL_HJ_OK;
 }
 
+int spdl_hj_set_resample_box(spdl_hj_ctx* ctx, int32_t filter, int32_t out_w, int32_t out_h,
+                             double reducing_gap, const spdl_hj_resample_box_item* items,
+                             int64_t n) {
+  if (!ctx || n < 0) return SPDL_HJ_ERR_INVALID_ARG;
+  // (as spdl_hj_set_resample: what the submission cannot take, the gap among
+  // it, is refused there, with nothing written)
+  ctx->resample = {};
+  ctx->resample.set = ctx->resample.by_box = true;
+  ctx->resample.filter = filter;
+  ctx->resample.out_w = out_w;
+  ctx->resample.out_h = out_h;
+  ctx->resample.gap = reducing_gap;
+  ctx->resample.has_items = items != nullptr;
+  if (items) ctx->resample.box_items.assign(items, items + n);
+  return SPDL_HJ_OK;
+}
+
+int spdl_hj_debug_reduce_plan(int32_t W, int32_t H, const spdl_hj_resample_box_item* item,
+                              int32_t out_w, int32_t out_h, int32_t filter, double reducing_gap,
+                              spdl_hj_reduce_plan* plan) {
+  if (!plan) return SPDL_HJ_ERR_INVALID_ARG;
+  rs::BoxGeo g;
+  const int rc = rs::resolve_box(item, W, H, out_w, out_h, filter, reducing_gap, &g);
+  if (rc) return rc;
+  *plan = spdl_hj_reduce_plan{g.fx, g.fy, {g.q[0], g.q[1], g.q[2], g.q[3]}, g.cw, g.ch,
+                              {g.box[0], g.box[1], g.box[2], g.box[3]}, {}, {}};
+  for (int k = 0; k < 4; k++) {
+    plan->div[k] = g.div[k];
+    plan->mult[k] = (int32_t)g.mult[k];
+  }
+  return SPDL_HJ_OK;
+}
+
 int spdl_hj_debug_resample_axis(int32_t in_size, int32_t out_size, int32_t filter, int32_t* xmin,
                                 int32_t* n, int32_t* K, int64_t cap, int32_t* ksize) {
+  return spdl_hj_debug_resample_axis_box(in_size, 0.0, (double)in_size, out_size, filter, xmin, n,
+                                         K, cap, ksize);
+}
+
+int spdl_hj_debug_resample_axis_box(int32_t in_size, double in0, double in1, int32_t out_size,
+                                    int32_t filter, int32_t* xmin, int32_t* n, int32_t* K,
+                                    int64_t cap, int32_t* ksize) {
   if (!ksize) return SPDL_HJ_ERR_INVALID_ARG;
   int rc = SPDL_HJ_OK;
-  const auto a = rs::make_axis(in_size, out_size, filter, &rc);
+  const auto a = rs::make_axis(in_size, in0, in1, out_size, filter, &rc);
   if (!a) return rc;
   *ksize = a->ksize;
   if (xmin) memcpy(xmin, a->xmin(), sizeof(int32_t) * a->out);
@@ -1957,6 +2042,7 @@ int spdl_hj_get_param(spdl_hj_ctx* ctx, const char* name, int64_t* value) {
       {"idct_workgroups", ctx->idct_workgroups},
       {"lowres_images", ctx->lowres_images},
       {"draft_images", ctx->draft_images},
+      {"reduce_images", ctx->reduce_images},
       {"planes_bytes", ctx->planes_bytes},
       {"fused_workgroups", ctx->fused_workgroups},
       {"generic_workgroups", ctx->generic_workgroups},

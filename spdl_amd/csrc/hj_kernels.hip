@@ -7186,6 +7186,215 @@ __global__ void __launch_bounds__(256) resample_kernel(const uint8_t* __restrict
 }
 
 // ---------------------------------------------------------------------------
+// resample_reduce_kernel: Pillow's Image.reduce ahead of the resize
+// (spdl_hipjpeg.h "Pillow-exact thumbnail") -- resample_kernel's grid, producer,
+// passes and store, with the tables describing the REDUCED picture and a stage
+// between producer and horizontal pass that sums fx x fy source pixels into
+// each of its cells.  The full-resolution RGB never stands in LDS, and neither
+// it nor the reduced picture in device memory.
+//
+// A tile's windows [c0, c1) x [r0, r1) are reduced cells (no alignment: the
+// producer's 8 x 2 units are aligned to the frame, not to the strip).  A strip
+// of rd.sr cell rows covers source rows Y0 .. Y1 and columns X0 .. X1 of the
+// safe box, q + cell * f clipped to it.  Per strip:
+//  a. two planes of cell sums are zeroed: R | G << 16 in the strip itself and
+//     B behind the tile's LDS (rs::reduce_lds_words), both on the strip's odd
+//     pitch, so the cells of a row lie on consecutive banks;
+//  b. a thread upsamples and converts one 8 x 2 unit of the frame, drops what
+//     lies outside [X0, X1) x [Y0, Y1), adds its two rows when they fall into
+//     one cell row, and walks the 8 columns: the pixels of one cell are summed
+//     in registers and leave as ONE ds_add per plane when the cell ends.
+//     255 fx fy fits 16 bits (rs::kReduceMaxCell), a partial sum much sooner;
+//     integer adds commute, so the sums do not depend on the waves' order;
+//  c. every cell becomes the packed u8 pixel of resample_kernel's strip, in
+//     place: ((sum + d / 2) floor(2^24 / d)) >> 24 with the (amend, mult) of
+//     its class -- last cell row, last cell column -- chosen by position;
+//  d. the horizontal pass, as resample_kernel's (lanes along the strip's rows).
+// An image of the submission without a factor has fx = fy = 1: a cell is a
+// pixel, d = 1.  (resample_kernel keeps its body, as turbo_rgb_kernel does:
+// its code object is held unchanged, so the two passes stand here again.)
+// ---------------------------------------------------------------------------
+
+// Columns [klo, khi) of a unit's row sums into the cells of one strip row: cx
+// the first column's cell, rem its offset in that cell
+__device__ __forceinline__ void reduce_add_row(uint32_t* srg, uint32_t* sb, const uint32_t (&rg)[8],
+                                               const uint32_t (&b)[8], int klo, int khi, int cx,
+                                               int rem, int fx) {
+  uint32_t arg = 0, ab = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    if (k >= klo && k < khi) {
+      arg += rg[k];
+      ab += b[k];
+      if (++rem == fx || k == khi - 1) {
+        atomicAdd(srg + cx, arg);
+        atomicAdd(sb + cx, ab);
+        arg = ab = 0;
+        rem = 0;
+        cx++;
+      }
+    }
+  }
+}
+
+template <bool DRAFT>
+__global__ void __launch_bounds__(256) resample_reduce_kernel(
+    const uint8_t* __restrict__ planes, const ImageDesc* __restrict__ desc,
+    const ImageInfo* __restrict__ infos, const rs::ResampleDesc* __restrict__ rdesc,
+    const rs::ReduceDesc* __restrict__ reduce, const int32_t* __restrict__ tables,
+    void* __restrict__ out, const BatchParams p, int32_t* __restrict__ host_status,
+    const uint32_t* __restrict__ sws_map, const draft::Desc* __restrict__ drafts) {
+  extern __shared__ uint32_t rs_lds[];
+  const int img = (int)sws_map[blockIdx.x], tid = threadIdx.x;
+  const ImageDesc& dd = desc[img];
+  const int t = (int)blockIdx.x - dd.sws_wg0;
+  const ImageInfo& in = infos[img];
+  if (host_status && t == 0 && tid == 0) host_status[img] = in.status;
+  if (in.status != kOk || dd.refuse) return;
+  const rs::ResampleDesc rd = rdesc[img];
+  const rs::ReduceDesc rr = reduce[img];
+  const rs::LdsLayout l = rs::lds_layout(rd);
+  const int ty = t / dd.sws_chunks, tx = t - ty * dd.sws_chunks;
+  const int ncol = min(rd.tw, dd.ow - tx * rd.tw), nrow = min(rd.th, dd.oh - ty * rd.th);
+  // 1. the windows, in cells, and the tile's coefficient rows
+  const rs::Window wc = rs::tile_window(tables + rd.hx, tables + rd.hn, 0, rd.ox, dd.ow, rd.tw, tx, 1);
+  const rs::Window wr = rs::tile_window(tables + rd.vx, tables + rd.vn, 0, rd.oy, dd.oh, rd.th, ty, 1);
+  const int c0 = wc.lo, ncell = wc.hi - wc.lo, r0 = wr.lo, r1 = wr.hi;
+  const int hcol0 = rd.ox + tx * rd.tw, vrow0 = rd.oy + ty * rd.th;
+  int32_t* const lds = reinterpret_cast<int32_t*>(rs_lds);
+  for (int i = tid; i < ncol; i += 256) {
+    lds[l.hx + i] = tables[rd.hx + hcol0 + i] - c0;  // (relative to the strip)
+    lds[l.hn + i] = tables[rd.hn + hcol0 + i];
+  }
+  for (int i = tid; i < ncol * rd.kh; i += 256)
+    lds[l.hk + i] = tables[rd.hk + (int64_t)hcol0 * rd.kh + i];
+  for (int i = tid; i < nrow; i += 256) {
+    lds[l.vx + i] = tables[rd.vx + vrow0 + i] - r0;  // (relative to the intermediate)
+    lds[l.vn + i] = tables[rd.vn + vrow0 + i];
+  }
+  for (int i = tid; i < nrow * rd.kv; i += 256)
+    lds[l.vk + i] = tables[rd.vk + (int64_t)vrow0 * rd.kv + i];
+  uint32_t* const strip = rs_lds + l.strip;  // the R | G << 16 sums, then the pixels
+  uint32_t* const sumb = rs_lds + l.words;   // the B sums
+  uint32_t* const inter = rs_lds + l.inter;
+  const int sr_shift = __builtin_ctz((unsigned)rd.sr);
+  // the tile's source columns, and the 8-column units of the frame over them
+  const int X0 = rr.qx + c0 * rr.fx, X1 = min(rr.qx + (c0 + ncell) * rr.fx, rr.qx + rr.qw);
+  const int ux0 = X0 >> 3, units_x = ((X1 + 7) >> 3) - ux0;
+  // 2. strips of cell rows
+  for (int s0 = r0; s0 < r1; s0 += rd.sr) {
+    const int srows = min(rd.sr, r1 - s0);
+    const int Y0 = rr.qy + s0 * rr.fy, Y1 = min(rr.qy + (s0 + srows) * rr.fy, rr.qy + rr.qh);
+    const int uy0 = Y0 >> 1, units = units_x * (((Y1 + 1) >> 1) - uy0);
+    __syncthreads();  // (the coefficient rows stand; the last strip is consumed)
+    for (int i = tid; i < srows * rd.pitch; i += 256) strip[i] = sumb[i] = 0;
+    __syncthreads();
+    for (int u = tid; u < units; u += 256) {
+      const int uy = u / units_x, ux = u - uy * units_x;
+      const int x0 = (ux0 + ux) * 8, y0 = (uy0 + uy) * 2;
+      int v[3][2][8];
+      if constexpr (DRAFT) turbo_samples_draft(planes, dd, drafts[img], x0, y0, v);
+      else turbo_samples(planes, dd, x0, y0, v);
+      uint32_t rg[2][8], bb[2][8];
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          int rgb[3];
+          turbo_pixel(dd, v[0][j][k], v[1][j][k], v[2][j][k], rgb);
+          rg[j][k] = (uint32_t)rgb[0] | (uint32_t)rgb[1] << 16;
+          bb[j][k] = (uint32_t)rgb[2];
+        }
+      }
+      // the unit's columns and rows inside the source rectangle, and their cells
+      const int klo = max(X0 - x0, 0), khi = min(X1 - x0, 8);
+      const int cx = (x0 + klo - rr.qx) / rr.fx, rem = (x0 + klo - rr.qx) - cx * rr.fx;
+      const bool ok0 = y0 >= Y0, ok1 = y0 + 1 < Y1;  // (y0 < Y1 and y0 + 1 >= Y0 by the units)
+      const int cy0 = (y0 - rr.qy) / rr.fy - s0, cy1 = (y0 + 1 - rr.qy) / rr.fy - s0;
+      if (ok0 && ok1 && cy0 == cy1) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          rg[0][k] += rg[1][k];
+          bb[0][k] += bb[1][k];
+        }
+        reduce_add_row(strip + cy0 * rd.pitch, sumb + cy0 * rd.pitch, rg[0], bb[0], klo, khi,
+                       cx - c0, rem, rr.fx);
+      } else {
+        if (ok0)
+          reduce_add_row(strip + cy0 * rd.pitch, sumb + cy0 * rd.pitch, rg[0], bb[0], klo, khi,
+                         cx - c0, rem, rr.fx);
+        if (ok1)
+          reduce_add_row(strip + cy1 * rd.pitch, sumb + cy1 * rd.pitch, rg[1], bb[1], klo, khi,
+                         cx - c0, rem, rr.fx);
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < srows * ncell; i += 256) {
+      const int row = i / ncell, col = i - row * ncell;
+      const bool right = c0 + col == rr.cw - 1, bottom = s0 + row == rr.ch - 1;
+      const uint32_t amend = bottom ? (right ? rr.amend[3] : rr.amend[2])
+                                    : (right ? rr.amend[1] : rr.amend[0]);
+      const uint32_t mult = bottom ? (right ? rr.mult[3] : rr.mult[2])
+                                   : (right ? rr.mult[1] : rr.mult[0]);
+      const uint32_t q = strip[row * rd.pitch + col], b = sumb[row * rd.pitch + col];
+      strip[row * rd.pitch + col] = (((q & 0xffffu) + amend) * mult) >> 24 |
+                                    ((((q >> 16) + amend) * mult) >> 24) << 8 |
+                                    (((b + amend) * mult) >> 24) << 16;
+    }
+    __syncthreads();
+    for (int i = tid; i < (ncol << sr_shift); i += 256) {
+      const int row = i & (rd.sr - 1), col = i >> sr_shift;
+      if (row >= srows) continue;
+      const int n = lds[l.hn + col];
+      const uint32_t* px = strip + row * rd.pitch + lds[l.hx + col];
+      const int32_t* kk = lds + l.hk + col * rd.kh;
+      uint32_t a0 = 1u << (rs::kCoefBits - 1), a1 = a0, a2 = a0;
+      for (int k = 0; k < n; k++) {
+        const uint32_t w = (uint32_t)kk[k], q = px[k];
+        a0 += w * (q & 255u);
+        a1 += w * ((q >> 8) & 255u);
+        a2 += w * (q >> 16);
+      }
+      inter[(s0 - r0 + row) * rd.tw + col] = rs_clip8(a0) | rs_clip8(a1) << 8 | rs_clip8(a2) << 16;
+    }
+  }
+  __syncthreads();
+  // 3. the vertical pass, the channel order and the store
+  const bool swap = p.pix_fmt == 1 || p.pix_fmt == 3;
+  const int groups = (ncol + 7) >> 3;
+  for (int i = tid; i < groups * nrow; i += 256) {
+    const int y = i / groups, g = i - y * groups;
+    const int n = lds[l.vn + y];
+    const uint32_t* px = inter + lds[l.vx + y] * rd.tw + 8 * g;
+    const int32_t* kk = lds + l.vk + y * rd.kv;
+    uint32_t a[3][8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) a[0][j] = a[1][j] = a[2][j] = 1u << (rs::kCoefBits - 1);
+    for (int k = 0; k < n; k++) {
+      const uint32_t w = (uint32_t)kk[k];
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const uint32_t q = px[k * rd.tw + j];
+        a[0][j] += w * (q & 255u);
+        a[1][j] += w * ((q >> 8) & 255u);
+        a[2][j] += w * (q >> 16);
+      }
+    }
+    int c0v[8], c1v[8], c2v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const int r = (int)rs_clip8(a[0][j]), b = (int)rs_clip8(a[2][j]);
+      c0v[j] = swap ? b : r;
+      c1v[j] = (int)rs_clip8(a[1][j]);
+      c2v[j] = swap ? r : b;
+    }
+    const int x = tx * rd.tw + 8 * g;
+    turbo_store_row(out, dd.out_off, p, dd.ow, dd.oh, x, ty * rd.th + y, min(8, dd.ow - x), c0v, c1v,
+                    c2v);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // launchers (host side, same TU; declared in hj_launch.h)
 // ---------------------------------------------------------------------------
 
@@ -7329,6 +7538,18 @@ static void launch_hscale(const BatchBuffers& b, int hs_wgs, hipStream_t st) {
   if (hs_wgs > 0)
     hipLaunchKernelGGL(hscale_kernel, dim3(hs_wgs), dim3(256), 0, st, b.planes, b.desc, b.infos,
                        b.wts, b.hs_map, b.hbuf);
+}
+hipError_t launch_resample_reduce(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
+                                  int lds_bytes, int32_t* host_status, hipStream_t st) {
+  if (b.draft)
+    hipLaunchKernelGGL(resample_reduce_kernel<true>, dim3(wgs), dim3(256), lds_bytes, st, b.planes,
+                       b.desc, b.infos, b.resample, b.reduce, b.wts, out, p, host_status, b.sws_map,
+                       b.draft);
+  else
+    hipLaunchKernelGGL(resample_reduce_kernel<false>, dim3(wgs), dim3(256), lds_bytes, st, b.planes,
+                       b.desc, b.infos, b.resample, b.reduce, b.wts, out, p, host_status, b.sws_map,
+                       b.draft);
+  return hipGetLastError();
 }
 hipError_t launch_sws(const BatchBuffers& b, void* out, const BatchParams& p, bool flat,
                       int sws_wgs, int bands, int chunks, int lds_bytes, int hs_wgs,

@@ -49,6 +49,9 @@ struct BatchBuffers {
   // above; null when every level is 0 -- the kernels of such a submission are
   // those of one without the call
   const draft::Desc* draft;
+  // Image.reduce records (spdl_hj_set_resample_box with a gap): one per image
+  // behind the draft records; null when no image has a factor above 1
+  const rs::ReduceDesc* reduce;
 };
 
 // parse_kernel + lut_kernel.  host_desc (descriptors, then the work list) and
@@ -85,6 +88,10 @@ hipError_t launch_turbo_rgb(const BatchBuffers& b, void* out, const BatchParams&
 // submission's largest tile (Layout::resample_lds)
 hipError_t launch_resample(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
                            int lds_bytes, int32_t* host_status, hipStream_t st);
+// resample_reduce_kernel in its place when b.reduce is set: rs::tile_reduce()'s tiles,
+// lds_bytes by rs::reduce_lds_words()
+hipError_t launch_resample_reduce(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
+                                  int lds_bytes, int32_t* host_status, hipStream_t st);
 hipError_t launch_rgb_unscaled(const BatchBuffers& b, void* out, const BatchParams& p,
                                int64_t max_px, int32_t* host_status, hipStream_t st);
 hipError_t launch_idct_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int idct,

@@ -862,15 +862,34 @@ struct Planner {
     const ResampleRequest& r = *rq.resample;
     const char* what = nullptr;
     if (rq.out->csc != SPDL_HJ_CSC_TURBO) what = "spdl_hj_set_resample needs csc = turbo";
-    else if (!rq.plans || !r.cache || !r.place) what = "spdl_hj_set_resample needs an output stage";
+    else if (!rq.plans || !r.cache || !(r.place || (r.place_box && r.probe_box)))
+      what = "spdl_hj_set_resample needs an output stage";
     else if (rq.out->pix_fmt == SPDL_HJ_FMT_YUV) what = "no resampled planar YUV output";
     else if (rq.ragged) what = "spdl_hj_set_resample and spdl_hj_set_ragged on one submission";
-    else if (r.items && r.n != rq.n) what = "spdl_hj_set_resample: one item per image of the batch";
+    else if ((r.items || r.box_items) && r.n != rq.n)
+      what = "spdl_hj_set_resample: one item per image of the batch";
+    else if (r.place_box && !(r.gap == 0.0 || r.gap >= 1.0))
+      what = "spdl_hj_set_resample_box: reducing_gap is 0 or at least 1";
     else if (r.out_w < 1 || r.out_w > 65535 || r.out_h < 1 || r.out_h > 65535)
       what = "spdl_hj_set_resample: out_w and out_h are 1 to 65535";
     else if (r.filter < 0 || r.filter > SPDL_HJ_FILTER_LANCZOS)
       what = "spdl_hj_set_resample: unknown filter";
-    if (!what) return SPDL_HJ_OK;
+    // a box request against every (draft) frame ahead of the plan: a box
+    // outside its frame refuses the submission, and one factor above 1 makes
+    // it resample_reduce_kernel's
+    bool reduces = false;
+    for (int i = 0; !what && r.place_box && i < rq.n; i++) {
+      int W = rq.infos[i].width, H = rq.infos[i].height, any = 0, pw[kMaxComp], ph[kMaxComp];
+      if (!L.draft.empty() && rq.infos[i].ncomp != 4) draft_plan(rq.infos[i], rq.draft[i], &W, &H, pw, ph);
+      if (r.probe_box(r.filter, r.gap, r.box_items ? &r.box_items[i] : nullptr, W, H, r.out_w,
+                      r.out_h, &any) == SPDL_HJ_ERR_INVALID_ARG)
+        what = "spdl_hj_set_resample_box: a box is empty or reaches outside its frame";
+      reduces |= any != 0;
+    }
+    if (!what) {
+      if (reduces) L.reduce.assign(rq.n, rs::ReduceDesc{});
+      return SPDL_HJ_OK;
+    }
     res.rc = SPDL_HJ_ERR_INVALID_ARG;
     snprintf(res.err, sizeof(res.err), "%s", what);
     return res.rc;
@@ -885,11 +904,20 @@ struct Planner {
     const ResampleRequest& r = *rq.resample;
     rs::ResampleDesc t;
     int bands, chunks;
-    if (const int rc = r.place(r.cache, r.filter, r.items ? &r.items[i] : nullptr, W, H,
-                               r.out_w, r.out_h, L.tables, rs_pool, &t, &bands, &chunks))
+    if (r.place_box) {
+      rs::ReduceDesc* red = L.reduce.empty() ? nullptr : &L.reduce[i];
+      if (const int rc = r.place_box(r.cache, r.filter, r.gap, r.box_items ? &r.box_items[i] : nullptr,
+                                     W, H, r.out_w, r.out_h, L.tables, rs_pool, &t, red, &bands,
+                                     &chunks))
+        return rc;
+      if (red && (red->fx > 1 || red->fy > 1)) L.reduce_images++;
+    } else if (const int rc = r.place(r.cache, r.filter, r.items ? &r.items[i] : nullptr, W, H,
+                                      r.out_w, r.out_h, L.tables, rs_pool, &t, &bands, &chunks)) {
       return rc;
+    }
     L.resample[i] = t;
-    L.resample_lds = std::max(L.resample_lds, rs::lds_layout(t).words * 4);
+    L.resample_lds = std::max(L.resample_lds, (L.reduce.empty() ? rs::lds_layout(t).words
+                                                                : rs::reduce_lds_words(t)) * 4);
     d.sws_wg0 = (int32_t)L.sws_wgs;
     d.sws_bands = bands;
     d.sws_chunks = chunks;

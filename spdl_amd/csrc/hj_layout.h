@@ -150,6 +150,12 @@ struct Layout {
   // items' coordinates of an image with L > 0 are the draft frame's.
   std::vector<draft::Desc> draft;
   int draft_images = 0;  // images with L > 0
+  // Image.reduce ahead of the resize (spdl_hj_set_resample_box with a gap): one
+  // record per image for resample_reduce_kernel, which then takes the place of
+  // resample_kernel; resample_lds is its LDS.  Empty when no image of the
+  // submission has a factor above 1: that submission launches resample_kernel.
+  std::vector<rs::ReduceDesc> reduce;
+  int reduce_images = 0;  // images with a factor above 1
 };
 
 // Image p at draft level lv (0..3), as libjpeg-turbo's scale (8 >> lv) / 8
@@ -199,12 +205,29 @@ struct ResamplePool {
 using ResamplePlaceFn = int (*)(void* cache, int filter, const spdl_hj_resample_item* it, int W,
                                 int H, int out_w, int out_h, std::vector<int32_t>& tables,
                                 ResamplePool& pool, rs::ResampleDesc* d, int* bands, int* chunks);
+// spdl_hj_set_resample_box's request the same way: rs::place_box_into (red
+// null: the image's record for resample_kernel; else resample_reduce_kernel's
+// pair) and rs::probe_box (the request's status against a W x H frame, and
+// whether it has a factor above 1)
+using ResampleBoxPlaceFn = int (*)(void* cache, int filter, double gap,
+                                   const spdl_hj_resample_box_item* it, int W, int H, int out_w,
+                                   int out_h, std::vector<int32_t>& tables, ResamplePool& pool,
+                                   rs::ResampleDesc* d, rs::ReduceDesc* red, int* bands,
+                                   int* chunks);
+using ResampleBoxProbeFn = int (*)(int filter, double gap, const spdl_hj_resample_box_item* it,
+                                   int W, int H, int out_w, int out_h, int* reduces);
 struct ResampleRequest {
   int filter, out_w, out_h;
   const spdl_hj_resample_item* items;
   int64_t n;
   void* cache;
   ResamplePlaceFn place;
+  // spdl_hj_set_resample_box (place_box set): box_items in place of items
+  // (null: every whole frame), the reducing gap (0: none)
+  const spdl_hj_resample_box_item* box_items = nullptr;
+  double gap = 0;
+  ResampleBoxPlaceFn place_box = nullptr;
+  ResampleBoxProbeFn probe_box = nullptr;
 };
 
 // One submission as the planner sees it: n images at offsets[i], sizes[i] of

@@ -29,12 +29,14 @@ constexpr int kMaxTaps = SPDL_HJ_RESAMPLE_MAX_TAPS;
 constexpr int kLdsBudget = 64 * 1024;
 constexpr int kTileW = 64, kTileH = 32, kStripRows = 32;  // the tiler's first choice
 
-// One axis of a resample: inSize samples over [0, inSize) into outSize.
+// One axis of a resample: the box [in0, in1) of inSize samples into outSize
+// (an integer request: in0 = 0, in1 = inSize of the cropped frame).
 // Output xx sums n[xx] samples from xmin[xx] on with the row K[xx * ksize ..];
 // ksize = max n.  blob is the three tables as the pool holds them:
 // xmin[outSize], n[outSize], K[outSize * ksize].
 struct Axis {
   int in = 0, out = 0, filter = 0, ksize = 0;
+  double in0 = 0, in1 = 0;
   std::vector<int32_t> blob;
   const int32_t* xmin() const { return blob.data(); }
   const int32_t* n() const { return blob.data() + out; }
@@ -43,18 +45,25 @@ struct Axis {
 };
 
 // The tap count of the widest output of an axis, without building it
-int axis_taps(int in, int out, int filter);
+int axis_taps(int in, double in0, double in1, int out, int filter);
+inline int axis_taps(int in, int out, int filter) { return axis_taps(in, 0.0, (double)in, out, filter); }
 // The axis, or null: sizes outside 1..65535, an unknown filter, or more than
 // kMaxTaps taps (*rc = SPDL_HJ_ERR_BAD_GEOMETRY)
-std::shared_ptr<const Axis> make_axis(int in, int out, int filter, int* rc);
+std::shared_ptr<const Axis> make_axis(int in, double in0, double in1, int out, int filter, int* rc);
+inline std::shared_ptr<const Axis> make_axis(int in, int out, int filter, int* rc) {
+  return make_axis(in, 0.0, (double)in, out, filter, rc);
+}
 
-// Axes by (inSize, outSize, filter): a box's origin is not in the key, the
-// kernel adds it.  The context's; a RandomResizedCrop stream has a new key per
+// Axes by (inSize, in0, in1, outSize, filter): an integer box's origin is not
+// in the key, the kernel adds it; a float box's xmin is absolute in its frame.  The context's; a RandomResizedCrop stream has a new key per
 // image, so the cache is emptied when it has grown to kCap axes.
 struct AxisCache {
   static constexpr size_t kCap = 512;
-  std::map<std::tuple<int, int, int>, std::shared_ptr<const Axis>> held;
-  std::shared_ptr<const Axis> get(int in, int out, int filter, int* rc);
+  std::map<std::tuple<int, double, double, int, int>, std::shared_ptr<const Axis>> held;
+  std::shared_ptr<const Axis> get(int in, double in0, double in1, int out, int filter, int* rc);
+  std::shared_ptr<const Axis> get(int in, int out, int filter, int* rc) {
+    return get(in, 0.0, (double)in, out, filter, rc);
+  }
 };
 
 // One image's request against its W x H frame and the out_w x out_h box:
@@ -85,6 +94,43 @@ int place(AxisCache& cache, int filter, const spdl_hj_resample_item* it, int W, 
 int place_into(void* cache, int filter, const spdl_hj_resample_item* it, int W, int H, int out_w,
                int out_h, std::vector<int32_t>& tables, ResamplePool& pool, ResampleDesc* d,
                int* bands, int* chunks);
+
+// ---- spdl_hj_set_resample_box: Pillow's float box= and reducing_gap= ----
+// One image's request against its W x H frame, resolved in Pillow's order: the
+// factors (1, 1 without a gap), the safe box q = (x0, y0, x1, y1), the reduced
+// picture cw x ch (the frame itself when both factors are 1: q the frame), the
+// box in it, and the four cell classes' divisors -- interior, right, bottom,
+// corner -- with floor(2^24 / d).
+struct BoxGeo {
+  int fx, fy, q[4], cw, ch;
+  double box[4];
+  int div[4];
+  uint32_t mult[4];
+  int rw, rh, ox, oy;
+};
+// 0; SPDL_HJ_ERR_INVALID_ARG (the submission's): a gap in (0, 1) or no number,
+// a box that is empty or outside the frame; SPDL_HJ_ERR_BAD_GEOMETRY (the
+// image's): the resized picture or the window, fx fy above kReduceMaxCell, a
+// frame with H > 100 W whose height shrinks
+int resolve_box(const spdl_hj_resample_box_item* it, int W, int H, int out_w, int out_h, int filter,
+                double gap, BoxGeo* g);
+
+// The tiling for resample_reduce_kernel: windows in reduced cells, no
+// alignment (the producer's units are the frame's, not the strip's), and the
+// B sums' plane beside the strip (rs::reduce_lds_words)
+int tile_reduce(const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h, ResampleDesc* d,
+                int* bands, int* chunks);
+
+// place_into for a box request.  red == null: the submission has no factor
+// above 1 and the record is resample_kernel's; else resample_reduce_kernel's,
+// *red beside it.  The planner's ResampleRequest::place_box.
+int place_box_into(void* cache, int filter, double gap, const spdl_hj_resample_box_item* it, int W,
+                   int H, int out_w, int out_h, std::vector<int32_t>& tables, ResamplePool& pool,
+                   ResampleDesc* d, ReduceDesc* red, int* bands, int* chunks);
+// ... and what the planner asks ahead of every image: the request's status
+// against this frame and whether it has a factor above 1 (ResampleRequest::probe_box)
+int probe_box(int filter, double gap, const spdl_hj_resample_box_item* it, int W, int H, int out_w,
+              int out_h, int* reduces);
 
 }  // namespace rs
 }  // namespace hj

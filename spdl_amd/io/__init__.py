@@ -15,6 +15,7 @@ from ._image import (
     load_image_list,
     load_image_views,
     pil_resize,
+    pil_thumbnail,
 )
 from ._preprocessing import get_video_filter_desc, parse_image_filter
 from ._tar import TarImageStream, iter_tarfile
@@ -56,6 +57,7 @@ __all__ = [
     "nv12_to_rgb",
     "parse_image_filter",
     "pil_resize",
+    "pil_thumbnail",
     "to_numpy",
     "to_torch",
     "transfer_buffer",

@@ -11,6 +11,7 @@ All of them decode on the GPU (gfx950 kernels); there is no CPU path.
 from __future__ import annotations
 
 import logging
+import math
 import os
 import warnings
 from collections.abc import Mapping, Sequence
@@ -362,6 +363,13 @@ class PilResize:
     filter: str = "bilinear"
     boxes: tuple | None = None
     shorter: int | None = None
+    resize_boxes: tuple | None = None
+    reducing_gap: float | None = None
+
+    @property
+    def by_box(self) -> bool:
+        """Pillow's own ``box=`` / ``reducing_gap=`` (spdl_hj_set_resample_box)"""
+        return self.resize_boxes is not None or self.reducing_gap is not None
 
     def geometry(self, width: int, height: int, box=None):
         """One image's item ``(box, (rw, rh), (ox, oy))`` for a ``width x
@@ -373,6 +381,8 @@ class PilResize:
         image; a window larger than the resized picture is refused by the
         decoder (torchvision would pad)."""
         w, h = self.size
+        if self.by_box:
+            return box, (w, h), (0, 0)
         if self.shorter is None:
             return box, (w, h), (0, 0)
         sw, sh = (box[2], box[3]) if box is not None else (width, height)
@@ -383,7 +393,8 @@ class PilResize:
         return box, (rw, rh), (int(round((rw - w) / 2.0)), int(round((rh - h) / 2.0)))
 
 
-def pil_resize(size, filter: str = "bilinear", boxes=None, shorter=None) -> PilResize:
+def pil_resize(size, filter: str = "bilinear", boxes=None, shorter=None, resize_boxes=None,
+               reducing_gap=None) -> PilResize:
     """Pillow's ``Image.resize`` on the GPU, for ``csc="turbo"``: the output is
     ``np.asarray(Image.open(f).convert("RGB").crop(box).resize(size, filter))``
     byte for byte (include/spdl_hipjpeg.h "Pillow-exact resize").  ``size=(w,
@@ -391,7 +402,24 @@ def pil_resize(size, filter: str = "bilinear", boxes=None, shorter=None) -> PilR
     ``"lanczos"``.  ``boxes``: per image a source rectangle ``(x, y, w, h)`` or
     ``None`` -- ``RandomResizedCrop``'s crop.  ``shorter``: resize the shorter
     side to this and write the centred ``size`` window -- ``Resize(shorter)``
-    then ``CenterCrop(size)`` (:meth:`PilResize.geometry`)."""
+    then ``CenterCrop(size)`` (:meth:`PilResize.geometry`).  ``resize_boxes``
+    and ``reducing_gap`` are ``Image.resize(size, filter, box=, reducing_gap=)``
+    itself (include/spdl_hipjpeg.h "Pillow-exact thumbnail"): per image a float
+    box ``(x0, y0, x1, y1)`` or ``None``, whose taps reach past its edge into the
+    frame -- which ``boxes``, a crop, does not do -- and a gap of at least 1,
+    which runs ``Image.reduce`` by whole factors ahead of the resize.
+    ``resize_boxes`` is exclusive with ``boxes`` and ``shorter``;
+    ``reducing_gap`` alone takes the whole frame."""
+    if resize_boxes is not None or reducing_gap is not None:
+        if boxes is not None or shorter is not None:
+            raise ValueError("resize_boxes= / reducing_gap= are exclusive with boxes= and shorter=")
+        if reducing_gap is not None and not float(reducing_gap) >= 1.0:
+            raise ValueError(f"reducing_gap is at least 1.0, not {reducing_gap!r}")
+    if resize_boxes is not None:
+        resize_boxes = tuple(None if b is None else tuple(float(v) for v in b) for b in resize_boxes)
+        if any(b is not None and (len(b) != 4 or not (0 <= b[0] < b[2] and 0 <= b[1] < b[3]))
+               for b in resize_boxes):
+            raise ValueError("a resize box is (x0, y0, x1, y1) with x0 < x1 and y0 < y1, or None")
     if len(size) != 2 or any(int(v) != v or not 1 <= v <= 65535 for v in size):
         raise ValueError(f"size is (width, height), each 1..65535, not {size!r}")
     if filter not in _lib.FILTERS:
@@ -403,7 +431,74 @@ def pil_resize(size, filter: str = "bilinear", boxes=None, shorter=None) -> PilR
         if any(b is not None and len(b) != 4 for b in boxes):
             raise ValueError("a box is (x, y, w, h) or None")
     return PilResize((int(size[0]), int(size[1])), filter, boxes,
-                     None if shorter is None else int(shorter))
+                     None if shorter is None else int(shorter), resize_boxes,
+                     None if reducing_gap is None else float(reducing_gap))
+
+
+@dataclass(frozen=True)
+class PilThumbnail:
+    """What :func:`pil_thumbnail` returns: ``resample=`` of :func:`load_image`
+    and :func:`load_image_batch`."""
+    size: tuple
+    filter: str = "bicubic"
+    reducing_gap: float | None = 2.0
+
+    def plan(self, width: int, height: int):
+        """``Image.thumbnail`` of a ``width x height`` file, restated: ``(level,
+        final_size, box)`` -- the draft level, the thumbnail's size, and
+        ``resize``'s float box in the draft frame (``None``: the frame is the
+        result as it is)."""
+        x, y = self.size
+        if x >= width and y >= height:
+            return 0, (width, height), None
+
+        def round_aspect(number, key):
+            return max(min(math.floor(number), math.ceil(number), key=key), 1)
+
+        aspect = width / height
+        if x / y >= aspect:
+            x = round_aspect(y * aspect, key=lambda n: abs(aspect - n / y))
+        else:
+            y = round_aspect(x / aspect, key=lambda n: 0 if n == 0 else abs(aspect - x / n))
+        level, box = 0, (0.0, 0.0, float(width), float(height))
+        if self.reducing_gap is not None:
+            g = self.reducing_gap
+            level = _lib.draft_level(width, height, int(self.size[0] * g), int(self.size[1] * g))
+            box = (0.0, 0.0, width / (1 << level), height / (1 << level))
+        if _lib.draft_size(width, height, level) == (x, y):
+            box = None
+        return level, (x, y), box
+
+
+def pil_thumbnail(size, filter: str = "bicubic", reducing_gap=2.0) -> PilThumbnail:
+    """Pillow's ``Image.thumbnail(size, filter, reducing_gap)`` on the GPU, for
+    ``csc="turbo"``: the draft decode, ``Image.reduce`` and the float-box resize
+    in its order, byte for byte (include/spdl_hipjpeg.h "Pillow-exact
+    thumbnail").  Accepted wherever ``resample=`` is, without ``draft=``: the
+    level is resolved per file.  ``load_image`` returns the file's own final
+    size; ``load_image_batch`` needs every file to resolve to one."""
+    size = tuple(math.floor(v) for v in size)
+    if len(size) != 2 or any(not 1 <= v <= 65535 for v in size):
+        raise ValueError(f"size is (width, height), each 1..65535, not {size!r}")
+    if filter not in _lib.FILTERS:
+        raise ValueError(f"filter must be one of {sorted(_lib.FILTERS)}, not {filter!r}")
+    if reducing_gap is not None and not float(reducing_gap) >= 1.0:
+        raise ValueError(f"reducing_gap is at least 1.0 or None, not {reducing_gap!r}")
+    return PilThumbnail(size, filter, None if reducing_gap is None else float(reducing_gap))
+
+
+def _thumbnail_of(thumb: PilThumbnail, infos):
+    """A thumbnail request resolved for these files: ``(levels, PilResize)``;
+    ``ValueError`` naming the sizes when they do not resolve to one."""
+    plans = [thumb.plan(i.width, i.height) for i in infos]
+    sizes = sorted({p[1] for p in plans})
+    if len(sizes) != 1:
+        raise ValueError(f"pil_thumbnail: the files resolve to different sizes {sizes}; one "
+                         "submission writes one size (ragged resample output is out of scope)")
+    levels = [p[0] for p in plans]
+    gap = thumb.reducing_gap if any(p[2] is not None for p in plans) else None
+    rs = PilResize(sizes[0], thumb.filter, None, None, tuple(p[2] for p in plans), gap)
+    return (levels if any(levels) else None), rs
 
 
 def _check_resample(resample, csc, n_src, filter_desc, pix_fmt) -> None:
@@ -411,12 +506,13 @@ def _check_resample(resample, csc, n_src, filter_desc, pix_fmt) -> None:
     ``csc="turbo"`` excludes is :func:`_check_csc`'s to refuse."""
     if resample is None:
         return
-    if not isinstance(resample, PilResize):
-        raise ValueError("resample= takes what pil_resize() returns")
+    if not isinstance(resample, (PilResize, PilThumbnail)):
+        raise ValueError("resample= takes what pil_resize() or pil_thumbnail() returns")
     if csc != "turbo":
         raise ValueError(f"resample= needs csc='turbo', not {csc!r}")
-    if resample.boxes is not None and len(resample.boxes) != n_src:
-        raise ValueError(f"{len(resample.boxes)} boxes for {n_src} images")
+    for boxes in (getattr(resample, "boxes", None), getattr(resample, "resize_boxes", None)):
+        if boxes is not None and len(boxes) != n_src:
+            raise ValueError(f"{len(boxes)} boxes for {n_src} images")
     if filter_desc is not None and filter_desc != _FILTER_DESC_DEFAULT:
         _with_csc(parse_image_filter(filter_desc, default_pix_fmt=pix_fmt), csc)
 
@@ -424,12 +520,13 @@ def _check_resample(resample, csc, n_src, filter_desc, pix_fmt) -> None:
 def _resample_of(resample: PilResize, infos, keep, levels=None) -> _lib.Resample:
     """The decoder's request for the images ``keep`` of the sources; with draft
     ``levels`` every frame is its draft frame, as after ``im.draft()``."""
-    boxes = resample.boxes
+    boxes = resample.resize_boxes if resample.by_box else resample.boxes
     sizes = [(i.width, i.height) if levels is None else _lib.draft_size(i.width, i.height, lv)
              for i, lv in zip(infos, levels or [0] * len(infos))]
     items = tuple(resample.geometry(w, h, None if boxes is None else boxes[k])
                   for (w, h), k in zip(sizes, keep))
-    return _lib.Resample(resample.filter, *resample.size, items)
+    return _lib.Resample(resample.filter, *resample.size, items, resample.by_box,
+                         resample.reducing_gap)
 
 
 def _check_draft(draft, csc, resample, n_src) -> None:
@@ -438,6 +535,8 @@ def _check_draft(draft, csc, resample, n_src) -> None:
     excludes is :func:`_check_csc`'s to refuse."""
     if draft is None:
         return
+    if isinstance(resample, PilThumbnail):
+        raise ValueError("draft= and pil_thumbnail(): the thumbnail resolves the level per file")
     if csc != "turbo":
         raise ValueError(f"draft= needs csc='turbo', not {csc!r}")
     if isinstance(draft, str):
@@ -445,7 +544,7 @@ def _check_draft(draft, csc, resample, n_src) -> None:
             raise ValueError(f'draft= takes 0..3, a list of them, a (w, h) request or "auto", not {draft!r}')
         if resample is None:
             raise ValueError('draft="auto" needs resample=pil_resize(...): it covers the requested output')
-        if resample.boxes is not None:
+        if resample.boxes is not None or resample.resize_boxes is not None:
             raise ValueError('draft="auto" and boxes: a box is in the draft frame\'s coordinates, '
                              "so the level comes first")
     elif isinstance(draft, list) and len(draft) != n_src:
@@ -575,7 +674,7 @@ def load_image_batch(
     (:func:`spdl_amd._lib.draft_level`).  A ``resample`` then acts on the draft
     frame, as after ``im.draft()``; ``draft="auto"`` with it picks per image
     the largest level whose frame still covers the requested output
-    (``thumbnail``'s rule without ``reducing_gap``)."""
+    (``Image.thumbnail`` itself is ``resample=pil_thumbnail(...)``)."""
     if not srcs:
         raise ValueError("`srcs` must not be empty.")
     storage = kwargs.pop("storage", None)
@@ -681,7 +780,12 @@ def load_image_batch(
     src = _src_size(info, crops[0] if crops is not None else out.src_crop)
     if levels is not None:  # (the chain sees the reduced frame)
         src = _lib.lowres_size(*src, levels[0])
-    dlevels = _draft_levels(draft, infos, keep, resample)
+    if isinstance(resample, PilThumbnail):  # (before anything is submitted)
+        dlevels, resample = _thumbnail_of(resample, infos)
+        rs_keep = list(range(len(infos)))  # (its boxes are the kept files')
+    else:
+        rs_keep = keep
+        dlevels = _draft_levels(draft, infos, keep, resample)
     if dlevels is not None:  # (the output is the draft frame)
         src = _lib.draft_size(*src, dlevels[0])
     ow, oh = _oriented_size(src, out, orients[0] if orients else _lib._orient(out.orient))
@@ -692,7 +796,7 @@ def load_image_batch(
         shape = _shape(out, ow, oh)
     rs = None
     if resample is not None:  # (every image leaves at the request's size)
-        rs = _resample_of(resample, infos, keep, dlevels)
+        rs = _resample_of(resample, infos, rs_keep, dlevels)
         shape = _shape(out, *resample.size)
     try:
         buf = _decode(datas, out, cfg, shape, True, dtype=dtype, crops=crops, flips=flips,
@@ -710,7 +814,8 @@ def load_image_batch(
                                     orients=None if orients is None else [orients[k]],
                                     lowres=None if levels is None else [levels[k]],
                                     resample=rs and _lib.Resample(rs.filter, rs.out_w, rs.out_h,
-                                                                  (rs.items[k],)),
+                                                                  (rs.items[k],), rs.by_box,
+                                                                  rs.reducing_gap),
                                     draft=None if dlevels is None else [dlevels[k]]))
             except RuntimeError as err:
                 _LG.error("Failed to decode an image: %s", err)
@@ -1172,7 +1277,10 @@ def load_image(
         shape = _yuv_shape([info], out, src)
     else:
         shape = _shape(out, *_oriented_size(src, out, _lib._orient(out.orient)))
-    dlevels = _draft_levels(draft, [info], [0], resample)
+    if isinstance(resample, PilThumbnail):
+        dlevels, resample = _thumbnail_of(resample, [info])
+    else:
+        dlevels = _draft_levels(draft, [info], [0], resample)
     if dlevels is not None:  # (the output is the draft frame)
         shape = _shape(out, *_lib.draft_size(*src, dlevels[0]))
     rs = None
