@@ -643,9 +643,9 @@ int spdl_hj_set_lowres(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n);
  * workgroups in the last submission; "turbo_workgroups" is 0 for it.
  *
  * Out of scope: the BOX, HAMMING
- * and NEAREST filters; ragged output sizes; an IDCT of the MCUs a box touches
- * alone (the whole frame is transformed); flips and orientations on a
- * resampled submission; gamma-aware or float resampling. */
+ * and NEAREST filters; an IDCT of the MCUs a box touches alone (the whole frame
+ * is transformed); orientations on a resampled submission; gamma-aware or float
+ * resampling.  (Ragged output sizes and flips: spdl_hj_set_resample_items.) */
 #define SPDL_HJ_RESAMPLE_MAX_TAPS 256
 typedef struct spdl_hj_resample_item {
   spdl_hj_rect box;      /* source rectangle of the W x H frame; w == 0: the whole frame */
@@ -750,8 +750,8 @@ int spdl_hj_set_draft(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n);
  * layer's pil_thumbnail restates it.
  *
  * The read-only parameter "reduce_images" reports the images with a factor
- * above 1 in the last submission.  Out of scope: thumbnails of several sizes in
- * one submission (ragged resampled output). */
+ * above 1 in the last submission.  Thumbnails of several sizes in one
+ * submission are spdl_hj_set_resample_items'. */
 #define SPDL_HJ_REDUCE_MAX_CELL 256
 typedef struct spdl_hj_resample_box_item {
   double x0, y0, x1, y1; /* Pillow's box= in the frame; all zero: the whole frame */
@@ -779,6 +779,78 @@ typedef struct spdl_hj_reduce_plan {
 int spdl_hj_debug_reduce_plan(int32_t W, int32_t H, const spdl_hj_resample_box_item* item,
                               int32_t out_w, int32_t out_h, int32_t filter, double reducing_gap,
                               spdl_hj_reduce_plan* plan);
+
+/* ---- Pillow-exact resample items: several outputs per image, each its own
+ * size (additive in ABI 7: two calls, two read-only parameters) ----------------
+ * spdl_hj_set_resample_items makes the NEXT batch submission one whose unit of
+ * output is an ITEM: an image of the batch, a box of it, a resized picture, the
+ * written window, a flip, and an output rectangle of its own at a byte offset of
+ * its own in the submission's one output buffer.  Any number of items per
+ * image, in any order; an image without items is decoded and nothing is written
+ * for it.  Every image is entropy-decoded and inverse-transformed once.  This
+ * is the thumbnail or Resize(int) of files of mixed sizes, DINO / SwAV
+ * multi-crop and RandomResizedCrop + RandomHorizontalFlip with Pillow's pixels.
+ * One-shot, exclusive with spdl_hj_set_resample / _box (the later call holds).
+ * The spec is a resampled submission's: csc = TURBO, resize = 0, an RGB / BGR
+ * pix_fmt, u8 / f16 / bf16 for all items.
+ *
+ * An item with clamp = 1 is
+ *   flip(np.asarray(im.crop(box).resize((rw, rh), filter, reducing_gap = g))
+ *          [oy : oy + out_h, ox : ox + out_w])
+ * (an integral box; taps stop at the box, as spdl_hj_set_resample's); with
+ * clamp = 0 it is im.resize((rw, rh), filter, box = box, reducing_gap = g),
+ * whose taps reach past the box to the frame's edge, as
+ * spdl_hj_set_resample_box's.  An all-zero box is the whole frame.  The gap
+ * resolves against the item's own box and (rw, rh); with spdl_hj_set_draft the
+ * boxes are in the draft frame's coordinates.  flip: SPDL_HJ_FLIP_* bits
+ * applied to the written window in the store (bit 0 mirrors its columns, bit 1
+ * its rows).  offset: the byte offset of the item's tight [out_h, out_w, 3]
+ * (planar: [3, out_h, out_w]) box, a multiple of the element size.  Overlap
+ * between items is the caller's business.
+ *
+ * status (NULL or n_items entries, which must outlive the submitting call): 0
+ * or SPDL_HJ_ERR_BAD_GEOMETRY for an item refused alone -- under the conditions
+ * of spdl_hj_set_resample / _box: taps above SPDL_HJ_RESAMPLE_MAX_TAPS, rw / rh
+ * or the window, fx fy above the cap, H > 100 W, a clamped box outside its
+ * frame.  That item's bytes are untouched and every other item is written.  The
+ * items of a failed image are untouched; their status is the image's, which the
+ * submission reports per image as always.
+ * SPDL_HJ_ERR_INVALID_ARG from the consuming call, nothing written: what
+ * spdl_hj_set_resample refuses; an image index outside the batch; an item that
+ * reaches past the buffer or whose offset is no multiple of the element size; a
+ * flip above 3; clamp = 1 with a non-integral box; an unclamped box that is
+ * empty or outside its frame; items together with spdl_hj_set_ragged, views,
+ * source crops, spdl_hj_set_flips / _orients or spdl_hj_set_lowres.
+ *
+ * resample_items_kernel's grid runs over the items' tiles, one image's items
+ * adjacent.  The read-only parameters "resample_items" and
+ * "resample_item_workgroups" report the items placed (not refused) and the
+ * workgroups launched in the last submission.
+ * Out of scope: orientations (transpose codes) on items; per-item dtypes or
+ * formats; an IDCT restricted to the MCUs the items touch. */
+typedef struct spdl_hj_resample_items_item {
+  int32_t image;         /* index into the batch */
+  int32_t clamp;         /* 1: .crop(box).resize(); 0: resize(box=) */
+  double x0, y0, x1, y1; /* Pillow's box= in the (draft) frame; all zero: the whole frame */
+  int32_t rw, rh;        /* the resized picture */
+  int32_t ox, oy;        /* the out_w x out_h window of it that is written */
+  int32_t out_w, out_h;
+  int32_t flip;          /* SPDL_HJ_FLIP_* bits, 0..3 */
+  int32_t reserved;
+  int64_t offset;        /* bytes into the output buffer */
+} spdl_hj_resample_items_item;
+int spdl_hj_set_resample_items(spdl_hj_ctx* ctx, int32_t filter, double reducing_gap,
+                               const spdl_hj_resample_items_item* items, int64_t n_items,
+                               int32_t* status);
+/* The same request against n probed images, without a device or a context: the
+ * return value is what the consuming call would return for the request itself
+ * (0 or SPDL_HJ_ERR_INVALID_ARG), status[i] item i's own (0 or
+ * SPDL_HJ_ERR_BAD_GEOMETRY).  draft: n levels or NULL; elem_size 1 or 2;
+ * out_bytes the buffer the offsets address. */
+int spdl_hj_resample_items_check(const spdl_hj_image_info* infos, int32_t n, const uint8_t* draft,
+                                 int32_t filter, double reducing_gap,
+                                 const spdl_hj_resample_items_item* items, int64_t n_items,
+                                 int32_t elem_size, int64_t out_bytes, int32_t* status);
 
 /* ABI version of the loaded library (== SPDL_HJ_ABI_VERSION). */
 int spdl_hj_abi_version(void);
@@ -1039,7 +1111,9 @@ const char* spdl_hj_stage_name(int32_t i);
  * Pillow-exact resize), those of resample_kernel; "draft_images" (with the
  * Pillow-exact draft), the images of the last submission with a draft level
  * above 0; "reduce_images" (with spdl_hj_set_resample_box), those with a
- * reduce factor above 1.
+ * reduce factor above 1; "resample_items" and "resample_item_workgroups" (with
+ * spdl_hj_set_resample_items), the items placed in the last submission and
+ * the workgroups of resample_items_kernel.
  * Builds with -DHJ_ABLATIONS=1 also take "debug_mask" (timing ablations that
  * skip kernel phases; outputs wrong); release builds reject it. */
 int spdl_hj_set_param(spdl_hj_ctx* ctx, const char* name, int64_t value);

@@ -69,6 +69,8 @@ EXPORTED = (
     "spdl_hj_set_resample_box",
     "spdl_hj_debug_resample_axis_box",
     "spdl_hj_debug_reduce_plan",
+    "spdl_hj_set_resample_items",
+    "spdl_hj_resample_items_check",
 )
 
 
@@ -480,6 +482,10 @@ def lib() -> ctypes.CDLL:
             L.spdl_hj_debug_resample_axis_box.argtypes = [i32, f64, f64, i32, i32, vp, vp, vp, i64,
                                                           ctypes.POINTER(i32)]
             L.spdl_hj_debug_reduce_plan.argtypes = [i32, i32, vp, i32, i32, i32, f64, vp]
+        if hasattr(L, "spdl_hj_set_resample_items"):  # (likewise)
+            L.spdl_hj_set_resample_items.argtypes = [vp, i32, ctypes.c_double, vp, i64, vp]
+            L.spdl_hj_resample_items_check.argtypes = [vp, i32, vp, i32, ctypes.c_double, vp, i64,
+                                                       i32, i64, vp]
         ver = L.spdl_hj_abi_version()
         # (an explicitly chosen older build, ABI >= 5, loads for A/B runs)
         if ver != ABI_VERSION and not (os.environ.get("SPDL_AMD_LIB") and 5 <= ver < ABI_VERSION):
@@ -551,6 +557,95 @@ def _resample_c(resample: Resample) -> tuple:
             raise ValueError(f"a resample item is (box | None, (rw, rh), (ox, oy)): {err}") from None
     return (FILTERS[resample.filter], int(resample.out_w), int(resample.out_h), arr,
             0 if items is None else len(items))
+
+
+class ResampleItemsItem(ctypes.Structure):  # spdl_hj_resample_items_item
+    _fields_ = [("image", ctypes.c_int32), ("clamp", ctypes.c_int32), ("x0", ctypes.c_double),
+                ("y0", ctypes.c_double), ("x1", ctypes.c_double), ("y1", ctypes.c_double),
+                ("rw", ctypes.c_int32), ("rh", ctypes.c_int32), ("ox", ctypes.c_int32),
+                ("oy", ctypes.c_int32), ("out_w", ctypes.c_int32), ("out_h", ctypes.c_int32),
+                ("flip", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_int64)]
+
+
+class ResampleItems:
+    """An items submission (spdl_hj_set_resample_items, include/spdl_hipjpeg.h
+    "resample items"): several outputs per image, each its own size, from one
+    decode.  ``items``: per item ``(image, box, clamp, (rw, rh), (ox, oy),
+    (out_w, out_h), flip, offset)`` -- the image's index in the batch, Pillow's
+    ``box=`` ``(x0, y0, x1, y1)`` or ``None`` for the whole frame, ``clamp``
+    (``True``: ``.crop(box).resize()``, an integral box; ``False``:
+    ``resize(box=)``), the resized picture, the window of it that is written,
+    a flip (``0..3``, ``"h"``, ``"v"``, ``"hv"`` or ``None``) and the byte
+    offset of the item's box in the output buffer.  ``statuses``, after the
+    submission: each item's own status (``0``, or ``7``: refused alone)."""
+
+    def __init__(self, filter: str, items, reducing_gap=None):
+        if filter not in FILTERS:
+            raise ValueError(f"filter must be one of {sorted(FILTERS)}, not {filter!r}")
+        self.filter, self.reducing_gap = filter, reducing_gap
+        self.items = tuple(items)
+        self._arr = (ResampleItemsItem * max(len(self.items), 1))()
+        self._status = (ctypes.c_int32 * max(len(self.items), 1))()
+        try:
+            for a, (image, box, clamp, (rw, rh), (ox, oy), (ow, oh), flip, offset) in zip(
+                    self._arr, self.items):
+                a.image, a.clamp = int(image), int(bool(clamp))
+                a.x0, a.y0, a.x1, a.y1 = (float(v) for v in (box or (0, 0, 0, 0)))
+                a.rw, a.rh, a.ox, a.oy, a.out_w, a.out_h = (int(v) for v in (rw, rh, ox, oy, ow, oh))
+                a.flip, a.offset = (flip if isinstance(flip, int) else _flip(flip)), int(offset)
+        except (TypeError, ValueError) as err:
+            raise ValueError("a resample item is (image, box | None, clamp, (rw, rh), (ox, oy), "
+                             f"(out_w, out_h), flip, offset): {err}") from None
+
+    @property
+    def statuses(self) -> list[int]:
+        return list(self._status)[:len(self.items)]
+
+    def _c(self) -> tuple:
+        return (FILTERS[self.filter], float(self.reducing_gap or 0.0), self._arr, len(self.items))
+
+
+def resample_items_check(infos, items: ResampleItems, elem_size: int, out_bytes: int,
+                         draft=None) -> list[int]:
+    """The items' own statuses against these probed images, as the submission
+    will resolve them (spdl_hj_resample_items_check; host only); ``ValueError``
+    for a request the submission refuses as a whole."""
+    n = len(infos)
+    inf = infos if isinstance(infos, ctypes.Array) else (ImageInfo * max(n, 1))(*infos)
+    lv = None if draft is None else (ctypes.c_uint8 * max(n, 1))(*draft)
+    st = (ctypes.c_int32 * max(len(items.items), 1))()
+    rc = lib().spdl_hj_resample_items_check(inf, n, lv, *items._c(), int(elem_size),
+                                            int(out_bytes), st)
+    if rc:
+        raise ValueError("the resample items do not make a submission: an image index outside "
+                         "the batch, a flip above 3, a non-integral clamped box, a box outside "
+                         f"its frame, or an item past the buffer (status {rc})")
+    return list(st)[:len(items.items)]
+
+
+def resample_layout(infos, requests, align: int = 256, *, filter: str = "bicubic",
+                    reducing_gap=None, elem_size: int = 1, draft=None):
+    """``(offsets, sizes, statuses, items)`` of an items submission (host only),
+    the sibling of :func:`ragged_layout`.  ``requests``: per item ``(image, box,
+    clamp, (rw, rh), window, flip)`` with ``window = (ox, oy, out_w, out_h)`` or
+    ``None`` for the whole resized picture.  Every item's ``out_h x out_w x 3``
+    box is packed in request order at a multiple of ``align`` bytes; ``offsets``
+    has one entry more than there are items, the last the buffer's size.
+    ``statuses``: each item's own (``7``: refused alone, its box stays unwritten).
+    ``items``: the :class:`ResampleItems` to submit.  ``ValueError`` for what the
+    submission refuses as a whole."""
+    if align < elem_size or align % elem_size:
+        raise ValueError(f"align is a multiple of the element size, not {align}")
+    offsets, sizes, items, end = [], [], [], 0
+    for image, box, clamp, (rw, rh), window, flip in requests:
+        ox, oy, ow, oh = window if window is not None else (0, 0, rw, rh)
+        offsets.append(-(-end // align) * align)
+        sizes.append((int(ow), int(oh)))
+        end = offsets[-1] + int(ow) * int(oh) * 3 * elem_size
+        items.append((image, box, clamp, (rw, rh), (ox, oy), (ow, oh), flip, offsets[-1]))
+    offsets.append(end)
+    held = ResampleItems(filter, items, reducing_gap)
+    return offsets, sizes, resample_items_check(infos, held, elem_size, end, draft), held
 
 
 def resample_axis(in_size: int, out_size: int, filter: str, box=None):
@@ -1119,7 +1214,7 @@ class Decoder:
     def decode_batch(self, datas, out: Output, out_ptr: int, out_bytes: int, stream=None,
                      sync: bool = True, check: bool = True, crops=None, views=None,
                      flips=None, orients=None, ragged=None, lowres=None,
-                     resample=None, draft=None) -> list[int]:
+                     resample=None, draft=None, resample_items=None) -> list[int]:
         """Per-image statuses.  A failed image raises RuntimeError unless
         ``check`` is False (synchronous calls), which returns the statuses.
         ``crops``: a source crop ``(x, y, w, h)`` or ``None`` per image.
@@ -1140,7 +1235,9 @@ class Decoder:
         ``csc="turbo"`` decode into one ``out_w x out_h`` box.  ``draft``: a
         draft level ``0..3`` per image (spdl_hj_set_draft, ``csc="turbo"``
         alone; :func:`draft_levels` resolves requests); a resample's items are
-        then in the draft frame's coordinates."""
+        then in the draft frame's coordinates.  ``resample_items``: a
+        :class:`ResampleItems` in place of ``resample`` -- several outputs per
+        image, each its own size at its own offset of ``out_ptr``."""
         n = len(datas)
         if n == 0:
             raise RuntimeError("Failed to decode an image. (the batch is empty)")
@@ -1164,10 +1261,11 @@ class Decoder:
             )
         return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
                                     check, status, call, orients, ragged, lowres, resample,
-                                    draft))
+                                    draft, resample_items))
 
     def _submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync, check, status,
-                call, orients=None, ragged=None, lowres=None, resample=None, draft=None):
+                call, orients=None, ragged=None, lowres=None, resample=None, draft=None,
+                resample_items=None):
         """What the three batch submissions share: the views, crops and flips
         (or orientations) go to the context, ``call(err)`` -- the method's own marshalling and
         its native call -- returns the library's code, and a failure raises
@@ -1176,6 +1274,18 @@ class Decoder:
         also run unbound, on objects that are no Decoder.)"""
         # (marshalled first: a malformed request raises before anything is on the context)
         rs = None if resample is None else _resample_c(resample)
+        if resample_items is not None:
+            # (what the items exclude is refused before anything is on the context)
+            if rs is not None or crops is not None or views is not None or ragged is not None:
+                raise ValueError("resample_items= takes no resample=, crops=, views= or ragged=")
+            if _has_flips(out, flips, views) or _has_orients(out, orients, views):
+                raise ValueError("resample_items= takes no flips= or orients=: an item has its own")
+            if lowres is not None and any(lowres):
+                raise ValueError("resample_items= takes no lowres=")
+            if out.csc != "turbo":
+                raise ValueError(f"resample_items= needs csc='turbo', not {out.csc!r}")
+            if not hasattr(lib(), "spdl_hj_set_resample_items"):
+                raise RuntimeError("this libspdl_hipjpeg build has no spdl_hj_set_resample_items")
         if views is not None:
             _check_views(views, out, crops, out_ptr, out_bytes)
             self.set_views(views)
@@ -1193,6 +1303,10 @@ class Decoder:
             Decoder._set_resample_c(self, rs)
         if draft is not None:  # (likewise)
             Decoder.set_draft(self, draft)
+        if resample_items is not None:
+            if lib().spdl_hj_set_resample_items(self._h, *resample_items._c(),
+                                                resample_items._status):
+                raise ValueError("invalid resample items")
         err = ctypes.create_string_buffer(1024)
         rc = call(err)
         if rc and not (not check and sync and (any(status) or _refused(views, rc))):
@@ -1203,7 +1317,8 @@ class Decoder:
                             out: Output, out_ptr: int, out_bytes: int, stream=None,
                             sync: bool = True, crops=None, check: bool = True,
                             views=None, flips=None, orients=None, ragged=None,
-                            lowres=None, resample=None, draft=None) -> list[int]:
+                            lowres=None, resample=None, draft=None,
+                            resample_items=None) -> list[int]:
         """``offsets``/``sizes``: sequences or int64 numpy arrays; ``infos``: a
         sequence of ImageInfo or a prebuilt ``(ImageInfo * n)`` array (pass the
         same objects again to skip re-marshalling on every call)."""
@@ -1224,7 +1339,7 @@ class Decoder:
             )
         return Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
                                check, status, call, orients, ragged, lowres, resample,
-                               draft).tolist()
+                               draft, resample_items).tolist()
 
     def _spec(self, out: Output) -> OutputSpec:
         cache = self.__dict__.setdefault("_spec_cache", {})
@@ -1284,7 +1399,8 @@ class Decoder:
     def decode_staged(self, ticket: int, nbytes: int, offsets, sizes, out: Output, out_ptr: int,
                       out_bytes: int, stream=None, sync: bool = True, crops=None,
                       check: bool = True, views=None, flips=None, orients=None,
-                      ragged=None, lowres=None, resample=None, draft=None) -> list[int]:
+                      ragged=None, lowres=None, resample=None, draft=None,
+                      resample_items=None) -> list[int]:
         n = len(offsets)
         status = (ctypes.c_int32 * max(n, 1))()
 
@@ -1297,7 +1413,7 @@ class Decoder:
                 out_bytes, _stream_handle(stream), int(bool(sync)), status, err, 1024)
         return list(Decoder._submit(self, n, out, out_ptr, out_bytes, crops, views, flips, sync,
                                     check, status, call, orients, ragged, lowres, resample,
-                                    draft))[:n]
+                                    draft, resample_items))[:n]
 
     def debug_entropy(self, data, nblocks: int):
         """Coefficients / destuffed bytes / diagnostics of one image (tests)."""

@@ -352,6 +352,23 @@ inline HJ_HD int reduce_lds_words(const ResampleDesc& d) {
   return lds_layout(d).words + d.sr * d.pitch;
 }
 
+// ---- Resample items (spdl_hj_set_resample_items): what resample_items_kernel
+// knows of one item -- int32 alone, behind the draft records.  The output box
+// ow x oh, its place and its tiles are the item's, not its image's descriptor's.
+// rd / rr as the two kernels above read them, with one difference: an item
+// clamped to an integer box of a submission with factors has the box's origin
+// in rr.qx / rr.qy (the cells count from there) and rd.bx = rd.by = 0.
+struct ItemDesc {
+  ResampleDesc rd;
+  ReduceDesc rr;             // (a submission without factors: unused)
+  int32_t image;             // whose planes it reads
+  int32_t ow, oh;            // the written window
+  int32_t flip;              // SPDL_HJ_FLIP_* of the written window
+  int32_t wg0, chunks;       // its first workgroup in the grid, tiles per band
+  uint32_t off_lo, off_hi;   // its first element in the output
+};
+constexpr uint32_t kItemNone = 0xFFFFFFFFu;  // a map entry of the status workgroups
+
 }  // namespace rs
 
 // ---- Pillow-exact draft (spdl_hj_set_draft; libjpeg-turbo's scale_num / 8) ----

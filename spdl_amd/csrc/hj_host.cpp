@@ -302,6 +302,8 @@ struct spdl_hj_ctx {
   int64_t turbo_workgroups = 0;  // turbo_rgb_kernel's in the last submission (csc = TURBO)
   int64_t resample_workgroups = 0;  // resample_kernel's (spdl_hj_set_resample)
   int64_t reduce_images = 0;  // images with a reduce factor above 1 (spdl_hj_set_resample_box)
+  // spdl_hj_set_resample_items: the items placed and resample_items_kernel's workgroups
+  int64_t resample_items = 0, resample_item_workgroups = 0;
   // spdl_hj_set_resample: the next batch submission's filter, box and items
   // (has_items: one per image; else every whole frame), and the axes it made
   struct HeldResample {
@@ -312,6 +314,11 @@ struct spdl_hj_ctx {
     bool by_box = false;
     double gap = 0;
     std::vector<spdl_hj_resample_box_item> box_items;
+    // spdl_hj_set_resample_items: the item list in their place, and where the
+    // items' own statuses go (the caller's array, or null)
+    bool by_items = false;
+    std::vector<spdl_hj_resample_items_item> list;
+    int32_t* item_status = nullptr;
   } resample;
   rs::AxisCache axes;
   // spdl_hj_set_views: the views of the next batch submission
@@ -488,7 +495,8 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
   HJ_HIP(grow(W.desc,
               sizeof(ImageDesc) * b->ndesc + sizeof(uint32_t) * b->nwork + L.flips.size() +
                   L.lowres.size() + L.resample.size() * sizeof(rs::ResampleDesc) +
-                  L.draft.size() * sizeof(draft::Desc) + L.reduce.size() * sizeof(rs::ReduceDesc),
+                  L.draft.size() * sizeof(draft::Desc) + L.reduce.size() * sizeof(rs::ReduceDesc) +
+                  L.items.size() * sizeof(rs::ItemDesc) + L.item_map.size() * sizeof(uint32_t),
               st, &b->desc));
   b->work = reinterpret_cast<uint32_t*>(b->desc + b->ndesc);
   b->flips = L.flips.empty() ? nullptr : reinterpret_cast<const uint8_t*>(b->work + b->nwork);
@@ -516,6 +524,15 @@ int workspace_buffers(Workspace& W, const Layout& L, int n, const uint8_t* d_byt
                         reinterpret_cast<const uint8_t*>(b->work + b->nwork) +
                         L.resample.size() * sizeof(rs::ResampleDesc) +
                         L.draft.size() * sizeof(draft::Desc));
+  // (... and an items submission's records and map behind the draft records:
+  // it has neither per-image records nor reduce records)
+  b->items = nullptr;
+  b->item_map = nullptr;
+  if (L.by_items) {
+    b->items = reinterpret_cast<const rs::ItemDesc*>(
+        reinterpret_cast<const uint8_t*>(b->work + b->nwork) + L.draft.size() * sizeof(draft::Desc));
+    b->item_map = reinterpret_cast<const uint32_t*>(b->items + L.items.size());
+  }
   HJ_HIP(grow(W.chain, (size_t)(kChainHead + L.chain_granules) * 8 + 64, st, &b->chain));
   HJ_HIP(grow(W.maps, (size_t)(L.ds_wgs + L.idct_wgs + L.hs_wgs + L.sws_wgs) * 4 + 64, st,
               &b->ds_map));
@@ -620,8 +637,10 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   const size_t rs_bytes = L.resample.size() * sizeof(rs::ResampleDesc);
   const size_t draft_bytes = L.draft.size() * sizeof(draft::Desc);
   const size_t reduce_bytes = L.reduce.size() * sizeof(rs::ReduceDesc);
-  const size_t desc_bytes =
-      work_end + L.flips.size() + L.lowres.size() + rs_bytes + draft_bytes + reduce_bytes;
+  const size_t items_bytes = L.items.size() * sizeof(rs::ItemDesc);
+  const size_t map_bytes = L.item_map.size() * sizeof(uint32_t);
+  const size_t desc_bytes = work_end + L.flips.size() + L.lowres.size() + rs_bytes + draft_bytes +
+                            reduce_bytes + items_bytes + map_bytes;
   HJ_HIP(slot.pin_desc.ensure(desc_bytes));
   HJ_HIP(slot.pin_status.ensure(sizeof(int32_t) * n));
   slot.n = n;
@@ -650,17 +669,26 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   if (B.reduce)  // (a resampled submission's: checked with it above)
     memcpy(static_cast<uint8_t*>(slot.pin_desc.p) + work_end + rs_bytes + draft_bytes,
            L.reduce.data(), reduce_bytes);
+  if (B.items) {
+    if (!L.flips.empty() || !L.lowres.empty() || rs_bytes || reduce_bytes) {  // (the planner's)
+      set_err(err, errlen, "an items submission with flips, levels or per-image records");
+      return SPDL_HJ_ERR_INVALID_ARG;
+    }
+    uint8_t* at = static_cast<uint8_t*>(slot.pin_desc.p) + work_end + draft_bytes;
+    memcpy(at, L.items.data(), items_bytes);
+    memcpy(at + items_bytes, L.item_map.data(), map_bytes);
+  }
   // the batch's swscale tables travel with the descriptors (a resampled
   // submission's axis tables likewise)
   const bool swscale = !sub.planes_only && out->csc == SPDL_HJ_CSC_SWSCALE;
-  const size_t tb = swscale || B.resample ? L.tables.size() * 4 : 0;
+  const size_t tb = swscale || B.resample || B.items ? L.tables.size() * 4 : 0;
   HJ_HIP(slot.pin_tables.ensure(tb + 16));
   if (tb) memcpy(slot.pin_tables.p, L.tables.data(), tb);
   const bool hs = ctx->host_staging != 0;  // parse_kernel pulls them from the pinned pages
   if (!hs) {
     HJ_HIP(hipMemcpyAsync(B.desc, slot.pin_desc.p, desc_bytes, hipMemcpyHostToDevice, st));
     if (tb) HJ_HIP(hipMemcpyAsync(B.wts, slot.pin_tables.p, tb, hipMemcpyHostToDevice, st));
-  } else if (B.flips || B.lowres || B.resample || B.draft) {
+  } else if (B.flips || B.lowres || B.resample || B.draft || B.items) {
     // (parse_kernel brings over the descriptors and the work list alone: the
     // flags and levels behind them take one small copy from the same pinned pages)
     HJ_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t*>(B.work + B.nwork),
@@ -728,6 +756,7 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   const int ragged_fused = L.ragged ? (int)L.fused_wgs : 0;
   ctx->idct_workgroups = ctx->fused_workgroups = ctx->generic_workgroups = 0;
   ctx->turbo_workgroups = ctx->resample_workgroups = 0;
+  ctx->resample_items = ctx->resample_item_workgroups = 0;
   ctx->entropy_workgroups = B.nwork;
   ctx->lowres_images = L.lowres_images;
   ctx->draft_images = L.draft_images;
@@ -762,7 +791,14 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
   mark(ctx, slot, 6, st);
   if (!sub.planes_only && !(abl & kAblNoOutput)) {
     const int sws_wgs = (int)L.sws_wgs, hs_wgs = (int)L.hs_wgs;
-    if (turbo && B.resample) {
+    if (turbo && B.items) {
+      // resample_items_kernel over the items' tiles and the status workgroups
+      // behind them (never empty: ceil(n / 256) of the latter)
+      const int wgs = (int)L.item_map.size();
+      HJ_HIP(launch_resample_items(B, sub.out_dev, bp, wgs, L.items_sum, L.resample_lds, hstat, st));
+      ctx->resample_items = (int64_t)L.items.size();
+      ctx->resample_item_workgroups = wgs;
+    } else if (turbo && B.resample) {
       // resample_kernel over every image's own tiles, as turbo_rgb_kernel's below
       if (sws_wgs > 0 && B.reduce)
         HJ_HIP(launch_resample_reduce(B, sub.out_dev, bp, sws_wgs, L.resample_lds, hstat, st));
@@ -1100,6 +1136,17 @@ struct Held {
         resample_rq.place_box = &rs::place_box_into;
         resample_rq.probe_box = &rs::probe_box;
       }
+      if (resamplev.by_items) {
+        resample_rq.items = nullptr;
+        resample_rq.place = nullptr;
+        resample_rq.n = 0;
+        resample_rq.gap = resamplev.gap;
+        resample_rq.list = resamplev.list.data();
+        resample_rq.n_items = (int64_t)resamplev.list.size();
+        resample_rq.item_status = resamplev.item_status;
+        resample_rq.place_item = &rs::place_item_into;
+        resample_rq.probe_item = &rs::probe_item;
+      }
       resample = &resample_rq;
     }
     crc = take_crops(ctx, n, out, &rects, &crops, err, errlen);
@@ -1184,8 +1231,11 @@ int submit(spdl_hj_ctx* ctx, const Held& held, const Batch& b, SlotRelease& slot
     }
   }
   Layout L;
-  // (views: one entropy workgroup per image, so no hand-off can give up)
-  int rc = plan_batch({b.offsets, b.sizes, infos, b.n, b.out, held.hv ? 0 : ctx->piece_bytes,
+  // (views and items: one entropy workgroup per image, so no hand-off can give
+  // up -- a re-decode would have to write several outputs again)
+  const bool by_items = held.resample && held.resample->place_item;
+  int rc = plan_batch({b.offsets, b.sizes, infos, b.n, b.out,
+                       held.hv || by_items ? 0 : ctx->piece_bytes,
                        &ctx->plans, held.crops, held.hv, held.flips, held.nflips, held.orients,
                        held.norients, held.ragged, (int64_t)b.out_bytes, ctx->output_path,
                        held.lowres, held.nlowres, held.resample, held.draft, held.ndraft},
@@ -1370,6 +1420,35 @@ int spdl_hj_set_resample_box(spdl_hj_ctx* ctx, int32_t filter, int32_t out_w, in
   ctx->resample.has_items = items != nullptr;
   if (items) ctx->resample.box_items.assign(items, items + n);
   return SPDL_HJ_OK;
+}
+
+int spdl_hj_set_resample_items(spdl_hj_ctx* ctx, int32_t filter, double reducing_gap,
+                               const spdl_hj_resample_items_item* items, int64_t n_items,
+                               int32_t* status) {
+  if (!ctx || n_items < 0 || (n_items > 0 && !items)) return SPDL_HJ_ERR_INVALID_ARG;
+  // (as spdl_hj_set_resample: what the submission cannot take is refused
+  // there, with nothing written)
+  ctx->resample = {};
+  ctx->resample.set = ctx->resample.by_items = true;
+  ctx->resample.filter = filter;
+  ctx->resample.gap = reducing_gap;
+  if (n_items) ctx->resample.list.assign(items, items + n_items);
+  ctx->resample.item_status = status;
+  return SPDL_HJ_OK;
+}
+
+int spdl_hj_resample_items_check(const spdl_hj_image_info* infos, int32_t n, const uint8_t* draft,
+                                 int32_t filter, double reducing_gap,
+                                 const spdl_hj_resample_items_item* items, int64_t n_items,
+                                 int32_t elem_size, int64_t out_bytes, int32_t* status) {
+  rs::AxisCache cache;
+  ResampleRequest r{filter, 0, 0, nullptr, 0, &cache, nullptr};
+  r.gap = reducing_gap;
+  r.list = items;
+  r.n_items = n_items;
+  r.place_item = &rs::place_item_into;
+  r.probe_item = &rs::probe_item;
+  return resample_items_check(infos, n, draft, r, elem_size, out_bytes, status);
 }
 
 int spdl_hj_debug_reduce_plan(int32_t W, int32_t H, const spdl_hj_resample_box_item* item,
@@ -2048,6 +2127,8 @@ int spdl_hj_get_param(spdl_hj_ctx* ctx, const char* name, int64_t* value) {
       {"generic_workgroups", ctx->generic_workgroups},
       {"turbo_workgroups", ctx->turbo_workgroups},
       {"resample_workgroups", ctx->resample_workgroups},
+      {"resample_items", ctx->resample_items},
+      {"resample_item_workgroups", ctx->resample_item_workgroups},
       {"entropy_workgroups", ctx->entropy_workgroups},
   };
   for (const auto& t : tab)

@@ -7395,6 +7395,303 @@ __global__ void __launch_bounds__(256) resample_reduce_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// resample_items_kernel: the Pillow-exact resize addressed by ITEM
+// (spdl_hipjpeg.h "resample items").  A workgroup is one tile of one item: it
+// finds its item through item_map, and everything the two kernels above take
+// from their image's descriptor -- the output box, its place, its tiles, its
+// ResampleDesc / ReduceDesc -- comes from the item's record; the image only
+// lends its planes and its status.  So any number of items read one image's
+// planes, each with a size, a box and tables of its own, and the image is
+// decoded once.  The grid is in image order: the tiles of one image's items
+// are neighbours and find its planes in L2.
+//
+// SUM = false is resample_kernel's data path (producer -> strip), SUM = true
+// resample_reduce_kernel's (producer -> 16-bit cell sums -> strip); a
+// submission without a reduce factor launches the former, so an item without
+// one pays for no sum stage.  The stages are the __device__ functions below,
+// shared by the four instantiations; the arithmetic is the two kernels'.
+//
+// The store mirrors for the item's flip.  The vertical pass of a mirrored item
+// reads its 8 columns of the intermediate in reverse (an LDS address, no
+// register shuffle), so a thread's row group x .. x + n - 1 comes out in the
+// order it is written in at columns ow - x - n ..; bit 1 sends row y to
+// oh - 1 - y.  turbo_store_row takes any alignment: a whole group leaves as
+// realigned dwords behind at most three head bytes, the ragged group of a row
+// (now its first) as bytes -- the widths an unflipped row of odd pitch has.
+//
+// The workgroups behind the tiles (map entry rs::kItemNone) write the images'
+// statuses to the host's array, 256 images each: an image may have no item.
+// ---------------------------------------------------------------------------
+
+// The tile's coefficient rows into LDS: output columns hcol0 .. of the
+// horizontal axis (xmin made relative to the strip: + hrel), rows vrow0 .. of
+// the vertical one (relative to the intermediate: + vrel)
+__device__ __forceinline__ void rs_stage_rows(int32_t* lds, const rs::LdsLayout& l,
+                                              const int32_t* __restrict__ tables,
+                                              const rs::ResampleDesc& rd, int hcol0, int vrow0,
+                                              int ncol, int nrow, int hrel, int vrel, int tid) {
+  for (int i = tid; i < ncol; i += 256) {
+    lds[l.hx + i] = tables[rd.hx + hcol0 + i] + hrel;
+    lds[l.hn + i] = tables[rd.hn + hcol0 + i];
+  }
+  for (int i = tid; i < ncol * rd.kh; i += 256)
+    lds[l.hk + i] = tables[rd.hk + (int64_t)hcol0 * rd.kh + i];
+  for (int i = tid; i < nrow; i += 256) {
+    lds[l.vx + i] = tables[rd.vx + vrow0 + i] + vrel;
+    lds[l.vn + i] = tables[rd.vn + vrow0 + i];
+  }
+  for (int i = tid; i < nrow * rd.kv; i += 256)
+    lds[l.vk + i] = tables[rd.vk + (int64_t)vrow0 * rd.kv + i];
+}
+
+// The horizontal pass over a strip of srows rows into rows row0 .. of the
+// intermediate: lanes along the strip's rows (resample_kernel's step 2)
+__device__ __forceinline__ void rs_hpass(const int32_t* lds, const rs::LdsLayout& l,
+                                         const rs::ResampleDesc& rd, const uint32_t* strip,
+                                         uint32_t* inter, int ncol, int srows, int row0, int tid) {
+  const int sr_shift = __builtin_ctz((unsigned)rd.sr);
+  for (int i = tid; i < (ncol << sr_shift); i += 256) {
+    const int row = i & (rd.sr - 1), col = i >> sr_shift;
+    if (row >= srows) continue;
+    const int n = lds[l.hn + col];
+    const uint32_t* px = strip + row * rd.pitch + lds[l.hx + col];
+    const int32_t* kk = lds + l.hk + col * rd.kh;
+    uint32_t a0 = 1u << (rs::kCoefBits - 1), a1 = a0, a2 = a0;
+    for (int k = 0; k < n; k++) {
+      const uint32_t w = (uint32_t)kk[k], q = px[k];
+      a0 += w * (q & 255u);
+      a1 += w * ((q >> 8) & 255u);
+      a2 += w * (q >> 16);
+    }
+    inter[(row0 + row) * rd.tw + col] = rs_clip8(a0) | rs_clip8(a1) << 8 | rs_clip8(a2) << 16;
+  }
+}
+
+// One thread's 8 columns of one output row from the intermediate.  MIRROR:
+// column j of the result is column npx - 1 - j of the group
+template <bool MIRROR>
+__device__ __forceinline__ void rs_vtaps(const uint32_t* px, const int32_t* kk, int n, int tw,
+                                         int npx, uint32_t (&a)[3][8]) {
+  int cj[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    cj[j] = MIRROR ? max(npx - 1 - j, 0) : j;
+    a[0][j] = a[1][j] = a[2][j] = 1u << (rs::kCoefBits - 1);
+  }
+  for (int k = 0; k < n; k++) {
+    const uint32_t w = (uint32_t)kk[k];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const uint32_t q = px[k * tw + cj[j]];
+      a[0][j] += w * (q & 255u);
+      a[1][j] += w * ((q >> 8) & 255u);
+      a[2][j] += w * (q >> 16);
+    }
+  }
+}
+
+// The vertical pass of tile (tx, ty) of item `it`, the channel order, the
+// flip and the store (resample_kernel's step 3, by item)
+__device__ __forceinline__ void rs_vpass_store(const int32_t* lds, const rs::LdsLayout& l,
+                                               const rs::ItemDesc& it, const uint32_t* inter,
+                                               int ncol, int nrow, int tx, int ty, void* out,
+                                               const BatchParams& p, int tid) {
+  const rs::ResampleDesc& rd = it.rd;
+  const bool swap = p.pix_fmt == 1 || p.pix_fmt == 3;
+  const int64_t base = (int64_t)((uint64_t)it.off_hi << 32 | it.off_lo);
+  const int groups = (ncol + 7) >> 3;
+  for (int i = tid; i < groups * nrow; i += 256) {
+    const int y = i / groups, g = i - y * groups;
+    const int x = tx * rd.tw + 8 * g, npx = min(8, it.ow - x);
+    const uint32_t* px = inter + lds[l.vx + y] * rd.tw + 8 * g;
+    const int32_t* kk = lds + l.vk + y * rd.kv;
+    uint32_t a[3][8];
+    if (it.flip & 1) rs_vtaps<true>(px, kk, lds[l.vn + y], rd.tw, npx, a);
+    else rs_vtaps<false>(px, kk, lds[l.vn + y], rd.tw, npx, a);
+    int c0v[8], c1v[8], c2v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const int r = (int)rs_clip8(a[0][j]), b = (int)rs_clip8(a[2][j]);
+      c0v[j] = swap ? b : r;
+      c1v[j] = (int)rs_clip8(a[1][j]);
+      c2v[j] = swap ? r : b;
+    }
+    const int yy = ty * rd.th + y;
+    turbo_store_row(out, base, p, it.ow, it.oh, it.flip & 1 ? it.ow - x - npx : x,
+                    it.flip & 2 ? it.oh - 1 - yy : yy, npx, c0v, c1v, c2v);
+  }
+}
+
+template <bool DRAFT>
+__device__ __forceinline__ void rs_samples(const uint8_t* __restrict__ planes, const ImageDesc& dd,
+                                           const draft::Desc* __restrict__ drafts, int img, int x0,
+                                           int y0, int (&v)[3][2][8]) {
+  if constexpr (DRAFT) turbo_samples_draft(planes, dd, drafts[img], x0, y0, v);
+  else turbo_samples(planes, dd, x0, y0, v);
+}
+
+// Strips of frame rows [r0, r1) from column c0 on, units_x 8-column units wide,
+// each through the horizontal pass (resample_kernel's step 2)
+template <bool DRAFT>
+__device__ __forceinline__ void rs_strips_plain(const uint8_t* __restrict__ planes,
+                                                const ImageDesc& dd,
+                                                const draft::Desc* __restrict__ drafts, int img,
+                                                const int32_t* lds, const rs::LdsLayout& l,
+                                                const rs::ResampleDesc& rd, uint32_t* strip,
+                                                uint32_t* inter, int c0, int units_x, int r0, int r1,
+                                                int ncol, int tid) {
+  for (int s0 = r0; s0 < r1; s0 += rd.sr) {
+    const int srows = min(rd.sr, r1 - s0);
+    __syncthreads();  // (the coefficient rows stand; the last strip is consumed)
+    const int units = units_x * ((srows + 1) >> 1);
+    for (int u = tid; u < units; u += 256) {
+      const int uy = u / units_x, ux = u - uy * units_x;
+      int v[3][2][8];
+      rs_samples<DRAFT>(planes, dd, drafts, img, c0 + 8 * ux, s0 + 2 * uy, v);
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        uint32_t* q = strip + (2 * uy + j) * rd.pitch + 8 * ux;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          int rgb[3];
+          turbo_pixel(dd, v[0][j][k], v[1][j][k], v[2][j][k], rgb);
+          q[k] = (uint32_t)rgb[0] | (uint32_t)rgb[1] << 8 | (uint32_t)rgb[2] << 16;
+        }
+      }
+    }
+    __syncthreads();
+    rs_hpass(lds, l, rd, strip, inter, ncol, srows, s0 - r0, tid);
+  }
+}
+
+// Strips of cell rows [r0, r1), cells c0 .. c0 + ncell - 1: the cell sums, their
+// division into the strip, the horizontal pass (resample_reduce_kernel's steps
+// a to d)
+template <bool DRAFT>
+__device__ __forceinline__ void rs_strips_sum(const uint8_t* __restrict__ planes,
+                                              const ImageDesc& dd,
+                                              const draft::Desc* __restrict__ drafts, int img,
+                                              const int32_t* lds, const rs::LdsLayout& l,
+                                              const rs::ResampleDesc& rd, const rs::ReduceDesc& rr,
+                                              uint32_t* strip, uint32_t* sumb, uint32_t* inter,
+                                              int c0, int ncell, int r0, int r1, int ncol, int tid) {
+  const int X0 = rr.qx + c0 * rr.fx, X1 = min(rr.qx + (c0 + ncell) * rr.fx, rr.qx + rr.qw);
+  const int ux0 = X0 >> 3, units_x = ((X1 + 7) >> 3) - ux0;
+  for (int s0 = r0; s0 < r1; s0 += rd.sr) {
+    const int srows = min(rd.sr, r1 - s0);
+    const int Y0 = rr.qy + s0 * rr.fy, Y1 = min(rr.qy + (s0 + srows) * rr.fy, rr.qy + rr.qh);
+    const int uy0 = Y0 >> 1, units = units_x * (((Y1 + 1) >> 1) - uy0);
+    __syncthreads();  // (the coefficient rows stand; the last strip is consumed)
+    for (int i = tid; i < srows * rd.pitch; i += 256) strip[i] = sumb[i] = 0;
+    __syncthreads();
+    for (int u = tid; u < units; u += 256) {
+      const int uy = u / units_x, ux = u - uy * units_x;
+      const int x0 = (ux0 + ux) * 8, y0 = (uy0 + uy) * 2;
+      int v[3][2][8];
+      rs_samples<DRAFT>(planes, dd, drafts, img, x0, y0, v);
+      uint32_t rg[2][8], bb[2][8];
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          int rgb[3];
+          turbo_pixel(dd, v[0][j][k], v[1][j][k], v[2][j][k], rgb);
+          rg[j][k] = (uint32_t)rgb[0] | (uint32_t)rgb[1] << 16;
+          bb[j][k] = (uint32_t)rgb[2];
+        }
+      }
+      // the unit's columns and rows inside the source rectangle, and their cells
+      const int klo = max(X0 - x0, 0), khi = min(X1 - x0, 8);
+      const int cx = (x0 + klo - rr.qx) / rr.fx, rem = (x0 + klo - rr.qx) - cx * rr.fx;
+      const bool ok0 = y0 >= Y0, ok1 = y0 + 1 < Y1;  // (y0 < Y1 and y0 + 1 >= Y0 by the units)
+      const int cy0 = (y0 - rr.qy) / rr.fy - s0, cy1 = (y0 + 1 - rr.qy) / rr.fy - s0;
+      if (ok0 && ok1 && cy0 == cy1) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          rg[0][k] += rg[1][k];
+          bb[0][k] += bb[1][k];
+        }
+        reduce_add_row(strip + cy0 * rd.pitch, sumb + cy0 * rd.pitch, rg[0], bb[0], klo, khi,
+                       cx - c0, rem, rr.fx);
+      } else {
+        if (ok0)
+          reduce_add_row(strip + cy0 * rd.pitch, sumb + cy0 * rd.pitch, rg[0], bb[0], klo, khi,
+                         cx - c0, rem, rr.fx);
+        if (ok1)
+          reduce_add_row(strip + cy1 * rd.pitch, sumb + cy1 * rd.pitch, rg[1], bb[1], klo, khi,
+                         cx - c0, rem, rr.fx);
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < srows * ncell; i += 256) {
+      const int row = i / ncell, col = i - row * ncell;
+      const bool right = c0 + col == rr.cw - 1, bottom = s0 + row == rr.ch - 1;
+      const uint32_t amend = bottom ? (right ? rr.amend[3] : rr.amend[2])
+                                    : (right ? rr.amend[1] : rr.amend[0]);
+      const uint32_t mult = bottom ? (right ? rr.mult[3] : rr.mult[2])
+                                   : (right ? rr.mult[1] : rr.mult[0]);
+      const uint32_t q = strip[row * rd.pitch + col], b = sumb[row * rd.pitch + col];
+      strip[row * rd.pitch + col] = (((q & 0xffffu) + amend) * mult) >> 24 |
+                                    ((((q >> 16) + amend) * mult) >> 24) << 8 |
+                                    (((b + amend) * mult) >> 24) << 16;
+    }
+    __syncthreads();
+    rs_hpass(lds, l, rd, strip, inter, ncol, srows, s0 - r0, tid);
+  }
+}
+
+template <bool DRAFT, bool SUM>
+__global__ void __launch_bounds__(256) resample_items_kernel(
+    const uint8_t* __restrict__ planes, const ImageDesc* __restrict__ desc,
+    const ImageInfo* __restrict__ infos, const rs::ItemDesc* __restrict__ items,
+    const uint32_t* __restrict__ item_map, const int32_t* __restrict__ tables,
+    void* __restrict__ out, const BatchParams p, int32_t* __restrict__ host_status,
+    const draft::Desc* __restrict__ drafts, int tiles) {
+  extern __shared__ uint32_t rs_lds[];
+  const int tid = threadIdx.x;
+  const uint32_t k = item_map[blockIdx.x];
+  if (k == rs::kItemNone) {  // (behind the tiles: the images' statuses, once per image)
+    const int i = ((int)blockIdx.x - tiles) * 256 + tid;
+    if (host_status && i >= 0 && i < p.n) host_status[i] = infos[i].status;
+    return;
+  }
+  const rs::ItemDesc& it = items[k];
+  const int img = it.image;
+  if (infos[img].status != kOk) return;  // (a failed image's items stay untouched)
+  const ImageDesc& dd = desc[img];
+  const rs::ResampleDesc rd = it.rd;
+  const rs::LdsLayout l = rs::lds_layout(rd);
+  const int t = (int)blockIdx.x - it.wg0;
+  const int ty = t / it.chunks, tx = t - ty * it.chunks;
+  const int ncol = min(rd.tw, it.ow - tx * rd.tw), nrow = min(rd.th, it.oh - ty * rd.th);
+  const int hcol0 = rd.ox + tx * rd.tw, vrow0 = rd.oy + ty * rd.th;
+  int32_t* const lds = reinterpret_cast<int32_t*>(rs_lds);
+  uint32_t* const strip = rs_lds + l.strip;
+  uint32_t* const inter = rs_lds + l.inter;
+  if constexpr (SUM) {
+    // the windows in cells of the item's reduced picture (no alignment)
+    const rs::Window wc =
+        rs::tile_window(tables + rd.hx, tables + rd.hn, 0, rd.ox, it.ow, rd.tw, tx, 1);
+    const rs::Window wr =
+        rs::tile_window(tables + rd.vx, tables + rd.vn, 0, rd.oy, it.oh, rd.th, ty, 1);
+    rs_stage_rows(lds, l, tables, rd, hcol0, vrow0, ncol, nrow, -wc.lo, -wr.lo, tid);
+    rs_strips_sum<DRAFT>(planes, dd, drafts, img, lds, l, rd, it.rr, strip, rs_lds + l.words, inter,
+                         wc.lo, wc.hi - wc.lo, wr.lo, wr.hi, ncol, tid);
+  } else {
+    // the windows in the frame, from the box's origin, on the producer's units
+    const rs::Window wc =
+        rs::tile_window(tables + rd.hx, tables + rd.hn, rd.bx, rd.ox, it.ow, rd.tw, tx, 8);
+    const rs::Window wr =
+        rs::tile_window(tables + rd.vx, tables + rd.vn, rd.by, rd.oy, it.oh, rd.th, ty, 2);
+    rs_stage_rows(lds, l, tables, rd, hcol0, vrow0, ncol, nrow, rd.bx - wc.lo, rd.by - wr.lo, tid);
+    rs_strips_plain<DRAFT>(planes, dd, drafts, img, lds, l, rd, strip, inter, wc.lo,
+                           (wc.hi - wc.lo + 7) >> 3, wr.lo, wr.hi, ncol, tid);
+  }
+  __syncthreads();
+  rs_vpass_store(lds, l, it, inter, ncol, nrow, tx, ty, out, p, tid);
+}
+
+// ---------------------------------------------------------------------------
 // launchers (host side, same TU; declared in hj_launch.h)
 // ---------------------------------------------------------------------------
 
@@ -7549,6 +7846,20 @@ hipError_t launch_resample_reduce(const BatchBuffers& b, void* out, const BatchP
     hipLaunchKernelGGL(resample_reduce_kernel<false>, dim3(wgs), dim3(256), lds_bytes, st, b.planes,
                        b.desc, b.infos, b.resample, b.reduce, b.wts, out, p, host_status, b.sws_map,
                        b.draft);
+  return hipGetLastError();
+}
+hipError_t launch_resample_items(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
+                                 bool sum, int lds_bytes, int32_t* host_status, hipStream_t st) {
+  const int tiles = wgs - (b.n + 255) / 256;
+#define HJ_ITEMS(D, S)                                                                           \
+  hipLaunchKernelGGL((resample_items_kernel<D, S>), dim3(wgs), dim3(256), lds_bytes, st, b.planes, \
+                     b.desc, b.infos, b.items, b.item_map, b.wts, out, p, host_status, b.draft,  \
+                     tiles)
+  if (b.draft && sum) HJ_ITEMS(true, true);
+  else if (b.draft) HJ_ITEMS(true, false);
+  else if (sum) HJ_ITEMS(false, true);
+  else HJ_ITEMS(false, false);
+#undef HJ_ITEMS
   return hipGetLastError();
 }
 hipError_t launch_sws(const BatchBuffers& b, void* out, const BatchParams& p, bool flat,

@@ -52,6 +52,11 @@ struct BatchBuffers {
   // Image.reduce records (spdl_hj_set_resample_box with a gap): one per image
   // behind the draft records; null when no image has a factor above 1
   const rs::ReduceDesc* reduce;
+  // an items submission (spdl_hj_set_resample_items): the placed items' records
+  // behind the draft records, and behind them the map from workgroup to item;
+  // null otherwise
+  const rs::ItemDesc* items;
+  const uint32_t* item_map;
 };
 
 // parse_kernel + lut_kernel.  host_desc (descriptors, then the work list) and
@@ -92,6 +97,11 @@ hipError_t launch_resample(const BatchBuffers& b, void* out, const BatchParams& 
 // lds_bytes by rs::reduce_lds_words()
 hipError_t launch_resample_reduce(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
                                   int lds_bytes, int32_t* host_status, hipStream_t st);
+// resample_items_kernel (spdl_hj_set_resample_items) over b.item_map: `wgs` workgroups, the
+// last ceil(n / 256) of them the status workgroups; sum: the submission has a reduce factor
+// (Layout::items_sum: rs::tile_reduce()'s tiles and LDS)
+hipError_t launch_resample_items(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
+                                 bool sum, int lds_bytes, int32_t* host_status, hipStream_t st);
 hipError_t launch_rgb_unscaled(const BatchBuffers& b, void* out, const BatchParams& p,
                                int64_t max_px, int32_t* host_status, hipStream_t st);
 hipError_t launch_idct_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int idct,

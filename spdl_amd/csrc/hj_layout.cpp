@@ -187,10 +187,83 @@ bool refused_alone(bool view, const Placement& pl) {
          (view && pl.rc == SPDL_HJ_ERR_BAD_GEOMETRY && (pl.at == kAtGeometry || pl.at == kAtFilter));
 }
 
+}  // namespace
+
+// The items of an items request against the batch's frames (fw[i] x fh[i]: image
+// i's, its draft frame with a level): held against the request's limits, then
+// resolved, tiled and placed in grid order -- one image's items adjacent, so
+// that the workgroups reading the same planes meet in one L2 -- with the map
+// from workgroup to item behind them.  Null and status[k] item k's own status
+// (0, or why it is refused alone and has no record); else why the submission
+// is refused.  The planner's and resample_items_check's.
+const char* place_items(const ResampleRequest& r, const std::vector<int>& fw,
+                        const std::vector<int>& fh, int64_t esz, int64_t out_bytes, Layout& L,
+                        ResamplePool& pool, std::vector<int32_t>& status) {
+  const int n = (int)fw.size();
+  if (r.n_items < 0 || (r.n_items > 0 && !r.list)) return "spdl_hj_set_resample_items: no items";
+  if (r.filter < 0 || r.filter > SPDL_HJ_FILTER_LANCZOS)
+    return "spdl_hj_set_resample_items: unknown filter";
+  if (!(r.gap == 0.0 || r.gap >= 1.0))
+    return "spdl_hj_set_resample_items: reducing_gap is 0 or at least 1";
+  status.assign((size_t)r.n_items, SPDL_HJ_OK);
+  bool sum = false;
+  for (int64_t k = 0; k < r.n_items; k++) {
+    const spdl_hj_resample_items_item& it = r.list[k];
+    if (it.image < 0 || it.image >= n)
+      return "spdl_hj_set_resample_items: an item's image index lies outside the batch";
+    int any = 0;
+    status[k] = r.probe_item(r.filter, r.gap, &it, fw[it.image], fh[it.image], &any);
+    if (status[k] == SPDL_HJ_ERR_INVALID_ARG)
+      return "spdl_hj_set_resample_items: an item's flip, box or output size is invalid";
+    sum = sum || any;
+    const int64_t extent = (int64_t)it.out_w * it.out_h * 3 * esz;
+    if (it.offset < 0 || it.offset % esz || it.offset > out_bytes || extent > out_bytes - it.offset)
+      return "spdl_hj_set_resample_items: an item reaches past the output buffer, or its offset "
+             "is no multiple of the element size";
+  }
+  L.by_items = true;
+  L.items_sum = sum;
+  std::vector<int64_t> order((size_t)r.n_items);
+  for (int64_t k = 0; k < r.n_items; k++) order[k] = k;
+  std::stable_sort(order.begin(), order.end(),
+                   [&](int64_t a, int64_t b) { return r.list[a].image < r.list[b].image; });
+  for (const int64_t k : order) {
+    if (status[k]) continue;
+    const spdl_hj_resample_items_item& it = r.list[k];
+    rs::ItemDesc rec{};
+    int bands = 0, chunks = 0;
+    const int rc = r.place_item(r.cache, r.filter, r.gap, &it, fw[it.image], fh[it.image], sum,
+                                L.tables, pool, &rec, &bands, &chunks);
+    if (rc == SPDL_HJ_ERR_INVALID_ARG) return "spdl_hj_set_resample_items: an item does not resolve";
+    if (rc) {  // (its axes or its tiles: refused alone)
+      status[k] = rc;
+      continue;
+    }
+    const int64_t tiles = (int64_t)bands * chunks, elem = it.offset / esz;
+    if ((int64_t)L.item_map.size() + tiles > INT32_MAX - 65536)
+      return "spdl_hj_set_resample_items: too many tiles for one submission";
+    rec.image = it.image;
+    rec.flip = it.flip;
+    rec.wg0 = (int32_t)L.item_map.size();
+    rec.chunks = chunks;
+    rec.off_lo = (uint32_t)elem;
+    rec.off_hi = (uint32_t)(elem >> 32);
+    L.resample_lds =
+        std::max(L.resample_lds, (sum ? rs::reduce_lds_words(rec.rd) : rs::lds_layout(rec.rd).words) * 4);
+    L.item_map.insert(L.item_map.end(), (size_t)tiles, (uint32_t)L.items.size());
+    L.items.push_back(rec);
+  }
+  L.item_map.insert(L.item_map.end(), (size_t)(n + 255) / 256, rs::kItemNone);
+  return nullptr;
+}
+
+namespace {
+
 struct Planner {
   const LayoutRequest& rq;
   Layout& L;
   LayoutResult res;
+  std::vector<int> item_fw, item_fh;  // an items submission: every image's (draft) frame
   TablePool pool;
   BoxSize size;           // the images' output size (L.ow x L.oh)
   bool have_fmt = false;  // the planar output's frame format is set (L.yuv_*)
@@ -545,6 +618,13 @@ struct Planner {
       refuse(d, crop_rc);
       return SPDL_HJ_OK;
     }
+    if (rq.resample && rq.resample->place_item) {
+      // (an items submission: the image has no box and no tile of its own --
+      // plan_items places the items once every frame is known)
+      item_fw[i] = src.w;
+      item_fh[i] = src.h;
+      return SPDL_HJ_OK;
+    }
     if (rq.resample) {
       // every image's box is the request's, whatever its frame; an image the
       // resample cannot take is refused alone, its box untouched
@@ -862,11 +942,17 @@ struct Planner {
     const ResampleRequest& r = *rq.resample;
     const char* what = nullptr;
     if (rq.out->csc != SPDL_HJ_CSC_TURBO) what = "spdl_hj_set_resample needs csc = turbo";
-    else if (!rq.plans || !r.cache || !(r.place || (r.place_box && r.probe_box)))
+    else if (!rq.plans || !r.cache ||
+             !(r.place || (r.place_box && r.probe_box) || (r.place_item && r.probe_item)))
       what = "spdl_hj_set_resample needs an output stage";
     else if (rq.out->pix_fmt == SPDL_HJ_FMT_YUV) what = "no resampled planar YUV output";
     else if (rq.ragged) what = "spdl_hj_set_resample and spdl_hj_set_ragged on one submission";
-    else if ((r.items || r.box_items) && r.n != rq.n)
+    else if (r.place_item) {
+      // (the items themselves are held once the frames are known: plan_items)
+      if (rq.crops || rq.views || rq.flips || rq.orients || rq.lowres)
+        what = "spdl_hj_set_resample_items with crops, views, per-image flips, orientations or "
+               "spdl_hj_set_lowres on one submission";
+    } else if ((r.items || r.box_items) && r.n != rq.n)
       what = "spdl_hj_set_resample: one item per image of the batch";
     else if (r.place_box && !(r.gap == 0.0 || r.gap >= 1.0))
       what = "spdl_hj_set_resample_box: reducing_gap is 0 or at least 1";
@@ -922,6 +1008,22 @@ struct Planner {
     d.sws_bands = bands;
     d.sws_chunks = chunks;
     L.sws_wgs += (int64_t)bands * chunks;
+    return SPDL_HJ_OK;
+  }
+
+  // An items submission once every image's frame stands: place_items, and the
+  // items' own statuses to the caller's array now that every limit has held
+  int plan_items() {
+    const ResampleRequest& r = *rq.resample;
+    std::vector<int32_t> status;
+    const int64_t esz = rq.out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
+    if (const char* what =
+            place_items(r, item_fw, item_fh, esz, rq.out_bytes, L, rs_pool, status)) {
+      res.rc = SPDL_HJ_ERR_INVALID_ARG;
+      snprintf(res.err, sizeof(res.err), "%s", what);
+      return res.rc;
+    }
+    if (r.item_status) std::copy(status.begin(), status.end(), r.item_status);
     return SPDL_HJ_OK;
   }
 
@@ -1026,12 +1128,18 @@ LayoutResult build_layout(const LayoutRequest& rq, Layout& L) {
       P.check_resample())
     return P.res;
   L.desc.assign(rq.n, ImageDesc{});
-  if (rq.resample) L.resample.assign(rq.n, rs::ResampleDesc{});
+  const bool by_items = rq.resample && rq.resample->place_item;
+  if (rq.resample && !by_items) L.resample.assign(rq.n, rs::ResampleDesc{});
+  if (by_items) {
+    P.item_fw.assign(rq.n, 0);
+    P.item_fh.assign(rq.n, 0);
+  }
   if (rq.ragged) P.fused_image.assign(rq.n, 0);
   if (rq.views) P.index_views();
   for (int i = 0; i < rq.n; i++)
     if (P.plan_image(i)) return P.res;
   if (rq.views && P.plan_views()) return P.res;
+  if (by_items && P.plan_items()) return P.res;
   P.finish();
   if (rq.ragged && P.finish_ragged()) return P.res;
   P.place_flips();
@@ -1113,6 +1221,29 @@ int ragged_layout(const spdl_hj_image_info* infos, int n, const spdl_hj_output* 
     end = offsets[i] + (int64_t)fw * fh * 3 * esz;
   }
   offsets[n] = end;
+  return SPDL_HJ_OK;
+}
+
+int resample_items_check(const spdl_hj_image_info* infos, int n, const uint8_t* draft,
+                         const ResampleRequest& r, int64_t esz, int64_t out_bytes, int32_t* status) {
+  if (!infos || n < 1 || !r.cache || !r.place_item || !r.probe_item || (esz != 1 && esz != 2) ||
+      out_bytes < 0)
+    return SPDL_HJ_ERR_INVALID_ARG;
+  std::vector<int> fw(n), fh(n);
+  for (int i = 0; i < n; i++) {
+    fw[i] = infos[i].width;
+    fh[i] = infos[i].height;
+    if (draft && draft[i] > 3) return SPDL_HJ_ERR_INVALID_ARG;
+    if (draft && infos[i].ncomp != 4) {
+      int pw[kMaxComp], ph[kMaxComp];
+      draft_plan(infos[i], draft[i], &fw[i], &fh[i], pw, ph);
+    }
+  }
+  Layout L;
+  ResamplePool pool;
+  std::vector<int32_t> st;
+  if (place_items(r, fw, fh, esz, out_bytes, L, pool, st)) return SPDL_HJ_ERR_INVALID_ARG;
+  if (status) std::copy(st.begin(), st.end(), status);
   return SPDL_HJ_OK;
 }
 

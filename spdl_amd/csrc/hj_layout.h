@@ -156,6 +156,18 @@ struct Layout {
   // submission has a factor above 1: that submission launches resample_kernel.
   std::vector<rs::ReduceDesc> reduce;
   int reduce_images = 0;  // images with a factor above 1
+  // An items submission (spdl_hj_set_resample_items): `resample` and `reduce`
+  // stay empty, no image has an output box or a tile of its own, and
+  // resample_items_kernel runs over item_map -- one entry per workgroup: the
+  // index into `items` of the item whose tile it is, one image's items
+  // adjacent, and behind the tiles ceil(n / 256) entries rs::kItemNone, the
+  // workgroups that report the images' statuses.  `items` holds the placed
+  // items alone (a refused one has no record and no tile), in grid order.
+  // items_sum: some item has a reduce factor above 1 (every record is
+  // rs::tile_reduce()'s); resample_lds is the kernel's LDS as above.
+  std::vector<rs::ItemDesc> items;
+  std::vector<uint32_t> item_map;
+  bool by_items = false, items_sum = false;
 };
 
 // Image p at draft level lv (0..3), as libjpeg-turbo's scale (8 >> lv) / 8
@@ -216,6 +228,14 @@ using ResampleBoxPlaceFn = int (*)(void* cache, int filter, double gap,
                                    int* chunks);
 using ResampleBoxProbeFn = int (*)(int filter, double gap, const spdl_hj_resample_box_item* it,
                                    int W, int H, int out_w, int out_h, int* reduces);
+// spdl_hj_set_resample_items' request the same way: rs::place_item_into and
+// rs::probe_item
+using ResampleItemPlaceFn = int (*)(void* cache, int filter, double gap,
+                                    const spdl_hj_resample_items_item* it, int W, int H, bool sum,
+                                    std::vector<int32_t>& tables, ResamplePool& pool,
+                                    rs::ItemDesc* rec, int* bands, int* chunks);
+using ResampleItemProbeFn = int (*)(int filter, double gap, const spdl_hj_resample_items_item* it,
+                                    int W, int H, int* reduces);
 struct ResampleRequest {
   int filter, out_w, out_h;
   const spdl_hj_resample_item* items;
@@ -228,7 +248,28 @@ struct ResampleRequest {
   double gap = 0;
   ResampleBoxPlaceFn place_box = nullptr;
   ResampleBoxProbeFn probe_box = nullptr;
+  // spdl_hj_set_resample_items (place_item set): n_items items in place of the
+  // per-image records, any number per image (out_w / out_h above mean nothing);
+  // item_status: null, or where each item's own status goes once every limit
+  // of the submission has held
+  const spdl_hj_resample_items_item* list = nullptr;
+  int64_t n_items = 0;
+  int32_t* item_status = nullptr;
+  ResampleItemPlaceFn place_item = nullptr;
+  ResampleItemProbeFn probe_item = nullptr;
 };
+
+// The planner's item path (hj_layout.cpp): request r against the frames
+// fw[i] x fh[i] into L.items / L.item_map / L.tables; null and each item's own
+// status, or why the submission is refused
+struct Layout;
+const char* place_items(const ResampleRequest& r, const std::vector<int>& fw,
+                        const std::vector<int>& fh, int64_t esz, int64_t out_bytes, Layout& L,
+                        ResamplePool& pool, std::vector<int32_t>& status);
+// spdl_hj_resample_items_check (spdl_hipjpeg.h): the items of a request held
+// against n probed images as the planner holds them, without a device
+int resample_items_check(const spdl_hj_image_info* infos, int n, const uint8_t* draft,
+                         const ResampleRequest& r, int64_t esz, int64_t out_bytes, int32_t* status);
 
 // One submission as the planner sees it: n images at offsets[i], sizes[i] of
 // the batch's bytes with their probes.  piece_bytes: the size from which a

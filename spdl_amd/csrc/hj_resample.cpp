@@ -386,5 +386,69 @@ int place_box_into(void* cache, int filter, double gap, const spdl_hj_resample_b
   return pool_tables(pl, tables, pool, d, bands, chunks);
 }
 
+int resolve_item(const spdl_hj_resample_items_item* it, int W, int H, int filter, double gap,
+                 ItemGeo* g) {
+  *g = ItemGeo{};
+  if (it->flip < 0 || it->flip > 3 || it->out_w < 1 || it->out_w > 65535 || it->out_h < 1 ||
+      it->out_h > 65535)
+    return SPDL_HJ_ERR_INVALID_ARG;
+  spdl_hj_resample_box_item b{it->x0, it->y0, it->x1, it->y1, it->rw, it->rh, it->ox, it->oy};
+  if (!it->clamp) return resolve_box(&b, W, H, it->out_w, it->out_h, filter, gap, &g->b);
+  int fw = W, fh = H;
+  if (b.x0 != 0 || b.y0 != 0 || b.x1 != 0 || b.y1 != 0) {
+    const double v[4] = {b.x0, b.y0, b.x1, b.y1};
+    for (double x : v)
+      if (!(x >= -65536.0 && x <= 65536.0) || x != floor(x)) return SPDL_HJ_ERR_INVALID_ARG;
+    if (b.x0 < 0 || b.y0 < 0 || b.x1 <= b.x0 || b.y1 <= b.y0 || b.x1 > W || b.y1 > H)
+      return SPDL_HJ_ERR_BAD_GEOMETRY;
+    g->bx = (int)b.x0;
+    g->by = (int)b.y0;
+    fw = (int)b.x1 - g->bx;
+    fh = (int)b.y1 - g->by;
+    b.x0 = b.y0 = b.x1 = b.y1 = 0;
+  }
+  return resolve_box(&b, fw, fh, it->out_w, it->out_h, filter, gap, &g->b);
+}
+
+int probe_item(int filter, double gap, const spdl_hj_resample_items_item* it, int W, int H,
+               int* reduces) {
+  ItemGeo g;
+  const int rc = resolve_item(it, W, H, filter, gap, &g);
+  *reduces = !rc && (g.b.fx > 1 || g.b.fy > 1);
+  return rc;
+}
+
+int place_item_into(void* cache, int filter, double gap, const spdl_hj_resample_items_item* it,
+                    int W, int H, bool sum, std::vector<int32_t>& tables, ResamplePool& pool,
+                    ItemDesc* rec, int* bands, int* chunks) {
+  ItemGeo ig;
+  int rc = resolve_item(it, W, H, filter, gap, &ig);
+  if (rc) return rc;
+  const BoxGeo& b = ig.b;
+  if (!sum && (b.fx > 1 || b.fy > 1)) return SPDL_HJ_ERR_INVALID_ARG;  // (the planner probed)
+  AxisCache& ac = *static_cast<AxisCache*>(cache);
+  Placed pl;
+  pl.H = ac.get(b.cw, b.box[0], b.box[2], b.rw, filter, &rc);
+  if (!pl.H) return rc;
+  pl.V = ac.get(b.ch, b.box[1], b.box[3], b.rh, filter, &rc);
+  if (!pl.V) return rc;
+  // (with sums the cells count from rr.qx / qy, which hold the clamped box's
+  // origin; without, the producer reads the frame at the box's origin + xmin)
+  const Geo g{sum ? 0 : ig.bx, sum ? 0 : ig.by, b.cw, b.ch, b.rw, b.rh, b.ox, b.oy};
+  rc = sum ? tile_reduce(*pl.H, *pl.V, g, it->out_w, it->out_h, &pl.d, &pl.bands, &pl.chunks)
+           : tile(*pl.H, *pl.V, g, it->out_w, it->out_h, &pl.d, &pl.bands, &pl.chunks);
+  if (rc) return rc;
+  rec->rr = ReduceDesc{ig.bx + b.q[0], ig.by + b.q[1], b.q[2] - b.q[0], b.q[3] - b.q[1],
+                       b.fx,           b.fy,           b.cw,            b.ch,
+                       {},             {}};
+  for (int k = 0; k < 4; k++) {
+    rec->rr.amend[k] = (uint32_t)b.div[k] / 2;
+    rec->rr.mult[k] = b.mult[k];
+  }
+  rec->ow = it->out_w;
+  rec->oh = it->out_h;
+  return pool_tables(pl, tables, pool, &rec->rd, bands, chunks);
+}
+
 }  // namespace rs
 }  // namespace hj

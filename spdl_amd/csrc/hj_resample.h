@@ -132,5 +132,31 @@ int place_box_into(void* cache, int filter, double gap, const spdl_hj_resample_b
 int probe_box(int filter, double gap, const spdl_hj_resample_box_item* it, int W, int H, int out_w,
               int out_h, int* reduces);
 
+// ---- spdl_hj_set_resample_items: one item against its image's W x H frame ----
+// resolve_box of the item's own request.  clamp = 0: as it stands.  clamp = 1:
+// the integral box (bx, by) + bw x bh is a frame of its own, the request its
+// whole frame: q, cw x ch and the box are relative to (bx, by).
+struct ItemGeo {
+  BoxGeo b;
+  int bx, by;
+};
+// 0; SPDL_HJ_ERR_INVALID_ARG (the submission's): what resolve_box gives it for,
+// a flip outside 0..3, an output box outside 1..65535, a clamped box that is
+// not integral; SPDL_HJ_ERR_BAD_GEOMETRY (the item's): what resolve_box gives
+// it for, a clamped box that is empty or outside the frame
+int resolve_item(const spdl_hj_resample_items_item* it, int W, int H, int filter, double gap,
+                 ItemGeo* g);
+// ... its status and whether it has a factor above 1 (ResampleRequest::probe_item)
+int probe_item(int filter, double gap, const spdl_hj_resample_items_item* it, int W, int H,
+               int* reduces);
+// ... and its record for resample_items_kernel, tables placed once per
+// submission.  sum: some item of the submission has a factor above 1 -- every
+// record is then tile_reduce()'s with rec->rr set, else tile()'s.
+// (ResampleRequest::place_item; the image, the flip, the offset and the tiles'
+// place in the grid are the planner's to fill.)
+int place_item_into(void* cache, int filter, double gap, const spdl_hj_resample_items_item* it,
+                    int W, int H, bool sum, std::vector<int32_t>& tables, ResamplePool& pool,
+                    ItemDesc* rec, int* bands, int* chunks);
+
 }  // namespace rs
 }  // namespace hj

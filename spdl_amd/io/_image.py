@@ -380,20 +380,20 @@ class PilResize:
         These restate torchvision's ``Resize(int)`` and ``CenterCrop`` on a PIL
         image; a window larger than the resized picture is refused by the
         decoder (torchvision would pad)."""
-        w, h = self.size
-        if self.by_box:
-            return box, (w, h), (0, 0)
-        if self.shorter is None:
-            return box, (w, h), (0, 0)
+        if self.size is not None and (self.by_box or self.shorter is None):
+            return box, self.size, (0, 0)
         sw, sh = (box[2], box[3]) if box is not None else (width, height)
         if sw <= sh:
             rw, rh = self.shorter, int(self.shorter * sh / sw)
         else:
             rw, rh = int(self.shorter * sw / sh), self.shorter
+        if self.size is None:  # (Resize(shorter) alone: load_image_list writes it whole)
+            return box, (rw, rh), (0, 0)
+        w, h = self.size
         return box, (rw, rh), (int(round((rw - w) / 2.0)), int(round((rh - h) / 2.0)))
 
 
-def pil_resize(size, filter: str = "bilinear", boxes=None, shorter=None, resize_boxes=None,
+def pil_resize(size=None, filter: str = "bilinear", boxes=None, shorter=None, resize_boxes=None,
                reducing_gap=None) -> PilResize:
     """Pillow's ``Image.resize`` on the GPU, for ``csc="turbo"``: the output is
     ``np.asarray(Image.open(f).convert("RGB").crop(box).resize(size, filter))``
@@ -409,7 +409,16 @@ def pil_resize(size, filter: str = "bilinear", boxes=None, shorter=None, resize_
     frame -- which ``boxes``, a crop, does not do -- and a gap of at least 1,
     which runs ``Image.reduce`` by whole factors ahead of the resize.
     ``resize_boxes`` is exclusive with ``boxes`` and ``shorter``;
-    ``reducing_gap`` alone takes the whole frame."""
+    ``reducing_gap`` alone takes the whole frame.  ``size=None`` with
+    ``shorter``: ``Resize(shorter)`` alone, every file at its own size --
+    :func:`load_image_list`'s, which writes one size per file."""
+    if size is None:
+        if shorter is None or resize_boxes is not None or reducing_gap is not None:
+            raise ValueError("pil_resize() without a size needs shorter= and nothing of box=")
+        size = (1, 1)  # (held below like any size, then dropped)
+        keep_size = False
+    else:
+        keep_size = True
     if resize_boxes is not None or reducing_gap is not None:
         if boxes is not None or shorter is not None:
             raise ValueError("resize_boxes= / reducing_gap= are exclusive with boxes= and shorter=")
@@ -430,7 +439,7 @@ def pil_resize(size, filter: str = "bilinear", boxes=None, shorter=None, resize_
         boxes = tuple(None if b is None else tuple(int(v) for v in b) for b in boxes)
         if any(b is not None and len(b) != 4 for b in boxes):
             raise ValueError("a box is (x, y, w, h) or None")
-    return PilResize((int(size[0]), int(size[1])), filter, boxes,
+    return PilResize((int(size[0]), int(size[1])) if keep_size else None, filter, boxes,
                      None if shorter is None else int(shorter), resize_boxes,
                      None if reducing_gap is None else float(reducing_gap))
 
@@ -494,20 +503,24 @@ def _thumbnail_of(thumb: PilThumbnail, infos):
     sizes = sorted({p[1] for p in plans})
     if len(sizes) != 1:
         raise ValueError(f"pil_thumbnail: the files resolve to different sizes {sizes}; one "
-                         "submission writes one size (ragged resample output is out of scope)")
+                         "[B,H,W,3] holds one size: load_image_list(resample=pil_thumbnail(...)) "
+                         "returns every file at its own")
     levels = [p[0] for p in plans]
     gap = thumb.reducing_gap if any(p[2] is not None for p in plans) else None
     rs = PilResize(sizes[0], thumb.filter, None, None, tuple(p[2] for p in plans), gap)
     return (levels if any(levels) else None), rs
 
 
-def _check_resample(resample, csc, n_src, filter_desc, pix_fmt) -> None:
+def _check_resample(resample, csc, n_src, filter_desc, pix_fmt, ragged: bool = False) -> None:
     """``resample=`` against what goes with it, before anything is read; what
     ``csc="turbo"`` excludes is :func:`_check_csc`'s to refuse."""
     if resample is None:
         return
     if not isinstance(resample, (PilResize, PilThumbnail)):
         raise ValueError("resample= takes what pil_resize() or pil_thumbnail() returns")
+    if resample.size is None and not ragged:
+        raise ValueError("pil_resize(shorter=) without a size gives every file its own size: "
+                         "load_image_list takes it")
     if csc != "turbo":
         raise ValueError(f"resample= needs csc='turbo', not {csc!r}")
     for boxes in (getattr(resample, "boxes", None), getattr(resample, "resize_boxes", None)):
@@ -527,6 +540,143 @@ def _resample_of(resample: PilResize, infos, keep, levels=None) -> _lib.Resample
                   for (w, h), k in zip(sizes, keep))
     return _lib.Resample(resample.filter, *resample.size, items, resample.by_box,
                          resample.reducing_gap)
+
+
+class _ResampleNeedsTurbo(TypeError, ValueError):
+    """``load_image_list(resample=)`` without ``csc="turbo"``.  The swscale
+    path of that function has never had the argument, which callers saw as a
+    ``TypeError``; as a refused combination of arguments it is a ``ValueError``
+    like every other one here.  It stays both."""
+
+
+def _item_requests(resample, infos, keep, dlevels, flips):
+    """``resample=`` of :func:`load_image_list` as one item per kept image:
+    ``(levels, requests, gap)`` for :func:`spdl_amd._lib.resample_layout` -- a
+    thumbnail's own size and draft level per file, ``pil_resize(shorter=)``'s
+    aspect-preserving size, or ``pil_resize(size)``'s one size for all."""
+    flips = flips or [0] * len(infos)
+    if isinstance(resample, PilThumbnail):
+        plans = [resample.plan(i.width, i.height) for i in infos]
+        levels = [p[0] for p in plans]
+        reqs = [(k, p[2], False, p[1], None, flips[k]) for k, p in enumerate(plans)]
+        gap = resample.reducing_gap if any(p[2] is not None for p in plans) else None
+        return (levels if any(levels) else None), reqs, gap
+    boxes = resample.resize_boxes if resample.by_box else resample.boxes
+    reqs = []
+    for k, (info, lv) in enumerate(zip(infos, dlevels or [0] * len(infos))):
+        w, h = _lib.draft_size(info.width, info.height, lv) if lv else (info.width, info.height)
+        box, rsz, (ox, oy) = resample.geometry(w, h, None if boxes is None else boxes[keep[k]])
+        if box is not None and not resample.by_box:  # (a crop (x, y, w, h): Pillow's corners)
+            box = (box[0], box[1], box[0] + box[2], box[1] + box[3])
+        window = None if resample.size is None else (ox, oy, *resample.size)
+        reqs.append((k, box, not resample.by_box, rsz, window, flips[k]))
+    return dlevels, reqs, resample.reducing_gap
+
+
+def _views_turbo(srcs, groups, cfg, strict: bool):
+    """:func:`load_image_views` with ``csc="turbo"``: every group's boxes of
+    every file as the items of one submission (include/spdl_hipjpeg.h
+    "resample items") -- parse, Huffman decode and IDCT run once per file."""
+    keys = {"resample", "boxes", "resize_boxes", "flips", "pix_fmt", "normalize", "dtype", "mean",
+            "std"}
+    outs = []
+    for g in groups:
+        if not hasattr(g, "keys") or set(g.keys()) - keys:
+            raise ValueError(f"a csc='turbo' group takes {sorted(keys)}")
+        rs = g.get("resample")
+        if not isinstance(rs, PilResize) or rs.size is None or rs.boxes or rs.resize_boxes:
+            raise ValueError("a group's resample= is pil_resize((w, h), filter): its boxes are "
+                             "the group's boxes= / resize_boxes=")
+        if (g.get("boxes") is None) == (g.get("resize_boxes") is None):
+            raise ValueError("a group needs boxes= or resize_boxes=: a list of boxes per image")
+        per = g.get("boxes") if g.get("boxes") is not None else g["resize_boxes"]
+        if len(per) != len(srcs):
+            raise ValueError(f"{len(per)} box lists for {len(srcs)} images")
+        if g.get("flips") is not None and [len(f) for f in g["flips"]] != [len(b) for b in per]:
+            raise ValueError("flips= is parallel to the boxes: one flip per box")
+        pix_fmt = g.get("pix_fmt", "rgb24")
+        if pix_fmt not in ("rgb", "bgr", "rgb24", "bgr24"):
+            raise ValueError(f"a group's pix_fmt is rgb, bgr, rgb24 or bgr24, not {pix_fmt!r}")
+        out = Output(pix_fmt=pix_fmt, csc="turbo")
+        if g.get("normalize", False):
+            out = Output(**{**out.__dict__, "normalize": True, "norm_dtype": g.get("dtype", "float16"),
+                            "mean": tuple(g.get("mean", Output.mean)),
+                            "std": tuple(g.get("std", Output.std))})
+        outs.append(out)
+    if any(o != outs[0] for o in outs):
+        raise ValueError("the groups of a csc='turbo' submission share pix_fmt, dtype and "
+                         "normalisation: one submission writes one format")
+    first = groups[0]["resample"]
+    if any((g["resample"].filter, g["resample"].reducing_gap) != (first.filter, first.reducing_gap)
+           for g in groups):
+        raise ValueError("the groups of a csc='turbo' submission share filter and reducing_gap")
+    out = outs[0]
+    datas, keep, infos = [], [], []
+    for i, s in enumerate(srcs):
+        try:
+            d = _read(s)
+            infos.append(_lib.get_image_info(d))
+        except Exception as err:  # reference logs and skips (strict=False)
+            _LG.error("Failed to load image %d: %s", i, err)
+            continue
+        datas.append(d)
+        keep.append(i)
+    if strict and len(datas) != len(srcs):
+        raise RuntimeError("Failed to load some images.")
+    if not datas:
+        raise RuntimeError("Failed to load all the images.")
+    # one request list: group by group, each in (image, box) order
+    reqs, rows = [], []
+    for g in groups:
+        clamp = g.get("boxes") is not None
+        per = g["boxes"] if clamp else g["resize_boxes"]
+        src_of = []
+        for k, i in enumerate(keep):
+            for j, b in enumerate(per[i]):
+                if clamp and b is not None:  # (a crop (x, y, w, h): Pillow's corners)
+                    b = (b[0], b[1], b[0] + b[2], b[1] + b[3])
+                f = 0 if g.get("flips") is None else _lib._flip(g["flips"][i][j])
+                reqs.append((k, b, clamp, g["resample"].size, None, f))
+                src_of.append(i)
+        if not src_of:
+            raise ValueError("a group without any box")
+        rows.append(src_of)
+    esz = 1 if out.torch_dtype == torch.uint8 else 2
+    # every box of a group has one size, so its rows are contiguous when each
+    # box is a multiple of the alignment apart: pack tight, align the groups
+    offsets, at = [], 0
+    for g, src_of in zip(groups, rows):
+        at = -(-at // 256) * 256
+        w, h = g["resample"].size
+        offsets += [at + r * w * h * 3 * esz for r in range(len(src_of))]
+        at += len(src_of) * w * h * 3 * esz
+    items = _lib.ResampleItems(first.filter, [(k, b, c, sz, (0, 0), sz, f, o)
+                                              for (k, b, c, sz, _, f), o in zip(reqs, offsets)],
+                               first.reducing_gap)
+    _lib.resample_items_check(infos, items, esz, at)  # (ValueError before anything is submitted)
+    total = _alloc_out(cfg, (max(at // esz, 1),), out.torch_dtype)
+    dec = _lib.thread_decoder(cfg.device_index)
+    status = dec.decode_batch(datas, out, total.data_ptr(), at, stream=_stream(cfg), sync=True,
+                              check=strict, resample_items=items)
+    from ._convert import to_torch
+
+    flat, result, q = to_torch(total), [], 0
+    for g, src_of in zip(groups, rows):
+        w, h = g["resample"].size
+        shape = (len(src_of), *_shape(out, w, h))
+        buf = flat[offsets[q] // esz:offsets[q] // esz + int(np.prod(shape))].view(shape)
+        ok = [r for r in range(len(src_of))
+              if items.statuses[q + r] == 0 and status[reqs[q + r][0]] == 0]
+        if len(ok) != len(src_of):
+            if strict:
+                raise RuntimeError("Failed to decode an image. (a box of a group is refused: "
+                                   f"statuses {items.statuses[q:q + len(src_of)]})")
+            if not ok:
+                raise RuntimeError("Failed to load all the images.")
+            buf = buf.index_select(0, torch.tensor(ok, device=buf.device))
+        result.append((CUDABuffer(buf, stream=cfg.stream, owner=total), [src_of[r] for r in ok]))
+        q += len(src_of)
+    return result
 
 
 def _check_draft(draft, csc, resample, n_src) -> None:
@@ -864,7 +1014,7 @@ def _view_group_output(g) -> Output:
 
 
 def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = True,
-                     exif_orientation: bool = False):
+                     exif_orientation: bool = False, csc: str = "swscale"):
     """Several crops and sizes of every image from one decode (an extension,
     like ``crops=`` and ``normalize=``): multi-crop augmentation, a thumbnail
     beside a training crop.  Every file is parsed and entropy-decoded once and
@@ -889,7 +1039,16 @@ def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = 
     order and ``image_indices[r]`` the image row r was made of.
     ``strict=False`` drops the rows of failed images and refused rectangles
     (``image_indices`` says what remains); ``strict=True`` raises, as
-    ``load_image_batch`` does."""
+    ``load_image_batch`` does.
+
+    ``csc="turbo"``: multi-crop with Pillow's pixels.  A group is then
+    ``dict(resample=pil_resize((w, h), filter), boxes=[[box, ...] per image],
+    flips=[[flip, ...] per image])`` with ``pix_fmt`` / ``normalize`` /
+    ``dtype`` / ``mean`` / ``std``: every box ``(x, y, w, h)`` is
+    ``im.crop(box).resize((w, h), filter)``; ``resize_boxes=`` in place of
+    ``boxes=`` takes float boxes ``(x0, y0, x1, y1)`` as ``im.resize(box=)``
+    does.  The groups share format, dtype, filter and ``reducing_gap`` and are
+    256-byte aligned slices of one allocation."""
     if not srcs:
         raise ValueError("`srcs` must not be empty.")
     if device_config is None:
@@ -897,6 +1056,12 @@ def load_image_views(srcs, groups, *, device_config: CUDAConfig, strict: bool = 
     groups = list(groups)
     if not 1 <= len(groups) <= 4:
         raise ValueError(f"1 to 4 groups, not {len(groups)}")
+    if csc not in _LOAD_CSC:
+        raise ValueError(f"csc must be one of {list(_LOAD_CSC)}, not {csc!r}")
+    if csc == "turbo":
+        if exif_orientation:
+            raise ValueError("csc='turbo' takes no exif_orientation=")
+        return _views_turbo(srcs, groups, device_config, strict)
     outs = [_view_group_output(g) for g in groups]
     for g in groups:
         per_image = list(g["crops"])
@@ -1033,6 +1198,7 @@ def load_image_list(
     csc: str = "swscale",
     lowres=None,
     draft=None,
+    resample=None,
 ):
     """Every image at its own size from one submission (an extension, like
     :func:`load_image_views`; include/spdl_hipjpeg.h "ragged batches"): native
@@ -1052,7 +1218,11 @@ def load_image_list(
     for byte) of every file at its native size -- no ``width`` / ``height``,
     ``crops``, ``flips``, ``exif_orientation`` or ``lowres`` with it;
     ``draft`` (``load_image_batch``'s, without ``"auto"``) decodes each file at
-    its own level, every box its draft frame.
+    its own level, every box its draft frame.  ``resample=`` with it
+    (include/spdl_hipjpeg.h "resample items"): ``pil_thumbnail(size)`` gives
+    every file Pillow's thumbnail of its own size, ``pil_resize(shorter=256)``
+    ``Resize(256)`` with the aspect kept, ``pil_resize((w, h), ...)`` that size
+    for all; ``flips`` then mirrors single files in the same pass.
 
     Returns ``(buffers, image_indices)``: one allocation, every buffer a view
     of it with its image's own shape (``[H,W,3]``, or ``[3,H,W]`` for ``rgb`` /
@@ -1067,9 +1237,16 @@ def load_image_list(
     if csc not in ("swscale", "turbo"):
         raise ValueError(f"load_image_list converts with csc='swscale' only, or with csc='turbo' "
                          f"at native size, not {csc!r}")
-    _check_csc(csc, width=width, height=height, crops=crops, flips=flips,
+    _check_csc(csc, width=width, height=height, crops=crops,
+               flips=None if resample is not None else flips,
                exif_orientation=exif_orientation, lowres=lowres, pix_fmt=pix_fmt)
-    _check_draft(draft, csc, None, len(srcs))
+    if resample is not None and csc != "turbo":
+        raise _ResampleNeedsTurbo(f"load_image_list() takes resample= with csc='turbo' alone, not "
+                                  f"with csc={csc!r}")
+    _check_resample(resample, csc, len(srcs), None, pix_fmt, ragged=True)
+    _check_draft(draft, csc, resample, len(srcs))
+    if resample is not None and draft == "auto" and resample.size is None:
+        raise ValueError('draft="auto" needs a size to cover')
     if filter_desc == _FILTER_DESC_DEFAULT:
         filter_desc = _list_filter_desc(width, height, scale_mode, scale_algo, pix_fmt)
     elif (width, height, scale_mode) != (None, None, None):
@@ -1127,16 +1304,25 @@ def load_image_list(
         lowres = [per_lowres[i] for i in keep]
     levels = _lib.lowres_levels(lowres, infos, out, codes)
     _no_crops_with_lowres(levels, crops, out)
-    dlevels = _draft_levels(draft, infos, keep, None)
-    offsets, sizes, planned = _lib.ragged_layout(infos, out, crops, codes, align, lowres=levels,
-                                                 draft=dlevels)
+    dlevels = _draft_levels(draft, infos, keep, resample)
     esz = 1 if out.torch_dtype == torch.uint8 else 2
+    items = None
+    if resample is not None:  # (one item per image: its own size, its flip in the store)
+        dlevels, reqs, gap = _item_requests(resample, infos, keep, dlevels, codes)
+        offsets, sizes, planned, items = _lib.resample_layout(
+            infos, reqs, align, filter=resample.filter, reducing_gap=gap, elem_size=esz,
+            draft=dlevels)
+        codes = None
+    else:
+        offsets, sizes, planned = _lib.ragged_layout(infos, out, crops, codes, align, lowres=levels,
+                                                     draft=dlevels)
     # (every offset and every extent is a multiple of the element size)
     total = _alloc_out(cfg, (max(offsets[n] // esz, 1),), out.torch_dtype)
     dec = _lib.thread_decoder(cfg.device_index)
     status = dec.decode_batch(datas, out, total.data_ptr(), offsets[n], stream=_stream(cfg),
                               sync=True, check=False, crops=crops, orients=codes,
-                              ragged=offsets[:n], lowres=levels, draft=dlevels)
+                              ragged=None if items is not None else offsets[:n], lowres=levels, draft=dlevels,
+                              resample_items=items)
     from ._convert import to_torch
 
     flat = to_torch(total)
