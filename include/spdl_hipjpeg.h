@@ -77,6 +77,9 @@ enum spdl_hj_pix_fmt {
   SPDL_HJ_FMT_RGB24 = 2,
   SPDL_HJ_FMT_BGR24 = 3,
   SPDL_HJ_FMT_YUV = 4,
+  /* one channel, csc = TURBO alone: "Pillow-exact grayscale" below */
+  SPDL_HJ_FMT_L = 5,
+  SPDL_HJ_FMT_Y = 6,
 };
 
 enum spdl_hj_aspect { SPDL_HJ_ASPECT_NONE = 0, SPDL_HJ_ASPECT_DECREASE = 1, SPDL_HJ_ASPECT_INCREASE = 2 };
@@ -593,6 +596,59 @@ int spdl_hj_set_lowres(spdl_hj_ctx* ctx, const uint8_t* levels, int32_t n);
  * flat grid of 128 x 32 pixel tiles; the read-only parameter
  * "turbo_workgroups" reports its workgroups in the last submission (0 for any
  * other csc). */
+
+/* ---- Pillow-exact grayscale (additive in ABI 7: two values of
+ * spdl_hj_pix_fmt) ------------------------------------------------------------------
+ * Pillow calls two different pictures mode "L"; each is a format here, one
+ * channel, taken with csc = SPDL_HJ_CSC_TURBO alone:
+ *
+ *   SPDL_HJ_FMT_L   np.asarray(PIL.Image.open(f).convert("L")): the Pillow-exact
+ *                   decode's RGB through Pillow's L24 rule,
+ *                     (R 19595 + G 38470 + B 7471 + 0x8000) >> 16;
+ *                   a 1-component file is its Y plane.
+ *   SPDL_HJ_FMT_Y   libjpeg-turbo's JCS_GRAYSCALE output, what
+ *                   im.draft("L", im.size) and torchvision's GRAY read mode
+ *                   return: component 0 after the islow IDCT (upsampled by its
+ *                   own ratio where luma is sampled below chroma), no chroma
+ *                   read at all.  An RGB-coded file has no luma plane:
+ *                   libjpeg converts its three planes by rgb_gray_convert,
+ *                   whose tables are L24's constants, so there Y equals L
+ *                   (found against Pillow 12.2 and pinned).
+ * The two differ on every YCbCr file: the clipping of R, G, B and the rounding
+ * of the colour tables do not cancel (about 1.6 % of a q90 file's pixels).
+ *
+ * The output is [n][H][W][1]: out_w x out_h elements per image, and a ragged
+ * box (spdl_hj_ragged_layout) counts one element per pixel.  U8, F16 and BF16;
+ * the latter two normalise with mean[0] / std[0] by the rule of every output.
+ * Both formats go through everything the csc = TURBO chain takes: plain and
+ * ragged submissions at native size; spdl_hj_set_draft, where Y at level L is
+ * im.draft("L", (w, h)) and L is im.draft("RGB", (w, h)) followed by
+ * convert("L"); spdl_hj_set_resample, _resample_box and _resample_items, where
+ * the conversion comes FIRST and the passes run on one channel:
+ *   Image.open(f).convert("L").crop(box).resize(size, filter, ...)
+ * (Y: im.draft("L", ...) in the place of convert("L")), with boxes, reducing
+ * gaps, thumbnails, items and their flips as the three-channel chain has them.
+ * An item's box holds out_w x out_h elements.  (spdl_hj_resample_items_check
+ * counts three elements a pixel: hold a one-channel layout against three times
+ * its size; the submission checks the true extent.)
+ *
+ * With SPDL_HJ_FMT_Y a YCbCr file's chroma is decoded by the entropy stage and
+ * goes no further: the planner lays out component 0's plane alone and the IDCT
+ * stage counts and transforms component 0's blocks alone ("planes_bytes" and
+ * "idct_workgroups" show it).  An RGB-coded file keeps its three planes.
+ *
+ * SPDL_HJ_ERR_INVALID_ARG, nothing written: either format with csc SWSCALE or
+ * JFIF, or in a view group (spdl_hj_set_views is csc SWSCALE's).  A
+ * 4-component frame stays SPDL_HJ_ERR_UNSUPPORTED.
+ *
+ * The five output kernels of the chain -- turbo_rgb_kernel,
+ * turbo_rgb_draft_kernel, resample_kernel, resample_reduce_kernel,
+ * resample_items_kernel -- take the channel count as a template argument; <3>
+ * is the code as it stood.  <1> ends its producer in one value a pixel in
+ * registers, holds a byte a pixel in the resize's LDS strip and intermediate
+ * (a 16-bit sum a cell under a reducing gap) on tiles of up to 128 x 32, and
+ * stores a lane's 8 pixels of a row as one 8-byte (F16 / BF16: 16-byte) store
+ * where the row's alignment allows, with bytes at a ragged row's end. */
 
 /* ---- Pillow-exact resize (additive in ABI 7: one call, one debug entry, one
  * read-only parameter) -----------------------------------------------------------

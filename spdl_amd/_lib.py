@@ -19,7 +19,10 @@ ABI_VERSION = 7
 
 # enums (mirror include/spdl_hipjpeg.h)
 # "yuv": the frame's own planar format (SPDL_HJ_FMT_YUV, see planar_layout)
-PIX_FMTS = {"rgb": 0, "bgr": 1, "rgb24": 2, "bgr24": 3, "yuv": 4}
+# "L" / "Y": the one-channel formats of csc="turbo" (include/spdl_hipjpeg.h "Pillow-exact
+# grayscale"): Pillow's convert("L"), and libjpeg-turbo's own grayscale output
+PIX_FMTS = {"rgb": 0, "bgr": 1, "rgb24": 2, "bgr24": 3, "yuv": 4, "L": 5, "Y": 6}
+LUMA_FMTS = ("L", "Y")
 ASPECT = {None: 0, "none": 0, "decrease": 1, "increase": 2}
 FILTERS = {"bicubic": 0, "bilinear": 1, "lanczos": 2}
 IDCT = {"simple": 0, "islow": 1}
@@ -198,6 +201,9 @@ class Output:
     aspect ratio, ``-n`` also makes the size divisible by n).
     ``pix_fmt="yuv"`` keeps the frame's own planar format: the chain with no
     format node (u8, ``csc="swscale"`` only; layout: :func:`planar_layout`).
+    ``pix_fmt="L"`` / ``"Y"`` are one channel, ``[H, W, 1]``, with
+    ``csc="turbo"`` only: Pillow's ``convert("L")``, and libjpeg-turbo's own
+    grayscale output (include/spdl_hipjpeg.h "Pillow-exact grayscale").
 
     ``src_crop=(x, y, w, h)`` crops the decoder's own frame before the chain,
     for every image (libavfilter's ``crop=w:h:x:y`` ahead of ``scale``; ``x``
@@ -266,6 +272,11 @@ class Output:
     @property
     def planar(self) -> bool:
         return self.pix_fmt in ("rgb", "bgr")
+
+    @property
+    def channels(self) -> int:
+        """Elements per pixel: 1 for ``"L"`` / ``"Y"``, else 3."""
+        return 1 if self.pix_fmt in LUMA_FMTS else 3
 
     @property
     def torch_dtype(self):
@@ -624,12 +635,12 @@ def resample_items_check(infos, items: ResampleItems, elem_size: int, out_bytes:
 
 
 def resample_layout(infos, requests, align: int = 256, *, filter: str = "bicubic",
-                    reducing_gap=None, elem_size: int = 1, draft=None):
+                    reducing_gap=None, elem_size: int = 1, draft=None, channels: int = 3):
     """``(offsets, sizes, statuses, items)`` of an items submission (host only),
     the sibling of :func:`ragged_layout`.  ``requests``: per item ``(image, box,
     clamp, (rw, rh), window, flip)`` with ``window = (ox, oy, out_w, out_h)`` or
-    ``None`` for the whole resized picture.  Every item's ``out_h x out_w x 3``
-    box is packed in request order at a multiple of ``align`` bytes; ``offsets``
+    ``None`` for the whole resized picture.  Every item's ``out_h x out_w x
+    channels`` box (``channels=1``: ``pix_fmt`` ``"L"`` / ``"Y"``) is packed in request order at a multiple of ``align`` bytes; ``offsets``
     has one entry more than there are items, the last the buffer's size.
     ``statuses``: each item's own (``7``: refused alone, its box stays unwritten).
     ``items``: the :class:`ResampleItems` to submit.  ``ValueError`` for what the
@@ -641,11 +652,14 @@ def resample_layout(infos, requests, align: int = 256, *, filter: str = "bicubic
         ox, oy, ow, oh = window if window is not None else (0, 0, rw, rh)
         offsets.append(-(-end // align) * align)
         sizes.append((int(ow), int(oh)))
-        end = offsets[-1] + int(ow) * int(oh) * 3 * elem_size
+        end = offsets[-1] + int(ow) * int(oh) * channels * elem_size
         items.append((image, box, clamp, (rw, rh), (ox, oy), (ow, oh), flip, offsets[-1]))
     offsets.append(end)
     held = ResampleItems(filter, items, reducing_gap)
-    return offsets, sizes, resample_items_check(infos, held, elem_size, end, draft), held
+    # (the check counts three elements a pixel: a one-channel layout is held
+    # against an upper bound, and the submission itself against its true extent)
+    return offsets, sizes, resample_items_check(infos, held, elem_size, end * (3 // channels),
+                                                draft), held
 
 
 def resample_axis(in_size: int, out_size: int, filter: str, box=None):

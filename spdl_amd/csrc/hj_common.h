@@ -217,6 +217,9 @@ struct ImageDesc {      // host-filled per image
   int32_t width, height, ncomp;
   int32_t h_samp[kMaxComp], v_samp[kMaxComp];
   int32_t nblocks;
+  // (8 bytes a block or a lane: at least 8 for every plane that is laid out.
+  // 0 for components 1 and 2 says that a SPDL_HJ_FMT_Y submission gave them no
+  // plane -- idct_luma_only() below reads exactly that)
   int32_t plane_stride[kMaxComp];
   // output placement: out(x, y) = scaled(x - dx, y - dy), black outside
   int32_t dx, dy, ow, oh;
@@ -296,11 +299,16 @@ struct ResampleDesc {
 
 // The LDS of a workgroup, in words, in this order: the tile's horizontal xmin,
 // n and K rows, the vertical ones, the strip (packed pixels, sr x pitch), the
-// intermediate (packed pixels, rows x tw)
+// intermediate (packed pixels, rows x tw).  nch = 1 (SPDL_HJ_FMT_L / _Y): a
+// pixel is a BYTE in both -- `pitch` is then the words of a strip row of bytes
+// (the tiler's, odd as well) and the intermediate rows x tw / 4 words (tw is a
+// multiple of 8).  The one-channel strip of resample_reduce_kernel is the
+// exception: one word a cell, the 16-bit sum and then the pixel, on the
+// three-channel pitch.
 struct LdsLayout {
   int hx, hn, hk, vx, vn, vk, strip, inter, words;
 };
-inline HJ_HD LdsLayout lds_layout(const ResampleDesc& d) {
+inline HJ_HD LdsLayout lds_layout(const ResampleDesc& d, int nch = 3) {
   LdsLayout l;
   l.hx = 0;
   l.hn = l.hx + d.tw;
@@ -310,7 +318,7 @@ inline HJ_HD LdsLayout lds_layout(const ResampleDesc& d) {
   l.vk = l.vn + d.th;
   l.strip = l.vk + d.th * d.kv;
   l.inter = l.strip + d.sr * d.pitch;
-  l.words = l.inter + d.rows * d.tw;
+  l.words = l.inter + (nch == 1 ? d.rows * d.tw / 4 : d.rows * d.tw);
   return l;
 }
 
@@ -348,8 +356,9 @@ struct ReduceDesc {
 };
 // resample_reduce_kernel's LDS in words: lds_layout()'s, whose strip holds the
 // R | G << 16 sums and then the packed pixels, and behind it the B sums
-inline HJ_HD int reduce_lds_words(const ResampleDesc& d) {
-  return lds_layout(d).words + d.sr * d.pitch;
+// (nch = 1: one plane of sums, the strip itself)
+inline HJ_HD int reduce_lds_words(const ResampleDesc& d, int nch = 3) {
+  return lds_layout(d, nch).words + (nch == 1 ? 0 : d.sr * d.pitch);
 }
 
 // ---- Resample items (spdl_hj_set_resample_items): what resample_items_kernel
@@ -459,6 +468,19 @@ inline HJ_HD IdctBlockPos idct_block_pos(const ImageInfo& in, uint32_t j) {
   const int b = (int)m.r, c = in.mcu_comp[b];
   if (in.ncomp == 1) return {c, (int)p.r, (int)p.q};
   return {c, (int)p.r * in.comp_h[c] + in.mcu_dx[b], (int)p.q * in.comp_v[c] + in.mcu_dy[b]};
+}
+
+// A submission of SPDL_HJ_FMT_Y lays out and transforms component 0 of a YCbCr
+// frame alone (hj_layout.cpp Planner::luma_only): its chroma components have no
+// plane, which a stride of 0 says -- a plane that exists has 8 bytes a block.
+// idct_blocks is then component 0's blocks, and luma block l -- MCU order,
+// component 0's blocks are the first comp_h[0] comp_v[0] of every MCU -- is
+// block idct_luma_block() of the image's order, which bdesc and idct_block_pos take.
+inline HJ_HD bool idct_luma_only(const ImageDesc& d) { return d.ncomp > 1 && d.plane_stride[1] == 0; }
+inline HJ_HD uint32_t idct_luma_block(const ImageInfo& in, uint32_t l) {
+  const uint32_t k = (uint32_t)(in.comp_h[0] * in.comp_v[0]);
+  const uint32_t m = l / k;
+  return m * (uint32_t)in.bpm + (l - m * k);
 }
 
 // idct_kernel over a source crop: its threads enumerate the blocks of the MCU

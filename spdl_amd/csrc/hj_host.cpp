@@ -572,6 +572,8 @@ struct Submission {
 
 // An output chain's share of the output kernels' parameters: the batch's
 // spec and size, or a view group's
+// (the kernels test the one-channel formats by value: hj_kernels.hip kFmtL / kFmtY)
+static_assert(SPDL_HJ_FMT_L == 5 && SPDL_HJ_FMT_Y == 6, "hj_kernels.hip kFmtL / kFmtY");
 void set_chain(BatchParams& p, const spdl_hj_output& o, int w, int h) {
   p.pix_fmt = o.pix_fmt;
   p.dtype = o.dtype;
@@ -872,7 +874,7 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
     for (const auto& m : L.multi) {
       const ImageDesc& d = L.desc[m.first];
       R.items.push_back({m.first, sub.ragged ? (size_t)sub.ragged[m.first] : m.first * img_bytes,
-                         sub.ragged ? (size_t)d.ow * d.oh * 3 * esz : img_bytes,
+                         sub.ragged ? (size_t)d.ow * d.oh * output_channels(*out) * esz : img_bytes,
                          d.in_off, d.in_size, m.second,
                          sub.crops ? sub.crops[m.first] : spdl_hj_rect{},
                          sub.flips ? sub.flips[m.first] : (uint8_t)0,
@@ -954,6 +956,7 @@ int retry_image(spdl_hj_ctx* ctx, const Slot::Retry& r, const Slot::Retry::Item&
     rq.draft = &item.draft;
     rq.ndraft = 1;
   }
+  ctx->axes.channels = output_channels(r.out);
   ResampleRequest one{r.rs_filter, r.rs_ow, r.rs_oh, &item.resample, 1, &ctx->axes, &rs::place_into};
   if (r.rs_by_box) {
     one.items = nullptr;
@@ -1056,7 +1059,7 @@ int take_views(spdl_hj_ctx* ctx, int n, const spdl_hj_output* out, const void* o
     return bad("the call's output spec must be valid, with csc = swscale");
   if (out_dev || out_bytes) return bad("the call's out_dev must be NULL and out_bytes 0");
   for (const HeldViews::Group& g : held->groups) {
-    if (!valid_output(&g.out) || g.out.pix_fmt == SPDL_HJ_FMT_YUV ||
+    if (!valid_output(&g.out) || g.out.pix_fmt == SPDL_HJ_FMT_YUV || output_channels(g.out) == 1 ||
         g.out.csc != SPDL_HJ_CSC_SWSCALE)
       return bad("a group's output must be RGB / BGR with csc = swscale");
     if (g.out.idct != out->idct) return bad("every group's idct must equal the call's");
@@ -1124,6 +1127,8 @@ struct Held {
     std::swap(resamplev, ctx->resample);
     ctx->resample = {};
     if (resamplev.set) {
+      // (the tiler's channel count: a one-channel tile is sized by bytes)
+      ctx->axes.channels = out && valid_output(out) ? output_channels(*out) : 3;
       resample_rq = {resamplev.filter, resamplev.out_w, resamplev.out_h,
                      resamplev.has_items ? resamplev.items.data() : nullptr,
                      (int64_t)resamplev.items.size(), &ctx->axes, &rs::place_into};

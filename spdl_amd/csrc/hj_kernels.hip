@@ -4822,6 +4822,8 @@ __global__ void __launch_bounds__(kIdctThreads) idct_kernel(const uint32_t* __re
   if (j >= nb) return;
   if (dd.reg_mw)
     j = (int)idct_region_block(in, dd.reg_mx0, dd.reg_my0, dd.reg_mw, dd.reg_mw_magic, (uint32_t)j);
+  // (SPDL_HJ_FMT_Y: nb counts component 0's blocks, the only ones with a plane)
+  else if (idct_luma_only(dd)) j = (int)idct_luma_block(in, (uint32_t)j);
   const IdctBlockPos bp = idct_block_pos(in, (uint32_t)j);
   const int c = bp.c;
   uint32_t* b32 = &sblk[0][threadIdx.x];
@@ -5190,8 +5192,10 @@ __global__ void __launch_bounds__(kIdctThreads) idct_draft_kernel(
     load_dequant<kIdctThreads>(sq, in, threadIdx.x);
     __syncthreads();
     if (j >= nb) return;
-    const IdctBlockPos bp = idct_block_pos(in, (uint32_t)j);
-    list_block<kIdctThreads>(ents, bdesc[(size_t)dd.coef_off + j], dd.coef_off, in.nblocks,
+    // (SPDL_HJ_FMT_Y: nb counts component 0's blocks, the only ones with a plane)
+    const int jb = idct_luma_only(dd) ? (int)idct_luma_block(in, (uint32_t)j) : j;
+    const IdctBlockPos bp = idct_block_pos(in, (uint32_t)jb);
+    list_block<kIdctThreads>(ents, bdesc[(size_t)dd.coef_off + jb], dd.coef_off, in.nblocks,
                              sq[bp.c], b32);
     uint2 rows[8];
     idct_block_rows<kIdctThreads, 1>(b32, rows);
@@ -6882,6 +6886,133 @@ __device__ __forceinline__ void turbo_row(void* out, const ImageDesc& dd, const 
   turbo_store_row(out, dd.out_off, p, dd.ow, dd.oh, x0, y, min(8, dd.ow - x0), c0, c1, c2);
 }
 
+__device__ __forceinline__ void turbo_samples(const uint8_t* __restrict__ planes,
+                                              const ImageDesc& dd, int x0, int y0,
+                                              int (&v)[3][2][8]);
+__device__ __forceinline__ void turbo_samples_draft(const uint8_t* __restrict__ planes,
+                                                    const ImageDesc& dd, const draft::Desc& dr,
+                                                    int x0, int y0, int (&v)[3][2][8]);
+
+// ---- the one-channel formats (spdl_hipjpeg.h "Pillow-exact grayscale") ----
+// NCH, the template argument of the two full-resolution kernels below, is the
+// output's channel count: 3 runs the bodies as they stood (their code is held
+// unchanged), 1 the luma path -- the same grid, tiles and thread-to-pixel map,
+// a producer that ends in ONE value per pixel in registers, and a store of 8
+// consecutive pixels per lane and row.
+//   L (pix_fmt 5): Pillow's convert("L") -- the frame's RGB through L24; a
+//     1-component frame is its Y plane.
+//   Y (pix_fmt 6): libjpeg's JCS_GRAYSCALE -- component 0 alone, no chroma
+//     load, no triangle rule, no colour table (the planner laid out no chroma
+//     plane: hj_common.h idct_luma_only); an RGB-coded frame has no luma plane and
+//     takes rgb_gray_convert, whose tables are L24's constants.
+constexpr int kFmtL = 5, kFmtY = 6;  // SPDL_HJ_FMT_L / _Y (hj_host.cpp holds them to the header)
+
+// Pillow's L24 (Convert.c) and libjpeg's rgb_gray_convert: FIX(0.299),
+// FIX(0.587), FIX(0.114) at 16 bits, rounded
+__device__ __forceinline__ int luma_l24(int r, int g, int b) {
+  return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16;
+}
+
+// Whether this image's one channel is component 0 as it stands
+__device__ __forceinline__ bool luma_is_plane0(const ImageDesc& dd, const BatchParams& p) {
+  return dd.ncomp == 1 || (p.pix_fmt == kFmtY && dd.color != kColorRgb);
+}
+
+// One channel of a pixel from its three components' samples (not plane 0's case)
+__device__ __forceinline__ int luma_pixel(const ImageDesc& dd, int v0, int v1, int v2) {
+  int rgb[3];
+  if (dd.color == kColorRgb) {
+    rgb[0] = v0;
+    rgb[1] = v1;
+    rgb[2] = v2;
+  } else {
+    up::ycc_rgb(v0, v1, v2, rgb);
+  }
+  return luma_l24(rgb[0], rgb[1], rgb[2]);
+}
+
+// Component 0's samples x0 .. x0 + 7 of rows y0 and y0 + 1 by its ratio (hr,
+// vr): (1, 1) except in a draft frame whose luma is not its largest component
+__device__ __forceinline__ void luma_plane0(const uint8_t* __restrict__ planes, const ImageDesc& dd,
+                                            int hr, int vr, bool fancy, int x0, int y0,
+                                            int (&g)[2][8]) {
+  const int cw = dd.win_w[0], ch = dd.win_h[0];
+  up::run8x2(planes + dd.plane_off[0], dd.plane_stride[0], cw, ch, up::mode_of(hr, vr, cw, fancy),
+             hr, vr, x0, y0, g[0], g[1]);
+}
+
+// A lane's row segment of one channel: 8 pixels, npx of them inside the
+// frame, to row y from column x0.  u8: the 8 bytes are one 8-byte store at a
+// 4-byte aligned address, else up to 3 head bytes, one realigned dword and the
+// tail bytes; f16 / bf16: 16 bytes likewise.  A row's ragged last segment
+// (npx < 8) leaves as bytes, so a width of 33 or 1 writes nothing behind it.
+__device__ __forceinline__ void turbo_store_luma(void* out, int64_t base, const BatchParams& p,
+                                                 int W, int x0, int y, int npx, const int (&g)[8]) {
+  const int64_t at = (int64_t)y * W + x0;
+  if (p.dtype == 0) {
+    uint32_t b[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++)
+      b[h] = (uint32_t)g[4 * h] | (uint32_t)g[4 * h + 1] << 8 | (uint32_t)g[4 * h + 2] << 16 |
+             (uint32_t)g[4 * h + 3] << 24;
+    store_run<2>(static_cast<uint8_t*>(out) + base + at, b, npx);
+    return;
+  }
+  uint32_t b[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    b[k] = turbo_norm(g[2 * k], p.mean[0], p.std[0], p.dtype) |
+           turbo_norm(g[2 * k + 1], p.mean[0], p.std[0], p.dtype) << 16;
+  store_run<4>(static_cast<uint8_t*>(out) + (base + at) * 2, b, npx * 2);
+}
+
+// One channel of the frame's pixels x0 .. x0 + 7 of rows y0 and y0 + 1 (x0 a
+// multiple of 8 below the width, y0 even and below the height): the producer
+// of every one-channel kernel.  dr: the image's draft record (null: none)
+__device__ __forceinline__ void turbo_luma_samples(const uint8_t* __restrict__ planes,
+                                                   const ImageDesc& dd, const draft::Desc* dr,
+                                                   const BatchParams& p, int x0, int y0,
+                                                   int (&g)[2][8]) {
+  if (luma_is_plane0(dd, p)) {
+    // (a frame whose luma is not its largest component: the ratio that remains)
+    int hr = 1, vr = 1;
+    if (dr) {
+      hr = dr->hr[0];
+      vr = dr->vr[0];
+    } else if (dd.ncomp > 1) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        hr = max(hr, dd.h_samp[c]);
+        vr = max(vr, dd.v_samp[c]);
+      }
+      hr /= dd.h_samp[0];
+      vr /= dd.v_samp[0];
+    }
+    luma_plane0(planes, dd, hr, vr, !dr || dr->level != 3, x0, y0, g);
+  } else {
+    int v[3][2][8];
+    if (dr) turbo_samples_draft(planes, dd, *dr, x0, y0, v);
+    else turbo_samples(planes, dd, x0, y0, v);
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+      for (int k = 0; k < 8; k++) g[j][k] = luma_pixel(dd, v[0][j][k], v[1][j][k], v[2][j][k]);
+  }
+}
+
+// The luma path of a full-resolution tile's thread: rows y0 and y0 + 1 from
+// column x0
+__device__ __forceinline__ void turbo_luma_rows(const uint8_t* __restrict__ planes,
+                                                const ImageDesc& dd, const draft::Desc* dr,
+                                                void* out, const BatchParams& p, int x0, int y0) {
+  int g[2][8];
+  turbo_luma_samples(planes, dd, dr, p, x0, y0, g);
+  const int npx = min(8, dd.ow - x0);
+  turbo_store_luma(out, dd.out_off, p, dd.ow, x0, y0, npx, g[0]);
+  if (y0 + 1 < dd.oh) turbo_store_luma(out, dd.out_off, p, dd.ow, x0, y0 + 1, npx, g[1]);
+}
+
+template <int NCH>
 __global__ void __launch_bounds__(256) turbo_rgb_kernel(const uint8_t* __restrict__ planes,
                                                         const ImageDesc* __restrict__ desc,
                                                         const ImageInfo* __restrict__ infos,
@@ -6899,37 +7030,41 @@ __global__ void __launch_bounds__(256) turbo_rgb_kernel(const uint8_t* __restric
   const int x0 = tx * kTurboTileW + (tid & 15) * 8;
   const int y0 = ty * kTurboTileH + (tid >> 4) * 2;
   if (x0 >= W || y0 >= H) return;
-  // (from here to turbo_row: the same steps as turbo_samples below, which
-  // resample_kernel calls -- a change to the ratios or the per-component
-  // rule goes into both)
-  // the ratios, from the sampling factors the planner laid the planes out by
-  int hmax = 1, vmax = 1;
-  if (dd.ncomp > 1) {
+  if constexpr (NCH == 1) {
+    turbo_luma_rows(planes, dd, nullptr, out, p, x0, y0);
+  } else {
+    // (from here to turbo_row: the same steps as turbo_samples below, which
+    // resample_kernel calls -- a change to the ratios or the per-component
+    // rule goes into both)
+    // the ratios, from the sampling factors the planner laid the planes out by
+    int hmax = 1, vmax = 1;
+    if (dd.ncomp > 1) {
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-      hmax = max(hmax, dd.h_samp[c]);
-      vmax = max(vmax, dd.v_samp[c]);
-    }
-  }
-  int v[3][2][8];
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    if (c < dd.ncomp) {
-      const int hr = dd.ncomp > 1 ? hmax / dd.h_samp[c] : 1;
-      const int vr = dd.ncomp > 1 ? vmax / dd.v_samp[c] : 1;
-      const int cw = dd.win_w[c], ch = dd.win_h[c];
-      up::run8x2(planes + dd.plane_off[c], dd.plane_stride[c], cw, ch, up::mode_of(hr, vr, cw), hr,
-                 vr, x0, y0, v[c][0], v[c][1]);
-    } else {  // (gray: every channel is Y)
-#pragma unroll
-      for (int k = 0; k < 8; k++) {
-        v[c][0][k] = v[0][0][k];
-        v[c][1][k] = v[0][1][k];
+      for (int c = 0; c < 3; c++) {
+        hmax = max(hmax, dd.h_samp[c]);
+        vmax = max(vmax, dd.v_samp[c]);
       }
     }
+    int v[3][2][8];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      if (c < dd.ncomp) {
+        const int hr = dd.ncomp > 1 ? hmax / dd.h_samp[c] : 1;
+        const int vr = dd.ncomp > 1 ? vmax / dd.v_samp[c] : 1;
+        const int cw = dd.win_w[c], ch = dd.win_h[c];
+        up::run8x2(planes + dd.plane_off[c], dd.plane_stride[c], cw, ch, up::mode_of(hr, vr, cw), hr,
+                   vr, x0, y0, v[c][0], v[c][1]);
+      } else {  // (gray: every channel is Y)
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          v[c][0][k] = v[0][0][k];
+          v[c][1][k] = v[0][1][k];
+        }
+      }
+    }
+    turbo_row(out, dd, p, x0, y0, v[0][0], v[1][0], v[2][0]);
+    if (y0 + 1 < H) turbo_row(out, dd, p, x0, y0 + 1, v[0][1], v[1][1], v[2][1]);
   }
-  turbo_row(out, dd, p, x0, y0, v[0][0], v[1][0], v[2][0]);
-  if (y0 + 1 < H) turbo_row(out, dd, p, x0, y0 + 1, v[0][1], v[1][1], v[2][1]);
 }
 
 // ---------------------------------------------------------------------------
@@ -7037,6 +7172,7 @@ __device__ __forceinline__ void turbo_samples_draft(const uint8_t* __restrict__ 
 
 // turbo_rgb_kernel over a submission with draft levels: the same grid, tiles,
 // colour step and stores; an image of level 0 has ratios hmax / h_c in its record
+template <int NCH>
 __global__ void __launch_bounds__(256) turbo_rgb_draft_kernel(
     const uint8_t* __restrict__ planes, const ImageDesc* __restrict__ desc,
     const ImageInfo* __restrict__ infos, void* __restrict__ out, const BatchParams p,
@@ -7053,10 +7189,14 @@ __global__ void __launch_bounds__(256) turbo_rgb_draft_kernel(
   const int x0 = tx * kTurboTileW + (tid & 15) * 8;
   const int y0 = ty * kTurboTileH + (tid >> 4) * 2;
   if (x0 >= W || y0 >= H) return;
-  int v[3][2][8];
-  turbo_samples_draft(planes, dd, drafts[img], x0, y0, v);
-  turbo_row(out, dd, p, x0, y0, v[0][0], v[1][0], v[2][0]);
-  if (y0 + 1 < H) turbo_row(out, dd, p, x0, y0 + 1, v[0][1], v[1][1], v[2][1]);
+  if constexpr (NCH == 1) {
+    turbo_luma_rows(planes, dd, &drafts[img], out, p, x0, y0);
+  } else {
+    int v[3][2][8];
+    turbo_samples_draft(planes, dd, drafts[img], x0, y0, v);
+    turbo_row(out, dd, p, x0, y0, v[0][0], v[1][0], v[2][0]);
+    if (y0 + 1 < H) turbo_row(out, dd, p, x0, y0 + 1, v[0][1], v[1][1], v[2][1]);
+  }
 }
 
 __device__ __forceinline__ uint32_t rs_clip8(uint32_t acc) {
@@ -7064,9 +7204,21 @@ __device__ __forceinline__ uint32_t rs_clip8(uint32_t acc) {
   return (uint32_t)min(max(v, 0), 255);
 }
 
+// One tile of a one-channel resize (defined behind the items kernel's stages,
+// which it shares): what the <.., 1> instantiations of the three kernels run
+template <bool DRAFT, bool SUM>
+__device__ __forceinline__ void rs_luma_tile(uint32_t* rs_lds, const uint8_t* __restrict__ planes,
+                                             const ImageDesc& dd,
+                                             const draft::Desc* __restrict__ drafts, int img,
+                                             const int32_t* __restrict__ tables,
+                                             const rs::ResampleDesc& rd, const rs::ReduceDesc* rr,
+                                             int ow, int oh, int tx, int ty, int64_t base, int flip,
+                                             void* out, const BatchParams& p, int tid);
+
 // DRAFT: the frame is a draft frame (spdl_hj_set_draft; `drafts` its records,
-// null otherwise): the producer is turbo_samples_draft, everything else as it is
-template <bool DRAFT>
+// null otherwise): the producer is turbo_samples_draft, everything else as it is.
+// NCH: the output's channels -- 3 is the body as it stood, 1 rs_luma_tile
+template <bool DRAFT, int NCH>
 __global__ void __launch_bounds__(256) resample_kernel(const uint8_t* __restrict__ planes,
                                                        const ImageDesc* __restrict__ desc,
                                                        const ImageInfo* __restrict__ infos,
@@ -7084,8 +7236,13 @@ __global__ void __launch_bounds__(256) resample_kernel(const uint8_t* __restrict
   if (host_status && t == 0 && tid == 0) host_status[img] = in.status;
   if (in.status != kOk || dd.refuse) return;
   const rs::ResampleDesc rd = rdesc[img];
-  const rs::LdsLayout l = rs::lds_layout(rd);
   const int ty = t / dd.sws_chunks, tx = t - ty * dd.sws_chunks;
+  if constexpr (NCH == 1) {
+    rs_luma_tile<DRAFT, false>(rs_lds, planes, dd, drafts, img, tables, rd, nullptr, dd.ow, dd.oh,
+                               tx, ty, dd.out_off, 0, out, p, tid);
+    return;
+  }
+  const rs::LdsLayout l = rs::lds_layout(rd);
   const int ncol = min(rd.tw, dd.ow - tx * rd.tw), nrow = min(rd.th, dd.oh - ty * rd.th);
   // 1. the windows and the tile's coefficient rows
   const rs::Window wc =
@@ -7237,7 +7394,7 @@ __device__ __forceinline__ void reduce_add_row(uint32_t* srg, uint32_t* sb, cons
   }
 }
 
-template <bool DRAFT>
+template <bool DRAFT, int NCH>
 __global__ void __launch_bounds__(256) resample_reduce_kernel(
     const uint8_t* __restrict__ planes, const ImageDesc* __restrict__ desc,
     const ImageInfo* __restrict__ infos, const rs::ResampleDesc* __restrict__ rdesc,
@@ -7253,8 +7410,13 @@ __global__ void __launch_bounds__(256) resample_reduce_kernel(
   if (in.status != kOk || dd.refuse) return;
   const rs::ResampleDesc rd = rdesc[img];
   const rs::ReduceDesc rr = reduce[img];
-  const rs::LdsLayout l = rs::lds_layout(rd);
   const int ty = t / dd.sws_chunks, tx = t - ty * dd.sws_chunks;
+  if constexpr (NCH == 1) {
+    rs_luma_tile<DRAFT, true>(rs_lds, planes, dd, drafts, img, tables, rd, &rr, dd.ow, dd.oh, tx, ty,
+                              dd.out_off, 0, out, p, tid);
+    return;
+  }
+  const rs::LdsLayout l = rs::lds_layout(rd);
   const int ncol = min(rd.tw, dd.ow - tx * rd.tw), nrow = min(rd.th, dd.oh - ty * rd.th);
   // 1. the windows, in cells, and the tile's coefficient rows
   const rs::Window wc = rs::tile_window(tables + rd.hx, tables + rd.hn, 0, rd.ox, dd.ow, rd.tw, tx, 1);
@@ -7640,7 +7802,190 @@ __device__ __forceinline__ void rs_strips_sum(const uint8_t* __restrict__ planes
   }
 }
 
+// ---- the one-channel resize (spdl_hipjpeg.h "Pillow-exact grayscale") ----
+// The three kernels' <.., 1> instantiations: the same grid, windows, tables and
+// coefficient rows, one channel through both passes.  A pixel is a BYTE in
+// the strip and in the intermediate (rs::lds_layout(rd, 1)): the producer ends
+// in turbo_luma_samples' one value a pixel and writes its 8 pixels of a strip
+// row as two words; the horizontal pass reads bytes along the strip's rows (a
+// row's pitch is an odd number of words: the lanes of a column on distinct
+// banks, as with three channels) and writes the rounded byte; the vertical
+// pass reads 8 bytes a tap and stores through turbo_store_luma.  With cell
+// sums (SUM) the strip is one word a cell -- the 16-bit sum, divided in place
+// into the pixel -- on the three-channel pitch, and there is no second plane.
+
+// Columns [klo, khi) of a unit's row into the cells of one strip row
+__device__ __forceinline__ void luma_add_row(uint32_t* s, const uint32_t (&v)[8], int klo, int khi,
+                                             int cx, int rem, int fx) {
+  uint32_t a = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    if (k >= klo && k < khi) {
+      a += v[k];
+      if (++rem == fx || k == khi - 1) {
+        atomicAdd(s + cx, a);
+        a = 0;
+        rem = 0;
+        cx++;
+      }
+    }
+  }
+}
+
+// The horizontal pass over a strip of srows rows into rows row0 .. of the byte
+// intermediate.  WORDS: the strip holds a word a pixel (the cell sums' strip)
+template <bool WORDS>
+__device__ __forceinline__ void luma_hpass(const int32_t* lds, const rs::LdsLayout& l,
+                                           const rs::ResampleDesc& rd, const uint32_t* strip,
+                                           uint8_t* inter, int ncol, int srows, int row0, int tid) {
+  const int sr_shift = __builtin_ctz((unsigned)rd.sr);
+  for (int i = tid; i < (ncol << sr_shift); i += 256) {
+    const int row = i & (rd.sr - 1), col = i >> sr_shift;
+    if (row >= srows) continue;
+    const int n = lds[l.hn + col], x = lds[l.hx + col];
+    const int32_t* kk = lds + l.hk + col * rd.kh;
+    uint32_t a = 1u << (rs::kCoefBits - 1);
+    if constexpr (WORDS) {
+      const uint32_t* px = strip + row * rd.pitch + x;
+      for (int k = 0; k < n; k++) a += (uint32_t)kk[k] * px[k];
+    } else {
+      const uint8_t* px = reinterpret_cast<const uint8_t*>(strip + row * rd.pitch) + x;
+      for (int k = 0; k < n; k++) a += (uint32_t)kk[k] * px[k];
+    }
+    inter[(row0 + row) * rd.tw + col] = (uint8_t)rs_clip8(a);
+  }
+}
+
 template <bool DRAFT, bool SUM>
+__device__ __forceinline__ void rs_luma_tile(uint32_t* rs_lds, const uint8_t* __restrict__ planes,
+                                             const ImageDesc& dd,
+                                             const draft::Desc* __restrict__ drafts, int img,
+                                             const int32_t* __restrict__ tables,
+                                             const rs::ResampleDesc& rd, const rs::ReduceDesc* rr,
+                                             int ow, int oh, int tx, int ty, int64_t base, int flip,
+                                             void* out, const BatchParams& p, int tid) {
+  const rs::LdsLayout l = rs::lds_layout(rd, 1);
+  const int ncol = min(rd.tw, ow - tx * rd.tw), nrow = min(rd.th, oh - ty * rd.th);
+  const int hcol0 = rd.ox + tx * rd.tw, vrow0 = rd.oy + ty * rd.th;
+  int32_t* const lds = reinterpret_cast<int32_t*>(rs_lds);
+  uint32_t* const strip = rs_lds + l.strip;
+  uint8_t* const inter = reinterpret_cast<uint8_t*>(rs_lds + l.inter);
+  const draft::Desc* dr = nullptr;
+  if constexpr (DRAFT) dr = &drafts[img];
+  if constexpr (SUM) {
+    // the windows in cells of the reduced picture (no alignment)
+    const rs::Window wc = rs::tile_window(tables + rd.hx, tables + rd.hn, 0, rd.ox, ow, rd.tw, tx, 1);
+    const rs::Window wr = rs::tile_window(tables + rd.vx, tables + rd.vn, 0, rd.oy, oh, rd.th, ty, 1);
+    rs_stage_rows(lds, l, tables, rd, hcol0, vrow0, ncol, nrow, -wc.lo, -wr.lo, tid);
+    const int c0 = wc.lo, ncell = wc.hi - wc.lo, r0 = wr.lo, r1 = wr.hi;
+    const int X0 = rr->qx + c0 * rr->fx, X1 = min(rr->qx + (c0 + ncell) * rr->fx, rr->qx + rr->qw);
+    const int ux0 = X0 >> 3, units_x = ((X1 + 7) >> 3) - ux0;
+    for (int s0 = r0; s0 < r1; s0 += rd.sr) {
+      const int srows = min(rd.sr, r1 - s0);
+      const int Y0 = rr->qy + s0 * rr->fy;
+      const int Y1 = min(rr->qy + (s0 + srows) * rr->fy, rr->qy + rr->qh);
+      const int uy0 = Y0 >> 1, units = units_x * (((Y1 + 1) >> 1) - uy0);
+      __syncthreads();  // (the coefficient rows stand; the last strip is consumed)
+      for (int i = tid; i < srows * rd.pitch; i += 256) strip[i] = 0;
+      __syncthreads();
+      for (int u = tid; u < units; u += 256) {
+        const int uy = u / units_x, ux = u - uy * units_x;
+        const int x0 = (ux0 + ux) * 8, y0 = (uy0 + uy) * 2;
+        int g[2][8];
+        turbo_luma_samples(planes, dd, dr, p, x0, y0, g);
+        uint32_t v[2][8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          v[0][k] = (uint32_t)g[0][k];
+          v[1][k] = (uint32_t)g[1][k];
+        }
+        // the unit's columns and rows inside the source rectangle, and their cells
+        const int klo = max(X0 - x0, 0), khi = min(X1 - x0, 8);
+        const int cx = (x0 + klo - rr->qx) / rr->fx, rem = (x0 + klo - rr->qx) - cx * rr->fx;
+        const bool ok0 = y0 >= Y0, ok1 = y0 + 1 < Y1;  // (y0 < Y1 and y0 + 1 >= Y0 by the units)
+        const int cy0 = (y0 - rr->qy) / rr->fy - s0, cy1 = (y0 + 1 - rr->qy) / rr->fy - s0;
+        if (ok0 && ok1 && cy0 == cy1) {
+#pragma unroll
+          for (int k = 0; k < 8; k++) v[0][k] += v[1][k];
+          luma_add_row(strip + cy0 * rd.pitch, v[0], klo, khi, cx - c0, rem, rr->fx);
+        } else {
+          if (ok0) luma_add_row(strip + cy0 * rd.pitch, v[0], klo, khi, cx - c0, rem, rr->fx);
+          if (ok1) luma_add_row(strip + cy1 * rd.pitch, v[1], klo, khi, cx - c0, rem, rr->fx);
+        }
+      }
+      __syncthreads();
+      for (int i = tid; i < srows * ncell; i += 256) {
+        const int row = i / ncell, col = i - row * ncell;
+        const bool right = c0 + col == rr->cw - 1, bottom = s0 + row == rr->ch - 1;
+        const uint32_t amend = bottom ? (right ? rr->amend[3] : rr->amend[2])
+                                      : (right ? rr->amend[1] : rr->amend[0]);
+        const uint32_t mult = bottom ? (right ? rr->mult[3] : rr->mult[2])
+                                     : (right ? rr->mult[1] : rr->mult[0]);
+        strip[row * rd.pitch + col] = ((strip[row * rd.pitch + col] + amend) * mult) >> 24;
+      }
+      __syncthreads();
+      luma_hpass<true>(lds, l, rd, strip, inter, ncol, srows, s0 - r0, tid);
+    }
+  } else {
+    // the windows in the frame, from the box's origin, on the producer's units
+    const rs::Window wc =
+        rs::tile_window(tables + rd.hx, tables + rd.hn, rd.bx, rd.ox, ow, rd.tw, tx, 8);
+    const rs::Window wr =
+        rs::tile_window(tables + rd.vx, tables + rd.vn, rd.by, rd.oy, oh, rd.th, ty, 2);
+    rs_stage_rows(lds, l, tables, rd, hcol0, vrow0, ncol, nrow, rd.bx - wc.lo, rd.by - wr.lo, tid);
+    const int c0 = wc.lo, units_x = (wc.hi - wc.lo + 7) >> 3, r0 = wr.lo, r1 = wr.hi;
+    for (int s0 = r0; s0 < r1; s0 += rd.sr) {
+      const int srows = min(rd.sr, r1 - s0);
+      __syncthreads();  // (the coefficient rows stand; the last strip is consumed)
+      const int units = units_x * ((srows + 1) >> 1);
+      for (int u = tid; u < units; u += 256) {
+        const int uy = u / units_x, ux = u - uy * units_x;
+        int g[2][8];
+        turbo_luma_samples(planes, dd, dr, p, c0 + 8 * ux, s0 + 2 * uy, g);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          uint32_t* q = strip + (2 * uy + j) * rd.pitch + 2 * ux;  // (8 bytes: two words)
+          q[0] = (uint32_t)g[j][0] | (uint32_t)g[j][1] << 8 | (uint32_t)g[j][2] << 16 |
+                 (uint32_t)g[j][3] << 24;
+          q[1] = (uint32_t)g[j][4] | (uint32_t)g[j][5] << 8 | (uint32_t)g[j][6] << 16 |
+                 (uint32_t)g[j][7] << 24;
+        }
+      }
+      __syncthreads();
+      luma_hpass<false>(lds, l, rd, strip, inter, ncol, srows, s0 - r0, tid);
+    }
+  }
+  __syncthreads();
+  // the vertical pass, the flip and the store: a thread 8 columns of a row
+  const int groups = (ncol + 7) >> 3;
+  for (int i = tid; i < groups * nrow; i += 256) {
+    const int y = i / groups, g = i - y * groups;
+    const int x = tx * rd.tw + 8 * g, npx = min(8, ow - x);
+    const uint8_t* px = inter + lds[l.vx + y] * rd.tw + 8 * g;
+    const int32_t* kk = lds + l.vk + y * rd.kv;
+    const int n = lds[l.vn + y];
+    uint32_t a[8];
+    int cj[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      cj[j] = flip & 1 ? max(npx - 1 - j, 0) : j;  // (a mirrored group leaves in written order)
+      a[j] = 1u << (rs::kCoefBits - 1);
+    }
+    for (int k = 0; k < n; k++) {
+      const uint32_t w = (uint32_t)kk[k];
+#pragma unroll
+      for (int j = 0; j < 8; j++) a[j] += w * px[k * rd.tw + cj[j]];
+    }
+    int v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = (int)rs_clip8(a[j]);
+    const int yy = ty * rd.th + y;
+    turbo_store_luma(out, base, p, ow, flip & 1 ? ow - x - npx : x, flip & 2 ? oh - 1 - yy : yy, npx,
+                     v);
+  }
+}
+
+template <bool DRAFT, bool SUM, int NCH>
 __global__ void __launch_bounds__(256) resample_items_kernel(
     const uint8_t* __restrict__ planes, const ImageDesc* __restrict__ desc,
     const ImageInfo* __restrict__ infos, const rs::ItemDesc* __restrict__ items,
@@ -7660,9 +8005,15 @@ __global__ void __launch_bounds__(256) resample_items_kernel(
   if (infos[img].status != kOk) return;  // (a failed image's items stay untouched)
   const ImageDesc& dd = desc[img];
   const rs::ResampleDesc rd = it.rd;
-  const rs::LdsLayout l = rs::lds_layout(rd);
   const int t = (int)blockIdx.x - it.wg0;
   const int ty = t / it.chunks, tx = t - ty * it.chunks;
+  if constexpr (NCH == 1) {
+    rs_luma_tile<DRAFT, SUM>(rs_lds, planes, dd, drafts, img, tables, rd, &it.rr, it.ow, it.oh, tx,
+                             ty, (int64_t)((uint64_t)it.off_hi << 32 | it.off_lo), it.flip, out, p,
+                             tid);
+    return;
+  }
+  const rs::LdsLayout l = rs::lds_layout(rd);
   const int ncol = min(rd.tw, it.ow - tx * rd.tw), nrow = min(rd.th, it.oh - ty * rd.th);
   const int hcol0 = rd.ox + tx * rd.tw, vrow0 = rd.oy + ty * rd.th;
   int32_t* const lds = reinterpret_cast<int32_t*>(rs_lds);
@@ -7805,22 +8156,33 @@ hipError_t launch_csc(const BatchBuffers& b, void* out, const BatchParams& p, in
 }
 hipError_t launch_turbo_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int turbo_wgs,
                             int32_t* host_status, hipStream_t st) {
-  if (b.draft)
-    hipLaunchKernelGGL(turbo_rgb_draft_kernel, dim3(turbo_wgs), dim3(256), 0, st, b.planes, b.desc,
+  // (the channel count is the format's: L and Y have one, the instantiation of their own)
+  const bool luma = p.pix_fmt == kFmtL || p.pix_fmt == kFmtY;
+  if (b.draft && luma)
+    hipLaunchKernelGGL(turbo_rgb_draft_kernel<1>, dim3(turbo_wgs), dim3(256), 0, st, b.planes, b.desc,
                        b.infos, out, p, host_status, b.sws_map, b.draft);
+  else if (b.draft)
+    hipLaunchKernelGGL(turbo_rgb_draft_kernel<3>, dim3(turbo_wgs), dim3(256), 0, st, b.planes, b.desc,
+                       b.infos, out, p, host_status, b.sws_map, b.draft);
+  else if (luma)
+    hipLaunchKernelGGL(turbo_rgb_kernel<1>, dim3(turbo_wgs), dim3(256), 0, st, b.planes, b.desc,
+                       b.infos, out, p, host_status, b.sws_map);
   else
-    hipLaunchKernelGGL(turbo_rgb_kernel, dim3(turbo_wgs), dim3(256), 0, st, b.planes, b.desc, b.infos,
-                       out, p, host_status, b.sws_map);
+    hipLaunchKernelGGL(turbo_rgb_kernel<3>, dim3(turbo_wgs), dim3(256), 0, st, b.planes, b.desc,
+                       b.infos, out, p, host_status, b.sws_map);
   return hipGetLastError();
 }
 hipError_t launch_resample(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
                            int lds_bytes, int32_t* host_status, hipStream_t st) {
-  if (b.draft)
-    hipLaunchKernelGGL(resample_kernel<true>, dim3(wgs), dim3(256), lds_bytes, st, b.planes, b.desc,
-                       b.infos, b.resample, b.wts, out, p, host_status, b.sws_map, b.draft);
-  else
-    hipLaunchKernelGGL(resample_kernel<false>, dim3(wgs), dim3(256), lds_bytes, st, b.planes, b.desc,
-                       b.infos, b.resample, b.wts, out, p, host_status, b.sws_map, b.draft);
+  const bool luma = p.pix_fmt == kFmtL || p.pix_fmt == kFmtY;
+#define HJ_RS(D, N)                                                                               \
+  hipLaunchKernelGGL((resample_kernel<D, N>), dim3(wgs), dim3(256), lds_bytes, st, b.planes, b.desc, \
+                     b.infos, b.resample, b.wts, out, p, host_status, b.sws_map, b.draft)
+  if (b.draft && luma) HJ_RS(true, 1);
+  else if (b.draft) HJ_RS(true, 3);
+  else if (luma) HJ_RS(false, 1);
+  else HJ_RS(false, 3);
+#undef HJ_RS
   return hipGetLastError();
 }
 hipError_t launch_rgb_unscaled(const BatchBuffers& b, void* out, const BatchParams& p,
@@ -7838,23 +8200,32 @@ static void launch_hscale(const BatchBuffers& b, int hs_wgs, hipStream_t st) {
 }
 hipError_t launch_resample_reduce(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
                                   int lds_bytes, int32_t* host_status, hipStream_t st) {
-  if (b.draft)
-    hipLaunchKernelGGL(resample_reduce_kernel<true>, dim3(wgs), dim3(256), lds_bytes, st, b.planes,
-                       b.desc, b.infos, b.resample, b.reduce, b.wts, out, p, host_status, b.sws_map,
-                       b.draft);
-  else
-    hipLaunchKernelGGL(resample_reduce_kernel<false>, dim3(wgs), dim3(256), lds_bytes, st, b.planes,
-                       b.desc, b.infos, b.resample, b.reduce, b.wts, out, p, host_status, b.sws_map,
-                       b.draft);
+  const bool luma = p.pix_fmt == kFmtL || p.pix_fmt == kFmtY;
+#define HJ_RR(D, N)                                                                                \
+  hipLaunchKernelGGL((resample_reduce_kernel<D, N>), dim3(wgs), dim3(256), lds_bytes, st, b.planes, \
+                     b.desc, b.infos, b.resample, b.reduce, b.wts, out, p, host_status, b.sws_map, \
+                     b.draft)
+  if (b.draft && luma) HJ_RR(true, 1);
+  else if (b.draft) HJ_RR(true, 3);
+  else if (luma) HJ_RR(false, 1);
+  else HJ_RR(false, 3);
+#undef HJ_RR
   return hipGetLastError();
 }
 hipError_t launch_resample_items(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
                                  bool sum, int lds_bytes, int32_t* host_status, hipStream_t st) {
   const int tiles = wgs - (b.n + 255) / 256;
 #define HJ_ITEMS(D, S)                                                                           \
-  hipLaunchKernelGGL((resample_items_kernel<D, S>), dim3(wgs), dim3(256), lds_bytes, st, b.planes, \
-                     b.desc, b.infos, b.items, b.item_map, b.wts, out, p, host_status, b.draft,  \
-                     tiles)
+  do {                                                                                            \
+    if (p.pix_fmt == kFmtL || p.pix_fmt == kFmtY)                                                 \
+      hipLaunchKernelGGL((resample_items_kernel<D, S, 1>), dim3(wgs), dim3(256), lds_bytes, st,   \
+                         b.planes, b.desc, b.infos, b.items, b.item_map, b.wts, out, p,           \
+                         host_status, b.draft, tiles);                                            \
+    else                                                                                          \
+      hipLaunchKernelGGL((resample_items_kernel<D, S, 3>), dim3(wgs), dim3(256), lds_bytes, st,   \
+                         b.planes, b.desc, b.infos, b.items, b.item_map, b.wts, out, p,           \
+                         host_status, b.draft, tiles);                                            \
+  } while (0)
   if (b.draft && sum) HJ_ITEMS(true, true);
   else if (b.draft) HJ_ITEMS(true, false);
   else if (sum) HJ_ITEMS(false, true);

@@ -96,7 +96,9 @@ bool valid_output(const spdl_hj_output* o) {
   if (o && o->pix_fmt == SPDL_HJ_FMT_YUV &&
       (o->dtype != SPDL_HJ_DTYPE_U8 || o->csc != SPDL_HJ_CSC_SWSCALE))
     return false;
-  return o && o->pix_fmt >= 0 && o->pix_fmt <= SPDL_HJ_FMT_YUV && (o->dtype >= 0 && o->dtype <= 2) &&
+  // ... and the one-channel formats are libjpeg-turbo's and Pillow's: csc TURBO alone
+  if (o && output_channels(*o) == 1 && o->csc != SPDL_HJ_CSC_TURBO) return false;
+  return o && o->pix_fmt >= 0 && o->pix_fmt <= SPDL_HJ_FMT_Y && (o->dtype >= 0 && o->dtype <= 2) &&
          (o->idct == 0 || o->idct == 1) && (o->filter >= 0 && o->filter <= 2) &&
          o->aspect >= 0 && o->aspect <= 2 &&
          (o->csc == SPDL_HJ_CSC_SWSCALE ||
@@ -198,7 +200,7 @@ bool refused_alone(bool view, const Placement& pl) {
 // is refused.  The planner's and resample_items_check's.
 const char* place_items(const ResampleRequest& r, const std::vector<int>& fw,
                         const std::vector<int>& fh, int64_t esz, int64_t out_bytes, Layout& L,
-                        ResamplePool& pool, std::vector<int32_t>& status) {
+                        ResamplePool& pool, std::vector<int32_t>& status, int channels) {
   const int n = (int)fw.size();
   if (r.n_items < 0 || (r.n_items > 0 && !r.list)) return "spdl_hj_set_resample_items: no items";
   if (r.filter < 0 || r.filter > SPDL_HJ_FILTER_LANCZOS)
@@ -216,7 +218,7 @@ const char* place_items(const ResampleRequest& r, const std::vector<int>& fw,
     if (status[k] == SPDL_HJ_ERR_INVALID_ARG)
       return "spdl_hj_set_resample_items: an item's flip, box or output size is invalid";
     sum = sum || any;
-    const int64_t extent = (int64_t)it.out_w * it.out_h * 3 * esz;
+    const int64_t extent = (int64_t)it.out_w * it.out_h * channels * esz;
     if (it.offset < 0 || it.offset % esz || it.offset > out_bytes || extent > out_bytes - it.offset)
       return "spdl_hj_set_resample_items: an item reaches past the output buffer, or its offset "
              "is no multiple of the element size";
@@ -249,7 +251,8 @@ const char* place_items(const ResampleRequest& r, const std::vector<int>& fw,
     rec.off_lo = (uint32_t)elem;
     rec.off_hi = (uint32_t)(elem >> 32);
     L.resample_lds =
-        std::max(L.resample_lds, (sum ? rs::reduce_lds_words(rec.rd) : rs::lds_layout(rec.rd).words) * 4);
+        std::max(L.resample_lds, (sum ? rs::reduce_lds_words(rec.rd, channels)
+                                      : rs::lds_layout(rec.rd, channels).words) * 4);
     L.item_map.insert(L.item_map.end(), (size_t)tiles, (uint32_t)L.items.size());
     L.items.push_back(rec);
   }
@@ -327,6 +330,14 @@ struct Planner {
     }
   }
 
+  // SPDL_HJ_FMT_Y of a YCbCr frame (spdl_hipjpeg.h "Pillow-exact grayscale"):
+  // component 0 is the whole output, so it alone is laid out and transformed.
+  // (An RGB-coded frame's gray takes its three planes; valid_output holds the
+  // format to csc = TURBO, which has neither crops, views nor lowres levels.)
+  bool luma_only(const spdl_hj_image_info& p) const {
+    return rq.plans && rq.out->pix_fmt == SPDL_HJ_FMT_Y && p.ncomp == 3 && p.color != kColorRgb;
+  }
+
   // d's workgroups in the flat IDCT grid, in image order (d.idct_blocks is set)
   void idct_share(ImageDesc& d) {
     if (d.idct_blocks > L.max_blocks) L.max_blocks = d.idct_blocks;
@@ -340,6 +351,7 @@ struct Planner {
   void front_end(int i, const FrameBlocks& fb, int lv, const draft::Desc* dr = nullptr) {
     ImageDesc& d = L.desc[i];
     const spdl_hj_image_info& p = rq.infos[i];
+    const bool luma = luma_only(p);
     const int64_t bytes = rq.sizes[i];
     d.in_off = rq.offsets[i];
     d.in_size = bytes;
@@ -347,6 +359,13 @@ struct Planner {
     d.coef_off = L.total_blocks;
     L.total_blocks += fb.nblocks;
     for (int c = 0; c < p.ncomp; c++) {
+      // (SPDL_HJ_FMT_Y: a chroma component has no plane -- stride 0 is how the
+      // IDCT kernels know, hj_common.h idct_luma_only)
+      if (luma && c > 0) {
+        d.plane_stride[c] = 0;
+        d.plane_off[c] = 0;
+        continue;
+      }
       // (a reduced plane: 8 >> L samples a block, each row padded to 8 bytes
       // a lane of idct_lowres_kernel, which writes the padding as well)
       d.plane_stride[c] = lv ? lowres_lanes_row(fb.bw[c], lv) * 8 : fb.bw[c] * 8;
@@ -561,6 +580,8 @@ struct Planner {
     const bool has_rect = rq.crops && !rect_is_none(rq.crops[i]);
     int crop_rc = SPDL_HJ_OK;
     d.idct_blocks = (int)fb.nblocks;
+    const int idct_comps = luma_only(p) ? 1 : p.ncomp;  // (the components with a plane)
+    if (idct_comps < p.ncomp) d.idct_blocks = fb.bw[0] * fb.bh[0];
     d.src = i;
     // Reduced-size decode: every later step sees the frame FFmpeg's decoder
     // emits at this level, and the IDCT stage is counted in lanes
@@ -581,7 +602,8 @@ struct Planner {
       dr = &L.draft[i];
       if (dr->level) {
         d.idct_blocks = 0;
-        for (int c = 0; c < p.ncomp; c++) d.idct_blocks += draft_lanes(fb.bw[c], fb.bh[c], dr->pc[c]);
+        // (idct_draft_kernel counts its lanes component by component, 0 first)
+        for (int c = 0; c < idct_comps; c++) d.idct_blocks += draft_lanes(fb.bw[c], fb.bh[c], dr->pc[c]);
         L.draft_images++;
       }
     }
@@ -1002,8 +1024,9 @@ struct Planner {
       return rc;
     }
     L.resample[i] = t;
-    L.resample_lds = std::max(L.resample_lds, (L.reduce.empty() ? rs::lds_layout(t).words
-                                                                : rs::reduce_lds_words(t)) * 4);
+    const int nch = output_channels(*rq.out);
+    L.resample_lds = std::max(L.resample_lds, (L.reduce.empty() ? rs::lds_layout(t, nch).words
+                                                                : rs::reduce_lds_words(t, nch)) * 4);
     d.sws_wg0 = (int32_t)L.sws_wgs;
     d.sws_bands = bands;
     d.sws_chunks = chunks;
@@ -1018,7 +1041,8 @@ struct Planner {
     std::vector<int32_t> status;
     const int64_t esz = rq.out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
     if (const char* what =
-            place_items(r, item_fw, item_fh, esz, rq.out_bytes, L, rs_pool, status)) {
+            place_items(r, item_fw, item_fh, esz, rq.out_bytes, L, rs_pool, status,
+                        output_channels(*rq.out))) {
       res.rc = SPDL_HJ_ERR_INVALID_ARG;
       snprintf(res.err, sizeof(res.err), "%s", what);
       return res.rc;
@@ -1069,7 +1093,7 @@ struct Planner {
     const int64_t esz = rq.out->dtype == SPDL_HJ_DTYPE_U8 ? 1 : 2;
     for (int i = 0; i < n; i++) {
       ImageDesc& d = L.desc[i];
-      const int64_t extent = (int64_t)d.ow * d.oh * 3 * esz;  // (a refused image: none)
+      const int64_t extent = (int64_t)d.ow * d.oh * output_channels(*rq.out) * esz;  // (a refused image: none)
       if (rq.ragged[i] > rq.out_bytes || extent > rq.out_bytes - rq.ragged[i]) {
         res.rc = SPDL_HJ_ERR_INVALID_ARG;
         res.image = i;
@@ -1101,7 +1125,7 @@ struct Planner {
     const int n = rq.n;
     L.ow = size.ow;
     L.oh = size.oh;
-    L.out_elems_per_image = (int64_t)L.ow * L.oh * 3;
+    L.out_elems_per_image = (int64_t)L.ow * L.oh * output_channels(*rq.out);
     if (rq.out->pix_fmt == SPDL_HJ_FMT_YUV)  // Y, then U and V of ceil(ow / hs) x ceil(oh / vs) (gray: Y alone)
       L.out_elems_per_image =
           (int64_t)L.ow * L.oh + (L.yuv_gray ? 0
@@ -1218,7 +1242,7 @@ int ragged_layout(const spdl_hj_image_info* infos, int n, const spdl_hj_output* 
     ow[i] = fw;
     oh[i] = fh;
     offsets[i] = round_up(end, align_bytes);
-    end = offsets[i] + (int64_t)fw * fh * 3 * esz;
+    end = offsets[i] + (int64_t)fw * fh * output_channels(*out) * esz;
   }
   offsets[n] = end;
   return SPDL_HJ_OK;

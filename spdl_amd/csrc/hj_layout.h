@@ -34,6 +34,11 @@ struct Geom {
 int geometry(int w, int h, const spdl_hj_output* o, Geom* g, int hs = 1, int vs = 1);
 
 bool valid_output(const spdl_hj_output* o);
+// Elements per pixel of a packed or planar RGB output (3) or of the one-channel
+// formats SPDL_HJ_FMT_L / _Y (1): what every output size and ragged box counts by
+inline int output_channels(const spdl_hj_output& o) {
+  return o.pix_fmt == SPDL_HJ_FMT_L || o.pix_fmt == SPDL_HJ_FMT_Y ? 1 : 3;
+}
 
 // The rectangle rules (chroma shifts, the source crop's rounding) are pure
 // arithmetic shared with views: hj_views.h.
@@ -265,7 +270,7 @@ struct ResampleRequest {
 struct Layout;
 const char* place_items(const ResampleRequest& r, const std::vector<int>& fw,
                         const std::vector<int>& fh, int64_t esz, int64_t out_bytes, Layout& L,
-                        ResamplePool& pool, std::vector<int32_t>& status);
+                        ResamplePool& pool, std::vector<int32_t>& status, int channels = 3);
 // spdl_hj_resample_items_check (spdl_hipjpeg.h): the items of a request held
 // against n probed images as the planner holds them, without a device
 int resample_items_check(const spdl_hj_image_info* infos, int n, const uint8_t* draft,

@@ -168,8 +168,10 @@ int resolve(const spdl_hj_resample_item* it, int W, int H, int out_w, int out_h,
 namespace {
 // tile() for either kernel.  reduce: resample_reduce_kernel's -- windows
 // unaligned, the LDS with the second sums' plane
-int tile_for(bool reduce, const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h,
+int tile_for(bool reduce, int nch, const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h,
              ResampleDesc* d, int* bands, int* chunks) {
+  const int tile_w = nch == 1 ? kTileW1 : kTileW;
+  const int sum_planes = nch == 1 ? 0 : 1;  // (planes of sums beside the strip)
   const int ax = reduce ? 1 : 8, ay = reduce ? 1 : 2;
   ResampleDesc t{};
   t.bx = g.bx;
@@ -178,8 +180,8 @@ int tile_for(bool reduce, const Axis& H, const Axis& V, const Geo& g, int out_w,
   t.oy = g.oy;
   t.kh = H.ksize;
   t.kv = V.ksize;
-  t.tw = 8;  // (8, 16, 32 or 64: halving keeps it a multiple of the store's 8 columns)
-  while (t.tw < kTileW && t.tw < out_w) t.tw *= 2;
+  t.tw = 8;  // (8, 16, 32, 64 or 128: halving keeps it a multiple of the store's 8 columns)
+  while (t.tw < tile_w && t.tw < out_w) t.tw *= 2;
   t.th = kTileH;
   while (t.th > 1 && t.th / 2 >= out_h) t.th /= 2;
   t.sr = kStripRows;
@@ -196,10 +198,11 @@ int tile_for(bool reduce, const Axis& H, const Axis& V, const Geo& g, int out_w,
       rows = std::max(rows, w.hi - w.lo);
     }
     while (t.sr > 2 && t.sr / 2 >= rows) t.sr /= 2;  // (no strip taller than the window)
-    t.pitch = ((cols + 7) & ~7) | 1;
+    // (one channel, no sums: a strip row of bytes, 8 columns are two words)
+    t.pitch = nch == 1 && !reduce ? (((cols + 7) >> 3) << 1) | 1 : ((cols + 7) & ~7) | 1;
     t.rows = rows;
-    LdsLayout l = lds_layout(t);
-    if (reduce) l.words = reduce_lds_words(t);
+    LdsLayout l = lds_layout(t, nch);
+    if (reduce) l.words = reduce_lds_words(t, nch);
     if (l.words * 4 <= kLdsBudget) {
       *d = t;
       *bands = ny;
@@ -209,7 +212,7 @@ int tile_for(bool reduce, const Axis& H, const Axis& V, const Geo& g, int out_w,
     // shrink what takes the most: the strip by its rows (down to 16: a wave's
     // lanes run along them) and then by the tile's columns, the intermediate
     // and the coefficient rows by the tile's rows first
-    const int strip = (reduce ? 2 : 1) * t.sr * t.pitch, rest = l.words - strip;
+    const int strip = (reduce ? 1 + sum_planes : 1) * t.sr * t.pitch, rest = l.words - strip;
     if (strip >= rest) {
       if (t.sr > 16) t.sr /= 2;
       else if (t.tw > 8) t.tw /= 2;
@@ -230,12 +233,12 @@ int tile_for(bool reduce, const Axis& H, const Axis& V, const Geo& g, int out_w,
 }  // namespace
 
 int tile(const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h, ResampleDesc* d,
-         int* bands, int* chunks) {
-  return tile_for(false, H, V, g, out_w, out_h, d, bands, chunks);
+         int* bands, int* chunks, int nch) {
+  return tile_for(false, nch, H, V, g, out_w, out_h, d, bands, chunks);
 }
 int tile_reduce(const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h, ResampleDesc* d,
-                int* bands, int* chunks) {
-  return tile_for(true, H, V, g, out_w, out_h, d, bands, chunks);
+                int* bands, int* chunks, int nch) {
+  return tile_for(true, nch, H, V, g, out_w, out_h, d, bands, chunks);
 }
 
 int place(AxisCache& cache, int filter, const spdl_hj_resample_item* it, int W, int H, int out_w,
@@ -247,7 +250,7 @@ int place(AxisCache& cache, int filter, const spdl_hj_resample_item* it, int W, 
   if (!out->H) return rc;
   out->V = cache.get(g.bh, g.rh, filter, &rc);
   if (!out->V) return rc;
-  return tile(*out->H, *out->V, g, out_w, out_h, &out->d, &out->bands, &out->chunks);
+  return tile(*out->H, *out->V, g, out_w, out_h, &out->d, &out->bands, &out->chunks, cache.channels);
 }
 
 namespace {
@@ -373,8 +376,8 @@ int place_box_into(void* cache, int filter, double gap, const spdl_hj_resample_b
   if (!pl.V) return rc;
   // (the tables' xmin is absolute in the picture: the kernels' box origin is 0)
   const Geo g{0, 0, b.cw, b.ch, b.rw, b.rh, b.ox, b.oy};
-  rc = red ? tile_reduce(*pl.H, *pl.V, g, out_w, out_h, &pl.d, &pl.bands, &pl.chunks)
-           : tile(*pl.H, *pl.V, g, out_w, out_h, &pl.d, &pl.bands, &pl.chunks);
+  rc = red ? tile_reduce(*pl.H, *pl.V, g, out_w, out_h, &pl.d, &pl.bands, &pl.chunks, ac.channels)
+           : tile(*pl.H, *pl.V, g, out_w, out_h, &pl.d, &pl.bands, &pl.chunks, ac.channels);
   if (rc) return rc;
   if (red) {
     *red = ReduceDesc{b.q[0], b.q[1], b.q[2] - b.q[0], b.q[3] - b.q[1], b.fx, b.fy, b.cw, b.ch, {}, {}};
@@ -435,8 +438,9 @@ int place_item_into(void* cache, int filter, double gap, const spdl_hj_resample_
   // (with sums the cells count from rr.qx / qy, which hold the clamped box's
   // origin; without, the producer reads the frame at the box's origin + xmin)
   const Geo g{sum ? 0 : ig.bx, sum ? 0 : ig.by, b.cw, b.ch, b.rw, b.rh, b.ox, b.oy};
-  rc = sum ? tile_reduce(*pl.H, *pl.V, g, it->out_w, it->out_h, &pl.d, &pl.bands, &pl.chunks)
-           : tile(*pl.H, *pl.V, g, it->out_w, it->out_h, &pl.d, &pl.bands, &pl.chunks);
+  rc = sum ? tile_reduce(*pl.H, *pl.V, g, it->out_w, it->out_h, &pl.d, &pl.bands, &pl.chunks,
+                         ac.channels)
+           : tile(*pl.H, *pl.V, g, it->out_w, it->out_h, &pl.d, &pl.bands, &pl.chunks, ac.channels);
   if (rc) return rc;
   rec->rr = ReduceDesc{ig.bx + b.q[0], ig.by + b.q[1], b.q[2] - b.q[0], b.q[3] - b.q[1],
                        b.fx,           b.fy,           b.cw,            b.ch,

@@ -28,6 +28,13 @@ constexpr int kMaxTaps = SPDL_HJ_RESAMPLE_MAX_TAPS;
 // attribute of its own.  A typical training resize (2x down into 224) takes 36 KiB.
 constexpr int kLdsBudget = 64 * 1024;
 constexpr int kTileW = 64, kTileH = 32, kStripRows = 32;  // the tiler's first choice
+// ... and of a one-channel output (SPDL_HJ_FMT_L / _Y): a pixel is a byte in
+// the strip and the intermediate, a quarter of the words, so twice the columns
+// still take half the LDS of a three-channel tile and the halo columns two
+// neighbouring tiles both stage are staged half as often.  The rows stay: the
+// vertical pass runs 8 columns a thread, and 128 x 32 is two such groups a
+// thread, where a taller tile would only lengthen the intermediate.
+constexpr int kTileW1 = 128;
 
 // One axis of a resample: the box [in0, in1) of inSize samples into outSize
 // (an integer request: in0 = 0, in1 = inSize of the cropped frame).
@@ -59,6 +66,10 @@ inline std::shared_ptr<const Axis> make_axis(int in, int out, int filter, int* r
 // image, so the cache is emptied when it has grown to kCap axes.
 struct AxisCache {
   static constexpr size_t kCap = 512;
+  // The channel count the tiler sizes its tiles for, 3 or 1: the host sets it
+  // from the submission's format ahead of the plan (place* take no such
+  // argument: their signatures are the planner's function pointers)
+  int channels = 3;
   std::map<std::tuple<int, double, double, int, int>, std::shared_ptr<const Axis>> held;
   std::shared_ptr<const Axis> get(int in, double in0, double in1, int out, int filter, int* rc);
   std::shared_ptr<const Axis> get(int in, int out, int filter, int* rc) {
@@ -78,7 +89,7 @@ int resolve(const spdl_hj_resample_item* it, int W, int H, int out_w, int out_h,
 // *chunks tiles; SPDL_HJ_ERR_BAD_GEOMETRY and everything zero when the
 // smallest tile does not fit.
 int tile(const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h, ResampleDesc* d,
-         int* bands, int* chunks);
+         int* bands, int* chunks, int nch = 3);
 
 // One image of a resampled submission, whole: its request resolved, its two
 // axes from the cache, its tiling.  0, or why the image is refused alone.
@@ -119,7 +130,7 @@ int resolve_box(const spdl_hj_resample_box_item* it, int W, int H, int out_w, in
 // alignment (the producer's units are the frame's, not the strip's), and the
 // B sums' plane beside the strip (rs::reduce_lds_words)
 int tile_reduce(const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h, ResampleDesc* d,
-                int* bands, int* chunks);
+                int* bands, int* chunks, int nch = 3);
 
 // place_into for a box request.  red == null: the submission has no factor
 // above 1 and the record is resample_kernel's; else resample_reduce_kernel's,

@@ -181,7 +181,7 @@ def _src_size(info, rect) -> tuple[int, int]:
 
 
 def _shape(out: Output, w: int, h: int) -> tuple:
-    return (3, h, w) if out.planar else (h, w, 3)
+    return (3, h, w) if out.planar else (h, w, out.channels)
 
 
 def _frame_format(info) -> tuple[int, int, bool]:
@@ -239,7 +239,7 @@ def decode_image_nvjpeg(
         raise ValueError("device_config must be provided.")
     if scale_algo not in _lib.FILTERS:
         raise ValueError(f"Unexpected scale_algo: {scale_algo}. Supported: {list(_lib.FILTERS)}")
-    if pix_fmt not in _lib.PIX_FMTS:
+    if pix_fmt not in _lib.PIX_FMTS or pix_fmt in _lib.LUMA_FMTS:  # (those are csc="turbo"'s)
         raise RuntimeError(
             f'Unexpected pix_fmt: {pix_fmt}. Supported values are "bgr", "bgr24", "rgb", "rgb24"'
         )
@@ -353,6 +353,17 @@ def _check_csc(csc: str, *, width=None, height=None, crops=None, flips=None,
         bad = "pix_fmt=None (it converts to RGB)"
     if bad:
         raise ValueError(f"csc='turbo' is the full-resolution decode alone: it takes no {bad}")
+
+
+def _check_luma(pix_fmt, csc: str, resample=None) -> None:
+    """``pix_fmt=`` ``"L"`` (Pillow's ``convert("L")``) or ``"Y"``
+    (libjpeg-turbo's grayscale output) against what takes them, before
+    anything is read: ``csc="turbo"`` alone.  (A format node of the caller's
+    own chain is :func:`_with_csc`'s to judge.)"""
+    if pix_fmt not in _lib.LUMA_FMTS:
+        return
+    if csc != "turbo":
+        raise ValueError(f"pix_fmt 'L' / 'Y' needs csc='turbo', not {csc!r}")
 
 
 @dataclass(frozen=True)
@@ -595,8 +606,8 @@ def _views_turbo(srcs, groups, cfg, strict: bool):
         if g.get("flips") is not None and [len(f) for f in g["flips"]] != [len(b) for b in per]:
             raise ValueError("flips= is parallel to the boxes: one flip per box")
         pix_fmt = g.get("pix_fmt", "rgb24")
-        if pix_fmt not in ("rgb", "bgr", "rgb24", "bgr24"):
-            raise ValueError(f"a group's pix_fmt is rgb, bgr, rgb24 or bgr24, not {pix_fmt!r}")
+        if pix_fmt not in ("rgb", "bgr", "rgb24", "bgr24", *_lib.LUMA_FMTS):
+            raise ValueError(f"a group's pix_fmt is rgb, bgr, rgb24, bgr24, L or Y, not {pix_fmt!r}")
         out = Output(pix_fmt=pix_fmt, csc="turbo")
         if g.get("normalize", False):
             out = Output(**{**out.__dict__, "normalize": True, "norm_dtype": g.get("dtype", "float16"),
@@ -648,12 +659,14 @@ def _views_turbo(srcs, groups, cfg, strict: bool):
     for g, src_of in zip(groups, rows):
         at = -(-at // 256) * 256
         w, h = g["resample"].size
-        offsets += [at + r * w * h * 3 * esz for r in range(len(src_of))]
-        at += len(src_of) * w * h * 3 * esz
+        offsets += [at + r * w * h * out.channels * esz for r in range(len(src_of))]
+        at += len(src_of) * w * h * out.channels * esz
     items = _lib.ResampleItems(first.filter, [(k, b, c, sz, (0, 0), sz, f, o)
                                               for (k, b, c, sz, _, f), o in zip(reqs, offsets)],
                                first.reducing_gap)
-    _lib.resample_items_check(infos, items, esz, at)  # (ValueError before anything is submitted)
+    # (ValueError before anything is submitted; the check counts three elements a
+    # pixel, so a one-channel buffer is held against an upper bound here)
+    _lib.resample_items_check(infos, items, esz, at * (3 // out.channels))
     total = _alloc_out(cfg, (max(at // esz, 1),), out.torch_dtype)
     dec = _lib.thread_decoder(cfg.device_index)
     status = dec.decode_batch(datas, out, total.data_ptr(), at, stream=_stream(cfg), sync=True,
@@ -733,6 +746,8 @@ def _csc_pix_fmt(filter_desc, pix_fmt):
 def _with_csc(out: Output, csc: str) -> Output:
     """``out`` converting with ``csc``; a chain ``"turbo"`` cannot run (a scale,
     pad, crop, flip or transpose node, no format) is refused here."""
+    if out.pix_fmt in _lib.LUMA_FMTS and csc != "turbo":
+        raise ValueError(f"pix_fmt 'L' / 'Y' needs csc='turbo', not {csc!r}")
     if csc == "swscale":
         return out
     if csc == "turbo" and (out.resize or out.src_crop is not None or out.flip is not None or
@@ -834,6 +849,7 @@ def load_image_batch(
     _check_csc(csc, width=width, height=height, crops=crops, flips=flips,
                exif_orientation=exif_orientation, lowres=lowres,
                pix_fmt=_csc_pix_fmt(filter_desc, pix_fmt))
+    _check_luma(pix_fmt, csc, resample)
     _check_resample(resample, csc, len(srcs), filter_desc, pix_fmt)
     _check_draft(draft, csc, resample, len(srcs))
     if filter_desc == _FILTER_DESC_DEFAULT:
@@ -1237,6 +1253,7 @@ def load_image_list(
     if csc not in ("swscale", "turbo"):
         raise ValueError(f"load_image_list converts with csc='swscale' only, or with csc='turbo' "
                          f"at native size, not {csc!r}")
+    _check_luma(pix_fmt, csc, resample)
     _check_csc(csc, width=width, height=height, crops=crops,
                flips=None if resample is not None else flips,
                exif_orientation=exif_orientation, lowres=lowres, pix_fmt=pix_fmt)
@@ -1311,7 +1328,7 @@ def load_image_list(
         dlevels, reqs, gap = _item_requests(resample, infos, keep, dlevels, codes)
         offsets, sizes, planned, items = _lib.resample_layout(
             infos, reqs, align, filter=resample.filter, reducing_gap=gap, elem_size=esz,
-            draft=dlevels)
+            draft=dlevels, channels=out.channels)
         codes = None
     else:
         offsets, sizes, planned = _lib.ragged_layout(infos, out, crops, codes, align, lowres=levels,
@@ -1425,6 +1442,7 @@ def load_image(
         raise TypeError(f"unexpected arguments: {sorted(kwargs)}")
     _check_csc(csc, flips=flip or None, exif_orientation=exif_orientation, lowres=lowres,
                pix_fmt=_csc_pix_fmt(filter_desc, pix_fmt))
+    _check_luma(pix_fmt, csc, resample)
     _check_resample(resample, csc, 1, filter_desc, pix_fmt)
     _check_draft(draft, csc, resample, 1)
     if resample is not None and filter_desc is None:

@@ -245,7 +245,7 @@ def parse_image_filter(filter_desc: str | None, default_pix_fmt: str | None = "r
             spec.update(resize=True, crop_w=_size(kv, "w", part), crop_h=_size(kv, "h", part))
         elif name == "format":
             pf = kv.get("pix_fmts", kv.get("w"))
-            if pf not in ("rgb24", "bgr24", "rgb", "bgr"):
+            if pf not in ("rgb24", "bgr24", "rgb", "bgr", "L", "Y"):
                 raise ValueError(f"unsupported output pix_fmt: {pf}")
             spec["pix_fmt"] = pf
         else:
