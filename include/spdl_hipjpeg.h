@@ -882,8 +882,28 @@ int spdl_hj_debug_reduce_plan(int32_t W, int32_t H, const spdl_hj_resample_box_i
  * adjacent.  The read-only parameters "resample_items" and
  * "resample_item_workgroups" report the items placed (not refused) and the
  * workgroups launched in the last submission.
- * Out of scope: orientations (transpose codes) on items; per-item dtypes or
- * formats; an IDCT restricted to the MCUs the items touch. */
+ * Out of scope: per-item dtypes or formats; an IDCT restricted to the MCUs the
+ * items touch.
+ *
+ * ---- Pillow-exact orientation (additive in ABI 7: the item's former
+ * `reserved` field, 0 as every earlier caller wrote it) ----
+ * orient: an orientation code 0..7 in the convention of spdl_hj_set_orients
+ * (bits 0 and 1 the flips, bit 2 a transpose applied before them; EXIF tag
+ * 0x0112 maps to it by spdl_hj_orient_code).  An item with code c is exactly
+ * the item above with im replaced by T_c(im), Pillow's Image.transpose:
+ *   1 FLIP_LEFT_RIGHT  2 FLIP_TOP_BOTTOM  3 ROTATE_180  4 TRANSPOSE
+ *   5 ROTATE_270       6 ROTATE_90        7 TRANSVERSE
+ * -- ImageOps.exif_transpose ahead of crop, resize and thumbnail.  The box,
+ * rw / rh, the window, the reduce factors, the H > 100 W rule and every
+ * BAD_GEOMETRY condition refer to the DISPLAYED frame, H x W for codes 4..7;
+ * flip still mirrors the written window.  Chroma upsampling and colour
+ * conversion run on the stored frame, as Pillow decodes before it transposes.
+ * SPDL_HJ_ERR_INVALID_ARG, nothing written: orient outside 0..7; a non-zero
+ * orient with SPDL_HJ_FMT_L / _Y.  spdl_hj_set_orients / _flips with
+ * csc = TURBO stay refused.  A submission in which no placed item has a code
+ * launches the kernel it launched before.
+ * Out of scope: one-channel oriented items; orientation on the views of
+ * csc = TURBO groups; the native-size TURBO decode without items. */
 typedef struct spdl_hj_resample_items_item {
   int32_t image;         /* index into the batch */
   int32_t clamp;         /* 1: .crop(box).resize(); 0: resize(box=) */
@@ -892,7 +912,7 @@ typedef struct spdl_hj_resample_items_item {
   int32_t ox, oy;        /* the out_w x out_h window of it that is written */
   int32_t out_w, out_h;
   int32_t flip;          /* SPDL_HJ_FLIP_* bits, 0..3 */
-  int32_t reserved;
+  int32_t orient;        /* 0..7, "Pillow-exact orientation" below; 0: the frame as stored */
   int64_t offset;        /* bytes into the output buffer */
 } spdl_hj_resample_items_item;
 int spdl_hj_set_resample_items(spdl_hj_ctx* ctx, int32_t filter, double reducing_gap,

@@ -575,7 +575,7 @@ class ResampleItemsItem(ctypes.Structure):  # spdl_hj_resample_items_item
                 ("y0", ctypes.c_double), ("x1", ctypes.c_double), ("y1", ctypes.c_double),
                 ("rw", ctypes.c_int32), ("rh", ctypes.c_int32), ("ox", ctypes.c_int32),
                 ("oy", ctypes.c_int32), ("out_w", ctypes.c_int32), ("out_h", ctypes.c_int32),
-                ("flip", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_int64)]
+                ("flip", ctypes.c_int32), ("orient", ctypes.c_int32), ("offset", ctypes.c_int64)]
 
 
 class ResampleItems:
@@ -587,8 +587,11 @@ class ResampleItems:
     (``True``: ``.crop(box).resize()``, an integral box; ``False``:
     ``resize(box=)``), the resized picture, the window of it that is written,
     a flip (``0..3``, ``"h"``, ``"v"``, ``"hv"`` or ``None``) and the byte
-    offset of the item's box in the output buffer.  ``statuses``, after the
-    submission: each item's own status (``0``, or ``7``: refused alone)."""
+    offset of the item's box in the output buffer.  A ninth entry is the
+    item's orientation code ``0..7`` (include/spdl_hipjpeg.h "Pillow-exact
+    orientation"): box, sizes and window are then in the DISPLAYED frame.
+    ``statuses``, after the submission: each item's own status (``0``, or
+    ``7``: refused alone)."""
 
     def __init__(self, filter: str, items, reducing_gap=None):
         if filter not in FILTERS:
@@ -598,8 +601,9 @@ class ResampleItems:
         self._arr = (ResampleItemsItem * max(len(self.items), 1))()
         self._status = (ctypes.c_int32 * max(len(self.items), 1))()
         try:
-            for a, (image, box, clamp, (rw, rh), (ox, oy), (ow, oh), flip, offset) in zip(
+            for a, (image, box, clamp, (rw, rh), (ox, oy), (ow, oh), flip, offset, *code) in zip(
                     self._arr, self.items):
+                (a.orient,) = (int(c) for c in code or (0,))
                 a.image, a.clamp = int(image), int(bool(clamp))
                 a.x0, a.y0, a.x1, a.y1 = (float(v) for v in (box or (0, 0, 0, 0)))
                 a.rw, a.rh, a.ox, a.oy, a.out_w, a.out_h = (int(v) for v in (rw, rh, ox, oy, ow, oh))
@@ -629,7 +633,7 @@ def resample_items_check(infos, items: ResampleItems, elem_size: int, out_bytes:
                                             int(out_bytes), st)
     if rc:
         raise ValueError("the resample items do not make a submission: an image index outside "
-                         "the batch, a flip above 3, a non-integral clamped box, a box outside "
+                         "the batch, a flip above 3, an orientation above 7, a non-integral clamped box, a box outside "
                          f"its frame, or an item past the buffer (status {rc})")
     return list(st)[:len(items.items)]
 
@@ -639,7 +643,8 @@ def resample_layout(infos, requests, align: int = 256, *, filter: str = "bicubic
     """``(offsets, sizes, statuses, items)`` of an items submission (host only),
     the sibling of :func:`ragged_layout`.  ``requests``: per item ``(image, box,
     clamp, (rw, rh), window, flip)`` with ``window = (ox, oy, out_w, out_h)`` or
-    ``None`` for the whole resized picture.  Every item's ``out_h x out_w x
+    ``None`` for the whole resized picture, and optionally the item's
+    orientation code behind them.  Every item's ``out_h x out_w x
     channels`` box (``channels=1``: ``pix_fmt`` ``"L"`` / ``"Y"``) is packed in request order at a multiple of ``align`` bytes; ``offsets``
     has one entry more than there are items, the last the buffer's size.
     ``statuses``: each item's own (``7``: refused alone, its box stays unwritten).
@@ -648,12 +653,12 @@ def resample_layout(infos, requests, align: int = 256, *, filter: str = "bicubic
     if align < elem_size or align % elem_size:
         raise ValueError(f"align is a multiple of the element size, not {align}")
     offsets, sizes, items, end = [], [], [], 0
-    for image, box, clamp, (rw, rh), window, flip in requests:
+    for image, box, clamp, (rw, rh), window, flip, *code in requests:
         ox, oy, ow, oh = window if window is not None else (0, 0, rw, rh)
         offsets.append(-(-end // align) * align)
         sizes.append((int(ow), int(oh)))
         end = offsets[-1] + int(ow) * int(oh) * channels * elem_size
-        items.append((image, box, clamp, (rw, rh), (ox, oy), (ow, oh), flip, offsets[-1]))
+        items.append((image, box, clamp, (rw, rh), (ox, oy), (ow, oh), flip, offsets[-1], *code))
     offsets.append(end)
     held = ResampleItems(filter, items, reducing_gap)
     # (the check counts three elements a pixel: a one-channel layout is held

@@ -367,6 +367,8 @@ inline HJ_HD int reduce_lds_words(const ResampleDesc& d, int nch = 3) {
 // rd / rr as the two kernels above read them, with one difference: an item
 // clamped to an integer box of a submission with factors has the box's origin
 // in rr.qx / rr.qy (the cells count from there) and rd.bx = rd.by = 0.
+// An item with an orientation code has its windows unaligned without factors
+// as well (rs::tile_oriented): its producer's units are the STORED frame's.
 struct ItemDesc {
   ResampleDesc rd;
   ReduceDesc rr;             // (a submission without factors: unused)
@@ -375,8 +377,33 @@ struct ItemDesc {
   int32_t flip;              // SPDL_HJ_FLIP_* of the written window
   int32_t wg0, chunks;       // its first workgroup in the grid, tiles per band
   uint32_t off_lo, off_hi;   // its first element in the output
+  // spdl_hj_resample_items_item.orient and the DISPLAYED frame dw x dh it turns
+  // the stored one into: everything above is in that frame's coordinates, and
+  // the orienting instantiation alone reads these three
+  int32_t orient, dw, dh;
 };
 constexpr uint32_t kItemNone = 0xFFFFFFFFu;  // a map entry of the status workgroups
+
+// An orientation code (bit 0 / 1: the flips, bit 2: a transpose ahead of them)
+// between the stored frame and the displayed dw x dh one.  The stored
+// rectangle [x0, x1) x [y0, y1) under the displayed [X0, X1) x [Y0, Y1) ...
+struct StoredRect {
+  int x0, x1, y0, y1;
+};
+inline HJ_HD StoredRect stored_rect(int code, int dw, int dh, int X0, int X1, int Y0, int Y1) {
+  const int a0 = code & 1 ? dw - X1 : X0, a1 = code & 1 ? dw - X0 : X1;
+  const int b0 = code & 2 ? dh - Y1 : Y0, b1 = code & 2 ? dh - Y0 : Y1;
+  return code & 4 ? StoredRect{b0, b1, a0, a1} : StoredRect{a0, a1, b0, b1};
+}
+// ... and the displayed place of stored pixel (sx, sy)
+inline HJ_HD int displayed_x(int code, int dw, int sx, int sy) {
+  const int px = code & 4 ? sy : sx;
+  return code & 1 ? dw - 1 - px : px;
+}
+inline HJ_HD int displayed_y(int code, int dh, int sx, int sy) {
+  const int py = code & 4 ? sx : sy;
+  return code & 2 ? dh - 1 - py : py;
+}
 
 }  // namespace rs
 

@@ -797,7 +797,8 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
       // resample_items_kernel over the items' tiles and the status workgroups
       // behind them (never empty: ceil(n / 256) of the latter)
       const int wgs = (int)L.item_map.size();
-      HJ_HIP(launch_resample_items(B, sub.out_dev, bp, wgs, L.items_sum, L.resample_lds, hstat, st));
+      HJ_HIP(launch_resample_items(B, sub.out_dev, bp, wgs, L.items_sum, L.items_orient,
+                                   L.resample_lds, hstat, st));
       ctx->resample_items = (int64_t)L.items.size();
       ctx->resample_item_workgroups = wgs;
     } else if (turbo && B.resample) {

@@ -7692,19 +7692,90 @@ __device__ __forceinline__ void rs_samples(const uint8_t* __restrict__ planes, c
   else turbo_samples(planes, dd, x0, y0, v);
 }
 
-// Strips of frame rows [r0, r1) from column c0 on, units_x 8-column units wide,
-// each through the horizontal pass (resample_kernel's step 2)
+// The orienting producer of one strip without cell sums: the strip holds
+// DISPLAYED rows [s0, s0 + srows) by displayed columns [c0, c1) of an item
+// with orientation code `code` in a displayed frame dw x dh.  The stored
+// rectangle under it (rs::stored_rect) is walked in the stored frame's 8 x 2
+// units -- the same rs_samples / turbo_pixel as everywhere, so chroma and colour
+// are the stored frame's -- and every pixel of a unit that lies inside the
+// rectangle is written at its displayed place: a flip bit mirrors the LDS
+// index, the transpose bit swaps the unit's roles (its 8 stored columns are 8
+// strip ROWS, its 2 stored rows 2 strip columns).  The address is linear in the
+// unit's (j, k), so the two strides are worked out once.
+// Unit order: the lanes run along the stored axis that is displayed x -- stored
+// x as ever without the transpose bit, stored Y with it.  Neighbouring lanes
+// then write 2 words apart within the same 8 strip rows (a 4-way conflict of a
+// 64-lane store on 32 banks where 2-way is the floor), where lanes along stored
+// x would write 8 strip rows apart: 8 * pitch words, pitch odd, which is 8 or
+// 24 modulo 32 -- four banks for all lanes, 16-way.  The price is the global
+// read: a lane's 8 bytes of a plane row lie 2 rows from its neighbour's.  A
+// strip is at most 32 displayed rows, that is 32 stored columns, so lanes along
+// stored x could share 32 bytes of a row at best, and the next strip of the
+// tile reads the same rows' next 32 bytes from L2 either way.
 template <bool DRAFT>
+__device__ __forceinline__ void rs_produce_oriented(const uint8_t* __restrict__ planes,
+                                                    const ImageDesc& dd,
+                                                    const draft::Desc* __restrict__ drafts, int img,
+                                                    const rs::ResampleDesc& rd, uint32_t* strip,
+                                                    int code, int dw, int dh, int c0, int c1, int s0,
+                                                    int srows, int tid) {
+  const rs::StoredRect sr = rs::stored_rect(code, dw, dh, c0, c1, s0, s0 + srows);
+  const int ux0 = sr.x0 >> 3, units_x = ((sr.x1 + 7) >> 3) - ux0;
+  const int uy0 = sr.y0 >> 1, units_y = ((sr.y1 + 1) >> 1) - uy0;
+  const bool tr = code & 4;
+  // a step along the unit's columns (k) and rows (j), in strip words
+  const int sx = code & 1 ? -1 : 1, sy = code & 2 ? -rd.pitch : rd.pitch;
+  const int sk = tr ? sy : sx, sj = tr ? sx : sy;
+  for (int u = tid; u < units_x * units_y; u += 256) {
+    int ux, uy;
+    if (tr) {
+      ux = u / units_y;
+      uy = u - ux * units_y;
+    } else {
+      uy = u / units_x;
+      ux = u - uy * units_x;
+    }
+    const int x0 = (ux0 + ux) * 8, y0 = (uy0 + uy) * 2;
+    int v[3][2][8];
+    rs_samples<DRAFT>(planes, dd, drafts, img, x0, y0, v);
+    uint32_t* const q = strip + (rs::displayed_y(code, dh, x0, y0) - s0) * rd.pitch +
+                        (rs::displayed_x(code, dw, x0, y0) - c0);
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        int rgb[3];
+        turbo_pixel(dd, v[0][j][k], v[1][j][k], v[2][j][k], rgb);
+        if (x0 + k >= sr.x0 && x0 + k < sr.x1 && y0 + j >= sr.y0 && y0 + j < sr.y1)
+          q[j * sj + k * sk] = (uint32_t)rgb[0] | (uint32_t)rgb[1] << 8 | (uint32_t)rgb[2] << 16;
+      }
+    }
+  }
+}
+
+// Strips of frame rows [r0, r1) from column c0 on, units_x 8-column units wide,
+// each through the horizontal pass (resample_kernel's step 2).  ORIENT: rows
+// and columns [c0, c1) of item `it`'s DISPLAYED frame, the producer
+// rs_produce_oriented
+template <bool DRAFT, bool ORIENT>
 __device__ __forceinline__ void rs_strips_plain(const uint8_t* __restrict__ planes,
                                                 const ImageDesc& dd,
                                                 const draft::Desc* __restrict__ drafts, int img,
                                                 const int32_t* lds, const rs::LdsLayout& l,
                                                 const rs::ResampleDesc& rd, uint32_t* strip,
                                                 uint32_t* inter, int c0, int units_x, int r0, int r1,
-                                                int ncol, int tid) {
+                                                int ncol, int tid, const rs::ItemDesc* it = nullptr,
+                                                int c1 = 0) {
   for (int s0 = r0; s0 < r1; s0 += rd.sr) {
     const int srows = min(rd.sr, r1 - s0);
     __syncthreads();  // (the coefficient rows stand; the last strip is consumed)
+    if constexpr (ORIENT) {
+      rs_produce_oriented<DRAFT>(planes, dd, drafts, img, rd, strip, it->orient, it->dw, it->dh, c0,
+                                 c1, s0, srows, tid);
+      __syncthreads();
+      rs_hpass(lds, l, rd, strip, inter, ncol, srows, s0 - r0, tid);
+      continue;
+    }
     const int units = units_x * ((srows + 1) >> 1);
     for (int u = tid; u < units; u += 256) {
       const int uy = u / units_x, ux = u - uy * units_x;
@@ -7729,26 +7800,130 @@ __device__ __forceinline__ void rs_strips_plain(const uint8_t* __restrict__ plan
 // Strips of cell rows [r0, r1), cells c0 .. c0 + ncell - 1: the cell sums, their
 // division into the strip, the horizontal pass (resample_reduce_kernel's steps
 // a to d)
-template <bool DRAFT>
+// The orienting producer's unit with cell sums.  The cells are the DISPLAYED
+// picture's: fx along displayed columns, fy along displayed rows.  The unit's
+// 8 x 2 sums rg / bb arrive in stored order, its stored corner (x0, y0).
+// Without the transpose bit they are put in displayed order (a flip bit
+// reverses the unit's columns or swaps its rows: register moves) and the unit
+// is an 8 x 2 unit of the displayed frame at (*dx0, *dy0), of no alignment,
+// which rs_strips_sum's own walk takes: returns false.  With the bit the unit
+// is 2 displayed columns by 8 displayed rows and is added here: returns true.
+// The pre-summing runs along both axes again -- the two columns leave as one
+// ds_add where they share a cell (the unit's 2-row axis is displayed x), and
+// the rows of one cell row are summed in registers while the 8-column axis
+// walks down the cell rows.
+__device__ __forceinline__ bool reduce_unit_oriented(uint32_t* strip, uint32_t* sumb,
+                                                     const rs::ResampleDesc& rd,
+                                                     const rs::ReduceDesc& rr, int code, int dw,
+                                                     int dh, int x0, int y0, uint32_t (&rg)[2][8],
+                                                     uint32_t (&bb)[2][8], int X0, int X1, int Y0,
+                                                     int Y1, int c0, int s0, int* dx0, int* dy0) {
+  const bool hf = code & 1, vf = code & 2;
+  if (!(code & 4)) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        const uint32_t a = rg[j][k], b = rg[j][7 - k], c = bb[j][k], d = bb[j][7 - k];
+        rg[j][k] = hf ? b : a;
+        rg[j][7 - k] = hf ? a : b;
+        bb[j][k] = hf ? d : c;
+        bb[j][7 - k] = hf ? c : d;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint32_t a = rg[0][k], b = rg[1][k], c = bb[0][k], d = bb[1][k];
+      rg[0][k] = vf ? b : a;
+      rg[1][k] = vf ? a : b;
+      bb[0][k] = vf ? d : c;
+      bb[1][k] = vf ? c : d;
+    }
+    *dx0 = hf ? dw - 8 - x0 : x0;
+    *dy0 = vf ? dh - 2 - y0 : y0;
+    return false;
+  }
+  // displayed columns xa, xa + 1 (the left one stored row y0 + jl), rows ya .. ya + 7
+  const int xa = hf ? dw - 2 - y0 : y0, ya = vf ? dh - 8 - x0 : x0;
+  const bool jl = hf;
+  const bool okl = xa >= X0 && xa < X1, okr = xa + 1 >= X0 && xa + 1 < X1;
+  const int cl = okl ? (xa - rr.qx) / rr.fx - c0 : 0, cr = okr ? (xa + 1 - rr.qx) / rr.fx - c0 : 0;
+  const bool one = okl && okr && cl == cr;
+  const int klo = max(Y0 - ya, 0), khi = min(Y1 - ya, 8);
+  int cy = (ya + klo - rr.qy) / rr.fy, rem = (ya + klo - rr.qy) - cy * rr.fy;
+  cy -= s0;
+  uint32_t al = 0, ar = 0, bl = 0, br = 0;
+#pragma unroll
+  for (int kk = 0; kk < 8; kk++) {
+    if (kk >= klo && kk < khi) {
+      const uint32_t g0 = vf ? rg[0][7 - kk] : rg[0][kk], g1 = vf ? rg[1][7 - kk] : rg[1][kk];
+      const uint32_t b0 = vf ? bb[0][7 - kk] : bb[0][kk], b1 = vf ? bb[1][7 - kk] : bb[1][kk];
+      al += jl ? g1 : g0;
+      ar += jl ? g0 : g1;
+      bl += jl ? b1 : b0;
+      br += jl ? b0 : b1;
+      if (++rem == rr.fy || kk == khi - 1) {
+        uint32_t* const srg = strip + cy * rd.pitch;
+        uint32_t* const sb = sumb + cy * rd.pitch;
+        if (one) {
+          atomicAdd(srg + cl, al + ar);
+          atomicAdd(sb + cl, bl + br);
+        } else {
+          if (okl) {
+            atomicAdd(srg + cl, al);
+            atomicAdd(sb + cl, bl);
+          }
+          if (okr) {
+            atomicAdd(srg + cr, ar);
+            atomicAdd(sb + cr, br);
+          }
+        }
+        al = ar = bl = br = 0;
+        rem = 0;
+        cy++;
+      }
+    }
+  }
+  return true;
+}
+
+// ORIENT: cells of item `it`'s DISPLAYED picture; the units are those of the
+// stored rectangle under the strip's cells (rs::stored_rect), their order
+// rs_produce_oriented's and their way into the cells reduce_unit_oriented's
+template <bool DRAFT, bool ORIENT>
 __device__ __forceinline__ void rs_strips_sum(const uint8_t* __restrict__ planes,
                                               const ImageDesc& dd,
                                               const draft::Desc* __restrict__ drafts, int img,
                                               const int32_t* lds, const rs::LdsLayout& l,
                                               const rs::ResampleDesc& rd, const rs::ReduceDesc& rr,
                                               uint32_t* strip, uint32_t* sumb, uint32_t* inter,
-                                              int c0, int ncell, int r0, int r1, int ncol, int tid) {
+                                              int c0, int ncell, int r0, int r1, int ncol, int tid,
+                                              const rs::ItemDesc* it = nullptr) {
   const int X0 = rr.qx + c0 * rr.fx, X1 = min(rr.qx + (c0 + ncell) * rr.fx, rr.qx + rr.qw);
-  const int ux0 = X0 >> 3, units_x = ((X1 + 7) >> 3) - ux0;
+  int ux0 = X0 >> 3, units_x = ((X1 + 7) >> 3) - ux0;
   for (int s0 = r0; s0 < r1; s0 += rd.sr) {
     const int srows = min(rd.sr, r1 - s0);
     const int Y0 = rr.qy + s0 * rr.fy, Y1 = min(rr.qy + (s0 + srows) * rr.fy, rr.qy + rr.qh);
-    const int uy0 = Y0 >> 1, units = units_x * (((Y1 + 1) >> 1) - uy0);
+    int uy0 = Y0 >> 1, units = units_x * (((Y1 + 1) >> 1) - uy0);
+    int units_y = 0;
+    if constexpr (ORIENT) {
+      const rs::StoredRect sr = rs::stored_rect(it->orient, it->dw, it->dh, X0, X1, Y0, Y1);
+      ux0 = sr.x0 >> 3, units_x = ((sr.x1 + 7) >> 3) - ux0;
+      uy0 = sr.y0 >> 1, units_y = ((sr.y1 + 1) >> 1) - uy0;
+      units = units_x * units_y;
+    }
     __syncthreads();  // (the coefficient rows stand; the last strip is consumed)
     for (int i = tid; i < srows * rd.pitch; i += 256) strip[i] = sumb[i] = 0;
     __syncthreads();
     for (int u = tid; u < units; u += 256) {
-      const int uy = u / units_x, ux = u - uy * units_x;
-      const int x0 = (ux0 + ux) * 8, y0 = (uy0 + uy) * 2;
+      int uy = u / units_x, ux = u - uy * units_x;
+      if constexpr (ORIENT) {
+        if (it->orient & 4) {  // (lanes along stored y: rs_produce_oriented)
+          ux = u / units_y;
+          uy = u - ux * units_y;
+        }
+      }
+      int x0 = (ux0 + ux) * 8, y0 = (uy0 + uy) * 2;
       int v[3][2][8];
       rs_samples<DRAFT>(planes, dd, drafts, img, x0, y0, v);
       uint32_t rg[2][8], bb[2][8];
@@ -7761,6 +7936,11 @@ __device__ __forceinline__ void rs_strips_sum(const uint8_t* __restrict__ planes
           rg[j][k] = (uint32_t)rgb[0] | (uint32_t)rgb[1] << 16;
           bb[j][k] = (uint32_t)rgb[2];
         }
+      }
+      if constexpr (ORIENT) {  // (from here on (x0, y0) is the unit's DISPLAYED corner)
+        if (reduce_unit_oriented(strip, sumb, rd, rr, it->orient, it->dw, it->dh, x0, y0, rg, bb, X0,
+                                 X1, Y0, Y1, c0, s0, &x0, &y0))
+          continue;
       }
       // the unit's columns and rows inside the source rectangle, and their cells
       const int klo = max(X0 - x0, 0), khi = min(X1 - x0, 8);
@@ -7985,7 +8165,15 @@ __device__ __forceinline__ void rs_luma_tile(uint32_t* rs_lds, const uint8_t* __
   }
 }
 
-template <bool DRAFT, bool SUM, int NCH>
+// ORIENT: the instantiation a submission with an orientation code on some
+// placed item launches (spdl_hipjpeg.h "Pillow-exact orientation"); without
+// one the kernel is the one before orientations.  An item's record is in its
+// DISPLAYED frame throughout -- tables, box, cells, windows -- and only the
+// producer knows the stored one: it lands every stored pixel at its displayed
+// place in the strip (rs_produce_oriented, reduce_unit_oriented), and
+// everything behind the strip runs as it is.  An item without a code keeps its
+// aligned windows there and takes the same producer with code 0.
+template <bool DRAFT, bool SUM, int NCH, bool ORIENT = false>
 __global__ void __launch_bounds__(256) resample_items_kernel(
     const uint8_t* __restrict__ planes, const ImageDesc* __restrict__ desc,
     const ImageInfo* __restrict__ infos, const rs::ItemDesc* __restrict__ items,
@@ -8026,17 +8214,20 @@ __global__ void __launch_bounds__(256) resample_items_kernel(
     const rs::Window wr =
         rs::tile_window(tables + rd.vx, tables + rd.vn, 0, rd.oy, it.oh, rd.th, ty, 1);
     rs_stage_rows(lds, l, tables, rd, hcol0, vrow0, ncol, nrow, -wc.lo, -wr.lo, tid);
-    rs_strips_sum<DRAFT>(planes, dd, drafts, img, lds, l, rd, it.rr, strip, rs_lds + l.words, inter,
-                         wc.lo, wc.hi - wc.lo, wr.lo, wr.hi, ncol, tid);
+    rs_strips_sum<DRAFT, ORIENT>(planes, dd, drafts, img, lds, l, rd, it.rr, strip,
+                                 rs_lds + l.words, inter, wc.lo, wc.hi - wc.lo, wr.lo, wr.hi, ncol,
+                                 tid, &it);
   } else {
     // the windows in the frame, from the box's origin, on the producer's units
+    // (an item with a code: unaligned, rs::tile_oriented)
+    const int ax = ORIENT && it.orient ? 1 : 8, ay = ORIENT && it.orient ? 1 : 2;
     const rs::Window wc =
-        rs::tile_window(tables + rd.hx, tables + rd.hn, rd.bx, rd.ox, it.ow, rd.tw, tx, 8);
+        rs::tile_window(tables + rd.hx, tables + rd.hn, rd.bx, rd.ox, it.ow, rd.tw, tx, ax);
     const rs::Window wr =
-        rs::tile_window(tables + rd.vx, tables + rd.vn, rd.by, rd.oy, it.oh, rd.th, ty, 2);
+        rs::tile_window(tables + rd.vx, tables + rd.vn, rd.by, rd.oy, it.oh, rd.th, ty, ay);
     rs_stage_rows(lds, l, tables, rd, hcol0, vrow0, ncol, nrow, rd.bx - wc.lo, rd.by - wr.lo, tid);
-    rs_strips_plain<DRAFT>(planes, dd, drafts, img, lds, l, rd, strip, inter, wc.lo,
-                           (wc.hi - wc.lo + 7) >> 3, wr.lo, wr.hi, ncol, tid);
+    rs_strips_plain<DRAFT, ORIENT>(planes, dd, drafts, img, lds, l, rd, strip, inter, wc.lo,
+                                   (wc.hi - wc.lo + 7) >> 3, wr.lo, wr.hi, ncol, tid, &it, wc.hi);
   }
   __syncthreads();
   rs_vpass_store(lds, l, it, inter, ncol, nrow, tx, ty, out, p, tid);
@@ -8213,8 +8404,21 @@ hipError_t launch_resample_reduce(const BatchBuffers& b, void* out, const BatchP
   return hipGetLastError();
 }
 hipError_t launch_resample_items(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
-                                 bool sum, int lds_bytes, int32_t* host_status, hipStream_t st) {
+                                 bool sum, bool orient, int lds_bytes, int32_t* host_status,
+                                 hipStream_t st) {
   const int tiles = wgs - (b.n + 255) / 256;
+  if (orient) {  // (three channels: the planner refuses a code on a one-channel item)
+#define HJ_ITEMS_ORIENT(D, S)                                                                      \
+  hipLaunchKernelGGL((resample_items_kernel<D, S, 3, true>), dim3(wgs), dim3(256), lds_bytes, st, \
+                     b.planes, b.desc, b.infos, b.items, b.item_map, b.wts, out, p, host_status,  \
+                     b.draft, tiles)
+    if (b.draft && sum) HJ_ITEMS_ORIENT(true, true);
+    else if (b.draft) HJ_ITEMS_ORIENT(true, false);
+    else if (sum) HJ_ITEMS_ORIENT(false, true);
+    else HJ_ITEMS_ORIENT(false, false);
+#undef HJ_ITEMS_ORIENT
+    return hipGetLastError();
+  }
 #define HJ_ITEMS(D, S)                                                                           \
   do {                                                                                            \
     if (p.pix_fmt == kFmtL || p.pix_fmt == kFmtY)                                                 \

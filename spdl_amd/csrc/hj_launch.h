@@ -99,9 +99,12 @@ hipError_t launch_resample_reduce(const BatchBuffers& b, void* out, const BatchP
                                   int lds_bytes, int32_t* host_status, hipStream_t st);
 // resample_items_kernel (spdl_hj_set_resample_items) over b.item_map: `wgs` workgroups, the
 // last ceil(n / 256) of them the status workgroups; sum: the submission has a reduce factor
-// (Layout::items_sum: rs::tile_reduce()'s tiles and LDS)
+// (Layout::items_sum: rs::tile_reduce()'s tiles and LDS); orient: some placed item has an
+// orientation code (Layout::items_orient) -- the orienting instantiation, which a submission
+// without one never launches
 hipError_t launch_resample_items(const BatchBuffers& b, void* out, const BatchParams& p, int wgs,
-                                 bool sum, int lds_bytes, int32_t* host_status, hipStream_t st);
+                                 bool sum, bool orient, int lds_bytes, int32_t* host_status,
+                                 hipStream_t st);
 hipError_t launch_rgb_unscaled(const BatchBuffers& b, void* out, const BatchParams& p,
                                int64_t max_px, int32_t* host_status, hipStream_t st);
 hipError_t launch_idct_rgb(const BatchBuffers& b, void* out, const BatchParams& p, int idct,

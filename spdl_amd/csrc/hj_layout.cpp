@@ -217,6 +217,8 @@ const char* place_items(const ResampleRequest& r, const std::vector<int>& fw,
     status[k] = r.probe_item(r.filter, r.gap, &it, fw[it.image], fh[it.image], &any);
     if (status[k] == SPDL_HJ_ERR_INVALID_ARG)
       return "spdl_hj_set_resample_items: an item's flip, box or output size is invalid";
+    if (it.orient && channels == 1)
+      return "spdl_hj_set_resample_items: no orientation on a one-channel item";
     sum = sum || any;
     const int64_t extent = (int64_t)it.out_w * it.out_h * channels * esz;
     if (it.offset < 0 || it.offset % esz || it.offset > out_bytes || extent > out_bytes - it.offset)
@@ -246,6 +248,7 @@ const char* place_items(const ResampleRequest& r, const std::vector<int>& fw,
       return "spdl_hj_set_resample_items: too many tiles for one submission";
     rec.image = it.image;
     rec.flip = it.flip;
+    L.items_orient = L.items_orient || it.orient != 0;
     rec.wg0 = (int32_t)L.item_map.size();
     rec.chunks = chunks;
     rec.off_lo = (uint32_t)elem;

@@ -172,7 +172,9 @@ struct Layout {
   // rs::tile_reduce()'s); resample_lds is the kernel's LDS as above.
   std::vector<rs::ItemDesc> items;
   std::vector<uint32_t> item_map;
-  bool by_items = false, items_sum = false;
+  // items_orient: some PLACED item has an orientation code (the orienting
+  // instantiation is launched; without one, the kernel as it was).
+  bool by_items = false, items_sum = false, items_orient = false;
 };
 
 // Image p at draft level lv (0..3), as libjpeg-turbo's scale (8 >> lv) / 8

@@ -167,12 +167,13 @@ int resolve(const spdl_hj_resample_item* it, int W, int H, int out_w, int out_h,
 
 namespace {
 // tile() for either kernel.  reduce: resample_reduce_kernel's -- windows
-// unaligned, the LDS with the second sums' plane
-int tile_for(bool reduce, int nch, const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h,
-             ResampleDesc* d, int* bands, int* chunks) {
+// unaligned, the LDS with the second sums' plane.  aligned: the windows start
+// on the producer's 8 x 2 units (tile()'s, not tile_oriented()'s)
+int tile_for(bool reduce, bool aligned, int nch, const Axis& H, const Axis& V, const Geo& g,
+             int out_w, int out_h, ResampleDesc* d, int* bands, int* chunks) {
   const int tile_w = nch == 1 ? kTileW1 : kTileW;
   const int sum_planes = nch == 1 ? 0 : 1;  // (planes of sums beside the strip)
-  const int ax = reduce ? 1 : 8, ay = reduce ? 1 : 2;
+  const int ax = aligned ? 8 : 1, ay = aligned ? 2 : 1;
   ResampleDesc t{};
   t.bx = g.bx;
   t.by = g.by;
@@ -234,11 +235,15 @@ int tile_for(bool reduce, int nch, const Axis& H, const Axis& V, const Geo& g, i
 
 int tile(const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h, ResampleDesc* d,
          int* bands, int* chunks, int nch) {
-  return tile_for(false, nch, H, V, g, out_w, out_h, d, bands, chunks);
+  return tile_for(false, true, nch, H, V, g, out_w, out_h, d, bands, chunks);
+}
+int tile_oriented(const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h, ResampleDesc* d,
+                  int* bands, int* chunks) {
+  return tile_for(false, false, 3, H, V, g, out_w, out_h, d, bands, chunks);
 }
 int tile_reduce(const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h, ResampleDesc* d,
                 int* bands, int* chunks, int nch) {
-  return tile_for(true, nch, H, V, g, out_w, out_h, d, bands, chunks);
+  return tile_for(true, false, nch, H, V, g, out_w, out_h, d, bands, chunks);
 }
 
 int place(AxisCache& cache, int filter, const spdl_hj_resample_item* it, int W, int H, int out_w,
@@ -392,6 +397,8 @@ int place_box_into(void* cache, int filter, double gap, const spdl_hj_resample_b
 int resolve_item(const spdl_hj_resample_items_item* it, int W, int H, int filter, double gap,
                  ItemGeo* g) {
   *g = ItemGeo{};
+  if (it->orient < 0 || it->orient > 7) return SPDL_HJ_ERR_INVALID_ARG;
+  if (it->orient & 4) std::swap(W, H);  // (the displayed frame: everything below is in it)
   if (it->flip < 0 || it->flip > 3 || it->out_w < 1 || it->out_w > 65535 || it->out_h < 1 ||
       it->out_h > 65535)
     return SPDL_HJ_ERR_INVALID_ARG;
@@ -438,10 +445,17 @@ int place_item_into(void* cache, int filter, double gap, const spdl_hj_resample_
   // (with sums the cells count from rr.qx / qy, which hold the clamped box's
   // origin; without, the producer reads the frame at the box's origin + xmin)
   const Geo g{sum ? 0 : ig.bx, sum ? 0 : ig.by, b.cw, b.ch, b.rw, b.rh, b.ox, b.oy};
-  rc = sum ? tile_reduce(*pl.H, *pl.V, g, it->out_w, it->out_h, &pl.d, &pl.bands, &pl.chunks,
-                         ac.channels)
-           : tile(*pl.H, *pl.V, g, it->out_w, it->out_h, &pl.d, &pl.bands, &pl.chunks, ac.channels);
+  if (sum)
+    rc = tile_reduce(*pl.H, *pl.V, g, it->out_w, it->out_h, &pl.d, &pl.bands, &pl.chunks,
+                     ac.channels);
+  else if (it->orient)
+    rc = tile_oriented(*pl.H, *pl.V, g, it->out_w, it->out_h, &pl.d, &pl.bands, &pl.chunks);
+  else
+    rc = tile(*pl.H, *pl.V, g, it->out_w, it->out_h, &pl.d, &pl.bands, &pl.chunks, ac.channels);
   if (rc) return rc;
+  rec->orient = it->orient;
+  rec->dw = it->orient & 4 ? H : W;
+  rec->dh = it->orient & 4 ? W : H;
   rec->rr = ReduceDesc{ig.bx + b.q[0], ig.by + b.q[1], b.q[2] - b.q[0], b.q[3] - b.q[1],
                        b.fx,           b.fy,           b.cw,            b.ch,
                        {},             {}};

@@ -132,6 +132,14 @@ int resolve_box(const spdl_hj_resample_box_item* it, int W, int H, int out_w, in
 int tile_reduce(const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h, ResampleDesc* d,
                 int* bands, int* chunks, int nch = 3);
 
+// The tiling of an item with an orientation code and no factor: tile()'s for
+// three channels, its windows unaligned as tile_reduce()'s -- the producer's
+// units are aligned to the STORED frame, which a mirror or a transpose sends
+// to no fixed alignment of the displayed one; the kernel drops what a unit
+// holds outside the window instead (rs::stored_rect)
+int tile_oriented(const Axis& H, const Axis& V, const Geo& g, int out_w, int out_h, ResampleDesc* d,
+                  int* bands, int* chunks);
+
 // place_into for a box request.  red == null: the submission has no factor
 // above 1 and the record is resample_kernel's; else resample_reduce_kernel's,
 // *red beside it.  The planner's ResampleRequest::place_box.
@@ -144,6 +152,9 @@ int probe_box(int filter, double gap, const spdl_hj_resample_box_item* it, int W
               int out_h, int* reduces);
 
 // ---- spdl_hj_set_resample_items: one item against its image's W x H frame ----
+// W x H is the STORED frame; an item with an orientation code (it->orient,
+// 0..7) is resolved against the displayed one, H x W for codes 4..7, and so
+// are its statuses.
 // resolve_box of the item's own request.  clamp = 0: as it stands.  clamp = 1:
 // the integral box (bx, by) + bw x bh is a frame of its own, the request its
 // whole frame: q, cw x ch and the box are relative to (bx, by).
@@ -152,7 +163,7 @@ struct ItemGeo {
   int bx, by;
 };
 // 0; SPDL_HJ_ERR_INVALID_ARG (the submission's): what resolve_box gives it for,
-// a flip outside 0..3, an output box outside 1..65535, a clamped box that is
+// a flip outside 0..3, an orientation outside 0..7, an output box outside 1..65535, a clamped box that is
 // not integral; SPDL_HJ_ERR_BAD_GEOMETRY (the item's): what resolve_box gives
 // it for, a clamped box that is empty or outside the frame
 int resolve_item(const spdl_hj_resample_items_item* it, int W, int H, int filter, double gap,
@@ -162,7 +173,8 @@ int probe_item(int filter, double gap, const spdl_hj_resample_items_item* it, in
                int* reduces);
 // ... and its record for resample_items_kernel, tables placed once per
 // submission.  sum: some item of the submission has a factor above 1 -- every
-// record is then tile_reduce()'s with rec->rr set, else tile()'s.
+// record is then tile_reduce()'s with rec->rr set, else tile()'s, or
+// tile_oriented()'s for an item with a code.
 // (ResampleRequest::place_item; the image, the flip, the offset and the tiles'
 // place in the grid are the planner's to fill.)
 int place_item_into(void* cache, int filter, double gap, const spdl_hj_resample_items_item* it,

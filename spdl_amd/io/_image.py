@@ -16,7 +16,7 @@ import os
 import warnings
 from collections.abc import Mapping, Sequence
 from types import SimpleNamespace
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 
 import numpy as np
 import torch
@@ -364,6 +364,48 @@ def _check_luma(pix_fmt, csc: str, resample=None) -> None:
         return
     if csc != "turbo":
         raise ValueError(f"pix_fmt 'L' / 'Y' needs csc='turbo', not {csc!r}")
+    if getattr(resample, "oriented", False):
+        raise ValueError("pix_fmt 'L' / 'Y' takes no exif_transpose= / orients=: an oriented "
+                         "item has three channels")
+
+
+def _held_orients(exif_transpose, orients):
+    """``exif_transpose=`` / ``orients=`` of :func:`pil_resize` and
+    :func:`pil_thumbnail`, held: one code or a tuple of them, or ``None``."""
+    if orients is None:
+        return None
+    if exif_transpose:
+        raise ValueError("exif_transpose= and orients= are exclusive")
+    if isinstance(orients, (list, tuple)):
+        return tuple(_lib._orient(o) for o in orients)
+    return _lib._orient(orients)
+
+
+def _orient_codes(resample, datas, keep):
+    """One orientation code per kept file for an oriented ``resample=``: the
+    file's own EXIF tag, or the request's codes; ``None`` without either."""
+    if not getattr(resample, "oriented", False):
+        return None
+    if resample.exif_transpose:
+        return [_lib.exif_code(_lib.get_orientation(d)) for d in datas]
+    if isinstance(resample.orients, tuple):
+        return [resample.orients[i] for i in keep]
+    return [resample.orients] * len(datas)
+
+
+def _request_repr(self) -> str:
+    """``repr`` of a :class:`PilResize` / :class:`PilThumbnail`: the dataclass's
+    own, with ``exif_transpose`` / ``orients`` shown only where one is set -- an
+    unoriented request prints as it did before the two existed (logs, and the
+    ids pytest makes of parameters, hold that text)."""
+    names = [f.name for f in fields(self)
+             if self.oriented or f.name not in ("exif_transpose", "orients")]
+    return f"{type(self).__name__}({', '.join(f'{n}={getattr(self, n)!r}' for n in names)})"
+
+
+def _displayed(size, code):
+    """``(w, h)`` as orientation ``code`` shows it"""
+    return (size[1], size[0]) if code & 4 else tuple(size)
 
 
 @dataclass(frozen=True)
@@ -376,6 +418,16 @@ class PilResize:
     shorter: int | None = None
     resize_boxes: tuple | None = None
     reducing_gap: float | None = None
+    exif_transpose: bool = False
+    orients: tuple | int | None = None
+
+    @property
+    def oriented(self) -> bool:
+        """``exif_transpose=`` or ``orients=``: every size below is the
+        displayed frame's, and the request is submitted as resample items"""
+        return self.exif_transpose or self.orients is not None
+
+    __repr__ = _request_repr
 
     @property
     def by_box(self) -> bool:
@@ -405,7 +457,7 @@ class PilResize:
 
 
 def pil_resize(size=None, filter: str = "bilinear", boxes=None, shorter=None, resize_boxes=None,
-               reducing_gap=None) -> PilResize:
+               reducing_gap=None, exif_transpose: bool = False, orients=None) -> PilResize:
     """Pillow's ``Image.resize`` on the GPU, for ``csc="turbo"``: the output is
     ``np.asarray(Image.open(f).convert("RGB").crop(box).resize(size, filter))``
     byte for byte (include/spdl_hipjpeg.h "Pillow-exact resize").  ``size=(w,
@@ -422,7 +474,15 @@ def pil_resize(size=None, filter: str = "bilinear", boxes=None, shorter=None, re
     ``resize_boxes`` is exclusive with ``boxes`` and ``shorter``;
     ``reducing_gap`` alone takes the whole frame.  ``size=None`` with
     ``shorter``: ``Resize(shorter)`` alone, every file at its own size --
-    :func:`load_image_list`'s, which writes one size per file."""
+    :func:`load_image_list`'s, which writes one size per file.
+    ``exif_transpose=True`` is ``ImageOps.exif_transpose(Image.open(f))`` ahead
+    of all that, from each file's own EXIF tag; ``orients`` (exclusive with it)
+    one orientation code ``0..7`` for all files or one per file, ``Image
+    .transpose`` of the decoded frame (include/spdl_hipjpeg.h "Pillow-exact
+    orientation").  Boxes, ``shorter`` and ``draft="auto"`` then see the
+    DISPLAYED frame; an explicit ``draft=`` is ``im.draft()`` ahead of the
+    transpose.  No ``pix_fmt`` ``"L"`` / ``"Y"`` with either."""
+    orients = _held_orients(exif_transpose, orients)
     if size is None:
         if shorter is None or resize_boxes is not None or reducing_gap is not None:
             raise ValueError("pil_resize() without a size needs shorter= and nothing of box=")
@@ -452,7 +512,8 @@ def pil_resize(size=None, filter: str = "bilinear", boxes=None, shorter=None, re
             raise ValueError("a box is (x, y, w, h) or None")
     return PilResize((int(size[0]), int(size[1])) if keep_size else None, filter, boxes,
                      None if shorter is None else int(shorter), resize_boxes,
-                     None if reducing_gap is None else float(reducing_gap))
+                     None if reducing_gap is None else float(reducing_gap), bool(exif_transpose),
+                     orients)
 
 
 @dataclass(frozen=True)
@@ -462,12 +523,23 @@ class PilThumbnail:
     size: tuple
     filter: str = "bicubic"
     reducing_gap: float | None = 2.0
+    exif_transpose: bool = False
+    orients: tuple | int | None = None
+
+    @property
+    def oriented(self) -> bool:
+        return self.exif_transpose or self.orients is not None
+
+    __repr__ = _request_repr
 
     def plan(self, width: int, height: int):
         """``Image.thumbnail`` of a ``width x height`` file, restated: ``(level,
         final_size, box)`` -- the draft level, the thumbnail's size, and
         ``resize``'s float box in the draft frame (``None``: the frame is the
-        result as it is)."""
+        result as it is).  An oriented request: ``width x height`` the
+        DISPLAYED frame, and no draft -- ``exif_transpose``'s result is no JPEG
+        file any more, so ``thumbnail`` asks for none and the gap works on the
+        full frame."""
         x, y = self.size
         if x >= width and y >= height:
             return 0, (width, height), None
@@ -481,7 +553,7 @@ class PilThumbnail:
         else:
             y = round_aspect(x / aspect, key=lambda n: 0 if n == 0 else abs(aspect - x / n))
         level, box = 0, (0.0, 0.0, float(width), float(height))
-        if self.reducing_gap is not None:
+        if self.reducing_gap is not None and not self.oriented:
             g = self.reducing_gap
             level = _lib.draft_level(width, height, int(self.size[0] * g), int(self.size[1] * g))
             box = (0.0, 0.0, width / (1 << level), height / (1 << level))
@@ -490,13 +562,18 @@ class PilThumbnail:
         return level, (x, y), box
 
 
-def pil_thumbnail(size, filter: str = "bicubic", reducing_gap=2.0) -> PilThumbnail:
+def pil_thumbnail(size, filter: str = "bicubic", reducing_gap=2.0, exif_transpose: bool = False,
+                  orients=None) -> PilThumbnail:
     """Pillow's ``Image.thumbnail(size, filter, reducing_gap)`` on the GPU, for
     ``csc="turbo"``: the draft decode, ``Image.reduce`` and the float-box resize
     in its order, byte for byte (include/spdl_hipjpeg.h "Pillow-exact
     thumbnail").  Accepted wherever ``resample=`` is, without ``draft=``: the
     level is resolved per file.  ``load_image`` returns the file's own final
-    size; ``load_image_batch`` needs every file to resolve to one."""
+    size; ``load_image_batch`` needs every file to resolve to one.
+    ``exif_transpose`` / ``orients`` as :func:`pil_resize`'s: ``im =
+    ImageOps.exif_transpose(Image.open(f)); im.thumbnail(size, filter,
+    reducing_gap)`` -- the displayed frame's thumbnail, without a draft."""
+    orients = _held_orients(exif_transpose, orients)
     size = tuple(math.floor(v) for v in size)
     if len(size) != 2 or any(not 1 <= v <= 65535 for v in size):
         raise ValueError(f"size is (width, height), each 1..65535, not {size!r}")
@@ -504,7 +581,8 @@ def pil_thumbnail(size, filter: str = "bicubic", reducing_gap=2.0) -> PilThumbna
         raise ValueError(f"filter must be one of {sorted(_lib.FILTERS)}, not {filter!r}")
     if reducing_gap is not None and not float(reducing_gap) >= 1.0:
         raise ValueError(f"reducing_gap is at least 1.0 or None, not {reducing_gap!r}")
-    return PilThumbnail(size, filter, None if reducing_gap is None else float(reducing_gap))
+    return PilThumbnail(size, filter, None if reducing_gap is None else float(reducing_gap),
+                        bool(exif_transpose), orients)
 
 
 def _thumbnail_of(thumb: PilThumbnail, infos):
@@ -537,6 +615,8 @@ def _check_resample(resample, csc, n_src, filter_desc, pix_fmt, ragged: bool = F
     for boxes in (getattr(resample, "boxes", None), getattr(resample, "resize_boxes", None)):
         if boxes is not None and len(boxes) != n_src:
             raise ValueError(f"{len(boxes)} boxes for {n_src} images")
+    if isinstance(resample.orients, tuple) and len(resample.orients) != n_src:
+        raise ValueError(f"{len(resample.orients)} orients for {n_src} images")
     if filter_desc is not None and filter_desc != _FILTER_DESC_DEFAULT:
         _with_csc(parse_image_filter(filter_desc, default_pix_fmt=pix_fmt), csc)
 
@@ -560,27 +640,31 @@ class _ResampleNeedsTurbo(TypeError, ValueError):
     like every other one here.  It stays both."""
 
 
-def _item_requests(resample, infos, keep, dlevels, flips):
+def _item_requests(resample, infos, keep, dlevels, flips, codes=None):
     """``resample=`` of :func:`load_image_list` as one item per kept image:
     ``(levels, requests, gap)`` for :func:`spdl_amd._lib.resample_layout` -- a
     thumbnail's own size and draft level per file, ``pil_resize(shorter=)``'s
-    aspect-preserving size, or ``pil_resize(size)``'s one size for all."""
+    aspect-preserving size, or ``pil_resize(size)``'s one size for all.
+    ``codes``: an oriented request's code per image, whose frame is then the
+    displayed one."""
     flips = flips or [0] * len(infos)
+    codes = codes or [0] * len(infos)
     if isinstance(resample, PilThumbnail):
-        plans = [resample.plan(i.width, i.height) for i in infos]
+        plans = [resample.plan(*_displayed((i.width, i.height), c)) for i, c in zip(infos, codes)]
         levels = [p[0] for p in plans]
-        reqs = [(k, p[2], False, p[1], None, flips[k]) for k, p in enumerate(plans)]
+        reqs = [(k, p[2], False, p[1], None, flips[k], codes[k]) for k, p in enumerate(plans)]
         gap = resample.reducing_gap if any(p[2] is not None for p in plans) else None
         return (levels if any(levels) else None), reqs, gap
     boxes = resample.resize_boxes if resample.by_box else resample.boxes
     reqs = []
     for k, (info, lv) in enumerate(zip(infos, dlevels or [0] * len(infos))):
         w, h = _lib.draft_size(info.width, info.height, lv) if lv else (info.width, info.height)
+        w, h = _displayed((w, h), codes[k])
         box, rsz, (ox, oy) = resample.geometry(w, h, None if boxes is None else boxes[keep[k]])
         if box is not None and not resample.by_box:  # (a crop (x, y, w, h): Pillow's corners)
             box = (box[0], box[1], box[0] + box[2], box[1] + box[3])
         window = None if resample.size is None else (ox, oy, *resample.size)
-        reqs.append((k, box, not resample.by_box, rsz, window, flips[k]))
+        reqs.append((k, box, not resample.by_box, rsz, window, flips[k], codes[k]))
     return dlevels, reqs, resample.reducing_gap
 
 
@@ -598,6 +682,8 @@ def _views_turbo(srcs, groups, cfg, strict: bool):
         if not isinstance(rs, PilResize) or rs.size is None or rs.boxes or rs.resize_boxes:
             raise ValueError("a group's resample= is pil_resize((w, h), filter): its boxes are "
                              "the group's boxes= / resize_boxes=")
+        if rs.oriented:
+            raise ValueError("a csc='turbo' group takes no exif_transpose= / orients=")
         if (g.get("boxes") is None) == (g.get("resize_boxes") is None):
             raise ValueError("a group needs boxes= or resize_boxes=: a list of boxes per image")
         per = g.get("boxes") if g.get("boxes") is not None else g["resize_boxes"]
@@ -718,7 +804,7 @@ def _check_draft(draft, csc, resample, n_src) -> None:
         _lib.draft_levels(draft, [SimpleNamespace(width=1, height=1)] * n_src)
 
 
-def _draft_levels(draft, infos, keep, resample):
+def _draft_levels(draft, infos, keep, resample, codes=None):
     """One level per kept image (``None``: all zero).  ``"auto"``: the largest
     level whose frame covers ``resample``'s output -- both sides of ``size``,
     and with ``shorter`` its shorter side that."""
@@ -730,7 +816,27 @@ def _draft_levels(draft, infos, keep, resample):
     if isinstance(draft, str):
         need = max(resample.shorter or 0, min(resample.size))
         sizes = [tuple(max(v, need) for v in resample.size)] * len(infos)
+        if codes:  # (the size to cover is the displayed frame's: the stored one's, turned back)
+            sizes = [_displayed(sz, c) for sz, c in zip(sizes, codes)]
     return _lib.draft_levels(draft, infos, sizes)
+
+
+def _oriented_batch(srcs, resample, cfg, to_host: bool, storage=None, **kwargs):
+    """An oriented ``resample=`` of :func:`load_image_batch` and
+    :func:`load_image`: the request as resample items, which is
+    :func:`load_image_list`'s submission, and its outputs as one ``[B, ...]``
+    -- ``ValueError`` naming the sizes when the files' displayed frames do not
+    resolve to one."""
+    from ._convert import to_torch
+
+    bufs, _ = load_image_list(srcs, device_config=cfg, csc="turbo", resample=resample, **kwargs)
+    ts = [to_torch(b) for b in bufs]
+    sizes = sorted({tuple(t.shape) for t in ts})
+    if len(sizes) != 1:
+        raise ValueError(f"the files resolve to different sizes {sizes}; one [B,H,W,3] holds one "
+                         "size: load_image_list returns every file at its own")
+    buf = CUDABuffer(torch.stack(ts), stream=cfg.stream)
+    return _to_host(buf, storage) if to_host else buf
 
 
 def _csc_pix_fmt(filter_desc, pix_fmt):
@@ -857,6 +963,11 @@ def load_image_batch(
             scale_width=width, scale_height=height, pix_fmt=pix_fmt
         )
     cfg = device_config or _default_config()
+    if getattr(resample, "oriented", False):
+        return _oriented_batch(srcs, resample, cfg, device_config is None, storage,
+                               filter_desc=filter_desc, pix_fmt=pix_fmt, strict=strict,
+                               normalize=normalize, mean=mean, std=std, norm_dtype=norm_dtype,
+                               draft=draft)
     if crops is not None:
         crops = list(crops)
         if len(crops) != len(srcs):
@@ -1321,11 +1432,12 @@ def load_image_list(
         lowres = [per_lowres[i] for i in keep]
     levels = _lib.lowres_levels(lowres, infos, out, codes)
     _no_crops_with_lowres(levels, crops, out)
-    dlevels = _draft_levels(draft, infos, keep, resample)
+    ocodes = _orient_codes(resample, datas, keep)
+    dlevels = _draft_levels(draft, infos, keep, resample, ocodes)
     esz = 1 if out.torch_dtype == torch.uint8 else 2
     items = None
     if resample is not None:  # (one item per image: its own size, its flip in the store)
-        dlevels, reqs, gap = _item_requests(resample, infos, keep, dlevels, codes)
+        dlevels, reqs, gap = _item_requests(resample, infos, keep, dlevels, codes, ocodes)
         offsets, sizes, planned, items = _lib.resample_layout(
             infos, reqs, align, filter=resample.filter, reducing_gap=gap, elem_size=esz,
             draft=dlevels, channels=out.channels)
@@ -1448,6 +1560,13 @@ def load_image(
     if resample is not None and filter_desc is None:
         raise ValueError("resample= needs an RGB pix_fmt: it converts to RGB")
     cfg = device_config or _default_config()
+    if getattr(resample, "oriented", False):
+        from ._convert import to_torch
+
+        buf = _oriented_batch([src], resample, cfg, False, filter_desc=filter_desc, pix_fmt=pix_fmt,
+                              draft=draft)
+        buf = CUDABuffer(to_torch(buf)[0], stream=cfg.stream)
+        return _to_host(buf) if device_config is None else buf
     data = _read(src)
     flip = _lib._flip(flip)
     if filter_desc is None:
