@@ -1158,7 +1158,12 @@ const char* spdl_hj_stage_name(int32_t i);
  * cross-stream event waits stream order already implies -- a workspace's
  * previous batch on the same stream, a caller stream with nothing pending;
  * 0 = always wait), "xcd_order" (ABI 6: XCD-aware tile order, bit 0 the
- * swscale kernel, bit 1 the IDCT kernel; default 1; byte-identical outputs).
+ * swscale kernel, bit 1 the IDCT kernel; default 1; byte-identical outputs),
+ * "destuff_fused_bytes" (a batch whose every file is at most this many bytes
+ * is destuffed in one launch, one workgroup walking each image's scan once;
+ * any larger file sends the whole batch through the count, prefix and write
+ * kernels, which spread an image over a workgroup per 4 KB; default 262144,
+ * 0 = always the three kernels; byte-identical outputs).
  * A/B knobs, byte-identical outputs: "entropy_prio" (0-3, s_setprio of the
  * entropy waves; default 0), "parse_threads" (64/128/256; default 64),
  * "sws_cols" (16-256 output columns per swscale workgroup; default 256),
@@ -1166,8 +1171,9 @@ const char* spdl_hj_stage_name(int32_t i);
  * "ms_skip_empty" (1: skip the multi-scan launch of a batch known to hold
  * no multi-scan image; default 0), "host_staging" (1, the default: kernels
  * move descriptors / statuses through mapped pinned memory; 0: DMA copies).
- * Read-only (spdl_hj_get_param): "handoff_retries", images re-decoded after a
- * hand-off gave up, since the context was created; "streams", the HIP
+ * Read-only (spdl_hj_get_param): "destuff_fused", 1 when the last submission
+ * was destuffed in one launch ("destuff_fused_bytes"); "handoff_retries",
+ * images re-decoded after a hand-off gave up, since the context was created; "streams", the HIP
  * streams a batch holding a progressive image may use (one per lane, a
  * multi-scan side stream per lane when the hardware queues allow, the copy
  * stream); "idct_workgroups" (with the source crop), the IDCT workgroups the last submission

@@ -270,6 +270,11 @@ struct spdl_hj_ctx {
   // skip the multi-scan launch of a batch known to hold no multi-scan image
   // (A/B knob; r05: 1 % slower, the empty launch staggered the lanes)
   int ms_skip_empty = 0;
+  // destuff in one launch (destuff_image_kernel, one workgroup per image) when
+  // every file of the batch is at most this many bytes; 0 = always the count /
+  // prefix / write kernels, which spread a large image over many workgroups
+  // (the default is an estimate, not a measured crossover: profiles/r27/destuff_fused/)
+  int64_t destuff_fused_bytes = 262144;
   // XCD-aware tile order (bit 0 sws_kernel, bit 1 idct_kernel): each XCD
   // takes a contiguous range of tiles, so neighbouring bands of an image
   // share their overlapping source rows in one L2 (r06 A/B: mixed 4 lanes
@@ -299,6 +304,7 @@ struct spdl_hj_ctx {
   // ... the fused-eligible images' idct_rgb_kernel workgroups, and those of
   // the generic output kernel (sws_kernel)
   int64_t fused_workgroups = 0, generic_workgroups = 0;
+  int64_t destuff_fused = 0;  // the last submission destuffed in one launch
   int64_t turbo_workgroups = 0;  // turbo_rgb_kernel's in the last submission (csc = TURBO)
   int64_t resample_workgroups = 0;  // resample_kernel's (spdl_hj_set_resample)
   int64_t reduce_images = 0;  // images with a reduce factor above 1 (spdl_hj_set_resample_box)
@@ -725,7 +731,12 @@ int run_pipeline(spdl_hj_ctx* ctx, Slot& slot, const Layout& L, const Submission
       (void)hipEventRecord(w->done, st);
     }
   } side_join{st, ms_side ? &W : nullptr};
-  HJ_HIP(launch_destuff(B, ds_flat, (int)L.ds_wgs, L.max_chunks, st));
+  // (file sizes: the host knows them before parse_kernel finds the scans)
+  int64_t ds_largest = 0;
+  for (int i = 0; i < n; i++) ds_largest = std::max<int64_t>(ds_largest, L.desc[i].in_size);
+  const bool ds_fused = ctx->destuff_fused_bytes > 0 && ds_largest <= ctx->destuff_fused_bytes;
+  ctx->destuff_fused = ds_fused;
+  HJ_HIP(launch_destuff(B, ds_flat, (int)L.ds_wgs, L.max_chunks, ds_fused, st));
   mark(ctx, slot, 3, st);
   int ent_threads;
   const EntropyParams ep = entropy_schedule(ctx, &ent_threads);
@@ -2058,6 +2069,11 @@ int spdl_hj_set_param(spdl_hj_ctx* ctx, const char* name, int64_t value) {
     ctx->ms_skip_empty = value != 0;
     return SPDL_HJ_OK;
   }
+  if (!strcmp(name, "destuff_fused_bytes")) {  // 0: always count / prefix / write
+    if (value < 0 || value > (1 << 30)) return SPDL_HJ_ERR_INVALID_ARG;
+    ctx->destuff_fused_bytes = value;
+    return SPDL_HJ_OK;
+  }
   if (!strcmp(name, "xcd_order")) {
     if (value < 0 || value > 3) return SPDL_HJ_ERR_INVALID_ARG;
     ctx->xcd_order = (int)value;
@@ -2123,6 +2139,8 @@ int spdl_hj_get_param(spdl_hj_ctx* ctx, const char* name, int64_t* value) {
       {"lean_waits", ctx->lean_waits},
       {"ms_skip_empty", ctx->ms_skip_empty},
       {"xcd_order", ctx->xcd_order},
+      {"destuff_fused_bytes", ctx->destuff_fused_bytes},
+      {"destuff_fused", ctx->destuff_fused},
       {"handoff_retries", ctx->handoff_retries},
       {"idct_workgroups", ctx->idct_workgroups},
       {"lowres_images", ctx->lowres_images},

@@ -27,6 +27,7 @@
 
 #include "hj_common.h"
 #include "hj_destuff.h"
+#include "hj_destuff_tile.h"
 #include "hj_idct.h"
 #include "hj_launch.h"
 #include "hj_sws_tile.h"
@@ -722,6 +723,7 @@ constexpr int kDsStageWords = (16 + 16 + kDsChunk + 32) / 4;
 
 // Copy the `n` staged bytes to `dst` (staged from byte 16 + (dst & 15) on):
 // head bytes singly, 16-byte LDS loads and global stores, tail bytes singly.
+template <int NT = kDsThreads>
 __device__ __forceinline__ void stage_to_global(uint8_t* __restrict__ dst, const uint32_t* stage,
                                                 int n, int tid) {
   const int a = (int)((uintptr_t)dst & 15);
@@ -731,7 +733,7 @@ __device__ __forceinline__ void stage_to_global(uint8_t* __restrict__ dst, const
   const int nv = (n - head) >> 4;
   const uint4* s4 = reinterpret_cast<const uint4*>(src + head);
   uint4* d4 = reinterpret_cast<uint4*>(dst + head);
-  for (int i = tid; i < nv; i += kDsThreads) d4[i] = s4[i];
+  for (int i = tid; i < nv; i += NT) d4[i] = s4[i];
   const int t0 = head + 16 * nv;
   if (t0 + tid < n) dst[t0 + tid] = src[t0 + tid];
 }
@@ -892,6 +894,161 @@ __global__ void __launch_bounds__(kDsThreads) destuff_write_kernel(
       infos[img].nseg = min(c.rst_pre + tr + 1, dd.seg_cap);
       sg[0] = 0;
     }
+  }
+}
+
+// The same in one launch for a batch of small images (hj_destuff_tile.h): one
+// workgroup walks one image's scan in tiles of NT groups, reads and classifies
+// every byte once and keeps the running output offset in a register, so no
+// chunk counts, no prefix and no second read.  What it writes -- the clean
+// bytes, the zero padding, the segment starts and ImageInfo's scan_end,
+// clean_len, nseg -- is what the three kernels write.
+//
+// Per tile two barriers: A after the wave totals and the tile's terminator
+// are in LDS, B after the groups are OR-ed into the stage.  The stage is
+// double-buffered: tile t's is zeroed again between A and B of tile t + 1
+// (every thread has left tile t's copy-out by then) and used next after A of
+// tile t + 2.  The loads of tile t + 1 are issued before tile t is classified.
+constexpr int kDsImageThreads = 512;  // the workgroup launch_destuff runs (tiles of 8 KB)
+
+template <int NT>
+struct DsImageShared {
+  static constexpr int kStageWords = (16 + 16 + 16 * NT + 32) / 4;
+  int wsum[NT / 64];
+  int term;
+  __attribute__((aligned(16))) uint32_t stage[2][kStageWords];
+};
+
+// A thread's group of a tile: the 16 bytes as ds_load reads them; the byte
+// before is loaded by a wave's first lane and the byte after by its last
+// alone -- the lanes between take theirs from their neighbours' words.
+__device__ __forceinline__ void ds_tile_load(const uint8_t* __restrict__ d, int size, int j0,
+                                             int lane, uint32_t (&w)[4], uint32_t& prev,
+                                             uint32_t& next) {
+  prev = lane == 0 ? ds_prev_byte(d, size, j0) : 0u;
+  if (j0 + 16 <= size) {
+    const uint4 q = *reinterpret_cast<const uint4*>(d + j0);
+    w[0] = q.x;
+    w[1] = q.y;
+    w[2] = q.z;
+    w[3] = q.w;
+  } else {
+    ds_load_bytes(d, size, j0, w);
+  }
+  next = lane == 63 ? ds_next_byte(d, size, j0) : 0u;
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT) destuff_image_kernel(
+    const uint8_t* __restrict__ bytes, const ImageDesc* __restrict__ desc,
+    ImageInfo* __restrict__ infos, uint8_t* __restrict__ clean, uint32_t* __restrict__ segs) {
+  constexpr int kTile = 16 * NT, kWaves = NT / 64;
+  using Sh = DsImageShared<NT>;
+  __shared__ Sh S;
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (infos[img].status != kOk || infos[img].multiscan) return;
+  const ImageDesc& dd = desc[img];
+  const int size = (int)dd.in_size, start = infos[img].scan_start;
+  const int base = start & ~15;
+  const uint8_t* d = bytes + dd.in_off;
+  uint8_t* out0 = clean + dd.in_off;
+  uint32_t* sg = segs + dd.seg_off;
+  static_assert(Sh::kStageWords % 4 == 0, "the stage is zeroed 16 bytes at a time");
+  for (int i = tid; i < 2 * Sh::kStageWords / 4; i += NT)
+    reinterpret_cast<uint4*>(&S.stage[0][0])[i] = make_uint4(0, 0, 0, 0);
+  if (tid == 0) S.term = kDsNoTerm;
+  __syncthreads();
+  int run_keep = 0, run_rst = 0, end = kDsNoTerm;
+  int j0 = base + tid * 16;
+  uint32_t w[4], prev, next;
+  ds_tile_load(d, size, j0, lane, w, prev, next);
+  for (int t = 0;; t++) {
+    // the next tile's loads first: they are in flight through this tile's
+    // scan and stores (size - tb: tb + kTile may pass 2^31)
+    const bool more = size - (base + t * kTile) > kTile;
+    uint32_t nw[4] = {0, 0, 0, 0}, nprev = 0, nnext = 0;
+    if (more) ds_tile_load(d, size, j0 + kTile, lane, nw, nprev, nnext);
+    // the carries: the neighbour lane's last / first byte
+    const uint32_t up = (uint32_t)__shfl_up((int)(w[3] >> 24), 1, 64);
+    const uint32_t dn = (uint32_t)__shfl_down((int)(w[0] & 0xFFu), 1, 64);
+    const DsStep s = ds_tile_step(w, lane == 0 ? prev : up, lane == 63 ? next : dn, j0, start, size);
+    uint32_t keep = s.keep, rst = 0;
+    if (s.slow) {  // a marker: rare, at most one per image besides RSTn
+      int term;
+      ds_resolve(d, size, j0, s.slow, rst, term);
+      if (term != kDsNoTerm) atomicMin(&S.term, term);
+    }
+    // rst << 16 | keep: at most 8 NT and 16 NT per tile
+    int v = (int)(__popc(rst) << 16) | s.kept;
+    int iv = wave_incl_scan_dpp(v);
+    if (lane == 63) S.wsum[wid] = iv;
+    __syncthreads();  // A
+    end = S.term;
+    if (end != kDsNoTerm) {
+      // the scan ends in this tile (once per image): cut the masks there and
+      // scan again
+      keep = ds_tile_cut(keep, j0, end);
+      rst = ds_tile_cut(rst, j0, end);
+      v = (int)(__popc(rst) << 16 | __popc(keep));
+      __syncthreads();  // every thread has read S.term and is past its S.wsum store
+      iv = wave_incl_scan_dpp(v);
+      if (lane == 63) S.wsum[wid] = iv;
+      __syncthreads();
+    }
+    int ex = iv - v, tot = 0;
+#pragma unroll
+    for (int q = 0; q < kWaves; q++) {
+      const int ws = S.wsum[q];
+      if (q < wid) ex += ws;
+      tot += ws;
+    }
+    const int ek = ex & 0xFFFF, er = ex >> 16, tk = tot & 0xFFFF, tr = tot >> 16;
+    // the other stage, for the next tile
+    uint32_t* other = S.stage[(t + 1) & 1];
+    if (t > 0)
+      for (int i = tid; i < Sh::kStageWords / 4; i += NT)
+        reinterpret_cast<uint4*>(other)[i] = make_uint4(0, 0, 0, 0);
+    if (rst) {  // RSTn markers record segment starts
+      int r = run_rst + er;
+      bool overflow = false;
+      for (uint32_t q = rst; q; q &= q - 1) {
+        const int i = ds_ctz(q);
+        r++;
+        if (r < dd.seg_cap) sg[r] = (uint32_t)(run_keep + ek + __popc(keep & ((1u << i) - 1u)));
+        else overflow = true;
+      }
+      if (overflow) infos[img].status = kErrBadRestart;
+    }
+    uint8_t* out = out0 + run_keep;
+    uint32_t* stage = S.stage[t & 1];
+    uint32_t drop;
+    ds_compact_begin(w, keep, drop);
+    while (__any(drop != 0u)) ds_compact_step(w, drop);
+    if (keep) {
+      const int p = 16 + (int)((uintptr_t)out & 15) + ek - ds_ctz(keep);
+      uint32_t x[5];
+      ds_shift_words(w, (uint32_t)(p & 3), x);
+      uint32_t* q = stage + (p >> 2);
+#pragma unroll
+      for (int i = 0; i < 5; i++) atomicOr(q + i, x[i]);
+    }
+    __syncthreads();  // B
+    stage_to_global<NT>(out, stage, tk, tid);
+    run_keep += tk;
+    run_rst += tr;
+    if (end != kDsNoTerm || !more) break;
+#pragma unroll
+    for (int i = 0; i < 4; i++) w[i] = nw[i];
+    prev = nprev;
+    next = nnext;
+    j0 += kTile;
+  }
+  if (tid < 64) out0[run_keep + tid] = 0;  // zero padding past the data
+  if (tid == 0) {
+    infos[img].scan_end = min(end, size);
+    infos[img].clean_len = run_keep;
+    infos[img].nseg = min(run_rst + 1, dd.seg_cap);
+    sg[0] = 0;
   }
 }
 
@@ -8249,7 +8406,13 @@ hipError_t launch_parse(const BatchBuffers& b, const ImageDesc* host_desc, const
   return hipGetLastError();
 }
 hipError_t launch_destuff(const BatchBuffers& b, bool flat, int ds_wgs, int max_chunks,
-                          hipStream_t st) {
+                          bool fused, hipStream_t st) {
+  if (fused) {
+    // (1024 threads: faster alone, 2.7x slower at four lanes -- profiles/r27/destuff_fused/)
+    hipLaunchKernelGGL(destuff_image_kernel<kDsImageThreads>, dim3(b.n), dim3(kDsImageThreads), 0,
+                       st, b.bytes, b.desc, b.infos, b.clean, b.segs);
+    return hipGetLastError();
+  }
   // not flat: the (max chunks, image) grid of a batch of similar sizes
   const dim3 grid = flat ? dim3(ds_wgs) : dim3(max_chunks, b.n);
   const uint32_t* map = flat ? b.ds_map : nullptr;

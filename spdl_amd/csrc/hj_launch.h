@@ -65,8 +65,10 @@ struct BatchBuffers {
 // copies brought them ("host_staging" 0).
 hipError_t launch_parse(const BatchBuffers& b, const ImageDesc* host_desc, const void* host_tables,
                         int64_t table_bytes, int threads, hipStream_t st);
+// fused: destuff_image_kernel, one workgroup per image; else the count, prefix and write
+// kernels over 4 KB chunks
 hipError_t launch_destuff(const BatchBuffers& b, bool flat, int ds_wgs, int max_chunks,
-                          hipStream_t st);
+                          bool fused, hipStream_t st);
 hipError_t launch_entropy(const BatchBuffers& b, const EntropyParams& ep, int threads, int lds_pad,
                           hipStream_t st);
 hipError_t launch_multiscan(const BatchBuffers& b, hipStream_t st);
